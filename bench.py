@@ -17,6 +17,10 @@ streams are independent units, so ranks shard captures with no data-path
 collective ("scaling": "weak": per-GPU work is fixed); the only collective is
 the RCCL broadcast of the shared taps from rank 0 at set-up.
 
+A plain run sets up, ramps the clock, warms up, times --steps steps, writes
+their outputs if --dump-outputs is given, and prints the line.  --full adds the
+other engines on the same step, the CPU baselines and the full-chain batch.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -34,6 +38,8 @@ import grhip_loader  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 FP32_VALU_PEAK_TFLOPS = 157.3  # spec, vector fp32
+DUMP_MAX_BYTES = 60 * 10**6    # --dump-outputs: payload bound (the files stay under 64 MB)
+DUMP_SEED = 0x444D5200
 
 
 def parse():
@@ -47,6 +53,15 @@ def parse():
                          "shader clock of an idle MI355X takes tens of ms of load to reach its steady state "
                          "(the same step measures 0.72 ms in the first 10 ms and 0.59 ms later)")
     ap.add_argument("--samples", type=int, default=10_000_000, help="complex samples per capture")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the same step on the vector-FMA, reference-tap and "
+                         "bit-exact engines, the CPU baselines and the full-chain batch (the last two trimmed by "
+                         "--no-cpu-baseline / --chain-captures)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (rank 0) as DIR/<name>.npy: "
+                         "demod_out.npy, float32, the demodulator output of every capture (captures x outputs), or a "
+                         "fixed seeded sample of its columns (and rows) when the whole would exceed %d MB"
+                         % (DUMP_MAX_BYTES // 10**6))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--per-capture-launch", action="store_true",
                     help="one work_device() call per capture (block API) instead of one batched launch")
@@ -54,7 +69,7 @@ def parse():
     ap.add_argument("--engine", choices=["fast", "fast_valu"], default="fast",
                     help="fast: GRHIP_MODE_FAST (matrix-core FIR engine); fast_valu: f32 vector FMAs only")
     ap.add_argument("--chain-captures", type=int, default=2048,
-                    help="captures of the full-chain (configs[3]) measurement that rides in the line at N=1 (0: skip); "
+                    help="captures of the full-chain (configs[3]) measurement that --full adds to the line at N=1 (0: skip); "
                          "reduced automatically to what fits the device")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU-only self-test of the N-rank launch path (gloo, a stub step that touches no GPU): "
@@ -157,7 +172,11 @@ def launcher_selftest(a):
 
 def synth_captures(torch, wl, n_caps, n_samples, first_stream_id, device):
     """4FSK captures synthesised on the device with torch (workload generation is
-    not on the measured path).  Same modulation as workload.fsk4_capture."""
+    not on the measured path).  Same modulation as workload.fsk4_capture.
+    Deterministic: the same arguments give the same bits on every run.  A
+    floating-point torch.cumsum on the device is not (its scan may add in a
+    different order each time), so the phase is the exact int64 running sum of
+    the instantaneous frequencies, which are whole numbers of Hz, scaled once."""
     c = wl.CFG2
     sps = int(round(c["fs"] / c["sym_rate"]))
     n_syms = (n_samples + sps - 1) // sps + 1
@@ -166,9 +185,11 @@ def synth_captures(torch, wl, n_caps, n_samples, first_stream_id, device):
     sigma = math.sqrt(n0 / 2.0)
     for k in range(n_caps):
         sid = first_stream_id + k
-        sym = torch.from_numpy(wl.fsk4_symbols(n_syms, wl.SEED_BASE + sid)).to(device)
-        f_inst = c["carrier"] + c["deviation"] * sym.repeat_interleave(sps)[:n_samples]
-        ph = torch.cumsum(f_inst.double() * (2 * math.pi / c["fs"]), 0)
+        f_sym = c["carrier"] + c["deviation"] * wl.fsk4_symbols(n_syms, wl.SEED_BASE + sid)
+        if not np.array_equal(f_sym, np.round(f_sym)):
+            raise ValueError("synth_captures: the 4FSK frequencies must be whole numbers of Hz")
+        f_inst = torch.from_numpy(f_sym.astype(np.int64)).to(device).repeat_interleave(sps)[:n_samples]
+        ph = torch.cumsum(f_inst, 0).double() * (2 * math.pi / c["fs"])
         ph = torch.remainder(ph, 2 * math.pi)
         gen = torch.Generator(device=device)
         gen.manual_seed(wl.SEED_BASE + sid)
@@ -435,10 +456,32 @@ def measured_traffic(kernel, captures, samples, launches_per_step):
     return None, None
 
 
+def dump_outputs(dirname, y):
+    """--dump-outputs: the demodulator output of the last timed step, `y` (captures x outputs, float32, on the device),
+    -> DIR/demod_out.npy.  Beyond DUMP_MAX_BYTES it is a fixed sample drawn with DUMP_SEED, so that the same arguments
+    always pick the same elements: the same sorted columns of every capture (and sorted captures only if one column
+    of each would not fit)."""
+    import torch
+    rows, cols = y.shape
+    cap = DUMP_MAX_BYTES // y.element_size()
+    rng = np.random.default_rng(DUMP_SEED)
+    ri = np.arange(rows) if rows <= cap else np.sort(rng.choice(rows, cap, replace=False))
+    kc = min(cols, cap // len(ri))
+    ci = np.arange(cols) if kc == cols else np.sort(rng.choice(cols, kc, replace=False))
+    if len(ri) < rows:
+        y = y.index_select(0, torch.from_numpy(ri).to(y.device))
+    if len(ci) < cols:
+        y = y.index_select(1, torch.from_numpy(ci).to(y.device))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "demod_out.npy"), y.cpu().numpy().astype(np.float32, copy=False))
+
+
 def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no torchrun around us: be the launcher (before torch / HIP are touched in this process)
         return launch_ranks(a)
@@ -481,7 +524,8 @@ def main():
     buf = torch.zeros((B, row, 2), dtype=torch.float32, device=dev)
     caps = synth_captures(torch, wl, B, n, my_streams[0], dev)
     buf[:, :n, :] = caps
-    x0_host = caps[0].cpu().numpy().reshape(-1).view(np.complex64).copy() if rank == 0 else None
+    want_cpu_baseline = a.full and world == 1 and not a.no_cpu_baseline
+    x0_host = caps[0].cpu().numpy().reshape(-1).view(np.complex64).copy() if want_cpu_baseline else None
     del caps
     orow = ((nout + 63) // 64) * 64
     out = torch.empty((B, orow), dtype=torch.float32, device=dev)
@@ -539,12 +583,14 @@ def main():
         allr = [None] * world
         dist.all_gather_object(allr, my_elapsed / a.steps * 1e3)
         per_rank_ms = allr
+    if a.dump_outputs and rank == 0:      # before anything else reuses `out`
+        dump_outputs(a.dump_outputs, out[:, :nout])
 
-    # the same step on the vector-FMA engine (the north star's "no MFMA" form), reported beside the headline: a few
-    # untimed steps for the clocks, then the same K steps under HIP events
+    # --full: the same step on the vector-FMA engine (the north star's "no MFMA" form), reported beside the headline: a
+    # few untimed steps for the clocks, then the same K steps under HIP events
     valu_ms = None
     reftaps_ms = None
-    if a.engine == "fast" and not a.per_capture_launch:
+    if a.full and a.engine == "fast" and not a.per_capture_launch:
         blk.set_mode(g.MODE_FAST_VALU)
         for _ in range(max(a.warmup, 3)):
             step()
@@ -574,7 +620,7 @@ def main():
     # ... and in the bit-exact mode (GRHIP_MODE_GENERIC: the reference's generic order, every operation unfused; the fused
     # generic-order kernel takes the batch in one launch like the fast engines)
     generic_ms = None
-    if a.engine == "fast" and not a.per_capture_launch and rank == 0:
+    if a.full and a.engine == "fast" and not a.per_capture_launch and rank == 0:
         blk.set_mode(g.MODE_GENERIC)
         for _ in range(2):
             step()
@@ -649,10 +695,10 @@ def main():
                 "kernel": "fir_generic_win_kernel<ccc,D=4,demod>", "kernel_ms": generic_ms,
                 "Msamples_per_s_per_gpu": B * n / generic_ms / 1e3,
                 "bound": "vector pipes: 256 unfused packed instructions per input sample"}
-        if world == 1 and not a.no_cpu_baseline:
+        if want_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(wl, x0_host[: a.cpu_samples], proto)
             res["gpu_over_cpu"] = value / res["cpu_baseline"]["value"]
-        if world == 1 and a.chain_captures > 0 and not a.per_capture_launch:
+        if a.full and world == 1 and a.chain_captures > 0 and not a.per_capture_launch:
             del buf, out
             torch.cuda.empty_cache()
             try:

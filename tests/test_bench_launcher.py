@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -107,3 +109,66 @@ def test_bench_generator_is_the_parity_workload():
             assert abs(np.mean(np.abs(x) ** 2) - (1 + n0)) < 0.02 * (1 + n0)
         # and the difference of the two is noise only: E|x_b - x_w|^2 = 2 n0
         assert abs(np.mean(np.abs(xb - xw) ** 2) - 2 * n0) < 0.03 * 2 * n0 + 1e-3
+
+
+def _bench_module(name):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: the whole output while it fits, else the same seeded columns of every capture -- float32, within
+    the size bound, and the same elements on every call"""
+    import numpy as np
+    import torch
+    b = _bench_module("bench_mod3")
+    y = torch.arange(8 * 1000, dtype=torch.float32).reshape(8, 1000)
+    b.dump_outputs(str(tmp_path / "whole"), y)
+    whole = np.load(tmp_path / "whole" / "demod_out.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, y.numpy())
+    b.DUMP_MAX_BYTES = 4000
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), y[:, :999])
+    s1, s2 = (np.load(tmp_path / d / "demod_out.npy") for d in ("s1", "s2"))
+    assert s1.dtype == np.float32 and s1.shape == (8, 125) and s1.nbytes <= 4000
+    assert np.array_equal(s1, s2)
+    cols = s1[0].astype(np.int64)
+    assert np.all(np.diff(cols) > 0) and cols[-1] < 999                       # sorted distinct columns
+    assert np.array_equal(s1, y.numpy()[:, cols])                             # the same columns in every capture
+
+
+def test_bench_captures_are_deterministic():
+    """the same stream ids give the same bits on every call (the phase is an exact integer running sum)"""
+    import torch
+    import grhip_loader
+    b = _bench_module("bench_mod4")
+    wl = grhip_loader.import_grhip().workload
+    x1 = b.synth_captures(torch, wl, 2, 100_000, 7, torch.device("cpu"))
+    x2 = b.synth_captures(torch, wl, 2, 100_000, 7, torch.device("cpu"))
+    assert torch.equal(x1.view(torch.int32), x2.view(torch.int32))
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_and_dump(tmp_path):
+    """a plain run on the device: --steps timed steps, the headline fields and ms_per_step in ONE line, nothing of --full;
+    two runs with the same arguments dump the same outputs (inputs synthesised on the device, bit for bit)"""
+    import numpy as np
+    lines = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--captures", "2", "--samples", "200000",
+                  "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        ls = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(ls) == 1, r.stdout
+        lines.append(json.loads(ls[0]))
+    res = lines[0]
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert res[k] == lines[1][k]
+    assert not {"vector_engine", "reference_taps_engine", "bit_exact_engine", "cpu_baseline", "chain"} & set(res)
+    a, b = (np.load(tmp_path / d / "demod_out.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (2, 200000 // 4) and np.isfinite(a).all()
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))

@@ -1,8 +1,6 @@
-mkdir -p gpurun_out
-timeout -k 10 300 python bench.py --no-cpu-baseline --chain-captures 0 > gpurun_out/bench_quick.json 2> gpurun_out/bench_quick.err; rc=$?
-python3 -c "
-import json
-d=json.loads(open('gpurun_out/bench_quick.json').read().strip().splitlines()[-1])
+set -o pipefail
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --chain-captures 0 | tail -1 | python3 -c "
+import json, sys
+d=json.loads(sys.stdin.read())
 print(d['value'], d['roofline']['frac']); print(d.get('bit_exact_engine')); print(d.get('vector_engine',{}).get('Msamples_per_s_per_gpu'))
 "
-exit $rc

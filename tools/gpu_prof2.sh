@@ -1,12 +1,12 @@
-# Profiles `python3 bench.py <args>` on the GPU box: rocprofv3 kernel stats + PMC passes (each in its own run),
+# Profiles `python3 bench.py --full <args>` on the GPU box: rocprofv3 kernel stats + PMC passes (each in its own run),
 # summarised for the kernels whose name contains <match>.  usage: bash tools/gpu_prof2.sh <tag> <match> [bench args]
 TAG=${1:-r02}; MATCH=${2:-fir_mfma}; shift; shift
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_$TAG
 rm -rf $O; mkdir -p $O
-python3 $R/bench.py "$@" > $O/bench_line.json 2> $O/bench_stderr.log
-BENCH="python3 $R/bench.py --no-cpu-baseline --chain-captures 0 $@"
+python3 $R/bench.py --full "$@" > $O/bench_line.json 2> $O/bench_stderr.log
+BENCH="python3 $R/bench.py --full --no-cpu-baseline --chain-captures 0 $@"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- $BENCH > $O/bench_trace.log 2>&1
 rocprofv3 --pmc GRBM_GUI_ACTIVE FETCH_SIZE --output-format csv -d $O/pmc_fetch -- $BENCH > $O/bench_pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --output-format csv -d $O/pmc_write -- $BENCH > $O/bench_pmc_write.log 2>&1

@@ -12,5 +12,5 @@ for v in ${VARIANTS:-diag:0 diag:1}; do
 done; done
 cat gpurun_out/rs_ab4.log
 timeout -k 10 500 python -m pytest tests/test_gpu_chain.py -x -q -m gpu -k "output_limit or full_size" > gpurun_out/chain_new_tests.log 2>&1; tail -5 gpurun_out/chain_new_tests.log
-timeout -k 10 500 python bench.py > gpurun_out/r03_bench_try.json 2> gpurun_out/r03_bench_try.err; python -c "
-import json; d=json.load(open('gpurun_out/r03_bench_try.json')); print('value',d['value'],'frac',d['roofline']['frac']); print(json.dumps(d.get('chain'))[:1500])"
+timeout -k 10 500 python bench.py --full | tail -1 | python -c "
+import json, sys; d=json.loads(sys.stdin.read()); print('value',d['value'],'frac',d['roofline']['frac']); print(json.dumps(d.get('chain'))[:1500])"
