@@ -10,7 +10,7 @@ __all__ = [
     "fir_filter_ccf", "fir_filter_fff", "fir_filter_ccc", "fir_filter_with_buffer",
     "freq_xlating_fir_filter_ccc", "quadrature_demod_cf", "xlating_demod",
     "clock_recovery_mm_ff", "clock_recovery_mm_cc", "binary_slicer_fb", "correlate_access_code_bb", "pager_slicer_fb", "unpack_k_bits_bb", "framer_sink_1", "framer_sink_1_batch", "stream_to_streams", "streams_to_stream", "vector_to_streams", "stream_to_vector", "head",
-    "fft_vcc", "fft_filter_ccc", "pfb_channelizer_ccf", "pfb_decimator_ccf", "dmr_chain", "run_sync_block",
+    "fft_vcc", "fft_filter_ccc", "pfb_channelizer_ccf", "pfb_decimator_ccf", "pfb_arb_resampler_ccf", "pfb_arb_resampler_fff", "dmr_chain", "run_sync_block",
 ]
 
 MODE_FAST = 0
@@ -1032,6 +1032,89 @@ class pfb_decimator_ccf(_Block):
                                                           C.c_void_p]
         return _check(L.grhip_pfb_decimator_ccf_work_device(self._h, int(noutput_items), _devptr(d_in),
                                                             int(stream_stride_items), _devptr(d_out), _stream(stream)))
+
+
+# ----------------------------------------------------------------------------
+# gr.pfb_arb_resampler_ccf / gr.pfb_arb_resampler_fff  (filter/gr_pfb_arb_resampler_ccf.i)
+# ----------------------------------------------------------------------------
+class _pfb_arb_resampler(_Block):
+    _kind = None
+    _dtype = None
+
+    def __init__(self, rate, taps, filter_size=32, device=0):
+        _Block.__init__(self)
+        self._destroy = "grhip_pfb_arb_resampler_%s_destroy" % self._kind
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        f = self._fn("create")
+        f.argtypes = [C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_size_t, C.c_uint, C.c_int]
+        _check(f(C.byref(self._h), float(rate), _ptr(t), len(t), int(filter_size), int(device)))
+
+    def _fn(self, name):
+        return getattr(lib(), "grhip_pfb_arb_resampler_%s_%s" % (self._kind, name))
+
+    def set_rate(self, rate):
+        f = self._fn("set_rate")
+        f.argtypes = [C.c_void_p, C.c_float]
+        _check(f(self._h, float(rate)))
+
+    def set_mode(self, mode):
+        _check(self._fn("set_mode")(self._h, int(mode)))
+
+    def history(self):
+        return _check(self._fn("history")(self._h))
+
+    def taps_per_filter(self):
+        return _check(self._fn("taps_per_filter")(self._h))
+
+    def forecast(self, noutput_items):
+        return _check(self._fn("forecast")(self._h, int(noutput_items)))
+
+    def general_work(self, noutput_items, input_items):
+        """returns (out, consumed); input_items carries the history in front"""
+        x = np.ascontiguousarray(input_items, dtype=self._dtype)
+        out = np.zeros(max(int(noutput_items), 1), dtype=self._dtype)
+        consumed = C.c_int(0)
+        f = self._fn("general_work")
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        n = _check(f(self._h, int(noutput_items), len(x), _ptr(x), _ptr(out), C.byref(consumed)))
+        return out[:n].copy(), consumed.value
+
+    def general_work_device(self, noutput_items, ninput_items, d_in, d_out, stream=None):
+        """returns (produced, consumed); the outputs are in d_out once `stream` has run"""
+        consumed = C.c_int(0)
+        f = self._fn("general_work_device")
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
+        n = _check(f(self._h, int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out),
+                     C.byref(consumed), _stream(stream)))
+        return n, consumed.value
+
+    def run_captures_device(self, n_streams, n_samples, d_in, in_stride_items, d_out, out_stride_items,
+                            stream=None):
+        """n_streams fresh-state captures (no history in front) in one launch; returns the outputs per capture.
+        d_out=None only returns that number."""
+        n_out = C.c_size_t(0)
+        f = self._fn("run_captures_device")
+        f.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                      C.POINTER(C.c_size_t), C.c_void_p]
+        _check(f(self._h, int(n_streams), int(n_samples), _devptr(d_in), int(in_stride_items), _devptr(d_out),
+                 int(out_stride_items), C.byref(n_out), _stream(stream)))
+        return n_out.value
+
+    def captures_nout(self, n_samples):
+        """outputs of one fresh-state capture of n_samples items"""
+        return self.run_captures_device(1, n_samples, None, n_samples, None, 0)
+
+
+class pfb_arb_resampler_ccf(_pfb_arb_resampler):
+    """gr.pfb_arb_resampler_ccf(rate, taps, filter_size=32)"""
+    _kind = "ccf"
+    _dtype = np.complex64
+
+
+class pfb_arb_resampler_fff(_pfb_arb_resampler):
+    """gr.pfb_arb_resampler_fff(rate, taps, filter_size=32)"""
+    _kind = "fff"
+    _dtype = np.float32
 
 
 # ----------------------------------------------------------------------------

@@ -255,7 +255,7 @@ int grhip_pager_slicer_fb_create(grhip_pager_slicer_fb **h, float alpha, int dev
     b->beta = (float)(1.0 - (double)alpha);          // pager_slicer_fb.cc:40
     int rc = b->init_device(device);
     if (!rc) rc = b->d_avg.reserve(sizeof(float));
-    if (!rc) { hipError_t e = hipMemset(b->d_avg.p, 0, sizeof(float)); if (e != hipSuccess) rc = fail(GRHIP_ERUNTIME, "memset"); }
+    if (!rc) rc = zero_device(b->d_avg.p, sizeof(float));
     if (rc) { b->d_avg.release(); b->destroy_base(); delete b; return rc; }
     *h = b;
     return GRHIP_OK;
@@ -447,7 +447,7 @@ int grhip_correlate_access_code_bb_create(grhip_correlate_access_code_bb **h, co
     c->p = p; c->flag_bit = fb;
     rc = c->init_device(device);
     if (!rc) rc = c->d_state.reserve(sizeof(CorrState));
-    if (!rc) { hipError_t e = hipMemset(c->d_state.p, 0, sizeof(CorrState)); if (e != hipSuccess) rc = fail(GRHIP_ERUNTIME, "memset"); }
+    if (!rc) rc = zero_device(c->d_state.p, sizeof(CorrState));
     if (rc) { c->d_state.release(); c->destroy_base(); delete c; return rc; }
     *h = c;
     return GRHIP_OK;

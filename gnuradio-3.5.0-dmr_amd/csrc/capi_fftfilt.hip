@@ -50,8 +50,8 @@ struct grhip_fft_filter_ccc : HandleBase {
             if (!rc4) rc4 = d_hist[0].reserve(hl * sizeof(float2));
             if (!rc4) rc4 = d_hist[1].reserve(hl * sizeof(float2));
             if (rc4) return rc4;
-            GRHIP_HIP(hipMemset(d_hist[0].p, 0, hl * sizeof(float2)));       // a fresh filter starts from silence
-            GRHIP_HIP(hipMemset(d_hist[1].p, 0, hl * sizeof(float2)));
+            if ((rc4 = zero_device(d_hist[0].p, hl * sizeof(float2)))) return rc4;   // a fresh filter starts from silence
+            if ((rc4 = zero_device(d_hist[1].p, hl * sizeof(float2)))) return rc4;
             hist_cur = 0;
         }
         const size_t tail_items = (size_t)(ntaps > 1 ? ntaps - 1 : 1);
@@ -59,7 +59,7 @@ struct grhip_fft_filter_ccc : HandleBase {
         if (!rc) rc = d_tail.reserve(tail_items * sizeof(float2));
         if (rc) return rc;
         GRHIP_HIP(hipMemcpy(d_xformed.p, H.data(), H.size() * sizeof(float2), hipMemcpyHostToDevice));
-        GRHIP_HIP(hipMemset(d_tail.p, 0, tail_items * sizeof(float2)));                 // tail cleared (:69-71)
+        if ((rc = zero_device(d_tail.p, tail_items * sizeof(float2)))) return rc;       // tail cleared (:69-71)
         return GRHIP_OK;
     }
     void release_all()

@@ -787,7 +787,7 @@ struct grhip_fir_filter_with_buffer : HandleBase {
         const size_t bytes = (size_t)(ntaps > 1 ? ntaps - 1 : 1) * item();
         int rc = d_hist.reserve(bytes);
         if (rc) return rc;
-        GRHIP_HIP(hipMemset(d_hist.p, 0, bytes));                       // memset(d_buffer, 0), .cc.t:55-57
+        if ((rc = zero_device(d_hist.p, bytes))) return rc;             // memset(d_buffer, 0), .cc.t:55-57
         return GRHIP_OK;
     }
 };
@@ -1158,7 +1158,7 @@ int grhip_xlating_demod_create(grhip_xlating_demod **h, int decimation, const fl
         rc = x->core.build(device);
     }
     if (!rc) rc = x->ystate.reserve(4 * sizeof(float2));
-    if (!rc) { hipError_t e = hipMemset(x->ystate.p, 0, 4 * sizeof(float2)); if (e != hipSuccess) rc = fail(GRHIP_ERUNTIME, "memset"); }
+    if (!rc) rc = zero_device(x->ystate.p, 4 * sizeof(float2));
     if (rc) { x->core.release(); x->ystate.release(); x->destroy_base(); delete x; return rc; }
     *h = x;
     return GRHIP_OK;

@@ -584,7 +584,7 @@ int grhip_framer_sink_1_create(grhip_framer_sink_1 **h, int device)
     if (!b) return fail(GRHIP_ENOMEM, "alloc");
     int rc = b->init_device(device);
     if (!rc) rc = b->d_state.reserve(sizeof(FramerState));
-    if (!rc && hipMemset(b->d_state.p, 0, sizeof(FramerState)) != hipSuccess) rc = fail(GRHIP_ERUNTIME, "hipMemset failed");   // enter_search(), .cc:84
+    if (!rc) rc = zero_device(b->d_state.p, sizeof(FramerState));   // enter_search(), .cc:84
     if (rc) { grhip_framer_sink_1_destroy(b); return rc; }
     *h = b;
     return GRHIP_OK;

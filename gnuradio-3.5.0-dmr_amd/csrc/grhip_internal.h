@@ -28,6 +28,16 @@ int fail(int code, const char *fmt, ...);
                                  __FILE__, __LINE__);                                       \
     } while (0)
 
+// Zero device memory and return once it is zero.  hipMemset is queued on the null stream, which the handles'
+// non-blocking streams do not wait for, and it may return before it has run: a kernel on a handle's stream could
+// read the buffer's previous contents.
+inline int zero_device(void *p, size_t bytes)
+{
+    GRHIP_HIP(hipMemset(p, 0, bytes));
+    GRHIP_HIP(hipStreamSynchronize(nullptr));
+    return GRHIP_OK;
+}
+
 // ---- device buffer that only ever grows -----------------------------------
 struct DevBuf {
     void *p = nullptr;
@@ -95,7 +105,7 @@ struct SchedBuf {
     {
         if (!b.p) {
             if (b.reserve(2 * sizeof(unsigned)) != GRHIP_OK) return nullptr;
-            if (hipMemset(b.p, 0, 2 * sizeof(unsigned)) != hipSuccess) { b.release(); return nullptr; }
+            if (zero_device(b.p, 2 * sizeof(unsigned)) != GRHIP_OK) { b.release(); return nullptr; }
         }
         return b.as<unsigned>();
     }

@@ -11,6 +11,7 @@
 //   grhip_correlate_access_code_bb           <- digital_correlate_access_code_bb
 //   gr_fft_vcc_hip (grhip_make_fft_vcc)       <- gr_fft_vcc_fftw, on the abstract gr_fft_vcc base (general/gr_fft_vcc.h:41-59)
 //   grhip_pfb_channelizer_ccf                <- gr_pfb_channelizer_ccf (filter/gr_pfb_channelizer_ccf.h:115-178)
+//   grhip_pfb_arb_resampler_ccf / _fff       <- gr_pfb_arb_resampler_ccf / _fff (filter/gr_pfb_arb_resampler_ccf.h:96-178)
 //
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
@@ -590,3 +591,69 @@ inline grhip_pfb_channelizer_ccf_sptr grhip_make_pfb_channelizer_ccf(unsigned nu
 {
     return gnuradio::get_initial_sptr(new grhip_pfb_channelizer_ccf_blk(numchans, taps, oversample_rate, device));
 }
+
+// ---------------------------------------------------------------------------
+// gr_pfb_arb_resampler_ccf / _fff  (a gr_block: general_work + consume_each, gr_block's default forecast)
+// ---------------------------------------------------------------------------
+template <class ITEM, class H, int (*CREATE)(H **, float, const float *, size_t, unsigned, int), void (*DESTROY)(H *),
+          int (*SET_RATE)(H *, float), int (*SET_MODE)(H *, int), int (*HISTORY)(const H *),
+          int (*WORK)(H *, int, int, const void *, void *, int *)>
+class grhip_pfb_arb_resampler_blk : public gr_block {
+    H *d_h = nullptr;
+protected:
+    grhip_pfb_arb_resampler_blk(const char *name, float rate, const std::vector<float> &taps, unsigned filter_size,
+                                int device)
+        : gr_block(name, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM)))
+    {
+        grhip_detail::check(CREATE(&d_h, rate, taps.data(), taps.size(), filter_size, device));
+        int h = HISTORY(d_h);
+        grhip_detail::check(h);
+        set_history((unsigned)h);                                      // tpf + 1 (.cc:118)
+        set_relative_rate(rate);                                       // set_rate (.h:169)
+    }
+public:
+    ~grhip_pfb_arb_resampler_blk() { DESTROY(d_h); }
+    void set_rate(float rate)
+    {
+        grhip_detail::check(SET_RATE(d_h, rate));
+        set_relative_rate(rate);
+    }
+    void set_mode(int mode) { grhip_detail::check(SET_MODE(d_h, mode)); }
+    int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
+                     gr_vector_void_star &out) override
+    {
+        int consumed = 0;
+        int r = WORK(d_h, noutput_items, ninput_items[0], in[0], out[0], &consumed);
+        grhip_detail::check(r);
+        consume_each(consumed);
+        return r;
+    }
+};
+
+#define GRHIP_ARB_BLOCK(SUF, ITEM)                                                                                     \
+    class grhip_pfb_arb_resampler_##SUF##_blk;                                                                         \
+    typedef boost::shared_ptr<grhip_pfb_arb_resampler_##SUF##_blk> grhip_pfb_arb_resampler_##SUF##_sptr;               \
+    class grhip_pfb_arb_resampler_##SUF##_blk                                                                          \
+        : public grhip_pfb_arb_resampler_blk<ITEM, grhip_pfb_arb_resampler_##SUF,                                      \
+                                             grhip_pfb_arb_resampler_##SUF##_create,                                   \
+                                             grhip_pfb_arb_resampler_##SUF##_destroy,                                  \
+                                             grhip_pfb_arb_resampler_##SUF##_set_rate,                                 \
+                                             grhip_pfb_arb_resampler_##SUF##_set_mode,                                 \
+                                             grhip_pfb_arb_resampler_##SUF##_history,                                  \
+                                             grhip_pfb_arb_resampler_##SUF##_general_work> {                           \
+        grhip_pfb_arb_resampler_##SUF##_blk(float rate, const std::vector<float> &taps, unsigned filter_size,          \
+                                            int device)                                                               \
+            : grhip_pfb_arb_resampler_blk("pfb_arb_resampler_" #SUF, rate, taps, filter_size, device) {}               \
+        friend grhip_pfb_arb_resampler_##SUF##_sptr grhip_make_pfb_arb_resampler_##SUF(float,                          \
+                                                                                      const std::vector<float> &,      \
+                                                                                      unsigned, int);                  \
+    };                                                                                                                 \
+    inline grhip_pfb_arb_resampler_##SUF##_sptr grhip_make_pfb_arb_resampler_##SUF(                                   \
+        float rate, const std::vector<float> &taps, unsigned filter_size = 32, int device = 0)                        \
+    {                                                                                                                  \
+        return gnuradio::get_initial_sptr(new grhip_pfb_arb_resampler_##SUF##_blk(rate, taps, filter_size, device));  \
+    }
+
+GRHIP_ARB_BLOCK(ccf, gr_complex)
+GRHIP_ARB_BLOCK(fff, float)
+#undef GRHIP_ARB_BLOCK

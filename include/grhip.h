@@ -394,6 +394,87 @@ GRHIP_API int grhip_pfb_decimator_ccf_work_device(grhip_pfb_decimator_ccf *h, in
                                                   size_t stream_stride_items, void *d_out, void *stream);
 
 /* ======================================================================
+ * gr_pfb_arb_resampler_ccf / gr_pfb_arb_resampler_fff  (arbitrary-rate polyphase resampler)
+ *   replaces gr_make_pfb_arb_resampler_ccf(float rate, const std::vector<float> &taps,
+ *                                          unsigned int filter_size = 32)   (and _fff: float items)
+ *   filter/gr_pfb_arb_resampler_ccf.h:166-170 (set_rate: D = floor(R/rate), f = R/rate - D in float),
+ *   filter/gr_pfb_arb_resampler_ccf.cc:42-83 (constructor), 93-124 (create_taps: R = filter_size filters,
+ *   tpf = ceil(ntaps/R), filter i gets taps[i + t*R], zero padded; history tpf + 1), 126-139 (create_diff_taps:
+ *   a second bank from taps[i+1] - taps[i], the last difference repeated), 158-209 (general_work:
+ *   out = filters[j].filter(&in[count]) + diff_filters[j].filter(&in[count]) * acc, then acc += f,
+ *   j += D + floor(acc), acc = fmod(acc, 1), count += j / R when j passes R; outputs while count < ninput - tpf;
+ *   state j, acc and the overshoot d_start_index carried between calls; consumes min(count, ninput)).
+ * gr_block: history() = tpf + 1, forecast(n) = n + tpf (gr_block's default, runtime/gr_block.cc:51-56).  The first
+ * general_work after create returns 0 and consumes nothing (d_updated, .cc:166-169); set_rate does not do that.
+ * Refused with GRHIP_EINVAL (undefined in the reference; std::invalid_argument in host/grhip_blocks.h):
+ *   - fewer than 2 taps (create_diff_taps underflows size()-1 for none, repeats an unset difference for one)
+ *   - filter_size == 0 (.cc:100 divides by it)
+ *   - rate <= 0 or not finite (set_relative_rate throws for negative rates, 0 gives floor(inf))
+ * Limits of the kernel (GRHIP_EINVAL beyond them): filter_size * (tpf | 1) <= 4096 (both banks in LDS, rows of an
+ * odd stride); filter_size / rate < 2^20.
+ * Modes: GRHIP_MODE_GENERIC is bit-exact against the reference's generic build (gr_fir_XXX_generic.cc.t:59-78 for
+ * both filters, the blend as a multiply and an add).  GRHIP_MODE_FAST, _FAST_VALU and _FAST_REFTAPS all mean the
+ * same FMA kernel with one blended tap h + acc*dh (there is no matrix-core engine for this block); the schedule is
+ * exact in every mode.  The default mode is grhip_get_default_mode() at create.
+ * Positions: the reference carries `count` through a float (.cc:196), exact below 2^24 items per call; this
+ * library keeps every position in exact integers (64-bit in run_captures_device), so calls of more than 2^24 items
+ * are where the two can part.
+ * The schedule: while the fractional rate f and the carried acc are multiples of 2^-23 it is a closed form the
+ * kernel evaluates per output, and the device entries never wait.  That holds for every call at rate <= filter_size
+ * from fresh state, and after set_rate between such rates.  Otherwise the float sums round: rate > filter_size, or
+ * a call at rate > filter_size left acc off the grid, after which a later rate <= filter_size keeps it off.  Then
+ * the host walks the reference's float32 arithmetic and uploads one entry per output.  Before that upload the
+ * device entries wait for this handle's previous walked launch to finish (that launch only, not the device).
+ * ====================================================================== */
+typedef struct grhip_pfb_arb_resampler_ccf grhip_pfb_arb_resampler_ccf;
+GRHIP_API int grhip_pfb_arb_resampler_ccf_create(grhip_pfb_arb_resampler_ccf **h, float rate, const float *taps,
+                                                 size_t ntaps, unsigned filter_size, int device);
+GRHIP_API void grhip_pfb_arb_resampler_ccf_destroy(grhip_pfb_arb_resampler_ccf *h);
+/* .h:166-170; takes effect at the next general_work, acc and j carried */
+GRHIP_API int grhip_pfb_arb_resampler_ccf_set_rate(grhip_pfb_arb_resampler_ccf *h, float rate);
+GRHIP_API int grhip_pfb_arb_resampler_ccf_set_mode(grhip_pfb_arb_resampler_ccf *h, int mode);
+GRHIP_API int grhip_pfb_arb_resampler_ccf_history(const grhip_pfb_arb_resampler_ccf *h);
+GRHIP_API int grhip_pfb_arb_resampler_ccf_taps_per_filter(const grhip_pfb_arb_resampler_ccf *h);
+GRHIP_API int grhip_pfb_arb_resampler_ccf_forecast(const grhip_pfb_arb_resampler_ccf *h, int noutput_items);
+/* general_work (.cc:158-209) on HOST buffers: in[0 .. ninput_items) with the history in front, out room for
+ * noutput_items; returns the items produced, *consumed the items to consume (consume_each, .cc:207) */
+GRHIP_API int grhip_pfb_arb_resampler_ccf_general_work(grhip_pfb_arb_resampler_ccf *h, int noutput_items,
+                                                       int ninput_items, const void *in, void *out, int *consumed);
+/* the same on DEVICE buffers, enqueued on `stream`; produced and *consumed are known on return (the schedule
+ * does not depend on the data), the outputs once the stream has run */
+GRHIP_API int grhip_pfb_arb_resampler_ccf_general_work_device(grhip_pfb_arb_resampler_ccf *h, int noutput_items,
+                                                              int ninput_items, const void *d_in, void *d_out,
+                                                              int *consumed, void *stream);
+/* n_streams captures in one launch, each from fresh state with the tpf history zeros a fresh flowgraph supplies
+ * (NOT in d_in): capture s at d_in + s*in_stride_items (n_samples items), its outputs at d_out + s*out_stride_items.
+ * *n_out receives the outputs per capture, the same for all: those with count_k < n_samples, exactly what the
+ * block produces from the whole stream however it is split into calls.  d_out == NULL only sets *n_out.  The
+ * handle's own state (j, acc, the first-call 0) is left alone. */
+GRHIP_API int grhip_pfb_arb_resampler_ccf_run_captures_device(grhip_pfb_arb_resampler_ccf *h, int n_streams,
+                                                              size_t n_samples, const void *d_in,
+                                                              size_t in_stride_items, void *d_out,
+                                                              size_t out_stride_items, size_t *n_out, void *stream);
+
+typedef struct grhip_pfb_arb_resampler_fff grhip_pfb_arb_resampler_fff;
+GRHIP_API int grhip_pfb_arb_resampler_fff_create(grhip_pfb_arb_resampler_fff **h, float rate, const float *taps,
+                                                 size_t ntaps, unsigned filter_size, int device);
+GRHIP_API void grhip_pfb_arb_resampler_fff_destroy(grhip_pfb_arb_resampler_fff *h);
+GRHIP_API int grhip_pfb_arb_resampler_fff_set_rate(grhip_pfb_arb_resampler_fff *h, float rate);
+GRHIP_API int grhip_pfb_arb_resampler_fff_set_mode(grhip_pfb_arb_resampler_fff *h, int mode);
+GRHIP_API int grhip_pfb_arb_resampler_fff_history(const grhip_pfb_arb_resampler_fff *h);
+GRHIP_API int grhip_pfb_arb_resampler_fff_taps_per_filter(const grhip_pfb_arb_resampler_fff *h);
+GRHIP_API int grhip_pfb_arb_resampler_fff_forecast(const grhip_pfb_arb_resampler_fff *h, int noutput_items);
+GRHIP_API int grhip_pfb_arb_resampler_fff_general_work(grhip_pfb_arb_resampler_fff *h, int noutput_items,
+                                                       int ninput_items, const void *in, void *out, int *consumed);
+GRHIP_API int grhip_pfb_arb_resampler_fff_general_work_device(grhip_pfb_arb_resampler_fff *h, int noutput_items,
+                                                              int ninput_items, const void *d_in, void *d_out,
+                                                              int *consumed, void *stream);
+GRHIP_API int grhip_pfb_arb_resampler_fff_run_captures_device(grhip_pfb_arb_resampler_fff *h, int n_streams,
+                                                              size_t n_samples, const void *d_in,
+                                                              size_t in_stride_items, void *d_out,
+                                                              size_t out_stride_items, size_t *n_out, void *stream);
+
+/* ======================================================================
  * gr_framer_sink_1  (the consumer of the correlator's flag bit)
  *   replaces gr_make_framer_sink_1(gr_msg_queue_sptr target_queue)
  *   general/gr_framer_sink_1.h:62-98, general/gr_framer_sink_1.cc:34-66 (states), 90-190 (work):
