@@ -1,5 +1,6 @@
 """ctypes binding of libgrhip.so.  See include/grhip.h for the contract."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -10,7 +11,10 @@ __all__ = [
     "fir_filter_ccf", "fir_filter_fff", "fir_filter_ccc", "fir_filter_with_buffer",
     "freq_xlating_fir_filter_ccc", "quadrature_demod_cf", "xlating_demod",
     "clock_recovery_mm_ff", "clock_recovery_mm_cc", "binary_slicer_fb", "correlate_access_code_bb", "pager_slicer_fb", "unpack_k_bits_bb", "framer_sink_1", "framer_sink_1_batch", "stream_to_streams", "streams_to_stream", "vector_to_streams", "stream_to_vector", "head",
-    "fft_vcc", "fft_filter_ccc", "pfb_channelizer_ccf", "pfb_decimator_ccf", "pfb_arb_resampler_ccf", "pfb_arb_resampler_fff", "dmr_chain", "run_sync_block",
+    "fft_vcc", "fft_filter_ccc", "pfb_channelizer_ccf", "pfb_decimator_ccf", "pfb_arb_resampler_ccf", "pfb_arb_resampler_fff",
+    "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
+    "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
+    "rational_resampler_ccf", "rational_resampler_fff", "rational_resampler_ccc", "design_filter", "dmr_chain", "run_sync_block",
 ]
 
 MODE_FAST = 0
@@ -1115,6 +1119,270 @@ class pfb_arb_resampler_fff(_pfb_arb_resampler):
     """gr.pfb_arb_resampler_fff(rate, taps, filter_size=32)"""
     _kind = "fff"
     _dtype = np.float32
+
+
+# ----------------------------------------------------------------------------
+# gr.interp_fir_filter_XXX / gr.rational_resampler_base_XXX  (filter/gr_interp_fir_filter_XXX.i.t,
+# filter/gr_rational_resampler_base_XXX.i.t) and blks2.rational_resampler_XXX
+# (python/gnuradio/blks2impl/rational_resampler.py)
+# ----------------------------------------------------------------------------
+_RS_CAPTURES_ARGS = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                     C.POINTER(C.c_size_t), C.c_void_p]
+
+
+class _rs_block(_Block):
+    _prefix = None
+    _kind = None
+    _dtype = np.complex64
+    _tap = np.float32
+
+    def _fn(self, name):
+        return getattr(lib(), "%s_%s" % (self._prefix, name))
+
+    def set_taps(self, taps):
+        t = np.ascontiguousarray(taps, dtype=self._tap)
+        f = self._fn("set_taps")
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        _check(f(self._h, _ptr(t), len(t)))
+
+    def set_mode(self, mode):
+        _check(self._fn("set_mode")(self._h, int(mode)))
+
+    def history(self):
+        return _check(self._fn("history")(self._h))
+
+    def interpolation(self):
+        return _check(self._fn("interpolation")(self._h))
+
+    def run_captures_device(self, n_streams, n_samples, d_in, in_stride_items, d_out, out_stride_items,
+                            stream=None):
+        """n_streams fresh captures in one launch; returns the outputs per capture.  d_out=None only returns that
+        number."""
+        n_out = C.c_size_t(0)
+        f = self._fn("run_captures_device")
+        f.argtypes = _RS_CAPTURES_ARGS
+        _check(f(self._h, int(n_streams), int(n_samples), _devptr(d_in), int(in_stride_items), _devptr(d_out),
+                 int(out_stride_items), C.byref(n_out), _stream(stream)))
+        return n_out.value
+
+    def captures_nout(self, n_samples):
+        """outputs of one fresh capture of n_samples items"""
+        return self.run_captures_device(1, n_samples, None, n_samples, None, 0)
+
+
+class _interp_fir_filter(_rs_block):
+    _prefix = "grhip_interp_fir_filter"
+    _destroy = "grhip_interp_fir_filter_destroy"
+
+    def __init__(self, interpolation, taps, device=0):
+        _Block.__init__(self)
+        t = np.ascontiguousarray(taps, dtype=self._tap)
+        f = self._fn("create")
+        f.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_uint, C.c_void_p, C.c_size_t, C.c_int]
+        _check(f(C.byref(self._h), self._kind.encode(), _uint_arg(interpolation), _ptr(t), len(t), int(device)))
+
+    def output_multiple(self):
+        return self.interpolation()
+
+    def work(self, noutput_items, input_items):
+        """gr_sync_interpolator work: input_items carries history()-1 items in front and holds at least
+        noutput_items/I + history() - 1; returns the outputs (none when the call installs latched taps)"""
+        x = np.ascontiguousarray(input_items, dtype=self._dtype)
+        n = int(noutput_items)
+        I = self.interpolation()
+        if n >= 0 and n % I == 0 and len(x) < n // I + self.history() - 1:
+            raise ValueError("work: %d outputs need %d input items, got %d" % (n, n // I + self.history() - 1, len(x)))
+        out = np.zeros(max(n, 1), dtype=self._dtype)
+        f = self._fn("work")
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        r = _check(f(self._h, n, _ptr(x), _ptr(out)))
+        return out[:r].copy()
+
+    def work_device(self, noutput_items, d_in, d_out, stream=None):
+        f = self._fn("work_device")
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        return _check(f(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out), _stream(stream)))
+
+
+class _rational_resampler_base(_rs_block):
+    _prefix = "grhip_rational_resampler_base"
+    _destroy = "grhip_rational_resampler_base_destroy"
+
+    def __init__(self, interpolation, decimation, taps, device=0):
+        _Block.__init__(self)
+        t = np.ascontiguousarray(taps, dtype=self._tap)
+        f = self._fn("create")
+        f.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.c_int]
+        _check(f(C.byref(self._h), self._kind.encode(), _uint_arg(interpolation), _uint_arg(decimation), _ptr(t),
+                 len(t), int(device)))
+
+    def decimation(self):
+        return _check(self._fn("decimation")(self._h))
+
+    def relative_rate(self):
+        return 1.0 * self.interpolation() / self.decimation()
+
+    def forecast(self, noutput_items):
+        return _check(self._fn("forecast")(self._h, int(noutput_items)))
+
+    def general_work(self, noutput_items, input_items):
+        """returns (out, consumed); no history in front of input_items (the scheduler sees history 1)"""
+        x = np.ascontiguousarray(input_items, dtype=self._dtype)
+        out = np.zeros(max(int(noutput_items), 1), dtype=self._dtype)
+        consumed = C.c_int(0)
+        f = self._fn("general_work")
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        n = _check(f(self._h, int(noutput_items), len(x), _ptr(x), _ptr(out), C.byref(consumed)))
+        return out[:n].copy(), consumed.value
+
+    def general_work_device(self, noutput_items, ninput_items, d_in, d_out, stream=None):
+        """returns (produced, consumed); the outputs are in d_out once `stream` has run"""
+        consumed = C.c_int(0)
+        f = self._fn("general_work_device")
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
+        n = _check(f(self._h, int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out),
+                     C.byref(consumed), _stream(stream)))
+        return n, consumed.value
+
+
+def _uint_arg(v):
+    """a rate factor for a C unsigned: a negative one is out of range, as 0 is"""
+    v = int(v)
+    if v < 0:
+        raise GrhipError(-2, "negative rate factor %d" % v)
+    return v
+
+
+class interp_fir_filter_ccf(_interp_fir_filter):
+    """gr.interp_fir_filter_ccf(interpolation, taps)"""
+    _kind = "ccf"
+
+
+class interp_fir_filter_fff(_interp_fir_filter):
+    """gr.interp_fir_filter_fff(interpolation, taps)"""
+    _kind = "fff"
+    _dtype = np.float32
+
+
+class interp_fir_filter_ccc(_interp_fir_filter):
+    """gr.interp_fir_filter_ccc(interpolation, taps)"""
+    _kind = "ccc"
+    _tap = np.complex64
+
+
+class rational_resampler_base_ccf(_rational_resampler_base):
+    """gr.rational_resampler_base_ccf(interpolation, decimation, taps)"""
+    _kind = "ccf"
+
+
+class rational_resampler_base_fff(_rational_resampler_base):
+    """gr.rational_resampler_base_fff(interpolation, decimation, taps)"""
+    _kind = "fff"
+    _dtype = np.float32
+
+
+class rational_resampler_base_ccc(_rational_resampler_base):
+    """gr.rational_resampler_base_ccc(interpolation, decimation, taps)"""
+    _kind = "ccc"
+    _tap = np.complex64
+
+
+def _izero(x):
+    """Izero of general/gr_firdes.cc:35-49 (double)"""
+    s = u = 1.0
+    n = 1
+    halfx = x / 2.0
+    while True:
+        temp = halfx / float(n)
+        n += 1
+        temp *= temp
+        u *= temp
+        s += u
+        if not (u >= 1e-21 * s):
+            return s
+
+
+def _firdes_low_pass_kaiser(gain, sampling_freq, cutoff_freq, transition_width, beta):
+    """gr_firdes::low_pass(..., WIN_KAISER, beta) of general/gr_firdes.cc:105-148, with compute_ntaps (:681-695) and
+    3.5.0's one-sided Kaiser window (:759-772): float taps and window, the normalisation a double sum of the floats"""
+    if sampling_freq <= 0.0:
+        raise ValueError("gr_firdes check failed: sampling_freq > 0")
+    if cutoff_freq <= 0.0 or cutoff_freq > sampling_freq / 2:
+        raise ValueError("gr_firdes check failed: 0 < fa <= sampling_freq / 2")
+    if transition_width <= 0:
+        raise ValueError("gr_dirdes check failed: transition_width > 0")
+    delta_f = transition_width / sampling_freq
+    ntaps = int(10.0 / delta_f + 0.5)                  # width_factor[WIN_KAISER] = 10 (a float, exactly 10)
+    if (ntaps & 1) == 0:
+        ntaps += 1
+    ibeta = 1.0 / _izero(beta)
+    inm1 = 1.0 / float(ntaps)
+    temp = np.arange(ntaps, dtype=np.float64) * inm1
+    arg = beta * np.sqrt(1.0 - temp * temp)
+    w = np.array([_izero(float(a)) * ibeta for a in arg], dtype=np.float32)
+    M = (ntaps - 1) // 2
+    fwT0 = 2 * np.pi * cutoff_freq / sampling_freq
+    n = np.arange(-M, M + 1, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        t = np.sin(n * fwT0) / (n * np.pi) * w.astype(np.float64)
+    t[M] = fwT0 / np.pi * np.float64(w[M])
+    taps = t.astype(np.float32)
+    fmax = float(taps[M])
+    for v in taps[M + 1:]:
+        fmax += float(np.float32(2) * v)
+    gain /= fmax
+    return (taps.astype(np.float64) * gain).astype(np.float32)
+
+
+def design_filter(interpolation, decimation, fractional_bw):
+    """blks2impl/rational_resampler.py:26-56: low-pass taps of gain I at cutoff mid/I, transition tw/I, Kaiser beta 5"""
+    if fractional_bw >= 0.5 or fractional_bw <= 0:
+        raise ValueError("Invalid fractional_bandwidth, must be in (0, 0.5)")
+    beta = 5.0
+    trans_width = 0.5 - fractional_bw
+    mid_transition_band = 0.5 - trans_width / 2
+    return _firdes_low_pass_kaiser(interpolation, 1, mid_transition_band / interpolation,
+                                   trans_width / interpolation, beta)
+
+
+class _rational_resampler(object):
+    """blks2impl/rational_resampler.py:60-100: the argument checks, I and D reduced by their gcd, taps designed when
+    none are given (fractional_bw 0.4 when neither is), then a rational_resampler_base_XXX.  Its methods are the base
+    block's (`resampler`)."""
+    _base = None
+
+    def __init__(self, interpolation, decimation, taps=None, fractional_bw=None, device=0):
+        if not isinstance(interpolation, int) or interpolation < 1:
+            raise ValueError("interpolation must be an integer >= 1")
+        if not isinstance(decimation, int) or decimation < 1:
+            raise ValueError("decimation must be an integer >= 1")
+        if taps is None and fractional_bw is None:
+            fractional_bw = 0.4
+        d = math.gcd(interpolation, decimation)
+        interpolation = interpolation // d
+        decimation = decimation // d
+        if taps is None:
+            taps = design_filter(interpolation, decimation, fractional_bw)
+        self.taps = np.asarray(taps)
+        self.resampler = self._base(interpolation, decimation, taps, device)
+
+    def __getattr__(self, name):
+        return getattr(self.__dict__["resampler"], name)
+
+
+class rational_resampler_ccf(_rational_resampler):
+    """blks2.rational_resampler_ccf(interpolation, decimation, taps=None, fractional_bw=None)"""
+    _base = rational_resampler_base_ccf
+
+
+class rational_resampler_fff(_rational_resampler):
+    """blks2.rational_resampler_fff(interpolation, decimation, taps=None, fractional_bw=None)"""
+    _base = rational_resampler_base_fff
+
+
+class rational_resampler_ccc(_rational_resampler):
+    """blks2.rational_resampler_ccc(interpolation, decimation, taps=None, fractional_bw=None)"""
+    _base = rational_resampler_base_ccc
 
 
 # ----------------------------------------------------------------------------

@@ -12,6 +12,8 @@
 //   gr_fft_vcc_hip (grhip_make_fft_vcc)       <- gr_fft_vcc_fftw, on the abstract gr_fft_vcc base (general/gr_fft_vcc.h:41-59)
 //   grhip_pfb_channelizer_ccf                <- gr_pfb_channelizer_ccf (filter/gr_pfb_channelizer_ccf.h:115-178)
 //   grhip_pfb_arb_resampler_ccf / _fff       <- gr_pfb_arb_resampler_ccf / _fff (filter/gr_pfb_arb_resampler_ccf.h:96-178)
+//   grhip_interp_fir_filter_XXX              <- gr_interp_fir_filter_XXX (filter/gr_interp_fir_filter_XXX.h.t)
+//   grhip_rational_resampler_base_XXX        <- gr_rational_resampler_base_XXX (filter/gr_rational_resampler_base_XXX.h.t)
 //
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
@@ -657,3 +659,107 @@ public:
 GRHIP_ARB_BLOCK(ccf, gr_complex)
 GRHIP_ARB_BLOCK(fff, float)
 #undef GRHIP_ARB_BLOCK
+
+// ---------------------------------------------------------------------------
+// gr_interp_fir_filter_XXX  (a gr_sync_interpolator: history nt, output_multiple I; filter/gr_interp_fir_filter_XXX.h.t)
+// gr_rational_resampler_base_XXX  (a gr_block: gr_block's history stays 1, the reference's own forecast, relative
+// rate I/D; filter/gr_rational_resampler_base_XXX.h.t)
+// ---------------------------------------------------------------------------
+template <class ITEM, class TAP> class grhip_interp_fir_filter_blk : public gr_sync_interpolator {
+    grhip_interp_fir_filter *d_h = nullptr;
+public:
+    grhip_interp_fir_filter_blk(const char *kind, unsigned interpolation, const std::vector<TAP> &taps, int device)
+        : gr_sync_interpolator(std::string("interp_fir_filter_") + kind, gr_make_io_signature(1, 1, sizeof(ITEM)),
+                               gr_make_io_signature(1, 1, sizeof(ITEM)), interpolation)
+    {
+        grhip_detail::check(grhip_interp_fir_filter_create(&d_h, kind, interpolation,
+                                                           reinterpret_cast<const float *>(taps.data()), taps.size(),
+                                                           device));
+        sync_history();
+    }
+    ~grhip_interp_fir_filter_blk() { grhip_interp_fir_filter_destroy(d_h); }
+    void set_taps(const std::vector<TAP> &taps)
+    {
+        grhip_detail::check(grhip_interp_fir_filter_set_taps(d_h, reinterpret_cast<const float *>(taps.data()),
+                                                             taps.size()));
+    }
+    void set_mode(int mode) { grhip_detail::check(grhip_interp_fir_filter_set_mode(d_h, mode)); }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int r = grhip_interp_fir_filter_work(d_h, noutput_items, in[0], out[0]);
+        grhip_detail::check(r);
+        sync_history();                                                 // install_taps: set_history(nt)
+        return r;
+    }
+private:
+    void sync_history()
+    {
+        int h = grhip_interp_fir_filter_history(d_h);
+        grhip_detail::check(h);
+        set_history((unsigned)h);
+    }
+};
+
+template <class ITEM, class TAP> class grhip_rational_resampler_base_blk : public gr_block {
+    grhip_rational_resampler_base *d_h = nullptr;
+public:
+    grhip_rational_resampler_base_blk(const char *kind, unsigned interpolation, unsigned decimation,
+                                      const std::vector<TAP> &taps, int device)
+        : gr_block(std::string("rational_resampler_base_") + kind, gr_make_io_signature(1, 1, sizeof(ITEM)),
+                   gr_make_io_signature(1, 1, sizeof(ITEM)))
+    {
+        grhip_detail::check(grhip_rational_resampler_base_create(&d_h, kind, interpolation, decimation,
+                                                                 reinterpret_cast<const float *>(taps.data()),
+                                                                 taps.size(), device));
+        set_relative_rate(1.0 * interpolation / decimation);          // .cc.t:63
+    }
+    ~grhip_rational_resampler_base_blk() { grhip_rational_resampler_base_destroy(d_h); }
+    unsigned interpolation() const { return (unsigned)grhip_rational_resampler_base_interpolation(d_h); }
+    unsigned decimation() const { return (unsigned)grhip_rational_resampler_base_decimation(d_h); }
+    // the block's own history (nt), which hides gr_block's: the scheduler keeps seeing 1 (.h.t:51,72-73)
+    unsigned resampler_history() const { return (unsigned)grhip_rational_resampler_base_history(d_h); }
+    void set_taps(const std::vector<TAP> &taps)
+    {
+        grhip_detail::check(grhip_rational_resampler_base_set_taps(d_h, reinterpret_cast<const float *>(taps.data()),
+                                                                   taps.size()));
+    }
+    void set_mode(int mode) { grhip_detail::check(grhip_rational_resampler_base_set_mode(d_h, mode)); }
+    void forecast(int noutput_items, gr_vector_int &req) override
+    {
+        int n = grhip_rational_resampler_base_forecast(d_h, noutput_items);
+        grhip_detail::check(n);
+        for (size_t i = 0; i < req.size(); i++) req[i] = n;
+    }
+    int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
+                     gr_vector_void_star &out) override
+    {
+        int consumed = 0;
+        int r = grhip_rational_resampler_base_general_work(d_h, noutput_items, ninput_items[0], in[0], out[0],
+                                                           &consumed);
+        grhip_detail::check(r);
+        consume_each(consumed);
+        return r;
+    }
+};
+
+#define GRHIP_RS_BLOCKS(SUF, ITEM, TAP)                                                                                \
+    typedef grhip_interp_fir_filter_blk<ITEM, TAP> grhip_interp_fir_filter_##SUF;                                     \
+    typedef boost::shared_ptr<grhip_interp_fir_filter_##SUF> grhip_interp_fir_filter_##SUF##_sptr;                    \
+    inline grhip_interp_fir_filter_##SUF##_sptr grhip_make_interp_fir_filter_##SUF(                                   \
+        unsigned interpolation, const std::vector<TAP> &taps, int device = 0)                                         \
+    {                                                                                                                  \
+        return gnuradio::get_initial_sptr(new grhip_interp_fir_filter_##SUF(#SUF, interpolation, taps, device));      \
+    }                                                                                                                  \
+    typedef grhip_rational_resampler_base_blk<ITEM, TAP> grhip_rational_resampler_base_##SUF;                         \
+    typedef boost::shared_ptr<grhip_rational_resampler_base_##SUF> grhip_rational_resampler_base_##SUF##_sptr;        \
+    inline grhip_rational_resampler_base_##SUF##_sptr grhip_make_rational_resampler_base_##SUF(                       \
+        unsigned interpolation, unsigned decimation, const std::vector<TAP> &taps, int device = 0)                    \
+    {                                                                                                                  \
+        return gnuradio::get_initial_sptr(                                                                             \
+            new grhip_rational_resampler_base_##SUF(#SUF, interpolation, decimation, taps, device));                   \
+    }
+
+GRHIP_RS_BLOCKS(ccf, gr_complex, float)
+GRHIP_RS_BLOCKS(fff, float, float)
+GRHIP_RS_BLOCKS(ccc, gr_complex, gr_complex)
+#undef GRHIP_RS_BLOCKS

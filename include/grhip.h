@@ -475,6 +475,100 @@ GRHIP_API int grhip_pfb_arb_resampler_fff_run_captures_device(grhip_pfb_arb_resa
                                                               size_t out_stride_items, size_t *n_out, void *stream);
 
 /* ======================================================================
+ * gr_interp_fir_filter_{ccf,fff,ccc}  (interpolating FIR: I outputs per input item)
+ *   replaces gr_make_interp_fir_filter_XXX(unsigned interpolation, const std::vector<TAP> &taps)
+ *   filter/gr_interp_fir_filter_XXX.cc.t:72-109 (set_taps: zeros in FRONT of the taps up to a multiple of I;
+ *   install_taps: nt = len/I, filter n gets taps[n + k*I], reversed by gr_fir_XXX::set_taps; set_history(nt)),
+ *   112-145 (work: out[i*I + nf] = firs[nf]->filter(&in[i])); runtime/gr_sync_interpolator.h:48-53
+ *   (output_multiple = I, forecast n/I + nt - 1, consumes n/I).
+ * kind: "ccf" | "fff" | "ccc" as grhip_fir_filter_create (complex taps interleaved, ntaps counts taps).
+ * history() = nt, so the input of work carries nt - 1 history items in front: in[0 .. n/I + nt - 1).
+ * The constructor installs the taps; set_taps latches new ones, and the next work call installs them and returns 0
+ * (nt, and with it history(), changes then).  That call waits for the handle's earlier launches (the bank is
+ * rewritten); no other call waits for the device beyond the host-buffer entries' own copies.
+ * Refused: interpolation == 0 -> GRHIP_ERANGE (std::out_of_range, as the reference); ntaps == 0 -> GRHIP_EINVAL
+ * (filters of 0 taps are outside the reference's defined behaviour); noutput_items not a multiple of I ->
+ * GRHIP_EINVAL (output_multiple); interpolation > 2^20 and shapes beyond the kernel's limits below -> GRHIP_EINVAL.
+ * Modes: GRHIP_MODE_GENERIC is bit-exact against the reference's generic build (gr_fir_XXX_generic.cc.t:59-78:
+ * 2 accumulators for ccf/ccc, 4 for fff, the tail into acc0, no contraction).  GRHIP_MODE_FAST, _FAST_VALU and
+ * _FAST_REFTAPS all mean the same FMA kernel (there is no matrix-core engine for these blocks), within 1e-5 of the
+ * output peak.  The default mode is grhip_get_default_mode() at create.
+ * Kernel limits (both blocks; g = gcd(I, D)): a workgroup stages 64 periods of input in LDS, so
+ * 63*D/g + nt + (a few items) must fit 160 KiB (about 20000 complex or 40000 float items).
+ * ====================================================================== */
+typedef struct grhip_interp_fir_filter grhip_interp_fir_filter;
+GRHIP_API int grhip_interp_fir_filter_create(grhip_interp_fir_filter **h, const char *kind, unsigned interpolation,
+                                             const float *taps, size_t ntaps, int device);
+GRHIP_API void grhip_interp_fir_filter_destroy(grhip_interp_fir_filter *h);
+GRHIP_API int grhip_interp_fir_filter_set_taps(grhip_interp_fir_filter *h, const float *taps, size_t ntaps);
+GRHIP_API int grhip_interp_fir_filter_set_mode(grhip_interp_fir_filter *h, int mode);
+GRHIP_API int grhip_interp_fir_filter_history(const grhip_interp_fir_filter *h);
+GRHIP_API int grhip_interp_fir_filter_interpolation(const grhip_interp_fir_filter *h);
+/* work on HOST buffers: in holds noutput_items/I + history() - 1 items; returns noutput_items (0 when it installs
+ * latched taps) */
+GRHIP_API int grhip_interp_fir_filter_work(grhip_interp_fir_filter *h, int noutput_items, const void *in, void *out);
+/* the same on DEVICE buffers, enqueued on `stream` (NULL: the handle's own stream) */
+GRHIP_API int grhip_interp_fir_filter_work_device(grhip_interp_fir_filter *h, int noutput_items, const void *d_in,
+                                                  void *d_out, void *stream);
+/* n_streams fresh captures in one launch: capture s at d_in + s*in_stride_items (n_samples items, the nt - 1 history
+ * zeros implied, NOT in d_in), its I*n_samples outputs at d_out + s*out_stride_items.  *n_out receives I*n_samples;
+ * d_out == NULL only sets it.  Uses the installed taps (a latched set_taps waits for the next work call); positions
+ * are 64-bit, n_samples <= 2^40. */
+GRHIP_API int grhip_interp_fir_filter_run_captures_device(grhip_interp_fir_filter *h, int n_streams, size_t n_samples,
+                                                          const void *d_in, size_t in_stride_items, void *d_out,
+                                                          size_t out_stride_items, size_t *n_out, void *stream);
+
+/* ======================================================================
+ * gr_rational_resampler_base_{ccf,fff,ccc}  (interpolate by I, decimate by D)
+ *   replaces gr_make_rational_resampler_base_XXX(unsigned interpolation, unsigned decimation,
+ *                                                 const std::vector<TAP> &taps)
+ *   filter/gr_rational_resampler_base_XXX.cc.t:49-72 (constructor; relative_rate I/D), 83-120 (set_taps /
+ *   install_taps: the bank of gr_interp_fir_filter_XXX), 135-141 (forecast), 144-172 (general_work: from ctr = d_ctr,
+ *   out[i++] = firs[ctr]->filter(in); ctr += D; while (ctr >= I) { ctr -= I; in++; }; consume_each(in - in0)).
+ * Closed form: output o of a call that starts at ctr = c0 uses filter (c0 + o*D) % I at in + (c0 + o*D) / I; a call of
+ * n outputs consumes (c0 + n*D) / I items and leaves ctr = (c0 + n*D) % I.
+ * history() returns the block's own nt.  The reference's class declares its own d_history / history() /
+ * set_history() (.h.t:51,72-73), which hide gr_block's non-virtual ones: the SCHEDULER-VISIBLE history is 1, there
+ * are no zeros in front of the stream, and the first output reads in[0 .. nt-1] of the raw stream.  nt appears only in
+ * forecast(n) = max(1, (int)((double)(n+1)*D/I) + nt - 1).
+ * The constructor installs the taps; set_taps latches, and the next general_work installs them and returns 0,
+ * consuming nothing (waiting for the handle's earlier launches, as the interpolator).
+ * Refused: interpolation or decimation == 0 -> GRHIP_ERANGE; ntaps == 0 -> GRHIP_EINVAL (outside the reference's
+ * defined behaviour); ninput_items below what the call reads, (c0 + (n-1)*D)/I + nt, or below what it consumes,
+ * (c0 + n*D)/I -> GRHIP_EINVAL (the reference would read or consume past its input); I or D > 2^20 and the kernel
+ * limits of gr_interp_fir_filter -> GRHIP_EINVAL.  Modes as gr_interp_fir_filter.
+ * ====================================================================== */
+typedef struct grhip_rational_resampler_base grhip_rational_resampler_base;
+GRHIP_API int grhip_rational_resampler_base_create(grhip_rational_resampler_base **h, const char *kind,
+                                                   unsigned interpolation, unsigned decimation, const float *taps,
+                                                   size_t ntaps, int device);
+GRHIP_API void grhip_rational_resampler_base_destroy(grhip_rational_resampler_base *h);
+GRHIP_API int grhip_rational_resampler_base_set_taps(grhip_rational_resampler_base *h, const float *taps, size_t ntaps);
+GRHIP_API int grhip_rational_resampler_base_set_mode(grhip_rational_resampler_base *h, int mode);
+GRHIP_API int grhip_rational_resampler_base_history(const grhip_rational_resampler_base *h);
+GRHIP_API int grhip_rational_resampler_base_interpolation(const grhip_rational_resampler_base *h);
+GRHIP_API int grhip_rational_resampler_base_decimation(const grhip_rational_resampler_base *h);
+GRHIP_API int grhip_rational_resampler_base_forecast(const grhip_rational_resampler_base *h, int noutput_items);
+/* general_work on HOST buffers: in[0 .. ninput_items), no history in front; returns the items produced (all
+ * noutput_items, or 0 when it installs latched taps), *consumed the items to consume */
+GRHIP_API int grhip_rational_resampler_base_general_work(grhip_rational_resampler_base *h, int noutput_items,
+                                                         int ninput_items, const void *in, void *out, int *consumed);
+/* the same on DEVICE buffers, enqueued on `stream`; produced and *consumed are known on return (the schedule does not
+ * depend on the data) without a device sync, the outputs once the stream has run */
+GRHIP_API int grhip_rational_resampler_base_general_work_device(grhip_rational_resampler_base *h, int noutput_items,
+                                                                int ninput_items, const void *d_in, void *d_out,
+                                                                int *consumed, void *stream);
+/* n_streams fresh captures (ctr = 0, no zeros in front) in one launch: capture s at d_in + s*in_stride_items
+ * (n_samples items), its outputs at d_out + s*out_stride_items.  *n_out receives the outputs per capture: every o
+ * whose window fits, (o*D)/I + nt <= n_samples.  A real scheduler may stop a few outputs earlier, because forecast asks
+ * for one output more than it produces.  d_out == NULL only sets *n_out.  The handle's ctr is left alone; the installed
+ * taps are used.  Positions are 64-bit, n_samples <= 2^40. */
+GRHIP_API int grhip_rational_resampler_base_run_captures_device(grhip_rational_resampler_base *h, int n_streams,
+                                                                size_t n_samples, const void *d_in,
+                                                                size_t in_stride_items, void *d_out,
+                                                                size_t out_stride_items, size_t *n_out, void *stream);
+
+/* ======================================================================
  * gr_framer_sink_1  (the consumer of the correlator's flag bit)
  *   replaces gr_make_framer_sink_1(gr_msg_queue_sptr target_queue)
  *   general/gr_framer_sink_1.h:62-98, general/gr_framer_sink_1.cc:34-66 (states), 90-190 (work):
