@@ -8,8 +8,10 @@ import numpy as np
 __all__ = [
     "GrhipError", "lib", "lib_path", "strerror", "device_count", "set_default_mode",
     "MODE_FAST", "MODE_GENERIC", "MODE_FAST_VALU", "MODE_FAST_REFTAPS", "WORK_DONE",
-    "fir_filter_ccf", "fir_filter_fff", "fir_filter_ccc", "fir_filter_with_buffer",
-    "freq_xlating_fir_filter_ccc", "quadrature_demod_cf", "xlating_demod",
+    "fir_filter_ccf", "fir_filter_fff", "fir_filter_ccc", "fir_filter_fcc", "fir_filter_scc", "fir_filter_fsf",
+    "fir_filter_with_buffer",
+    "freq_xlating_fir_filter_ccc", "freq_xlating_fir_filter_ccf", "freq_xlating_fir_filter_fcf",
+    "freq_xlating_fir_filter_fcc", "freq_xlating_fir_filter_scf", "freq_xlating_fir_filter_scc", "quadrature_demod_cf", "xlating_demod",
     "clock_recovery_mm_ff", "clock_recovery_mm_cc", "binary_slicer_fb", "correlate_access_code_bb", "pager_slicer_fb", "unpack_k_bits_bb", "framer_sink_1", "framer_sink_1_batch", "stream_to_streams", "streams_to_stream", "vector_to_streams", "stream_to_vector", "head",
     "fft_vcc", "fft_filter_ccc", "pfb_channelizer_ccf", "pfb_decimator_ccf", "pfb_arb_resampler_ccf", "pfb_arb_resampler_fff",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
@@ -256,6 +258,114 @@ class fir_filter_fff(_fir_filter):
 
 class fir_filter_ccc(_fir_filter):
     _kind = "ccc"
+    _tap = np.complex64
+
+
+class fir_filter_fcc(_fir_filter):
+    """gr.fir_filter_fcc: float in, complex out, complex taps"""
+    _kind = "fcc"
+    _in = np.float32
+    _tap = np.complex64
+
+
+class fir_filter_scc(_fir_filter):
+    """gr.fir_filter_scc: short in, complex out, complex taps"""
+    _kind = "scc"
+    _in = np.int16
+    _tap = np.complex64
+
+
+class fir_filter_fsf(_fir_filter):
+    """gr.fir_filter_fsf: float in, short out, float taps"""
+    _kind = "fsf"
+    _in = np.float32
+    _out = np.int16
+
+
+# ----------------------------------------------------------------------------
+# gr.freq_xlating_fir_filter_{ccf,fcf,fcc,scf,scc}: one C handle for the family
+# (filter/gr_freq_xlating_fir_filter_XXX.i.t; the _ccc class below keeps its own entries)
+# ----------------------------------------------------------------------------
+class _freq_xlating_fir_filter(_Block):
+    _destroy = "grhip_freq_xlating_fir_filter_destroy"
+    _kind = None
+    _in = np.complex64
+    _tap = np.float32
+
+    def __init__(self, decimation, taps, center_freq, sampling_freq, device=0):
+        _Block.__init__(self)
+        t = np.ascontiguousarray(taps, dtype=self._tap)
+        self._decim = int(decimation)
+        L = lib()
+        L.grhip_freq_xlating_fir_filter_create.argtypes = [
+            C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_int]
+        _check(L.grhip_freq_xlating_fir_filter_create(C.byref(self._h), self._kind.encode(), self._decim, _ptr(t), len(t),
+                                                      float(center_freq), float(sampling_freq), int(device)))
+
+    def set_center_freq(self, center_freq):
+        L = lib()
+        L.grhip_freq_xlating_fir_filter_set_center_freq.argtypes = [C.c_void_p, C.c_double]
+        _check(L.grhip_freq_xlating_fir_filter_set_center_freq(self._h, float(center_freq)))
+
+    def set_taps(self, taps):
+        t = np.ascontiguousarray(taps, dtype=self._tap)
+        L = lib()
+        L.grhip_freq_xlating_fir_filter_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        _check(L.grhip_freq_xlating_fir_filter_set_taps(self._h, _ptr(t), len(t)))
+
+    def set_mode(self, mode):
+        _check(lib().grhip_freq_xlating_fir_filter_set_mode(self._h, int(mode)))
+
+    def reset(self):
+        _check(lib().grhip_freq_xlating_fir_filter_reset(self._h))
+
+    def history(self):
+        return _check(lib().grhip_freq_xlating_fir_filter_history(self._h))
+
+    def decimation(self):
+        return self._decim
+
+    def work(self, noutput_items, input_items):
+        x = np.ascontiguousarray(input_items, dtype=self._in)
+        need = noutput_items * self._decim + self.history() - 1
+        if len(x) < need:
+            raise ValueError("work needs %d input items, got %d" % (need, len(x)))
+        out = np.zeros(noutput_items, dtype=np.complex64)
+        L = lib()
+        L.grhip_freq_xlating_fir_filter_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        n = _check(L.grhip_freq_xlating_fir_filter_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        return out[:n]
+
+    def work_device(self, noutput_items, d_in, d_out, stream=None):
+        L = lib()
+        L.grhip_freq_xlating_fir_filter_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        return _check(L.grhip_freq_xlating_fir_filter_work_device(self._h, int(noutput_items), _devptr(d_in),
+                                                                  _devptr(d_out), _stream(stream)))
+
+
+class freq_xlating_fir_filter_ccf(_freq_xlating_fir_filter):
+    _kind = "ccf"
+
+
+class freq_xlating_fir_filter_fcf(_freq_xlating_fir_filter):
+    _kind = "fcf"
+    _in = np.float32
+
+
+class freq_xlating_fir_filter_fcc(_freq_xlating_fir_filter):
+    _kind = "fcc"
+    _in = np.float32
+    _tap = np.complex64
+
+
+class freq_xlating_fir_filter_scf(_freq_xlating_fir_filter):
+    _kind = "scf"
+    _in = np.int16
+
+
+class freq_xlating_fir_filter_scc(_freq_xlating_fir_filter):
+    _kind = "scc"
+    _in = np.int16
     _tap = np.complex64
 
 

@@ -105,6 +105,7 @@ int XlatingCore::build(int device)
         cf e = std::exp(cf(0, i * fwT0));
         // complex product in libgcc order (ac - bd, ad + bc)
         float a = proto[i].real(), b = proto[i].imag(), c = e.real(), d = e.imag();
+        if (real_tap_type) { ctaps[i] = cf(a * c, a * d); continue; }       // float * complex
         float ac = a * c, bd = b * d, ad = a * d, bc = b * c;
         ctaps[i] = cf(ac - bd, ad + bc);
     }
@@ -118,6 +119,20 @@ int XlatingCore::build(int device)
     // generic kernel wants d_taps order; after reverse(reverse()) that is ctaps itself
     int rc = upload(d_taps_generic, ctaps.data(), sizeof(cf) * ntaps);
     if (rc) return rc;
+    if (in_kind != 0) {
+        // real items: gr_fir_fcc / gr_fir_scc over the composite taps (c[k] multiplies x[nD + k]: ctaps itself)
+        use_tiled = premix = use_mfma = use_ols = prefer_ols = use_hidec = hidec_premix = false;
+        use_realin = realin_supported(decim, ntaps);
+        if (use_realin) {
+            std::vector<float> hp;
+            ri_Tq = realin_pack_taps((const float *)ctaps.data(), ntaps, decim, hp);
+            rc = upload(d_ri_hp, hp.data(), hp.size() * sizeof(float));
+            if (rc) return rc;
+        }
+        reset();
+        (void)device;
+        return GRHIP_OK;
+    }
 
     bool real_proto = true;
     for (auto &t : proto) if (t.imag() != 0.0f) real_proto = false;
@@ -333,7 +348,7 @@ void XlatingCore::release()
     for (int i = 0; i < 2; ++i) { d_mf_A[i].release(); d_mf_wlane[i].release(); }
     d_mf_stab.release(); d_mf_vtab.release(); mf_sched.release();
     scratch_y.release(); sched.release(); d_ols_tw.release(); d_ols_H.release(); d_hidec_taps.release();
-    d_hidec_etab.release(); d_hidec_vtab.release();
+    d_hidec_etab.release(); d_hidec_vtab.release(); d_ri_hp.release();
 }
 
 // run the FIR + rotator (+ demod) for n_out outputs on device pointers.
@@ -345,6 +360,20 @@ int XlatingCore::run(int mode, const float2 *d_in, long long n_in, long long n_o
 {
     if (n_out <= 0) return GRHIP_OK;
     const float2 *gtab = nullptr;
+    if (in_kind != 0) {
+        // real items: inner FIR with the rotator epilogue, one stream with its history in front
+        if (d_demod || n_streams != 1 || n_lo != 0) return fail(GRHIP_EINVAL, "real-input xlating: one stream, no demodulator");
+        int rc = ensure_rot(n_out, &gtab, st);
+        if (rc) return rc;
+        const bool sh = in_kind == 2;
+        if (mode_fast(mode) && use_realin && !(((uintptr_t)d_y) & 7) && !(((uintptr_t)d_in) & (sh ? 1 : 3)))
+            rc = launch_fir_realin(sh, decim, d_ri_hp.as<float>(), ri_Tq, d_in, n_in, d_y, n_out, gtab, st);
+        else
+            rc = launch_fir_generic(sh ? FIR_SCC : FIR_FCC, d_taps_generic.as<float>(), ntaps, d_in, d_y, n_out, decim, gtab, st);
+        if (rc) return rc;
+        pos += n_out;
+        return GRHIP_OK;
+    }
     const bool demod = d_demod != nullptr;
     const bool batched = !(n_streams == 1 && n_lo == 0);
     const bool mfma_now = mode_matrix(mode) && use_mfma && (n_streams == 1 || !(x_stride & 1));
@@ -513,9 +542,14 @@ struct grhip_fir_filter : HandleBase {
     DevBuf d_mf_A[2];
     SchedBuf mf_sched;
 
-    int tw() const { return kind == FIR_CCC ? 2 : 1; }
-    size_t in_item() const { return kind == FIR_FFF ? 4 : 8; }
-    size_t out_item() const { return kind == FIR_FFF ? 4 : 8; }
+    // real input (fir_realin.hip): fcc / scc FAST; fsf runs the fff engines (ekind) and converts
+    FirKind ekind;                  // the kind whose engines run: kind, or FIR_FFF for FIR_FSF
+    bool use_realin = false;
+    DevBuf d_scratch;               // fsf: the float outputs before the conversion
+
+    int tw() const { return fir_kind_ctaps(kind) ? 2 : 1; }
+    size_t in_item() const { return kind == FIR_SCC ? 2 : (kind == FIR_FFF || kind == FIR_FSF || kind == FIR_FCC) ? 4 : 8; }
+    size_t out_item() const { return kind == FIR_FFF ? 4 : kind == FIR_FSF ? 2 : 8; }
 
     int install(const std::vector<float> &t)
     {
@@ -526,10 +560,20 @@ struct grhip_fir_filter : HandleBase {
             for (int w = 0; w < tw(); ++w) rev[(size_t)k * tw() + w] = taps[(size_t)(ntaps - 1 - k) * tw() + w];
         int rc = upload(d_taps_rev, rev.data(), rev.size() * sizeof(float));
         if (rc) return rc;
+        if (kind == FIR_FCC || kind == FIR_SCC) {
+            use_tiled = use_mfma = use_ols = prefer_ols = use_hidec = false;
+            use_realin = realin_supported(decim, ntaps);
+            if (use_realin) {
+                std::vector<float> hp;
+                Tq = realin_pack_taps(rev.data(), ntaps, decim, hp);
+                rc = upload(d_hp, hp.data(), hp.size() * sizeof(float));
+            }
+            return rc;
+        }
         use_tiled = false;
-        if (ntaps > 0 && (kind != FIR_FFF || decim <= 2)) {
+        if (ntaps > 0 && (ekind != FIR_FFF || decim <= 2)) {
             // float data runs the complex kernel on overlapped pairs at twice the decimation
-            const int dk = kind == FIR_FFF ? 2 * decim : decim;
+            const int dk = ekind == FIR_FFF ? 2 * decim : decim;
             std::vector<float> hp;
             Tq = pack_phase_major(rev.data(), ntaps, tw(), dk, hp);
             if (tiled_supported(dk, Tq)) {
@@ -539,7 +583,7 @@ struct grhip_fir_filter : HandleBase {
             }
         }
         use_mfma = false;
-        if (kind == FIR_CCF && mfma_supported(decim, ntaps) && ntaps / decim >= 24) {
+        if (ekind == FIR_CCF && mfma_supported(decim, ntaps) && ntaps / decim >= 24) {
             rc = build_mfma_taps(rev.data(), ntaps, decim, d_mf_A, &mf_kexp);
             if (rc) return rc;
             use_mfma = true;
@@ -548,15 +592,15 @@ struct grhip_fir_filter : HandleBase {
         if (ntaps >= 48 && ntaps <= OLS_MAX_TAPS && (OLS_N - (ntaps - 1)) / decim >= 1) {
             std::vector<float> ct((size_t)ntaps * 2);
             for (int k = 0; k < ntaps; ++k) {
-                ct[2 * k] = kind == FIR_CCC ? taps[2 * k] : taps[k];
-                ct[2 * k + 1] = kind == FIR_CCC ? taps[2 * k + 1] : 0.f;
+                ct[2 * k] = ekind == FIR_CCC ? taps[2 * k] : taps[k];
+                ct[2 * k + 1] = ekind == FIR_CCC ? taps[2 * k + 1] : 0.f;
             }
             rc = ols_build(ct.data(), ntaps, decim, d_ols_tw, d_ols_H, &ols_L, &ols_fold);
             if (rc) return rc;
             use_ols = true;
         }
         // (crossover between the tiled kernel and the overlap-save engine: ols_crossover above)
-        use_hidec = !use_tiled && kind != FIR_FFF && hidec_wanted(decim, ntaps, kind == FIR_CCC, use_ols);
+        use_hidec = !use_tiled && ekind != FIR_FFF && hidec_wanted(decim, ntaps, ekind == FIR_CCC, use_ols);
         if (use_hidec) {
             std::vector<float> hp2;
             hidec_pad_taps(rev.data(), ntaps, tw(), decim, hp2);
@@ -565,13 +609,33 @@ struct grhip_fir_filter : HandleBase {
         }
         // (float data: the tiled kernel's float-pair mode runs at about 50000 / taps Gsamples/s, the real-data engine at
         // 250-290: the engine where the float-pair mode does not reach, and from 176 taps per phase on)
-        prefer_ols = use_ols && (!use_tiled || ntaps / decim > (kind == FIR_FFF ? 176 : ols_crossover(kind == FIR_CCC, decim)));
+        prefer_ols = use_ols && (!use_tiled || ntaps / decim > (ekind == FIR_FFF ? 176 : ols_crossover(ekind == FIR_CCC, decim)));
         return GRHIP_OK;
     }
 
     int run(const void *d_in, void *d_out, long long n, int dec, hipStream_t st)
     {
         if (n <= 0) return GRHIP_OK;
+        if (kind == FIR_FCC || kind == FIR_SCC) {
+            if (mode_fast(mode) && use_realin && dec == decim && !(((uintptr_t)d_out) & 7) &&
+                !(((uintptr_t)d_in) & (kind == FIR_SCC ? 1 : 3)))
+                return launch_fir_realin(kind == FIR_SCC, dec, d_hp.as<float>(), Tq, d_in, (n - 1) * dec + ntaps, (float2 *)d_out,
+                                         n, nullptr, st);
+            return launch_fir_generic(kind, d_taps_rev.as<float>(), ntaps, d_in, d_out, n, dec, nullptr, st);
+        }
+        if (kind == FIR_FSF) {
+            if (!mode_fast(mode)) return launch_fir_generic(kind, d_taps_rev.as<float>(), ntaps, d_in, d_out, n, dec, nullptr, st);
+            int rc = d_scratch.reserve((size_t)n * sizeof(float));
+            if (!rc) rc = run_engines(d_in, d_scratch.p, n, dec, st);
+            if (!rc) rc = launch_f2s(d_scratch.as<float>(), (short *)d_out, n, st);
+            return rc;
+        }
+        return run_engines(d_in, d_out, n, dec, st);
+    }
+
+    // the engines of fff / ccf / ccc (ekind)
+    int run_engines(const void *d_in, void *d_out, long long n, int dec, hipStream_t st)
+    {
         if (mode_matrix(mode) && use_mfma && dec == decim) {
             FirMfmaArgs a;
             memset(&a, 0, sizeof(a));
@@ -583,7 +647,7 @@ struct grhip_fir_filter : HandleBase {
             a.sched = mf_sched.get();
             return launch_fir_mfma(dec, ntaps, false, EPI_NONE, a, st);
         }
-        if (mode_fast(mode) && use_tiled && !prefer_ols && dec == decim && (kind != FIR_FFF || n >= 2)) {
+        if (mode_fast(mode) && use_tiled && !prefer_ols && dec == decim && (ekind != FIR_FFF || n >= 2)) {
             FirTiledArgs a;
             memset(&a, 0, sizeof(a));
             a.x = (const float2 *)d_in; a.n_in = (n - 1) * dec + ntaps;
@@ -591,22 +655,22 @@ struct grhip_fir_filter : HandleBase {
             a.y_out = (float2 *)d_out;
             a.vec_store = (((uintptr_t)d_out) & 15) == 0;
             a.sched = sched.get();
-            if (kind != FIR_FFF) return launch_fir_tiled(dec, kind == FIR_CCC, false, EPI_NONE, a, 1, st);
+            if (ekind != FIR_FFF) return launch_fir_tiled(dec, ekind == FIR_CCC, false, EPI_NONE, a, 1, st);
             // gr_fir_fff: output pairs (y[2j], y[2j+1]); an odd last output goes through the generic kernel
             a.fpair = dec;
             a.n_out = n / 2;
             int rc = launch_fir_tiled(2 * dec, false, false, EPI_NONE, a, 1, st);
             if (rc || !(n & 1)) return rc;
-            return launch_fir_generic(kind, d_taps_rev.as<float>(), ntaps, (const float *)d_in + (n - 1) * dec,
+            return launch_fir_generic(ekind, d_taps_rev.as<float>(), ntaps, (const float *)d_in + (n - 1) * dec,
                                       (float *)d_out + (n - 1), 1, dec, nullptr, st);
         }
         if (mode_fast(mode) && use_hidec && dec == decim)
-            return launch_fir_hidec(kind == FIR_CCC, d_hidec_taps.as<float>(), ntaps, dec, (const float2 *)d_in,
+            return launch_fir_hidec(ekind == FIR_CCC, d_hidec_taps.as<float>(), ntaps, dec, (const float2 *)d_in,
                                     (n - 1) * dec + ntaps, (float2 *)d_out, n, nullptr, st);
         if (mode_fast(mode) && use_ols && (prefer_ols || !use_tiled) && dec == decim) {
             // y[n] = sum_k taps[k] x[nD + ntaps-1-k]: the ntaps-1 history items in front of d_in are the
             // engine's "previous call" samples, the rest is the stream
-            if (kind == FIR_FFF) {
+            if (ekind == FIR_FFF) {
                 const float *xf = (const float *)d_in;
                 return launch_fftfilt4096_real(xf + (ntaps - 1), (n - 1) * dec + 1, xf, ntaps, d_ols_tw.as<float2>(),
                                                d_ols_H.as<float2>(), (float *)d_out, n, dec, ols_L, ols_fold, st);
@@ -616,7 +680,7 @@ struct grhip_fir_filter : HandleBase {
             return launch_fftfilt4096(x + (ntaps - 1), (n - 1) * dec + 1, x, ntaps, d_ols_tw.as<float2>(),
                                       d_ols_H.as<float2>(), (float2 *)d_out, n, dec, ols_L, ols_fold, st);
         }
-        return launch_fir_generic(kind, d_taps_rev.as<float>(), ntaps, d_in, d_out, n, dec, nullptr, st);
+        return launch_fir_generic(ekind, d_taps_rev.as<float>(), ntaps, d_in, d_out, n, dec, nullptr, st);
     }
 };
 
@@ -631,15 +695,18 @@ int grhip_fir_filter_create(grhip_fir_filter **h, const char *kind, int decimati
     if (!strcmp(kind, "ccf")) k = FIR_CCF;
     else if (!strcmp(kind, "fff")) k = FIR_FFF;
     else if (!strcmp(kind, "ccc")) k = FIR_CCC;
+    else if (!strcmp(kind, "fcc")) k = FIR_FCC;
+    else if (!strcmp(kind, "scc")) k = FIR_SCC;
+    else if (!strcmp(kind, "fsf")) k = FIR_FSF;
     else return fail(GRHIP_EINVAL, "unknown FIR kind '%s'", kind);
     if (decimation < 1) return fail(GRHIP_EINVAL, "decimation must be >= 1");
     if (ntaps && !taps) return fail(GRHIP_EINVAL, "taps is NULL");
     grhip_fir_filter *f = new (std::nothrow) grhip_fir_filter();
     if (!f) return fail(GRHIP_ENOMEM, "alloc");
-    f->kind = k; f->decim = decimation; f->mode = default_mode();
+    f->kind = k; f->ekind = k == FIR_FSF ? FIR_FFF : k; f->decim = decimation; f->mode = default_mode();
     int rc = f->init_device(device);
     if (!rc) rc = f->install(std::vector<float>(taps, taps + ntaps * f->tw()));
-    if (rc) { f->d_taps_rev.release(); f->d_hp.release(); f->sched.release(); f->d_ols_tw.release(); f->d_ols_H.release(); f->d_hidec_taps.release(); f->d_mf_A[0].release(); f->d_mf_A[1].release(); f->mf_sched.release(); f->destroy_base(); delete f; return rc; }
+    if (rc) { f->d_taps_rev.release(); f->d_hp.release(); f->sched.release(); f->d_ols_tw.release(); f->d_ols_H.release(); f->d_hidec_taps.release(); f->d_mf_A[0].release(); f->d_mf_A[1].release(); f->mf_sched.release(); f->d_scratch.release(); f->destroy_base(); delete f; return rc; }
     *h = f;
     return GRHIP_OK;
 }
@@ -649,7 +716,7 @@ void grhip_fir_filter_destroy(grhip_fir_filter *h)
     if (!h) return;
     (void)hipSetDevice(h->device);
     h->d_taps_rev.release(); h->d_hp.release(); h->sched.release(); h->d_ols_tw.release(); h->d_ols_H.release(); h->d_hidec_taps.release();
-    h->d_mf_A[0].release(); h->d_mf_A[1].release(); h->mf_sched.release();
+    h->d_mf_A[0].release(); h->d_mf_A[1].release(); h->mf_sched.release(); h->d_scratch.release();
     h->destroy_base();
     delete h;
 }
@@ -1268,6 +1335,176 @@ int grhip_xlating_demod_work(grhip_xlating_demod *h, int noutput_items, const vo
     rc = grhip_xlating_demod_work_device(h, noutput_items, h->stage_in.p, h->stage_out.p, st);
     if (rc < 0) return rc;
     GRHIP_D2H(h, out, h->stage_out.p, (size_t)n * 4, st);
+    GRHIP_HIP(hipStreamSynchronize(st));
+    return noutput_items;
+}
+
+}  // extern "C"
+
+// ============================================================================
+// gr_freq_xlating_fir_filter_{ccf,fcf,fcc,scf,scc} (and ccc), one handle for the family
+//   filter/generate_gr_freq_xlating_fir_filter_XXX.py:30 (signatures, FIR_TYPE = gr_fir_ + i_code + cc),
+//   filter/gr_freq_xlating_fir_filter_XXX.cc.t:38-123
+// ============================================================================
+struct grhip_freq_xlating_fir_filter : HandleBase {
+    XlatingCore core;
+    int mode = GRHIP_MODE_FAST;
+    bool ctaps_in = true;           // ?cc: interleaved complex taps; ?cf: float taps
+    size_t in_item = 8;
+    std::vector<cf> new_proto; double new_center_freq = 0; bool updated = false;
+
+    void set_proto(std::vector<cf> &dst, const float *taps, size_t ntaps) const
+    {
+        if (ctaps_in) dst.assign((const cf *)taps, (const cf *)taps + ntaps);
+        else {
+            dst.resize(ntaps);
+            for (size_t i = 0; i < ntaps; ++i) dst[i] = cf(taps[i], 0.f);
+        }
+    }
+};
+
+extern "C" {
+
+int grhip_freq_xlating_fir_filter_create(grhip_freq_xlating_fir_filter **h, const char *kind, int decimation,
+                                         const float *taps, size_t ntaps, double center_freq, double sampling_freq,
+                                         int device)
+{
+    if (!h || !kind) return fail(GRHIP_EINVAL, "null argument");
+    *h = nullptr;
+    int in_kind;
+    bool ctaps_in;
+    if (!strcmp(kind, "ccc")) { in_kind = 0; ctaps_in = true; }
+    else if (!strcmp(kind, "ccf")) { in_kind = 0; ctaps_in = false; }
+    else if (!strcmp(kind, "fcf")) { in_kind = 1; ctaps_in = false; }
+    else if (!strcmp(kind, "fcc")) { in_kind = 1; ctaps_in = true; }
+    else if (!strcmp(kind, "scf")) { in_kind = 2; ctaps_in = false; }
+    else if (!strcmp(kind, "scc")) { in_kind = 2; ctaps_in = true; }
+    else return fail(GRHIP_EINVAL, "unknown freq_xlating kind '%s'", kind);
+    int rc = xlating_args_ok(decimation, taps, ntaps, sampling_freq);
+    if (rc) return rc;
+    auto *x = new (std::nothrow) grhip_freq_xlating_fir_filter();
+    if (!x) return fail(GRHIP_ENOMEM, "alloc");
+    x->mode = default_mode();
+    x->ctaps_in = ctaps_in;
+    x->in_item = in_kind == 0 ? 8 : in_kind == 1 ? 4 : 2;
+    rc = x->init_device(device);
+    if (!rc) {
+        x->core.decim = decimation;
+        x->core.in_kind = in_kind;
+        x->core.real_tap_type = !ctaps_in;
+        x->set_proto(x->core.proto, taps, ntaps);
+        x->core.center_freq = center_freq; x->core.sampling_freq = sampling_freq;
+        rc = x->core.build(device);
+    }
+    if (rc) { x->core.release(); x->destroy_base(); delete x; return rc; }
+    *h = x;
+    return GRHIP_OK;
+}
+
+void grhip_freq_xlating_fir_filter_destroy(grhip_freq_xlating_fir_filter *h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    h->core.release();
+    h->destroy_base();
+    delete h;
+}
+
+int grhip_freq_xlating_fir_filter_set_center_freq(grhip_freq_xlating_fir_filter *h, double center_freq)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    std::lock_guard<std::mutex> lk(h->setter_mutex);
+    if (!h->updated) h->new_proto = h->core.proto;
+    h->new_center_freq = center_freq;
+    h->updated = true;
+    return GRHIP_OK;
+}
+
+int grhip_freq_xlating_fir_filter_set_taps(grhip_freq_xlating_fir_filter *h, const float *taps, size_t ntaps)
+{
+    if (!h || (ntaps && !taps)) return fail(GRHIP_EINVAL, "null argument");
+    std::lock_guard<std::mutex> lk(h->setter_mutex);
+    if (!h->updated) h->new_center_freq = h->core.center_freq;
+    h->set_proto(h->new_proto, taps, ntaps);
+    h->updated = true;
+    return GRHIP_OK;
+}
+
+int grhip_freq_xlating_fir_filter_set_mode(grhip_freq_xlating_fir_filter *h, int mode)
+{
+    if (!h || !mode_valid(mode)) return fail(GRHIP_EINVAL, "bad mode");
+    h->mode = mode;
+    return GRHIP_OK;
+}
+
+int grhip_freq_xlating_fir_filter_history(const grhip_freq_xlating_fir_filter *h)
+{
+    return h ? (h->core.ntaps > 0 ? h->core.ntaps : 1) : GRHIP_EINVAL;
+}
+
+int grhip_freq_xlating_fir_filter_decimation(const grhip_freq_xlating_fir_filter *h) { return h ? h->core.decim : GRHIP_EINVAL; }
+
+int grhip_freq_xlating_fir_filter_reset(grhip_freq_xlating_fir_filter *h)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    h->core.reset();
+    return GRHIP_OK;
+}
+
+// as xl_apply_update: set_history; build_composite_fir(); return 0 once (.cc.t:109-114), rotator phase and counter kept
+static int xlf_apply_update(grhip_freq_xlating_fir_filter *h, hipStream_t st)
+{
+    std::lock_guard<std::mutex> lk(h->setter_mutex);
+    if (!h->updated) return 0;
+    GRHIP_HIP(hipStreamSynchronize(st));
+    if (st != h->own_stream) GRHIP_HIP(hipStreamSynchronize(h->own_stream));
+    h->core.proto = h->new_proto;
+    h->core.center_freq = h->new_center_freq;
+    int rc = h->core.rebuild_keep_phase(h->device);
+    if (rc) return rc;
+    h->updated = false;
+    return 1;
+}
+
+int grhip_freq_xlating_fir_filter_work_device(grhip_freq_xlating_fir_filter *h, int noutput_items, const void *d_in,
+                                              void *d_out, void *stream)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
+    int rc = h->bind();
+    if (rc) return rc;
+    rc = xlf_apply_update(h, h->pick(stream));
+    if (rc < 0) return rc;
+    if (rc == 1) return 0;
+    long long n = noutput_items;
+    long long n_in = n > 0 ? (n - 1) * h->core.decim + h->core.ntaps : 0;
+    rc = h->core.run(h->mode, (const float2 *)d_in, n_in, n, (float2 *)d_out, nullptr, 0.f, nullptr, nullptr, nullptr,
+                     h->pick(stream));
+    return rc ? rc : noutput_items;
+}
+
+int grhip_freq_xlating_fir_filter_work(grhip_freq_xlating_fir_filter *h, int noutput_items, const void *in, void *out)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
+    int rc = h->bind();
+    if (rc) return rc;
+    rc = xlf_apply_update(h, h->own_stream);
+    if (rc < 0) return rc;
+    if (rc == 1) return 0;
+    if (noutput_items == 0) return 0;
+    long long n = noutput_items;
+    size_t n_in = (size_t)((n - 1) * h->core.decim + h->core.ntaps);
+    if (n_in == 0) n_in = 1;
+    const size_t it = h->in_item;
+    if ((rc = h->stage_in.reserve(n_in * it + 16))) return rc;
+    if ((rc = h->stage_out.reserve((size_t)n * 8))) return rc;
+    hipStream_t st = h->own_stream;
+    GRHIP_H2D(h, h->stage_in.p, in, n_in * it, st);
+    rc = h->core.run(h->mode, h->stage_in.as<float2>(), (long long)n_in, n, h->stage_out.as<float2>(), nullptr, 0.f, nullptr,
+                     nullptr, nullptr, st);
+    if (rc) return rc;
+    GRHIP_D2H(h, out, h->stage_out.p, (size_t)n * 8, st);
     GRHIP_HIP(hipStreamSynchronize(st));
     return noutput_items;
 }

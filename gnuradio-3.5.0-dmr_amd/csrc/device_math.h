@@ -21,6 +21,14 @@ __device__ __forceinline__ float2 cmul_fma(float2 a, float2 b)
     return make_float2(__builtin_fmaf(a.x, b.x, -(a.y * b.y)), __builtin_fmaf(a.x, b.y, a.y * b.x));
 }
 
+// (short)f as the reference's x86-64 build converts: cvttss2si to int32 (NaN and |f| >= 2^31 give 0x80000000), then
+// the low 16 bits.  v_cvt_i32_f32 saturates instead, so those inputs are taken out first.
+__host__ __device__ __forceinline__ short ref_f2s(float f)
+{
+    const int v = (f < 2147483648.f && f > -2147483648.f) ? (int)f : 0;
+    return (short)(unsigned short)(unsigned)v;
+}
+
 // the same product as cmul_fma in two packed instructions: the halves of the operands
 // are routed with op_sel and the one negation is an operand modifier, so nothing is
 // moved or sign-flipped beforehand

@@ -6,11 +6,14 @@
 
 namespace grhip {
 
-enum FirKind { FIR_FFF = 0, FIR_CCF = 1, FIR_CCC = 2 };
+enum FirKind { FIR_FFF = 0, FIR_CCF = 1, FIR_CCC = 2, FIR_FCC = 3, FIR_SCC = 4, FIR_FSF = 5 };
+// complex taps (interleaved): ccc and the real-input kinds with complex output
+inline bool fir_kind_ctaps(FirKind k) { return k == FIR_CCC || k == FIR_FCC || k == FIR_SCC; }
 
 // ---- (A) generic-order kernel: bit-exact gr_fir_XXX_generic -----------------
 // taps_rev: device, d_taps order (reversed forward taps); complex interleaved
-// for CCC.  in: device, item 0 = input[0] of output 0.  Any decimation.
+// for CCC / FCC / SCC.  FCC / SCC read float / int16 items and write complex ones, FSF reads float and writes
+// int16 (the x86-64 conversion, ref_f2s in device_math.h).  in: device, item 0 = input[0] of output 0.  Any decimation.
 // epilogue: if gtab != nullptr (complex kinds) out[n] = rotate(out[n], gtab[n])
 // with the reference's unfused complex product (gr_rotator.h:43).
 // seq: one accumulator, terms in order (gri_fir_filter_with_buffer_XXX.cc.t:75-79) instead of the unrolled order
@@ -122,6 +125,18 @@ int launch_fir_hidec_demod(const float *taps_padded, int ntaps, int decim, const
 int launch_fir_hidec(bool ctaps, const float *taps_padded, int ntaps, int decim, const float2 *x, long long n_in, float2 *y,
                      long long n_out, const float2 *gtab, hipStream_t st, const float2 *etab = nullptr,
                      const float2 *vtab = nullptr);
+
+// ---- (B3) real-input FIR (fir_realin.hip): float / int16 items, complex taps --------------------------------
+// gr_fir_fcc / gr_fir_scc and the inner FIR of the real-input freq_xlating kinds.  Decimation 1 / 2 / 4 / 8, up to
+// 1024 taps (realin_supported); other shapes run the generic-order kernel.  c (complex interleaved) multiplies x[nD + k];
+// realin_pack_taps lays it out phase-major (returns Tq, taps per phase).  x item 0 = input[0] of output 0, n_in items
+// readable, only 4-byte (float) / 2-byte (int16) alignment needed.  gtab != null: rotator epilogue (gr_rotator.h:43).
+bool realin_supported(int decim, int ntaps);
+int realin_pack_taps(const float *c, int ntaps, int decim, std::vector<float> &hp);
+int launch_fir_realin(bool in_short, int decim, const float *hp, int Tq, const void *x, long long n_in, float2 *y,
+                      long long n_out, const float2 *gtab, hipStream_t st);
+// o[i] = (short)a[i] as the reference's x86-64 build converts (gr_fir_fsf's FAST form: float engines + this pass)
+int launch_f2s(const float *a, short *o, long long n, hipStream_t st);
 
 // in-place rotator multiply with a phase table (gr_rotator.h:43)
 int launch_rotate(float2 *y, const float2 *gtab, long long n, hipStream_t st);

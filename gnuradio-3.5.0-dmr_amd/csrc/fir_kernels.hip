@@ -39,11 +39,54 @@ fir_generic_kernel(const float *__restrict__ taps_rev, int ntaps, const float *_
                    const float2 *__restrict__ gtab)
 {
     extern __shared__ __attribute__((aligned(16))) float s_taps[];
-    const int tw = (KIND == FIR_CCC) ? 2 : 1;
+    const int tw = (KIND == FIR_CCC || KIND == FIR_FCC || KIND == FIR_SCC) ? 2 : 1;
     for (int i = threadIdx.x; i < ntaps * tw; i += blockDim.x) s_taps[i] = taps_rev[i];
     __syncthreads();
     long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_out) return;
+
+    if (KIND == FIR_FCC || KIND == FIR_SCC) {
+        // real input, complex taps, complex accumulators: N_UNROLL 2 (.cc.t:59-79 as generate_gr_fir_XXX.py:31-66
+        // expands it); each product is complex * float = (tr*x, ti*x), scc's input cast with (float) (exact)
+        const float2 *tc = (const float2 *)s_taps;
+        const long long b = n * decim;
+        auto ld = [&](int i) -> float {
+            return KIND == FIR_SCC ? (float)((const short *)in)[b + i] : in[b + i];
+        };
+        float a0r = 0, a0i = 0, a1r = 0, a1i = 0;
+        int i = 0, nn = (ntaps / 2) * 2;
+        for (i = 0; i < nn; i += 2) {
+            const float x0 = ld(i), x1 = ld(i + 1);
+            float pr = tc[i].x * x0, pi = tc[i].y * x0;
+            a0r += pr; a0i += pi;
+            pr = tc[i + 1].x * x1; pi = tc[i + 1].y * x1;
+            a1r += pr; a1i += pi;
+        }
+        for (; i < ntaps; i++) {
+            const float x0 = ld(i);
+            const float pr = tc[i].x * x0, pi = tc[i].y * x0;
+            a0r += pr; a0i += pi;
+        }
+        float2 y = make_float2(a0r + a1r, a0i + a1i);
+        if (gtab) y = cmul_ref(y, gtab[n]);     // gr_rotator::rotate: z = in * d_phase
+        ((float2 *)out)[n] = y;
+        return;
+    }
+    if (KIND == FIR_FSF) {
+        // float accumulators, N_UNROLL 4 as fff, then (short) of the sum as the reference's x86-64 build converts
+        const float *x = in + n * decim;
+        float acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
+        int i = 0, nn = (ntaps / 4) * 4;
+        for (i = 0; i < nn; i += 4) {
+            acc0 += s_taps[i + 0] * x[i + 0];
+            acc1 += s_taps[i + 1] * x[i + 1];
+            acc2 += s_taps[i + 2] * x[i + 2];
+            acc3 += s_taps[i + 3] * x[i + 3];
+        }
+        for (; i < ntaps; i++) acc0 += s_taps[i] * x[i];
+        ((short *)out)[n] = ref_f2s(acc0 + acc1 + acc2 + acc3);
+        return;
+    }
 
     if (SEQ) {
         if (KIND == FIR_FFF) {
@@ -549,7 +592,7 @@ static int launch_generic_inst(const float *taps_rev, int ntaps, const void *in,
 // 16-byte loads: the stream on an 8-byte boundary is served by the range check only if it starts on a 16-byte one)
 static bool generic_tiled_ok(FirKind kind, int ntaps, const void *in, long long n_out, int decim)
 {
-    return kind != FIR_FFF && ntaps >= 8 && n_out >= 2 * GT_NT && decim >= 1 && decim <= 16 &&
+    return (kind == FIR_CCF || kind == FIR_CCC) && ntaps >= 8 && n_out >= 2 * GT_NT && decim >= 1 && decim <= 16 &&
            (size_t)decim * (GT_NT + ntaps / decim + 3) * 8 + (size_t)ntaps * 8 + 64 <= 150 * 1024 && (((uintptr_t)in) & 15) == 0 &&
            ((n_out - 1) * decim + ntaps) * 8 < 0x7ffffff0ll;
 }
@@ -591,15 +634,39 @@ int launch_fir_generic(FirKind kind, const float *taps_rev, int ntaps, const voi
                        long long n_out, int decim, const float2 *gtab, hipStream_t st, bool seq)
 {
     if (n_out <= 0) return GRHIP_OK;
-    size_t sh = (size_t)(ntaps > 0 ? ntaps : 1) * (kind == FIR_CCC ? 8 : 4);
+    size_t sh = (size_t)(ntaps > 0 ? ntaps : 1) * (fir_kind_ctaps(kind) ? 8 : 4);
     if (sh > 160 * 1024 - 256) return fail(GRHIP_EINVAL, "generic FIR: %d taps exceed LDS", ntaps);
     if (seq) {
         if (gtab) return fail(GRHIP_EINVAL, "sequential-order FIR has no rotator epilogue");
         switch (kind) {
         case FIR_FFF: return launch_generic_inst<FIR_FFF, true>(taps_rev, ntaps, in, out, n_out, decim, sh, st);
         case FIR_CCF: return launch_generic_inst<FIR_CCF, true>(taps_rev, ntaps, in, out, n_out, decim, sh, st);
-        default: return launch_generic_inst<FIR_CCC, true>(taps_rev, ntaps, in, out, n_out, decim, sh, st);
+        case FIR_CCC: return launch_generic_inst<FIR_CCC, true>(taps_rev, ntaps, in, out, n_out, decim, sh, st);
+        default: return fail(GRHIP_EINVAL, "sequential-order FIR: no such kind");
         }
+    }
+    // real-input kinds: one output per lane (gtab: the rotator epilogue of the real-input xlating kinds)
+    if (kind == FIR_FCC || kind == FIR_SCC || kind == FIR_FSF) {
+        if (gtab && kind == FIR_FSF) return fail(GRHIP_EINVAL, "fsf has no rotator epilogue");
+        dim3 grid((unsigned)((n_out + 255) / 256)), block(256);
+        if (kind == FIR_FCC) {
+            if (sh > 64 * 1024)
+                GRHIP_HIP(hipFuncSetAttribute((const void *)fir_generic_kernel<FIR_FCC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+            hipLaunchKernelGGL(fir_generic_kernel<FIR_FCC>, grid, block, sh, st, taps_rev, ntaps, (const float *)in, (float *)out, n_out,
+                               decim, gtab);
+        } else if (kind == FIR_SCC) {
+            if (sh > 64 * 1024)
+                GRHIP_HIP(hipFuncSetAttribute((const void *)fir_generic_kernel<FIR_SCC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+            hipLaunchKernelGGL(fir_generic_kernel<FIR_SCC>, grid, block, sh, st, taps_rev, ntaps, (const float *)in, (float *)out, n_out,
+                               decim, gtab);
+        } else {
+            if (sh > 64 * 1024)
+                GRHIP_HIP(hipFuncSetAttribute((const void *)fir_generic_kernel<FIR_FSF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
+            hipLaunchKernelGGL(fir_generic_kernel<FIR_FSF>, grid, block, sh, st, taps_rev, ntaps, (const float *)in, (float *)out, n_out,
+                               decim, gtab);
+        }
+        GRHIP_HIP(hipGetLastError());
+        return GRHIP_OK;
     }
     // the tiled form of the same arithmetic wherever it applies: complex data, a tile's worth of outputs, a decimation
     // and a tap count whose tile fits LDS (16-byte loads: the stream on an 8-byte boundary is served by the range check

@@ -27,6 +27,15 @@ struct XlatingCore {
     // engines with a fused demodulator -- they need no rotator phases, whose exact recurrence is computed on the host at
     // ~3 ns per output and bounds a STREAMING block on any other path (measured: 1-8 Gsamples/s against 200-320)
     bool for_demod = false;
+    // set before build(): the items the handle reads -- 0 complex (ccc, ccf), 1 float (fcf, fcc), 2 int16 (scf, scc).
+    // Real items run the inner gr_fir_fcc / gr_fir_scc (fir_realin.hip, or the generic-order kernel) + rotator table;
+    // build() then skips the complex-input engines' tables
+    int in_kind = 0;
+    // set before build(): the prototype taps are float (?cf kinds), so proto[i] * exp(...) is float * complex = (a*c, a*d)
+    bool real_tap_type = false;
+    bool use_realin = false;
+    int ri_Tq = 0;
+    DevBuf d_ri_hp;
     // built by build()
     int ntaps = 0;
     std::vector<std::complex<float>> ctaps;     // composite taps, reference arithmetic

@@ -8,7 +8,7 @@
 //   gr_sync_interpolator gnuradio-core/src/lib/runtime/gr_sync_interpolator.cc:30-75
 //   gr_io_signature     gnuradio-core/src/lib/runtime/gr_io_signature.h
 //   gr_message / gr_msg_queue  gnuradio-core/src/lib/runtime/gr_message.h:36-81, gr_msg_queue.h:36-86
-//   gr_fir_{ccf,fff,ccc}, gr_fir_XXX_info   gnuradio-core/src/lib/filter/gr_fir_XXX.h.t:48-122,
+//   gr_fir_{ccf,fff,ccc,fcc,scc,fsf}, gr_fir_XXX_info   gnuradio-core/src/lib/filter/gr_fir_XXX.h.t:48-122,
 //                                           filter/generate_gr_fir_util.py:25-32 (the kernel-level seam)
 //   gr_fft_vcc (abstract base)              gnuradio-core/src/lib/general/gr_fft_vcc.h:41-59, gr_fft_vcc.cc:40-64
 // When building against a real GNU Radio 3.5 tree define GRHIP_USE_GNURADIO and
@@ -19,7 +19,10 @@
 #include <gr_fft_vcc.h>
 #include <gr_fir_ccc.h>
 #include <gr_fir_ccf.h>
+#include <gr_fir_fcc.h>
 #include <gr_fir_fff.h>
+#include <gr_fir_fsf.h>
+#include <gr_fir_scc.h>
 #include <gr_fir_util.h>
 #include <gr_block.h>
 #include <gr_io_signature.h>
@@ -268,6 +271,9 @@ template <class T> inline std::vector<T> gr_reverse(const std::vector<T> &v) { r
 GRHIP_SHIM_FIR(gr_fir_ccf, gr_complex, gr_complex, float)
 GRHIP_SHIM_FIR(gr_fir_fff, float, float, float)
 GRHIP_SHIM_FIR(gr_fir_ccc, gr_complex, gr_complex, gr_complex)
+GRHIP_SHIM_FIR(gr_fir_fcc, float, gr_complex, gr_complex)
+GRHIP_SHIM_FIR(gr_fir_scc, short, gr_complex, gr_complex)
+GRHIP_SHIM_FIR(gr_fir_fsf, float, short, float)
 
 // ---- gr_fft_vcc: the abstract base that holds size / window / direction (general/gr_fft_vcc.h:41-59) ----
 class gr_fft_vcc : public gr_sync_block {

@@ -5,6 +5,7 @@
 //
 //   grhip_fir_filter_ccf / _fff / _ccc      <- gr_fir_filter_XXX   (filter/gr_fir_filter_XXX.h.t:36-66)
 //   grhip_freq_xlating_fir_filter_ccc        <- gr_freq_xlating_fir_filter_ccc (.h.t:64-99)
+//   grhip_freq_xlating_fir_filter_{ccf,fcf,fcc,scf,scc} <- gr_freq_xlating_fir_filter_XXX (the family handle)
 //   grhip_quadrature_demod_cf                <- gr_quadrature_demod_cf (general/gr_quadrature_demod_cf.h)
 //   grhip_clock_recovery_mm_ff               <- digital_clock_recovery_mm_ff (gr-digital/include/...h:44-92)
 //   grhip_binary_slicer_fb                   <- digital_binary_slicer_fb
@@ -103,6 +104,55 @@ public:
 GRHIP_FIR_CLASS(grhip_fir_filter_ccf, fir_filter_ccf, gr_complex, gr_complex, float)
 GRHIP_FIR_CLASS(grhip_fir_filter_fff, fir_filter_fff, float, float, float)
 GRHIP_FIR_CLASS(grhip_fir_filter_ccc, fir_filter_ccc, gr_complex, gr_complex, gr_complex)
+GRHIP_FIR_CLASS(grhip_fir_filter_fcc, fir_filter_fcc, float, gr_complex, gr_complex)
+GRHIP_FIR_CLASS(grhip_fir_filter_scc, fir_filter_scc, short, gr_complex, gr_complex)
+GRHIP_FIR_CLASS(grhip_fir_filter_fsf, fir_filter_fsf, float, short, float)
+
+// ---------------------------------------------------------------------------
+// gr_freq_xlating_fir_filter_{ccf,fcf,fcc,scf,scc}: one template over the family handle
+// (filter/gr_freq_xlating_fir_filter_XXX.cc.t:38-123; _ccc keeps its own class below)
+// ---------------------------------------------------------------------------
+template <class IN, class TAP> class grhip_freq_xlating_fir_filter_blk : public gr_sync_decimator {
+    grhip_freq_xlating_fir_filter *d_h = nullptr;
+public:
+    grhip_freq_xlating_fir_filter_blk(const char *name, const char *kind, int decimation, const std::vector<TAP> &taps,
+                                      double center_freq, double sampling_freq, int device)
+        : gr_sync_decimator(name, gr_make_io_signature(1, 1, sizeof(IN)), gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                            decimation)
+    {
+        grhip_detail::check(grhip_freq_xlating_fir_filter_create(&d_h, kind, decimation, (const float *)taps.data(),
+                                                                 taps.size(), center_freq, sampling_freq, device));
+        set_history(grhip_freq_xlating_fir_filter_history(d_h));
+    }
+    ~grhip_freq_xlating_fir_filter_blk() { grhip_freq_xlating_fir_filter_destroy(d_h); }
+    void set_center_freq(double f) { grhip_detail::check(grhip_freq_xlating_fir_filter_set_center_freq(d_h, f)); }
+    void set_taps(const std::vector<TAP> &taps)
+    {
+        grhip_detail::check(grhip_freq_xlating_fir_filter_set_taps(d_h, (const float *)taps.data(), taps.size()));
+    }
+    void set_mode(int mode) { grhip_detail::check(grhip_freq_xlating_fir_filter_set_mode(d_h, mode)); }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int r = grhip_freq_xlating_fir_filter_work(d_h, noutput_items, in[0], out[0]);
+        grhip_detail::check(r);
+        if (r == 0) set_history(grhip_freq_xlating_fir_filter_history(d_h));   // set_history(ntaps), return 0 (.cc.t:109-114)
+        return r;
+    }
+};
+#define GRHIP_XLATING_CLASS(SUF, IN, TAP)                                                                          \
+    typedef grhip_freq_xlating_fir_filter_blk<IN, TAP> grhip_freq_xlating_fir_filter_##SUF##_blk;                  \
+    typedef boost::shared_ptr<grhip_freq_xlating_fir_filter_##SUF##_blk> grhip_freq_xlating_fir_filter_##SUF##_sptr; \
+    inline grhip_freq_xlating_fir_filter_##SUF##_sptr grhip_make_freq_xlating_fir_filter_##SUF(                     \
+        int decimation, const std::vector<TAP> &taps, double center_freq, double sampling_freq, int device = 0)     \
+    {                                                                                                              \
+        return gnuradio::get_initial_sptr(new grhip_freq_xlating_fir_filter_##SUF##_blk(                          \
+            "freq_xlating_fir_filter_" #SUF, #SUF, decimation, taps, center_freq, sampling_freq, device));        \
+    }
+GRHIP_XLATING_CLASS(ccf, gr_complex, float)
+GRHIP_XLATING_CLASS(fcf, float, float)
+GRHIP_XLATING_CLASS(fcc, float, gr_complex)
+GRHIP_XLATING_CLASS(scf, short, float)
+GRHIP_XLATING_CLASS(scc, short, gr_complex)
 
 // ---------------------------------------------------------------------------
 // gr_freq_xlating_fir_filter_ccc

@@ -1,7 +1,7 @@
 // grhip_fir_kernels.h -- the reference's KERNEL-level plug-in seams filled in for gfx950 (SURVEY 8b seams 2 and 3,
 // 8a row a14), plus the N-port adapter blocks:
 //
-//   gr_fir_{ccf,fff,ccc}_hip : gr_fir_{ccf,fff,ccc}     filter / filterN / filterNdec through the C ABI
+//   gr_fir_{ccf,fff,ccc,fcc,scc,fsf}_hip : gr_fir_XXX     filter / filterN / filterNdec through the C ABI
 //                                                       (filter/gr_fir_XXX.h.t:48-122)
 //   grhip_fir_sysconfig::get_gr_fir_XXX_info / create   one more `info{name, create}` entry, "hip-gfx950", as every
 //                                                       platform's gr_fir_sysconfig adds its own
@@ -49,6 +49,9 @@
 GRHIP_FIR_IMPL(gr_fir_ccf_hip, gr_fir_ccf, "ccf", gr_complex, gr_complex, float)
 GRHIP_FIR_IMPL(gr_fir_fff_hip, gr_fir_fff, "fff", float, float, float)
 GRHIP_FIR_IMPL(gr_fir_ccc_hip, gr_fir_ccc, "ccc", gr_complex, gr_complex, gr_complex)
+GRHIP_FIR_IMPL(gr_fir_fcc_hip, gr_fir_fcc, "fcc", float, gr_complex, gr_complex)
+GRHIP_FIR_IMPL(gr_fir_scc_hip, gr_fir_scc, "scc", short, gr_complex, gr_complex)
+GRHIP_FIR_IMPL(gr_fir_fsf_hip, gr_fir_fsf, "fsf", float, short, float)
 
 // what a platform's gr_fir_sysconfig does for its implementations (filter/gr_fir_sysconfig_x86.cc:175-201, 260-300):
 // create_gr_fir_XXX picks the best one, get_gr_fir_XXX_info APPENDS to the table the base class started
@@ -67,6 +70,21 @@ struct grhip_fir_sysconfig {
     static void get_gr_fir_ccc_info(std::vector<gr_fir_ccc_info> *info)
     {
         gr_fir_ccc_info t; t.name = "hip-gfx950"; t.create = create_gr_fir_ccc; info->push_back(t);
+    }
+    static gr_fir_fcc *create_gr_fir_fcc(const std::vector<gr_complex> &taps) { return new gr_fir_fcc_hip(taps); }
+    static gr_fir_scc *create_gr_fir_scc(const std::vector<gr_complex> &taps) { return new gr_fir_scc_hip(taps); }
+    static gr_fir_fsf *create_gr_fir_fsf(const std::vector<float> &taps) { return new gr_fir_fsf_hip(taps); }
+    static void get_gr_fir_fcc_info(std::vector<gr_fir_fcc_info> *info)
+    {
+        gr_fir_fcc_info t; t.name = "hip-gfx950"; t.create = create_gr_fir_fcc; info->push_back(t);
+    }
+    static void get_gr_fir_scc_info(std::vector<gr_fir_scc_info> *info)
+    {
+        gr_fir_scc_info t; t.name = "hip-gfx950"; t.create = create_gr_fir_scc; info->push_back(t);
+    }
+    static void get_gr_fir_fsf_info(std::vector<gr_fir_fsf_info> *info)
+    {
+        gr_fir_fsf_info t; t.name = "hip-gfx950"; t.create = create_gr_fir_fsf; info->push_back(t);
     }
 };
 

@@ -107,11 +107,21 @@ GRHIP_API int grhip_set_default_mode(int mode);
 GRHIP_API int grhip_get_default_mode(void);
 
 /* ======================================================================
- * gr_fir_filter_{ccf,fff,ccc}
+ * gr_fir_filter_{ccf,fff,ccc,fcc,scc,fsf}
  *   replaces gr_make_fir_filter_XXX(int decimation, const std::vector<TAP>&)
  *   filter/gr_fir_filter_XXX.h.t:36-66, filter/gr_fir_filter_XXX.cc.t:37-88
- * kind: "ccf" | "fff" | "ccc".  taps in forward order (complex taps
+ *   (signatures: filter/generate_utils.py:25)
+ * kind: "ccf" | "fff" | "ccc" | "fcc" | "scc" | "fsf".  taps in forward order (complex taps
  * interleaved, ntaps counts taps not floats).  history = ntaps.
+ *   kind  item in  item out  taps
+ *   fcc   float    complex   complex      real input: float / int16 items read as they are (no widened copy)
+ *   scc   int16    complex   complex
+ *   fsf   float    int16     float        output (short)acc as the reference's x86-64 build converts it:
+ *                                         truncation to int32, low 16 bits; NaN and |acc| >= 2^31 give 0
+ * GRHIP_MODE_GENERIC: gr_fir_XXX_generic's order (filter/gr_fir_XXX_generic.cc.t as generate_gr_fir_XXX.py:31-66
+ * expands it: fcc / scc N_UNROLL 2 with complex * float products, scc's (float) cast; fsf N_UNROLL 4), bit-exact.
+ * FAST: fcc / scc at decimation 1 / 2 / 4 / 8 with up to 1024 taps run the real-input kernel (fir_realin.hip, 1e-5);
+ * other shapes run the generic-order kernel.  fsf runs fff's FAST engines, then the conversion (within 1 LSB).
  * ====================================================================== */
 typedef struct grhip_fir_filter grhip_fir_filter;
 GRHIP_API int grhip_fir_filter_create(grhip_fir_filter **h, const char *kind, int decimation,
@@ -181,6 +191,37 @@ GRHIP_API int grhip_freq_xlating_fir_filter_ccc_work_device(grhip_freq_xlating_f
 /* restart the stream (rotator phase 1, counter 0) without rebuilding taps:
  * what constructing a fresh block for the next capture does. */
 GRHIP_API int grhip_freq_xlating_fir_filter_ccc_reset(grhip_freq_xlating_fir_filter_ccc *h);
+
+/* ======================================================================
+ * gr_freq_xlating_fir_filter_{ccf,fcf,fcc,scf,scc} (and ccc): one handle for the family
+ *   replaces gr_make_freq_xlating_fir_filter_XXX(int decimation, const std::vector<TAP>& taps,
+ *       double center_freq, double sampling_freq)
+ *   filter/generate_gr_freq_xlating_fir_filter_XXX.py:30, filter/gr_freq_xlating_fir_filter_XXX.cc.t:38-123
+ * kind: "ccf" | "fcf" | "fcc" | "scf" | "scc" | "ccc" (items in: c complex, f float, s int16; out: complex).
+ * taps: float for ?cf, interleaved complex for ?cc (ntaps counts taps).  The contract of _ccc: history = ntaps,
+ * set_center_freq / set_taps latch and the next work returns 0 once, set_center_freq keeps the rotator phase and
+ * counter (.cc.t:82).  Composite taps with the reference's arithmetic (.cc.t:72-83): for ?cf, proto[i] * exp(...) is
+ * float * complex = (a*c, a*d).  Inner FIR (FIR_TYPE = gr_fir_ + i_code + cc): gr_fir_ccc for ccf / ccc, gr_fir_fcc
+ * for fcf / fcc, gr_fir_scc for scf / scc.  "ccc" gives the _ccc entries' results bit for bit.
+ * GRHIP_MODE_GENERIC: bit-exact.  FAST: ccf / ccc run the complex-input engines of _ccc; the real-input kinds run
+ * the real-input kernel (fir_realin.hip) at decimation 1 / 2 / 4 / 8 with up to 1024 taps, otherwise the
+ * generic-order kernel, both with the rotator table multiply in the epilogue.
+ * ====================================================================== */
+typedef struct grhip_freq_xlating_fir_filter grhip_freq_xlating_fir_filter;
+GRHIP_API int grhip_freq_xlating_fir_filter_create(grhip_freq_xlating_fir_filter **h, const char *kind, int decimation,
+                                                   const float *taps, size_t ntaps, double center_freq,
+                                                   double sampling_freq, int device);
+GRHIP_API void grhip_freq_xlating_fir_filter_destroy(grhip_freq_xlating_fir_filter *h);
+GRHIP_API int grhip_freq_xlating_fir_filter_set_center_freq(grhip_freq_xlating_fir_filter *h, double center_freq);
+GRHIP_API int grhip_freq_xlating_fir_filter_set_taps(grhip_freq_xlating_fir_filter *h, const float *taps, size_t ntaps);
+GRHIP_API int grhip_freq_xlating_fir_filter_set_mode(grhip_freq_xlating_fir_filter *h, int mode);
+GRHIP_API int grhip_freq_xlating_fir_filter_history(const grhip_freq_xlating_fir_filter *h);
+GRHIP_API int grhip_freq_xlating_fir_filter_decimation(const grhip_freq_xlating_fir_filter *h);
+GRHIP_API int grhip_freq_xlating_fir_filter_reset(grhip_freq_xlating_fir_filter *h);
+GRHIP_API int grhip_freq_xlating_fir_filter_work(grhip_freq_xlating_fir_filter *h, int noutput_items, const void *in,
+                                                 void *out);
+GRHIP_API int grhip_freq_xlating_fir_filter_work_device(grhip_freq_xlating_fir_filter *h, int noutput_items,
+                                                        const void *d_in, void *d_out, void *stream);
 
 /* ======================================================================
  * gr_quadrature_demod_cf
