@@ -283,44 +283,49 @@ class fir_filter_fsf(_fir_filter):
 
 
 # ----------------------------------------------------------------------------
-# gr.freq_xlating_fir_filter_{ccf,fcf,fcc,scf,scc}: one C handle for the family
-# (filter/gr_freq_xlating_fir_filter_XXX.i.t; the _ccc class below keeps its own entries)
+# gr.freq_xlating_fir_filter_{ccc,ccf,fcf,fcc,scf,scc}: one C handle for the family
+# (filter/gr_freq_xlating_fir_filter_XXX.i.t)
 # ----------------------------------------------------------------------------
 class _freq_xlating_fir_filter(_Block):
-    _destroy = "grhip_freq_xlating_fir_filter_destroy"
+    _sym = "grhip_freq_xlating_fir_filter"     # prefix of the C entries
+    _destroy = _sym + "_destroy"
     _kind = None
     _in = np.complex64
     _tap = np.float32
+
+    def _fn(self, name):
+        return getattr(lib(), self._sym + name)
 
     def __init__(self, decimation, taps, center_freq, sampling_freq, device=0):
         _Block.__init__(self)
         t = np.ascontiguousarray(taps, dtype=self._tap)
         self._decim = int(decimation)
-        L = lib()
-        L.grhip_freq_xlating_fir_filter_create.argtypes = [
-            C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_int]
-        _check(L.grhip_freq_xlating_fir_filter_create(C.byref(self._h), self._kind.encode(), self._decim, _ptr(t), len(t),
-                                                      float(center_freq), float(sampling_freq), int(device)))
+        create = self._fn("_create")
+        kind = [self._kind.encode()] if self._kind else []      # the _ccc entry takes no kind
+        create.argtypes = ([C.POINTER(C.c_void_p)] + [C.c_char_p] * len(kind) +
+                           [C.c_int, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_int])
+        _check(create(C.byref(self._h), *kind, self._decim, _ptr(t), len(t), float(center_freq), float(sampling_freq),
+                      int(device)))
 
     def set_center_freq(self, center_freq):
-        L = lib()
-        L.grhip_freq_xlating_fir_filter_set_center_freq.argtypes = [C.c_void_p, C.c_double]
-        _check(L.grhip_freq_xlating_fir_filter_set_center_freq(self._h, float(center_freq)))
+        f = self._fn("_set_center_freq")
+        f.argtypes = [C.c_void_p, C.c_double]
+        _check(f(self._h, float(center_freq)))
 
     def set_taps(self, taps):
         t = np.ascontiguousarray(taps, dtype=self._tap)
-        L = lib()
-        L.grhip_freq_xlating_fir_filter_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        _check(L.grhip_freq_xlating_fir_filter_set_taps(self._h, _ptr(t), len(t)))
+        f = self._fn("_set_taps")
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        _check(f(self._h, _ptr(t), len(t)))
 
     def set_mode(self, mode):
-        _check(lib().grhip_freq_xlating_fir_filter_set_mode(self._h, int(mode)))
+        _check(self._fn("_set_mode")(self._h, int(mode)))
 
     def reset(self):
-        _check(lib().grhip_freq_xlating_fir_filter_reset(self._h))
+        _check(self._fn("_reset")(self._h))
 
     def history(self):
-        return _check(lib().grhip_freq_xlating_fir_filter_history(self._h))
+        return _check(self._fn("_history")(self._h))
 
     def decimation(self):
         return self._decim
@@ -331,16 +336,22 @@ class _freq_xlating_fir_filter(_Block):
         if len(x) < need:
             raise ValueError("work needs %d input items, got %d" % (need, len(x)))
         out = np.zeros(noutput_items, dtype=np.complex64)
-        L = lib()
-        L.grhip_freq_xlating_fir_filter_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_freq_xlating_fir_filter_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        f = self._fn("_work")
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        n = _check(f(self._h, int(noutput_items), _ptr(x), _ptr(out)))
         return out[:n]
 
     def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_freq_xlating_fir_filter_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_freq_xlating_fir_filter_work_device(self._h, int(noutput_items), _devptr(d_in),
-                                                                  _devptr(d_out), _stream(stream)))
+        f = self._fn("_work_device")
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        return _check(f(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out), _stream(stream)))
+
+
+class freq_xlating_fir_filter_ccc(_freq_xlating_fir_filter):
+    # the family handle of kind "ccc" behind gr.freq_xlating_fir_filter_ccc's own C entries
+    _sym = "grhip_freq_xlating_fir_filter_ccc"
+    _destroy = _sym + "_destroy"
+    _tap = np.complex64
 
 
 class freq_xlating_fir_filter_ccf(_freq_xlating_fir_filter):
@@ -367,65 +378,6 @@ class freq_xlating_fir_filter_scc(_freq_xlating_fir_filter):
     _kind = "scc"
     _in = np.int16
     _tap = np.complex64
-
-
-# ----------------------------------------------------------------------------
-# gr.freq_xlating_fir_filter_ccc
-# ----------------------------------------------------------------------------
-class freq_xlating_fir_filter_ccc(_Block):
-    _destroy = "grhip_freq_xlating_fir_filter_ccc_destroy"
-
-    def __init__(self, decimation, taps, center_freq, sampling_freq, device=0):
-        _Block.__init__(self)
-        t = np.ascontiguousarray(taps, dtype=np.complex64)
-        self._decim = int(decimation)
-        L = lib()
-        L.grhip_freq_xlating_fir_filter_ccc_create.argtypes = [
-            C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_int]
-        _check(L.grhip_freq_xlating_fir_filter_ccc_create(C.byref(self._h), self._decim, _ptr(t), len(t),
-                                                          float(center_freq), float(sampling_freq),
-                                                          int(device)))
-
-    def set_center_freq(self, center_freq):
-        L = lib()
-        L.grhip_freq_xlating_fir_filter_ccc_set_center_freq.argtypes = [C.c_void_p, C.c_double]
-        _check(L.grhip_freq_xlating_fir_filter_ccc_set_center_freq(self._h, float(center_freq)))
-
-    def set_taps(self, taps):
-        t = np.ascontiguousarray(taps, dtype=np.complex64)
-        L = lib()
-        L.grhip_freq_xlating_fir_filter_ccc_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        _check(L.grhip_freq_xlating_fir_filter_ccc_set_taps(self._h, _ptr(t), len(t)))
-
-    def set_mode(self, mode):
-        _check(lib().grhip_freq_xlating_fir_filter_ccc_set_mode(self._h, int(mode)))
-
-    def reset(self):
-        _check(lib().grhip_freq_xlating_fir_filter_ccc_reset(self._h))
-
-    def history(self):
-        return _check(lib().grhip_freq_xlating_fir_filter_ccc_history(self._h))
-
-    def decimation(self):
-        return self._decim
-
-    def work(self, noutput_items, input_items):
-        x = np.ascontiguousarray(input_items, dtype=np.complex64)
-        need = noutput_items * self._decim + self.history() - 1
-        if len(x) < need:
-            raise ValueError("work needs %d input items, got %d" % (need, len(x)))
-        out = np.zeros(noutput_items, dtype=np.complex64)
-        L = lib()
-        L.grhip_freq_xlating_fir_filter_ccc_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_freq_xlating_fir_filter_ccc_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
-        return out[:n]
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_freq_xlating_fir_filter_ccc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p,
-                                                                    C.c_void_p, C.c_void_p]
-        return _check(L.grhip_freq_xlating_fir_filter_ccc_work_device(
-            self._h, int(noutput_items), _devptr(d_in), _devptr(d_out), _stream(stream)))
 
 
 # ----------------------------------------------------------------------------

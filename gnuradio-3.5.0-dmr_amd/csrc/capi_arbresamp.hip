@@ -266,15 +266,10 @@ struct grhip_pfb_arb_resampler_base : HandleBase {
         if ((!in && ninput_items) || (!out && noutput_items)) return fail(GRHIP_EINVAL, "null buffer");
         int rc = bind();
         if (rc) return rc;
-        hipStream_t s = own_stream;
-        if ((rc = stage_in.reserve((size_t)ninput_items * item() + 16))) return rc;
-        if ((rc = stage_out.reserve((size_t)noutput_items * item() + 16))) return rc;
-        GRHIP_H2D(this, stage_in.p, in, (size_t)ninput_items * item(), s);
-        const int n = general_work_device(noutput_items, ninput_items, stage_in.p, stage_out.p, consumed, s);
-        if (n < 0) return n;
-        GRHIP_D2H(this, out, stage_out.p, (size_t)n * item(), s);
-        GRHIP_HIP(hipStreamSynchronize(s));
-        return n;
+        return (int)host_call(in, (size_t)ninput_items * item(), (size_t)ninput_items * item() + 16,
+                              (size_t)noutput_items * item() + 16, out, item(), [&](void *d_in, void *d_out, hipStream_t s) {
+                                  return general_work_device(noutput_items, ninput_items, d_in, d_out, consumed, s);
+                              });
     }
 
     // n_streams fresh-state captures: tpf history zeros in front of each (the scheduler's, .cc:123), outputs while

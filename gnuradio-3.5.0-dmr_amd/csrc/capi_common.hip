@@ -87,7 +87,7 @@ int HandleBase::h2d(void *dst_dev, const void *src_host, size_t bytes, hipStream
 {
     if (!bytes) return GRHIP_OK;
     // mapped staging: the CPU writes the buffer the kernels are about to read (nothing of an earlier call is in flight:
-    // every host-buffer entry ends with a synchronisation)
+    // every host-buffer entry ends with a synchronisation, HandleBase::host_call)
     for (StageBuf *b : {&stage_in, &stage_out})
         if (void *hp = b->host_of(dst_dev)) { memcpy(hp, src_host, bytes); return GRHIP_OK; }
     if (bytes > PIN_MAX) {

@@ -233,15 +233,10 @@ int grhip_binary_slicer_fb_work(grhip_binary_slicer_fb *h, int noutput_items, co
     int rc = h->bind();
     if (rc) return rc;
     size_t n = (size_t)noutput_items;
-    if ((rc = h->stage_in.reserve(n * 4))) return rc;
-    if ((rc = h->stage_out.reserve(n))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, in, n * 4, st);
-    if ((rc = launch_binary_slicer(h->stage_in.as<float>(), h->stage_out.as<unsigned char>(), (long long)n, st)))
-        return rc;
-    GRHIP_D2H(h, out, h->stage_out.p, n, st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return noutput_items;
+    return (int)h->host_call(in, n * 4, n * 4, n, out, 1, [&](void *d_in, void *d_out, hipStream_t st) {
+        rc = launch_binary_slicer((const float *)d_in, (unsigned char *)d_out, (long long)n, st);
+        return rc ? rc : noutput_items;
+    });
 }
 
 // ---- pager_slicer_fb -------------------------------------------------------------
@@ -290,16 +285,11 @@ int grhip_pager_slicer_fb_work(grhip_pager_slicer_fb *h, int noutput_items, cons
     int rc = h->bind();
     if (rc) return rc;
     size_t n = (size_t)noutput_items;
-    if ((rc = h->stage_in.reserve(n * 4))) return rc;
-    if ((rc = h->stage_out.reserve(n))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, in, n * 4, st);
-    if ((rc = launch_pager_slicer(h->d_avg.as<float>(), 1, h->alpha, h->beta, h->stage_in.as<float>(), 0,
-                                  h->stage_out.as<unsigned char>(), 0, (long long)n, st)))
-        return rc;
-    GRHIP_D2H(h, out, h->stage_out.p, n, st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return noutput_items;
+    return (int)h->host_call(in, n * 4, n * 4, n, out, 1, [&](void *d_in, void *d_out, hipStream_t st) {
+        rc = launch_pager_slicer(h->d_avg.as<float>(), 1, h->alpha, h->beta, (const float *)d_in, 0, (unsigned char *)d_out, 0,
+                                 (long long)n, st);
+        return rc ? rc : noutput_items;
+    });
 }
 
 int grhip_pager_slicer_fb_dc_offset(grhip_pager_slicer_fb *h, float *dc_offset)
@@ -355,15 +345,10 @@ int grhip_unpack_k_bits_bb_work(grhip_unpack_k_bits_bb *h, int noutput_items, co
     int rc = h->bind();
     if (rc) return rc;
     size_t n = (size_t)noutput_items, ni = n / h->k;
-    if ((rc = h->stage_in.reserve(ni))) return rc;
-    if ((rc = h->stage_out.reserve(n))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, in, ni, st);
-    if ((rc = launch_unpack_k_bits(h->k, h->stage_in.as<unsigned char>(), h->stage_out.as<unsigned char>(), (long long)n, st)))
-        return rc;
-    GRHIP_D2H(h, out, h->stage_out.p, n, st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return noutput_items;
+    return (int)h->host_call(in, ni, ni, n, out, 1, [&](void *d_in, void *d_out, hipStream_t st) {
+        rc = launch_unpack_k_bits(h->k, (const unsigned char *)d_in, (unsigned char *)d_out, (long long)n, st);
+        return rc ? rc : noutput_items;
+    });
 }
 
 // ---- stream_to_streams / streams_to_stream ------------------------------------------
@@ -498,16 +483,10 @@ int grhip_correlate_access_code_bb_work(grhip_correlate_access_code_bb *h, int n
     int rc = h->bind();
     if (rc) return rc;
     size_t n = (size_t)noutput_items;
-    if ((rc = h->stage_in.reserve(n + 8))) return rc;
-    if ((rc = h->stage_out.reserve(n + 8))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, in, n, st);
-    rc = grhip_correlate_access_code_bb_work_device(h, noutput_items, h->stage_in.as<unsigned char>(),
-                                                    h->stage_out.as<unsigned char>(), st);
-    if (rc < 0) return rc;
-    GRHIP_D2H(h, out, h->stage_out.p, n, st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return noutput_items;
+    return (int)h->host_call(in, n, n + 8, n + 8, out, 1, [&](void *d_in, void *d_out, hipStream_t st) {
+        rc = grhip_correlate_access_code_bb_work_device(h, noutput_items, (const unsigned char *)d_in, (unsigned char *)d_out, st);
+        return rc < 0 ? rc : noutput_items;
+    });
 }
 
 }  // extern "C"

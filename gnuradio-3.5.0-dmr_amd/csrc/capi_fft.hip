@@ -118,15 +118,10 @@ int grhip_fft_vcc_work(grhip_fft_vcc *h, int noutput_items, const void *in, void
     int rc = h->bind();
     if (rc) return rc;
     size_t bytes = (size_t)noutput_items * h->N * 8;
-    if ((rc = h->stage_in.reserve(bytes))) return rc;
-    if ((rc = h->stage_out.reserve(bytes))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, in, bytes, st);
-    rc = grhip_fft_vcc_work_device(h, noutput_items, h->stage_in.p, h->stage_out.p, st);
-    if (rc < 0) return rc;
-    GRHIP_D2H(h, out, h->stage_out.p, bytes, st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return noutput_items;
+    return (int)h->host_call(in, bytes, bytes, bytes, out, (size_t)h->N * 8, [&](void *d_in, void *d_out, hipStream_t st) {
+        rc = grhip_fft_vcc_work_device(h, noutput_items, d_in, d_out, st);
+        return rc < 0 ? rc : noutput_items;
+    });
 }
 
 // ---- pfb_channelizer_ccf ---------------------------------------------------------

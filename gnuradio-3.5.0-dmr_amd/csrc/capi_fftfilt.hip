@@ -159,17 +159,12 @@ int grhip_fft_filter_ccc_work(grhip_fft_filter_ccc *h, int noutput_items, const 
     if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
     int rc = h->bind();
     if (rc) return rc;
-    hipStream_t st = h->own_stream;
-    if (h->updated || noutput_items == 0) return grhip_fft_filter_ccc_work_device(h, noutput_items, nullptr, nullptr, st);
+    if (h->updated || noutput_items == 0)
+        return grhip_fft_filter_ccc_work_device(h, noutput_items, nullptr, nullptr, h->own_stream);
     const size_t nin = (size_t)noutput_items * h->decim;
-    if ((rc = h->stage_in.reserve(nin * 8))) return rc;
-    if ((rc = h->stage_out.reserve((size_t)noutput_items * 8))) return rc;
-    GRHIP_H2D(h, h->stage_in.p, in, nin * 8, st);
-    rc = grhip_fft_filter_ccc_work_device(h, noutput_items, h->stage_in.p, h->stage_out.p, st);
-    if (rc < 0) return rc;
-    GRHIP_D2H(h, out, h->stage_out.p, (size_t)noutput_items * 8, st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return rc;
+    return (int)h->host_call(in, nin * 8, nin * 8, (size_t)noutput_items * 8, out, 8, [&](void *d_in, void *d_out, hipStream_t st) {
+        return grhip_fft_filter_ccc_work_device(h, noutput_items, d_in, d_out, st);
+    });
 }
 
 }  // extern "C"

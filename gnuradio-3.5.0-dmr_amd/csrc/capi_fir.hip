@@ -1,4 +1,4 @@
-// capi_fir.hip -- C ABI for gr_fir_filter_XXX, gr_freq_xlating_fir_filter_ccc,
+// capi_fir.hip -- C ABI for gr_fir_filter_XXX, gr_freq_xlating_fir_filter_XXX,
 // gr_quadrature_demod_cf and the fused xlating->demod hier block.
 #include <cmath>
 #include <complex>
@@ -551,6 +551,13 @@ struct grhip_fir_filter : HandleBase {
     size_t in_item() const { return kind == FIR_SCC ? 2 : (kind == FIR_FFF || kind == FIR_FSF || kind == FIR_FCC) ? 4 : 8; }
     size_t out_item() const { return kind == FIR_FFF ? 4 : kind == FIR_FSF ? 2 : 8; }
 
+    void release()
+    {
+        d_taps_rev.release(); d_hp.release(); sched.release(); d_ols_tw.release(); d_ols_H.release(); d_hidec_taps.release();
+        d_mf_A[0].release(); d_mf_A[1].release(); mf_sched.release(); d_scratch.release();
+        destroy_base();
+    }
+
     int install(const std::vector<float> &t)
     {
         taps = t;
@@ -706,7 +713,7 @@ int grhip_fir_filter_create(grhip_fir_filter **h, const char *kind, int decimati
     f->kind = k; f->ekind = k == FIR_FSF ? FIR_FFF : k; f->decim = decimation; f->mode = default_mode();
     int rc = f->init_device(device);
     if (!rc) rc = f->install(std::vector<float>(taps, taps + ntaps * f->tw()));
-    if (rc) { f->d_taps_rev.release(); f->d_hp.release(); f->sched.release(); f->d_ols_tw.release(); f->d_ols_H.release(); f->d_hidec_taps.release(); f->d_mf_A[0].release(); f->d_mf_A[1].release(); f->mf_sched.release(); f->d_scratch.release(); f->destroy_base(); delete f; return rc; }
+    if (rc) { f->release(); delete f; return rc; }
     *h = f;
     return GRHIP_OK;
 }
@@ -715,9 +722,7 @@ void grhip_fir_filter_destroy(grhip_fir_filter *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    h->d_taps_rev.release(); h->d_hp.release(); h->sched.release(); h->d_ols_tw.release(); h->d_ols_H.release(); h->d_hidec_taps.release();
-    h->d_mf_A[0].release(); h->d_mf_A[1].release(); h->mf_sched.release(); h->d_scratch.release();
-    h->destroy_base();
+    h->release();
     delete h;
 }
 
@@ -745,16 +750,14 @@ int grhip_fir_filter_history(const grhip_fir_filter *h)
 
 int grhip_fir_filter_decimation(const grhip_fir_filter *h) { return h ? h->decim : GRHIP_EINVAL; }
 
-// `st`: the stream this work call will use.  install() rewrites the tap buffers with blocking copies on
-// the null stream, which do not wait for the handle's non-blocking streams: an earlier *_work_device
+// `st`: the stream this work call will use.  install() rewrites the tap buffers: an earlier *_work_device
 // launch may still be reading them, so the streams are drained first.
 static int fir_apply_update(grhip_fir_filter *h, hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(h->setter_mutex);
     if (!h->updated) return 0;
-    GRHIP_HIP(hipStreamSynchronize(st));
-    if (st != h->own_stream) GRHIP_HIP(hipStreamSynchronize(h->own_stream));
-    int rc = h->install(h->new_taps);
+    int rc = h->drain(st);
+    if (!rc) rc = h->install(h->new_taps);
     if (rc) return rc;
     h->updated = false;
     return 1;
@@ -787,14 +790,11 @@ int grhip_fir_filter_work(grhip_fir_filter *h, int noutput_items, const void *in
     long long n = noutput_items;
     size_t n_in = (size_t)((n - 1) * h->decim + (h->ntaps > 0 ? h->ntaps : 0));
     if (n_in == 0) n_in = 1;
-    if ((rc = h->stage_in.reserve(n_in * h->in_item() + 16))) return rc;
-    if ((rc = h->stage_out.reserve((size_t)n * h->out_item()))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, in, n_in * h->in_item(), st);
-    if ((rc = h->run(h->stage_in.p, h->stage_out.p, n, h->decim, st))) return rc;
-    GRHIP_D2H(h, out, h->stage_out.p, (size_t)n * h->out_item(), st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return noutput_items;
+    return (int)h->host_call(in, n_in * h->in_item(), n_in * h->in_item() + 16, (size_t)n * h->out_item(), out, h->out_item(),
+                             [&](void *d_in, void *d_out, hipStream_t st) {
+                                 rc = h->run(d_in, d_out, n, h->decim, st);
+                                 return rc ? rc : noutput_items;
+                             });
 }
 
 int grhip_fir_filterNdec(grhip_fir_filter *h, void *output, const void *input, unsigned long n,
@@ -807,14 +807,12 @@ int grhip_fir_filterNdec(grhip_fir_filter *h, void *output, const void *input, u
     if (n == 0) return GRHIP_OK;
     size_t n_in = (size_t)((n - 1) * decimate + h->ntaps);
     if (n_in == 0) n_in = 1;
-    if ((rc = h->stage_in.reserve(n_in * h->in_item() + 16))) return rc;
-    if ((rc = h->stage_out.reserve((size_t)n * h->out_item()))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, input, n_in * h->in_item(), st);
-    if ((rc = h->run(h->stage_in.p, h->stage_out.p, (long long)n, (int)decimate, st))) return rc;
-    GRHIP_D2H(h, output, h->stage_out.p, (size_t)n * h->out_item(), st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return GRHIP_OK;
+    const long long r = h->host_call(input, n_in * h->in_item(), n_in * h->in_item() + 16, (size_t)n * h->out_item(), output,
+                                     h->out_item(), [&](void *d_in, void *d_out, hipStream_t st) {
+                                         rc = h->run(d_in, d_out, (long long)n, (int)decimate, st);
+                                         return rc ? (long long)rc : (long long)n;
+                                     });
+    return r < 0 ? (int)r : GRHIP_OK;
 }
 
 }  // extern "C"
@@ -967,29 +965,19 @@ int grhip_fir_filter_with_buffer_filterNdec(grhip_fir_filter_with_buffer *h, voi
     int rc = h->bind();
     if (rc) return rc;
     const size_t it = h->item(), nin = (size_t)n * decimate;
-    if ((rc = h->stage_in.reserve(nin * it + 16))) return rc;
-    if ((rc = h->stage_out.reserve((size_t)n * it))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, input, nin * it, st);
-    rc = grhip_fir_filter_with_buffer_filterNdec_device(h, h->stage_out.p, h->stage_in.p, n, decimate, st);
-    if (rc) return rc;
-    GRHIP_D2H(h, output, h->stage_out.p, (size_t)n * it, st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return GRHIP_OK;
+    const long long r = h->host_call(input, nin * it, nin * it + 16, (size_t)n * it, output, it,
+                                     [&](void *d_in, void *d_out, hipStream_t st) {
+                                         rc = grhip_fir_filter_with_buffer_filterNdec_device(h, d_out, d_in, n, decimate, st);
+                                         return rc ? (long long)rc : (long long)n;
+                                     });
+    return r < 0 ? (int)r : GRHIP_OK;
 }
 
 }  // extern "C"
 
 // ============================================================================
-// gr_freq_xlating_fir_filter_ccc, gr_quadrature_demod_cf, fused hier block
+// gr_quadrature_demod_cf, fused xlating -> demod hier block
 // ============================================================================
-struct grhip_freq_xlating_fir_filter_ccc : HandleBase {
-    XlatingCore core;
-    int mode = GRHIP_MODE_FAST;
-    // latched by the setters (.cc.t:86-98)
-    std::vector<cf> new_proto; double new_center_freq = 0; bool updated = false;
-};
-
 struct grhip_quadrature_demod_cf : HandleBase {
     float gain = 1.f;
     const DeviceTables *tabs = nullptr;
@@ -1016,138 +1004,6 @@ static int xlating_args_ok(int decimation, const float *taps, size_t ntaps, doub
 }
 
 extern "C" {
-
-int grhip_freq_xlating_fir_filter_ccc_create(grhip_freq_xlating_fir_filter_ccc **h, int decimation,
-                                             const float *taps, size_t ntaps, double center_freq,
-                                             double sampling_freq, int device)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null argument");
-    *h = nullptr;
-    int rc = xlating_args_ok(decimation, taps, ntaps, sampling_freq);
-    if (rc) return rc;
-    auto *x = new (std::nothrow) grhip_freq_xlating_fir_filter_ccc();
-    if (!x) return fail(GRHIP_ENOMEM, "alloc");
-    x->mode = default_mode();
-    rc = x->init_device(device);
-    if (!rc) {
-        x->core.decim = decimation;
-        x->core.proto.assign((const cf *)taps, (const cf *)taps + ntaps);
-        x->core.center_freq = center_freq; x->core.sampling_freq = sampling_freq;
-        rc = x->core.build(device);
-    }
-    if (rc) { x->core.release(); x->destroy_base(); delete x; return rc; }
-    *h = x;
-    return GRHIP_OK;
-}
-
-void grhip_freq_xlating_fir_filter_ccc_destroy(grhip_freq_xlating_fir_filter_ccc *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    h->core.release();
-    h->destroy_base();
-    delete h;
-}
-
-int grhip_freq_xlating_fir_filter_ccc_set_center_freq(grhip_freq_xlating_fir_filter_ccc *h, double center_freq)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    std::lock_guard<std::mutex> lk(h->setter_mutex);
-    if (!h->updated) h->new_proto = h->core.proto;
-    h->new_center_freq = center_freq;
-    h->updated = true;
-    return GRHIP_OK;
-}
-
-int grhip_freq_xlating_fir_filter_ccc_set_taps(grhip_freq_xlating_fir_filter_ccc *h, const float *taps,
-                                              size_t ntaps)
-{
-    if (!h || (ntaps && !taps)) return fail(GRHIP_EINVAL, "null argument");
-    std::lock_guard<std::mutex> lk(h->setter_mutex);
-    if (!h->updated) h->new_center_freq = h->core.center_freq;
-    h->new_proto.assign((const cf *)taps, (const cf *)taps + ntaps);
-    h->updated = true;
-    return GRHIP_OK;
-}
-
-int grhip_freq_xlating_fir_filter_ccc_set_mode(grhip_freq_xlating_fir_filter_ccc *h, int mode)
-{
-    if (!h || !mode_valid(mode)) return fail(GRHIP_EINVAL, "bad mode");
-    h->mode = mode;
-    return GRHIP_OK;
-}
-
-int grhip_freq_xlating_fir_filter_ccc_history(const grhip_freq_xlating_fir_filter_ccc *h)
-{
-    return h ? (h->core.ntaps > 0 ? h->core.ntaps : 1) : GRHIP_EINVAL;
-}
-
-int grhip_freq_xlating_fir_filter_ccc_reset(grhip_freq_xlating_fir_filter_ccc *h)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    h->core.reset();
-    return GRHIP_OK;
-}
-
-static int xl_apply_update(grhip_freq_xlating_fir_filter_ccc *h, hipStream_t st)
-{
-    std::lock_guard<std::mutex> lk(h->setter_mutex);
-    if (!h->updated) return 0;
-    GRHIP_HIP(hipStreamSynchronize(st));         // see fir_apply_update
-    if (st != h->own_stream) GRHIP_HIP(hipStreamSynchronize(h->own_stream));
-    // work(): set_history; build_composite_fir(); d_updated = false; return 0 (.cc.t:109-114).
-    // NB the reference keeps the rotator's d_phase/d_counter and only replaces
-    // d_phase_incr; XlatingCore::rebuild_keep_phase does the same.
-    h->core.proto = h->new_proto;
-    h->core.center_freq = h->new_center_freq;
-    int rc = h->core.rebuild_keep_phase(h->device);
-    if (rc) return rc;
-    h->updated = false;
-    return 1;
-}
-
-int grhip_freq_xlating_fir_filter_ccc_work_device(grhip_freq_xlating_fir_filter_ccc *h, int noutput_items,
-                                                  const void *d_in, void *d_out, void *stream)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
-    int rc = h->bind();
-    if (rc) return rc;
-    rc = xl_apply_update(h, h->pick(stream));
-    if (rc < 0) return rc;
-    if (rc == 1) return 0;
-    long long n = noutput_items;
-    long long n_in = n > 0 ? (n - 1) * h->core.decim + h->core.ntaps : 0;
-    rc = h->core.run(h->mode, (const float2 *)d_in, n_in, n, (float2 *)d_out, nullptr, 0.f, nullptr, nullptr,
-                     nullptr, h->pick(stream));
-    return rc ? rc : noutput_items;
-}
-
-int grhip_freq_xlating_fir_filter_ccc_work(grhip_freq_xlating_fir_filter_ccc *h, int noutput_items,
-                                           const void *in, void *out)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
-    int rc = h->bind();
-    if (rc) return rc;
-    rc = xl_apply_update(h, h->own_stream);
-    if (rc < 0) return rc;
-    if (rc == 1) return 0;
-    if (noutput_items == 0) return 0;
-    long long n = noutput_items;
-    size_t n_in = (size_t)((n - 1) * h->core.decim + h->core.ntaps);
-    if (n_in == 0) n_in = 1;
-    if ((rc = h->stage_in.reserve(n_in * 8 + 16))) return rc;
-    if ((rc = h->stage_out.reserve((size_t)n * 8))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, in, n_in * 8, st);
-    rc = h->core.run(h->mode, h->stage_in.as<float2>(), (long long)n_in, n, h->stage_out.as<float2>(), nullptr,
-                     0.f, nullptr, nullptr, nullptr, st);
-    if (rc) return rc;
-    GRHIP_D2H(h, out, h->stage_out.p, (size_t)n * 8, st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return noutput_items;
-}
 
 // ---- quadrature_demod_cf -----------------------------------------------------
 int grhip_quadrature_demod_cf_create(grhip_quadrature_demod_cf **h, float gain, int device)
@@ -1191,16 +1047,10 @@ int grhip_quadrature_demod_cf_work(grhip_quadrature_demod_cf *h, int noutput_ite
     int rc = h->bind();
     if (rc) return rc;
     size_t n = (size_t)noutput_items;
-    if ((rc = h->stage_in.reserve((n + 1) * 8))) return rc;
-    if ((rc = h->stage_out.reserve(n * 4))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, in, (n + 1) * 8, st);
-    if ((rc = launch_quad_demod(h->stage_in.as<float2>(), h->stage_out.as<float>(), (long long)n, h->gain,
-                                h->tabs->atan_tab, st)))
-        return rc;
-    GRHIP_D2H(h, out, h->stage_out.p, n * 4, st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return noutput_items;
+    return (int)h->host_call(in, (n + 1) * 8, (n + 1) * 8, n * 4, out, 4, [&](void *d_in, void *d_out, hipStream_t st) {
+        rc = launch_quad_demod((const float2 *)d_in, (float *)d_out, (long long)n, h->gain, h->tabs->atan_tab, st);
+        return rc ? rc : noutput_items;
+    });
 }
 
 // ---- fused xlating -> demod ----------------------------------------------------
@@ -1328,29 +1178,26 @@ int grhip_xlating_demod_work(grhip_xlating_demod *h, int noutput_items, const vo
     long long n = noutput_items;
     size_t n_in = (size_t)((n - 1) * h->core.decim + h->core.ntaps);
     if (n_in == 0) n_in = 1;
-    if ((rc = h->stage_in.reserve(n_in * 8 + 16))) return rc;
-    if ((rc = h->stage_out.reserve((size_t)n * 4))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, in, n_in * 8, st);
-    rc = grhip_xlating_demod_work_device(h, noutput_items, h->stage_in.p, h->stage_out.p, st);
-    if (rc < 0) return rc;
-    GRHIP_D2H(h, out, h->stage_out.p, (size_t)n * 4, st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return noutput_items;
+    return (int)h->host_call(in, n_in * 8, n_in * 8 + 16, (size_t)n * 4, out, 4, [&](void *d_in, void *d_out, hipStream_t st) {
+        rc = grhip_xlating_demod_work_device(h, noutput_items, d_in, d_out, st);
+        return rc < 0 ? rc : noutput_items;
+    });
 }
 
 }  // extern "C"
 
 // ============================================================================
-// gr_freq_xlating_fir_filter_{ccf,fcf,fcc,scf,scc} (and ccc), one handle for the family
+// gr_freq_xlating_fir_filter_{ccc,ccf,fcf,fcc,scf,scc}, one handle for the family
 //   filter/generate_gr_freq_xlating_fir_filter_XXX.py:30 (signatures, FIR_TYPE = gr_fir_ + i_code + cc),
 //   filter/gr_freq_xlating_fir_filter_XXX.cc.t:38-123
+// The grhip_freq_xlating_fir_filter_ccc_* entries are the family handle of kind "ccc".
 // ============================================================================
 struct grhip_freq_xlating_fir_filter : HandleBase {
     XlatingCore core;
     int mode = GRHIP_MODE_FAST;
     bool ctaps_in = true;           // ?cc: interleaved complex taps; ?cf: float taps
     size_t in_item = 8;
+    // latched by the setters (.cc.t:86-98)
     std::vector<cf> new_proto; double new_center_freq = 0; bool updated = false;
 
     void set_proto(std::vector<cf> &dst, const float *taps, size_t ntaps) const
@@ -1363,11 +1210,12 @@ struct grhip_freq_xlating_fir_filter : HandleBase {
     }
 };
 
-extern "C" {
+struct grhip_freq_xlating_fir_filter_ccc : grhip_freq_xlating_fir_filter {};
 
-int grhip_freq_xlating_fir_filter_create(grhip_freq_xlating_fir_filter **h, const char *kind, int decimation,
-                                         const float *taps, size_t ntaps, double center_freq, double sampling_freq,
-                                         int device)
+// H: the family handle, or its _ccc type
+template <class H>
+static int xlating_create(H **h, const char *kind, int decimation, const float *taps, size_t ntaps, double center_freq,
+                          double sampling_freq, int device)
 {
     if (!h || !kind) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
@@ -1382,7 +1230,7 @@ int grhip_freq_xlating_fir_filter_create(grhip_freq_xlating_fir_filter **h, cons
     else return fail(GRHIP_EINVAL, "unknown freq_xlating kind '%s'", kind);
     int rc = xlating_args_ok(decimation, taps, ntaps, sampling_freq);
     if (rc) return rc;
-    auto *x = new (std::nothrow) grhip_freq_xlating_fir_filter();
+    auto *x = new (std::nothrow) H();
     if (!x) return fail(GRHIP_ENOMEM, "alloc");
     x->mode = default_mode();
     x->ctaps_in = ctaps_in;
@@ -1401,7 +1249,8 @@ int grhip_freq_xlating_fir_filter_create(grhip_freq_xlating_fir_filter **h, cons
     return GRHIP_OK;
 }
 
-void grhip_freq_xlating_fir_filter_destroy(grhip_freq_xlating_fir_filter *h)
+template <class H>
+static void xlating_destroy(H *h)
 {
     if (!h) return;
     (void)hipSetDevice(h->device);
@@ -1409,6 +1258,17 @@ void grhip_freq_xlating_fir_filter_destroy(grhip_freq_xlating_fir_filter *h)
     h->destroy_base();
     delete h;
 }
+
+extern "C" {
+
+int grhip_freq_xlating_fir_filter_create(grhip_freq_xlating_fir_filter **h, const char *kind, int decimation,
+                                         const float *taps, size_t ntaps, double center_freq, double sampling_freq,
+                                         int device)
+{
+    return xlating_create(h, kind, decimation, taps, ntaps, center_freq, sampling_freq, device);
+}
+
+void grhip_freq_xlating_fir_filter_destroy(grhip_freq_xlating_fir_filter *h) { xlating_destroy(h); }
 
 int grhip_freq_xlating_fir_filter_set_center_freq(grhip_freq_xlating_fir_filter *h, double center_freq)
 {
@@ -1451,16 +1311,18 @@ int grhip_freq_xlating_fir_filter_reset(grhip_freq_xlating_fir_filter *h)
     return GRHIP_OK;
 }
 
-// as xl_apply_update: set_history; build_composite_fir(); return 0 once (.cc.t:109-114), rotator phase and counter kept
+// work(): set_history; build_composite_fir(); d_updated = false; return 0 (.cc.t:109-114).
+// NB the reference keeps the rotator's d_phase/d_counter and only replaces
+// d_phase_incr; XlatingCore::rebuild_keep_phase does the same.
 static int xlf_apply_update(grhip_freq_xlating_fir_filter *h, hipStream_t st)
 {
     std::lock_guard<std::mutex> lk(h->setter_mutex);
     if (!h->updated) return 0;
-    GRHIP_HIP(hipStreamSynchronize(st));
-    if (st != h->own_stream) GRHIP_HIP(hipStreamSynchronize(h->own_stream));
+    int rc = h->drain(st);       // see fir_apply_update
+    if (rc) return rc;
     h->core.proto = h->new_proto;
     h->core.center_freq = h->new_center_freq;
-    int rc = h->core.rebuild_keep_phase(h->device);
+    rc = h->core.rebuild_keep_phase(h->device);
     if (rc) return rc;
     h->updated = false;
     return 1;
@@ -1497,16 +1359,53 @@ int grhip_freq_xlating_fir_filter_work(grhip_freq_xlating_fir_filter *h, int nou
     size_t n_in = (size_t)((n - 1) * h->core.decim + h->core.ntaps);
     if (n_in == 0) n_in = 1;
     const size_t it = h->in_item;
-    if ((rc = h->stage_in.reserve(n_in * it + 16))) return rc;
-    if ((rc = h->stage_out.reserve((size_t)n * 8))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, in, n_in * it, st);
-    rc = h->core.run(h->mode, h->stage_in.as<float2>(), (long long)n_in, n, h->stage_out.as<float2>(), nullptr, 0.f, nullptr,
-                     nullptr, nullptr, st);
-    if (rc) return rc;
-    GRHIP_D2H(h, out, h->stage_out.p, (size_t)n * 8, st);
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return noutput_items;
+    return (int)h->host_call(in, n_in * it, n_in * it + 16, (size_t)n * 8, out, 8, [&](void *d_in, void *d_out, hipStream_t st) {
+        rc = h->core.run(h->mode, (const float2 *)d_in, (long long)n_in, n, (float2 *)d_out, nullptr, 0.f, nullptr, nullptr,
+                         nullptr, st);
+        return rc ? rc : noutput_items;
+    });
+}
+
+// ---- gr_freq_xlating_fir_filter_ccc: forwards to the family entries ----
+int grhip_freq_xlating_fir_filter_ccc_create(grhip_freq_xlating_fir_filter_ccc **h, int decimation, const float *taps,
+                                             size_t ntaps, double center_freq, double sampling_freq, int device)
+{
+    return xlating_create(h, "ccc", decimation, taps, ntaps, center_freq, sampling_freq, device);
+}
+
+void grhip_freq_xlating_fir_filter_ccc_destroy(grhip_freq_xlating_fir_filter_ccc *h) { xlating_destroy(h); }
+
+int grhip_freq_xlating_fir_filter_ccc_set_center_freq(grhip_freq_xlating_fir_filter_ccc *h, double center_freq)
+{
+    return grhip_freq_xlating_fir_filter_set_center_freq(h, center_freq);
+}
+
+int grhip_freq_xlating_fir_filter_ccc_set_taps(grhip_freq_xlating_fir_filter_ccc *h, const float *taps, size_t ntaps)
+{
+    return grhip_freq_xlating_fir_filter_set_taps(h, taps, ntaps);
+}
+
+int grhip_freq_xlating_fir_filter_ccc_set_mode(grhip_freq_xlating_fir_filter_ccc *h, int mode)
+{
+    return grhip_freq_xlating_fir_filter_set_mode(h, mode);
+}
+
+int grhip_freq_xlating_fir_filter_ccc_history(const grhip_freq_xlating_fir_filter_ccc *h)
+{
+    return grhip_freq_xlating_fir_filter_history(h);
+}
+
+int grhip_freq_xlating_fir_filter_ccc_reset(grhip_freq_xlating_fir_filter_ccc *h) { return grhip_freq_xlating_fir_filter_reset(h); }
+
+int grhip_freq_xlating_fir_filter_ccc_work(grhip_freq_xlating_fir_filter_ccc *h, int noutput_items, const void *in, void *out)
+{
+    return grhip_freq_xlating_fir_filter_work(h, noutput_items, in, out);
+}
+
+int grhip_freq_xlating_fir_filter_ccc_work_device(grhip_freq_xlating_fir_filter_ccc *h, int noutput_items, const void *d_in,
+                                                  void *d_out, void *stream)
+{
+    return grhip_freq_xlating_fir_filter_work_device(h, noutput_items, d_in, d_out, stream);
 }
 
 }  // extern "C"

@@ -869,11 +869,10 @@ int grhip_framer_sink_1_work(grhip_framer_sink_1 *h, int noutput_items, const un
     if (!in) return fail(GRHIP_EINVAL, "null buffer");
     int rc = h->bind();
     if (rc) return rc;
-    if ((rc = h->stage_in.reserve((size_t)noutput_items))) return rc;
-    hipStream_t st = h->own_stream;
-    GRHIP_H2D(h, h->stage_in.p, in, (size_t)noutput_items, st);
-    rc = grhip_framer_sink_1_work_device(h, noutput_items, h->stage_in.as<unsigned char>(), st);
-    if (rc < 0) return rc;
-    GRHIP_HIP(hipStreamSynchronize(st));
-    return noutput_items;
+    // (a sink: no output is staged or copied back)
+    const size_t n = (size_t)noutput_items;
+    return (int)h->host_call(in, n, n, 0, nullptr, 0, [&](void *d_in, void *, hipStream_t st) {
+        rc = grhip_framer_sink_1_work_device(h, noutput_items, (const unsigned char *)d_in, st);
+        return rc < 0 ? rc : noutput_items;
+    });
 }

@@ -148,9 +148,8 @@ struct grhip_rs_core : HandleBase {
     {
         *did = false;
         if (!updated) return GRHIP_OK;
-        GRHIP_HIP(hipStreamSynchronize(st));
-        if (st != own_stream) GRHIP_HIP(hipStreamSynchronize(own_stream));
-        int rc = install(new_taps);
+        int rc = drain(st);
+        if (!rc) rc = install(new_taps);
         if (rc) return rc;
         updated = false;
         *did = true;
@@ -212,15 +211,10 @@ struct grhip_rs_core : HandleBase {
         if ((!in && ninput_items) || (!out && noutput_items)) return fail(GRHIP_EINVAL, "null buffer");
         int rc = bind();
         if (rc) return rc;
-        hipStream_t s = own_stream;
-        if ((rc = stage_in.reserve((size_t)ninput_items * item() + 16))) return rc;
-        if ((rc = stage_out.reserve((size_t)noutput_items * item() + 16))) return rc;
-        GRHIP_H2D(this, stage_in.p, in, (size_t)ninput_items * item(), s);
-        const int n = general_work_device(noutput_items, ninput_items, stage_in.p, stage_out.p, consumed, s);
-        if (n < 0) return n;
-        GRHIP_D2H(this, out, stage_out.p, (size_t)n * item(), s);
-        GRHIP_HIP(hipStreamSynchronize(s));
-        return n;
+        return (int)host_call(in, (size_t)ninput_items * item(), (size_t)ninput_items * item() + 16,
+                              (size_t)noutput_items * item() + 16, out, item(), [&](void *d_in, void *d_out, hipStream_t s) {
+                                  return general_work_device(noutput_items, ninput_items, d_in, d_out, consumed, s);
+                              });
     }
 
     // ---- gr_interp_fir_filter_XXX ----
@@ -253,7 +247,6 @@ struct grhip_rs_core : HandleBase {
         if ((!in || !out) && noutput_items) return fail(GRHIP_EINVAL, "null buffer");
         int rc = bind();
         if (rc) return rc;
-        hipStream_t s = own_stream;
         // the items this call reads: n/I + nt - 1, history in front (gr_sync_interpolator with set_history(nt)); a call
         // that installs new taps reads nothing
         size_t nin;
@@ -261,14 +254,8 @@ struct grhip_rs_core : HandleBase {
             std::lock_guard<std::mutex> lk(setter_mutex);
             nin = updated || noutput_items == 0 ? 0 : (size_t)(noutput_items / (long long)I) + nt - 1;
         }
-        if ((rc = stage_in.reserve(nin * item() + 16))) return rc;
-        if ((rc = stage_out.reserve((size_t)noutput_items * item() + 16))) return rc;
-        if (nin) GRHIP_H2D(this, stage_in.p, in, nin * item(), s);
-        const int n = work_device(noutput_items, stage_in.p, stage_out.p, s);
-        if (n < 0) return n;
-        GRHIP_D2H(this, out, stage_out.p, (size_t)n * item(), s);
-        GRHIP_HIP(hipStreamSynchronize(s));
-        return n;
+        return (int)host_call(in, nin * item(), nin * item() + 16, (size_t)noutput_items * item() + 16, out, item(),
+                              [&](void *d_in, void *d_out, hipStream_t s) { return work_device(noutput_items, d_in, d_out, s); });
     }
 
     // ---- both: fresh captures ----

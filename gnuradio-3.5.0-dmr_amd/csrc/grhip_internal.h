@@ -141,6 +141,37 @@ struct HandleBase {
     void destroy_base();
     hipStream_t pick(void *stream) const { return stream ? (hipStream_t)stream : own_stream; }
     int bind() const;          // hipSetDevice for the calling thread
+
+    // Wait for the launches that may still read a handle's tap buffers (on `st`, the stream of the coming work call,
+    // and on the handle's own stream) before a latched update rewrites them with blocking copies on the null stream,
+    // which does not wait for the handles' non-blocking streams.
+    int drain(hipStream_t st)
+    {
+        GRHIP_HIP(hipStreamSynchronize(st));
+        if (st != own_stream) GRHIP_HIP(hipStreamSynchronize(own_stream));
+        return GRHIP_OK;
+    }
+
+    // The body of a host-buffer entry point: reserve the staging buffers, stage in_bytes of `in`, run
+    // work(d_in, d_out, stream) on the handle's own stream, copy the n * out_item bytes of the n items it reports back to
+    // `out` and return n (or work's negative error code).  The call ends with a synchronisation, which every host-buffer
+    // entry needs: h2d writes straight into mapped staging memory, so nothing of this call may still be in flight when
+    // the next call's h2d runs.
+    template <class Work>
+    long long host_call(const void *in, size_t in_bytes, size_t in_reserve, size_t out_reserve, void *out,
+                        size_t out_item, Work &&work)
+    {
+        int rc;
+        if ((rc = stage_in.reserve(in_reserve))) return rc;
+        if ((rc = stage_out.reserve(out_reserve))) return rc;
+        hipStream_t st = own_stream;
+        GRHIP_H2D(this, stage_in.p, in, in_bytes, st);
+        const long long n = work(stage_in.p, stage_out.p, st);
+        if (n < 0) return n;
+        GRHIP_D2H(this, out, stage_out.p, (size_t)n * out_item, st);
+        GRHIP_HIP(hipStreamSynchronize(st));
+        return n;
+    }
 };
 
 int default_mode();

@@ -4,8 +4,7 @@
 // names and exception types:
 //
 //   grhip_fir_filter_ccf / _fff / _ccc      <- gr_fir_filter_XXX   (filter/gr_fir_filter_XXX.h.t:36-66)
-//   grhip_freq_xlating_fir_filter_ccc        <- gr_freq_xlating_fir_filter_ccc (.h.t:64-99)
-//   grhip_freq_xlating_fir_filter_{ccf,fcf,fcc,scf,scc} <- gr_freq_xlating_fir_filter_XXX (the family handle)
+//   grhip_freq_xlating_fir_filter_{ccc,ccf,fcf,fcc,scf,scc} <- gr_freq_xlating_fir_filter_XXX (the family handle)
 //   grhip_quadrature_demod_cf                <- gr_quadrature_demod_cf (general/gr_quadrature_demod_cf.h)
 //   grhip_clock_recovery_mm_ff               <- digital_clock_recovery_mm_ff (gr-digital/include/...h:44-92)
 //   grhip_binary_slicer_fb                   <- digital_binary_slicer_fb
@@ -109,8 +108,8 @@ GRHIP_FIR_CLASS(grhip_fir_filter_scc, fir_filter_scc, short, gr_complex, gr_comp
 GRHIP_FIR_CLASS(grhip_fir_filter_fsf, fir_filter_fsf, float, short, float)
 
 // ---------------------------------------------------------------------------
-// gr_freq_xlating_fir_filter_{ccf,fcf,fcc,scf,scc}: one template over the family handle
-// (filter/gr_freq_xlating_fir_filter_XXX.cc.t:38-123; _ccc keeps its own class below)
+// gr_freq_xlating_fir_filter_{ccc,ccf,fcf,fcc,scf,scc}: one template over the family handle
+// (filter/gr_freq_xlating_fir_filter_XXX.h.t:64-99, .cc.t:38-123)
 // ---------------------------------------------------------------------------
 template <class IN, class TAP> class grhip_freq_xlating_fir_filter_blk : public gr_sync_decimator {
     grhip_freq_xlating_fir_filter *d_h = nullptr;
@@ -148,51 +147,12 @@ public:
         return gnuradio::get_initial_sptr(new grhip_freq_xlating_fir_filter_##SUF##_blk(                          \
             "freq_xlating_fir_filter_" #SUF, #SUF, decimation, taps, center_freq, sampling_freq, device));        \
     }
+GRHIP_XLATING_CLASS(ccc, gr_complex, gr_complex)
 GRHIP_XLATING_CLASS(ccf, gr_complex, float)
 GRHIP_XLATING_CLASS(fcf, float, float)
 GRHIP_XLATING_CLASS(fcc, float, gr_complex)
 GRHIP_XLATING_CLASS(scf, short, float)
 GRHIP_XLATING_CLASS(scc, short, gr_complex)
-
-// ---------------------------------------------------------------------------
-// gr_freq_xlating_fir_filter_ccc
-// ---------------------------------------------------------------------------
-class grhip_freq_xlating_fir_filter_ccc_blk;
-typedef boost::shared_ptr<grhip_freq_xlating_fir_filter_ccc_blk> grhip_freq_xlating_fir_filter_ccc_sptr;
-class grhip_freq_xlating_fir_filter_ccc_blk : public gr_sync_decimator {
-    grhip_freq_xlating_fir_filter_ccc *d_h = nullptr;
-    grhip_freq_xlating_fir_filter_ccc_blk(int decimation, const std::vector<gr_complex> &taps, double center_freq,
-                                          double sampling_freq, int device)
-        : gr_sync_decimator("freq_xlating_fir_filter_ccc", gr_make_io_signature(1, 1, sizeof(gr_complex)),
-                            gr_make_io_signature(1, 1, sizeof(gr_complex)), decimation)
-    {
-        grhip_detail::check(grhip_freq_xlating_fir_filter_ccc_create(&d_h, decimation, (const float *)taps.data(),
-                                                                     taps.size(), center_freq, sampling_freq, device));
-        set_history(grhip_freq_xlating_fir_filter_ccc_history(d_h));
-    }
-    friend grhip_freq_xlating_fir_filter_ccc_sptr grhip_make_freq_xlating_fir_filter_ccc(
-        int, const std::vector<gr_complex> &, double, double, int);
-public:
-    ~grhip_freq_xlating_fir_filter_ccc_blk() { grhip_freq_xlating_fir_filter_ccc_destroy(d_h); }
-    void set_center_freq(double f) { grhip_detail::check(grhip_freq_xlating_fir_filter_ccc_set_center_freq(d_h, f)); }
-    void set_taps(const std::vector<gr_complex> &taps)
-    {
-        grhip_detail::check(grhip_freq_xlating_fir_filter_ccc_set_taps(d_h, (const float *)taps.data(), taps.size()));
-    }
-    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
-    {
-        int r = grhip_freq_xlating_fir_filter_ccc_work(d_h, noutput_items, in[0], out[0]);
-        grhip_detail::check(r);
-        if (r == 0) set_history(grhip_freq_xlating_fir_filter_ccc_history(d_h));
-        return r;
-    }
-};
-inline grhip_freq_xlating_fir_filter_ccc_sptr grhip_make_freq_xlating_fir_filter_ccc(
-    int decimation, const std::vector<gr_complex> &taps, double center_freq, double sampling_freq, int device = 0)
-{
-    return gnuradio::get_initial_sptr(
-        new grhip_freq_xlating_fir_filter_ccc_blk(decimation, taps, center_freq, sampling_freq, device));
-}
 
 // ---------------------------------------------------------------------------
 // gr_quadrature_demod_cf
