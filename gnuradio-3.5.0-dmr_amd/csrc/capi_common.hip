@@ -177,6 +177,39 @@ int get_device_tables(int device, const DeviceTables **out)
     return GRHIP_OK;
 }
 
+// What each kernel may use beyond 48 KB of dynamic LDS and how many CUs there are, per device: a handle on a second
+// device needs the attribute raised there too, and launches from several threads share the cache.
+static std::mutex g_launch_mutex;
+static std::map<std::pair<int, const void *>, size_t> g_lds_allowed;
+static std::map<int, int> g_cus;
+
+int allow_lds(const void *kernel, size_t bytes)
+{
+    if (bytes <= 48 * 1024) return GRHIP_OK;
+    int dev = 0;
+    GRHIP_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_launch_mutex);
+    size_t &allowed = g_lds_allowed[{dev, kernel}];
+    if (bytes <= allowed) return GRHIP_OK;
+    GRHIP_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    allowed = bytes;
+    return GRHIP_OK;
+}
+
+int device_cus()
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    std::lock_guard<std::mutex> lk(g_launch_mutex);
+    auto it = g_cus.find(dev);
+    if (it == g_cus.end()) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
+        it = g_cus.emplace(dev, n).first;
+    }
+    return it->second;
+}
+
 }  // namespace grhip
 
 using namespace grhip;

@@ -315,18 +315,6 @@ fft4096_kernel(const float *__restrict__ window, const float2 *__restrict__ twid
     }
 }
 
-static int fft_num_cus()
-{
-    static int n_cus = 0;
-    if (n_cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            n = 0;
-        n_cus = n > 0 ? n : 256;
-    }
-    return n_cus;
-}
-
 template <bool FWD>
 static void launch_fft4096(int shift, const float *window, const float2 *twiddle, const float2 *in, float2 *out,
                            long long nvec, hipStream_t st)
@@ -334,7 +322,7 @@ static void launch_fft4096(int shift, const float *window, const float2 *twiddle
     // at most 2^31 - 1 vectors per launch (8 TB of samples): the caller's sizes are far below
     const int nv = (int)nvec;
     const int mode = (window ? 1 : 0) | (shift ? 2 : 0);
-    const long long cap = (long long)fft4096_wg_per_cu(mode) * fft_num_cus();
+    const long long cap = (long long)fft4096_wg_per_cu(mode) * device_cus();
     const dim3 grid((unsigned)(nvec < cap ? nvec : cap));
     switch (mode) {
     case 0: hipLaunchKernelGGL((fft4096_kernel<FWD, 0>), grid, dim3(256), 0, st, window, twiddle, in, out, nv); break;
@@ -365,21 +353,12 @@ int launch_fft(int N, int forward, int shift, const float *window, const float2 
     }
     size_t lds = (size_t)N * 2 * sizeof(float2);
     const int nthr = N / 4 >= 256 ? 256 : (N / 4 <= 64 ? 64 : N / 4);
-    static size_t cfg_f = 0, cfg_b = 0;
     if (forward) {
-        if (lds > 48 * 1024 && lds > cfg_f) {
-            GRHIP_HIP(hipFuncSetAttribute((const void *)fft_kernel<true>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            cfg_f = lds;
-        }
+        if (int rc = allow_lds((const void *)fft_kernel<true>, lds)) return rc;
         hipLaunchKernelGGL(fft_kernel<true>, dim3((unsigned)nvec), dim3(nthr), lds, st, N, shift, window,
                            twiddle, in, out);
     } else {
-        if (lds > 48 * 1024 && lds > cfg_b) {
-            GRHIP_HIP(hipFuncSetAttribute((const void *)fft_kernel<false>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            cfg_b = lds;
-        }
+        if (int rc = allow_lds((const void *)fft_kernel<false>, lds)) return rc;
         hipLaunchKernelGGL(fft_kernel<false>, dim3((unsigned)nvec), dim3(nthr), lds, st, N, shift, window,
                            twiddle, in, out);
     }
@@ -747,16 +726,12 @@ template <int M, int NT, bool IL = false>
 static int launch_pfb_os1_nt(const PfbArgs &a, size_t lds, hipStream_t st)
 {
     const int TT = 512;
-    static size_t cfg = 0;
-    if (lds > 48 * 1024 && lds > cfg) {
-        GRHIP_HIP(hipFuncSetAttribute((const void *)pfb_os1_kernel<M, NT, IL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        cfg = lds;
-    }
+    if (int rc = allow_lds((const void *)pfb_os1_kernel<M, NT, IL>, lds)) return rc;
     const long long ntiles = (a.nout + TT - 1) / TT;
     int per_cu = 0;                                    // resident workgroups per CU (registers and LDS both count)
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)pfb_os1_kernel<M, NT, IL>, 64 * M, lds) != hipSuccess || per_cu < 1)
         per_cu = 1;
-    const long long cap = (long long)per_cu * fft_num_cus();
+    const long long cap = (long long)per_cu * device_cus();
     hipLaunchKernelGGL((pfb_os1_kernel<M, NT, IL>), dim3((unsigned)(ntiles < cap ? ntiles : cap)), dim3(64 * M), lds, st, a, ntiles);
     GRHIP_HIP(hipGetLastError());
     return GRHIP_OK;
@@ -1098,10 +1073,9 @@ static int launch_pfb_fir_t_tp(const PfbArgs &a, hipStream_t st)
     const int XSW = NS + (R > 1 ? NS / R : 0) + 1;
     const size_t lds = ((size_t)TT * (M + 1) + (size_t)4 * XSW) * sizeof(float2) + (size_t)4 * tpfp * sizeof(float);
     if (lds > 150 * 1024) return -1;
-    if (lds > 48 * 1024)
-        GRHIP_HIP(hipFuncSetAttribute((const void *)pfb_fir_t_kernel<R, M, TP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = allow_lds((const void *)pfb_fir_t_kernel<R, M, TP>, lds)) return rc;
     const long long ntiles = (a.nout + TT - 1) / TT;
-    const long long cap = M < 64 ? (long long)fft_num_cus() * (lds > 80 * 1024 ? 1 : 2) : ntiles;      // (M = 64 / 128: one tile per workgroup)
+    const long long cap = M < 64 ? (long long)device_cus() * (lds > 80 * 1024 ? 1 : 2) : ntiles;      // (M = 64 / 128: one tile per workgroup)
     hipLaunchKernelGGL((pfb_fir_t_kernel<R, M, TP>), dim3((unsigned)(ntiles < cap ? ntiles : cap)), dim3(256), lds, st, a);
     GRHIP_HIP(hipGetLastError());
     if (M <= 64) return GRHIP_OK;                      // (the kernel has done the DFT)
@@ -1429,7 +1403,7 @@ static void launch_fft16x_t(int shift, const float *window, const float2 *twiddl
 {
     constexpr int VPG = 4096 / N;
     const long long ngroups = (nvec + VPG - 1) / VPG;
-    const long long cap = 3LL * fft_num_cus();
+    const long long cap = 3LL * device_cus();
     const dim3 grid((unsigned)(ngroups < cap ? ngroups : cap));
     const int nv = (int)nvec;
     switch ((window ? 1 : 0) | (shift ? 2 : 0)) {
@@ -1525,7 +1499,7 @@ template <bool FWD>
 static void launch_fft8192_t(int shift, const float *window, const float2 *twiddle, const float2 *in, float2 *out,
                              long long nvec, hipStream_t st)
 {
-    const long long cap = (window ? 2LL : 3LL) * fft_num_cus();
+    const long long cap = (window ? 2LL : 3LL) * device_cus();
     const dim3 grid((unsigned)(nvec < cap ? nvec : cap));
     const int nv = (int)nvec;
     switch ((window ? 1 : 0) | (shift ? 2 : 0)) {
@@ -1793,7 +1767,7 @@ static int launch_fftfilt4096_t(const void *in, long long nin, const void *hist,
     constexpr long long ISZ = REAL ? 4 : 8;
     const long long max_blocks = (0x7fff0000LL / ISZ - 2 * OLS_N) / L;
     const long long nblk_all = (nin + L - 1) / L;
-    const long long cap = 3LL * fft_num_cus();
+    const long long cap = 3LL * device_cus();
     for (long long b0 = 0; b0 < nblk_all; b0 += max_blocks) {
         const long long nb = nblk_all - b0 < max_blocks ? nblk_all - b0 : max_blocks;
         const long long i0 = b0 * L, o0 = b0 * (L / decim);

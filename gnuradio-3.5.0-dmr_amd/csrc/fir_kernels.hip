@@ -518,30 +518,23 @@ fir_generic_win_kernel(const float *__restrict__ taps_rev, int ntaps, const floa
     }
 }
 
-static int g_gt_cus = 0;
-static const bool g_generic_no_window = getenv("GRHIP_GENERIC_NO_WINDOW") != nullptr;      // (A/B: the (A') kernel on every shape)
+#ifdef GRHIP_DIAG       // diagnostic builds only: the (A') kernel on every shape (A/B)
+static const bool g_generic_no_window = getenv("GRHIP_GENERIC_NO_WINDOW") != nullptr;
+#else
+static constexpr bool g_generic_no_window = false;
+#endif
 template <int KIND>
 static int launch_generic_tiled(const float *taps_rev, int ntaps, const void *in, void *out, long long n_out, int decim,
                                 const float2 *gtab, hipStream_t st)
 {
     const int per_row = GT_NT + (ntaps + decim - 1) / decim + 2;
     const size_t lds = (((size_t)decim * per_row * 8 + 15) & ~(size_t)15) + (size_t)(ntaps + 1) * (KIND == FIR_CCC ? 8 : 4);
-    static size_t cfg = 0;
-    if (lds > 64 * 1024 && lds > cfg) {
-        GRHIP_HIP(hipFuncSetAttribute((const void *)fir_generic_tiled_kernel<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        cfg = lds;
-    }
-    if (g_gt_cus == 0) {
-        int dev = 0, n = 0;
-        GRHIP_HIP(hipGetDevice(&dev));
-        GRHIP_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-        g_gt_cus = n > 0 ? n : 256;
-    }
+    if (int rc = allow_lds((const void *)fir_generic_tiled_kernel<KIND>, lds)) return rc;
     const long long ntiles = (n_out + GT_NT - 1) / GT_NT;
     long long per_cu = (long long)(160 * 1024) / (long long)(lds + 512);
     if (per_cu > 8) per_cu = 8;
     if (per_cu < 1) per_cu = 1;
-    long long grid = per_cu * g_gt_cus;
+    long long grid = per_cu * device_cus();
     if (grid > ntiles) grid = ntiles;
     const long long n_in = (n_out - 1) * decim + ntaps;               // what the caller guarantees readable
     hipLaunchKernelGGL(fir_generic_tiled_kernel<KIND>, dim3((unsigned)grid), dim3(GT_T), lds, st, taps_rev, ntaps,
@@ -557,11 +550,7 @@ static int launch_generic_win(const float *taps_rev, int ntaps, const void *in, 
 {
     const int kmax = (ntaps + D - 1) / D;
     const size_t lds = (size_t)D * GT_R * (GW_T + (kmax + GT_R - 1) / GT_R + 2) * 8 + GW_T * 8 + (GRHIP_GW_TAPS_LDS ? (size_t)ntaps * 8 : 0);
-    static size_t cfg = 0;
-    if (lds > 64 * 1024 && lds > cfg) {
-        GRHIP_HIP(hipFuncSetAttribute((const void *)fir_generic_win_kernel<KIND, D, DEMOD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        cfg = lds;
-    }
+    if (int rc = allow_lds((const void *)fir_generic_win_kernel<KIND, D, DEMOD>, lds)) return rc;
     // one workgroup per tile (nothing is set up per workgroup: the taps are scalar loads): the dispatcher hands a CU its
     // next tile when one is done, so a stream of a few tiles per CU -- 10 M samples are 9.5 -- does not wait for the
     // workgroups that drew one tile more (a persistent grid of 4 per CU: 80 against 84.5 Gsamples/s on one 10 M-sample capture)
@@ -577,13 +566,11 @@ static int launch_generic_win(const float *taps_rev, int ntaps, const void *in, 
 
 template <int KIND, bool SEQ>
 static int launch_generic_inst(const float *taps_rev, int ntaps, const void *in, void *out, long long n_out, int decim,
-                               size_t sh, hipStream_t st)
+                               const float2 *gtab, size_t sh, hipStream_t st)
 {
-    dim3 grid((unsigned)((n_out + 255) / 256)), block(256);
-    if (sh > 64 * 1024)
-        GRHIP_HIP(hipFuncSetAttribute((const void *)fir_generic_kernel<KIND, SEQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-    hipLaunchKernelGGL((fir_generic_kernel<KIND, SEQ>), grid, block, sh, st, taps_rev, ntaps, (const float *)in, (float *)out, n_out,
-                       decim, (const float2 *)nullptr);
+    if (int rc = allow_lds((const void *)fir_generic_kernel<KIND, SEQ>, sh)) return rc;
+    hipLaunchKernelGGL((fir_generic_kernel<KIND, SEQ>), dim3((unsigned)((n_out + 255) / 256)), dim3(256), sh, st, taps_rev, ntaps,
+                       (const float *)in, (float *)out, n_out, decim, gtab);
     GRHIP_HIP(hipGetLastError());
     return GRHIP_OK;
 }
@@ -639,34 +626,18 @@ int launch_fir_generic(FirKind kind, const float *taps_rev, int ntaps, const voi
     if (seq) {
         if (gtab) return fail(GRHIP_EINVAL, "sequential-order FIR has no rotator epilogue");
         switch (kind) {
-        case FIR_FFF: return launch_generic_inst<FIR_FFF, true>(taps_rev, ntaps, in, out, n_out, decim, sh, st);
-        case FIR_CCF: return launch_generic_inst<FIR_CCF, true>(taps_rev, ntaps, in, out, n_out, decim, sh, st);
-        case FIR_CCC: return launch_generic_inst<FIR_CCC, true>(taps_rev, ntaps, in, out, n_out, decim, sh, st);
+        case FIR_FFF: return launch_generic_inst<FIR_FFF, true>(taps_rev, ntaps, in, out, n_out, decim, nullptr, sh, st);
+        case FIR_CCF: return launch_generic_inst<FIR_CCF, true>(taps_rev, ntaps, in, out, n_out, decim, nullptr, sh, st);
+        case FIR_CCC: return launch_generic_inst<FIR_CCC, true>(taps_rev, ntaps, in, out, n_out, decim, nullptr, sh, st);
         default: return fail(GRHIP_EINVAL, "sequential-order FIR: no such kind");
         }
     }
     // real-input kinds: one output per lane (gtab: the rotator epilogue of the real-input xlating kinds)
     if (kind == FIR_FCC || kind == FIR_SCC || kind == FIR_FSF) {
         if (gtab && kind == FIR_FSF) return fail(GRHIP_EINVAL, "fsf has no rotator epilogue");
-        dim3 grid((unsigned)((n_out + 255) / 256)), block(256);
-        if (kind == FIR_FCC) {
-            if (sh > 64 * 1024)
-                GRHIP_HIP(hipFuncSetAttribute((const void *)fir_generic_kernel<FIR_FCC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-            hipLaunchKernelGGL(fir_generic_kernel<FIR_FCC>, grid, block, sh, st, taps_rev, ntaps, (const float *)in, (float *)out, n_out,
-                               decim, gtab);
-        } else if (kind == FIR_SCC) {
-            if (sh > 64 * 1024)
-                GRHIP_HIP(hipFuncSetAttribute((const void *)fir_generic_kernel<FIR_SCC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-            hipLaunchKernelGGL(fir_generic_kernel<FIR_SCC>, grid, block, sh, st, taps_rev, ntaps, (const float *)in, (float *)out, n_out,
-                               decim, gtab);
-        } else {
-            if (sh > 64 * 1024)
-                GRHIP_HIP(hipFuncSetAttribute((const void *)fir_generic_kernel<FIR_FSF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-            hipLaunchKernelGGL(fir_generic_kernel<FIR_FSF>, grid, block, sh, st, taps_rev, ntaps, (const float *)in, (float *)out, n_out,
-                               decim, gtab);
-        }
-        GRHIP_HIP(hipGetLastError());
-        return GRHIP_OK;
+        if (kind == FIR_FCC) return launch_generic_inst<FIR_FCC, false>(taps_rev, ntaps, in, out, n_out, decim, gtab, sh, st);
+        if (kind == FIR_SCC) return launch_generic_inst<FIR_SCC, false>(taps_rev, ntaps, in, out, n_out, decim, gtab, sh, st);
+        return launch_generic_inst<FIR_FSF, false>(taps_rev, ntaps, in, out, n_out, decim, gtab, sh, st);
     }
     // the tiled form of the same arithmetic wherever it applies: complex data, a tile's worth of outputs, a decimation
     // and a tap count whose tile fits LDS (16-byte loads: the stream on an 8-byte boundary is served by the range check
@@ -684,32 +655,11 @@ int launch_fir_generic(FirKind kind, const float *taps_rev, int ntaps, const voi
         return ccc ? launch_generic_tiled<FIR_CCC>(taps_rev, ntaps, in, out, n_out, decim, gtab, st)
                    : launch_generic_tiled<FIR_CCF>(taps_rev, ntaps, in, out, n_out, decim, gtab, st);
     }
-    dim3 grid((unsigned)((n_out + 255) / 256)), block(256);
     switch (kind) {
-    case FIR_FFF:
-        if (sh > 64 * 1024)
-            GRHIP_HIP(hipFuncSetAttribute((const void *)fir_generic_kernel<FIR_FFF>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL(fir_generic_kernel<FIR_FFF>, grid, block, sh, st, taps_rev, ntaps,
-                           (const float *)in, (float *)out, n_out, decim, gtab);
-        break;
-    case FIR_CCF:
-        if (sh > 64 * 1024)
-            GRHIP_HIP(hipFuncSetAttribute((const void *)fir_generic_kernel<FIR_CCF>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL(fir_generic_kernel<FIR_CCF>, grid, block, sh, st, taps_rev, ntaps,
-                           (const float *)in, (float *)out, n_out, decim, gtab);
-        break;
-    default:
-        if (sh > 64 * 1024)
-            GRHIP_HIP(hipFuncSetAttribute((const void *)fir_generic_kernel<FIR_CCC>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-        hipLaunchKernelGGL(fir_generic_kernel<FIR_CCC>, grid, block, sh, st, taps_rev, ntaps,
-                           (const float *)in, (float *)out, n_out, decim, gtab);
-        break;
+    case FIR_FFF: return launch_generic_inst<FIR_FFF, false>(taps_rev, ntaps, in, out, n_out, decim, gtab, sh, st);
+    case FIR_CCF: return launch_generic_inst<FIR_CCF, false>(taps_rev, ntaps, in, out, n_out, decim, gtab, sh, st);
+    default: return launch_generic_inst<FIR_CCC, false>(taps_rev, ntaps, in, out, n_out, decim, gtab, sh, st);
     }
-    GRHIP_HIP(hipGetLastError());
-    return GRHIP_OK;
 }
 
 // ===========================================================================
@@ -1061,22 +1011,12 @@ int launch_fir_hidec(bool ctaps, const float *taps_padded, int ntaps, int decim,
     const int v1 = hidec_sub_log(decim);
     const int nsub = 1 << v1, sub = ((HIDEC_LDS_SAMPLES >> v1) + 2) | 1;
     const size_t lds = (size_t)nsub * sub * 8 + (size_t)(ntaps + 2 * decim + 64) * (ctaps ? 2 : 1) * 4;
-    static int n_cus = 0;
-    if (n_cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-        n_cus = n > 0 ? n : 256;
-    }
     const long long per_cu = lds <= 53 * 1024 ? 3 : (lds <= 80 * 1024 ? 2 : 1);
-    const long long cap = per_cu * n_cus;
+    const long long cap = per_cu * device_cus();
     const unsigned blocks = (unsigned)(ntiles < cap ? ntiles : cap);
 #define GRHIP_HIDEC(C, V, P)                                                                                            \
     do {                                                                                                                \
-        static size_t cfg = 0;                                                                                          \
-        if (lds > 48 * 1024 && lds > cfg) {                                                                             \
-            GRHIP_HIP(hipFuncSetAttribute((const void *)fir_hidec_kernel<C, V, P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            cfg = lds;                                                                                                  \
-        }                                                                                                               \
+        if (int rc = allow_lds((const void *)fir_hidec_kernel<C, V, P>, lds)) return rc;                                \
         hipLaunchKernelGGL((fir_hidec_kernel<C, V, P>), dim3(blocks), dim3(256), lds, st, x, n_in, taps_padded, ntaps, decim, \
                            G, n_out, y, gtab, etab, vtab, ntiles);                                                      \
     } while (0)
@@ -1108,9 +1048,7 @@ int launch_fir_hidec_demod(const float *taps_padded, int ntaps, int decim, const
     const int v1 = hidec_sub_log(decim);
     const int nsub = 1 << v1, sub = ((HIDEC_LDS_SAMPLES >> v1) + 2) | 1;
     const size_t lds = (size_t)nsub * sub * 8 + (size_t)(ntaps + 2 * decim + 64) * 4;
-    int dev = 0, n_cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cus < 1)
-        n_cus = 256;
+    const int n_cus = device_cus();
     long long per_cu = lds <= 53 * 1024 ? 3 : (lds <= 80 * 1024 ? 2 : 1);
     if (max_wg_per_cu > 0 && per_cu > max_wg_per_cu) per_cu = max_wg_per_cu;
     if (n_streams < 1 || n_lo < 0 || n_lo > n_in) return fail(GRHIP_EINVAL, "high-decimation FIR + demodulator: bad batch arguments");
@@ -1119,11 +1057,7 @@ int launch_fir_hidec_demod(const float *taps_padded, int ntaps, int decim, const
     const unsigned blocks = (unsigned)(nids < cap ? nids : cap);
 #define GRHIP_HIDEC_D(V)                                                                                                \
     do {                                                                                                                \
-        static size_t cfg = 0;                                                                                          \
-        if (lds > 48 * 1024 && lds > cfg) {                                                                             \
-            GRHIP_HIP(hipFuncSetAttribute((const void *)fir_hidec_kernel<false, V, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            cfg = lds;                                                                                                  \
-        }                                                                                                               \
+        if (int rc = allow_lds((const void *)fir_hidec_kernel<false, V, true, true>, lds)) return rc;                  \
         hipLaunchKernelGGL((fir_hidec_kernel<false, V, true, true>), dim3(blocks), dim3(256), lds, st, x, n_in, taps_padded, ntaps, decim, \
                            G, n_out, (float2 *)nullptr, (const float2 *)nullptr, etab, vtab, ntiles, d_out, gain, y_prev, y_last, atan_tab, \
                            n_streams, x_stride, d_stride, n_lo);                                                        \

@@ -1364,24 +1364,13 @@ __global__ void __launch_bounds__(rs::THREADS, 1) fir_mfma_rs_kernel(const FirMf
 
 #endif  // GRHIP_DIAG
 
-static int g_mf_cus = 0;
-
 template <int D, int KS, bool PREMIX, int EPI, bool TAPQ = false>
 static int launch_mfma_inst(const FirMfmaArgs &a, hipStream_t st)
 {
     using G = Geo<D, KS>;
     auto kern = fir_mfma_kernel<D, KS, PREMIX, EPI, TAPQ>;
-    static bool configured = false;
-    if (!configured) {
-        GRHIP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        configured = true;
-    }
-    if (g_mf_cus == 0) {
-        int dev = 0, n = 0;
-        GRHIP_HIP(hipGetDevice(&dev));
-        GRHIP_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-        g_mf_cus = n > 0 ? n : 256;
-    }
+    if (int rc = allow_lds((const void *)kern, G::LDS)) return rc;
+    const int n_cus = device_cus(), cus = a.max_cus > 0 && a.max_cus < n_cus ? a.max_cus : n_cus;
     const long long tiles = ((a.n_out + mf::NTE - 1) / mf::NTE) * a.n_streams;
     // The role-split kernel (one 768-lane workgroup per CU, the whole register file) wherever the FIR has its CUs to
     // itself; a caller that runs another kernel on the same CUs (max_wg_per_cu = 1: the chain's clock recovery beside
@@ -1395,12 +1384,8 @@ static int launch_mfma_inst(const FirMfmaArgs &a, hipStream_t st)
     if (role_split) {
         using R = GeoRS<D, KS>;
         auto kern_rs = fir_mfma_rs_kernel<D, KS, PREMIX, EPI>;
-        static bool configured_rs = false;
-        if (!configured_rs) {
-            GRHIP_HIP(hipFuncSetAttribute((const void *)kern_rs, hipFuncAttributeMaxDynamicSharedMemorySize, R::LDS));
-            configured_rs = true;
-        }
-        long long grid = a.max_cus > 0 && a.max_cus < g_mf_cus ? a.max_cus : g_mf_cus;
+        if (int rc = allow_lds((const void *)kern_rs, R::LDS)) return rc;
+        long long grid = cus;
         if (grid > tiles) grid = tiles;
         hipLaunchKernelGGL(kern_rs, dim3((unsigned)grid), dim3(rs::THREADS), R::LDS, st, a);
         GRHIP_HIP(hipGetLastError());
@@ -1412,7 +1397,7 @@ static int launch_mfma_inst(const FirMfmaArgs &a, hipStream_t st)
     if (wgs > GRHIP_MF_WGS) wgs = GRHIP_MF_WGS;
     if (a.max_wg_per_cu > 0 && wgs > a.max_wg_per_cu) wgs = a.max_wg_per_cu;
     if (wgs < 1) wgs = 1;
-    long long grid = (long long)wgs * (a.max_cus > 0 && a.max_cus < g_mf_cus ? a.max_cus : g_mf_cus);
+    long long grid = (long long)wgs * cus;
     if (grid > tiles) grid = tiles;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(mf::THREADS), G::LDS, st, a);
     GRHIP_HIP(hipGetLastError());

@@ -169,19 +169,10 @@ int launch_realin_inst(const float *hp, int Tq, const void *x, long long n_in, f
                        hipStream_t st)
 {
     const size_t lds = ri_lds_bytes(D, Tq);
-    if (lds > 64 * 1024)
-        GRHIP_HIP(hipFuncSetAttribute((const void *)fir_realin_kernel<T, D, ROT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (int rc = allow_lds((const void *)fir_realin_kernel<T, D, ROT>, lds)) return rc;
     const long long ntiles = (n_out + RI_NT - 1) / RI_NT;
-    int cus = 256;
-    {
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        }
-    }
     const int per_cu = lds * 2 <= 160 * 1024 ? 2 : 1;
-    long long grid = (long long)cus * per_cu;
+    long long grid = (long long)device_cus() * per_cu;
     if (grid > ntiles) grid = ntiles;
     hipLaunchKernelGGL((fir_realin_kernel<T, D, ROT>), dim3((unsigned)grid), dim3(RI_T), lds, st, (const T *)x, n_in,
                        (cfloat_p)hp, Tq, y, n_out, gtab, ntiles);

@@ -571,25 +571,12 @@ __global__ void __launch_bounds__(TILED_THREADS, tiled_wg_per_cu(D, PREMIX, EPI)
 #endif
 }
 
-static int g_num_cus = 0;
-
 template <int D, bool CTAPS, bool PREMIX, int EPI, int FP = 0>
 static int launch_tiled_inst(const FirTiledArgs &a, hipStream_t st)
 {
     size_t lds = tiled_lds_bytes(D, a.Tq);
     auto kern = fir_tiled_kernel<D, CTAPS, PREMIX, EPI, FP>;
-    static size_t configured = 0;   // per instantiation
-    if (lds > 48 * 1024 && lds > configured) {
-        GRHIP_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds));
-        configured = lds;
-    }
-    if (g_num_cus == 0) {
-        int dev = 0, n = 0;
-        GRHIP_HIP(hipGetDevice(&dev));
-        GRHIP_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-        g_num_cus = n > 0 ? n : 256;
-    }
+    if (int rc = allow_lds((const void *)kern, lds)) return rc;
     constexpr int NEW_PER_TILE = EPI == EPI_DEMOD ? TILED_NT - TILED_R * (TILED_THREADS / 64) : TILED_NT;
     const long long tiles = ((a.n_out + NEW_PER_TILE - 1) / NEW_PER_TILE) * a.n_streams;
     int wgs = tiled_wg_per_cu(D, PREMIX, EPI);
@@ -600,7 +587,7 @@ static int launch_tiled_inst(const FirTiledArgs &a, hipStream_t st)
 #endif
     const int fit = (int)((160 * 1024) / (lds + 256));                 // what the LDS tile allows
     if (wgs > fit) wgs = fit < 1 ? 1 : fit;
-    long long grid = (long long)wgs * g_num_cus;   // persistent workgroups
+    long long grid = (long long)wgs * device_cus();   // persistent workgroups
     if (grid > tiles) grid = tiles;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(TILED_THREADS), lds, st, a);
     GRHIP_HIP(hipGetLastError());

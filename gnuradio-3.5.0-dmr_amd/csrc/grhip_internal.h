@@ -186,4 +186,8 @@ struct DeviceTables {
 };
 int get_device_tables(int device, const DeviceTables **out);
 
+// launch limits of the calling thread's current device (cached per device; launchers run with the handle's device bound)
+int allow_lds(const void *kernel, size_t bytes);   // let `kernel` launch with `bytes` of dynamic LDS here
+int device_cus();                                  // the device's CU count (256 when the runtime cannot say)
+
 }  // namespace grhip

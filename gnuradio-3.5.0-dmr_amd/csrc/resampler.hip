@@ -217,7 +217,8 @@ int prepare_kind()
 {
     void *k[] = {kernel_ptr<T, H, true, 1>(), kernel_ptr<T, H, false, 1>(), kernel_ptr<T, H, false, 2>(),
                  kernel_ptr<T, H, false, 3>(), kernel_ptr<T, H, false, 4>(), kernel_ptr<T, H, false, 8>()};
-    for (void *f : k) GRHIP_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RS_LDS_MAX));
+    for (void *f : k)
+        if (int rc = allow_lds(f, RS_LDS_MAX)) return rc;
     return GRHIP_OK;
 }
 

@@ -59,6 +59,23 @@ def test_product_never_references_the_oracle():
     assert not bad, bad
 
 
+def test_launch_limits_come_from_one_place():
+    # the per-device LDS attribute and CU count live in capi_common.hip (allow_lds, device_cus); the chain's
+    # create-time query for its CU masks is the one other reader of the CU count
+    csrc = os.path.join(PKG, "csrc")
+    where = {"hipFuncSetAttribute": set(), "hipDeviceAttributeMultiprocessorCount": set()}
+    for f in os.listdir(csrc):
+        if not f.endswith((".hip", ".h", ".inc")):
+            continue
+        s = open(os.path.join(csrc, f), errors="ignore").read()
+        for name in where:
+            if name in s:
+                where[name].add(f)
+    assert where["hipFuncSetAttribute"] == {"capi_common.hip"}, where
+    assert where["hipDeviceAttributeMultiprocessorCount"] <= {"capi_common.hip", "capi_chain.hip"}, where
+    assert "capi_common.hip" in where["hipDeviceAttributeMultiprocessorCount"], where
+
+
 def test_workload_shapes(wl):
     x = wl.fsk4_capture(40_000, stream_id=5)
     assert x.dtype == np.complex64 and len(x) == 40_000

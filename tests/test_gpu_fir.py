@@ -72,6 +72,22 @@ def test_fir_generic_window_kernel_shapes(gpu, po, kind, ntaps, decim):
     assert bits_equal(got, ref)
 
 
+def test_fir_generic_tiled_large_lds_on_a_second_device(gpu, po):
+    """a handle on device 1 in a process that has launched the same kernel on device 0: decimation 3 with 3000 taps is
+    the bit-exact mode's LDS-tiled kernel with about 72 KB of LDS, which needs the dynamic-LDS limit raised on each device"""
+    if gpu.device_count() < 2:
+        pytest.skip("fewer than two devices visible")
+    rng = np.random.default_rng(3003)
+    ntaps, decim, n = 3000, 3, 5000
+    x = _rand_c(rng, n * decim + ntaps - 1)
+    taps = _rand_c(rng, ntaps)
+    ref = po.fir_ccc(taps, x, n, decim)
+    for dev in (0, 1):
+        blk = gpu.fir_filter_ccc(decim, taps, device=dev)
+        blk.set_mode(gpu.MODE_GENERIC)
+        assert bits_equal(blk.work(n, x), ref), "device %d" % dev
+
+
 @pytest.mark.parametrize("kind", ["ccf", "ccc"])
 @pytest.mark.parametrize("ntaps,decim", [(1, 1), (3, 1), (64, 1), (65, 2), (256, 4), (255, 4), (256, 1), (31, 8), (40, 3),
                                          (200, 3), (1500, 1), (2049, 5), (600, 8), (700, 16), (1100, 2),
