@@ -16,7 +16,8 @@ __all__ = [
     "fft_vcc", "fft_filter_ccc", "pfb_channelizer_ccf", "pfb_decimator_ccf", "pfb_arb_resampler_ccf", "pfb_arb_resampler_fff",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
     "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
-    "rational_resampler_ccf", "rational_resampler_fff", "rational_resampler_ccc", "design_filter", "dmr_chain", "run_sync_block",
+    "rational_resampler_ccf", "rational_resampler_fff", "rational_resampler_ccc", "design_filter",
+    "pfb_interpolator_ccf", "pfb_synthesis_filterbank_ccf", "dmr_chain", "run_sync_block",
 ]
 
 MODE_FAST = 0
@@ -1445,6 +1446,91 @@ class rational_resampler_fff(_rational_resampler):
 class rational_resampler_ccc(_rational_resampler):
     """blks2.rational_resampler_ccc(interpolation, decimation, taps=None, fractional_bw=None)"""
     _base = rational_resampler_base_ccc
+
+
+# ----------------------------------------------------------------------------
+# gr.pfb_interpolator_ccf / gr.pfb_synthesis_filterbank_ccf  (filter/gr_pfb_interpolator_ccf.i,
+# filter/gr_pfb_synthesis_filterbank_ccf.i)
+# ----------------------------------------------------------------------------
+class pfb_interpolator_ccf(_interp_fir_filter):
+    """gr.pfb_interpolator_ccf(interp, taps): gr_interp_fir_filter's schedule with the zeros behind the taps.
+    (blks2.pfb_interpolator_ccf designs default taps with optfir; here the taps are required.)"""
+    _prefix = "grhip_pfb_interpolator_ccf"
+    _destroy = "grhip_pfb_interpolator_ccf_destroy"
+
+    def __init__(self, interp, taps, device=0):
+        _Block.__init__(self)
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        f = self._fn("create")
+        f.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_void_p, C.c_size_t, C.c_int]
+        _check(f(C.byref(self._h), _uint_arg(interp), _ptr(t), len(t), int(device)))
+
+    def taps_per_filter(self):
+        return self.history()
+
+    def run_captures_device(self, *args, **kwargs):
+        raise NotImplementedError("pfb_interpolator_ccf has no run_captures_device entry; use work_device")
+
+    def captures_nout(self, n_samples):
+        raise NotImplementedError("pfb_interpolator_ccf has no run_captures_device entry; use work_device")
+
+
+class pfb_synthesis_filterbank_ccf(_Block):
+    """gr.pfb_synthesis_filterbank_ccf(numchans, taps): 1..numchans complex streams in, one stream out at numchans
+    times the rate"""
+    _destroy = "grhip_pfb_synthesis_filterbank_ccf_destroy"
+
+    def __init__(self, numchans, taps, device=0):
+        _Block.__init__(self)
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        self.numchans = int(numchans)
+        f = lib().grhip_pfb_synthesis_filterbank_ccf_create
+        f.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_void_p, C.c_size_t, C.c_int]
+        _check(f(C.byref(self._h), _uint_arg(numchans), _ptr(t), len(t), int(device)))
+
+    def set_taps(self, taps):
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        f = lib().grhip_pfb_synthesis_filterbank_ccf_set_taps
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        _check(f(self._h, _ptr(t), len(t)))
+
+    def set_mode(self, mode):
+        _check(lib().grhip_pfb_synthesis_filterbank_ccf_set_mode(self._h, int(mode)))
+
+    def history(self):
+        return _check(lib().grhip_pfb_synthesis_filterbank_ccf_history(self._h))
+
+    def taps_per_filter(self):
+        return _check(lib().grhip_pfb_synthesis_filterbank_ccf_taps_per_filter(self._h))
+
+    def output_multiple(self):
+        return self.numchans
+
+    def work(self, noutput_items, streams):
+        """gr_sync_interpolator work: streams is a list of 1..numchans complex arrays, each with history()-1 old items
+        in front and at least noutput_items/numchans + history() - 1 items; returns the outputs (none when the call
+        installs latched taps)"""
+        arrs = [np.ascontiguousarray(s, dtype=np.complex64) for s in streams]
+        n = int(noutput_items)
+        M = self.numchans
+        if n >= 0 and n % M == 0 and 1 <= len(arrs) <= M:
+            need = n // M + self.history() - 1
+            for a in arrs:
+                if len(a) < need:
+                    raise ValueError("work: %d outputs need %d items per stream, got %d" % (n, need, len(a)))
+        ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
+        out = np.zeros(max(n, 1), dtype=np.complex64)
+        f = lib().grhip_pfb_synthesis_filterbank_ccf_work
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        r = _check(f(self._h, n, ptrs, len(arrs), _ptr(out)))
+        return out[:r].copy()
+
+    def work_device(self, noutput_items, d_in, stream_stride_items, numsigs, d_out, stream=None):
+        """stream s at d_in + s*stream_stride_items; the outputs are in d_out once `stream` has run"""
+        f = lib().grhip_pfb_synthesis_filterbank_ccf_work_device
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
+        return _check(f(self._h, int(noutput_items), _devptr(d_in), int(stream_stride_items), int(numsigs),
+                        _devptr(d_out), _stream(stream)))
 
 
 # ----------------------------------------------------------------------------

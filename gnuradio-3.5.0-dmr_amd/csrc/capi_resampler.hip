@@ -1,4 +1,5 @@
-// capi_resampler.hip -- gr_rational_resampler_base_XXX and gr_interp_fir_filter_XXX (ccf, fff, ccc): handles and C ABI.
+// capi_resampler.hip -- gr_rational_resampler_base_XXX and gr_interp_fir_filter_XXX (ccf, fff, ccc), and
+// gr_pfb_interpolator_ccf: handles and C ABI.
 //
 // Reference (gnuradio-core/src/lib/filter/):
 //   gr_rational_resampler_base_XXX.cc.t:49-72 (constructor: I or D == 0 throws std::out_of_range), 83-120 (set_taps:
@@ -7,6 +8,9 @@
 //   d_history / history() / set_history(), which hide gr_block's: the scheduler sees history 1, no zeros in front).
 //   gr_interp_fir_filter_XXX.cc.t:72-109 (the same bank; set_history(nt)), 112-145 (work: out[i*I + nf] =
 //   firs[nf]->filter(&in[i])); runtime/gr_sync_interpolator.h:48-53 (output_multiple I).
+//   gr_pfb_interpolator_ccf.cc:69-104 (set_taps: tpf = ceil(ntaps/R), zeros at the END of the taps, filter j gets
+//   padded[j + k*R] through gr_fir_ccf; set_history(tpf)), 122-148 (work: out[n*R + j] = filters[j]->filter(&in[n])):
+//   the interpolator's schedule with another bank.
 //
 // Both run the closed form of resampler.h: output o of a call that starts at c0 = ctr uses filter (c0 + o*D) % I at
 // input (c0 + o*D) / I; a call of n outputs consumes (c0 + n*D) / I items and leaves ctr = (c0 + n*D) % I.  The
@@ -50,6 +54,7 @@ int kind_of(const char *kind, RsKind *k)
 struct grhip_rs_core : HandleBase {
     RsKind kind = RS_CCF;
     bool interp = false;
+    bool pad_end = false;               // gr_pfb_interpolator_ccf: the zeros go behind the taps
     unsigned long long I = 1, D = 1, P = 1, Dp = 1;
     int nt = 1, WP = 0;
     int mode = GRHIP_MODE_FAST;
@@ -61,7 +66,8 @@ struct grhip_rs_core : HandleBase {
     int tw() const { return kind == RS_CCC ? 2 : 1; }
     size_t item() const { return kind == RS_FFF ? 4 : 8; }
 
-    // set_taps (.cc.t:83-99): the taps, zeros in front up to a multiple of I; refuses what the kernel cannot take
+    // set_taps (.cc.t:83-99): the taps, zeros in front up to a multiple of I (behind them for the pfb interpolator,
+    // gr_pfb_interpolator_ccf.cc:82-87); refuses what the kernel cannot take
     int pad_taps(const float *taps, size_t ntaps, std::vector<float> *out) const
     {
         if (ntaps == 0)
@@ -76,12 +82,13 @@ struct grhip_rs_core : HandleBase {
         int rc = rs_config(kind, true, I, D, nt_new, 0, &c);
         if (!rc) rc = rs_config(kind, false, I, D, nt_new, 0, &c);
         if (rc) return rc;
-        out->assign((size_t)((padded - ntaps) * tw()), 0.f);
+        out->assign((size_t)(pad_end ? 0 : (padded - ntaps) * tw()), 0.f);
         out->insert(out->end(), taps, taps + ntaps * tw());
+        out->resize((size_t)(padded * tw()), 0.f);
         return GRHIP_OK;
     }
 
-    const char *name() const { return interp ? "interp_fir_filter" : "rational_resampler_base"; }
+    const char *name() const { return pad_end ? "pfb_interpolator" : interp ? "interp_fir_filter" : "rational_resampler_base"; }
 
     // install_taps (.cc.t:102-120): filter f gets padded[f + k*I], reversed as gr_fir_XXX::set_taps stores them; bank
     // row f = WP zeros, the reversed taps, WP zeros (resampler.hip); row I zeros
@@ -105,9 +112,9 @@ struct grhip_rs_core : HandleBase {
     }
 
     int init(RsKind k, bool is_interp, unsigned long long i, unsigned long long d, const float *taps, size_t ntaps,
-             int device)
+             int device, bool zeros_behind = false)
     {
-        kind = k; interp = is_interp;
+        kind = k; interp = is_interp; pad_end = zeros_behind;
         if (i == 0) return fail(GRHIP_ERANGE, "%s: interpolation must be > 0", name());
         if (d == 0) return fail(GRHIP_ERANGE, "%s: decimation must be > 0", name());
         if (i > RS_MAX_ID || d > RS_MAX_ID) return fail(GRHIP_EINVAL, "%s: interpolation and decimation must be <= 2^20", name());
@@ -222,8 +229,8 @@ struct grhip_rs_core : HandleBase {
     {
         if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
         if ((unsigned long long)noutput_items % I)
-            return fail(GRHIP_EINVAL, "interp_fir_filter: noutput_items %d is not a multiple of the interpolation %llu "
-                                      "(output_multiple)", noutput_items, I);
+            return fail(GRHIP_EINVAL, "%s: noutput_items %d is not a multiple of the interpolation %llu "
+                                      "(output_multiple)", name(), noutput_items, I);
         int rc = bind();
         if (rc) return rc;
         hipStream_t st = pick(stream);
@@ -242,8 +249,8 @@ struct grhip_rs_core : HandleBase {
     {
         if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
         if ((unsigned long long)noutput_items % I)
-            return fail(GRHIP_EINVAL, "interp_fir_filter: noutput_items %d is not a multiple of the interpolation %llu "
-                                      "(output_multiple)", noutput_items, I);
+            return fail(GRHIP_EINVAL, "%s: noutput_items %d is not a multiple of the interpolation %llu "
+                                      "(output_multiple)", name(), noutput_items, I);
         if ((!in || !out) && noutput_items) return fail(GRHIP_EINVAL, "null buffer");
         int rc = bind();
         if (rc) return rc;
@@ -297,12 +304,14 @@ struct grhip_rs_core : HandleBase {
 };
 
 struct grhip_interp_fir_filter : grhip_rs_core {};
+struct grhip_pfb_interpolator_ccf : grhip_rs_core {};
 struct grhip_rational_resampler_base : grhip_rs_core {};
 
 namespace {
 
 template <class H>
-int create_t(H **h, const char *kind, bool interp, long long I, long long D, const float *taps, size_t ntaps, int device)
+int create_t(H **h, const char *kind, bool interp, long long I, long long D, const float *taps, size_t ntaps, int device,
+             bool zeros_behind = false)
 {
     if (!h) return fail(GRHIP_EINVAL, "null handle pointer");
     *h = nullptr;
@@ -312,7 +321,7 @@ int create_t(H **h, const char *kind, bool interp, long long I, long long D, con
     if (I < 0 || D < 0) return fail(GRHIP_ERANGE, "interpolation and decimation must be > 0");
     auto *b = new (std::nothrow) H();
     if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    rc = b->init(k, interp, (unsigned long long)I, (unsigned long long)D, taps, ntaps, device);
+    rc = b->init(k, interp, (unsigned long long)I, (unsigned long long)D, taps, ntaps, device, zeros_behind);
     if (rc) {
         if (b->own_stream) b->destroy();
         delete b;
@@ -383,6 +392,57 @@ int grhip_interp_fir_filter_run_captures_device(grhip_interp_fir_filter *h, int 
 {
     if (!h) return fail(GRHIP_EINVAL, "null handle");
     return h->run_captures_device(n_streams, n_samples, d_in, in_stride_items, d_out, out_stride_items, n_out, stream);
+}
+
+// ---- gr_pfb_interpolator_ccf ----
+int grhip_pfb_interpolator_ccf_create(grhip_pfb_interpolator_ccf **h, unsigned interp, const float *taps, size_t ntaps,
+                                      int device)
+{
+    return create_t(h, "ccf", true, interp, 1, taps, ntaps, device, true);
+}
+
+void grhip_pfb_interpolator_ccf_destroy(grhip_pfb_interpolator_ccf *h)
+{
+    if (!h) return;
+    h->destroy();
+    delete h;
+}
+
+int grhip_pfb_interpolator_ccf_set_taps(grhip_pfb_interpolator_ccf *h, const float *taps, size_t ntaps)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    return h->set_taps(taps, ntaps);
+}
+
+int grhip_pfb_interpolator_ccf_set_mode(grhip_pfb_interpolator_ccf *h, int mode)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    return h->set_mode(mode);
+}
+
+int grhip_pfb_interpolator_ccf_history(const grhip_pfb_interpolator_ccf *h)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    return h->nt;                                        // set_history(d_taps_per_filter), .cc:101
+}
+
+int grhip_pfb_interpolator_ccf_interpolation(const grhip_pfb_interpolator_ccf *h)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    return (int)h->I;
+}
+
+int grhip_pfb_interpolator_ccf_work(grhip_pfb_interpolator_ccf *h, int noutput_items, const void *in, void *out)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    return h->work(noutput_items, in, out);
+}
+
+int grhip_pfb_interpolator_ccf_work_device(grhip_pfb_interpolator_ccf *h, int noutput_items, const void *d_in,
+                                           void *d_out, void *stream)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    return h->work_device(noutput_items, d_in, d_out, stream);
 }
 
 // ---- gr_rational_resampler_base_XXX ----

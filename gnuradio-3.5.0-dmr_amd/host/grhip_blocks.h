@@ -14,6 +14,8 @@
 //   grhip_pfb_arb_resampler_ccf / _fff       <- gr_pfb_arb_resampler_ccf / _fff (filter/gr_pfb_arb_resampler_ccf.h:96-178)
 //   grhip_interp_fir_filter_XXX              <- gr_interp_fir_filter_XXX (filter/gr_interp_fir_filter_XXX.h.t)
 //   grhip_rational_resampler_base_XXX        <- gr_rational_resampler_base_XXX (filter/gr_rational_resampler_base_XXX.h.t)
+//   grhip_pfb_interpolator_ccf               <- gr_pfb_interpolator_ccf (filter/gr_pfb_interpolator_ccf.h)
+//   grhip_pfb_synthesis_filterbank_ccf       <- gr_pfb_synthesis_filterbank_ccf (filter/gr_pfb_synthesis_filterbank_ccf.h)
 //
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
@@ -773,3 +775,91 @@ GRHIP_RS_BLOCKS(ccf, gr_complex, float)
 GRHIP_RS_BLOCKS(fff, float, float)
 GRHIP_RS_BLOCKS(ccc, gr_complex, gr_complex)
 #undef GRHIP_RS_BLOCKS
+
+// ---------------------------------------------------------------------------
+// gr_pfb_interpolator_ccf  (a gr_sync_interpolator by interp: history tpf; filter/gr_pfb_interpolator_ccf.h)
+// gr_pfb_synthesis_filterbank_ccf  (a gr_sync_interpolator by numchans: 1..numchans inputs, history tpf + 1;
+// filter/gr_pfb_synthesis_filterbank_ccf.h).  set_taps latches; the next work() installs the taps, returns 0 and the
+// history follows (the library's convention, as grhip_interp_fir_filter_XXX).
+// ---------------------------------------------------------------------------
+class grhip_pfb_interpolator_ccf_blk;
+typedef boost::shared_ptr<grhip_pfb_interpolator_ccf_blk> grhip_pfb_interpolator_ccf_sptr;
+class grhip_pfb_interpolator_ccf_blk : public gr_sync_interpolator {
+    grhip_pfb_interpolator_ccf *d_h = nullptr;
+    grhip_pfb_interpolator_ccf_blk(unsigned interp, const std::vector<float> &taps, int device)
+        : gr_sync_interpolator("pfb_interpolator_ccf", gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                               gr_make_io_signature(1, 1, sizeof(gr_complex)), interp)
+    {
+        grhip_detail::check(grhip_pfb_interpolator_ccf_create(&d_h, interp, taps.data(), taps.size(), device));
+        sync_history();
+    }
+    friend grhip_pfb_interpolator_ccf_sptr grhip_make_pfb_interpolator_ccf(unsigned, const std::vector<float> &, int);
+    void sync_history()
+    {
+        int h = grhip_pfb_interpolator_ccf_history(d_h);
+        grhip_detail::check(h);
+        set_history((unsigned)h);                                       // set_history(d_taps_per_filter), .cc:101
+    }
+public:
+    ~grhip_pfb_interpolator_ccf_blk() { grhip_pfb_interpolator_ccf_destroy(d_h); }
+    void set_taps(const std::vector<float> &taps)
+    {
+        grhip_detail::check(grhip_pfb_interpolator_ccf_set_taps(d_h, taps.data(), taps.size()));
+    }
+    void set_mode(int mode) { grhip_detail::check(grhip_pfb_interpolator_ccf_set_mode(d_h, mode)); }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int r = grhip_pfb_interpolator_ccf_work(d_h, noutput_items, in[0], out[0]);
+        grhip_detail::check(r);
+        sync_history();
+        return r;
+    }
+};
+inline grhip_pfb_interpolator_ccf_sptr grhip_make_pfb_interpolator_ccf(unsigned interp, const std::vector<float> &taps,
+                                                                       int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_pfb_interpolator_ccf_blk(interp, taps, device));
+}
+
+class grhip_pfb_synthesis_filterbank_ccf_blk;
+typedef boost::shared_ptr<grhip_pfb_synthesis_filterbank_ccf_blk> grhip_pfb_synthesis_filterbank_ccf_sptr;
+class grhip_pfb_synthesis_filterbank_ccf_blk : public gr_sync_interpolator {
+    grhip_pfb_synthesis_filterbank_ccf *d_h = nullptr;
+    grhip_pfb_synthesis_filterbank_ccf_blk(unsigned numchans, const std::vector<float> &taps, int device)
+        : gr_sync_interpolator("pfb_synthesis_filterbank_ccf", gr_make_io_signature(1, numchans, sizeof(gr_complex)),
+                               gr_make_io_signature(1, 1, sizeof(gr_complex)), numchans)      // .cc:43-46
+    {
+        grhip_detail::check(grhip_pfb_synthesis_filterbank_ccf_create(&d_h, numchans, taps.data(), taps.size(), device));
+        sync_history();
+    }
+    friend grhip_pfb_synthesis_filterbank_ccf_sptr grhip_make_pfb_synthesis_filterbank_ccf(unsigned,
+                                                                                            const std::vector<float> &, int);
+    void sync_history()
+    {
+        int h = grhip_pfb_synthesis_filterbank_ccf_history(d_h);
+        grhip_detail::check(h);
+        set_history((unsigned)h);                                       // set_history(d_taps_per_filter + 1), .cc:103
+    }
+public:
+    ~grhip_pfb_synthesis_filterbank_ccf_blk() { grhip_pfb_synthesis_filterbank_ccf_destroy(d_h); }
+    unsigned taps_per_filter() const { return (unsigned)grhip_pfb_synthesis_filterbank_ccf_taps_per_filter(d_h); }
+    void set_taps(const std::vector<float> &taps)
+    {
+        grhip_detail::check(grhip_pfb_synthesis_filterbank_ccf_set_taps(d_h, taps.data(), taps.size()));
+    }
+    void set_mode(int mode) { grhip_detail::check(grhip_pfb_synthesis_filterbank_ccf_set_mode(d_h, mode)); }
+    // the connected inputs are the streams (numsigs = input_items.size(), .cc:129)
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int r = grhip_pfb_synthesis_filterbank_ccf_work(d_h, noutput_items, in.data(), (int)in.size(), out[0]);
+        grhip_detail::check(r);
+        sync_history();
+        return r;
+    }
+};
+inline grhip_pfb_synthesis_filterbank_ccf_sptr grhip_make_pfb_synthesis_filterbank_ccf(unsigned numchans,
+                                                                                       const std::vector<float> &taps,
+                                                                                       int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_pfb_synthesis_filterbank_ccf_blk(numchans, taps, device));
+}

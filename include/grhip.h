@@ -610,6 +610,78 @@ GRHIP_API int grhip_rational_resampler_base_run_captures_device(grhip_rational_r
                                                                 size_t out_stride_items, size_t *n_out, void *stream);
 
 /* ======================================================================
+ * gr_pfb_interpolator_ccf  (polyphase interpolator: R outputs per input item)
+ *   replaces gr_make_pfb_interpolator_ccf(unsigned interp, const std::vector<float> &taps)
+ *   filter/gr_pfb_interpolator_ccf.cc:40-60 (constructor: a gr_sync_interpolator by interp), 69-104 (set_taps:
+ *   tpf = ceil(ntaps/interp), zeros at the END of the taps -- gr_interp_fir_filter pads in front --, filter j gets
+ *   padded[j + k*interp] through gr_fir_ccf; set_history(tpf)), 122-148 (work: out[n*interp + j] =
+ *   filters[j]->filter(&in[n])).
+ * The schedule, the kernel, the tap-update convention, the modes and the kernel limits are gr_interp_fir_filter's
+ * (GRHIP_MODE_GENERIC: bit-exact against gr_fir_ccf_generic per branch); only the bank differs.
+ * Refused: interp == 0 -> GRHIP_ERANGE; ntaps == 0, noutput_items not a multiple of interp -> GRHIP_EINVAL.
+ * ====================================================================== */
+typedef struct grhip_pfb_interpolator_ccf grhip_pfb_interpolator_ccf;
+GRHIP_API int grhip_pfb_interpolator_ccf_create(grhip_pfb_interpolator_ccf **h, unsigned interp, const float *taps,
+                                                size_t ntaps, int device);
+GRHIP_API void grhip_pfb_interpolator_ccf_destroy(grhip_pfb_interpolator_ccf *h);
+GRHIP_API int grhip_pfb_interpolator_ccf_set_taps(grhip_pfb_interpolator_ccf *h, const float *taps, size_t ntaps);
+GRHIP_API int grhip_pfb_interpolator_ccf_set_mode(grhip_pfb_interpolator_ccf *h, int mode);
+GRHIP_API int grhip_pfb_interpolator_ccf_history(const grhip_pfb_interpolator_ccf *h);         /* tpf (.cc:101) */
+GRHIP_API int grhip_pfb_interpolator_ccf_interpolation(const grhip_pfb_interpolator_ccf *h);
+/* work on HOST buffers (.cc:122-148): in holds noutput_items/interp + history() - 1 items; returns noutput_items (0
+ * when it installs latched taps) */
+GRHIP_API int grhip_pfb_interpolator_ccf_work(grhip_pfb_interpolator_ccf *h, int noutput_items, const void *in,
+                                              void *out);
+/* the same on DEVICE buffers, enqueued on `stream` (NULL: the handle's own stream) */
+GRHIP_API int grhip_pfb_interpolator_ccf_work_device(grhip_pfb_interpolator_ccf *h, int noutput_items, const void *d_in,
+                                                     void *d_out, void *stream);
+
+/* ======================================================================
+ * gr_pfb_synthesis_filterbank_ccf  (polyphase synthesis: 1..numchans streams in, one stream at numchans times the rate)
+ *   replaces gr_make_pfb_synthesis_filterbank_ccf(unsigned numchans, const std::vector<float> &taps)
+ *   filter/gr_pfb_synthesis_filterbank_ccf.cc:41-62 (constructor: a gr_sync_interpolator by numchans = M, 1..M inputs;
+ *   gri_fft_complex(M, true): a FORWARD unnormalised DFT), 71-106 (set_taps: tpf = ceil(ntaps/M), zeros at the END,
+ *   branch f gets h_f[q] = padded[f + q*M]; set_history(tpf + 1)), 122-169 (work);
+ *   gri_fir_filter_with_buffer_XXX.cc.t:41-78 (the branches: delay lines that start at zero and live across calls).
+ * Output vector n of a call (numsigs connected streams, ndiff = M - numsigs, nhalf = ceil(numsigs/2)):
+ *   bin i < nhalf is ins[i][n + i], bins nhalf <= i < nhalf + ndiff are zero, bin i >= nhalf + ndiff is
+ *   ins[i - ndiff][n + i] (.cc:139-156; the offset + i is the reference's `(in+i)[n]`);
+ *   V = forward DFT of the bins; branch f is fed V[M-1-f] and writes out[n*M + f] = sum_q h_f[q] u_f[n-q] (.cc:161-163).
+ * Tap updates as gr_interp_fir_filter: create installs the taps; set_taps latches new ones; the next work call installs
+ * them, clears the delay lines (waiting for the launches that still read them) and returns 0; history() and taps_per_filter() report the installed taps.
+ * Modes: GRHIP_MODE_GENERIC sums every branch in the reference's order (one accumulator, oldest sample first, a product
+ * and a sum per term) over the library's float32 DFT; the FAST modes are one FMA kernel.  The DFT is not the reference's
+ * FFTW bit for bit; with a single connected stream, or M = 1, 2, 4, it is exact and GENERIC equals the reference.
+ * Refused with GRHIP_EINVAL: numchans == 0 or > 256 (the kernels' limit); ntaps == 0; more than 65536 taps per filter;
+ * numsigs outside 1..M; noutput_items not a multiple of M; and numsigs >= 2 with M - 1 > tpf: bin M-1 reads item
+ * n + M - 1 of its stream while the scheduler only provides items up to n + tpf, so the reference reads past its input
+ * there (undefined).  numsigs == 1 fills only bin 0 and is always in range.
+ * ====================================================================== */
+typedef struct grhip_pfb_synthesis_filterbank_ccf grhip_pfb_synthesis_filterbank_ccf;
+GRHIP_API int grhip_pfb_synthesis_filterbank_ccf_create(grhip_pfb_synthesis_filterbank_ccf **h, unsigned numchans,
+                                                        const float *taps, size_t ntaps, int device);
+GRHIP_API void grhip_pfb_synthesis_filterbank_ccf_destroy(grhip_pfb_synthesis_filterbank_ccf *h);
+GRHIP_API int grhip_pfb_synthesis_filterbank_ccf_set_taps(grhip_pfb_synthesis_filterbank_ccf *h, const float *taps,
+                                                          size_t ntaps);
+GRHIP_API int grhip_pfb_synthesis_filterbank_ccf_set_mode(grhip_pfb_synthesis_filterbank_ccf *h, int mode);
+GRHIP_API int grhip_pfb_synthesis_filterbank_ccf_history(const grhip_pfb_synthesis_filterbank_ccf *h);   /* tpf + 1 (.cc:103) */
+GRHIP_API int grhip_pfb_synthesis_filterbank_ccf_taps_per_filter(const grhip_pfb_synthesis_filterbank_ccf *h);
+GRHIP_API int grhip_pfb_synthesis_filterbank_ccf_numchans(const grhip_pfb_synthesis_filterbank_ccf *h);
+/* work on HOST buffers (.cc:122-169): ins[0 .. numsigs) each hold noutput_items/M + tpf items (history() - 1 old ones
+ * in front); out receives noutput_items items.  Returns noutput_items (0 when it installs latched taps). */
+GRHIP_API int grhip_pfb_synthesis_filterbank_ccf_work(grhip_pfb_synthesis_filterbank_ccf *h, int noutput_items,
+                                                      const void *const *ins, int numsigs, void *out);
+/* the same on DEVICE buffers: stream s at d_in + s*stream_stride_items (complex items), as the channeliser's device
+ * entry; d_out 16-byte aligned for full-width stores.  Enqueued on `stream` (NULL: the handle's own stream).  On the
+ * fused kernel's shapes (numchans 2..16, at most 513 taps per filter) the call never waits for the device.  The other
+ * shapes keep a scratch buffer of (noutput_items/numchans + tpf - 1) * numchans complex items in device memory; a call
+ * larger than every earlier one grows it, and that reallocation waits for the device.  Calls that continue a stream
+ * must be enqueued in order (the delay lines are carried in device memory). */
+GRHIP_API int grhip_pfb_synthesis_filterbank_ccf_work_device(grhip_pfb_synthesis_filterbank_ccf *h, int noutput_items,
+                                                             const void *d_in, size_t stream_stride_items, int numsigs,
+                                                             void *d_out, void *stream);
+
+/* ======================================================================
  * gr_framer_sink_1  (the consumer of the correlator's flag bit)
  *   replaces gr_make_framer_sink_1(gr_msg_queue_sptr target_queue)
  *   general/gr_framer_sink_1.h:62-98, general/gr_framer_sink_1.cc:34-66 (states), 90-190 (work):
