@@ -14,6 +14,7 @@ __all__ = [
     "freq_xlating_fir_filter_fcc", "freq_xlating_fir_filter_scf", "freq_xlating_fir_filter_scc", "quadrature_demod_cf", "xlating_demod",
     "clock_recovery_mm_ff", "clock_recovery_mm_cc", "binary_slicer_fb", "correlate_access_code_bb", "pager_slicer_fb", "unpack_k_bits_bb", "framer_sink_1", "framer_sink_1_batch", "stream_to_streams", "streams_to_stream", "vector_to_streams", "stream_to_vector", "head",
     "fft_vcc", "fft_filter_ccc", "pfb_channelizer_ccf", "pfb_decimator_ccf", "pfb_arb_resampler_ccf", "pfb_arb_resampler_fff",
+    "fractional_interpolator_ff", "fractional_interpolator_cc",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
     "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
     "rational_resampler_ccf", "rational_resampler_fff", "rational_resampler_ccc", "design_filter",
@@ -1182,6 +1183,103 @@ class pfb_arb_resampler_fff(_pfb_arb_resampler):
     """gr.pfb_arb_resampler_fff(rate, taps, filter_size=32)"""
     _kind = "fff"
     _dtype = np.float32
+
+
+# ----------------------------------------------------------------------------
+# gr.fractional_interpolator_ff / gr.fractional_interpolator_cc  (filter/gr_fractional_interpolator_ff.i)
+# ----------------------------------------------------------------------------
+class _fractional_interpolator(_Block):
+    _kind = None
+    _dtype = None
+
+    def __init__(self, phase_shift, interp_ratio, device=0):
+        _Block.__init__(self)
+        self._destroy = "grhip_fractional_interpolator_%s_destroy" % self._kind
+        f = self._fn("create")
+        f.argtypes = [C.POINTER(C.c_void_p), C.c_float, C.c_float, C.c_int]
+        _check(f(C.byref(self._h), float(phase_shift), float(interp_ratio), int(device)))
+
+    def _fn(self, name):
+        return getattr(lib(), "grhip_fractional_interpolator_%s_%s" % (self._kind, name))
+
+    def _getf(self, name):
+        f = self._fn(name)
+        f.argtypes = [C.c_void_p]
+        f.restype = C.c_float
+        return float(f(self._h))
+
+    def _setf(self, name, v):
+        f = self._fn(name)
+        f.argtypes = [C.c_void_p, C.c_float]
+        _check(f(self._h, float(v)))
+
+    def mu(self):
+        return self._getf("mu")
+
+    def interp_ratio(self):
+        return self._getf("interp_ratio")
+
+    def set_mu(self, mu):
+        self._setf("set_mu", mu)
+
+    def set_interp_ratio(self, interp_ratio):
+        self._setf("set_interp_ratio", interp_ratio)
+
+    def set_mode(self, mode):
+        _check(self._fn("set_mode")(self._h, int(mode)))
+
+    def history(self):
+        return _check(self._fn("history")(self._h))
+
+    def forecast(self, noutput_items):
+        return _check(self._fn("forecast")(self._h, int(noutput_items)))
+
+    def general_work(self, noutput_items, input_items):
+        """returns (out, consumed)"""
+        x = np.ascontiguousarray(input_items, dtype=self._dtype)
+        out = np.zeros(max(int(noutput_items), 1), dtype=self._dtype)
+        consumed = C.c_int(0)
+        f = self._fn("general_work")
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        n = _check(f(self._h, int(noutput_items), len(x), _ptr(x), _ptr(out), C.byref(consumed)))
+        return out[:n].copy(), consumed.value
+
+    def general_work_device(self, noutput_items, ninput_items, d_in, d_out, stream=None):
+        """returns (produced, consumed); the outputs are in d_out once `stream` has run"""
+        consumed = C.c_int(0)
+        f = self._fn("general_work_device")
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
+        n = _check(f(self._h, int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out),
+                     C.byref(consumed), _stream(stream)))
+        return n, consumed.value
+
+    def run_captures_device(self, n_streams, n_samples, d_in, in_stride_items, d_out, out_stride_items,
+                            stream=None):
+        """n_streams fresh-state captures in one launch; returns the outputs per capture.  d_out=None only returns
+        that number."""
+        n_out = C.c_size_t(0)
+        f = self._fn("run_captures_device")
+        f.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                      C.POINTER(C.c_size_t), C.c_void_p]
+        _check(f(self._h, int(n_streams), int(n_samples), _devptr(d_in), int(in_stride_items), _devptr(d_out),
+                 int(out_stride_items), C.byref(n_out), _stream(stream)))
+        return n_out.value
+
+    def captures_nout(self, n_samples):
+        """outputs of one fresh-state capture of n_samples items"""
+        return self.run_captures_device(1, n_samples, None, n_samples, None, 0)
+
+
+class fractional_interpolator_ff(_fractional_interpolator):
+    """gr.fractional_interpolator_ff(phase_shift, interp_ratio)"""
+    _kind = "ff"
+    _dtype = np.float32
+
+
+class fractional_interpolator_cc(_fractional_interpolator):
+    """gr.fractional_interpolator_cc(phase_shift, interp_ratio)"""
+    _kind = "cc"
+    _dtype = np.complex64
 
 
 # ----------------------------------------------------------------------------

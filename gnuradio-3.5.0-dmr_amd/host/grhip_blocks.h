@@ -12,6 +12,7 @@
 //   gr_fft_vcc_hip (grhip_make_fft_vcc)       <- gr_fft_vcc_fftw, on the abstract gr_fft_vcc base (general/gr_fft_vcc.h:41-59)
 //   grhip_pfb_channelizer_ccf                <- gr_pfb_channelizer_ccf (filter/gr_pfb_channelizer_ccf.h:115-178)
 //   grhip_pfb_arb_resampler_ccf / _fff       <- gr_pfb_arb_resampler_ccf / _fff (filter/gr_pfb_arb_resampler_ccf.h:96-178)
+//   grhip_fractional_interpolator_ff / _cc   <- gr_fractional_interpolator_ff / _cc (filter/gr_fractional_interpolator_ff.h:41-66)
 //   grhip_interp_fir_filter_XXX              <- gr_interp_fir_filter_XXX (filter/gr_interp_fir_filter_XXX.h.t)
 //   grhip_rational_resampler_base_XXX        <- gr_rational_resampler_base_XXX (filter/gr_rational_resampler_base_XXX.h.t)
 //   grhip_pfb_interpolator_ccf               <- gr_pfb_interpolator_ccf (filter/gr_pfb_interpolator_ccf.h)
@@ -671,6 +672,61 @@ public:
 GRHIP_ARB_BLOCK(ccf, gr_complex)
 GRHIP_ARB_BLOCK(fff, float)
 #undef GRHIP_ARB_BLOCK
+
+// ---------------------------------------------------------------------------
+// gr_fractional_interpolator_ff / _cc  (a gr_block: general_work + consume_each, its own forecast, relative rate
+// 1 / interp_ratio; filter/gr_fractional_interpolator_ff.h:41-66).  std::out_of_range where the reference throws it.
+// ---------------------------------------------------------------------------
+#define GRHIP_FRAC_BLOCK(SUF, ITEM)                                                                                    \
+    class grhip_fractional_interpolator_##SUF##_blk;                                                                   \
+    typedef boost::shared_ptr<grhip_fractional_interpolator_##SUF##_blk> grhip_fractional_interpolator_##SUF##_sptr;   \
+    class grhip_fractional_interpolator_##SUF##_blk : public gr_block {                                                \
+        grhip_fractional_interpolator_##SUF *d_h = nullptr;                                                            \
+        grhip_fractional_interpolator_##SUF##_blk(float phase_shift, float interp_ratio, int device)                   \
+            : gr_block("fractional_interpolator_" #SUF, gr_make_io_signature(1, 1, sizeof(ITEM)),                      \
+                       gr_make_io_signature(1, 1, sizeof(ITEM)))                                                       \
+        {                                                                                                              \
+            grhip_detail::check(grhip_fractional_interpolator_##SUF##_create(&d_h, phase_shift, interp_ratio, device)); \
+            set_relative_rate(1.0 / interp_ratio);                             /* .cc:49 */                            \
+        }                                                                                                              \
+        friend grhip_fractional_interpolator_##SUF##_sptr grhip_make_fractional_interpolator_##SUF(float, float, int); \
+    public:                                                                                                            \
+        ~grhip_fractional_interpolator_##SUF##_blk() { grhip_fractional_interpolator_##SUF##_destroy(d_h); }           \
+        float mu() const { return grhip_fractional_interpolator_##SUF##_mu(d_h); }                                     \
+        float interp_ratio() const { return grhip_fractional_interpolator_##SUF##_interp_ratio(d_h); }                 \
+        void set_mu(float mu) { grhip_detail::check(grhip_fractional_interpolator_##SUF##_set_mu(d_h, mu)); }          \
+        void set_interp_ratio(float r)                                                                                 \
+        {                                                                                                              \
+            grhip_detail::check(grhip_fractional_interpolator_##SUF##_set_interp_ratio(d_h, r));                       \
+        }                                                                                                              \
+        void set_mode(int mode) { grhip_detail::check(grhip_fractional_interpolator_##SUF##_set_mode(d_h, mode)); }    \
+        void forecast(int noutput_items, gr_vector_int &ninput_items_required) override                               \
+        {                                                                                                              \
+            int n = grhip_fractional_interpolator_##SUF##_forecast(d_h, noutput_items);     /* .cc:57-65 */            \
+            grhip_detail::check(n);                                                                                    \
+            for (size_t i = 0; i < ninput_items_required.size(); i++) ninput_items_required[i] = n;                    \
+        }                                                                                                              \
+        int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,                \
+                         gr_vector_void_star &out) override                                                            \
+        {                                                                                                              \
+            int consumed = 0;                                                                                          \
+            int r = grhip_fractional_interpolator_##SUF##_general_work(d_h, noutput_items, ninput_items[0], in[0],     \
+                                                                       out[0], &consumed);                             \
+            grhip_detail::check(r);                                                                                    \
+            consume_each(consumed);                                                                                    \
+            return r;                                                                                                  \
+        }                                                                                                              \
+    };                                                                                                                 \
+    inline grhip_fractional_interpolator_##SUF##_sptr grhip_make_fractional_interpolator_##SUF(                       \
+        float phase_shift, float interp_ratio, int device = 0)                                                        \
+    {                                                                                                                  \
+        return gnuradio::get_initial_sptr(                                                                             \
+            new grhip_fractional_interpolator_##SUF##_blk(phase_shift, interp_ratio, device));                         \
+    }
+
+GRHIP_FRAC_BLOCK(ff, float)
+GRHIP_FRAC_BLOCK(cc, gr_complex)
+#undef GRHIP_FRAC_BLOCK
 
 // ---------------------------------------------------------------------------
 // gr_interp_fir_filter_XXX  (a gr_sync_interpolator: history nt, output_multiple I; filter/gr_interp_fir_filter_XXX.h.t)

@@ -516,6 +516,97 @@ GRHIP_API int grhip_pfb_arb_resampler_fff_run_captures_device(grhip_pfb_arb_resa
                                                               size_t out_stride_items, size_t *n_out, void *stream);
 
 /* ======================================================================
+ * gr_fractional_interpolator_ff / gr_fractional_interpolator_cc  (MMSE fractional resampler)
+ *   replaces gr_make_fractional_interpolator_ff(float phase_shift, float interp_ratio)   (and _cc: complex items)
+ *   filter/gr_fractional_interpolator_ff.cc:38-50 (constructor), 57-65 (forecast), 67-93 (general_work:
+ *   out[oo++] = interp->interpolate(&in[ii], mu); s = mu + mu_inc (a float sum); f = floor(s); mu = s - f;
+ *   ii += f; consume_each(ii)), filter/gr_fractional_interpolator_ff.h:51-54 (mu, interp_ratio, set_mu,
+ *   set_interp_ratio), filter/gri_mmse_fir_interpolator.cc:61-71 (imu = rint(mu * 128), filters[imu]: 8 taps
+ *   through gr_fir_fff / gr_fir_ccf).  One output per interp_ratio input items.
+ * gr_block: history() = 1 (the block never calls set_history), forecast(n) = (int) ceil(n * mu_inc + 8) evaluated
+ * in float as the reference writes it.
+ * GRHIP_ERANGE (std::out_of_range in the reference, .cc:44-47): interp_ratio <= 0, phase_shift < 0 or > 1 -- at
+ * create, and for set_interp_ratio / set_mu as well, where the reference accepts the value and trips the
+ * interpolator's assert on imu later -- and values that are not finite.  GRHIP_EINVAL: interp_ratio >= 2^20, the
+ * limit of the kernel (positions inside a tile are 32-bit; on the host every position is a 64-bit integer).
+ * Input shortfall: the reference trusts forecast and always produces noutput_items.  Here a call produces the
+ * outputs k < noutput_items with ii_k + 8 <= ninput_items and consumes ii after the last one produced, at most
+ * ninput_items; what a short call could not consume is carried and skipped at the start of the next.  With
+ * forecast honoured that is the reference's result, and nothing but mu is carried.  So from fresh state the outputs
+ * of a stream of N items are exactly those with ii_k + 8 <= N, however the stream is cut into calls; there are no
+ * history zeros in front.
+ * Modes: GRHIP_MODE_GENERIC is bit-exact against the reference's generic build (gr_fir_XXX_generic.cc.t:59-78).
+ * GRHIP_MODE_FAST, _FAST_VALU and _FAST_REFTAPS all mean one FMA kernel (there is no matrix-core engine for 8
+ * taps); the schedule is exact in every mode.  The default mode is grhip_get_default_mode() at create.
+ * The schedule: the float sum mu + mu_inc is the one operation of the walk that rounds.  It is exact while mu and
+ * mu_inc are multiples of a power of two g with 1 + mu_inc <= 2^24 * g (ratios such as 0.5, 0.75, 1.25, 2.5 or 10,
+ * and 1.3f, 160/147.f or 4.8f, whose last bits happen to be zero, from a phase on the same grid); the walk is then a closed form the kernel evaluates per output, and the device
+ * entries never wait.  mu == 1.0f at the start of a call (phase_shift = 1 or set_mu(1)) is such a case too: its
+ * first output uses filter 128 at offset 0.  Otherwise (1.0001f, 147/160.f, 0.01f, a phase of 0.1f) the host walks
+ * the reference's arithmetic and uploads one entry per output; before that upload the device entries wait for this
+ * handle's previous walked launch to finish (that launch only, not the device).
+ * ====================================================================== */
+typedef struct grhip_fractional_interpolator_ff grhip_fractional_interpolator_ff;
+GRHIP_API int grhip_fractional_interpolator_ff_create(grhip_fractional_interpolator_ff **h, float phase_shift,
+                                                      float interp_ratio, int device);
+GRHIP_API void grhip_fractional_interpolator_ff_destroy(grhip_fractional_interpolator_ff *h);
+/* .h:51-54; the setters take effect at the next general_work */
+GRHIP_API int grhip_fractional_interpolator_ff_set_mu(grhip_fractional_interpolator_ff *h, float mu);
+GRHIP_API int grhip_fractional_interpolator_ff_set_interp_ratio(grhip_fractional_interpolator_ff *h,
+                                                                float interp_ratio);
+GRHIP_API float grhip_fractional_interpolator_ff_mu(grhip_fractional_interpolator_ff *h);
+GRHIP_API float grhip_fractional_interpolator_ff_interp_ratio(grhip_fractional_interpolator_ff *h);
+GRHIP_API int grhip_fractional_interpolator_ff_set_mode(grhip_fractional_interpolator_ff *h, int mode);
+GRHIP_API int grhip_fractional_interpolator_ff_history(const grhip_fractional_interpolator_ff *h);
+GRHIP_API int grhip_fractional_interpolator_ff_forecast(grhip_fractional_interpolator_ff *h, int noutput_items);
+/* general_work (.cc:67-93) on HOST buffers: in[0 .. ninput_items), out room for noutput_items; returns the items
+ * produced, *consumed the items to consume (consume_each, .cc:90) */
+GRHIP_API int grhip_fractional_interpolator_ff_general_work(grhip_fractional_interpolator_ff *h, int noutput_items,
+                                                            int ninput_items, const void *in, void *out,
+                                                            int *consumed);
+/* the same on DEVICE buffers, enqueued on `stream`; produced and *consumed are known on return (the schedule
+ * does not depend on the data), the outputs once the stream has run */
+GRHIP_API int grhip_fractional_interpolator_ff_general_work_device(grhip_fractional_interpolator_ff *h,
+                                                                   int noutput_items, int ninput_items,
+                                                                   const void *d_in, void *d_out, int *consumed,
+                                                                   void *stream);
+/* n_streams captures in one launch, each from fresh state (mu = the phase_shift given at create, the current
+ * interp_ratio): capture s at d_in + s*in_stride_items (n_samples items), its outputs at d_out + s*out_stride_items.
+ * *n_out receives the outputs per capture, the same for all: those with ii_k + 8 <= n_samples, exactly what the
+ * block produces from the whole stream however it is split into calls.  d_out == NULL only sets *n_out.  The
+ * handle's own mu is left alone. */
+GRHIP_API int grhip_fractional_interpolator_ff_run_captures_device(grhip_fractional_interpolator_ff *h, int n_streams,
+                                                                   size_t n_samples, const void *d_in,
+                                                                   size_t in_stride_items, void *d_out,
+                                                                   size_t out_stride_items, size_t *n_out,
+                                                                   void *stream);
+
+typedef struct grhip_fractional_interpolator_cc grhip_fractional_interpolator_cc;
+GRHIP_API int grhip_fractional_interpolator_cc_create(grhip_fractional_interpolator_cc **h, float phase_shift,
+                                                      float interp_ratio, int device);
+GRHIP_API void grhip_fractional_interpolator_cc_destroy(grhip_fractional_interpolator_cc *h);
+GRHIP_API int grhip_fractional_interpolator_cc_set_mu(grhip_fractional_interpolator_cc *h, float mu);
+GRHIP_API int grhip_fractional_interpolator_cc_set_interp_ratio(grhip_fractional_interpolator_cc *h,
+                                                                float interp_ratio);
+GRHIP_API float grhip_fractional_interpolator_cc_mu(grhip_fractional_interpolator_cc *h);
+GRHIP_API float grhip_fractional_interpolator_cc_interp_ratio(grhip_fractional_interpolator_cc *h);
+GRHIP_API int grhip_fractional_interpolator_cc_set_mode(grhip_fractional_interpolator_cc *h, int mode);
+GRHIP_API int grhip_fractional_interpolator_cc_history(const grhip_fractional_interpolator_cc *h);
+GRHIP_API int grhip_fractional_interpolator_cc_forecast(grhip_fractional_interpolator_cc *h, int noutput_items);
+GRHIP_API int grhip_fractional_interpolator_cc_general_work(grhip_fractional_interpolator_cc *h, int noutput_items,
+                                                            int ninput_items, const void *in, void *out,
+                                                            int *consumed);
+GRHIP_API int grhip_fractional_interpolator_cc_general_work_device(grhip_fractional_interpolator_cc *h,
+                                                                   int noutput_items, int ninput_items,
+                                                                   const void *d_in, void *d_out, int *consumed,
+                                                                   void *stream);
+GRHIP_API int grhip_fractional_interpolator_cc_run_captures_device(grhip_fractional_interpolator_cc *h, int n_streams,
+                                                                   size_t n_samples, const void *d_in,
+                                                                   size_t in_stride_items, void *d_out,
+                                                                   size_t out_stride_items, size_t *n_out,
+                                                                   void *stream);
+
+/* ======================================================================
  * gr_interp_fir_filter_{ccf,fff,ccc}  (interpolating FIR: I outputs per input item)
  *   replaces gr_make_interp_fir_filter_XXX(unsigned interpolation, const std::vector<TAP> &taps)
  *   filter/gr_interp_fir_filter_XXX.cc.t:72-109 (set_taps: zeros in FRONT of the taps up to a multiple of I;
