@@ -14,7 +14,10 @@
 //                integers, so the phase keeps its accuracy at any N).
 // Parity: the reference's result is FFTW's, planner dependent and not in the tree; like the
 // power-of-two kernels these paths are checked against a float64 DFT at 1e-6 log2 N of the spectrum's
-// peak (tests/test_gpu_fft_pfb.py).
+// peak: N = 3 ... 2^20 in tests/test_gpu_fft_pfb.py; in tests/test_gpu_fft_large.py every power of two from 2^17 to 2^26
+// except 2^20 (each register kernel, 256 ... 8192 points, as an in-place row transform; both chunk loops across a seam; window
+// and shifts at 2^17, shifts at 2^23) and Bluestein on L = 1024, 4096, 8192 in place and on four-step sub-plans up to
+// L = 2^23 (N = 3 000 001).  Bluestein on L = 2^24 ... 2^26 is accepted and unpinned (set-up alone takes seconds of host time).
 #include <cmath>
 #include <complex>
 #include <vector>

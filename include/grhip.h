@@ -884,6 +884,12 @@ GRHIP_API int grhip_correlate_access_code_bb_work_device(grhip_correlate_access_
  * by the radix-16 register kernels, larger ones (up to 2^26) in four-step form, sizes that
  * are not a power of two by a direct DFT (<= 128) or Bluestein's chirp convolution (up to
  * 2^25); beyond that GRHIP_EINVAL (a handle's work buffers are sized for 2^26 points).
+ * Parity against a float64 DFT (1e-6 log2 N of the spectrum's peak) is pinned by the test
+ * suite for powers of two up to 2^26 and for Bluestein up to a convolution length of
+ * L = 2^23 (fft_size 3 000 001; L is the power of two >= 2 fft_size - 1).  Larger Bluestein
+ * sizes (fft_size above 2^22 that is not a power of two, L = 2^24 ... 2^26) are accepted and
+ * run the same code, but their parity is unpinned: the set-up alone needs up to 1 GB of host
+ * doubles and many seconds, too much for a per-commit test.
  * ====================================================================== */
 typedef struct grhip_fft_vcc grhip_fft_vcc;
 GRHIP_API int grhip_fft_vcc_create(grhip_fft_vcc **h, int fft_size, int forward, const float *window,
