@@ -13,7 +13,7 @@ __all__ = [
     "freq_xlating_fir_filter_ccc", "freq_xlating_fir_filter_ccf", "freq_xlating_fir_filter_fcf",
     "freq_xlating_fir_filter_fcc", "freq_xlating_fir_filter_scf", "freq_xlating_fir_filter_scc", "quadrature_demod_cf", "xlating_demod",
     "clock_recovery_mm_ff", "clock_recovery_mm_cc", "binary_slicer_fb", "correlate_access_code_bb", "pager_slicer_fb", "unpack_k_bits_bb", "framer_sink_1", "framer_sink_1_batch", "stream_to_streams", "streams_to_stream", "vector_to_streams", "stream_to_vector", "head",
-    "fft_vcc", "fft_filter_ccc", "pfb_channelizer_ccf", "pfb_decimator_ccf", "pfb_arb_resampler_ccf", "pfb_arb_resampler_fff",
+    "fft_vcc", "fft_vfc", "fft_filter_ccc", "fft_filter_fff", "pfb_channelizer_ccf", "pfb_decimator_ccf", "pfb_arb_resampler_ccf", "pfb_arb_resampler_fff",
     "fractional_interpolator_ff", "fractional_interpolator_cc",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
     "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
@@ -999,6 +999,88 @@ class fft_filter_ccc(_Block):
         L.grhip_fft_filter_ccc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         return _check(L.grhip_fft_filter_ccc_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
                                                          _stream(stream)))
+
+
+class fft_filter_fff(_Block):
+    """gr.fft_filter_fff(decimation, taps): fast convolution of a float stream with float taps (history 1, output
+    multiple nsamples); two consecutive blocks share one complex transform"""
+    _destroy = "grhip_fft_filter_fff_destroy"
+
+    def __init__(self, decimation, taps, device=0):
+        _Block.__init__(self)
+        L = lib()
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        L.grhip_fft_filter_fff_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_size_t, C.c_int]
+        _check(L.grhip_fft_filter_fff_create(C.byref(self._h), int(decimation), _ptr(t), len(t), int(device)))
+
+    def history(self):
+        return 1
+
+    def decimation(self):
+        return _check(lib().grhip_fft_filter_fff_decimation(self._h))
+
+    def nsamples(self):
+        """the block's output multiple"""
+        return _check(lib().grhip_fft_filter_fff_nsamples(self._h))
+
+    def set_taps(self, taps):
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        L = lib()
+        L.grhip_fft_filter_fff_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        _check(L.grhip_fft_filter_fff_set_taps(self._h, _ptr(t), len(t)))
+
+    def work(self, noutput_items, input_items):
+        x = np.ascontiguousarray(input_items, dtype=np.float32)
+        if len(x) < noutput_items * self.decimation():
+            raise ValueError("not enough input")
+        out = np.zeros(noutput_items, dtype=np.float32)
+        L = lib()
+        L.grhip_fft_filter_fff_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        n = _check(L.grhip_fft_filter_fff_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        return out[:n]
+
+    def work_device(self, noutput_items, d_in, d_out, stream=None):
+        L = lib()
+        L.grhip_fft_filter_fff_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        return _check(L.grhip_fft_filter_fff_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
+                                                         _stream(stream)))
+
+
+class fft_vfc(_Block):
+    """gr.fft_vfc(fft_size, forward, window): items of fft_size floats in, fft_size complex out; forward only"""
+    _destroy = "grhip_fft_vfc_destroy"
+
+    def __init__(self, fft_size, forward, window, device=0):
+        _Block.__init__(self)
+        w = np.ascontiguousarray(window if window is not None else [], dtype=np.float32)
+        self.fft_size = int(fft_size)
+        L = lib()
+        L.grhip_fft_vfc_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int]
+        _check(L.grhip_fft_vfc_create(C.byref(self._h), self.fft_size, int(bool(forward)),
+                                      _ptr(w) if len(w) else None, len(w), int(device)))
+
+    def set_window(self, window):
+        w = np.ascontiguousarray(window, dtype=np.float32)
+        L = lib()
+        L.grhip_fft_vfc_set_window.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        return bool(_check(L.grhip_fft_vfc_set_window(self._h, _ptr(w) if len(w) else None, len(w))))
+
+    def work(self, noutput_items, input_items):
+        """items are vectors: input_items has noutput_items*fft_size floats."""
+        x = np.ascontiguousarray(input_items, dtype=np.float32).reshape(-1)
+        if len(x) < noutput_items * self.fft_size:
+            raise ValueError("not enough input")
+        out = np.zeros(noutput_items * self.fft_size, dtype=np.complex64)
+        L = lib()
+        L.grhip_fft_vfc_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        n = _check(L.grhip_fft_vfc_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        return out[:n * self.fft_size]
+
+    def work_device(self, noutput_items, d_in, d_out, stream=None):
+        L = lib()
+        L.grhip_fft_vfc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        return _check(L.grhip_fft_vfc_work_device(self._h, int(noutput_items), _devptr(d_in),
+                                                  _devptr(d_out), _stream(stream)))
 
 
 class pfb_channelizer_ccf(_Block):

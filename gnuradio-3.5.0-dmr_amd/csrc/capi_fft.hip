@@ -1,4 +1,4 @@
-// capi_fft.hip -- C ABI for gr_fft_vcc and gr_pfb_channelizer_ccf.
+// capi_fft.hip -- C ABI for gr_fft_vcc, gr_fft_vfc and gr_pfb_channelizer_ccf.
 #include <cmath>
 
 #include "digital_kernels.h"
@@ -12,6 +12,24 @@ struct grhip_fft_vcc : HandleBase {
     std::vector<float> window;     // empty or N
     DevBuf d_window;
     FftPlan plan;              // any fft_size > 0 (fft_any.hip)
+    bool has_window = false;
+    int upload_window()
+    {
+        has_window = !window.empty();
+        if (!has_window) return GRHIP_OK;
+        int rc = d_window.reserve(window.size() * 4);
+        if (rc) return rc;
+        GRHIP_HIP(hipMemcpy(d_window.p, window.data(), window.size() * 4, hipMemcpyHostToDevice));
+        return GRHIP_OK;
+    }
+};
+
+// gr_fft_vfc: N floats in, N complex out, forward only, no shift; the window and the plan as grhip_fft_vcc
+struct grhip_fft_vfc : HandleBase {
+    int N = 0;
+    std::vector<float> window;     // empty or N
+    DevBuf d_window;
+    FftPlan plan;
     bool has_window = false;
     int upload_window()
     {
@@ -120,6 +138,77 @@ int grhip_fft_vcc_work(grhip_fft_vcc *h, int noutput_items, const void *in, void
     size_t bytes = (size_t)noutput_items * h->N * 8;
     return (int)h->host_call(in, bytes, bytes, bytes, out, (size_t)h->N * 8, [&](void *d_in, void *d_out, hipStream_t st) {
         rc = grhip_fft_vcc_work_device(h, noutput_items, d_in, d_out, st);
+        return rc < 0 ? rc : noutput_items;
+    });
+}
+
+// ---- fft_vfc (general/gr_fft_vfc.cc:42-118) ---------------------------------------
+int grhip_fft_vfc_create(grhip_fft_vfc **h, int fft_size, int forward, const float *window, size_t window_len, int device)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null argument");
+    *h = nullptr;
+    if (!forward) return fail(GRHIP_EINVAL, "fft_vfc: forward must == true");       // gr_fft_vfc.cc:54-57
+    if (fft_size <= 0) return fail(GRHIP_ERANGE, "gri_fftw: invalid fft_size");      // gri_fft.cc:104-105
+    if (!FftPlan::size_ok(fft_size))
+        return fail(GRHIP_EINVAL, "fft_size %d: more than 2^26 points (2^25 when not a power of two)", fft_size);
+    if (window_len && !window) return fail(GRHIP_EINVAL, "window is NULL");
+    auto *f = new (std::nothrow) grhip_fft_vfc();
+    if (!f) return fail(GRHIP_ENOMEM, "alloc");
+    f->N = fft_size;
+    // set_window accepts only size 0 or fft_size (gr_fft_vfc.cc:109-118); the ctor ignores the result (:61)
+    if (window_len == (size_t)fft_size) f->window.assign(window, window + window_len);
+    int rc = f->init_device(device);
+    if (!rc) rc = f->plan.build(fft_size, 1);
+    if (!rc) rc = f->upload_window();
+    if (rc) { f->d_window.release(); f->plan.release(); f->destroy_base(); delete f; return rc; }
+    *h = f;
+    return GRHIP_OK;
+}
+
+void grhip_fft_vfc_destroy(grhip_fft_vfc *h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    h->d_window.release(); h->plan.release();
+    h->destroy_base();
+    delete h;
+}
+
+int grhip_fft_vfc_set_window(grhip_fft_vfc *h, const float *window, size_t window_len)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    if (!(window_len == 0 || window_len == (size_t)h->N)) return 0;     // false (gr_fft_vfc.cc:112-117)
+    if (window_len && !window) return fail(GRHIP_EINVAL, "window is NULL");
+    std::lock_guard<std::mutex> lk(h->setter_mutex);
+    int rc = h->bind();
+    if (rc) return rc;
+    if ((rc = h->drain(h->own_stream))) return rc;
+    if (window_len) h->window.assign(window, window + window_len); else h->window.clear();
+    rc = h->upload_window();
+    return rc ? rc : 1;
+}
+
+int grhip_fft_vfc_work_device(grhip_fft_vfc *h, int noutput_items, const void *d_in, void *d_out, void *stream)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
+    int rc = h->bind();
+    if (rc) return rc;
+    rc = h->plan.exec_real(h->has_window ? h->d_window.as<float>() : nullptr, (const float *)d_in, (float2 *)d_out,
+                           noutput_items, h->pick(stream));
+    return rc ? rc : noutput_items;
+}
+
+int grhip_fft_vfc_work(grhip_fft_vfc *h, int noutput_items, const void *in, void *out)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
+    if (noutput_items == 0) return 0;
+    int rc = h->bind();
+    if (rc) return rc;
+    const size_t items = (size_t)noutput_items * h->N;
+    return (int)h->host_call(in, items * 4, items * 4, items * 8, out, (size_t)h->N * 8, [&](void *d_in, void *d_out, hipStream_t st) {
+        rc = grhip_fft_vfc_work_device(h, noutput_items, d_in, d_out, st);
         return rc < 0 ? rc : noutput_items;
     });
 }

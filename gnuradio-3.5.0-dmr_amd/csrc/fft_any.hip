@@ -36,8 +36,10 @@ constexpr int TLO_BITS = 13, TLO = 1 << TLO_BITS;      // two-level twiddle tabl
 template <bool FWD>
 __global__ void __launch_bounds__(256)
 dft_direct_kernel(int N, int vpw, int ishift, int oshift, const float *__restrict__ window, const float2 *__restrict__ tw,
-                  const float2 *__restrict__ in, float2 *__restrict__ out, long long nvec)
+                  const float2 *in, float2 *out, long long nvec)
 {
+    // in == out is a supported form (FftPlan::exec_real transforms the widened floats in place), hence no __restrict__ on
+    // the two: a workgroup reads its own vectors completely into LDS before the barrier and writes only them after it
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float2 *T = reinterpret_cast<float2 *>(smem);          // [N] e^{-2 pi i k / N}
     float2 *X = T + N;                                     // [vpw][N]
@@ -179,6 +181,16 @@ blu_post_kernel(const float2 *__restrict__ s, float2 *__restrict__ out, int N, i
             o[dst] = cmul_fma(x[k], chirp[k]);
         }
     }
+}
+
+// gr_fft_vfc on the kinds without a real-input load path: float -> (x, 0) (gr_fft_vfc.cc:92-93), into the OUTPUT buffer,
+// which the transform then works on in place
+__global__ void __launch_bounds__(256)
+widen_kernel(const float *__restrict__ in, float2 *__restrict__ out, long long n)
+{
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) out[i] = make_float2(in[i], 0.f);
 }
 
 int up(DevBuf &b, const void *src, size_t bytes)
@@ -338,6 +350,20 @@ int FftPlan::exec_pow2(int fwd, int shift, const float *window, const float2 *in
         GRHIP_HIP(hipGetLastError());
     }
     return GRHIP_OK;
+}
+
+int FftPlan::exec_real(const float *window, const float *in, float2 *out, long long nvec, hipStream_t st)
+{
+    if (nvec <= 0) return GRHIP_OK;
+    if (!forward) return fail(GRHIP_EINVAL, "fft plan: real input is forward only");
+    if (kind == NATIVE) return launch_fft_real(N, window, d_tw.as<float2>(), in, out, nvec, st);
+    // DIRECT / FOURSTEP / BLUESTEIN: every one of them reads a vector completely before it writes it (in place is a
+    // supported form), so the widened copy needs no buffer beside the output
+    const long long n = nvec * N;
+    const long long nb = (n + 255) / 256;
+    hipLaunchKernelGGL(widen_kernel, dim3((unsigned)(nb > 16384 ? 16384 : nb)), dim3(256), 0, st, in, out, n);
+    GRHIP_HIP(hipGetLastError());
+    return exec(0, window, out, out, nvec, st);
 }
 
 int FftPlan::exec(int shift, const float *window, const float2 *in, float2 *out, long long nvec, hipStream_t st)

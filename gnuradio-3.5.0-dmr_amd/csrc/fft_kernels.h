@@ -12,6 +12,9 @@ namespace grhip {
 int launch_fft(int N, int forward, int shift, const float *window, const float2 *twiddle,
                const float2 *in, float2 *out, long long nvec, hipStream_t st);
 bool fft_size_supported(int N);
+// gr_fft_vfc: the forward transform of N floats per item (no shift), the same kernels reading the floats directly
+int launch_fft_real(int N, const float *window, const float2 *twiddle, const float *in, float2 *out, long long nvec,
+                    hipStream_t st);
 
 // A transform of ANY size the reference's gri_fft_complex accepts (general/gri_fft.cc:97-123), on top of launch_fft:
 // fft_any.hip.  `forward` is fixed at build time for the Bluestein kind (its transformed chirp depends on the sign);
@@ -29,6 +32,8 @@ struct FftPlan {
     void release();
     int exec(int shift, const float *window, const float2 *in, float2 *out, long long nvec, hipStream_t st);
     int exec_pow2(int fwd, int shift, const float *window, const float2 *in, float2 *out, long long nvec, hipStream_t st);
+    // gr_fft_vfc: forward, no shift, items of N floats (NATIVE: read directly; the other kinds widen into `out` first)
+    int exec_real(const float *window, const float *in, float2 *out, long long nvec, hipStream_t st);
 };
 
 }  // namespace grhip
@@ -71,6 +76,10 @@ int launch_fftfilt4096(const float2 *in, long long nin, const float2 *hist, int 
                        float2 *hist_new = nullptr);
 int launch_fftfilt4096_real(const float *in, long long nin, const float *hist, int ntaps, const float2 *twiddle,
                             const float2 *H, float *out, long long nout, int decim, int L, int fold, hipStream_t st);
+// gr_fft_filter_fff: two consecutive real blocks per complex transform (block 2p in .x, block 2p+1 in .y); float history
+int launch_fftfilt4096_pair(const float *in, long long nin, const float *hist, int ntaps, const float2 *twiddle,
+                            const float2 *H, float *out, long long nout, int decim, int L, int fold, hipStream_t st,
+                            float *hist_new);
 int launch_fftfilt_hist(const float2 *in, long long nin, const float2 *hist_old, float2 *hist_new, int hlen, hipStream_t st);
 // gr_fft_filter_ccc helpers (overlap-add around launch_fft)
 int launch_fftfilt_pack(const float2 *in, float2 *blocks, int nsamples, int fftsize, long long nblk, hipStream_t st);
@@ -79,5 +88,11 @@ int launch_fftfilt_ola(const float2 *blocks, const float2 *tail, float2 *out, lo
                        int fftsize, int tailsize, hipStream_t st);
 int launch_fftfilt_tail(const float2 *blocks, float2 *tail, long long nblk, int nsamples, int fftsize, int tailsize,
                         hipStream_t st);
+// gr_fft_filter_fff helpers: real block b is plane b & 1 of complex block b >> 1 (nblk real blocks, float tail)
+int launch_fftfilt_pack_real(const float *in, float2 *blocks, int nsamples, int fftsize, long long nblk, hipStream_t st);
+int launch_fftfilt_ola_real(const float2 *blocks, const float *tail, float *out, long long nitems, int decim, int nsamples,
+                            int fftsize, int tailsize, hipStream_t st);
+int launch_fftfilt_tail_real(const float2 *blocks, float *tail, long long nblk, int nsamples, int fftsize, int tailsize,
+                             hipStream_t st);
 
 }  // namespace grhip

@@ -29,7 +29,8 @@ __device__ __forceinline__ float2 tw(const float2 *__restrict__ table, int m)
     return w;
 }
 
-template <bool FWD>
+// RIN (gr_fft_vfc): the items are N floats; a sample enters as (x, 0) -- the same arithmetic from there on
+template <bool FWD, bool RIN = false>
 __global__ void __launch_bounds__(256)
 fft_kernel(int N, int shift, const float *__restrict__ window, const float2 *__restrict__ twiddle,
            const float2 *__restrict__ in, float2 *__restrict__ out)
@@ -39,10 +40,17 @@ fft_kernel(int N, int shift, const float *__restrict__ window, const float2 *__r
     float2 *B = A + N;
     const int t = threadIdx.x, nthr = blockDim.x;      // N/4 lanes (64..256): small transforms get more workgroups per CU
     const float2 *__restrict__ x = in + (long long)blockIdx.x * N;
+    const float *__restrict__ xr = reinterpret_cast<const float *>(in) + (long long)blockIdx.x * N;
     float2 *__restrict__ y = out + (long long)blockIdx.x * N;
 
-    // ---- load (gr_fft_vcc_fftw.cc:68-83)
-    if (window) {
+    // ---- load (gr_fft_vcc_fftw.cc:68-83; gr_fft_vfc.cc:85-94)
+    if (RIN) {
+        for (int i = t; i < N; i += nthr) {
+            const float2 v = make_float2(xr[i], 0.f);
+            if (window) { const float w = window[i]; A[i] = make_float2(v.x * w, v.y * w); }
+            else A[i] = v;
+        }
+    } else if (window) {
         for (int i = t; i < N; i += nthr) {
             float2 v = x[i];
             float w = window[i];
@@ -222,7 +230,7 @@ __device__ __forceinline__ void dft16(float2 (&v)[16])
 // HBM latency runs under passes 2 and 3 and the stores.
 // (the window's sixteen values per lane are resident too: three workgroups per CU then, four otherwise)
 constexpr int fft4096_wg_per_cu(int mode) { return (mode & 1) ? 3 : 4; }
-template <bool FWD, int MODE>
+template <bool FWD, int MODE, bool RIN = false>
 __global__ void __launch_bounds__(256, fft4096_wg_per_cu(MODE))
 fft4096_kernel(const float *__restrict__ window, const float2 *__restrict__ twiddle,
                const float2 *__restrict__ in, float2 *__restrict__ out, int nvec)
@@ -254,6 +262,14 @@ fft4096_kernel(const float *__restrict__ window, const float2 *__restrict__ twid
     typedef unsigned int fft_u32x2 __attribute__((ext_vector_type(2)));
     f32x2_t pre[16];
     auto request = [&](int vec) __attribute__((always_inline)) {
+        if (RIN) {                          // N floats per item (gr_fft_vfc.cc:85-94): 4 B per sample from HBM, (x, 0) in registers
+            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<float *>(reinterpret_cast<const float *>(in) + (long long)vec * N), 0, N * 4, 0x00020000);
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                pre[q] = f32x2_t{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, 4 * t, 1024 * (q ^ SW_IN), 0)), 0.f};
+            return;
+        }
         const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(in + (long long)vec * N), 0, N * 8, 0x00020000);
 #pragma unroll
         for (int q = 0; q < 16; ++q) {      // dst[k] = in[(k + N/2) mod N] when shifting
@@ -1273,7 +1289,7 @@ __device__ __forceinline__ void dft8(f32x2_t &x0, f32x2_t &x1, f32x2_t &x2, f32x
     x3 = e3 + o3; x7 = e3 - o3;
 }
 
-template <int N, bool FWD, int MODE>
+template <int N, bool FWD, int MODE, bool RIN = false>
 __global__ void __launch_bounds__(256, 3)
 fft16x_kernel(const float *__restrict__ window, const float2 *__restrict__ twiddle, const float2 *__restrict__ in,
               float2 *__restrict__ out, int nvec)
@@ -1325,6 +1341,16 @@ fft16x_kernel(const float *__restrict__ window, const float2 *__restrict__ twidd
         const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(in + grp * VPG * (long long)N), 0,
                                                                           (int)(left < (long long)VPG * N * 8 ? left : (long long)VPG * N * 8), 0x00020000);
         (void)vec;
+        if (RIN) {                          // N floats per item (gr_fft_vfc.cc:85-94), the group through a descriptor of floats
+            const long long leftr = ((long long)nvec - grp * VPG) * (long long)(N * 4);
+            const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<float *>(reinterpret_cast<const float *>(in) + grp * VPG * (long long)N), 0,
+                (int)(leftr < (long long)VPG * N * 4 ? leftr : (long long)VPG * N * 4), 0x00020000);
+#pragma unroll
+            for (int q = 0; q < 16; ++q)
+                pre[q] = f32x2_t{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, 4 * (vl * N + l), 4 * LPV * (q ^ SW_IN), 0)), 0.f};
+            return;
+        }
 #pragma unroll
         for (int q = 0; q < 16; ++q)
             pre[q] = __builtin_bit_cast(f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(r, 8 * (vl * N + l), 8 * LPV * (q ^ SW_IN), 0));
@@ -1443,7 +1469,7 @@ static int launch_fft16x(int N, int forward, int shift, const float *window, con
 // twiddles (table entries 2m) and the sixteen combine twiddles W^{t + 256 m} of the lane resident.
 // MODE as fft4096_kernel: bit 0 window, bit 1 shift (a shift by N/2 swaps the two output halves / is q ^ 8 on the way in).
 // ===========================================================================
-template <bool FWD, int MODE>
+template <bool FWD, int MODE, bool RIN = false>
 __global__ void __launch_bounds__(256, (MODE & 1) ? 2 : 3)      // (the window's values in flight beside the points: two per CU)
 fft8192_kernel(const float *__restrict__ window, const float2 *__restrict__ twiddle, const float2 *__restrict__ in,
                float2 *__restrict__ out, int nvec)
@@ -1467,10 +1493,18 @@ fft8192_kernel(const float *__restrict__ window, const float2 *__restrict__ twid
         W2[(t >> 4) * 17 + (t & 15)] = f32x2_t{w.x, w.y};              // visible after the first barrier of the loop
     }
     for (int vec = blockIdx.x; vec < nvec; vec += gridDim.x) {
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(in + (long long)vec * N), 0, N * 8, 0x00020000);
+        const __amdgpu_buffer_rsrc_t xr = RIN
+            ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(reinterpret_cast<const float *>(in) + (long long)vec * N), 0, N * 4, 0x00020000)
+            : __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(in + (long long)vec * N), 0, N * 8, 0x00020000);
         f32x2_t ve[16], vo[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) {       // samples 2j, 2j + 1, j = t + 256 (q ^ SW_IN)
+            if (RIN) {                       // floats (gr_fft_vfc.cc:85-94): the pair is 8 bytes, each sample enters as (x, 0)
+                const f32x2_t u = __builtin_bit_cast(f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(xr, 8 * t, 2048 * (q ^ SW_IN), 0));
+                ve[q] = f32x2_t{u[0], 0.f};
+                vo[q] = f32x2_t{u[1], 0.f};
+                continue;
+            }
             const f32x4_t u = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_raw_buffer_load_b128(xr, 16 * t, 4096 * (q ^ SW_IN), 0));
             ve[q] = f32x2_t{u[0], u[1]};
             vo[q] = f32x2_t{u[2], u[3]};
@@ -1516,6 +1550,51 @@ static int launch_fft8192(int forward, int shift, const float *window, const flo
     if (nvec > 0x7fffffffLL) return fail(GRHIP_EINVAL, "fft: too many vectors in one call");
     if (forward) launch_fft8192_t<true>(shift, window, twiddle, in, out, nvec, st);
     else launch_fft8192_t<false>(shift, window, twiddle, in, out, nvec, st);
+    GRHIP_HIP(hipGetLastError());
+    return GRHIP_OK;
+}
+
+// gr_fft_vfc (general/gr_fft_vfc.cc:69-107): the forward transform of N FLOATS per item, no shift.  The same kernels with
+// the real-input load path (RIN): 4 B in + 8 B out per sample, no widened copy of the input anywhere.
+int launch_fft_real(int N, const float *window, const float2 *twiddle, const float *in_f, float2 *out, long long nvec,
+                    hipStream_t st)
+{
+    if (nvec <= 0) return GRHIP_OK;
+    if (!fft_size_supported(N)) return fail(GRHIP_EINVAL, "fft size %d not supported on device", N);
+    if (nvec > 0x7fffffffLL) return fail(GRHIP_EINVAL, "fft: too many vectors in one call");
+    const float2 *in = reinterpret_cast<const float2 *>(in_f);
+    const int nv = (int)nvec;
+    if (N == 8192) {
+        const long long cap = (window ? 2LL : 3LL) * device_cus();
+        const dim3 grid((unsigned)(nvec < cap ? nvec : cap));
+        if (window) hipLaunchKernelGGL((fft8192_kernel<true, 1, true>), grid, dim3(256), 0, st, window, twiddle, in, out, nv);
+        else hipLaunchKernelGGL((fft8192_kernel<true, 0, true>), grid, dim3(256), 0, st, window, twiddle, in, out, nv);
+    } else if (N == 4096) {
+        const long long cap = (long long)fft4096_wg_per_cu(window ? 1 : 0) * device_cus();
+        const dim3 grid((unsigned)(nvec < cap ? nvec : cap));
+        if (window) hipLaunchKernelGGL((fft4096_kernel<true, 1, true>), grid, dim3(256), 0, st, window, twiddle, in, out, nv);
+        else hipLaunchKernelGGL((fft4096_kernel<true, 0, true>), grid, dim3(256), 0, st, window, twiddle, in, out, nv);
+    } else if (N >= 32) {
+        const long long vpg = 4096 / N, ngroups = (nvec + vpg - 1) / vpg, cap = 3LL * device_cus();
+        const dim3 grid((unsigned)(ngroups < cap ? ngroups : cap));
+#define GRHIP_FFT16X_REAL(NN) do { \
+            if (window) hipLaunchKernelGGL((fft16x_kernel<NN, true, 1, true>), grid, dim3(256), 0, st, window, twiddle, in, out, nv); \
+            else hipLaunchKernelGGL((fft16x_kernel<NN, true, 0, true>), grid, dim3(256), 0, st, window, twiddle, in, out, nv); } while (0)
+        switch (N) {
+        case 32: GRHIP_FFT16X_REAL(32); break;
+        case 64: GRHIP_FFT16X_REAL(64); break;
+        case 128: GRHIP_FFT16X_REAL(128); break;
+        case 256: GRHIP_FFT16X_REAL(256); break;
+        case 512: GRHIP_FFT16X_REAL(512); break;
+        case 1024: GRHIP_FFT16X_REAL(1024); break;
+        default: GRHIP_FFT16X_REAL(2048); break;
+        }
+#undef GRHIP_FFT16X_REAL
+    } else {
+        const size_t lds = (size_t)N * 2 * sizeof(float2);
+        if (int rc = allow_lds((const void *)fft_kernel<true, true>, lds)) return rc;
+        hipLaunchKernelGGL((fft_kernel<true, true>), dim3((unsigned)nvec), dim3(64), lds, st, N, 0, window, twiddle, in, out);
+    }
     GRHIP_HIP(hipGetLastError());
     return GRHIP_OK;
 }
@@ -1704,6 +1783,192 @@ fftfilt4096_kernel(const void *__restrict__ in_v, long long nin, const void *__r
     }
 }
 
+// gr_fft_filter_fff (filter/gri_fft_filter_fff_generic.cc:107-158), fused: TWO consecutive real blocks per 4096-point
+// complex transform.  With real taps H is Hermitian (the ntaps-1 shift folded into it for the folded inverse keeps it
+// so), hence filtering z = x_a + j x_b gives y_a + j y_b: block 2p rides the real plane, block 2p+1 the imaginary one,
+// and no untangling step exists.  Everything else is fftfilt4096_kernel: the same passes, the same descriptor tricks
+// (positions outside the stream read as zero), the same folded inverse for D = 2/4/8/16, the float history of the next
+// call written by the last workgroup.  4 B in + 4/D B out per sample.  A lone last block (odd block count) has a zero
+// imaginary plane and stores nothing from it.  The two planes meet only through rounding: for finite input the leakage
+// between paired blocks is of the transform's own rounding error; a non-finite sample reaches both blocks of its pair.
+template <int FOLD>
+__global__ void __launch_bounds__(256, 3)
+fftfilt4096_pair_kernel(const float *__restrict__ in, long long nin, const float *__restrict__ hist, int ntaps,
+                        const float2 *__restrict__ twiddle, const float2 *__restrict__ H, float *__restrict__ out,
+                        long long nout, int decim, int L, long long nblk, float *__restrict__ hist_new)
+{
+    constexpr int N = 4096;
+    __shared__ f32x2_t S[N + N / 16];
+    __shared__ f32x2_t W2[16 * 17];
+    const int t = threadIdx.x;
+    if (hist_new && blockIdx.x == gridDim.x - 1) {
+        const int hlen = ntaps - 1;
+        for (int j = t; j < hlen; j += 256) {
+            const long long i = nin - hlen + j;          // index into the stream, negative: still in the old history
+            hist_new[j] = i >= 0 ? in[i] : hist[i + hlen];
+        }
+    }
+    f32x2_t w3[16];
+#pragma unroll
+    for (int q = 1; q < 16; ++q) { const float2 w = twiddle[t * q]; w3[q] = f32x2_t{w.x, w.y}; }
+    {
+        const float2 w = twiddle[16 * (t >> 4) * (t & 15)];
+        W2[(t >> 4) * 17 + (t & 15)] = f32x2_t{w.x, w.y};          // visible after the first barrier of the loop
+    }
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(in), 0, (int)(nin * 4), 0x00020000);
+    const long long npair = (nblk + 1) >> 1;
+    f32x2_t pre[16];
+    auto request = [&](long long p) __attribute__((always_inline)) {
+        // block 2p into .x, block 2p + 1 into .y; offsets as in fftfilt4096_kernel (whole offset in the VGPR, positions
+        // before the stream -- and the whole plane of a block past the last one -- through an explicit out-of-range offset)
+        const long long base_a = 2 * p * L - (ntaps - 1), base_b = base_a + L;
+        int tq = t;
+        asm volatile("" : "+v"(tq));
+        const int va = ((int)base_a + tq) * 4, vb = va + 4 * L;
+        const int first_a = base_a < 0 ? (int)-base_a : 0;
+        const int first_b = 2 * p + 1 >= nblk ? 0x7fffffff : (base_b < 0 ? (int)-base_b : 0);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int oa = (tq + 256 * q >= first_a) ? va + 1024 * q : 0x7ffffff0;
+            const int ob = (tq + 256 * q >= first_b) ? vb + 1024 * q : 0x7ffffff0;
+            pre[q] = f32x2_t{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, oa, 0, 0)),
+                             __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, ob, 0, 0))};
+        }
+    };
+    long long p = blockIdx.x;
+    if (p < npair) request(p);
+    for (; p < npair; p += gridDim.x) {
+        const bool has_b = 2 * p + 1 < nblk;
+        f32x2_t v[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) v[q] = pre[q];
+        if (2 * p * L < ntaps - 1) {
+            // positions before the call come from the history: block position i of block b is history item b L + i, and
+            // every position past the history's end is out of its descriptor's range (zero)
+            const __amdgpu_buffer_rsrc_t hr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(hist), 0, (ntaps - 1) * 4, 0x00020000);
+            const int ha = ((int)(2 * p * L) + t) * 4, hb = ha + 4 * L;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) v[q].x += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hr, ha + 1024 * q, 0, 0));
+            if (has_b) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q) v[q].y += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hr, hb + 1024 * q, 0, 0));
+            }
+        }
+        f32x2_t Hr[16];
+        const __amdgpu_buffer_rsrc_t Hd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(H), 0, N * 8, 0x00020000);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) Hr[m] = __builtin_bit_cast(f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(Hd, 8 * t, 2048 * m, 0));
+        dft16<true>(v);
+        fft4096_mid_passes<true>(v, S, W2, w3, t);           // v[m] = Z[t + 256 m], Z = X_a + j X_b
+#pragma unroll
+        for (int m = 0; m < 16; ++m) v[m] = cmul_pk(v[m], Hr[m]);
+        __builtin_amdgcn_sched_barrier(0);                  // (the requests must not be hoisted over the bins of H: same registers)
+        if (FOLD == 0 && p + gridDim.x < npair) request(p + gridDim.x);
+        __builtin_amdgcn_sched_barrier(0);
+        if (FOLD > 0) {
+            constexpr int DD = 1 << FOLD, NP = N >> FOLD, MP = 16 >> FOLD;     // decimation, inverse size, bins per lane
+            int tf = t;
+            asm volatile("" : "+v"(tf));
+            f32x2_t *A = S, *B = S + NP;
+            const __amdgpu_buffer_rsrc_t Td = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(twiddle), 0, N * 8, 0x00020000);
+#pragma unroll
+            for (int mp = 0; mp < MP; ++mp) {
+                f32x2_t f = v[mp];
+#pragma unroll
+                for (int a = 1; a < DD; ++a) f = f + v[mp + a * MP];
+                A[tf + 256 * mp] = f;
+            }
+            __syncthreads();
+            if (p + gridDim.x < npair) request(p + gridDim.x);      // (the spectrum has left its registers)
+            __builtin_amdgcn_sched_barrier(0);
+            f32x2_t *src = A, *dst = B;
+            int pp = 1;
+            constexpr int T4 = NP >> 2;
+            while (pp * 4 <= NP) {
+                const int tstep = (NP / (4 * pp)) << FOLD;             // step in the 4096-entry twiddle table
+#pragma unroll 1
+                for (int i = tf; i < T4; i += 256) {
+                    const int k = i & (pp - 1);
+                    const int j = ((i - k) << 2) + k;
+                    const int m = k * tstep;
+                    f32x2_t u0 = src[i], u1 = src[i + T4], u2 = src[i + 2 * T4], u3 = src[i + 3 * T4];
+                    if (pp > 1) {
+                        u1 = cmul_conj_pk(u1, __builtin_bit_cast(f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(Td, 8 * m, 0, 0)));
+                        u2 = cmul_conj_pk(u2, __builtin_bit_cast(f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(Td, 16 * m, 0, 0)));
+                        u3 = cmul_conj_pk(u3, __builtin_bit_cast(f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(Td, 24 * m, 0, 0)));
+                    }
+                    radix4<false>(u0, u1, u2, u3);
+                    dst[j] = u0; dst[j + pp] = u1; dst[j + 2 * pp] = u2; dst[j + 3 * pp] = u3;
+                }
+                __syncthreads();
+                f32x2_t *tmp = src; src = dst; dst = tmp;
+                pp <<= 2;
+            }
+            if (pp < NP) {                                            // one radix-2 pass, pp == NP/2
+                constexpr int T2 = NP >> 1;
+#pragma unroll 1
+                for (int i = tf; i < T2; i += 256) {
+                    f32x2_t u0 = src[i], u1 = src[i + T2];
+                    if (pp > 1) u1 = cmul_conj_pk(u1, __builtin_bit_cast(f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(Td, 8 * ((i & (pp - 1)) << FOLD), 0, 0)));
+                    dst[i] = u0 + u1;
+                    dst[i + pp] = u0 - u1;
+                }
+                __syncthreads();
+                f32x2_t *tmp = src; src = dst; dst = tmp;
+            }
+            const int nvalid = L >> FOLD;                             // outputs of each of the two blocks
+#pragma unroll 1
+            for (int r = tf; r < nvalid; r += 256) {
+                const long long na = 2 * p * nvalid + r, nb = na + nvalid;
+                const f32x2_t y = src[r];
+                if (na < nout) out[na] = y.x;
+                if (has_b && nb < nout) out[nb] = y.y;
+            }
+            __syncthreads();                                          // S belongs to the next pair from here
+            continue;
+        }
+        dft16<false>(v);                                     // inverse pass 1 on the same registers
+        fft4096_mid_passes<false>(v, S, W2, w3, t);          // v[m] = y_a[t + 256 m] + j y_b[t + 256 m]
+        if (decim == 1) {
+            // point t + 256 m is output j = t + 256 m - (ntaps - 1) of its block when 0 <= j < L: .x to block 2p's stretch of
+            // the output stream, .y to block 2p + 1's, through a descriptor (outputs past nout are out of its range)
+            const __amdgpu_buffer_rsrc_t orr = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)(nout * 4), 0x00020000);
+            const int j0 = t - (ntaps - 1);
+            const int oa = (int)((2 * p * L + j0) * 4), ob = oa + 4 * L;
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const int j = j0 + 256 * m;
+                const bool valid = j >= 0 && j < L;
+                // (scalars first: clang's __builtin_bit_cast of a vector ELEMENT reads element 0)
+                const float ya = v[m].x, yb = v[m].y;
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ya), orr, valid ? oa + 1024 * m : (int)0xfffffff0, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, yb), orr, (valid && has_b) ? ob + 1024 * m : (int)0xfffffff0, 0, 0);
+            }
+            continue;
+        }
+#pragma unroll 1
+        for (int m = 0; m < 16; ++m) {                       // any other decimation (2, 4, 8, 16 fold)
+            const int j = t + 256 * m - (ntaps - 1);         // offset of this point inside its block's outputs
+            if (j >= 0 && j < L && (j % decim) == 0) {
+                const long long na = (2 * p * L + j) / decim, nb = na + L / decim;
+                if (na < nout) out[na] = v[m].x;
+                if (has_b && nb < nout) out[nb] = v[m].y;
+            }
+        }
+    }
+}
+
+// the last hlen items of (hist_old ++ in), float items
+__global__ void __launch_bounds__(256)
+fftfilt_hist_real_kernel(const float *__restrict__ in, long long nin, const float *__restrict__ hist_old,
+                         float *__restrict__ hist_new, int hlen)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= hlen) return;
+    const long long i = nin - hlen + j;
+    hist_new[j] = i >= 0 ? in[i] : hist_old[i + hlen];
+}
+
 __global__ void __launch_bounds__(256)
 fftfilt_hist_kernel(const float2 *__restrict__ in, long long nin, const float2 *__restrict__ hist_old,
                     float2 *__restrict__ hist_new, int hlen)
@@ -1756,7 +2021,7 @@ int ols_build(const float *taps_cplx, int ntaps, int decim, DevBuf &d_tw, DevBuf
 
 static int launch_fftfilt_hist_any(bool real, const void *in, long long nin, const void *hist_old, void *hist_new, int hlen, hipStream_t st);
 
-template <bool REAL>
+template <bool REAL, bool PAIR = false>
 static int launch_fftfilt4096_t(const void *in, long long nin, const void *hist, int ntaps, const float2 *twiddle,
                                 const float2 *H, void *out, long long nout, int decim, int L, int fold, hipStream_t st,
                                 void *hist_new)
@@ -1765,7 +2030,8 @@ static int launch_fftfilt4096_t(const void *in, long long nin, const void *hist,
     // The kernel addresses a launch's input and output through 32-bit byte offsets: a longer call goes out in pieces of
     // whole blocks (blocks are independent: the history of a later piece is the stream itself).
     constexpr long long ISZ = REAL ? 4 : 8;
-    const long long max_blocks = (0x7fff0000LL / ISZ - 2 * OLS_N) / L;
+    // (PAIR: two blocks per transform, a piece is a whole number of pairs)
+    const long long max_blocks = ((0x7fff0000LL / ISZ - 2 * OLS_N) / L) & ~(PAIR ? 1LL : 0LL);
     const long long nblk_all = (nin + L - 1) / L;
     const long long cap = 3LL * device_cus();
     for (long long b0 = 0; b0 < nblk_all; b0 += max_blocks) {
@@ -1778,7 +2044,8 @@ static int launch_fftfilt4096_t(const void *in, long long nin, const void *hist,
         // (a piece in the middle reads on into the next one: its last block needs up to 4096 items from its start)
         const long long nin_rd = last || nin - i0 < nb * (long long)L + OLS_N ? nin - i0 : nb * (long long)L + OLS_N;
         const long long nout_c = last ? nout - o0 : nb * (L / decim);
-        const unsigned grid = (unsigned)(nb < cap ? nb : cap);
+        const long long nwork = PAIR ? (nb + 1) / 2 : nb;
+        const unsigned grid = (unsigned)(nwork < cap ? nwork : cap);
         void *hn = last ? hist_new : nullptr;
         if (hn && b0 != 0) {
             // the next call's history is defined against the whole call: written by a piece only when the piece is the call
@@ -1786,8 +2053,11 @@ static int launch_fftfilt4096_t(const void *in, long long nin, const void *hist,
             if (rc) return rc;
             hn = nullptr;
         }
-#define GRHIP_OLS_LAUNCH(F) hipLaunchKernelGGL((fftfilt4096_kernel<REAL, F>), dim3(grid), dim3(256), 0, st, in_c, nin_rd, hist_c, ntaps, \
-                                               twiddle, H, out_c, nout_c, decim, L, nb, hn)
+#define GRHIP_OLS_LAUNCH(F) do { \
+            if (PAIR) hipLaunchKernelGGL((fftfilt4096_pair_kernel<F>), dim3(grid), dim3(256), 0, st, (const float *)in_c, nin_rd, \
+                                         (const float *)hist_c, ntaps, twiddle, H, (float *)out_c, nout_c, decim, L, nb, (float *)hn); \
+            else hipLaunchKernelGGL((fftfilt4096_kernel<REAL, F>), dim3(grid), dim3(256), 0, st, in_c, nin_rd, hist_c, ntaps, \
+                                    twiddle, H, out_c, nout_c, decim, L, nb, hn); } while (0)
         switch (fold) {
         case 1: GRHIP_OLS_LAUNCH(1); break;
         case 2: GRHIP_OLS_LAUNCH(2); break;
@@ -1814,9 +2084,22 @@ int launch_fftfilt4096_real(const float *in, long long nin, const float *hist, i
     return launch_fftfilt4096_t<true>(in, nin, hist, ntaps, twiddle, H, out, nout, decim, L, fold, st, nullptr);
 }
 
+int launch_fftfilt4096_pair(const float *in, long long nin, const float *hist, int ntaps, const float2 *twiddle,
+                            const float2 *H, float *out, long long nout, int decim, int L, int fold, hipStream_t st,
+                            float *hist_new)
+{
+    return launch_fftfilt4096_t<true, true>(in, nin, hist, ntaps, twiddle, H, out, nout, decim, L, fold, st, hist_new);
+}
+
 static int launch_fftfilt_hist_any(bool real, const void *in, long long nin, const void *hist_old, void *hist_new, int hlen, hipStream_t st)
 {
-    if (real) return fail(GRHIP_EINVAL, "overlap-save engine: no history buffer for real data");
+    if (real) {
+        if (hlen <= 0) return GRHIP_OK;
+        hipLaunchKernelGGL(fftfilt_hist_real_kernel, dim3((hlen + 255) / 256), dim3(256), 0, st, (const float *)in, nin,
+                           (const float *)hist_old, (float *)hist_new, hlen);
+        GRHIP_HIP(hipGetLastError());
+        return GRHIP_OK;
+    }
     return launch_fftfilt_hist((const float2 *)in, nin, (const float2 *)hist_old, (float2 *)hist_new, hlen, st);
 }
 
@@ -1881,6 +2164,55 @@ fftfilt_tail_kernel(const float2 *__restrict__ blocks, float2 *__restrict__ tail
     if (j < tailsize) tail[j] = blocks[(nblk - 1) * fftsize + nsamples + j];            // :160-161
 }
 
+// ---- gr_fft_filter_fff, long filters (gri_fft_filter_fff_generic.cc:107-158): the same batched overlap-add with TWO real
+// blocks per complex block -- real block b is plane b & 1 (.x / .y) of complex block b >> 1.  The taps are real, so the
+// transformed taps are Hermitian and the planes stay apart through multiply and inverse; block 2p's tail lands on block
+// 2p + 1, the other plane of the same complex block.  An odd block count leaves the last .y plane zero.
+__device__ __forceinline__ float fftfilt_plane(float2 v, long long b) { return (b & 1) ? v.y : v.x; }
+
+__global__ void __launch_bounds__(256)
+fftfilt_pack_real_kernel(const float *__restrict__ in, float2 *__restrict__ blocks, int nsamples, int fftsize, long long nblk,
+                         long long total)
+{
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (; i < total; i += stride) {
+        const long long cb = i / fftsize;
+        const int j = (int)(i - cb * fftsize);
+        float2 v = make_float2(0.f, 0.f);
+        if (j < nsamples) {                                                           // :116-119
+            v.x = in[2 * cb * nsamples + j];
+            if (2 * cb + 1 < nblk) v.y = in[(2 * cb + 1) * nsamples + j];
+        }
+        blocks[i] = v;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+fftfilt_ola_real_kernel(const float2 *__restrict__ blocks, const float *__restrict__ tail, float *__restrict__ out,
+                        long long nitems, int decim, int nsamples, int fftsize, int tailsize)
+{
+    long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (; o < nitems; o += stride) {
+        const long long i = o * decim;                      // position in the full-rate overlap-added sequence (:143-148)
+        const long long b = i / nsamples;
+        const int j = (int)(i - b * nsamples);
+        float v = fftfilt_plane(blocks[(b >> 1) * fftsize + j], b);
+        if (j < tailsize)                                   // :135-136 outbuf[j] += d_tail[j]
+            v += b > 0 ? fftfilt_plane(blocks[((b - 1) >> 1) * fftsize + nsamples + j], b - 1) : tail[j];
+        out[o] = v;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+fftfilt_tail_real_kernel(const float2 *__restrict__ blocks, float *__restrict__ tail, long long nblk, int nsamples,
+                         int fftsize, int tailsize)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < tailsize) tail[j] = fftfilt_plane(blocks[((nblk - 1) >> 1) * fftsize + nsamples + j], nblk - 1);      // :151-152
+}
+
 static unsigned grid_for(long long n)
 {
     long long b = (n + 255) / 256;
@@ -1917,6 +2249,33 @@ int launch_fftfilt_tail(const float2 *blocks, float2 *tail, long long nblk, int 
 {
     if (tailsize <= 0) return GRHIP_OK;
     hipLaunchKernelGGL(fftfilt_tail_kernel, dim3((tailsize + 255) / 256), dim3(256), 0, st, blocks, tail, nblk,
+                       nsamples, fftsize, tailsize);
+    GRHIP_HIP(hipGetLastError());
+    return GRHIP_OK;
+}
+
+int launch_fftfilt_pack_real(const float *in, float2 *blocks, int nsamples, int fftsize, long long nblk, hipStream_t st)
+{
+    const long long total = ((nblk + 1) / 2) * fftsize;
+    hipLaunchKernelGGL(fftfilt_pack_real_kernel, dim3(grid_for(total)), dim3(256), 0, st, in, blocks, nsamples, fftsize, nblk, total);
+    GRHIP_HIP(hipGetLastError());
+    return GRHIP_OK;
+}
+
+int launch_fftfilt_ola_real(const float2 *blocks, const float *tail, float *out, long long nitems, int decim, int nsamples,
+                            int fftsize, int tailsize, hipStream_t st)
+{
+    hipLaunchKernelGGL(fftfilt_ola_real_kernel, dim3(grid_for(nitems)), dim3(256), 0, st, blocks, tail, out, nitems, decim,
+                       nsamples, fftsize, tailsize);
+    GRHIP_HIP(hipGetLastError());
+    return GRHIP_OK;
+}
+
+int launch_fftfilt_tail_real(const float2 *blocks, float *tail, long long nblk, int nsamples, int fftsize, int tailsize,
+                             hipStream_t st)
+{
+    if (tailsize <= 0) return GRHIP_OK;
+    hipLaunchKernelGGL(fftfilt_tail_real_kernel, dim3((tailsize + 255) / 256), dim3(256), 0, st, blocks, tail, nblk,
                        nsamples, fftsize, tailsize);
     GRHIP_HIP(hipGetLastError());
     return GRHIP_OK;

@@ -10,6 +10,8 @@
 //   grhip_binary_slicer_fb                   <- digital_binary_slicer_fb
 //   grhip_correlate_access_code_bb           <- digital_correlate_access_code_bb
 //   gr_fft_vcc_hip (grhip_make_fft_vcc)       <- gr_fft_vcc_fftw, on the abstract gr_fft_vcc base (general/gr_fft_vcc.h:41-59)
+//   grhip_fft_filter_ccc / _fff              <- gr_fft_filter_ccc / _fff (filter/gr_fft_filter_fff.cc:44-97)
+//   grhip_fft_vfc                            <- gr_fft_vfc (general/gr_fft_vfc.cc:42-118)
 //   grhip_pfb_channelizer_ccf                <- gr_pfb_channelizer_ccf (filter/gr_pfb_channelizer_ccf.h:115-178)
 //   grhip_pfb_arb_resampler_ccf / _fff       <- gr_pfb_arb_resampler_ccf / _fff (filter/gr_pfb_arb_resampler_ccf.h:96-178)
 //   grhip_fractional_interpolator_ff / _cc   <- gr_fractional_interpolator_ff / _cc (filter/gr_fractional_interpolator_ff.h:41-66)
@@ -532,6 +534,75 @@ public:
 inline grhip_fft_filter_ccc_sptr grhip_make_fft_filter_ccc(int decimation, const std::vector<gr_complex> &taps, int device = 0)
 {
     return gnuradio::get_initial_sptr(new grhip_fft_filter_ccc_blk(decimation, taps, device));
+}
+
+// gr_fft_filter_fff (filter/gr_fft_filter_fff.h, .cc:44-97): gr_sync_decimator on floats, history 1, output multiple nsamples
+class grhip_fft_filter_fff_blk;
+typedef boost::shared_ptr<grhip_fft_filter_fff_blk> grhip_fft_filter_fff_sptr;
+class grhip_fft_filter_fff_blk : public gr_sync_decimator {
+    grhip_fft_filter_fff *d_h = nullptr;
+    grhip_fft_filter_fff_blk(int decimation, const std::vector<float> &taps, int device)
+        : gr_sync_decimator("fft_filter_fff", gr_make_io_signature(1, 1, sizeof(float)),
+                            gr_make_io_signature(1, 1, sizeof(float)), decimation)
+    {
+        grhip_detail::check(grhip_fft_filter_fff_create(&d_h, decimation, taps.data(), taps.size(), device));
+        set_history(1);                                                       // gr_fft_filter_fff.cc:51
+        set_output_multiple(grhip_fft_filter_fff_nsamples(d_h));          // .cc:59-60
+    }
+    friend grhip_fft_filter_fff_sptr grhip_make_fft_filter_fff(int, const std::vector<float> &, int);
+public:
+    ~grhip_fft_filter_fff_blk() { grhip_fft_filter_fff_destroy(d_h); }
+    void set_taps(const std::vector<float> &taps)                             // .cc:69-73
+    {
+        grhip_detail::check(grhip_fft_filter_fff_set_taps(d_h, taps.data(), taps.size()));
+    }
+    int work(int n, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int r = grhip_fft_filter_fff_work(d_h, n, in[0], out[0]);
+        grhip_detail::check(r);
+        if (r == 0) set_output_multiple(grhip_fft_filter_fff_nsamples(d_h));   // .cc:83-88
+        return r;
+    }
+};
+inline grhip_fft_filter_fff_sptr grhip_make_fft_filter_fff(int decimation, const std::vector<float> &taps, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_fft_filter_fff_blk(decimation, taps, device));
+}
+
+// gr_fft_vfc (general/gr_fft_vfc.h, .cc:42-118): gr_sync_block, items of fft_size floats in, fft_size complex out; forward only
+class grhip_fft_vfc_blk;
+typedef boost::shared_ptr<grhip_fft_vfc_blk> grhip_fft_vfc_sptr;
+class grhip_fft_vfc_blk : public gr_sync_block {
+    grhip_fft_vfc *d_h = nullptr;
+    unsigned int d_fft_size;
+    grhip_fft_vfc_blk(int fft_size, bool forward, const std::vector<float> &window, int device)
+        : gr_sync_block("fft_vfc", gr_make_io_signature(1, 1, fft_size * sizeof(float)),
+                        gr_make_io_signature(1, 1, fft_size * sizeof(gr_complex))),
+          d_fft_size(fft_size)
+    {
+        if (!forward) throw std::invalid_argument("fft_vfc: forward must == true");     // .cc:54-57
+        grhip_detail::check(grhip_fft_vfc_create(&d_h, fft_size, forward, window.data(), window.size(), device));
+    }
+    friend grhip_fft_vfc_sptr grhip_make_fft_vfc(int, bool, const std::vector<float> &, int);
+public:
+    ~grhip_fft_vfc_blk() { grhip_fft_vfc_destroy(d_h); }
+    bool set_window(const std::vector<float> &window)                         // .cc:109-118
+    {
+        int r = grhip_fft_vfc_set_window(d_h, window.data(), window.size());
+        grhip_detail::check(r);
+        return r == 1;
+    }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int r = grhip_fft_vfc_work(d_h, noutput_items, in[0], out[0]);
+        grhip_detail::check(r);
+        return r;
+    }
+};
+inline grhip_fft_vfc_sptr grhip_make_fft_vfc(int fft_size, bool forward, const std::vector<float> &window, int device = 0)
+{
+    if (fft_size <= 0) throw std::out_of_range("fft_vfc: invalid fft_size");            // gri_fft.cc:104-105
+    return gnuradio::get_initial_sptr(new grhip_fft_vfc_blk(fft_size, forward, window, device));
 }
 
 // gr_pfb_decimator_ccf (filter/gr_pfb_decimator_ccf.h:100-140)

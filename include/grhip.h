@@ -925,6 +925,57 @@ GRHIP_API int grhip_fft_filter_ccc_work_device(grhip_fft_filter_ccc *h, int nout
                                                void *d_out, void *stream);
 
 /* ======================================================================
+ * gr_fft_filter_fff  
+ *   replaces gr_make_fft_filter_fff(int decimation, const std::vector<float>& taps)
+ *   filter/gr_fft_filter_fff.cc:44-97, filter/gri_fft_filter_fff_generic.cc:34-158
+ * The real-signal sibling of gr_fft_filter_ccc: float items in and out, float taps; the same
+ * sizes (fftsize = 2*2^ceil(log2 ntaps), nsamples = fftsize - ntaps + 1 = the output multiple),
+ * taps pre-scaled by 1/fftsize, tail carried between blocks and calls.  gr_sync_decimator,
+ * history 1.  noutput_items must be a multiple of nsamples (the reference asserts it, .cc:90;
+ * GRHIP_EINVAL here).  set_taps takes effect at the next work call, which returns 0 (.cc:83-88)
+ * and clears the carried state (generic.cc:56-58).  Any tap count up to 2^25.  No bit-exact
+ * mode: the reference's transforms are FFTW, unpinned.
+ * Two consecutive blocks share one complex transform (one in the real plane, the next in the
+ * imaginary plane; the transformed taps of a real filter are Hermitian, so the planes come out
+ * apart with no untangling step).  Caveat: a non-finite sample (Inf, NaN) in one engine block
+ * therefore reaches the outputs of the block it is paired with, the EARLIER one included; the
+ * reference confines such a sample to its own block and the next.  For finite input the leakage
+ * between paired blocks is rounding error of the transform, bounded by the parity tolerance
+ * 2e-6 * log2(2 * nsamples) of the call's peak.
+ * ====================================================================== */
+typedef struct grhip_fft_filter_fff grhip_fft_filter_fff;
+GRHIP_API int grhip_fft_filter_fff_create(grhip_fft_filter_fff **h, int decimation, const float *taps,
+                                          size_t ntaps, int device);
+GRHIP_API void grhip_fft_filter_fff_destroy(grhip_fft_filter_fff *h);
+GRHIP_API int grhip_fft_filter_fff_set_taps(grhip_fft_filter_fff *h, const float *taps, size_t ntaps);
+GRHIP_API int grhip_fft_filter_fff_nsamples(const grhip_fft_filter_fff *h);   /* output multiple */
+GRHIP_API int grhip_fft_filter_fff_decimation(const grhip_fft_filter_fff *h);
+GRHIP_API int grhip_fft_filter_fff_work(grhip_fft_filter_fff *h, int noutput_items, const void *in, void *out);
+GRHIP_API int grhip_fft_filter_fff_work_device(grhip_fft_filter_fff *h, int noutput_items, const void *d_in,
+                                               void *d_out, void *stream);
+
+/* ======================================================================
+ * gr_fft_vfc
+ *   replaces gr_make_fft_vfc(int fft_size, bool forward, const std::vector<float>& window)
+ *   general/gr_fft_vfc.cc:42-118
+ * items are vectors of fft_size floats in, fft_size complex out (the full spectrum).  Forward
+ * only: forward == 0 is GRHIP_EINVAL (.cc:54-57).  No shift.  window: NULL/0 or fft_size floats.
+ * GRHIP_ERANGE if fft_size <= 0 (general/gri_fft.cc:104-105); the same sizes as gr_fft_vcc.
+ * The result equals gr_fft_vcc (shift off) on the widened input value for value: powers of two
+ * up to 8192 read the floats directly in the register kernels (12 B of memory traffic per
+ * sample), the other sizes widen into the output buffer first and transform it in place.
+ * ====================================================================== */
+typedef struct grhip_fft_vfc grhip_fft_vfc;
+GRHIP_API int grhip_fft_vfc_create(grhip_fft_vfc **h, int fft_size, int forward, const float *window,
+                                   size_t window_len, int device);
+GRHIP_API void grhip_fft_vfc_destroy(grhip_fft_vfc *h);
+/* returns 1 if accepted, 0 if the length is wrong (gr_fft_vfc::set_window); the old window stays */
+GRHIP_API int grhip_fft_vfc_set_window(grhip_fft_vfc *h, const float *window, size_t window_len);
+GRHIP_API int grhip_fft_vfc_work(grhip_fft_vfc *h, int noutput_items, const void *in, void *out);
+GRHIP_API int grhip_fft_vfc_work_device(grhip_fft_vfc *h, int noutput_items, const void *d_in,
+                                        void *d_out, void *stream);
+
+/* ======================================================================
  * gr_pfb_channelizer_ccf
  *   replaces gr_make_pfb_channelizer_ccf(unsigned numchans,
  *       const std::vector<float>& taps, float oversample_rate)
