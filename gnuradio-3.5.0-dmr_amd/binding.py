@@ -15,6 +15,8 @@ __all__ = [
     "clock_recovery_mm_ff", "clock_recovery_mm_cc", "binary_slicer_fb", "correlate_access_code_bb", "pager_slicer_fb", "unpack_k_bits_bb", "framer_sink_1", "framer_sink_1_batch", "stream_to_streams", "streams_to_stream", "vector_to_streams", "stream_to_vector", "head",
     "fft_vcc", "fft_vfc", "fft_filter_ccc", "fft_filter_fff", "pfb_channelizer_ccf", "pfb_decimator_ccf", "pfb_arb_resampler_ccf", "pfb_arb_resampler_fff",
     "fractional_interpolator_ff", "fractional_interpolator_cc",
+    "firdes_hilbert", "hilbert_fc", "filter_delay_fc", "goertzel_fc",
+    "WIN_HAMMING", "WIN_HANN", "WIN_BLACKMAN", "WIN_RECTANGULAR", "WIN_KAISER", "WIN_BLACKMAN_hARRIS",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
     "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
     "rational_resampler_ccf", "rational_resampler_fff", "rational_resampler_ccc", "design_filter",
@@ -1363,6 +1365,164 @@ class fractional_interpolator_cc(_fractional_interpolator):
     _kind = "cc"
     _dtype = np.complex64
 
+
+# ----------------------------------------------------------------------------
+# gr.firdes.hilbert, gr.hilbert_fc, gr.filter_delay_fc, gr.goertzel_fc  (general/gr_firdes.i, filter/gr_hilbert_fc.i,
+# filter/gr_filter_delay_fc.i, filter/gr_goertzel_fc.i)
+# ----------------------------------------------------------------------------
+WIN_HAMMING, WIN_HANN, WIN_BLACKMAN, WIN_RECTANGULAR, WIN_KAISER, WIN_BLACKMAN_hARRIS = range(6)
+
+
+def firdes_hilbert(ntaps, window=WIN_RECTANGULAR, beta=6.76):
+    """gr.firdes.hilbert(ntaps, window, beta): host arithmetic only, no device needed.  WIN_RECTANGULAR gives the
+    Hamming-windowed taps, as the reference's window() does (its case has no break)."""
+    ntaps = int(ntaps)
+    if ntaps < 0 or ntaps > (1 << 24):
+        raise ValueError("ntaps out of range")
+    out = np.zeros(max(ntaps, 1), dtype=np.float32)
+    L = lib()
+    L.grhip_firdes_hilbert.argtypes = [C.c_uint, C.c_int, C.c_double, C.c_void_p]
+    _raise_like_reference(L.grhip_firdes_hilbert(ntaps, int(window), float(beta), _ptr(out)))
+    return out[:ntaps]
+
+
+class _analytic(_Block):
+    _name = None
+
+    def _fn(self, name):
+        return getattr(lib(), "grhip_%s_%s" % (self._name, name))
+
+    def set_mode(self, mode):
+        _check(self._fn("set_mode")(self._h, int(mode)))
+
+    def history(self):
+        return _check(self._fn("history")(self._h))
+
+    def decimation(self):
+        return 1
+
+    def ntaps(self):
+        return _check(self._fn("ntaps")(self._h))
+
+    def is_sparse(self):
+        """True when FAST mode runs the kernel that uses the Hilbert structure of the taps"""
+        return bool(_check(self._fn("is_sparse")(self._h)))
+
+    def taps(self):
+        out = np.zeros(self.ntaps(), dtype=np.float32)
+        f = self._fn("taps")
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        n = _check(f(self._h, _ptr(out), len(out)))
+        return out[:n]
+
+    def _input(self, noutput_items, a):
+        x = np.ascontiguousarray(a, dtype=np.float32)
+        need = noutput_items + self.history() - 1
+        if len(x) < need:
+            raise ValueError("work needs %d input items, got %d" % (need, len(x)))
+        return x
+
+
+class hilbert_fc(_analytic):
+    """gr.hilbert_fc(ntaps): real stream -> analytic signal; history ntaps | 1"""
+    _destroy = "grhip_hilbert_fc_destroy"
+    _name = "hilbert_fc"
+
+    def __init__(self, ntaps, device=0):
+        _Block.__init__(self)
+        L = lib()
+        L.grhip_hilbert_fc_create.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_int]
+        if int(ntaps) < 0:
+            raise GrhipError(-1, "negative ntaps %d" % int(ntaps))
+        _check(L.grhip_hilbert_fc_create(C.byref(self._h), int(ntaps), int(device)))
+
+    def work(self, noutput_items, input_items):
+        x = self._input(noutput_items, input_items)
+        out = np.zeros(noutput_items, dtype=np.complex64)
+        L = lib()
+        L.grhip_hilbert_fc_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        n = _check(L.grhip_hilbert_fc_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        return out[:n]
+
+    def work_device(self, noutput_items, d_in, d_out, stream=None):
+        L = lib()
+        L.grhip_hilbert_fc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        return _check(L.grhip_hilbert_fc_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
+                                                     _stream(stream)))
+
+
+class filter_delay_fc(_analytic):
+    """gr.filter_delay_fc(taps): out = (in0 delayed by ntaps/2, taps * in1); one input: in1 = in0"""
+    _destroy = "grhip_filter_delay_fc_destroy"
+    _name = "filter_delay_fc"
+
+    def __init__(self, taps, device=0):
+        _Block.__init__(self)
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        L = lib()
+        L.grhip_filter_delay_fc_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_int]
+        _check(L.grhip_filter_delay_fc_create(C.byref(self._h), _ptr(t) if len(t) else None, len(t), int(device)))
+
+    def work(self, noutput_items, input_items, input_items1=None):
+        x0 = self._input(noutput_items, input_items)
+        x1 = None if input_items1 is None else self._input(noutput_items, input_items1)
+        out = np.zeros(noutput_items, dtype=np.complex64)
+        L = lib()
+        L.grhip_filter_delay_fc_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        n = _check(L.grhip_filter_delay_fc_work(self._h, int(noutput_items), _ptr(x0),
+                                                None if x1 is None else _ptr(x1), _ptr(out)))
+        return out[:n]
+
+    def work_device(self, noutput_items, d_in0, d_in1, d_out, stream=None):
+        L = lib()
+        L.grhip_filter_delay_fc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p]
+        return _check(L.grhip_filter_delay_fc_work_device(self._h, int(noutput_items), _devptr(d_in0), _devptr(d_in1),
+                                                          _devptr(d_out), _stream(stream)))
+
+
+class goertzel_fc(_Block):
+    """gr.goertzel_fc(rate, len, freq): one DFT bin per block of len floats (a sync decimator by len)"""
+    _destroy = "grhip_goertzel_fc_destroy"
+
+    def __init__(self, rate, len, freq, device=0):
+        _Block.__init__(self)
+        L = lib()
+        L.grhip_goertzel_fc_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_float, C.c_int]
+        _check(L.grhip_goertzel_fc_create(C.byref(self._h), int(rate), int(len), float(freq), int(device)))
+
+    def set_freq(self, freq):
+        L = lib()
+        L.grhip_goertzel_fc_set_freq.argtypes = [C.c_void_p, C.c_float]
+        _check(L.grhip_goertzel_fc_set_freq(self._h, float(freq)))
+
+    def set_rate(self, rate):
+        _check(lib().grhip_goertzel_fc_set_rate(self._h, int(rate)))
+
+    def set_mode(self, mode):
+        _check(lib().grhip_goertzel_fc_set_mode(self._h, int(mode)))
+
+    def history(self):
+        return 1
+
+    def decimation(self):
+        return _check(lib().grhip_goertzel_fc_decimation(self._h))
+
+    def work(self, noutput_items, input_items):
+        x = np.ascontiguousarray(input_items, dtype=np.float32)
+        if len(x) < noutput_items * self.decimation():
+            raise ValueError("not enough input")
+        out = np.zeros(noutput_items, dtype=np.complex64)
+        L = lib()
+        L.grhip_goertzel_fc_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        n = _check(L.grhip_goertzel_fc_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        return out[:n]
+
+    def work_device(self, noutput_items, d_in, d_out, stream=None):
+        L = lib()
+        L.grhip_goertzel_fc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        return _check(L.grhip_goertzel_fc_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
+                                                      _stream(stream)))
 
 # ----------------------------------------------------------------------------
 # gr.interp_fir_filter_XXX / gr.rational_resampler_base_XXX  (filter/gr_interp_fir_filter_XXX.i.t,

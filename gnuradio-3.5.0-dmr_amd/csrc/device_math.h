@@ -15,6 +15,23 @@ __device__ __forceinline__ float2 cmul_ref(float2 a, float2 b)
     return make_float2(ac - bd, ad + bc);
 }
 
+// gr_fir_fff_generic::filter (filter/gr_fir_XXX_generic.cc.t:30-55): N_UNROLL 4 float accumulators over the reversed
+// taps, the rest into the first, summed ((a0 + a1) + a2) + a3; unfused.  Shared by fir_filter_fff's generic-order
+// kernel and the analytic-signal blocks (hilbert_fc / filter_delay_fc).
+__device__ __forceinline__ float fir_fff_generic_sum(const float *taps_rev, const float *x, int ntaps)
+{
+    float acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
+    int i = 0, nn = (ntaps / 4) * 4;
+    for (i = 0; i < nn; i += 4) {
+        acc0 += taps_rev[i + 0] * x[i + 0];
+        acc1 += taps_rev[i + 1] * x[i + 1];
+        acc2 += taps_rev[i + 2] * x[i + 2];
+        acc3 += taps_rev[i + 3] * x[i + 3];
+    }
+    for (; i < ntaps; i++) acc0 += taps_rev[i] * x[i];
+    return (acc0 + acc1 + acc2 + acc3);
+}
+
 // fused form for the fast kernels
 __device__ __forceinline__ float2 cmul_fma(float2 a, float2 b)
 {

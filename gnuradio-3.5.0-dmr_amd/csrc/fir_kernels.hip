@@ -117,17 +117,7 @@ fir_generic_kernel(const float *__restrict__ taps_rev, int ntaps, const float *_
     }
     if (KIND == FIR_FFF) {
         // N_UNROLL 4, float accumulators (.cc.t:30-55)
-        const float *x = in + n * decim;
-        float acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
-        int i = 0, nn = (ntaps / 4) * 4;
-        for (i = 0; i < nn; i += 4) {
-            acc0 += s_taps[i + 0] * x[i + 0];
-            acc1 += s_taps[i + 1] * x[i + 1];
-            acc2 += s_taps[i + 2] * x[i + 2];
-            acc3 += s_taps[i + 3] * x[i + 3];
-        }
-        for (; i < ntaps; i++) acc0 += s_taps[i] * x[i];
-        out[n] = (acc0 + acc1 + acc2 + acc3);
+        out[n] = fir_fff_generic_sum(s_taps, in + n * decim, ntaps);
     } else {
         // N_UNROLL 2, complex accumulators (.cc.t:59-79)
         const float2 *x = (const float2 *)in + n * decim;

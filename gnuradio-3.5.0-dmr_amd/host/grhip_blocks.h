@@ -19,6 +19,8 @@
 //   grhip_rational_resampler_base_XXX        <- gr_rational_resampler_base_XXX (filter/gr_rational_resampler_base_XXX.h.t)
 //   grhip_pfb_interpolator_ccf               <- gr_pfb_interpolator_ccf (filter/gr_pfb_interpolator_ccf.h)
 //   grhip_pfb_synthesis_filterbank_ccf       <- gr_pfb_synthesis_filterbank_ccf (filter/gr_pfb_synthesis_filterbank_ccf.h)
+//   grhip_hilbert_fc / grhip_filter_delay_fc <- gr_hilbert_fc (filter/gr_hilbert_fc.h), gr_filter_delay_fc (filter/gr_filter_delay_fc.h)
+//   grhip_goertzel_fc                        <- gr_goertzel_fc (filter/gr_goertzel_fc.h)
 //
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
@@ -989,4 +991,97 @@ inline grhip_pfb_synthesis_filterbank_ccf_sptr grhip_make_pfb_synthesis_filterba
                                                                                        int device = 0)
 {
     return gnuradio::get_initial_sptr(new grhip_pfb_synthesis_filterbank_ccf_blk(numchans, taps, device));
+}
+
+// ---------------------------------------------------------------------------
+// gr_hilbert_fc(ntaps)  (gr_sync_block, float -> complex, history ntaps | 1; filter/gr_hilbert_fc.cc:39-50)
+// gr_filter_delay_fc(taps)  (gr_sync_block, 1 or 2 float inputs -> complex, history ntaps; filter/gr_filter_delay_fc.cc:38-46)
+// gr_goertzel_fc(rate, len, freq)  (gr_sync_decimator by len, float -> complex; filter/gr_goertzel_fc.cc:38-50)
+// ---------------------------------------------------------------------------
+class grhip_hilbert_fc_blk;
+typedef boost::shared_ptr<grhip_hilbert_fc_blk> grhip_hilbert_fc_sptr;
+class grhip_hilbert_fc_blk : public gr_sync_block {
+    grhip_hilbert_fc *d_h = nullptr;
+    grhip_hilbert_fc_blk(unsigned ntaps, int device)
+        : gr_sync_block("hilbert_fc", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(gr_complex)))
+    {
+        grhip_detail::check(grhip_hilbert_fc_create(&d_h, ntaps, device));
+        set_history((unsigned)grhip_hilbert_fc_history(d_h));           // set_history(d_ntaps), .cc:49
+    }
+    friend grhip_hilbert_fc_sptr grhip_make_hilbert_fc(unsigned, int);
+public:
+    ~grhip_hilbert_fc_blk() { grhip_hilbert_fc_destroy(d_h); }
+    void set_mode(int mode) { grhip_detail::check(grhip_hilbert_fc_set_mode(d_h, mode)); }
+    std::vector<float> taps() const
+    {
+        std::vector<float> t((size_t)grhip_hilbert_fc_ntaps(d_h));
+        grhip_detail::check(grhip_hilbert_fc_taps(d_h, t.data(), t.size()));
+        return t;
+    }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int r = grhip_hilbert_fc_work(d_h, noutput_items, in[0], out[0]);
+        grhip_detail::check(r);
+        return r;
+    }
+};
+inline grhip_hilbert_fc_sptr grhip_make_hilbert_fc(unsigned ntaps, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_hilbert_fc_blk(ntaps, device));
+}
+
+class grhip_filter_delay_fc_blk;
+typedef boost::shared_ptr<grhip_filter_delay_fc_blk> grhip_filter_delay_fc_sptr;
+class grhip_filter_delay_fc_blk : public gr_sync_block {
+    grhip_filter_delay_fc *d_h = nullptr;
+    grhip_filter_delay_fc_blk(const std::vector<float> &taps, int device)
+        : gr_sync_block("filter_delay_fc", gr_make_io_signature(1, 2, sizeof(float)),
+                        gr_make_io_signature(1, 1, sizeof(gr_complex)))
+    {
+        grhip_detail::check(grhip_filter_delay_fc_create(&d_h, taps.data(), taps.size(), device));
+        set_history((unsigned)grhip_filter_delay_fc_history(d_h));      // set_history(d_fir->ntaps()), .cc:45
+    }
+    friend grhip_filter_delay_fc_sptr grhip_make_filter_delay_fc(const std::vector<float> &, int);
+public:
+    ~grhip_filter_delay_fc_blk() { grhip_filter_delay_fc_destroy(d_h); }
+    void set_mode(int mode) { grhip_detail::check(grhip_filter_delay_fc_set_mode(d_h, mode)); }
+    // the connected inputs decide the form (input_items.size(), .cc:61)
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int r = grhip_filter_delay_fc_work(d_h, noutput_items, in[0], in.size() > 1 ? in[1] : nullptr, out[0]);
+        grhip_detail::check(r);
+        return r;
+    }
+};
+inline grhip_filter_delay_fc_sptr grhip_make_filter_delay_fc(const std::vector<float> &taps, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_filter_delay_fc_blk(taps, device));
+}
+
+class grhip_goertzel_fc_blk;
+typedef boost::shared_ptr<grhip_goertzel_fc_blk> grhip_goertzel_fc_sptr;
+class grhip_goertzel_fc_blk : public gr_sync_decimator {
+    grhip_goertzel_fc *d_h = nullptr;
+    grhip_goertzel_fc_blk(int rate, int len, float freq, int device)
+        : gr_sync_decimator("goertzel_fc", gr_make_io_signature(1, 1, sizeof(float)),
+                            gr_make_io_signature(1, 1, sizeof(gr_complex)), len < 1 ? 1 : len)
+    {
+        grhip_detail::check(grhip_goertzel_fc_create(&d_h, rate, len, freq, device));
+    }
+    friend grhip_goertzel_fc_sptr grhip_make_goertzel_fc(int, int, float, int);
+public:
+    ~grhip_goertzel_fc_blk() { grhip_goertzel_fc_destroy(d_h); }
+    void set_freq(float freq) { grhip_detail::check(grhip_goertzel_fc_set_freq(d_h, freq)); }
+    void set_rate(int rate) { grhip_detail::check(grhip_goertzel_fc_set_rate(d_h, rate)); }
+    void set_mode(int mode) { grhip_detail::check(grhip_goertzel_fc_set_mode(d_h, mode)); }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int r = grhip_goertzel_fc_work(d_h, noutput_items, in[0], out[0]);
+        grhip_detail::check(r);
+        return r;
+    }
+};
+inline grhip_goertzel_fc_sptr grhip_make_goertzel_fc(int rate, int len, float freq, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_goertzel_fc_blk(rate, len, freq, device));
 }

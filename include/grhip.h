@@ -976,6 +976,98 @@ GRHIP_API int grhip_fft_vfc_work_device(grhip_fft_vfc *h, int noutput_items, con
                                         void *d_out, void *stream);
 
 /* ======================================================================
+ * gr_firdes::hilbert  -- host only, no device needed
+ *   replaces gr_firdes::hilbert(unsigned ntaps, win_type windowtype, double beta)
+ *   general/gr_firdes.cc:538-565 with gr_firdes::window, :720-780
+ * out receives ntaps floats.  window_type is gr_firdes::win_type (0 Hamming, 1 Hann, 2 Blackman,
+ * 3 rectangular, 4 Kaiser, 5 Blackman-harris).  Reproduced literally: window()'s WIN_RECTANGULAR
+ * case has no break and runs on into WIN_HAMMING, so type 3 gives the taps of type 0; the taps
+ * are formed in float (1/(float)i, the alternating recurrence gain = taps[h+i] - gain, a float
+ * division by 2*fabs(gain)).  GRHIP_ERANGE for an even ntaps or a window type out of range (the
+ * reference throws std::out_of_range).
+ * ====================================================================== */
+GRHIP_API int grhip_firdes_hilbert(unsigned ntaps, int window_type, double beta, float *out);
+
+/* ======================================================================
+ * gr_hilbert_fc
+ *   replaces gr_make_hilbert_fc(unsigned int ntaps)
+ *   filter/gr_hilbert_fc.cc:39-67, taps from general/gr_firdes.cc:538-565
+ * float in, complex out: out[i] = (in[i + d_ntaps/2], fir_fff(&in[i])) with d_ntaps = ntaps | 1
+ * and the taps of grhip_firdes_hilbert(d_ntaps, 3, 6.76).  gr_sync_block, history = d_ntaps: work
+ * reads noutput_items + d_ntaps - 1 items.
+ * Stated deviation: ntaps <= 1 is GRHIP_EINVAL.  The reference accepts it, divides 0 by 0 in
+ * gr_firdes::hilbert and filters with one NaN tap.
+ * GRHIP_MODE_GENERIC sums every tap, zeros included, in gr_fir_fff_generic's order: bit-exact.
+ * FAST uses the structure of the taps (see gr_filter_delay_fc below).  work takes host pointers,
+ * work_device device pointers (items 4-byte aligned, at any offset) and a stream.
+ * taps() copies the d_ntaps forward taps into out (capacity floats) and returns their number.
+ * ====================================================================== */
+typedef struct grhip_hilbert_fc grhip_hilbert_fc;
+GRHIP_API int grhip_hilbert_fc_create(grhip_hilbert_fc **h, unsigned ntaps, int device);
+GRHIP_API void grhip_hilbert_fc_destroy(grhip_hilbert_fc *h);
+GRHIP_API int grhip_hilbert_fc_set_mode(grhip_hilbert_fc *h, int mode);
+GRHIP_API int grhip_hilbert_fc_history(const grhip_hilbert_fc *h);
+GRHIP_API int grhip_hilbert_fc_ntaps(const grhip_hilbert_fc *h);
+GRHIP_API int grhip_hilbert_fc_taps(const grhip_hilbert_fc *h, float *out, size_t capacity);
+GRHIP_API int grhip_hilbert_fc_is_sparse(const grhip_hilbert_fc *h);
+GRHIP_API int grhip_hilbert_fc_work(grhip_hilbert_fc *h, int noutput_items, const void *in, void *out);
+GRHIP_API int grhip_hilbert_fc_work_device(grhip_hilbert_fc *h, int noutput_items, const void *d_in, void *d_out,
+                                           void *stream);
+
+/* ======================================================================
+ * gr_filter_delay_fc
+ *   replaces gr_make_filter_delay_fc(const std::vector<float> &taps)
+ *   filter/gr_filter_delay_fc.cc:38-80
+ * One or two float inputs, complex out: out[j] = (in0[j + d_delay], fir_fff(&in1[j])) with
+ * d_delay = ntaps / 2 and history = ntaps on every input; in1 == NULL is the one-input form
+ * (in1 = in0).  Any tap count from 1 to 16384, even counts included.  The reference block has no
+ * set_taps; neither has this one.
+ * GRHIP_MODE_GENERIC: bit-exact (gr_fir_fff_generic's order over all taps).  FAST: when the taps
+ * are of odd length >= 3, exactly zero at every even distance from the centre and exactly
+ * antisymmetric (is_sparse() == 1; checked on the given floats, no tolerance) and there is one
+ * input, a kernel that multiplies t[h+i] by (x[c-i] - x[c+i]) over odd i only; otherwise, and
+ * with two inputs, a kernel that uses every tap.  Above 2048 taps FAST runs the GENERIC kernel.
+ * ====================================================================== */
+typedef struct grhip_filter_delay_fc grhip_filter_delay_fc;
+GRHIP_API int grhip_filter_delay_fc_create(grhip_filter_delay_fc **h, const float *taps, size_t ntaps, int device);
+GRHIP_API void grhip_filter_delay_fc_destroy(grhip_filter_delay_fc *h);
+GRHIP_API int grhip_filter_delay_fc_set_mode(grhip_filter_delay_fc *h, int mode);
+GRHIP_API int grhip_filter_delay_fc_history(const grhip_filter_delay_fc *h);
+GRHIP_API int grhip_filter_delay_fc_ntaps(const grhip_filter_delay_fc *h);
+GRHIP_API int grhip_filter_delay_fc_taps(const grhip_filter_delay_fc *h, float *out, size_t capacity);
+GRHIP_API int grhip_filter_delay_fc_is_sparse(const grhip_filter_delay_fc *h);
+GRHIP_API int grhip_filter_delay_fc_work(grhip_filter_delay_fc *h, int noutput_items, const void *in0,
+                                         const void *in1, void *out);
+GRHIP_API int grhip_filter_delay_fc_work_device(grhip_filter_delay_fc *h, int noutput_items, const void *d_in0,
+                                                const void *d_in1, void *d_out, void *stream);
+
+/* ======================================================================
+ * gr_goertzel_fc
+ *   replaces gr_make_goertzel_fc(int rate, int len, float freq)
+ *   filter/gr_goertzel_fc.cc:38-78, filter/gri_goertzel.cc:36-75
+ * gr_sync_decimator by len: one DFT bin per block of len floats, no state across blocks.
+ * w = (float)(2 pi freq / rate), wr = 2 cosf(w), wi = sinf(w) on the host; per sample
+ * y = (x + wr*d1) - d2 in float; out = ((float)((0.5*wr*d1 - d2)/len) formed in double,
+ * (wi*d1)/(float)len in float).  set_freq / set_rate hold from the next call on (the reference
+ * has no latch here).  GRHIP_EINVAL for len < 1 (or above 2^24) and for rate == 0.
+ * GRHIP_MODE_GENERIC is that recurrence, one lane per block: bit-exact, and as inaccurate as the
+ * reference at low bin frequencies (its float state loses 3e-4 at rate 8000, len 2000, freq 5).
+ * FAST evaluates the recurrence's closed form, sum_n x[n] (cos((len-n)w'), wi U_(len-1-n)) / len
+ * with cos w' = wr/2, from a table built in double: a better-conditioned sum than the
+ * reference's, so it is compared with the float64 recurrence, not with the float one.
+ * ====================================================================== */
+typedef struct grhip_goertzel_fc grhip_goertzel_fc;
+GRHIP_API int grhip_goertzel_fc_create(grhip_goertzel_fc **h, int rate, int len, float freq, int device);
+GRHIP_API void grhip_goertzel_fc_destroy(grhip_goertzel_fc *h);
+GRHIP_API int grhip_goertzel_fc_set_freq(grhip_goertzel_fc *h, float freq);
+GRHIP_API int grhip_goertzel_fc_set_rate(grhip_goertzel_fc *h, int rate);
+GRHIP_API int grhip_goertzel_fc_set_mode(grhip_goertzel_fc *h, int mode);
+GRHIP_API int grhip_goertzel_fc_decimation(const grhip_goertzel_fc *h);   /* len */
+GRHIP_API int grhip_goertzel_fc_work(grhip_goertzel_fc *h, int noutput_items, const void *in, void *out);
+GRHIP_API int grhip_goertzel_fc_work_device(grhip_goertzel_fc *h, int noutput_items, const void *d_in, void *d_out,
+                                            void *stream);
+
+/* ======================================================================
  * gr_pfb_channelizer_ccf
  *   replaces gr_make_pfb_channelizer_ccf(unsigned numchans,
  *       const std::vector<float>& taps, float oversample_rate)
