@@ -1187,127 +1187,20 @@ class pfb_decimator_ccf(_Block):
 
 
 # ----------------------------------------------------------------------------
-# gr.pfb_arb_resampler_ccf / gr.pfb_arb_resampler_fff  (filter/gr_pfb_arb_resampler_ccf.i)
+# What the schedule-driven general_work blocks share (csrc/sched_block.h): their C entry points differ only in the
+# symbol prefix, their buffers only in the item type.
 # ----------------------------------------------------------------------------
-class _pfb_arb_resampler(_Block):
+class _sched_block(_Block):
+    _prefix = None      # C symbol prefix up to the signature suffix
     _kind = None
     _dtype = None
 
-    def __init__(self, rate, taps, filter_size=32, device=0):
+    def __init__(self):
         _Block.__init__(self)
-        self._destroy = "grhip_pfb_arb_resampler_%s_destroy" % self._kind
-        t = np.ascontiguousarray(taps, dtype=np.float32)
-        f = self._fn("create")
-        f.argtypes = [C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_size_t, C.c_uint, C.c_int]
-        _check(f(C.byref(self._h), float(rate), _ptr(t), len(t), int(filter_size), int(device)))
+        self._destroy = "%s_%s_destroy" % (self._prefix, self._kind)
 
     def _fn(self, name):
-        return getattr(lib(), "grhip_pfb_arb_resampler_%s_%s" % (self._kind, name))
-
-    def set_rate(self, rate):
-        f = self._fn("set_rate")
-        f.argtypes = [C.c_void_p, C.c_float]
-        _check(f(self._h, float(rate)))
-
-    def set_mode(self, mode):
-        _check(self._fn("set_mode")(self._h, int(mode)))
-
-    def history(self):
-        return _check(self._fn("history")(self._h))
-
-    def taps_per_filter(self):
-        return _check(self._fn("taps_per_filter")(self._h))
-
-    def forecast(self, noutput_items):
-        return _check(self._fn("forecast")(self._h, int(noutput_items)))
-
-    def general_work(self, noutput_items, input_items):
-        """returns (out, consumed); input_items carries the history in front"""
-        x = np.ascontiguousarray(input_items, dtype=self._dtype)
-        out = np.zeros(max(int(noutput_items), 1), dtype=self._dtype)
-        consumed = C.c_int(0)
-        f = self._fn("general_work")
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        n = _check(f(self._h, int(noutput_items), len(x), _ptr(x), _ptr(out), C.byref(consumed)))
-        return out[:n].copy(), consumed.value
-
-    def general_work_device(self, noutput_items, ninput_items, d_in, d_out, stream=None):
-        """returns (produced, consumed); the outputs are in d_out once `stream` has run"""
-        consumed = C.c_int(0)
-        f = self._fn("general_work_device")
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
-        n = _check(f(self._h, int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out),
-                     C.byref(consumed), _stream(stream)))
-        return n, consumed.value
-
-    def run_captures_device(self, n_streams, n_samples, d_in, in_stride_items, d_out, out_stride_items,
-                            stream=None):
-        """n_streams fresh-state captures (no history in front) in one launch; returns the outputs per capture.
-        d_out=None only returns that number."""
-        n_out = C.c_size_t(0)
-        f = self._fn("run_captures_device")
-        f.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                      C.POINTER(C.c_size_t), C.c_void_p]
-        _check(f(self._h, int(n_streams), int(n_samples), _devptr(d_in), int(in_stride_items), _devptr(d_out),
-                 int(out_stride_items), C.byref(n_out), _stream(stream)))
-        return n_out.value
-
-    def captures_nout(self, n_samples):
-        """outputs of one fresh-state capture of n_samples items"""
-        return self.run_captures_device(1, n_samples, None, n_samples, None, 0)
-
-
-class pfb_arb_resampler_ccf(_pfb_arb_resampler):
-    """gr.pfb_arb_resampler_ccf(rate, taps, filter_size=32)"""
-    _kind = "ccf"
-    _dtype = np.complex64
-
-
-class pfb_arb_resampler_fff(_pfb_arb_resampler):
-    """gr.pfb_arb_resampler_fff(rate, taps, filter_size=32)"""
-    _kind = "fff"
-    _dtype = np.float32
-
-
-# ----------------------------------------------------------------------------
-# gr.fractional_interpolator_ff / gr.fractional_interpolator_cc  (filter/gr_fractional_interpolator_ff.i)
-# ----------------------------------------------------------------------------
-class _fractional_interpolator(_Block):
-    _kind = None
-    _dtype = None
-
-    def __init__(self, phase_shift, interp_ratio, device=0):
-        _Block.__init__(self)
-        self._destroy = "grhip_fractional_interpolator_%s_destroy" % self._kind
-        f = self._fn("create")
-        f.argtypes = [C.POINTER(C.c_void_p), C.c_float, C.c_float, C.c_int]
-        _check(f(C.byref(self._h), float(phase_shift), float(interp_ratio), int(device)))
-
-    def _fn(self, name):
-        return getattr(lib(), "grhip_fractional_interpolator_%s_%s" % (self._kind, name))
-
-    def _getf(self, name):
-        f = self._fn(name)
-        f.argtypes = [C.c_void_p]
-        f.restype = C.c_float
-        return float(f(self._h))
-
-    def _setf(self, name, v):
-        f = self._fn(name)
-        f.argtypes = [C.c_void_p, C.c_float]
-        _check(f(self._h, float(v)))
-
-    def mu(self):
-        return self._getf("mu")
-
-    def interp_ratio(self):
-        return self._getf("interp_ratio")
-
-    def set_mu(self, mu):
-        self._setf("set_mu", mu)
-
-    def set_interp_ratio(self, interp_ratio):
-        self._setf("set_interp_ratio", interp_ratio)
+        return getattr(lib(), "%s_%s_%s" % (self._prefix, self._kind, name))
 
     def set_mode(self, mode):
         _check(self._fn("set_mode")(self._h, int(mode)))
@@ -1352,6 +1245,88 @@ class _fractional_interpolator(_Block):
     def captures_nout(self, n_samples):
         """outputs of one fresh-state capture of n_samples items"""
         return self.run_captures_device(1, n_samples, None, n_samples, None, 0)
+
+
+# ----------------------------------------------------------------------------
+# gr.pfb_arb_resampler_ccf / gr.pfb_arb_resampler_fff  (filter/gr_pfb_arb_resampler_ccf.i)
+# ----------------------------------------------------------------------------
+class _pfb_arb_resampler(_sched_block):
+    _prefix = "grhip_pfb_arb_resampler"
+
+    def __init__(self, rate, taps, filter_size=32, device=0):
+        _sched_block.__init__(self)
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        f = self._fn("create")
+        f.argtypes = [C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_size_t, C.c_uint, C.c_int]
+        _check(f(C.byref(self._h), float(rate), _ptr(t), len(t), int(filter_size), int(device)))
+
+    def set_rate(self, rate):
+        f = self._fn("set_rate")
+        f.argtypes = [C.c_void_p, C.c_float]
+        _check(f(self._h, float(rate)))
+
+    def taps_per_filter(self):
+        return _check(self._fn("taps_per_filter")(self._h))
+
+    # the two overrides below only carry this block's wording of the docstrings
+    def general_work(self, noutput_items, input_items):
+        """returns (out, consumed); input_items carries the history in front"""
+        return _sched_block.general_work(self, noutput_items, input_items)
+
+    def run_captures_device(self, n_streams, n_samples, d_in, in_stride_items, d_out, out_stride_items,
+                            stream=None):
+        """n_streams fresh-state captures (no history in front) in one launch; returns the outputs per capture.
+        d_out=None only returns that number."""
+        return _sched_block.run_captures_device(self, n_streams, n_samples, d_in, in_stride_items, d_out,
+                                                out_stride_items, stream)
+
+
+class pfb_arb_resampler_ccf(_pfb_arb_resampler):
+    """gr.pfb_arb_resampler_ccf(rate, taps, filter_size=32)"""
+    _kind = "ccf"
+    _dtype = np.complex64
+
+
+class pfb_arb_resampler_fff(_pfb_arb_resampler):
+    """gr.pfb_arb_resampler_fff(rate, taps, filter_size=32)"""
+    _kind = "fff"
+    _dtype = np.float32
+
+
+# ----------------------------------------------------------------------------
+# gr.fractional_interpolator_ff / gr.fractional_interpolator_cc  (filter/gr_fractional_interpolator_ff.i)
+# ----------------------------------------------------------------------------
+class _fractional_interpolator(_sched_block):
+    _prefix = "grhip_fractional_interpolator"
+
+    def __init__(self, phase_shift, interp_ratio, device=0):
+        _sched_block.__init__(self)
+        f = self._fn("create")
+        f.argtypes = [C.POINTER(C.c_void_p), C.c_float, C.c_float, C.c_int]
+        _check(f(C.byref(self._h), float(phase_shift), float(interp_ratio), int(device)))
+
+    def _getf(self, name):
+        f = self._fn(name)
+        f.argtypes = [C.c_void_p]
+        f.restype = C.c_float
+        return float(f(self._h))
+
+    def _setf(self, name, v):
+        f = self._fn(name)
+        f.argtypes = [C.c_void_p, C.c_float]
+        _check(f(self._h, float(v)))
+
+    def mu(self):
+        return self._getf("mu")
+
+    def interp_ratio(self):
+        return self._getf("interp_ratio")
+
+    def set_mu(self, mu):
+        self._setf("set_mu", mu)
+
+    def set_interp_ratio(self, interp_ratio):
+        self._setf("set_interp_ratio", interp_ratio)
 
 
 class fractional_interpolator_ff(_fractional_interpolator):

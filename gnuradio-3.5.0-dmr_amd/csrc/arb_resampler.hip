@@ -2,7 +2,7 @@
 //
 // Output k of the reference's general_work is  out = o0 + o1*acc  with  o0 = filters[j].filter(&in[count]),
 // o1 = diff_filters[j].filter(&in[count]).  Where (count, j, acc) of output k comes from does not depend on the data
-// (ArbSched, arb_resampler.h): every lane computes the place of its own outputs, there is no serial pass.
+// (ArbSched, sched_plan.h): every lane computes the place of its own outputs, there is no serial pass.
 //
 // arb_kernel: one workgroup = `tile` consecutive outputs of one capture (blockIdx.y), one output per lane and step
 // (lane t: outputs t, t + 256, ...; neighbouring lanes read neighbouring samples).  The tile's input span
@@ -17,24 +17,12 @@
 //                    as a multiply and an add per component: bit-exact against the reference's generic build.
 //   generic = false: one blended tap h + acc*dh per tap (an FMA), then FMAs into two accumulators.
 #include "arb_resampler.h"
+#include "fir_arith.h"
 #include "grhip_internal.h"
 
 namespace grhip {
 
 namespace {
-
-__device__ inline float2 zero_of(float2) { return make_float2(0.f, 0.f); }
-__device__ inline float zero_of(float) { return 0.f; }
-// acc + h*x, unfused (float * gr_complex is (h*re, h*im))
-__device__ inline float2 mac_unfused(float2 acc, float h, float2 x) { return make_float2(acc.x + h * x.x, acc.y + h * x.y); }
-__device__ inline float mac_unfused(float acc, float h, float x) { return acc + h * x; }
-__device__ inline float2 mac_fma(float2 acc, float h, float2 x)
-{
-    return make_float2(__builtin_fmaf(h, x.x, acc.x), __builtin_fmaf(h, x.y, acc.y));
-}
-__device__ inline float mac_fma(float acc, float h, float x) { return __builtin_fmaf(h, x, acc); }
-__device__ inline float2 add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ inline float add(float a, float b) { return a + b; }
 
 template <class T, bool GENERIC>
 __global__ void __launch_bounds__(ARB_THREADS) arb_kernel(ArbLaunch a)
@@ -70,6 +58,7 @@ __global__ void __launch_bounds__(ARB_THREADS) arb_kernel(ArbLaunch a)
     if (span > a.span_cap) span = a.span_cap;           // never past the LDS image (the host sizes tiles so it fits)
 
     for (int i = t; i < a.R * a.S; i += ARB_THREADS) hs[i] = a.taps[i];
+    // fir_arith.h's stage_span written out: as a call it costs this kernel a different scalar register allocation
     const long long p0 = cf - a.lead;                    // physical index of xs[0]
     for (int ub = t; ub < span; ub += ARB_THREADS * 8) {
         T v[8];

@@ -294,21 +294,12 @@ namespace {
 template <class H>
 int create_analytic(H **h, const float *taps, size_t ntaps, int device)
 {
-    *h = nullptr;
-    auto *b = new (std::nothrow) H();
-    if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    int rc = b->init_device(device);
-    if (!rc) {
+    return make_handle(h, [&](H *b) {
+        int rc = b->init_device(device);
+        if (rc) return rc;
         b->mode = default_mode();
-        rc = b->install(taps, ntaps);
-    }
-    if (rc) {
-        if (b->own_stream) b->destroy();
-        delete b;
-        return rc;
-    }
-    *h = b;
-    return GRHIP_OK;
+        return b->install(taps, ntaps);
+    });
 }
 
 }  // namespace

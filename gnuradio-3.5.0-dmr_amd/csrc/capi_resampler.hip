@@ -319,16 +319,9 @@ int create_t(H **h, const char *kind, bool interp, long long I, long long D, con
     int rc = kind_of(kind, &k);
     if (rc) return rc;
     if (I < 0 || D < 0) return fail(GRHIP_ERANGE, "interpolation and decimation must be > 0");
-    auto *b = new (std::nothrow) H();
-    if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    rc = b->init(k, interp, (unsigned long long)I, (unsigned long long)D, taps, ntaps, device, zeros_behind);
-    if (rc) {
-        if (b->own_stream) b->destroy();
-        delete b;
-        return rc;
-    }
-    *h = b;
-    return GRHIP_OK;
+    return make_handle(h, [&](H *b) {
+        return b->init(k, interp, (unsigned long long)I, (unsigned long long)D, taps, ntaps, device, zeros_behind);
+    });
 }
 
 }  // namespace

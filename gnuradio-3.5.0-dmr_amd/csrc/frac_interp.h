@@ -1,7 +1,9 @@
 // frac_interp.h -- launcher of the fractional_interpolator kernel (csrc/frac_interp.hip), used by
-// csrc/capi_fracinterp.hip.  Not part of the ABI.
+// csrc/capi_fracinterp.hip.  The index schedule it carries (FracSched) is csrc/sched_plan.h.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "sched_plan.h"
 
 namespace grhip {
 
@@ -12,20 +14,7 @@ namespace grhip {
 constexpr int FRAC_THREADS = 256;
 constexpr int FRAC_TILE = 1024;                         // outputs per workgroup, at most
 constexpr int FRAC_SPAN_BYTES = 32 * 1024;
-constexpr int FRAC_NTAPS = 8;
-constexpr int FRAC_NSTEPS = 128;
 constexpr float FRAC_MAX_RATIO = 1048576.0f;            // 2^20
-
-// The index schedule of one call.  Closed form (steps == nullptr), output k of the launch:
-//   T_k = A0 + k*F,  ii_k = ii0 + (T_k >> 24),  m_k = T_k mod 2^24,  imu_k = round-half-even(m_k / 2^17);
-//   with first_one (mu == 1.0f at the start) output 0 is ii0 with filter 128 instead.
-// Walked: steps[k] = ((ii_k - 0) << 8) | imu_k, ii_k counted from the start of `in` as in the closed form.
-struct FracSched {
-    long long ii0 = 0;
-    unsigned long long A0 = 0, F = 0;
-    int first_one = 0;
-    const unsigned long long *steps = nullptr;  // device array of nout entries, or nullptr for the closed form
-};
 
 struct FracLaunch {
     const void *in = nullptr;                   // float2 (cc) or float (ff) items
@@ -36,7 +25,7 @@ struct FracLaunch {
     const float *taps = nullptr;                // DeviceTables::mmse_rev: [8][129], taps[t][imu] multiplies in[ii + t]
     int tile = 1;                               // outputs per workgroup
     int span_cap = 0;                           // LDS items reserved for a tile's input span
-    FracSched sc;
+    FracSched sc;                               // sched_plan.h (with FRAC_NTAPS and FRAC_NSTEPS)
 };
 
 // complex: float2 items (cc) else float (ff); generic: the reference's generic order, bit-exact

@@ -2,7 +2,7 @@
 //
 // Output k of the reference's general_work is filters[imu_k]->filter(&in[ii_k]) with the 8-tap MMSE bank
 // (filter/gri_mmse_fir_interpolator.cc:61-71).  Where (ii_k, imu_k) comes from does not depend on the data
-// (FracSched, frac_interp.h): every lane computes the place of its own outputs, there is no serial pass.
+// (FracSched, sched_plan.h): every lane computes the place of its own outputs, there is no serial pass.
 //
 // frac_kernel: one workgroup = `tile` consecutive outputs of one capture (blockIdx.y), one output per lane and step
 // (lane t: outputs t, t + 256, ...; neighbouring lanes read neighbouring samples).  The tile's input span
@@ -17,6 +17,7 @@
 //                    ones over the even and the odd taps and their sum for cc; unfused multiply then add (the
 //                    Makefile's -ffp-contract=off keeps them apart): bit-exact against the reference's generic build.
 //   generic = false: FMAs into two accumulators.
+#include "fir_arith.h"
 #include "frac_interp.h"
 #include "grhip_internal.h"
 
@@ -25,21 +26,6 @@ namespace grhip {
 namespace {
 
 constexpr int FRAC_BANK = FRAC_NTAPS * (FRAC_NSTEPS + 1);       // 1032 floats
-
-__device__ inline float2 zero_of(float2) { return make_float2(0.f, 0.f); }
-__device__ inline float zero_of(float) { return 0.f; }
-__device__ inline float2 mac_unfused(float2 acc, float h, float2 x) { return make_float2(acc.x + h * x.x, acc.y + h * x.y); }
-__device__ inline float mac_unfused(float acc, float h, float x) { return acc + h * x; }
-__device__ inline float2 mac_fma(float2 acc, float h, float2 x)
-{
-    return make_float2(__builtin_fmaf(h, x.x, acc.x), __builtin_fmaf(h, x.y, acc.y));
-}
-__device__ inline float mac_fma(float acc, float h, float x) { return __builtin_fmaf(h, x, acc); }
-__device__ inline float2 add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ inline float add(float a, float b) { return a + b; }
-
-// imu = (int) rint(mu * NSTEPS) for mu = m * 2^-24: round-half-even of m / 2^17
-__device__ inline int imu_of(unsigned m) { return (int)((m + 0xffffu + ((m >> 17) & 1u)) >> 17); }
 
 template <class T, bool GENERIC>
 __global__ void __launch_bounds__(FRAC_THREADS) frac_kernel(FracLaunch a)
@@ -77,21 +63,7 @@ __global__ void __launch_bounds__(FRAC_THREADS) frac_kernel(FracLaunch a)
         const int k = i / (FRAC_NSTEPS + 1), imu = i - k * (FRAC_NSTEPS + 1);       // taps[k][imu], coalesced
         hs[imu * FRAC_NTAPS + (k ^ (((imu >> 3) & 1) << 2))] = a.taps[i];
     }
-    for (int ub = t; ub < span; ub += FRAC_THREADS * 8) {
-        T v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int u = ub + FRAC_THREADS * i;
-            const long long p = cf + u;
-            v[i] = zero_of(T());
-            if (u < span && p >= 0 && p < a.n_phys) v[i] = in[p];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int u = ub + FRAC_THREADS * i;
-            if (u < span) xs[u] = v[i];
-        }
-    }
+    stage_span<T, FRAC_THREADS>(xs, in, cf, span, a.n_phys);
     __syncthreads();
 
     const int off_max = a.span_cap - FRAC_NTAPS;
@@ -105,7 +77,7 @@ __global__ void __launch_bounds__(FRAC_THREADS) frac_kernel(FracLaunch a)
         } else {
             const unsigned long long tl = Tm + (unsigned long long)k * a.sc.F;
             off = boff + (int)(tl >> 24);
-            imu = imu_of((unsigned)(tl & 0xffffffull));
+            imu = frac_imu_of((unsigned)(tl & 0xffffffull));
         }
         off = off < 0 ? 0 : (off > off_max ? off_max : off);        // the host's tiles keep it inside; never read past xs
         imu = imu > FRAC_NSTEPS ? FRAC_NSTEPS : imu;

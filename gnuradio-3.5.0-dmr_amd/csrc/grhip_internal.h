@@ -174,6 +174,24 @@ struct HandleBase {
     }
 };
 
+// The tail of a create entry point: allocate a handle H, run init(handle) and hand it out in *h.  When init fails
+// the handle is torn down again (its destroy() only once init_device has given it a stream) and *h stays null.
+template <class H, class Init>
+int make_handle(H **h, Init &&init)
+{
+    *h = nullptr;
+    auto *b = new (std::nothrow) H();
+    if (!b) return fail(GRHIP_ENOMEM, "alloc");
+    int rc = init(b);
+    if (rc) {
+        if (b->own_stream) b->destroy();
+        delete b;
+        return rc;
+    }
+    *h = b;
+    return GRHIP_OK;
+}
+
 int default_mode();
 inline bool mode_valid(int m) { return m == GRHIP_MODE_FAST || m == GRHIP_MODE_GENERIC || m == GRHIP_MODE_FAST_VALU || m == GRHIP_MODE_FAST_REFTAPS; }
 inline bool mode_fast(int m) { return m != GRHIP_MODE_GENERIC; }          // FAST, FAST_VALU or FAST_REFTAPS

@@ -17,6 +17,7 @@
 //   generic = false: RG residues per task share each input item read from LDS (RG FMAs per read).  Residue q of the
 //                    group starts d_q items after the group's first; its taps come from a bank row padded with WP zeros
 //                    on both sides, so every residue runs the same loop over u < nt + d_max with tap [WP - d_q + u].
+#include "fir_arith.h"
 #include "resampler.h"
 #include "grhip_internal.h"
 
@@ -25,30 +26,6 @@
 namespace grhip {
 
 namespace {
-
-__device__ inline float2 zero_of(float2) { return make_float2(0.f, 0.f); }
-__device__ inline float zero_of(float) { return 0.f; }
-
-// acc + h*x unfused, in the reference's operand order
-__device__ inline float mac_ref(float acc, float h, float x) { return acc + h * x; }
-__device__ inline float2 mac_ref(float2 acc, float h, float2 x) { return make_float2(acc.x + x.x * h, acc.y + x.y * h); }
-__device__ inline float2 mac_ref(float2 acc, float2 h, float2 x)
-{
-    const float ac = h.x * x.x, bd = h.y * x.y, ad = h.x * x.y, bc = h.y * x.x;
-    return make_float2(acc.x + (ac - bd), acc.y + (ad + bc));
-}
-__device__ inline float mac_fma(float acc, float h, float x) { return __builtin_fmaf(h, x, acc); }
-__device__ inline float2 mac_fma(float2 acc, float h, float2 x)
-{
-    return make_float2(__builtin_fmaf(h, x.x, acc.x), __builtin_fmaf(h, x.y, acc.y));
-}
-__device__ inline float2 mac_fma(float2 acc, float2 h, float2 x)
-{
-    return make_float2(__builtin_fmaf(h.x, x.x, __builtin_fmaf(-h.y, x.y, acc.x)),
-                       __builtin_fmaf(h.x, x.y, __builtin_fmaf(h.y, x.x, acc.y)));
-}
-__device__ inline float2 add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ inline float add(float a, float b) { return a + b; }
 
 template <class T, class H, bool GENERIC, int RG>
 __global__ void __launch_bounds__(RS_THREADS)
@@ -135,12 +112,12 @@ rs_kernel(const T *__restrict__ in, T *__restrict__ out, const H *__restrict__ b
             for (; k < nn; k += NU) {
 #pragma unroll
                 for (int q = 0; q < NU; ++q) {
-                    acc[q] = mac_ref(acc[q], h[k + q], xl[uo]);
+                    acc[q] = mac_unfused(acc[q], h[k + q], xl[uo]);
                     if (++ph == Dp) { ph = 0; uo += 1 - (Dp - 1) * L; } else uo += L;
                 }
             }
             for (; k < nt; ++k) {
-                acc[0] = mac_ref(acc[0], h[k], xl[uo]);
+                acc[0] = mac_unfused(acc[0], h[k], xl[uo]);
                 if (++ph == Dp) { ph = 0; uo += 1 - (Dp - 1) * L; } else uo += L;
             }
             r = acc[0];
