@@ -18,13 +18,10 @@ static int adapter_create(grhip_copy_adapter **h, size_t item_bytes, bool head, 
     if (!h) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
     if (item_bytes == 0) return fail(GRHIP_EINVAL, "item size must be > 0");
-    auto *b = new (std::nothrow) grhip_copy_adapter();
-    if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    b->item_size = item_bytes; b->head = head; b->nitems = nitems;
-    int rc = b->init_device(device);
-    if (rc) { b->destroy_base(); delete b; return rc; }
-    *h = b;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_copy_adapter *b) {
+        b->item_size = item_bytes; b->head = head; b->nitems = nitems;
+        return b->init_device(device);
+    });
 }
 
 extern "C" {
@@ -42,9 +39,7 @@ int grhip_head_create(grhip_copy_adapter **h, size_t sizeof_stream_item, unsigne
 
 void grhip_copy_adapter_destroy(grhip_copy_adapter *h)
 {
-    if (!h) return;
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_head_reset(grhip_copy_adapter *h)           // gr_head::reset(), general/gr_head.h:51

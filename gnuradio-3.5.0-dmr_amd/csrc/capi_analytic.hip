@@ -200,14 +200,6 @@ struct grhip_analytic_base : HandleBase {
         memcpy(out, taps.data(), (size_t)ntaps * sizeof(float));
         return ntaps;
     }
-
-    void destroy()
-    {
-        (void)bind();
-        d_rev.release();
-        d_odd.release();
-        destroy_base();
-    }
 };
 
 struct grhip_hilbert_fc : grhip_analytic_base {};
@@ -280,13 +272,6 @@ struct grhip_goertzel_fc : HandleBase {
                                   return work_device(noutput_items, d_in, d_out, s);
                               });
     }
-
-    void destroy()
-    {
-        (void)bind();
-        d_tab.release();
-        destroy_base();
-    }
 };
 
 namespace {
@@ -340,9 +325,7 @@ int grhip_filter_delay_fc_create(grhip_filter_delay_fc **h, const float *taps, s
 #define GRHIP_ANALYTIC_COMMON(NAME)                                                                                    \
     void grhip_##NAME##_destroy(grhip_##NAME *h)                                                                       \
     {                                                                                                                  \
-        if (!h) return;                                                                                                \
-        h->destroy();                                                                                                  \
-        delete h;                                                                                                      \
+        destroy_handle(h);                                                                                             \
     }                                                                                                                  \
     int grhip_##NAME##_set_mode(grhip_##NAME *h, int mode)                                                             \
     {                                                                                                                  \
@@ -393,25 +376,17 @@ int grhip_goertzel_fc_create(grhip_goertzel_fc **h, int rate, int len, float fre
     *h = nullptr;
     if (len < 1 || len > (1 << 24)) return fail(GRHIP_EINVAL, "goertzel_fc: len must be in [1, 2^24]");
     if (rate == 0) return fail(GRHIP_EINVAL, "goertzel_fc: rate must not be 0");
-    auto *g = new (std::nothrow) grhip_goertzel_fc();
-    if (!g) return fail(GRHIP_ENOMEM, "alloc");
-    g->rate = rate; g->len = len; g->freq = freq;
-    g->setparms();
-    int rc = g->init_device(device);
-    if (rc) {
-        delete g;
-        return rc;
-    }
-    g->mode = default_mode();
-    *h = g;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_goertzel_fc *g) {
+        g->rate = rate; g->len = len; g->freq = freq;
+        g->setparms();
+        g->mode = default_mode();
+        return g->init_device(device);
+    });
 }
 
 void grhip_goertzel_fc_destroy(grhip_goertzel_fc *h)
 {
-    if (!h) return;
-    h->destroy();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_goertzel_fc_set_freq(grhip_goertzel_fc *h, float freq)

@@ -144,14 +144,6 @@ struct grhip_pfb_arb_resampler_base : SchedBlock<grhip_pfb_arb_resampler_base> {
         rp = n; rate = r;
         return GRHIP_OK;
     }
-
-    void destroy()
-    {
-        (void)bind();
-        walked.release();
-        d_taps.release();
-        destroy_base();
-    }
 };
 
 struct grhip_pfb_arb_resampler_ccf : grhip_pfb_arb_resampler_base {};

@@ -20,7 +20,32 @@ int mm_init_state(MMState &s, float omega, float gain_omega, float mu, float gai
 int corr_set_code(CorrParams &p, unsigned long long &flag_bit, const char *code, size_t len);
 }
 
+// A stream or an event the chain makes beside the handle's own stream, destroyed with the handle.
+template <class T, hipError_t (*Destroy)(T)>
+struct Owned {
+    T v = nullptr;
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    ~Owned() { reset(); }
+    void reset() { if (v) (void)Destroy(v); v = nullptr; }
+    operator T() const { return v; }
+    T *put() { return &v; }         // for the create call of an empty owner
+};
+using OwnedStream = Owned<hipStream_t, hipStreamDestroy>;
+using OwnedEvent = Owned<hipEvent_t, hipEventDestroy>;
+
 struct grhip_dmr_chain : HandleBase {
+    // FAST modes: the capture is processed in PIPE_CHUNKS time slices; the clock recovery of slice c (second
+    // stream) runs beside the FIR of slice c+1
+#ifndef GRHIP_PIPE_CHUNKS
+#define GRHIP_PIPE_CHUNKS 32
+#endif
+    static constexpr int PIPE_CHUNKS = GRHIP_PIPE_CHUNKS;
+    // The side streams and the events come first: members go in reverse order, so the buffers below are freed
+    // before them, and the handle's own stream goes last.
+    OwnedStream st_mm8, st_fir8, st2, st3;
+    OwnedEvent ev_begin, ev_end, ev_tail, ev_fir[PIPE_CHUNKS], ev_mm[PIPE_CHUNKS];
     XlatingCore core;
     float gain = 1.f;
     MMState mm_init;
@@ -31,11 +56,6 @@ struct grhip_dmr_chain : HandleBase {
     DevBuf d_demod, d_soft, d_mm, d_mm_init, d_counts, d_ystate, d_corr, d_scratch;
     size_t out_stride = 0;
     int mode = GRHIP_MODE_FAST;
-    // FAST modes: the capture is processed in PIPE_CHUNKS time slices; the clock recovery of slice c (second
-    // stream) runs beside the FIR of slice c+1
-#ifndef GRHIP_PIPE_CHUNKS
-#define GRHIP_PIPE_CHUNKS 32
-#endif
 #ifndef GRHIP_CHAIN_WGCAP
 #define GRHIP_CHAIN_WGCAP 1
 #endif
@@ -61,7 +81,6 @@ struct grhip_dmr_chain : HandleBase {
 #ifndef GRHIP_MM_BIG_FORM
 #define GRHIP_MM_BIG_FORM 8           // the form from GRHIP_MM_ROWS_MIN captures on: 8 or 32 captures per wave
 #endif
-    hipStream_t st_mm8 = nullptr, st_fir8 = nullptr;
     int fir8_cus = 0, mm8_cus = 0, ncu = 0;
     int captures_per_wave = 0;        // 0: by batch size; 1 / 8 / 32: forced (grhip_dmr_chain_set_captures_per_wave)
     size_t max_symbols = 0;           // 0: none (grhip_dmr_chain_set_max_symbols)
@@ -76,20 +95,18 @@ struct grhip_dmr_chain : HandleBase {
     void ensure_masks(int cus)
     {
         if (cus == mm8_cus && st_mm8 && st_fir8) return;
-        if (st_mm8) (void)hipStreamDestroy(st_mm8);
-        if (st_fir8) (void)hipStreamDestroy(st_fir8);
-        st_mm8 = st_fir8 = nullptr; mm8_cus = fir8_cus = 0;
+        st_mm8.reset(); st_fir8.reset();
+        mm8_cus = fir8_cus = 0;
         if (cus <= 0 || ncu < 4 * cus || ncu > 1024) return;
         uint32_t m_mm[32] = {}, m_fir[32] = {};
         for (int i = 0; i < ncu; ++i) (i < cus ? m_mm : m_fir)[i / 32] |= 1u << (i % 32);
         const uint32_t words = (uint32_t)((ncu + 31) / 32);
-        if (hipExtStreamCreateWithCUMask(&st_mm8, words, m_mm) != hipSuccess) st_mm8 = nullptr;
-        if (st_mm8 && hipExtStreamCreateWithCUMask(&st_fir8, words, m_fir) != hipSuccess) st_fir8 = nullptr;
-        if (st_mm8 && !st_fir8) { (void)hipStreamDestroy(st_mm8); st_mm8 = nullptr; }
+        if (hipExtStreamCreateWithCUMask(st_mm8.put(), words, m_mm) != hipSuccess) st_mm8.v = nullptr;
+        if (st_mm8 && hipExtStreamCreateWithCUMask(st_fir8.put(), words, m_fir) != hipSuccess) st_fir8.v = nullptr;
+        if (st_mm8 && !st_fir8) st_mm8.reset();
         if (st_fir8) { fir8_cus = ncu - cus; mm8_cus = cus; }
         (void)hipGetLastError();
     }
-    static constexpr int PIPE_CHUNKS = GRHIP_PIPE_CHUNKS;
     // 4FSK tail (grhip_dmr_chain_set_four_level): pager_slicer_fb -> unpack_k_bits(2) in front of the correlator
     bool four_level = false;
     float pager_alpha = 0.f;
@@ -104,8 +121,6 @@ struct grhip_dmr_chain : HandleBase {
 #define GRHIP_CHAIN_SLICED_TAIL 0
 #endif
     DevBuf d_cnt_hist, d_pos;
-    hipStream_t st2 = nullptr, st3 = nullptr;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_tail = nullptr, ev_fir[PIPE_CHUNKS] = {}, ev_mm[PIPE_CHUNKS] = {};
 };
 
 extern "C" {
@@ -128,78 +143,55 @@ int grhip_dmr_chain_create(grhip_dmr_chain **h, const grhip_dmr_chain_params *p,
     if (rc) return rc;
     cp.threshold = (unsigned)p->threshold;
 
-    auto *c = new (std::nothrow) grhip_dmr_chain();
-    if (!c) return fail(GRHIP_ENOMEM, "alloc");
-    c->gain = p->demod_gain; c->mm_init = ms; c->cp = cp; c->S = n_streams;
-    c->max_samples = max_samples_per_stream;
-    c->max_out = max_samples_per_stream / p->decimation;
-    c->out_stride = ((c->max_out + 63) / 64) * 64 + 64;     // 16-byte aligned rows
-    rc = c->init_device(device);
-    if (!rc) rc = get_device_tables(device, &c->tabs);
-    if (!rc) {
+    return make_handle(h, [&](grhip_dmr_chain *c) {
+        c->gain = p->demod_gain; c->mm_init = ms; c->cp = cp; c->S = n_streams;
+        c->max_samples = max_samples_per_stream;
+        c->max_out = max_samples_per_stream / p->decimation;
+        c->out_stride = ((c->max_out + 63) / 64) * 64 + 64;     // 16-byte aligned rows
+        int rc = c->init_device(device);
+        if (!rc) rc = get_device_tables(device, &c->tabs);
+        if (rc) return rc;
         c->core.decim = p->decimation;
         c->core.proto.assign((const std::complex<float> *)p->taps, (const std::complex<float> *)p->taps + p->ntaps);
         c->core.center_freq = p->center_freq; c->core.sampling_freq = p->sampling_freq;
         c->core.for_demod = true;           // decimations other than 1/2/4: the direct kernel with the fused demodulator
-        rc = c->core.build(device);
-    }
-    if (!rc && !c->core.use_tiled && !c->core.use_mfma && !(c->core.use_hidec && c->core.hidec_premix))
-        rc = fail(GRHIP_EINVAL, "dmr_chain needs a decimation/tap count a batched FIR engine supports");
-    if (!rc) {
-        hipError_t e = hipStreamCreateWithFlags(&c->st2, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->st3, hipStreamNonBlocking);
+        if ((rc = c->core.build(device))) return rc;
+        if (!c->core.use_tiled && !c->core.use_mfma && !(c->core.use_hidec && c->core.hidec_premix))
+            return fail(GRHIP_EINVAL, "dmr_chain needs a decimation/tap count a batched FIR engine supports");
+        hipError_t e = hipStreamCreateWithFlags(c->st2.put(), hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(c->st3.put(), hipStreamNonBlocking);
         if (e == hipSuccess && GRHIP_MM_CUS > 0) {
             (void)hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, device);
             c->ensure_masks(c->mm_cus_wanted());
         }
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_begin, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_end, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(c->ev_begin.put(), hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(c->ev_end.put(), hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(c->ev_tail.put(), hipEventDisableTiming);
         for (int i = 0; i < grhip_dmr_chain::PIPE_CHUNKS && e == hipSuccess; ++i)
-            e = hipEventCreateWithFlags(&c->ev_fir[i], hipEventDisableTiming);
+            e = hipEventCreateWithFlags(c->ev_fir[i].put(), hipEventDisableTiming);
         for (int i = 0; i < grhip_dmr_chain::PIPE_CHUNKS && e == hipSuccess; ++i)
-            e = hipEventCreateWithFlags(&c->ev_mm[i], hipEventDisableTiming);
-        if (e != hipSuccess) rc = fail(GRHIP_ERUNTIME, "stream / event creation: %s", hipGetErrorString(e));
-    }
-    size_t S = (size_t)n_streams;
-    if (!rc) rc = c->d_demod.reserve(S * c->out_stride * 4);
-    if (!rc) rc = c->d_soft.reserve(S * c->out_stride * 4);
-    if (!rc) rc = c->d_mm.reserve(S * sizeof(MMState));
-    if (!rc) rc = c->d_mm_init.reserve(S * sizeof(MMState));
-    if (!rc) rc = c->d_counts.reserve(S * 2 * sizeof(int));
-    if (!rc) rc = c->d_cnt_hist.reserve((size_t)grhip_dmr_chain::PIPE_CHUNKS * S * 2 * sizeof(int));
-    if (!rc) rc = c->d_ystate.reserve(S * 2 * sizeof(float2));
-    if (!rc) rc = c->d_corr.reserve(S * sizeof(CorrState));
-    if (!rc) {
+            e = hipEventCreateWithFlags(c->ev_mm[i].put(), hipEventDisableTiming);
+        if (e != hipSuccess) return fail(GRHIP_ERUNTIME, "stream / event creation: %s", hipGetErrorString(e));
+        const size_t S = (size_t)n_streams;
+        rc = c->d_demod.reserve(S * c->out_stride * 4);
+        if (!rc) rc = c->d_soft.reserve(S * c->out_stride * 4);
+        if (!rc) rc = c->d_mm.reserve(S * sizeof(MMState));
+        if (!rc) rc = c->d_mm_init.reserve(S * sizeof(MMState));
+        if (!rc) rc = c->d_counts.reserve(S * 2 * sizeof(int));
+        if (!rc) rc = c->d_cnt_hist.reserve((size_t)grhip_dmr_chain::PIPE_CHUNKS * S * 2 * sizeof(int));
+        if (!rc) rc = c->d_ystate.reserve(S * 2 * sizeof(float2));
+        if (!rc) rc = c->d_corr.reserve(S * sizeof(CorrState));
+        if (rc) return rc;
         std::vector<MMState> init(S, ms);
-        hipError_t e = hipMemcpy(c->d_mm_init.p, init.data(), S * sizeof(MMState), hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = fail(GRHIP_ERUNTIME, "state upload");
-    }
-    if (rc) { grhip_dmr_chain_destroy(c); return rc; }
-    *h = c;
-    return GRHIP_OK;
+        if (hipMemcpy(c->d_mm_init.p, init.data(), S * sizeof(MMState), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(GRHIP_ERUNTIME, "state upload");
+        return GRHIP_OK;
+    });
 }
 
 void grhip_dmr_chain_destroy(grhip_dmr_chain *h)
 {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    h->core.release();
-    h->d_demod.release(); h->d_soft.release(); h->d_mm.release(); h->d_mm_init.release();
-    h->d_counts.release(); h->d_ystate.release(); h->d_corr.release(); h->d_scratch.release();
-    h->d_sym.release(); h->d_dibits.release(); h->d_avg.release(); h->d_nbits2.release();
-    h->d_cnt_hist.release(); h->d_pos.release();
-    if (h->st2) (void)hipStreamDestroy(h->st2);
-    if (h->st3) (void)hipStreamDestroy(h->st3);
-    if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
-    for (auto &e : h->ev_mm) if (e) (void)hipEventDestroy(e);
-    if (h->st_mm8) (void)hipStreamDestroy(h->st_mm8);
-    if (h->st_fir8) (void)hipStreamDestroy(h->st_fir8);
-    if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
-    if (h->ev_end) (void)hipEventDestroy(h->ev_end);
-    for (auto &e : h->ev_fir) if (e) (void)hipEventDestroy(e);
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_dmr_chain_run_device(grhip_dmr_chain *h, const void *d_in, size_t n_samples,

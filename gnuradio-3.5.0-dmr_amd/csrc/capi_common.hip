@@ -145,15 +145,13 @@ int HandleBase::d2h(void *dst_host, const void *src_dev, size_t bytes, hipStream
     return GRHIP_OK;
 }
 
-void HandleBase::destroy_base()
+HandleBase::~HandleBase()
 {
-    (void)hipSetDevice(device);
     pin_release(pin_up);
     pin_release(pin_down);
     stage_in.release();
     stage_out.release();
     if (own_stream) (void)hipStreamDestroy(own_stream);
-    own_stream = nullptr;
 }
 
 static std::mutex g_tab_mutex;

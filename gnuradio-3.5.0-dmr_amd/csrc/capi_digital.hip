@@ -98,25 +98,19 @@ int grhip_clock_recovery_mm_ff_create(grhip_clock_recovery_mm_ff **h, float omeg
     MMState s;
     int rc = mm_init_state(s, omega, gain_omega, mu, gain_mu, omega_relative_limit);
     if (rc) return rc;
-    auto *m = new (std::nothrow) grhip_clock_recovery_mm_ff();
-    if (!m) return fail(GRHIP_ENOMEM, "alloc");
-    rc = m->init_device(device);
-    if (!rc) rc = get_device_tables(device, &m->tabs);
-    if (!rc) rc = m->d_state.reserve(sizeof(MMState));
-    if (!rc) rc = m->d_counts.reserve(2 * sizeof(int));
-    if (!rc) rc = m->write_state(s);
-    if (rc) { m->d_state.release(); m->d_counts.release(); m->destroy_base(); delete m; return rc; }
-    *h = m;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_clock_recovery_mm_ff *m) {
+        int rc = m->init_device(device);
+        if (!rc) rc = get_device_tables(device, &m->tabs);
+        if (!rc) rc = m->d_state.reserve(sizeof(MMState));
+        if (!rc) rc = m->d_counts.reserve(2 * sizeof(int));
+        if (!rc) rc = m->write_state(s);
+        return rc;
+    });
 }
 
 void grhip_clock_recovery_mm_ff_destroy(grhip_clock_recovery_mm_ff *h)
 {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    h->d_state.release(); h->d_counts.release();
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_clock_recovery_mm_ff_forecast(const grhip_clock_recovery_mm_ff *h, int noutput_items)
@@ -198,19 +192,12 @@ int grhip_binary_slicer_fb_create(grhip_binary_slicer_fb **h, int device)
 {
     if (!h) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
-    auto *b = new (std::nothrow) grhip_binary_slicer_fb();
-    if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    int rc = b->init_device(device);
-    if (rc) { b->destroy_base(); delete b; return rc; }
-    *h = b;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_binary_slicer_fb *b) { return b->init_device(device); });
 }
 
 void grhip_binary_slicer_fb_destroy(grhip_binary_slicer_fb *h)
 {
-    if (!h) return;
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_binary_slicer_fb_work_device(grhip_binary_slicer_fb *h, int noutput_items, const float *d_in,
@@ -244,25 +231,19 @@ int grhip_pager_slicer_fb_create(grhip_pager_slicer_fb **h, float alpha, int dev
 {
     if (!h) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
-    auto *b = new (std::nothrow) grhip_pager_slicer_fb();
-    if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    b->alpha = alpha;
-    b->beta = (float)(1.0 - (double)alpha);          // pager_slicer_fb.cc:40
-    int rc = b->init_device(device);
-    if (!rc) rc = b->d_avg.reserve(sizeof(float));
-    if (!rc) rc = zero_device(b->d_avg.p, sizeof(float));
-    if (rc) { b->d_avg.release(); b->destroy_base(); delete b; return rc; }
-    *h = b;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_pager_slicer_fb *b) {
+        b->alpha = alpha;
+        b->beta = (float)(1.0 - (double)alpha);          // pager_slicer_fb.cc:40
+        int rc = b->init_device(device);
+        if (!rc) rc = b->d_avg.reserve(sizeof(float));
+        if (!rc) rc = zero_device(b->d_avg.p, sizeof(float));
+        return rc;
+    });
 }
 
 void grhip_pager_slicer_fb_destroy(grhip_pager_slicer_fb *h)
 {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    h->d_avg.release();
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_pager_slicer_fb_work_device(grhip_pager_slicer_fb *h, int noutput_items, const float *d_in,
@@ -309,20 +290,15 @@ int grhip_unpack_k_bits_bb_create(grhip_unpack_k_bits_bb **h, unsigned k, int de
     *h = nullptr;
     if (k == 0) return fail(GRHIP_ERANGE, "interpolation must be > 0");          // .cc:45-46
     if (k > 32) return fail(GRHIP_EINVAL, "k > 32: the reference shifts an unsigned int");
-    auto *b = new (std::nothrow) grhip_unpack_k_bits_bb();
-    if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    b->k = k;
-    int rc = b->init_device(device);
-    if (rc) { b->destroy_base(); delete b; return rc; }
-    *h = b;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_unpack_k_bits_bb *b) {
+        b->k = k;
+        return b->init_device(device);
+    });
 }
 
 void grhip_unpack_k_bits_bb_destroy(grhip_unpack_k_bits_bb *h)
 {
-    if (!h) return;
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_unpack_k_bits_bb_work_device(grhip_unpack_k_bits_bb *h, int noutput_items, const unsigned char *d_in,
@@ -357,20 +333,15 @@ int grhip_stream_adapter_create(grhip_stream_adapter **h, int split, size_t item
     if (!h) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
     if (item_size == 0 || nstreams == 0 || nstreams > 65536) return fail(GRHIP_EINVAL, "bad item_size / nstreams");
-    auto *b = new (std::nothrow) grhip_stream_adapter();
-    if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    b->split = split != 0; b->item_size = item_size; b->nstreams = nstreams;
-    int rc = b->init_device(device);
-    if (rc) { b->destroy_base(); delete b; return rc; }
-    *h = b;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_stream_adapter *b) {
+        b->split = split != 0; b->item_size = item_size; b->nstreams = nstreams;
+        return b->init_device(device);
+    });
 }
 
 void grhip_stream_adapter_destroy(grhip_stream_adapter *h)
 {
-    if (!h) return;
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_stream_adapter_work_device(grhip_stream_adapter *h, int n, void *d_single, void *d_streams,
@@ -427,24 +398,18 @@ int grhip_correlate_access_code_bb_create(grhip_correlate_access_code_bb **h, co
     int rc = corr_set_code(p, fb, access_code, len);
     if (rc) return rc;
     p.threshold = (unsigned)threshold;
-    auto *c = new (std::nothrow) grhip_correlate_access_code_bb();
-    if (!c) return fail(GRHIP_ENOMEM, "alloc");
-    c->p = p; c->flag_bit = fb;
-    rc = c->init_device(device);
-    if (!rc) rc = c->d_state.reserve(sizeof(CorrState));
-    if (!rc) rc = zero_device(c->d_state.p, sizeof(CorrState));
-    if (rc) { c->d_state.release(); c->destroy_base(); delete c; return rc; }
-    *h = c;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_correlate_access_code_bb *c) {
+        c->p = p; c->flag_bit = fb;
+        int rc = c->init_device(device);
+        if (!rc) rc = c->d_state.reserve(sizeof(CorrState));
+        if (!rc) rc = zero_device(c->d_state.p, sizeof(CorrState));
+        return rc;
+    });
 }
 
 void grhip_correlate_access_code_bb_destroy(grhip_correlate_access_code_bb *h)
 {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    h->d_state.release();
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_correlate_access_code_bb_set_access_code(grhip_correlate_access_code_bb *h, const char *access_code,

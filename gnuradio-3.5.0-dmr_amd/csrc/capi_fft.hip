@@ -7,30 +7,19 @@
 
 using namespace grhip;
 
-struct grhip_fft_vcc : HandleBase {
+// gr_fft_vcc and gr_fft_vfc in one body.  fft_vfc reads N floats per item and is forward only, without shift
+// (general/gr_fft_vfc.cc:42-118); everything else -- the window, the plan of any fft_size > 0 (fft_any.hip), the
+// host-buffer path -- is the same.
+struct FftBlock : HandleBase {
     int N = 0, forward = 1, shift = 0;
+    bool real_in = false;          // fft_vfc
     std::vector<float> window;     // empty or N
-    DevBuf d_window;
-    FftPlan plan;              // any fft_size > 0 (fft_any.hip)
-    bool has_window = false;
-    int upload_window()
-    {
-        has_window = !window.empty();
-        if (!has_window) return GRHIP_OK;
-        int rc = d_window.reserve(window.size() * 4);
-        if (rc) return rc;
-        GRHIP_HIP(hipMemcpy(d_window.p, window.data(), window.size() * 4, hipMemcpyHostToDevice));
-        return GRHIP_OK;
-    }
-};
-
-// gr_fft_vfc: N floats in, N complex out, forward only, no shift; the window and the plan as grhip_fft_vcc
-struct grhip_fft_vfc : HandleBase {
-    int N = 0;
-    std::vector<float> window;     // empty or N
-    DevBuf d_window;
     FftPlan plan;
+    DevBuf d_window;
     bool has_window = false;
+
+    size_t in_item() const { return (size_t)N * (real_in ? 4 : 8); }
+
     int upload_window()
     {
         has_window = !window.empty();
@@ -40,7 +29,67 @@ struct grhip_fft_vfc : HandleBase {
         GRHIP_HIP(hipMemcpy(d_window.p, window.data(), window.size() * 4, hipMemcpyHostToDevice));
         return GRHIP_OK;
     }
+
+    // gr_fft_vcc.cc:55-64, gr_fft_vfc.cc:109-118: only size 0 or fft_size is accepted (1), anything else is refused (0)
+    int set_window(const float *w, size_t window_len)
+    {
+        if (!(window_len == 0 || window_len == (size_t)N)) return 0;
+        if (window_len && !w) return fail(GRHIP_EINVAL, "window is NULL");
+        std::lock_guard<std::mutex> lk(setter_mutex);
+        int rc = bind();
+        if (rc) return rc;
+        if ((rc = drain(own_stream))) return rc;        // upload_window rewrites d_window on the null stream
+        if (window_len) window.assign(w, w + window_len); else window.clear();
+        rc = upload_window();
+        return rc ? rc : 1;
+    }
+
+    int work_device(int noutput_items, const void *d_in, void *d_out, void *stream)
+    {
+        if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
+        int rc = bind();
+        if (rc) return rc;
+        const float *w = has_window ? d_window.as<float>() : nullptr;
+        rc = real_in ? plan.exec_real(w, (const float *)d_in, (float2 *)d_out, noutput_items, pick(stream))
+                     : plan.exec(shift, w, (const float2 *)d_in, (float2 *)d_out, noutput_items, pick(stream));
+        return rc ? rc : noutput_items;
+    }
+
+    int work(int noutput_items, const void *in, void *out)
+    {
+        if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
+        if (noutput_items == 0) return 0;
+        int rc = bind();
+        if (rc) return rc;
+        const size_t in_bytes = (size_t)noutput_items * in_item(), out_bytes = (size_t)noutput_items * N * 8;
+        return (int)host_call(in, in_bytes, in_bytes, out_bytes, out, (size_t)N * 8, [&](void *d_in, void *d_out, hipStream_t st) {
+            rc = work_device(noutput_items, d_in, d_out, st);
+            return rc < 0 ? rc : noutput_items;
+        });
+    }
 };
+struct grhip_fft_vcc : FftBlock {};
+struct grhip_fft_vfc : FftBlock {};
+
+// the create entries from the fft_size check on (h is not null and *h already cleared)
+template <class H>
+static int fft_create(H **h, int fft_size, int forward, const float *window, size_t window_len, int shift, bool real_in,
+                      int device)
+{
+    if (fft_size <= 0) return fail(GRHIP_ERANGE, "gri_fftw: invalid fft_size");      // gri_fft.cc:104-105
+    if (!FftPlan::size_ok(fft_size))
+        return fail(GRHIP_EINVAL, "fft_size %d: more than 2^26 points (2^25 when not a power of two)", fft_size);
+    if (window_len && !window) return fail(GRHIP_EINVAL, "window is NULL");
+    return make_handle(h, [&](H *f) {
+        f->N = fft_size; f->forward = forward ? 1 : 0; f->shift = shift ? 1 : 0; f->real_in = real_in;
+        // set_window accepts only size 0 or fft_size; the reference's ctor ignores the result (gr_fft_vfc.cc:61)
+        if (window_len == (size_t)fft_size) f->window.assign(window, window + window_len);
+        int rc = f->init_device(device);
+        if (!rc) rc = f->plan.build(fft_size, f->forward);
+        if (!rc) rc = f->upload_window();
+        return rc;
+    });
+}
 
 struct grhip_pfb_channelizer_ccf : HandleBase {
     unsigned M = 0;
@@ -79,139 +128,33 @@ int grhip_fft_vcc_create(grhip_fft_vcc **h, int fft_size, int forward, const flo
 {
     if (!h) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
-    if (fft_size <= 0) return fail(GRHIP_ERANGE, "gri_fftw: invalid fft_size");      // gri_fft.cc:104-105
-    if (!FftPlan::size_ok(fft_size))
-        return fail(GRHIP_EINVAL, "fft_size %d: more than 2^26 points (2^25 when not a power of two)", fft_size);
-    if (window_len && !window) return fail(GRHIP_EINVAL, "window is NULL");
-    auto *f = new (std::nothrow) grhip_fft_vcc();
-    if (!f) return fail(GRHIP_ENOMEM, "alloc");
-    f->N = fft_size; f->forward = forward ? 1 : 0; f->shift = shift ? 1 : 0;
-    // set_window accepts only size 0 or fft_size (gr_fft_vcc.cc:55-64); the ctor ignores the result
-    if (window_len == (size_t)fft_size) f->window.assign(window, window + window_len);
-    int rc = f->init_device(device);
-    if (!rc) rc = f->plan.build(fft_size, f->forward);
-    if (!rc) rc = f->upload_window();
-    if (rc) { f->d_window.release(); f->plan.release(); f->destroy_base(); delete f; return rc; }
-    *h = f;
-    return GRHIP_OK;
+    return fft_create(h, fft_size, forward, window, window_len, shift, false, device);
 }
 
-void grhip_fft_vcc_destroy(grhip_fft_vcc *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    h->d_window.release(); h->plan.release();
-    h->destroy_base();
-    delete h;
-}
-
-int grhip_fft_vcc_set_window(grhip_fft_vcc *h, const float *window, size_t window_len)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (!(window_len == 0 || window_len == (size_t)h->N)) return 0;     // false
-    std::lock_guard<std::mutex> lk(h->setter_mutex);
-    int rc = h->bind();
-    if (rc) return rc;
-    if (window_len) h->window.assign(window, window + window_len); else h->window.clear();
-    rc = h->upload_window();
-    return rc ? rc : 1;
-}
-
-int grhip_fft_vcc_work_device(grhip_fft_vcc *h, int noutput_items, const void *d_in, void *d_out, void *stream)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
-    int rc = h->bind();
-    if (rc) return rc;
-    rc = h->plan.exec(h->shift, h->has_window ? h->d_window.as<float>() : nullptr, (const float2 *)d_in, (float2 *)d_out,
-                      noutput_items, h->pick(stream));
-    return rc ? rc : noutput_items;
-}
-
-int grhip_fft_vcc_work(grhip_fft_vcc *h, int noutput_items, const void *in, void *out)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
-    if (noutput_items == 0) return 0;
-    int rc = h->bind();
-    if (rc) return rc;
-    size_t bytes = (size_t)noutput_items * h->N * 8;
-    return (int)h->host_call(in, bytes, bytes, bytes, out, (size_t)h->N * 8, [&](void *d_in, void *d_out, hipStream_t st) {
-        rc = grhip_fft_vcc_work_device(h, noutput_items, d_in, d_out, st);
-        return rc < 0 ? rc : noutput_items;
-    });
-}
-
-// ---- fft_vfc (general/gr_fft_vfc.cc:42-118) ---------------------------------------
 int grhip_fft_vfc_create(grhip_fft_vfc **h, int fft_size, int forward, const float *window, size_t window_len, int device)
 {
     if (!h) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
     if (!forward) return fail(GRHIP_EINVAL, "fft_vfc: forward must == true");       // gr_fft_vfc.cc:54-57
-    if (fft_size <= 0) return fail(GRHIP_ERANGE, "gri_fftw: invalid fft_size");      // gri_fft.cc:104-105
-    if (!FftPlan::size_ok(fft_size))
-        return fail(GRHIP_EINVAL, "fft_size %d: more than 2^26 points (2^25 when not a power of two)", fft_size);
-    if (window_len && !window) return fail(GRHIP_EINVAL, "window is NULL");
-    auto *f = new (std::nothrow) grhip_fft_vfc();
-    if (!f) return fail(GRHIP_ENOMEM, "alloc");
-    f->N = fft_size;
-    // set_window accepts only size 0 or fft_size (gr_fft_vfc.cc:109-118); the ctor ignores the result (:61)
-    if (window_len == (size_t)fft_size) f->window.assign(window, window + window_len);
-    int rc = f->init_device(device);
-    if (!rc) rc = f->plan.build(fft_size, 1);
-    if (!rc) rc = f->upload_window();
-    if (rc) { f->d_window.release(); f->plan.release(); f->destroy_base(); delete f; return rc; }
-    *h = f;
-    return GRHIP_OK;
+    return fft_create(h, fft_size, 1, window, window_len, 0, true, device);
 }
 
-void grhip_fft_vfc_destroy(grhip_fft_vfc *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    h->d_window.release(); h->plan.release();
-    h->destroy_base();
-    delete h;
-}
-
-int grhip_fft_vfc_set_window(grhip_fft_vfc *h, const float *window, size_t window_len)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (!(window_len == 0 || window_len == (size_t)h->N)) return 0;     // false (gr_fft_vfc.cc:112-117)
-    if (window_len && !window) return fail(GRHIP_EINVAL, "window is NULL");
-    std::lock_guard<std::mutex> lk(h->setter_mutex);
-    int rc = h->bind();
-    if (rc) return rc;
-    if ((rc = h->drain(h->own_stream))) return rc;
-    if (window_len) h->window.assign(window, window + window_len); else h->window.clear();
-    rc = h->upload_window();
-    return rc ? rc : 1;
-}
-
-int grhip_fft_vfc_work_device(grhip_fft_vfc *h, int noutput_items, const void *d_in, void *d_out, void *stream)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
-    int rc = h->bind();
-    if (rc) return rc;
-    rc = h->plan.exec_real(h->has_window ? h->d_window.as<float>() : nullptr, (const float *)d_in, (float2 *)d_out,
-                           noutput_items, h->pick(stream));
-    return rc ? rc : noutput_items;
-}
-
-int grhip_fft_vfc_work(grhip_fft_vfc *h, int noutput_items, const void *in, void *out)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
-    if (noutput_items == 0) return 0;
-    int rc = h->bind();
-    if (rc) return rc;
-    const size_t items = (size_t)noutput_items * h->N;
-    return (int)h->host_call(in, items * 4, items * 4, items * 8, out, (size_t)h->N * 8, [&](void *d_in, void *d_out, hipStream_t st) {
-        rc = grhip_fft_vfc_work_device(h, noutput_items, d_in, d_out, st);
-        return rc < 0 ? rc : noutput_items;
-    });
-}
+#define GRHIP_FFT_ENTRIES(NAME)                                                                                        \
+    void grhip_##NAME##_destroy(grhip_##NAME *h) { destroy_handle(h); }                                                \
+    int grhip_##NAME##_set_window(grhip_##NAME *h, const float *window, size_t window_len)                            \
+    {                                                                                                                  \
+        return h ? h->set_window(window, window_len) : fail(GRHIP_EINVAL, "null handle");                             \
+    }                                                                                                                  \
+    int grhip_##NAME##_work_device(grhip_##NAME *h, int noutput_items, const void *d_in, void *d_out, void *stream)   \
+    {                                                                                                                  \
+        return h ? h->work_device(noutput_items, d_in, d_out, stream) : fail(GRHIP_EINVAL, "null handle");            \
+    }                                                                                                                  \
+    int grhip_##NAME##_work(grhip_##NAME *h, int noutput_items, const void *in, void *out)                            \
+    {                                                                                                                  \
+        return h ? h->work(noutput_items, in, out) : fail(GRHIP_EINVAL, "null handle");                               \
+    }
+GRHIP_FFT_ENTRIES(fft_vcc)
+GRHIP_FFT_ENTRIES(fft_vfc)
 
 // ---- pfb_channelizer_ccf ---------------------------------------------------------
 int grhip_pfb_channelizer_ccf_create(grhip_pfb_channelizer_ccf **h, unsigned numchans, const float *taps,
@@ -226,48 +169,36 @@ int grhip_pfb_channelizer_ccf_create(grhip_pfb_channelizer_ccf **h, unsigned num
     double fltp = modf(numchans / oversample_rate, &intp);      // .cc:57-60
     if (fltp != 0.0)
         return fail(GRHIP_EINVAL, "gr_pfb_channelizer: oversample rate must be N/i for i in [1, N]");
-    auto *p = new (std::nothrow) grhip_pfb_channelizer_ccf();
-    if (!p) return fail(GRHIP_ENOMEM, "alloc");
-    p->M = numchans; p->oversample_rate = oversample_rate;
-    int rc = p->init_device(device);
-    if (!rc) rc = p->set_taps(taps, ntaps);
-    if (!rc) {
+    return make_handle(h, [&](grhip_pfb_channelizer_ccf *p) {
+        p->M = numchans; p->oversample_rate = oversample_rate;
+        int rc = p->init_device(device);
+        if (!rc) rc = p->set_taps(taps, ntaps);
+        if (rc) return rc;
         p->rate_ratio = (int)rintf(numchans / oversample_rate);                           // .cc:82
         p->idxlut.resize(numchans);
         for (unsigned i = 0; i < numchans; i++)
             p->idxlut[i] = numchans - ((i + p->rate_ratio) % numchans) - 1;                // .cc:85
         p->output_multiple = 1;
         while ((p->output_multiple * p->rate_ratio) % numchans != 0) p->output_multiple++; // .cc:90-92
-        rc = p->d_idxlut.reserve(numchans * sizeof(int));
-        if (!rc) {
-            hipError_t e = hipMemcpy(p->d_idxlut.p, p->idxlut.data(), numchans * sizeof(int), hipMemcpyHostToDevice);
-            if (e != hipSuccess) rc = fail(GRHIP_ERUNTIME, "idxlut upload");
-        }
+        if ((rc = p->d_idxlut.reserve(numchans * sizeof(int)))) return rc;
+        if (hipMemcpy(p->d_idxlut.p, p->idxlut.data(), numchans * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(GRHIP_ERUNTIME, "idxlut upload");
         std::vector<float2> dft(2 * (size_t)numchans);
         for (unsigned m = 0; m < numchans; ++m) {
             double ang = 2.0 * M_PI * (double)m / (double)numchans;     // FFTW_BACKWARD: +sign
             dft[m] = make_float2((float)cos(ang), (float)sin(ang));
             dft[numchans + m] = make_float2((float)cos(-ang), (float)sin(-ang));    // forward table (batched-FFT kernels)
         }
-        if (!rc) rc = p->d_dft.reserve(2 * (size_t)numchans * sizeof(float2));
-        if (!rc) {
-            hipError_t e = hipMemcpy(p->d_dft.p, dft.data(), 2 * (size_t)numchans * sizeof(float2), hipMemcpyHostToDevice);
-            if (e != hipSuccess) rc = fail(GRHIP_ERUNTIME, "dft upload");
-        }
-    }
-    if (rc) { p->d_ftaps.release(); p->d_idxlut.release(); p->d_dft.release(); p->destroy_base(); delete p; return rc; }
-    *h = p;
-    return GRHIP_OK;
+        if ((rc = p->d_dft.reserve(2 * (size_t)numchans * sizeof(float2)))) return rc;
+        if (hipMemcpy(p->d_dft.p, dft.data(), 2 * (size_t)numchans * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(GRHIP_ERUNTIME, "dft upload");
+        return GRHIP_OK;
+    });
 }
 
 void grhip_pfb_channelizer_ccf_destroy(grhip_pfb_channelizer_ccf *h)
 {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    h->d_ftaps.release(); h->d_idxlut.release(); h->d_dft.release();
-    h->d_hier_in.release(); h->d_hier_vec.release();
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_pfb_channelizer_ccf_set_taps(grhip_pfb_channelizer_ccf *h, const float *taps, size_t ntaps)

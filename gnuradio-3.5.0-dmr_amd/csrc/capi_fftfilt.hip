@@ -1,9 +1,16 @@
-// capi_fftfilt.hip -- C ABI for gr_fft_filter_ccc.
-// filter/gr_fft_filter_ccc.cc:46-128, filter/gri_fft_filter_ccc_generic.cc:63-170:
+// capi_fftfilt.hip -- C ABI for gr_fft_filter_ccc and gr_fft_filter_fff.
+// filter/gr_fft_filter_ccc.cc:46-128, filter/gri_fft_filter_ccc_generic.cc:63-170,
+// filter/gr_fft_filter_fff.cc:44-97, filter/gri_fft_filter_fff_generic.cc:34-158:
 // overlap-ADD fast convolution with the reference's sizes, taps pre-scaled by 1/fftsize,
 // tail carried between blocks and calls.  All blocks of a call are transformed in one
 // batched launch of the FFT kernels (fft_kernels.hip); the overlap-add + decimation is a
-// gather over the inverse transforms.
+// gather over the inverse transforms.  Up to OLS_MAX_TAPS taps the fused overlap-save kernel on
+// 4096-point blocks runs instead (fftfilt4096_kernel, fftfilt4096_pair_kernel).
+//
+// The reference's fff runs a real-to-complex transform per block; here TWO consecutive real blocks
+// share one complex transform (block 2p in the real plane, block 2p+1 in the imaginary one): the
+// transformed taps of a real filter are Hermitian, so z = x_a + j x_b comes out as y_a + j y_b with
+// nothing to untangle.  One handle template serves both; the traits below are all that differs.
 #include <cmath>
 #include <complex>
 #include <vector>
@@ -13,158 +20,193 @@
 
 using namespace grhip;
 
-struct grhip_fft_filter_ccc : HandleBase {
+struct FftFiltCcc {
+    using item = float2;
+    using tap = std::complex<float>;
+    static constexpr const char *name = "fft_filter_ccc";
+    static std::complex<float> cplx(tap t) { return t; }
+    static constexpr int blocks_per_xform = 1;
+    // a fused ccc handle still builds the overlap-add plan and spectrum it never runs
+    static constexpr bool fused_needs_ola = true;
+    static constexpr auto fused = launch_fftfilt4096;
+    static constexpr auto pack = launch_fftfilt_pack;
+    static constexpr auto ola = launch_fftfilt_ola;
+    static constexpr auto tail = launch_fftfilt_tail;
+};
+
+struct FftFiltFff {
+    using item = float;
+    using tap = float;
+    static constexpr const char *name = "fft_filter_fff";
+    static std::complex<float> cplx(tap t) { return {t, 0.f}; }      // imaginary parts zero: H Hermitian
+    static constexpr int blocks_per_xform = 2;
+    // a fused fff handle has no overlap-add plan and no spectrum
+    static constexpr bool fused_needs_ola = false;
+    static constexpr auto fused = launch_fftfilt4096_pair;
+    static constexpr auto pack = launch_fftfilt_pack_real;
+    static constexpr auto ola = launch_fftfilt_ola_real;
+    static constexpr auto tail = launch_fftfilt_tail_real;
+};
+
+template <class T>
+struct FftFilter : HandleBase {
+    using item = typename T::item;
+    using tap = typename T::tap;
     int decim = 1, ntaps = 0, fftsize = 0, nsamples = 0;
-    std::vector<std::complex<float>> new_taps;
+    std::vector<tap> new_taps;
     bool updated = false;
     DevBuf d_xformed, d_tail, d_a, d_b;
     FftPlan plan;              // the fftsize-point transform, both directions (four-step form above 8192 points)
-    // fused overlap-save path (ntaps <= FUSED_MAX_TAPS): 4096-point blocks, see fftfilt4096_kernel
+    // fused overlap-save path (ntaps <= OLS_MAX_TAPS): 4096-point blocks
     bool fused = false;
     int L = 0, fold = 0;             // full-rate outputs per block (a multiple of the decimation); folded inverse
     DevBuf d_tw4096, d_H4096, d_hist[2];
     int hist_cur = 0;
 
-    int install(const std::complex<float> *taps, size_t n)
+    int install(const tap *taps, size_t n)
     {
-        // compute_sizes + set_taps (gri_fft_filter_ccc_generic.cc:63-118)
+        // compute_sizes + set_taps (gri_fft_filter_ccc_generic.cc:63-118, gri_fft_filter_fff_generic.cc:51-105)
         ntaps = (int)n;
         fftsize = (int)(2 * pow(2.0, ceil(log((double)ntaps) / log(2.0))));
         nsamples = fftsize - ntaps + 1;
         if (ntaps > (1 << 25) || !FftPlan::size_ok(fftsize))
-            return fail(GRHIP_EINVAL, "fft_filter_ccc: %d taps need an FFT of more than 2^26 points", ntaps);
-        int rcp = plan.build(fftsize, 1);
-        if (rcp) return rcp;
+            return fail(GRHIP_EINVAL, "%s: %d taps need an FFT of more than 2^26 points", T::name, ntaps);
+        fused = ntaps <= OLS_MAX_TAPS && ((OLS_N - (ntaps - 1)) / decim) >= 1;
+        const bool ola = !fused || T::fused_needs_ola;
+        int rc;
+        if (ola && (rc = plan.build(fftsize, 1))) return rc;
+        std::vector<std::complex<float>> tc((size_t)ntaps);
+        for (int i = 0; i < ntaps; ++i) tc[(size_t)i] = T::cplx(taps[i]);
+        const size_t hl = (size_t)(ntaps > 1 ? ntaps - 1 : 1);                          // history / tail items
+        if (fused) {
+            rc = ols_build((const float *)tc.data(), ntaps, decim, d_tw4096, d_H4096, &L, &fold);
+            if (!rc) rc = d_hist[0].reserve(hl * sizeof(item));
+            if (!rc) rc = d_hist[1].reserve(hl * sizeof(item));
+            if (rc) return rc;
+            if ((rc = zero_device(d_hist[0].p, hl * sizeof(item)))) return rc;          // a fresh filter starts from silence
+            if ((rc = zero_device(d_hist[1].p, hl * sizeof(item)))) return rc;
+            hist_cur = 0;
+        }
+        if (!ola) return GRHIP_OK;
         // forward transform of the scaled, zero-padded taps (double, rounded once)
-        const float scale = 1.0 / fftsize;                                              // :76
+        const float scale = 1.0 / fftsize;                                              // ccc :76, fff :63
         std::vector<std::complex<double>> t((size_t)fftsize, std::complex<double>(0, 0));
         for (int i = 0; i < ntaps; ++i)
-            t[i] = std::complex<double>((double)(taps[i].real() * scale), (double)(taps[i].imag() * scale));
+            t[i] = std::complex<double>((double)(tc[i].real() * scale), (double)(tc[i].imag() * scale));
         host_fft_pow2(t, -1);
         std::vector<float2> H((size_t)fftsize);
         for (int k = 0; k < fftsize; ++k) H[k] = make_float2((float)t[k].real(), (float)t[k].imag());
-        fused = ntaps <= OLS_MAX_TAPS && ((OLS_N - (ntaps - 1)) / decim) >= 1;
-        if (fused) {
-            int rc4 = ols_build((const float *)taps, ntaps, decim, d_tw4096, d_H4096, &L, &fold);
-            const size_t hl = (size_t)(ntaps > 1 ? ntaps - 1 : 1);
-            if (!rc4) rc4 = d_hist[0].reserve(hl * sizeof(float2));
-            if (!rc4) rc4 = d_hist[1].reserve(hl * sizeof(float2));
-            if (rc4) return rc4;
-            if ((rc4 = zero_device(d_hist[0].p, hl * sizeof(float2)))) return rc4;   // a fresh filter starts from silence
-            if ((rc4 = zero_device(d_hist[1].p, hl * sizeof(float2)))) return rc4;
-            hist_cur = 0;
-        }
-        const size_t tail_items = (size_t)(ntaps > 1 ? ntaps - 1 : 1);
-        int rc = d_xformed.reserve(H.size() * sizeof(float2));
-        if (!rc) rc = d_tail.reserve(tail_items * sizeof(float2));
+        rc = d_xformed.reserve(H.size() * sizeof(float2));
+        if (!rc) rc = d_tail.reserve(hl * sizeof(item));
         if (rc) return rc;
         GRHIP_HIP(hipMemcpy(d_xformed.p, H.data(), H.size() * sizeof(float2), hipMemcpyHostToDevice));
-        if ((rc = zero_device(d_tail.p, tail_items * sizeof(float2)))) return rc;       // tail cleared (:69-71)
+        return zero_device(d_tail.p, hl * sizeof(item));                                // tail cleared (ccc :69-71, fff :56-58)
+    }
+
+    int set_taps(const tap *taps, size_t n)
+    {
+        new_taps.assign(taps, taps + n);
+        updated = true;                                  // gr_fft_filter_ccc.cc:88-93, gr_fft_filter_fff.cc:69-73
         return GRHIP_OK;
     }
-    void release_all()
+
+    int work_device(int noutput_items, const void *d_in, void *d_out, void *stream)
     {
-        plan.release(); d_xformed.release(); d_tail.release(); d_a.release(); d_b.release();
-        d_tw4096.release(); d_H4096.release(); d_hist[0].release(); d_hist[1].release();
+        if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
+        int rc = bind();
+        if (rc) return rc;
+        hipStream_t st = pick(stream);
+        if (updated) {                                   // ccc .cc:113-118, fff .cc:83-88: new sizes, produce nothing this call
+            if ((rc = drain(st))) return rc;
+            rc = install(new_taps.data(), new_taps.size());
+            if (rc) return rc;
+            updated = false;
+            return 0;
+        }
+        if (noutput_items == 0) return 0;
+        if (noutput_items % nsamples)
+            return fail(GRHIP_EINVAL, "noutput_items must be a multiple of nsamples (%d)", nsamples);
+        const long long nin = (long long)noutput_items * decim;
+        if (fused) {
+            if ((rc = T::fused((const item *)d_in, nin, d_hist[hist_cur].as<item>(), ntaps, d_tw4096.as<float2>(),
+                               d_H4096.as<float2>(), (item *)d_out, noutput_items, decim, L, fold, st,
+                               d_hist[hist_cur ^ 1].as<item>())))
+                return rc;
+            hist_cur ^= 1;
+            return noutput_items;
+        }
+        // nblk blocks of the stream, T::blocks_per_xform of them per complex transform
+        const long long nblk = nin / nsamples, ncb = (nblk + T::blocks_per_xform - 1) / T::blocks_per_xform;
+        const size_t bytes = (size_t)ncb * fftsize * sizeof(float2);
+        if ((rc = d_a.reserve(bytes))) return rc;
+        if ((rc = d_b.reserve(bytes))) return rc;
+        float2 *A = d_a.as<float2>(), *B = d_b.as<float2>();
+        const int tailsize = ntaps - 1;
+        if ((rc = T::pack((const item *)d_in, A, nsamples, fftsize, nblk, st))) return rc;
+        if ((rc = plan.exec_pow2(1, 0, nullptr, A, B, ncb, st))) return rc;
+        if ((rc = launch_fftfilt_mul(B, d_xformed.as<float2>(), fftsize, ncb, st))) return rc;
+        if ((rc = plan.exec_pow2(0, 0, nullptr, B, A, ncb, st))) return rc;
+        if ((rc = T::ola(A, d_tail.as<item>(), (item *)d_out, noutput_items, decim, nsamples, fftsize, tailsize, st)))
+            return rc;
+        if ((rc = T::tail(A, d_tail.as<item>(), nblk, nsamples, fftsize, tailsize, st))) return rc;
+        return noutput_items;
+    }
+
+    int work(int noutput_items, const void *in, void *out)
+    {
+        if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
+        int rc = bind();
+        if (rc) return rc;
+        if (updated || noutput_items == 0) return work_device(noutput_items, nullptr, nullptr, own_stream);
+        const size_t nin = (size_t)noutput_items * decim, sz = sizeof(item);
+        return (int)host_call(in, nin * sz, nin * sz, (size_t)noutput_items * sz, out, sz, [&](void *d_in, void *d_out, hipStream_t st) {
+            return work_device(noutput_items, d_in, d_out, st);
+        });
     }
 };
+struct grhip_fft_filter_ccc : FftFilter<FftFiltCcc> {};
+struct grhip_fft_filter_fff : FftFilter<FftFiltFff> {};
 
-extern "C" {
-
-int grhip_fft_filter_ccc_create(grhip_fft_filter_ccc **h, int decimation, const float *taps, size_t ntaps, int device)
+template <class H>
+static int fftfilt_create(H **h, const char *name, int decimation, const float *taps, size_t ntaps, int device)
 {
     if (!h) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
     if (decimation < 1) return fail(GRHIP_EINVAL, "decimation must be >= 1");
-    if (!taps || ntaps < 1) return fail(GRHIP_EINVAL, "fft_filter_ccc needs at least one tap");
-    auto *f = new (std::nothrow) grhip_fft_filter_ccc();
-    if (!f) return fail(GRHIP_ENOMEM, "alloc");
-    f->decim = decimation;
-    int rc = f->init_device(device);
-    if (!rc) rc = f->install((const std::complex<float> *)taps, ntaps);
-    if (rc) { f->release_all(); f->destroy_base(); delete f; return rc; }
-    *h = f;
-    return GRHIP_OK;
-}
-
-void grhip_fft_filter_ccc_destroy(grhip_fft_filter_ccc *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    h->release_all();
-    h->destroy_base();
-    delete h;
-}
-
-int grhip_fft_filter_ccc_set_taps(grhip_fft_filter_ccc *h, const float *taps, size_t ntaps)
-{
-    if (!h || !taps || ntaps < 1) return fail(GRHIP_EINVAL, "bad argument");
-    h->new_taps.assign((const std::complex<float> *)taps, (const std::complex<float> *)taps + ntaps);
-    h->updated = true;                                   // gr_fft_filter_ccc.cc:88-93
-    return GRHIP_OK;
-}
-
-int grhip_fft_filter_ccc_nsamples(const grhip_fft_filter_ccc *h) { return h ? h->nsamples : GRHIP_EINVAL; }
-int grhip_fft_filter_ccc_decimation(const grhip_fft_filter_ccc *h) { return h ? h->decim : GRHIP_EINVAL; }
-
-int grhip_fft_filter_ccc_work_device(grhip_fft_filter_ccc *h, int noutput_items, const void *d_in, void *d_out,
-                                     void *stream)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
-    int rc = h->bind();
-    if (rc) return rc;
-    hipStream_t st = h->pick(stream);
-    if (h->updated) {                                    // .cc:113-118: new sizes, produce nothing this call
-        GRHIP_HIP(hipStreamSynchronize(st));
-        rc = h->install(h->new_taps.data(), h->new_taps.size());
-        if (rc) return rc;
-        h->updated = false;
-        return 0;
-    }
-    if (noutput_items == 0) return 0;
-    if (noutput_items % h->nsamples)
-        return fail(GRHIP_EINVAL, "noutput_items must be a multiple of nsamples (%d)", h->nsamples);
-    const long long nin = (long long)noutput_items * h->decim;
-    if (h->fused) {
-        const float2 *hist = h->d_hist[h->hist_cur].as<float2>();
-        float2 *hist_new = h->d_hist[h->hist_cur ^ 1].as<float2>();
-        if ((rc = launch_fftfilt4096((const float2 *)d_in, nin, hist, h->ntaps, h->d_tw4096.as<float2>(),
-                                     h->d_H4096.as<float2>(), (float2 *)d_out, noutput_items, h->decim, h->L, h->fold, st,
-                                     hist_new)))
-            return rc;
-        h->hist_cur ^= 1;
-        return noutput_items;
-    }
-    const long long nblk = nin / h->nsamples;
-    const size_t bytes = (size_t)nblk * h->fftsize * sizeof(float2);
-    if ((rc = h->d_a.reserve(bytes))) return rc;
-    if ((rc = h->d_b.reserve(bytes))) return rc;
-    float2 *A = h->d_a.as<float2>(), *B = h->d_b.as<float2>();
-    const int tailsize = h->ntaps - 1;
-    if ((rc = launch_fftfilt_pack((const float2 *)d_in, A, h->nsamples, h->fftsize, nblk, st))) return rc;
-    if ((rc = h->plan.exec_pow2(1, 0, nullptr, A, B, nblk, st))) return rc;
-    if ((rc = launch_fftfilt_mul(B, h->d_xformed.as<float2>(), h->fftsize, nblk, st))) return rc;
-    if ((rc = h->plan.exec_pow2(0, 0, nullptr, B, A, nblk, st))) return rc;
-    if ((rc = launch_fftfilt_ola(A, h->d_tail.as<float2>(), (float2 *)d_out, noutput_items, h->decim, h->nsamples,
-                                 h->fftsize, tailsize, st)))
+    if (!taps || ntaps < 1) return fail(GRHIP_EINVAL, "%s needs at least one tap", name);
+    return make_handle(h, [&](H *f) {
+        f->decim = decimation;
+        int rc = f->init_device(device);
+        if (!rc) rc = f->install((const typename H::tap *)taps, ntaps);
         return rc;
-    if ((rc = launch_fftfilt_tail(A, h->d_tail.as<float2>(), nblk, h->nsamples, h->fftsize, tailsize, st))) return rc;
-    return noutput_items;
-}
-
-int grhip_fft_filter_ccc_work(grhip_fft_filter_ccc *h, int noutput_items, const void *in, void *out)
-{
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
-    int rc = h->bind();
-    if (rc) return rc;
-    if (h->updated || noutput_items == 0)
-        return grhip_fft_filter_ccc_work_device(h, noutput_items, nullptr, nullptr, h->own_stream);
-    const size_t nin = (size_t)noutput_items * h->decim;
-    return (int)h->host_call(in, nin * 8, nin * 8, (size_t)noutput_items * 8, out, 8, [&](void *d_in, void *d_out, hipStream_t st) {
-        return grhip_fft_filter_ccc_work_device(h, noutput_items, d_in, d_out, st);
     });
 }
+
+extern "C" {
+
+// `taps` holds ntaps taps of the block's tap type (ccc: interleaved complex floats)
+#define GRHIP_FFTFILT_ENTRIES(NAME)                                                                                    \
+    int grhip_##NAME##_create(grhip_##NAME **h, int decimation, const float *taps, size_t ntaps, int device)          \
+    {                                                                                                                  \
+        return fftfilt_create(h, #NAME, decimation, taps, ntaps, device);                                             \
+    }                                                                                                                  \
+    void grhip_##NAME##_destroy(grhip_##NAME *h) { destroy_handle(h); }                                                \
+    int grhip_##NAME##_set_taps(grhip_##NAME *h, const float *taps, size_t ntaps)                                     \
+    {                                                                                                                  \
+        if (!h || !taps || ntaps < 1) return fail(GRHIP_EINVAL, "bad argument");                                      \
+        return h->set_taps((const grhip_##NAME::tap *)taps, ntaps);                                                   \
+    }                                                                                                                  \
+    int grhip_##NAME##_nsamples(const grhip_##NAME *h) { return h ? h->nsamples : GRHIP_EINVAL; }                      \
+    int grhip_##NAME##_decimation(const grhip_##NAME *h) { return h ? h->decim : GRHIP_EINVAL; }                       \
+    int grhip_##NAME##_work_device(grhip_##NAME *h, int noutput_items, const void *d_in, void *d_out, void *stream)   \
+    {                                                                                                                  \
+        return h ? h->work_device(noutput_items, d_in, d_out, stream) : fail(GRHIP_EINVAL, "null handle");            \
+    }                                                                                                                  \
+    int grhip_##NAME##_work(grhip_##NAME *h, int noutput_items, const void *in, void *out)                            \
+    {                                                                                                                  \
+        return h ? h->work(noutput_items, in, out) : fail(GRHIP_EINVAL, "null handle");                               \
+    }
+GRHIP_FFTFILT_ENTRIES(fft_filter_ccc)
+GRHIP_FFTFILT_ENTRIES(fft_filter_fff)
 
 }  // extern "C"

@@ -318,8 +318,7 @@ int XlatingCore::ensure_rot(long long n, const float2 **gtab, hipStream_t st)
             int rc = nb.reserve(new_items * sizeof(cf) * 2);
             if (rc) return rc;
             if (tab_len) GRHIP_HIP(hipMemcpy(nb.p, d_rot.p, (size_t)tab_len * sizeof(cf), hipMemcpyDeviceToDevice));
-            d_rot.release();
-            d_rot = nb;
+            d_rot.swap(nb);         // nb frees the old table on leaving this scope
         }
         GRHIP_HIP(hipMemcpy(d_rot.as<cf>() + tab_len, fresh.data(), (size_t)need * sizeof(cf),
                             hipMemcpyHostToDevice));
@@ -340,15 +339,6 @@ int XlatingCore::phase_before_pos(std::complex<float> *g)
     GRHIP_HIP(hipMemcpy(&ph, gtab, sizeof(ph), hipMemcpyDeviceToHost));
     *g = ph * std::conj(incr);
     return GRHIP_OK;
-}
-
-void XlatingCore::release()
-{
-    d_taps_generic.release(); d_hp.release(); d_wtab.release(); d_stab.release(); d_vtab.release(); d_rot.release();
-    for (int i = 0; i < 2; ++i) { d_mf_A[i].release(); d_mf_wlane[i].release(); }
-    d_mf_stab.release(); d_mf_vtab.release(); mf_sched.release();
-    scratch_y.release(); sched.release(); d_ols_tw.release(); d_ols_H.release(); d_hidec_taps.release();
-    d_hidec_etab.release(); d_hidec_vtab.release(); d_ri_hp.release();
 }
 
 // run the FIR + rotator (+ demod) for n_out outputs on device pointers.
@@ -551,13 +541,6 @@ struct grhip_fir_filter : HandleBase {
     size_t in_item() const { return kind == FIR_SCC ? 2 : (kind == FIR_FFF || kind == FIR_FSF || kind == FIR_FCC) ? 4 : 8; }
     size_t out_item() const { return kind == FIR_FFF ? 4 : kind == FIR_FSF ? 2 : 8; }
 
-    void release()
-    {
-        d_taps_rev.release(); d_hp.release(); sched.release(); d_ols_tw.release(); d_ols_H.release(); d_hidec_taps.release();
-        d_mf_A[0].release(); d_mf_A[1].release(); mf_sched.release(); d_scratch.release();
-        destroy_base();
-    }
-
     int install(const std::vector<float> &t)
     {
         taps = t;
@@ -708,22 +691,17 @@ int grhip_fir_filter_create(grhip_fir_filter **h, const char *kind, int decimati
     else return fail(GRHIP_EINVAL, "unknown FIR kind '%s'", kind);
     if (decimation < 1) return fail(GRHIP_EINVAL, "decimation must be >= 1");
     if (ntaps && !taps) return fail(GRHIP_EINVAL, "taps is NULL");
-    grhip_fir_filter *f = new (std::nothrow) grhip_fir_filter();
-    if (!f) return fail(GRHIP_ENOMEM, "alloc");
-    f->kind = k; f->ekind = k == FIR_FSF ? FIR_FFF : k; f->decim = decimation; f->mode = default_mode();
-    int rc = f->init_device(device);
-    if (!rc) rc = f->install(std::vector<float>(taps, taps + ntaps * f->tw()));
-    if (rc) { f->release(); delete f; return rc; }
-    *h = f;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_fir_filter *f) {
+        f->kind = k; f->ekind = k == FIR_FSF ? FIR_FFF : k; f->decim = decimation; f->mode = default_mode();
+        int rc = f->init_device(device);
+        if (!rc) rc = f->install(std::vector<float>(taps, taps + ntaps * f->tw()));
+        return rc;
+    });
 }
 
 void grhip_fir_filter_destroy(grhip_fir_filter *h)
 {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    h->release();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_fir_filter_set_taps(grhip_fir_filter *h, const float *taps, size_t ntaps)
@@ -834,6 +812,7 @@ struct grhip_fir_filter_with_buffer : HandleBase {
     grhip_fir_filter *inner = nullptr;  // engines of the FIR family at the decimation last used
     unsigned inner_dec = 0;
     DevBuf d_hist, d_both;
+    ~grhip_fir_filter_with_buffer() { grhip_fir_filter_destroy(inner); }     // before the delay line
     size_t item() const { return kind == FIR_FFF ? 4 : 8; }
     int tw() const { return kind == FIR_CCC ? 2 : 1; }
     const char *kind_name() const { return kind == FIR_FFF ? "fff" : kind == FIR_CCF ? "ccf" : "ccc"; }
@@ -870,29 +849,20 @@ int grhip_fir_filter_with_buffer_create(grhip_fir_filter_with_buffer **h, const 
     else if (!strcmp(kind, "ccc")) k = FIR_CCC;
     else return fail(GRHIP_EINVAL, "unknown FIR kind '%s'", kind);
     if (ntaps && !taps) return fail(GRHIP_EINVAL, "taps is NULL");
-    auto *f = new (std::nothrow) grhip_fir_filter_with_buffer();
-    if (!f) return fail(GRHIP_ENOMEM, "alloc");
-    f->kind = k; f->mode = default_mode();
-    int rc = f->init_device(device);
-    if (!rc) {
+    return make_handle(h, [&](grhip_fir_filter_with_buffer *f) {
+        f->kind = k; f->mode = default_mode();
+        int rc = f->init_device(device);
+        if (rc) return rc;
         f->taps.assign(taps, taps + ntaps * f->tw());
         f->ntaps = (int)ntaps;
-        rc = f->reset_line();
-    }
-    if (!rc) rc = f->ensure_inner(1);
-    if (rc) { grhip_fir_filter_with_buffer_destroy(f); return rc; }
-    *h = f;
-    return GRHIP_OK;
+        if ((rc = f->reset_line())) return rc;
+        return f->ensure_inner(1);
+    });
 }
 
 void grhip_fir_filter_with_buffer_destroy(grhip_fir_filter_with_buffer *h)
 {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->inner) grhip_fir_filter_destroy(h->inner);
-    h->d_hist.release(); h->d_both.release();
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 // set_taps (.cc.t:44-59): new taps, delay line zeroed, takes effect at once (this is a kernel-level object,
@@ -1010,21 +980,17 @@ int grhip_quadrature_demod_cf_create(grhip_quadrature_demod_cf **h, float gain, 
 {
     if (!h) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
-    auto *q = new (std::nothrow) grhip_quadrature_demod_cf();
-    if (!q) return fail(GRHIP_ENOMEM, "alloc");
-    q->gain = gain;
-    int rc = q->init_device(device);
-    if (!rc) rc = get_device_tables(device, &q->tabs);
-    if (rc) { q->destroy_base(); delete q; return rc; }
-    *h = q;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_quadrature_demod_cf *q) {
+        q->gain = gain;
+        int rc = q->init_device(device);
+        if (!rc) rc = get_device_tables(device, &q->tabs);
+        return rc;
+    });
 }
 
 void grhip_quadrature_demod_cf_destroy(grhip_quadrature_demod_cf *h)
 {
-    if (!h) return;
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_quadrature_demod_cf_work_device(grhip_quadrature_demod_cf *h, int noutput_items, const void *d_in,
@@ -1061,33 +1027,25 @@ int grhip_xlating_demod_create(grhip_xlating_demod **h, int decimation, const fl
     *h = nullptr;
     int rc = xlating_args_ok(decimation, taps, ntaps, sampling_freq);
     if (rc) return rc;
-    auto *x = new (std::nothrow) grhip_xlating_demod();
-    if (!x) return fail(GRHIP_ENOMEM, "alloc");
-    x->mode = default_mode();
-    x->gain = gain;
-    rc = x->init_device(device);
-    if (!rc) rc = get_device_tables(device, &x->tabs);
-    if (!rc) {
+    return make_handle(h, [&](grhip_xlating_demod *x) {
+        x->mode = default_mode();
+        x->gain = gain;
+        int rc = x->init_device(device);
+        if (!rc) rc = get_device_tables(device, &x->tabs);
+        if (rc) return rc;
         x->core.decim = decimation;
         x->core.for_demod = true;
         x->core.proto.assign((const cf *)taps, (const cf *)taps + ntaps);
         x->core.center_freq = center_freq; x->core.sampling_freq = sampling_freq;
-        rc = x->core.build(device);
-    }
-    if (!rc) rc = x->ystate.reserve(4 * sizeof(float2));
-    if (!rc) rc = zero_device(x->ystate.p, 4 * sizeof(float2));
-    if (rc) { x->core.release(); x->ystate.release(); x->destroy_base(); delete x; return rc; }
-    *h = x;
-    return GRHIP_OK;
+        if ((rc = x->core.build(device))) return rc;
+        if ((rc = x->ystate.reserve(4 * sizeof(float2)))) return rc;
+        return zero_device(x->ystate.p, 4 * sizeof(float2));
+    });
 }
 
 void grhip_xlating_demod_destroy(grhip_xlating_demod *h)
 {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    h->core.release(); h->ystate.release();
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_xlating_demod_set_mode(grhip_xlating_demod *h, int mode)
@@ -1230,33 +1188,19 @@ static int xlating_create(H **h, const char *kind, int decimation, const float *
     else return fail(GRHIP_EINVAL, "unknown freq_xlating kind '%s'", kind);
     int rc = xlating_args_ok(decimation, taps, ntaps, sampling_freq);
     if (rc) return rc;
-    auto *x = new (std::nothrow) H();
-    if (!x) return fail(GRHIP_ENOMEM, "alloc");
-    x->mode = default_mode();
-    x->ctaps_in = ctaps_in;
-    x->in_item = in_kind == 0 ? 8 : in_kind == 1 ? 4 : 2;
-    rc = x->init_device(device);
-    if (!rc) {
+    return make_handle(h, [&](H *x) {
+        x->mode = default_mode();
+        x->ctaps_in = ctaps_in;
+        x->in_item = in_kind == 0 ? 8 : in_kind == 1 ? 4 : 2;
+        int rc = x->init_device(device);
+        if (rc) return rc;
         x->core.decim = decimation;
         x->core.in_kind = in_kind;
         x->core.real_tap_type = !ctaps_in;
         x->set_proto(x->core.proto, taps, ntaps);
         x->core.center_freq = center_freq; x->core.sampling_freq = sampling_freq;
-        rc = x->core.build(device);
-    }
-    if (rc) { x->core.release(); x->destroy_base(); delete x; return rc; }
-    *h = x;
-    return GRHIP_OK;
-}
-
-template <class H>
-static void xlating_destroy(H *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    h->core.release();
-    h->destroy_base();
-    delete h;
+        return x->core.build(device);
+    });
 }
 
 extern "C" {
@@ -1268,7 +1212,7 @@ int grhip_freq_xlating_fir_filter_create(grhip_freq_xlating_fir_filter **h, cons
     return xlating_create(h, kind, decimation, taps, ntaps, center_freq, sampling_freq, device);
 }
 
-void grhip_freq_xlating_fir_filter_destroy(grhip_freq_xlating_fir_filter *h) { xlating_destroy(h); }
+void grhip_freq_xlating_fir_filter_destroy(grhip_freq_xlating_fir_filter *h) { destroy_handle(h); }
 
 int grhip_freq_xlating_fir_filter_set_center_freq(grhip_freq_xlating_fir_filter *h, double center_freq)
 {
@@ -1373,7 +1317,7 @@ int grhip_freq_xlating_fir_filter_ccc_create(grhip_freq_xlating_fir_filter_ccc *
     return xlating_create(h, "ccc", decimation, taps, ntaps, center_freq, sampling_freq, device);
 }
 
-void grhip_freq_xlating_fir_filter_ccc_destroy(grhip_freq_xlating_fir_filter_ccc *h) { xlating_destroy(h); }
+void grhip_freq_xlating_fir_filter_ccc_destroy(grhip_freq_xlating_fir_filter_ccc *h) { destroy_handle(h); }
 
 int grhip_freq_xlating_fir_filter_ccc_set_center_freq(grhip_freq_xlating_fir_filter_ccc *h, double center_freq)
 {

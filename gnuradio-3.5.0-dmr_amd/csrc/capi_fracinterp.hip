@@ -153,13 +153,6 @@ struct grhip_fractional_interpolator_base : SchedBlock<grhip_fractional_interpol
         if (!(c < 2147483648.0)) return fail(GRHIP_EINVAL, "fractional_interpolator: forecast does not fit an int");
         return (int)c;
     }
-
-    void destroy()
-    {
-        (void)bind();
-        walked.release();
-        destroy_base();
-    }
 };
 
 struct grhip_fractional_interpolator_ff : grhip_fractional_interpolator_base {};

@@ -570,8 +570,7 @@ struct grhip_framer_sink_1 : HandleBase {
         if (rc) return rc;
         if (b.p && keep_bytes) GRHIP_HIP(hipMemcpyAsync(nb.p, b.p, std::min(keep_bytes, b.cap), hipMemcpyDeviceToDevice, st));
         GRHIP_HIP(hipStreamSynchronize(st));
-        b.release();
-        b = nb;
+        b.swap(nb);                 // nb frees the old buffer on return
         return GRHIP_OK;
     }
 };
@@ -580,23 +579,17 @@ int grhip_framer_sink_1_create(grhip_framer_sink_1 **h, int device)
 {
     if (!h) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
-    auto *b = new (std::nothrow) grhip_framer_sink_1();
-    if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    int rc = b->init_device(device);
-    if (!rc) rc = b->d_state.reserve(sizeof(FramerState));
-    if (!rc) rc = zero_device(b->d_state.p, sizeof(FramerState));   // enter_search(), .cc:84
-    if (rc) { grhip_framer_sink_1_destroy(b); return rc; }
-    *h = b;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_framer_sink_1 *b) {
+        int rc = b->init_device(device);
+        if (!rc) rc = b->d_state.reserve(sizeof(FramerState));
+        if (!rc) rc = zero_device(b->d_state.p, sizeof(FramerState));   // enter_search(), .cc:84
+        return rc;
+    });
 }
 
 void grhip_framer_sink_1_destroy(grhip_framer_sink_1 *h)
 {
-    if (!h) return;
-    (void)h->bind();
-    h->d_state.release(); h->d_F.release(); h->d_D.release(); h->d_jobs.release(); h->d_msgs.release(); h->d_pool.release(); h->d_recs.release(); h->d_segs.release();
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_framer_sink_1_set_segment_items(grhip_framer_sink_1 *h, long long items)
@@ -758,33 +751,27 @@ int grhip_framer_sink_1_batch_create(grhip_framer_sink_1_batch **h, int n_stream
     *h = nullptr;
     if (n_streams < 1 || max_items_per_stream < 1 || max_items_per_stream >= (1ull << 31))
         return fail(GRHIP_EINVAL, "framer_sink_1_batch: bad stream count / capture length");
-    auto *b = new (std::nothrow) grhip_framer_sink_1_batch();
-    if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    b->S = n_streams;
-    b->max_items = (long long)max_items_per_stream;
-    b->words_stride = ((b->max_items + 31) >> 5) + 2;            // two zero words behind every stream
-    b->rec_stride = b->max_items / 32 + 8;                        // a packet costs at least 32 items
-    b->pool_stride = ((b->max_items / 8 + 4096 + 16 + 15) / 16) * 16;
-    const size_t S = (size_t)n_streams;
-    int rc = b->init_device(device);
-    if (!rc) rc = b->d_state.reserve(S * sizeof(FramerState));
-    if (!rc) rc = b->d_F.reserve(S * b->words_stride * 4);
-    if (!rc) rc = b->d_D.reserve(S * b->words_stride * 4);
-    if (!rc) rc = b->d_jobs.reserve(S * b->rec_stride * sizeof(FramerJob));
-    if (!rc) rc = b->d_msgs.reserve(S * b->rec_stride * sizeof(FramerMsg));
-    if (!rc) rc = b->d_pool.reserve(S * b->pool_stride);
-    if (rc) { grhip_framer_sink_1_batch_destroy(b); return rc; }
-    *h = b;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_framer_sink_1_batch *b) {
+        b->S = n_streams;
+        b->max_items = (long long)max_items_per_stream;
+        b->words_stride = ((b->max_items + 31) >> 5) + 2;            // two zero words behind every stream
+        b->rec_stride = b->max_items / 32 + 8;                        // a packet costs at least 32 items
+        b->pool_stride = ((b->max_items / 8 + 4096 + 16 + 15) / 16) * 16;
+        const size_t S = (size_t)n_streams;
+        int rc = b->init_device(device);
+        if (!rc) rc = b->d_state.reserve(S * sizeof(FramerState));
+        if (!rc) rc = b->d_F.reserve(S * b->words_stride * 4);
+        if (!rc) rc = b->d_D.reserve(S * b->words_stride * 4);
+        if (!rc) rc = b->d_jobs.reserve(S * b->rec_stride * sizeof(FramerJob));
+        if (!rc) rc = b->d_msgs.reserve(S * b->rec_stride * sizeof(FramerMsg));
+        if (!rc) rc = b->d_pool.reserve(S * b->pool_stride);
+        return rc;
+    });
 }
 
 void grhip_framer_sink_1_batch_destroy(grhip_framer_sink_1_batch *h)
 {
-    if (!h) return;
-    (void)h->bind();
-    h->d_state.release(); h->d_F.release(); h->d_D.release(); h->d_jobs.release(); h->d_msgs.release(); h->d_pool.release();
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_framer_sink_1_batch_run_device(grhip_framer_sink_1_batch *h, const unsigned char *d_in, size_t stream_stride_items,

@@ -172,27 +172,21 @@ int grhip_clock_recovery_mm_cc_create(grhip_clock_recovery_mm_cc **h, float omeg
     *h = nullptr;
     if (omega <= 0.0) return fail(GRHIP_ERANGE, "clock rate must be > 0");                        // .cc:62-63
     if (gain_mu < 0 || gain_omega < 0) return fail(GRHIP_ERANGE, "Gains must be non-negative");   // .cc:64-65
-    auto *b = new (std::nothrow) grhip_clock_recovery_mm_cc();
-    if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    memset(&b->host, 0, sizeof(b->host));
-    b->host.mu = mu; b->host.gain_omega = gain_omega; b->host.gain_mu = gain_mu;
-    b->host.omega_relative_limit = omega_relative_limit;
-    b->set_omega(omega);
-    int rc = b->init_device(device);
-    if (!rc) rc = get_device_tables(device, &b->tabs);
-    if (!rc) rc = b->d_state.reserve(sizeof(MMccState));
-    if (rc) { grhip_clock_recovery_mm_cc_destroy(b); return rc; }
-    *h = b;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_clock_recovery_mm_cc *b) {
+        memset(&b->host, 0, sizeof(b->host));
+        b->host.mu = mu; b->host.gain_omega = gain_omega; b->host.gain_mu = gain_mu;
+        b->host.omega_relative_limit = omega_relative_limit;
+        b->set_omega(omega);
+        int rc = b->init_device(device);
+        if (!rc) rc = get_device_tables(device, &b->tabs);
+        if (!rc) rc = b->d_state.reserve(sizeof(MMccState));
+        return rc;
+    });
 }
 
 void grhip_clock_recovery_mm_cc_destroy(grhip_clock_recovery_mm_cc *h)
 {
-    if (!h) return;
-    (void)h->bind();
-    h->d_state.release();
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_clock_recovery_mm_cc_forecast(grhip_clock_recovery_mm_cc *h, int noutput_items)

@@ -141,34 +141,26 @@ int grhip_pfb_decimator_ccf_create(grhip_pfb_decimator_ccf **h, unsigned decim, 
     if (!h || (!taps && ntaps)) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
     if (decim == 0 || decim > 4096) return fail(GRHIP_EINVAL, "pfb_decimator_ccf: decimation must be in 1..4096");
-    auto *b = new (std::nothrow) grhip_pfb_decimator_ccf();
-    if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    b->M = decim; b->chan = channel;
-    int rc = b->init_device(device);
-    if (!rc) {
+    return make_handle(h, [&](grhip_pfb_decimator_ccf *b) {
+        b->M = decim; b->chan = channel;
+        int rc = b->init_device(device);
+        if (rc) return rc;
         // the rotators the backward FFT applies to bin `channel`: exp(+2*pi*i*j*chan/M) (.cc:57, 165-173)
         std::vector<float> rot(2 * (size_t)decim);
         for (unsigned j = 0; j < decim; ++j) {
             const double a = 2.0 * M_PI * (double)(((unsigned long long)j * channel) % decim) / (double)decim;
             rot[2 * j] = (float)cos(a); rot[2 * j + 1] = (float)sin(a);
         }
-        rc = b->d_rot.reserve(rot.size() * 4);
-        if (!rc && hipMemcpy(b->d_rot.p, rot.data(), rot.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(GRHIP_ERUNTIME, "hipMemcpy failed");
-    }
-    if (!rc) rc = b->set_taps(taps, ntaps);
-    if (rc) { grhip_pfb_decimator_ccf_destroy(b); return rc; }
-    *h = b;
-    return GRHIP_OK;
+        if ((rc = b->d_rot.reserve(rot.size() * 4))) return rc;
+        if (hipMemcpy(b->d_rot.p, rot.data(), rot.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+            return fail(GRHIP_ERUNTIME, "hipMemcpy failed");
+        return b->set_taps(taps, ntaps);
+    });
 }
 
 void grhip_pfb_decimator_ccf_destroy(grhip_pfb_decimator_ccf *h)
 {
-    if (!h) return;
-    (void)h->bind();
-    h->d_ftaps.release(); h->d_rot.release();
-    h->destroy_base();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_pfb_decimator_ccf_set_taps(grhip_pfb_decimator_ccf *h, const float *taps, size_t ntaps)

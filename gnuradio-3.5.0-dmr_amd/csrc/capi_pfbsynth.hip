@@ -187,13 +187,7 @@ struct grhip_pfb_synthesis_filterbank_ccf : HandleBase {
         return n;
     }
 
-    void destroy()
-    {
-        (void)bind();
-        if (own_stream) (void)hipStreamSynchronize(own_stream);
-        d_taps.release(); d_tw.release(); d_state[0].release(); d_state[1].release(); d_scratch.release();
-        destroy_base();
-    }
+    ~grhip_pfb_synthesis_filterbank_ccf() { if (own_stream) (void)hipStreamSynchronize(own_stream); }   // then the buffers go
 };
 
 extern "C" {
@@ -203,23 +197,12 @@ int grhip_pfb_synthesis_filterbank_ccf_create(grhip_pfb_synthesis_filterbank_ccf
 {
     if (!h) return fail(GRHIP_EINVAL, "null handle pointer");
     *h = nullptr;
-    auto *b = new (std::nothrow) grhip_pfb_synthesis_filterbank_ccf();
-    if (!b) return fail(GRHIP_ENOMEM, "alloc");
-    int rc = b->init(numchans, taps, ntaps, device);
-    if (rc) {
-        if (b->own_stream) b->destroy();
-        delete b;
-        return rc;
-    }
-    *h = b;
-    return GRHIP_OK;
+    return make_handle(h, [&](grhip_pfb_synthesis_filterbank_ccf *b) { return b->init(numchans, taps, ntaps, device); });
 }
 
 void grhip_pfb_synthesis_filterbank_ccf_destroy(grhip_pfb_synthesis_filterbank_ccf *h)
 {
-    if (!h) return;
-    h->destroy();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_pfb_synthesis_filterbank_ccf_set_taps(grhip_pfb_synthesis_filterbank_ccf *h, const float *taps, size_t ntaps)

@@ -294,13 +294,7 @@ struct grhip_rs_core : HandleBase {
                       pick(stream));
     }
 
-    void destroy()
-    {
-        (void)bind();
-        if (own_stream) (void)hipStreamSynchronize(own_stream);
-        d_bank.release();
-        destroy_base();
-    }
+    ~grhip_rs_core() { if (own_stream) (void)hipStreamSynchronize(own_stream); }     // then the bank is freed
 };
 
 struct grhip_interp_fir_filter : grhip_rs_core {};
@@ -337,9 +331,7 @@ int grhip_interp_fir_filter_create(grhip_interp_fir_filter **h, const char *kind
 
 void grhip_interp_fir_filter_destroy(grhip_interp_fir_filter *h)
 {
-    if (!h) return;
-    h->destroy();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_interp_fir_filter_set_taps(grhip_interp_fir_filter *h, const float *taps, size_t ntaps)
@@ -396,9 +388,7 @@ int grhip_pfb_interpolator_ccf_create(grhip_pfb_interpolator_ccf **h, unsigned i
 
 void grhip_pfb_interpolator_ccf_destroy(grhip_pfb_interpolator_ccf *h)
 {
-    if (!h) return;
-    h->destroy();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_pfb_interpolator_ccf_set_taps(grhip_pfb_interpolator_ccf *h, const float *taps, size_t ntaps)
@@ -447,9 +437,7 @@ int grhip_rational_resampler_base_create(grhip_rational_resampler_base **h, cons
 
 void grhip_rational_resampler_base_destroy(grhip_rational_resampler_base *h)
 {
-    if (!h) return;
-    h->destroy();
-    delete h;
+    destroy_handle(h);
 }
 
 int grhip_rational_resampler_base_set_taps(grhip_rational_resampler_base *h, const float *taps, size_t ntaps)

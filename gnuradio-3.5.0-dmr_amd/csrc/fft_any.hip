@@ -244,7 +244,8 @@ bool FftPlan::size_ok(long long N) { return N >= 1 && N <= (1ll << 26) && (((N &
 
 int FftPlan::build(int n, int fwd)
 {
-    release();
+    for (DevBuf *b : {&d_tw, &d_tw2, &d_thi, &d_tlo, &d_chirp, &d_B, &d_s1, &d_s2}) b->release();
+    sub.reset();
     N = n; forward = fwd ? 1 : 0;
     if (n < 1) return fail(GRHIP_ERANGE, "gri_fftw: invalid fft_size");
     if (!size_ok(n)) return fail(GRHIP_EINVAL, "fft_size %d: more than 2^26 points (2^25 when not a power of two)", n);
@@ -285,7 +286,7 @@ int FftPlan::build(int n, int fwd)
     kind = BLUESTEIN;
     L = 1;
     while (L < 2 * n - 1) L <<= 1;
-    sub = new (std::nothrow) FftPlan();
+    sub.reset(new (std::nothrow) FftPlan());
     if (!sub) return fail(GRHIP_ENOMEM, "alloc");
     int rc = sub->build(L, 1);
     if (rc) return rc;
@@ -306,13 +307,6 @@ int FftPlan::build(int n, int fwd)
     for (int i = 0; i < L; ++i) B[(size_t)i] = make_float2((float)(b[(size_t)i].real() / L), (float)(b[(size_t)i].imag() / L));
     if ((rc = up(d_chirp, c.data(), c.size() * sizeof(float2)))) return rc;
     return up(d_B, B.data(), B.size() * sizeof(float2));
-}
-
-void FftPlan::release()
-{
-    d_tw.release(); d_tw2.release(); d_thi.release(); d_tlo.release(); d_chirp.release(); d_B.release();
-    d_s1.release(); d_s2.release();
-    if (sub) { sub->release(); delete sub; sub = nullptr; }
 }
 
 // one power-of-two transform of the plan's size, either direction (NATIVE / FOURSTEP only)

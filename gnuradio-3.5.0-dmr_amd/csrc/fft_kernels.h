@@ -2,6 +2,7 @@
 #pragma once
 #include "grhip_internal.h"
 #include <hip/hip_runtime.h>
+#include <memory>
 
 namespace grhip {
 
@@ -25,11 +26,10 @@ struct FftPlan {
     Kind kind = NATIVE;
     int N1 = 0, N2 = 0;         // FOURSTEP: N = N1 N2
     int L = 0;                  // BLUESTEIN: convolution length (power of two >= 2N - 1)
-    FftPlan *sub = nullptr;     // BLUESTEIN: the plan of size L
+    std::unique_ptr<FftPlan> sub;   // BLUESTEIN: the plan of size L
     DevBuf d_tw, d_tw2, d_thi, d_tlo, d_chirp, d_B, d_s1, d_s2;
     static bool size_ok(long long N);
-    int build(int N, int forward);
-    void release();
+    int build(int N, int forward);  // drops what an earlier build() left
     int exec(int shift, const float *window, const float2 *in, float2 *out, long long nvec, hipStream_t st);
     int exec_pow2(int fwd, int shift, const float *window, const float2 *in, float2 *out, long long nvec, hipStream_t st);
     // gr_fft_vfc: forward, no shift, items of N floats (NATIVE: read directly; the other kinds widen into `out` first)

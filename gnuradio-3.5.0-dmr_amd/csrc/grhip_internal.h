@@ -9,6 +9,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/grhip.h"
@@ -39,9 +40,15 @@ inline int zero_device(void *p, size_t bytes)
 }
 
 // ---- device buffer that only ever grows -----------------------------------
+// The owners below (DevBuf, StageBuf, SchedBuf and the structs built from them) free what they hold when they are
+// destroyed and cannot be copied; release() is for a live handle that drops a buffer it is about to rebuild.
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
     int reserve(size_t bytes)
     {
         if (bytes <= cap) return GRHIP_OK;
@@ -57,6 +64,7 @@ struct DevBuf {
         if (p) (void)hipFree(p);
         p = nullptr; cap = 0;
     }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(cap, o.cap); }
     template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
@@ -71,6 +79,7 @@ struct StageBuf : DevBuf {
 #endif
     static constexpr size_t MAPPED_MAX = GRHIP_MAPPED_MAX;
     void *host = nullptr;       // host address of a mapped buffer (p is its device address); null: device memory
+    ~StageBuf() { release(); }  // a mapped buffer goes back to the host allocator; ~DevBuf then finds nothing
     int reserve(size_t bytes)
     {
         if (bytes <= cap) return GRHIP_OK;
@@ -109,7 +118,6 @@ struct SchedBuf {
         }
         return b.as<unsigned>();
     }
-    void release() { b.release(); }
 };
 
 // ---- base of every block handle -------------------------------------------
@@ -138,7 +146,13 @@ struct HandleBase {
     int d2h(void *dst_host, const void *src_dev, size_t bytes, hipStream_t st);     // complete on return (<= PIN_MAX) or queued
 
     int init_device(int dev);
-    void destroy_base();
+    HandleBase() = default;
+    HandleBase(const HandleBase &) = delete;
+    HandleBase &operator=(const HandleBase &) = delete;
+    // Pin rings, then staging, then the stream.  A derived handle's members are destroyed before this runs, so its
+    // buffers are freed while the stream still exists.  Never binds a device (destroy_handle does): after a failed
+    // init_device there is no stream, nothing allocated, and `device` may be out of range.
+    ~HandleBase();
     hipStream_t pick(void *stream) const { return stream ? (hipStream_t)stream : own_stream; }
     int bind() const;          // hipSetDevice for the calling thread
 
@@ -174,8 +188,18 @@ struct HandleBase {
     }
 };
 
+// The body of every destroy entry point: bind the handle's device (only a handle that init_device gave a stream has
+// one) and delete it; the members' destructors free what it owns.
+template <class H>
+void destroy_handle(H *h)
+{
+    if (!h) return;
+    if (h->own_stream) (void)hipSetDevice(h->device);
+    delete h;
+}
+
 // The tail of a create entry point: allocate a handle H, run init(handle) and hand it out in *h.  When init fails
-// the handle is torn down again (its destroy() only once init_device has given it a stream) and *h stays null.
+// the handle is destroyed again and *h stays null.
 template <class H, class Init>
 int make_handle(H **h, Init &&init)
 {
@@ -184,8 +208,7 @@ int make_handle(H **h, Init &&init)
     if (!b) return fail(GRHIP_ENOMEM, "alloc");
     int rc = init(b);
     if (rc) {
-        if (b->own_stream) b->destroy();
-        delete b;
+        destroy_handle(b);
         return rc;
     }
     *h = b;

@@ -40,14 +40,14 @@ struct WalkedSteps {
         return GRHIP_OK;
     }
 
-    void release()
+    WalkedSteps() = default;
+    WalkedSteps(const WalkedSteps &) = delete;
+    WalkedSteps &operator=(const WalkedSteps &) = delete;
+    ~WalkedSteps()                  // the event first, then (as a member) d_steps
     {
-        if (ev) {
-            if (busy) (void)hipEventSynchronize(ev);
-            (void)hipEventDestroy(ev);
-            ev = nullptr; busy = false;
-        }
-        d_steps.release();
+        if (!ev) return;
+        if (busy) (void)hipEventSynchronize(ev);
+        (void)hipEventDestroy(ev);
     }
 };
 
@@ -112,9 +112,7 @@ struct SchedBlock : HandleBase {
 #define GRHIP_SCHED_ENTRIES(NAME)                                                                                      \
     void grhip_##NAME##_destroy(grhip_##NAME *h)                                                                       \
     {                                                                                                                  \
-        if (!h) return;                                                                                                \
-        h->destroy();                                                                                                  \
-        delete h;                                                                                                      \
+        destroy_handle(h);                                                                                             \
     }                                                                                                                  \
     int grhip_##NAME##_set_mode(grhip_##NAME *h, int mode)                                                             \
     {                                                                                                                  \

@@ -110,7 +110,6 @@ struct XlatingCore {
     int run(int mode, const float2 *d_in, long long n_in, long long n_out, float2 *d_y, float *d_demod,
             float gain, const float2 *y_prev, float2 *y_last, const float *atan_tab, hipStream_t st,
             int n_streams = 1, long long x_stride = 0, long long n_lo = 0, long long out_stride = 0);
-    void release();
 };
 
 }  // namespace grhip
