@@ -16,6 +16,8 @@ __all__ = [
     "fft_vcc", "fft_vfc", "fft_filter_ccc", "fft_filter_fff", "pfb_channelizer_ccf", "pfb_decimator_ccf", "pfb_arb_resampler_ccf", "pfb_arb_resampler_fff",
     "fractional_interpolator_ff", "fractional_interpolator_cc",
     "firdes_hilbert", "hilbert_fc", "filter_delay_fc", "goertzel_fc",
+    "dc_blocker_ff", "dc_blocker_cc", "moving_average_ff", "moving_average_cc", "moving_average_ss", "moving_average_ii",
+    "integrate_ff", "integrate_cc", "integrate_ss", "integrate_ii",
     "WIN_HAMMING", "WIN_HANN", "WIN_BLACKMAN", "WIN_RECTANGULAR", "WIN_KAISER", "WIN_BLACKMAN_hARRIS",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
     "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
@@ -1498,6 +1500,175 @@ class goertzel_fc(_Block):
         L.grhip_goertzel_fc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         return _check(L.grhip_goertzel_fc_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
                                                       _stream(stream)))
+
+# ----------------------------------------------------------------------------
+# gr.dc_blocker_ff / _cc, gr.moving_average_XX, gr.integrate_XX  (filter/gr_dc_blocker_ff.i, gengen/gr_moving_average_XX.i.t,
+# gengen/gr_integrate_XX.i.t)
+# ----------------------------------------------------------------------------
+_RUNSUM_DTYPE = {"ff": np.float32, "cc": np.complex64, "ss": np.int16, "ii": np.int32}
+
+
+class _runsum(_Block):
+    _name = None
+
+    def __init__(self):
+        _Block.__init__(self)
+        self._dtype = _RUNSUM_DTYPE[self._name[-2:]]
+        self._destroy = "grhip_%s_destroy" % self._name
+
+    def _fn(self, name, argtypes=None):
+        f = getattr(lib(), "grhip_%s_%s" % (self._name, name))
+        if argtypes is not None:
+            f.argtypes = argtypes
+        return f
+
+    def set_mode(self, mode):
+        _check(self._fn("set_mode", [C.c_void_p, C.c_int])(self._h, int(mode)))
+
+    def _work(self, n, x, nout):
+        out = np.zeros(nout, dtype=self._dtype)
+        r = _check(self._fn("work", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])(self._h, int(n), _ptr(x), _ptr(out)))
+        return out, r
+
+    def work_device(self, noutput_items, d_in, d_out, stream=None):
+        f = self._fn("work_device", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+        return _check(f(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out), _stream(stream)))
+
+
+class _dc_blocker(_runsum):
+    """gr.dc_blocker_XX(D=32, long_form=True): the input delayed by get_group_delay() minus 2 or 4 cascaded D-point
+    moving averages of it.  The state lives in the block and carries across work calls."""
+
+    def __init__(self, D=32, long_form=True, device=0):
+        _runsum.__init__(self)
+        self._streams = 1
+        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int])
+        _check(f(C.byref(self._h), int(D), 1 if long_form else 0, int(device)))
+
+    def get_group_delay(self):
+        return _check(self._fn("group_delay", [C.c_void_p])(self._h))
+
+    def history(self):
+        return 1
+
+    def decimation(self):
+        return 1
+
+    def set_streams(self, nstreams):
+        """work / work_device then take nstreams streams of noutput_items each, back to back; restarts the filter"""
+        _check(self._fn("set_streams", [C.c_void_p, C.c_int])(self._h, int(nstreams)))
+        self._streams = int(nstreams)
+
+    def work(self, noutput_items, input_items):
+        x = np.ascontiguousarray(input_items, dtype=self._dtype).reshape(-1)
+        if len(x) < noutput_items * self._streams:
+            raise ValueError("work needs %d input items, got %d" % (noutput_items * self._streams, len(x)))
+        out, r = self._work(noutput_items, x, noutput_items * self._streams)
+        return out[:r * self._streams]
+
+
+class dc_blocker_ff(_dc_blocker):
+    _name = "dc_blocker_ff"
+
+
+class dc_blocker_cc(_dc_blocker):
+    _name = "dc_blocker_cc"
+
+
+class _moving_average(_runsum):
+    """gr.moving_average_XX(length, scale, max_iter=4096): history length; work returns min(noutput_items, max_iter)
+    outputs, as one reference work call; work_device stands for successive calls of max_iter outputs."""
+
+    def _scale_args(self, scale):
+        k = self._name[-2:]
+        if k == "ff":
+            return [C.c_float], [float(scale)]
+        if k == "cc":
+            z = complex(scale)
+            return [C.c_float, C.c_float], [z.real, z.imag]
+        if k == "ss":
+            return [C.c_short], [int(scale)]
+        return [C.c_int], [int(scale)]
+
+    def __init__(self, length, scale, max_iter=4096, device=0):
+        _runsum.__init__(self)
+        t, v = self._scale_args(scale)
+        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_int] + t + [C.c_int, C.c_int])
+        _check(f(C.byref(self._h), int(length), *(v + [int(max_iter), int(device)])))
+
+    def set_length_and_scale(self, length, scale):
+        t, v = self._scale_args(scale)
+        _check(self._fn("set_length_and_scale", [C.c_void_p, C.c_int] + t)(self._h, int(length), *v))
+
+    def history(self):
+        return _check(self._fn("history", [C.c_void_p])(self._h))
+
+    def max_iter(self):
+        return _check(self._fn("max_iter", [C.c_void_p])(self._h))
+
+    def decimation(self):
+        return 1
+
+    def work(self, noutput_items, input_items):
+        x = np.ascontiguousarray(input_items, dtype=self._dtype)
+        need = min(noutput_items, self.max_iter()) + self.history() - 1
+        if len(x) < need:
+            raise ValueError("work needs %d input items, got %d" % (need, len(x)))
+        out, r = self._work(noutput_items, x, max(noutput_items, 1))
+        return out[:r]
+
+
+class moving_average_ff(_moving_average):
+    _name = "moving_average_ff"
+
+
+class moving_average_cc(_moving_average):
+    _name = "moving_average_cc"
+
+
+class moving_average_ss(_moving_average):
+    _name = "moving_average_ss"
+
+
+class moving_average_ii(_moving_average):
+    _name = "moving_average_ii"
+
+
+class _integrate(_runsum):
+    """gr.integrate_XX(decim): out[i] = sum of in[i decim .. i decim + decim - 1] (a sync decimator by decim)"""
+
+    def __init__(self, decim, device=0):
+        _runsum.__init__(self)
+        _check(self._fn("create", [C.POINTER(C.c_void_p), C.c_int, C.c_int])(C.byref(self._h), int(decim), int(device)))
+
+    def history(self):
+        return 1
+
+    def decimation(self):
+        return _check(self._fn("decimation", [C.c_void_p])(self._h))
+
+    def work(self, noutput_items, input_items):
+        x = np.ascontiguousarray(input_items, dtype=self._dtype)
+        if len(x) < noutput_items * self.decimation():
+            raise ValueError("not enough input")
+        out, r = self._work(noutput_items, x, noutput_items)
+        return out[:r]
+
+
+class integrate_ff(_integrate):
+    _name = "integrate_ff"
+
+
+class integrate_cc(_integrate):
+    _name = "integrate_cc"
+
+
+class integrate_ss(_integrate):
+    _name = "integrate_ss"
+
+
+class integrate_ii(_integrate):
+    _name = "integrate_ii"
 
 # ----------------------------------------------------------------------------
 # gr.interp_fir_filter_XXX / gr.rational_resampler_base_XXX  (filter/gr_interp_fir_filter_XXX.i.t,

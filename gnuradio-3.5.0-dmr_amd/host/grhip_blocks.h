@@ -21,6 +21,9 @@
 //   grhip_pfb_synthesis_filterbank_ccf       <- gr_pfb_synthesis_filterbank_ccf (filter/gr_pfb_synthesis_filterbank_ccf.h)
 //   grhip_hilbert_fc / grhip_filter_delay_fc <- gr_hilbert_fc (filter/gr_hilbert_fc.h), gr_filter_delay_fc (filter/gr_filter_delay_fc.h)
 //   grhip_goertzel_fc                        <- gr_goertzel_fc (filter/gr_goertzel_fc.h)
+//   grhip_dc_blocker_ff / _cc                <- gr_dc_blocker_ff / _cc (filter/gr_dc_blocker_ff.h:60-100)
+//   grhip_moving_average_XX                  <- gr_moving_average_XX (gengen/gr_moving_average_XX.h.t)
+//   grhip_integrate_XX                       <- gr_integrate_XX (gengen/gr_integrate_XX.h.t)
 //
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
@@ -1085,3 +1088,115 @@ inline grhip_goertzel_fc_sptr grhip_make_goertzel_fc(int rate, int len, float fr
 {
     return gnuradio::get_initial_sptr(new grhip_goertzel_fc_blk(rate, len, freq, device));
 }
+
+// ---------------------------------------------------------------------------
+// gr_dc_blocker_ff / _cc (D = 32, long_form = true)  (gr_sync_block, history 1; filter/gr_dc_blocker_ff.cc:63-103)
+// gr_moving_average_XX (length, scale, max_iter = 4096)  (gr_sync_block, history length; gengen/gr_moving_average_XX.cc.t:38-62)
+// gr_integrate_XX (decim)  (gr_sync_decimator by decim; gengen/gr_integrate_XX.cc.t:38-46)
+// ---------------------------------------------------------------------------
+#define GRHIP_DC_BLOCKER_BLK(SFX, ITEM)                                                                                \
+    class grhip_dc_blocker_##SFX##_blk;                                                                                \
+    typedef boost::shared_ptr<grhip_dc_blocker_##SFX##_blk> grhip_dc_blocker_##SFX##_sptr;                             \
+    class grhip_dc_blocker_##SFX##_blk : public gr_sync_block {                                                        \
+        grhip_dc_blocker_##SFX *d_h = nullptr;                                                                         \
+        grhip_dc_blocker_##SFX##_blk(int D, bool long_form, int device)                                                \
+            : gr_sync_block("dc_blocker_" #SFX, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM))) \
+        {                                                                                                              \
+            grhip_detail::check(grhip_dc_blocker_##SFX##_create(&d_h, D, long_form ? 1 : 0, device));                  \
+        }                                                                                                              \
+        friend grhip_dc_blocker_##SFX##_sptr grhip_make_dc_blocker_##SFX(int, bool, int);                              \
+    public:                                                                                                            \
+        ~grhip_dc_blocker_##SFX##_blk() { grhip_dc_blocker_##SFX##_destroy(d_h); }                                     \
+        int get_group_delay() { return grhip_dc_blocker_##SFX##_group_delay(d_h); }                                    \
+        void set_mode(int mode) { grhip_detail::check(grhip_dc_blocker_##SFX##_set_mode(d_h, mode)); }                 \
+        int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override                  \
+        {                                                                                                              \
+            int r = grhip_dc_blocker_##SFX##_work(d_h, noutput_items, in[0], out[0]);                                  \
+            grhip_detail::check(r);                                                                                    \
+            return r;                                                                                                  \
+        }                                                                                                              \
+    };                                                                                                                 \
+    inline grhip_dc_blocker_##SFX##_sptr grhip_make_dc_blocker_##SFX(int D = 32, bool long_form = true, int device = 0) \
+    {                                                                                                                  \
+        return gnuradio::get_initial_sptr(new grhip_dc_blocker_##SFX##_blk(D, long_form, device));                     \
+    }
+GRHIP_DC_BLOCKER_BLK(ff, float)
+GRHIP_DC_BLOCKER_BLK(cc, gr_complex)
+#undef GRHIP_DC_BLOCKER_BLK
+
+namespace grhip_detail {
+inline int ma_create(grhip_moving_average_ff **h, int n, float s, int m, int d) { return grhip_moving_average_ff_create(h, n, s, m, d); }
+inline int ma_create(grhip_moving_average_cc **h, int n, gr_complex s, int m, int d) { return grhip_moving_average_cc_create(h, n, s.real(), s.imag(), m, d); }
+inline int ma_create(grhip_moving_average_ss **h, int n, short s, int m, int d) { return grhip_moving_average_ss_create(h, n, s, m, d); }
+inline int ma_create(grhip_moving_average_ii **h, int n, int s, int m, int d) { return grhip_moving_average_ii_create(h, n, s, m, d); }
+inline int ma_set(grhip_moving_average_ff *h, int n, float s) { return grhip_moving_average_ff_set_length_and_scale(h, n, s); }
+inline int ma_set(grhip_moving_average_cc *h, int n, gr_complex s) { return grhip_moving_average_cc_set_length_and_scale(h, n, s.real(), s.imag()); }
+inline int ma_set(grhip_moving_average_ss *h, int n, short s) { return grhip_moving_average_ss_set_length_and_scale(h, n, s); }
+inline int ma_set(grhip_moving_average_ii *h, int n, int s) { return grhip_moving_average_ii_set_length_and_scale(h, n, s); }
+}  // namespace grhip_detail
+
+#define GRHIP_MOVING_AVERAGE_BLK(SFX, ITEM)                                                                            \
+    class grhip_moving_average_##SFX##_blk;                                                                            \
+    typedef boost::shared_ptr<grhip_moving_average_##SFX##_blk> grhip_moving_average_##SFX##_sptr;                     \
+    class grhip_moving_average_##SFX##_blk : public gr_sync_block {                                                    \
+        grhip_moving_average_##SFX *d_h = nullptr;                                                                     \
+        grhip_moving_average_##SFX##_blk(int length, ITEM scale, int max_iter, int device)                             \
+            : gr_sync_block("moving_average_" #SFX, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM))) \
+        {                                                                                                              \
+            grhip_detail::check(grhip_detail::ma_create(&d_h, length, scale, max_iter, device));                       \
+            set_history((unsigned)length);                                          /* .cc.t:49 */                     \
+        }                                                                                                              \
+        friend grhip_moving_average_##SFX##_sptr grhip_make_moving_average_##SFX(int, ITEM, int, int);                 \
+    public:                                                                                                            \
+        ~grhip_moving_average_##SFX##_blk() { grhip_moving_average_##SFX##_destroy(d_h); }                             \
+        void set_length_and_scale(int length, ITEM scale) { grhip_detail::check(grhip_detail::ma_set(d_h, length, scale)); } \
+        void set_mode(int mode) { grhip_detail::check(grhip_moving_average_##SFX##_set_mode(d_h, mode)); }             \
+        int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override                  \
+        {                                                                                                              \
+            int r = grhip_moving_average_##SFX##_work(d_h, noutput_items, in[0], out[0]);                              \
+            grhip_detail::check(r);                                                                                    \
+            set_history((unsigned)grhip_moving_average_##SFX##_history(d_h));       /* .cc.t:72: after a latched update */ \
+            return r;                                                                                                  \
+        }                                                                                                              \
+    };                                                                                                                 \
+    inline grhip_moving_average_##SFX##_sptr grhip_make_moving_average_##SFX(int length, ITEM scale, int max_iter = 4096, int device = 0) \
+    {                                                                                                                  \
+        return gnuradio::get_initial_sptr(new grhip_moving_average_##SFX##_blk(length, scale, max_iter, device));      \
+    }
+GRHIP_MOVING_AVERAGE_BLK(ff, float)
+GRHIP_MOVING_AVERAGE_BLK(cc, gr_complex)
+GRHIP_MOVING_AVERAGE_BLK(ss, short)
+GRHIP_MOVING_AVERAGE_BLK(ii, int)
+#undef GRHIP_MOVING_AVERAGE_BLK
+
+#define GRHIP_INTEGRATE_BLK(SFX, ITEM)                                                                                 \
+    class grhip_integrate_##SFX##_blk;                                                                                 \
+    typedef boost::shared_ptr<grhip_integrate_##SFX##_blk> grhip_integrate_##SFX##_sptr;                               \
+    class grhip_integrate_##SFX##_blk : public gr_sync_decimator {                                                     \
+        grhip_integrate_##SFX *d_h = nullptr;                                                                          \
+        grhip_integrate_##SFX##_blk(int decim, int device)                                                             \
+            : gr_sync_decimator("integrate_" #SFX, gr_make_io_signature(1, 1, sizeof(ITEM)),                           \
+                                gr_make_io_signature(1, 1, sizeof(ITEM)), decim < 1 ? 1 : decim)                       \
+        {                                                                                                              \
+            grhip_detail::check(grhip_integrate_##SFX##_create(&d_h, decim, device));                                  \
+        }                                                                                                              \
+        friend grhip_integrate_##SFX##_sptr grhip_make_integrate_##SFX(int, int);                                      \
+    public:                                                                                                            \
+        ~grhip_integrate_##SFX##_blk() { grhip_integrate_##SFX##_destroy(d_h); }                                       \
+        void set_mode(int mode) { grhip_detail::check(grhip_integrate_##SFX##_set_mode(d_h, mode)); }                  \
+        int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override                  \
+        {                                                                                                              \
+            int r = grhip_integrate_##SFX##_work(d_h, noutput_items, in[0], out[0]);                                   \
+            grhip_detail::check(r);                                                                                    \
+            return r;                                                                                                  \
+        }                                                                                                              \
+    };                                                                                                                 \
+    inline grhip_integrate_##SFX##_sptr grhip_make_integrate_##SFX(int decim, int device = 0)                          \
+    {                                                                                                                  \
+        return gnuradio::get_initial_sptr(new grhip_integrate_##SFX##_blk(decim, device));                             \
+    }
+GRHIP_INTEGRATE_BLK(ff, float)
+GRHIP_INTEGRATE_BLK(cc, gr_complex)
+GRHIP_INTEGRATE_BLK(ss, short)
+GRHIP_INTEGRATE_BLK(ii, int)
+#undef GRHIP_INTEGRATE_BLK

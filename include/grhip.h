@@ -1068,6 +1068,161 @@ GRHIP_API int grhip_goertzel_fc_work_device(grhip_goertzel_fc *h, int noutput_it
                                             void *stream);
 
 /* ======================================================================
+ * gr_dc_blocker_ff / gr_dc_blocker_cc
+ *   replaces gr_make_dc_blocker_ff(int D = 32, bool long_form = true), _cc likewise
+ *   filter/gr_dc_blocker_ff.cc:31-53 (moving_averager_f::filter), 57-80, 96-103 (get_group_delay),
+ *   105-138 (work); filter/gr_dc_blocker_cc.cc the same lines
+ * gr_sync_block, history 1.  2 (short form) or 4 (long form) moving averagers in a row, each
+ * y = (x - x[n-D]) + y_prev kept as a float recurrence and returned as y / (float)D; the output is
+ * the input delayed by get_group_delay() = D - 1 (short) or 2D - 2 (long) minus the last average.
+ * All state is in the handle and carries across calls.  D = 1 is legal; GRHIP_EINVAL for D < 1 (the
+ * reference's deque(D - 1) throws) and for D > 1345, the most the FAST kernel's LDS layout carries
+ * in its tightest form (complex, long form).
+ * GRHIP_MODE_GENERIC is that recurrence, one wavefront per stream: bit-exact, including the rounding
+ * errors the recurrence never forgets (the output drifts from the float64 value of the same filter
+ * by about 1e-4 of a DC level of 1 over 2 M samples, 1e-3 at DC 10).  FAST forms every stage as a true
+ * D-window sum of the stage before it: no state older than the filter's span, an error of a few ulp
+ * of the input level whatever the stream length; it is compared with the float64 filter.
+ * The two modes keep different states; set_mode and set_streams restart the filter from zero.
+ * set_streams(S): work and work_device then take S streams of noutput_items each, back to back in
+ * `in` and `out`, each with its own state (S = 1 after create).
+ * ====================================================================== */
+typedef struct grhip_dc_blocker_ff grhip_dc_blocker_ff;
+GRHIP_API int grhip_dc_blocker_ff_create(grhip_dc_blocker_ff **h, int D, int long_form, int device);
+GRHIP_API void grhip_dc_blocker_ff_destroy(grhip_dc_blocker_ff *h);
+GRHIP_API int grhip_dc_blocker_ff_set_mode(grhip_dc_blocker_ff *h, int mode);
+GRHIP_API int grhip_dc_blocker_ff_set_streams(grhip_dc_blocker_ff *h, int nstreams);
+GRHIP_API int grhip_dc_blocker_ff_group_delay(const grhip_dc_blocker_ff *h);
+GRHIP_API int grhip_dc_blocker_ff_work(grhip_dc_blocker_ff *h, int noutput_items, const void *in,
+                                            void *out);
+GRHIP_API int grhip_dc_blocker_ff_work_device(grhip_dc_blocker_ff *h, int noutput_items,
+                                                   const void *d_in, void *d_out, void *stream);
+typedef struct grhip_dc_blocker_cc grhip_dc_blocker_cc;
+GRHIP_API int grhip_dc_blocker_cc_create(grhip_dc_blocker_cc **h, int D, int long_form, int device);
+GRHIP_API void grhip_dc_blocker_cc_destroy(grhip_dc_blocker_cc *h);
+GRHIP_API int grhip_dc_blocker_cc_set_mode(grhip_dc_blocker_cc *h, int mode);
+GRHIP_API int grhip_dc_blocker_cc_set_streams(grhip_dc_blocker_cc *h, int nstreams);
+GRHIP_API int grhip_dc_blocker_cc_group_delay(const grhip_dc_blocker_cc *h);
+GRHIP_API int grhip_dc_blocker_cc_work(grhip_dc_blocker_cc *h, int noutput_items, const void *in,
+                                            void *out);
+GRHIP_API int grhip_dc_blocker_cc_work_device(grhip_dc_blocker_cc *h, int noutput_items,
+                                                   const void *d_in, void *d_out, void *stream);
+
+/* ======================================================================
+ * gr_moving_average_ff / _cc / _ss / _ii
+ *   replaces gr_make_moving_average_XX(int length, O scale, int max_iter = 4096)
+ *   gengen/gr_moving_average_XX.cc.t:38-50 (set_history(length)), 56-62 (set_length_and_scale),
+ *   64-93 (work)
+ * gr_sync_block, history = length.  Every work call starts sum at 0, adds the first length - 1
+ * items in order and then, per output, sum += in[i+length-1]; out = sum * scale; sum -= in[i]; it
+ * returns min(noutput_items, max_iter).  _ss sums in a short and _ii in an int (wrapping), and
+ * multiplies by scale in the output type; _cc's scale is complex.  set_length_and_scale latches:
+ * the next work (or work_device) call applies it, computes nothing and returns 0 (.cc.t:69-75).
+ * work is ONE reference work call: `in` holds min(noutput_items, max_iter) + length - 1 items.
+ * work_device stands for the SUCCESSIVE reference work calls that produce noutput_items outputs:
+ * calls of exactly max_iter outputs, the last one shorter; d_in holds noutput_items + length - 1
+ * items and it returns noutput_items.  The reference scheduler's own chunking depends on buffer
+ * fill and is not deterministic, so this chunking is the one DEFINED HERE; GRHIP_MODE_GENERIC is
+ * bit-exact to the reference's arithmetic run with it.  FAST forms every window sum on its own
+ * (no dependence on the chunking, error a few ulp of length max|x|); the integer types are exact
+ * in both modes.  GRHIP_EINVAL for length < 1, length > 8449 (LDS layout) and max_iter < 1.
+ * ====================================================================== */
+typedef struct grhip_moving_average_ff grhip_moving_average_ff;
+GRHIP_API void grhip_moving_average_ff_destroy(grhip_moving_average_ff *h);
+GRHIP_API int grhip_moving_average_ff_set_mode(grhip_moving_average_ff *h, int mode);
+GRHIP_API int grhip_moving_average_ff_history(const grhip_moving_average_ff *h);
+GRHIP_API int grhip_moving_average_ff_max_iter(const grhip_moving_average_ff *h);
+GRHIP_API int grhip_moving_average_ff_work(grhip_moving_average_ff *h, int noutput_items,
+                                                const void *in, void *out);
+GRHIP_API int grhip_moving_average_ff_work_device(grhip_moving_average_ff *h, int noutput_items,
+                                                       const void *d_in, void *d_out, void *stream);
+typedef struct grhip_moving_average_cc grhip_moving_average_cc;
+GRHIP_API void grhip_moving_average_cc_destroy(grhip_moving_average_cc *h);
+GRHIP_API int grhip_moving_average_cc_set_mode(grhip_moving_average_cc *h, int mode);
+GRHIP_API int grhip_moving_average_cc_history(const grhip_moving_average_cc *h);
+GRHIP_API int grhip_moving_average_cc_max_iter(const grhip_moving_average_cc *h);
+GRHIP_API int grhip_moving_average_cc_work(grhip_moving_average_cc *h, int noutput_items,
+                                                const void *in, void *out);
+GRHIP_API int grhip_moving_average_cc_work_device(grhip_moving_average_cc *h, int noutput_items,
+                                                       const void *d_in, void *d_out, void *stream);
+typedef struct grhip_moving_average_ss grhip_moving_average_ss;
+GRHIP_API void grhip_moving_average_ss_destroy(grhip_moving_average_ss *h);
+GRHIP_API int grhip_moving_average_ss_set_mode(grhip_moving_average_ss *h, int mode);
+GRHIP_API int grhip_moving_average_ss_history(const grhip_moving_average_ss *h);
+GRHIP_API int grhip_moving_average_ss_max_iter(const grhip_moving_average_ss *h);
+GRHIP_API int grhip_moving_average_ss_work(grhip_moving_average_ss *h, int noutput_items,
+                                                const void *in, void *out);
+GRHIP_API int grhip_moving_average_ss_work_device(grhip_moving_average_ss *h, int noutput_items,
+                                                       const void *d_in, void *d_out, void *stream);
+typedef struct grhip_moving_average_ii grhip_moving_average_ii;
+GRHIP_API void grhip_moving_average_ii_destroy(grhip_moving_average_ii *h);
+GRHIP_API int grhip_moving_average_ii_set_mode(grhip_moving_average_ii *h, int mode);
+GRHIP_API int grhip_moving_average_ii_history(const grhip_moving_average_ii *h);
+GRHIP_API int grhip_moving_average_ii_max_iter(const grhip_moving_average_ii *h);
+GRHIP_API int grhip_moving_average_ii_work(grhip_moving_average_ii *h, int noutput_items,
+                                                const void *in, void *out);
+GRHIP_API int grhip_moving_average_ii_work_device(grhip_moving_average_ii *h, int noutput_items,
+                                                       const void *d_in, void *d_out, void *stream);
+GRHIP_API int grhip_moving_average_ff_create(grhip_moving_average_ff **h, int length, float scale, int max_iter,
+                                             int device);
+GRHIP_API int grhip_moving_average_cc_create(grhip_moving_average_cc **h, int length, float scale_re, float scale_im,
+                                             int max_iter, int device);
+GRHIP_API int grhip_moving_average_ss_create(grhip_moving_average_ss **h, int length, short scale, int max_iter,
+                                             int device);
+GRHIP_API int grhip_moving_average_ii_create(grhip_moving_average_ii **h, int length, int scale, int max_iter,
+                                             int device);
+GRHIP_API int grhip_moving_average_ff_set_length_and_scale(grhip_moving_average_ff *h, int length, float scale);
+GRHIP_API int grhip_moving_average_cc_set_length_and_scale(grhip_moving_average_cc *h, int length, float scale_re,
+                                                           float scale_im);
+GRHIP_API int grhip_moving_average_ss_set_length_and_scale(grhip_moving_average_ss *h, int length, short scale);
+GRHIP_API int grhip_moving_average_ii_set_length_and_scale(grhip_moving_average_ii *h, int length, int scale);
+
+/* ======================================================================
+ * gr_integrate_ff / _cc / _ss / _ii
+ *   replaces gr_make_integrate_XX(int decim)
+ *   gengen/gr_integrate_XX.cc.t:38-46, 52-67
+ * gr_sync_decimator by decim, no state (d_count is unused): out[i] = 0, then += in[i*decim + j] for
+ * j ascending.  GRHIP_MODE_GENERIC keeps that order (bit-exact); FAST sums each output with up to
+ * 64 lanes; the integer types wrap and are exact in both.  GRHIP_EINVAL for decim < 1.
+ * ====================================================================== */
+typedef struct grhip_integrate_ff grhip_integrate_ff;
+GRHIP_API int grhip_integrate_ff_create(grhip_integrate_ff **h, int decim, int device);
+GRHIP_API void grhip_integrate_ff_destroy(grhip_integrate_ff *h);
+GRHIP_API int grhip_integrate_ff_set_mode(grhip_integrate_ff *h, int mode);
+GRHIP_API int grhip_integrate_ff_decimation(const grhip_integrate_ff *h);
+GRHIP_API int grhip_integrate_ff_work(grhip_integrate_ff *h, int noutput_items, const void *in,
+                                           void *out);
+GRHIP_API int grhip_integrate_ff_work_device(grhip_integrate_ff *h, int noutput_items,
+                                                  const void *d_in, void *d_out, void *stream);
+typedef struct grhip_integrate_cc grhip_integrate_cc;
+GRHIP_API int grhip_integrate_cc_create(grhip_integrate_cc **h, int decim, int device);
+GRHIP_API void grhip_integrate_cc_destroy(grhip_integrate_cc *h);
+GRHIP_API int grhip_integrate_cc_set_mode(grhip_integrate_cc *h, int mode);
+GRHIP_API int grhip_integrate_cc_decimation(const grhip_integrate_cc *h);
+GRHIP_API int grhip_integrate_cc_work(grhip_integrate_cc *h, int noutput_items, const void *in,
+                                           void *out);
+GRHIP_API int grhip_integrate_cc_work_device(grhip_integrate_cc *h, int noutput_items,
+                                                  const void *d_in, void *d_out, void *stream);
+typedef struct grhip_integrate_ss grhip_integrate_ss;
+GRHIP_API int grhip_integrate_ss_create(grhip_integrate_ss **h, int decim, int device);
+GRHIP_API void grhip_integrate_ss_destroy(grhip_integrate_ss *h);
+GRHIP_API int grhip_integrate_ss_set_mode(grhip_integrate_ss *h, int mode);
+GRHIP_API int grhip_integrate_ss_decimation(const grhip_integrate_ss *h);
+GRHIP_API int grhip_integrate_ss_work(grhip_integrate_ss *h, int noutput_items, const void *in,
+                                           void *out);
+GRHIP_API int grhip_integrate_ss_work_device(grhip_integrate_ss *h, int noutput_items,
+                                                  const void *d_in, void *d_out, void *stream);
+typedef struct grhip_integrate_ii grhip_integrate_ii;
+GRHIP_API int grhip_integrate_ii_create(grhip_integrate_ii **h, int decim, int device);
+GRHIP_API void grhip_integrate_ii_destroy(grhip_integrate_ii *h);
+GRHIP_API int grhip_integrate_ii_set_mode(grhip_integrate_ii *h, int mode);
+GRHIP_API int grhip_integrate_ii_decimation(const grhip_integrate_ii *h);
+GRHIP_API int grhip_integrate_ii_work(grhip_integrate_ii *h, int noutput_items, const void *in,
+                                           void *out);
+GRHIP_API int grhip_integrate_ii_work_device(grhip_integrate_ii *h, int noutput_items,
+                                                  const void *d_in, void *d_out, void *stream);
+
+/* ======================================================================
  * gr_pfb_channelizer_ccf
  *   replaces gr_make_pfb_channelizer_ccf(unsigned numchans,
  *       const std::vector<float>& taps, float oversample_rate)
