@@ -18,6 +18,7 @@ __all__ = [
     "firdes_hilbert", "hilbert_fc", "filter_delay_fc", "goertzel_fc",
     "dc_blocker_ff", "dc_blocker_cc", "moving_average_ff", "moving_average_cc", "moving_average_ss", "moving_average_ii",
     "integrate_ff", "integrate_cc", "integrate_ss", "integrate_ii",
+    "complex_to_mag_squared", "single_pole_iir_filter_ff", "nlog10_ff", "keep_one_in_n",
     "WIN_HAMMING", "WIN_HANN", "WIN_BLACKMAN", "WIN_RECTANGULAR", "WIN_KAISER", "WIN_BLACKMAN_hARRIS",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
     "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
@@ -1669,6 +1670,131 @@ class integrate_ss(_integrate):
 
 class integrate_ii(_integrate):
     _name = "integrate_ii"
+
+# ----------------------------------------------------------------------------
+# gr.complex_to_mag_squared, gr.single_pole_iir_filter_ff, gr.nlog10_ff, gr.keep_one_in_n (general/gr_complex_to_xxx.i,
+# filter/gr_single_pole_iir_filter_ff.i, general/gr_nlog10_ff.i, general/gr_keep_one_in_n.i)
+# ----------------------------------------------------------------------------
+class _spectrum(_Block):
+    _name = None
+    _in = np.float32
+
+    def __init__(self, vlen):
+        _Block.__init__(self)
+        self._destroy = "grhip_%s_destroy" % self._name
+        self._vlen = int(vlen)
+        self._streams = 1
+
+    def _fn(self, name, argtypes=None):
+        f = getattr(lib(), "grhip_%s_%s" % (self._name, name))
+        if argtypes is not None:
+            f.argtypes = argtypes
+        return f
+
+    def set_mode(self, mode):
+        _check(self._fn("set_mode", [C.c_void_p, C.c_int])(self._h, int(mode)))
+
+    def set_streams(self, nstreams):
+        """work / work_device then take nstreams streams of noutput_items each, back to back; restarts the block"""
+        _check(self._fn("set_streams", [C.c_void_p, C.c_int])(self._h, int(nstreams)))
+        self._streams = int(nstreams)
+
+    def history(self):
+        return 1
+
+    def work(self, noutput_items, input_items):
+        """items are vectors of vlen; input_items holds streams x noutput_items of them"""
+        x = np.ascontiguousarray(input_items, dtype=self._in).reshape(-1)
+        need = noutput_items * self._streams * self._vlen
+        if len(x) < need:
+            raise ValueError("work needs %d input elements, got %d" % (need, len(x)))
+        out = np.zeros(need, dtype=np.float32)
+        r = _check(self._fn("work", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        return out[:r * self._streams * self._vlen]
+
+    def work_device(self, noutput_items, d_in, d_out, stream=None):
+        f = self._fn("work_device", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+        return _check(f(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out), _stream(stream)))
+
+
+class complex_to_mag_squared(_spectrum):
+    """gr.complex_to_mag_squared(vlen=1): re * re + im * im, unfused"""
+    _name = "complex_to_mag_squared"
+    _in = np.complex64
+
+    def __init__(self, vlen=1, device=0):
+        _spectrum.__init__(self, vlen)
+        _check(self._fn("create", [C.POINTER(C.c_void_p), C.c_int, C.c_int])(C.byref(self._h), int(vlen), int(device)))
+
+
+class single_pole_iir_filter_ff(_spectrum):
+    """gr.single_pole_iir_filter_ff(alpha, vlen=1): y = alpha x + (1 - alpha) y_prev per element, taps in double, state
+    in float; the state carries across work calls and set_taps keeps it"""
+    _name = "single_pole_iir_filter_ff"
+
+    def __init__(self, alpha, vlen=1, device=0):
+        _spectrum.__init__(self, vlen)
+        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_double, C.c_int, C.c_int])
+        _check(f(C.byref(self._h), float(alpha), int(vlen), int(device)))
+
+    def set_taps(self, alpha):
+        _check(self._fn("set_taps", [C.c_void_p, C.c_double])(self._h, float(alpha)))
+
+    @staticmethod
+    def chunk():
+        """items per chunk of the FAST mode's cut of the item axis"""
+        return lib().grhip_single_pole_iir_filter_ff_chunk()
+
+
+class nlog10_ff(_spectrum):
+    """gr.nlog10_ff(n=1, vlen=1, k=0): n * log10(max(x, 1e-18)) + k"""
+    _name = "nlog10_ff"
+
+    def __init__(self, n=1, vlen=1, k=0, device=0):
+        _spectrum.__init__(self, vlen)
+        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_float, C.c_int, C.c_float, C.c_int])
+        _check(f(C.byref(self._h), float(n), int(vlen), float(k), int(device)))
+
+
+class keep_one_in_n(_Block):
+    """gr.keep_one_in_n(item_size, n): work takes the input items as an array whose itemsize is item_size (or as bytes)
+    and returns the kept ones; the countdown carries across calls"""
+    _destroy = "grhip_keep_one_in_n_destroy"
+
+    def __init__(self, item_size, n, device=0):
+        _Block.__init__(self)
+        self._item = int(item_size)
+        self._streams = 1
+        L = lib()
+        L.grhip_keep_one_in_n_create.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_int, C.c_int]
+        _check(L.grhip_keep_one_in_n_create(C.byref(self._h), self._item, int(n), int(device)))
+
+    def set_n(self, n):
+        _check(lib().grhip_keep_one_in_n_set_n(self._h, int(n)))
+
+    def set_streams(self, nstreams):
+        _check(lib().grhip_keep_one_in_n_set_streams(self._h, int(nstreams)))
+        self._streams = int(nstreams)
+
+    def produced(self, n_in):
+        return _check(lib().grhip_keep_one_in_n_produced(self._h, int(n_in)))
+
+    def work(self, n_in, input_items):
+        x = np.ascontiguousarray(input_items)
+        raw = x.reshape(-1).view(np.uint8)
+        if len(raw) < n_in * self._streams * self._item:
+            raise ValueError("work needs %d input bytes, got %d" % (n_in * self._streams * self._item, len(raw)))
+        out = np.zeros(max(self.produced(n_in), 1) * self._streams * self._item, dtype=np.uint8)
+        L = lib()
+        L.grhip_keep_one_in_n_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        r = _check(L.grhip_keep_one_in_n_work(self._h, int(n_in), _ptr(raw), _ptr(out)))
+        out = out[:r * self._streams * self._item]
+        return out.view(x.dtype) if self._item % x.dtype.itemsize == 0 else out
+
+    def work_device(self, n_in, d_in, d_out, stream=None):
+        L = lib()
+        L.grhip_keep_one_in_n_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        return _check(L.grhip_keep_one_in_n_work_device(self._h, int(n_in), _devptr(d_in), _devptr(d_out), _stream(stream)))
 
 # ----------------------------------------------------------------------------
 # gr.interp_fir_filter_XXX / gr.rational_resampler_base_XXX  (filter/gr_interp_fir_filter_XXX.i.t,

@@ -24,6 +24,9 @@
 //   grhip_dc_blocker_ff / _cc                <- gr_dc_blocker_ff / _cc (filter/gr_dc_blocker_ff.h:60-100)
 //   grhip_moving_average_XX                  <- gr_moving_average_XX (gengen/gr_moving_average_XX.h.t)
 //   grhip_integrate_XX                       <- gr_integrate_XX (gengen/gr_integrate_XX.h.t)
+//   gr_make_complex_to_mag_squared, gr_make_single_pole_iir_filter_ff, gr_make_nlog10_ff, gr_make_keep_one_in_n
+//                                            <- the factories of the same names (general/gr_complex_to_xxx.h,
+//                                               filter/gr_single_pole_iir_filter_ff.h, general/gr_nlog10_ff.h, general/gr_keep_one_in_n.h)
 //
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
@@ -1200,3 +1203,94 @@ GRHIP_INTEGRATE_BLK(cc, gr_complex)
 GRHIP_INTEGRATE_BLK(ss, short)
 GRHIP_INTEGRATE_BLK(ii, int)
 #undef GRHIP_INTEGRATE_BLK
+
+// ---------------------------------------------------------------------------
+// gr_complex_to_mag_squared (vlen = 1), gr_single_pole_iir_filter_ff (alpha, vlen = 1), gr_nlog10_ff (n, vlen = 1, k = 0):
+// gr_sync_block, history 1 (general/gr_complex_to_xxx.cc:180-203, filter/gr_single_pole_iir_filter_ff.cc:32-81,
+// general/gr_nlog10_ff.cc:31-64).  gr_keep_one_in_n (item_size, n): gr_block, general_work
+// (general/gr_keep_one_in_n.cc:31-105).
+// ---------------------------------------------------------------------------
+#define GRHIP_SPECTRUM_BLK(NAME, IN_T, CTOR_ARGS, CTOR_DECL, CREATE_ARGS, EXTRA)                                       \
+    class grhip_##NAME##_blk;                                                                                          \
+    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                 \
+    class grhip_##NAME##_blk : public gr_sync_block {                                                                  \
+        grhip_##NAME *d_h = nullptr;                                                                                   \
+        grhip_##NAME##_blk CTOR_DECL                                                                                   \
+            : gr_sync_block(#NAME, gr_make_io_signature(1, 1, sizeof(IN_T) * (vlen ? vlen : 1)),                       \
+                            gr_make_io_signature(1, 1, sizeof(float) * (vlen ? vlen : 1)))                             \
+        {                                                                                                              \
+            grhip_detail::check(grhip_##NAME##_create CREATE_ARGS);                                                    \
+        }                                                                                                              \
+        friend grhip_##NAME##_sptr gr_make_##NAME CTOR_ARGS;                                                           \
+    public:                                                                                                            \
+        ~grhip_##NAME##_blk() { grhip_##NAME##_destroy(d_h); }                                                         \
+        void set_mode(int mode) { grhip_detail::check(grhip_##NAME##_set_mode(d_h, mode)); }                           \
+        EXTRA                                                                                                          \
+        int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override                  \
+        {                                                                                                              \
+            int r = grhip_##NAME##_work(d_h, noutput_items, in[0], out[0]);                                            \
+            grhip_detail::check(r);                                                                                    \
+            return r;                                                                                                  \
+        }                                                                                                              \
+    };
+GRHIP_SPECTRUM_BLK(complex_to_mag_squared, gr_complex, (unsigned int, int), (unsigned int vlen, int device),
+                   (&d_h, (int)vlen, device), )
+inline grhip_complex_to_mag_squared_sptr gr_make_complex_to_mag_squared(unsigned int vlen = 1, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_complex_to_mag_squared_blk(vlen, device));
+}
+GRHIP_SPECTRUM_BLK(single_pole_iir_filter_ff, float, (double, unsigned int, int), (double alpha, unsigned int vlen, int device),
+                   (&d_h, alpha, (int)vlen, device),
+                   void set_taps(double alpha) { grhip_detail::check(grhip_single_pole_iir_filter_ff_set_taps(d_h, alpha)); })
+inline grhip_single_pole_iir_filter_ff_sptr gr_make_single_pole_iir_filter_ff(double alpha, unsigned int vlen = 1, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_single_pole_iir_filter_ff_blk(alpha, vlen, device));
+}
+GRHIP_SPECTRUM_BLK(nlog10_ff, float, (float, unsigned, float, int), (float n, unsigned vlen, float k, int device),
+                   (&d_h, n, (int)vlen, k, device), )
+inline grhip_nlog10_ff_sptr gr_make_nlog10_ff(float n, unsigned vlen = 1, float k = 0, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_nlog10_ff_blk(n, vlen, k, device));
+}
+#undef GRHIP_SPECTRUM_BLK
+
+class grhip_keep_one_in_n_blk;
+typedef boost::shared_ptr<grhip_keep_one_in_n_blk> grhip_keep_one_in_n_sptr;
+class grhip_keep_one_in_n_blk : public gr_block {
+    grhip_keep_one_in_n *d_h = nullptr;
+    int d_n = 1;
+    grhip_keep_one_in_n_blk(size_t item_size, int n, int device)
+        : gr_block("keep_one_in_n", gr_make_io_signature(1, 1, (int)item_size), gr_make_io_signature(1, 1, (int)item_size))
+    {
+        grhip_detail::check(grhip_keep_one_in_n_create(&d_h, item_size, n, device));
+        set_n(n);
+    }
+    friend grhip_keep_one_in_n_sptr gr_make_keep_one_in_n(size_t, int, int);
+public:
+    ~grhip_keep_one_in_n_blk() { grhip_keep_one_in_n_destroy(d_h); }
+    void set_n(int n)
+    {
+        d_n = n < 1 ? 1 : n;
+        grhip_detail::check(grhip_keep_one_in_n_set_n(d_h, n));
+        set_relative_rate(1.0 / d_n);
+    }
+    // forecast is gr_block's own, as in the reference (it overrides none): a finite stream is consumed to its last item.
+    // as many inputs as there are, cut so that no more than noutput_items come out (gr_keep_one_in_n.cc:80)
+    int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
+                     gr_vector_void_star &out) override
+    {
+        int ni = ninput_items[0];
+        while (ni > 0 && grhip_keep_one_in_n_produced(d_h, ni) > noutput_items) {
+            const int over = grhip_keep_one_in_n_produced(d_h, ni) - noutput_items;
+            ni -= over > 1 ? (over - 1) * d_n : 1;
+        }
+        int r = ni > 0 ? grhip_keep_one_in_n_work(d_h, ni, in[0], out[0]) : 0;
+        grhip_detail::check(r);
+        consume_each(ni > 0 ? ni : 0);
+        return r;
+    }
+};
+inline grhip_keep_one_in_n_sptr gr_make_keep_one_in_n(size_t item_size, int n, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_keep_one_in_n_blk(item_size, n, device));
+}

@@ -1223,6 +1223,95 @@ GRHIP_API int grhip_integrate_ii_work_device(grhip_integrate_ii *h, int noutput_
                                                   const void *d_in, void *d_out, void *stream);
 
 /* ======================================================================
+ * The spectrum-estimate blocks: the stages of blks2.logpwrfft behind its transform
+ * (python/gnuradio/blks2impl/logpwrfft.py:47-63), each a block of its own.
+ * All of them take S streams back to back in `in` and `out` ([S][items], S = 1 after create;
+ * set_streams(S) restarts a block from the reference's initial state).  set_mode keeps the state.
+ *
+ * gr_complex_to_mag_squared
+ *   replaces gr_make_complex_to_mag_squared(unsigned int vlen = 1)
+ *   general/gr_complex_to_xxx.cc:180-203
+ * Items of vlen gr_complex in, vlen floats out: re * re + im * im as two rounded float products and
+ * one rounded add, never contracted.  Bit-exact in both modes (the modes do not differ).
+ * ====================================================================== */
+typedef struct grhip_complex_to_mag_squared grhip_complex_to_mag_squared;
+GRHIP_API int grhip_complex_to_mag_squared_create(grhip_complex_to_mag_squared **h, int vlen, int device);
+GRHIP_API void grhip_complex_to_mag_squared_destroy(grhip_complex_to_mag_squared *h);
+GRHIP_API int grhip_complex_to_mag_squared_set_mode(grhip_complex_to_mag_squared *h, int mode);
+GRHIP_API int grhip_complex_to_mag_squared_set_streams(grhip_complex_to_mag_squared *h, int nstreams);
+GRHIP_API int grhip_complex_to_mag_squared_work(grhip_complex_to_mag_squared *h, int noutput_items, const void *in,
+                                                void *out);
+GRHIP_API int grhip_complex_to_mag_squared_work_device(grhip_complex_to_mag_squared *h, int noutput_items,
+                                                       const void *d_in, void *d_out, void *stream);
+
+/* ======================================================================
+ * gr_single_pole_iir_filter_ff
+ *   replaces gr_make_single_pole_iir_filter_ff(double alpha, unsigned int vlen = 1)
+ *   filter/gr_single_pole_iir.h:60-97 (set_taps, filter), filter/gr_single_pole_iir_filter_ff.cc:53-81
+ * Items of vlen floats, one filter per element.  The taps are double and the state is a float:
+ * y = (float)(alpha * (double)x + (1.0 - alpha) * (double)y_prev), two double products and one
+ * double add, never contracted.  The state starts at 0, carries across calls, and set_taps keeps
+ * it.  GRHIP_ERANGE for alpha outside [0, 1] (create and set_taps; std::out_of_range there).
+ * GRHIP_MODE_GENERIC: one lane per (stream, element) walks the items in order; bit-exact for any
+ * vlen.  With vlen == 1 that is one lane per stream: correct and slow.
+ * GRHIP_MODE_FAST: the same kernel when streams x vlen is at least 65536 lanes (the device is full
+ * then); otherwise the item axis is cut into chunks of grhip_single_pole_iir_filter_ff_chunk() items:
+ * every chunk's answer from a zero start, the chunks chained through the recurrence's affine form
+ * (y_end = local_end + (1 - alpha)^len y_start), and a second walk from each chunk's true start.
+ * Within 1e-5 of the output's peak of the float64 recurrence.
+ * ====================================================================== */
+typedef struct grhip_single_pole_iir_filter_ff grhip_single_pole_iir_filter_ff;
+GRHIP_API int grhip_single_pole_iir_filter_ff_create(grhip_single_pole_iir_filter_ff **h, double alpha, int vlen,
+                                                     int device);
+GRHIP_API void grhip_single_pole_iir_filter_ff_destroy(grhip_single_pole_iir_filter_ff *h);
+GRHIP_API int grhip_single_pole_iir_filter_ff_set_taps(grhip_single_pole_iir_filter_ff *h, double alpha);
+GRHIP_API int grhip_single_pole_iir_filter_ff_set_mode(grhip_single_pole_iir_filter_ff *h, int mode);
+GRHIP_API int grhip_single_pole_iir_filter_ff_set_streams(grhip_single_pole_iir_filter_ff *h, int nstreams);
+GRHIP_API int grhip_single_pole_iir_filter_ff_chunk(void);
+GRHIP_API int grhip_single_pole_iir_filter_ff_work(grhip_single_pole_iir_filter_ff *h, int noutput_items,
+                                                   const void *in, void *out);
+GRHIP_API int grhip_single_pole_iir_filter_ff_work_device(grhip_single_pole_iir_filter_ff *h, int noutput_items,
+                                                          const void *d_in, void *d_out, void *stream);
+
+/* ======================================================================
+ * gr_nlog10_ff
+ *   replaces gr_make_nlog10_ff(float n, unsigned vlen = 1, float k = 0)
+ *   general/gr_nlog10_ff.cc:49-64
+ * out = n * log10(max(in, 1e-18f)) + k in float.  The device's log10f is not glibc's, so neither
+ * mode is bit-exact: both stay within 4 float ulps (at the output's magnitude) of the value computed
+ * in float64 from the same float input.  Zero and negative inputs give what the clamp gives,
+ * n * -18 + k; a NaN stays NaN (std::max returns its first argument then).
+ * ====================================================================== */
+typedef struct grhip_nlog10_ff grhip_nlog10_ff;
+GRHIP_API int grhip_nlog10_ff_create(grhip_nlog10_ff **h, float n, int vlen, float k, int device);
+GRHIP_API void grhip_nlog10_ff_destroy(grhip_nlog10_ff *h);
+GRHIP_API int grhip_nlog10_ff_set_mode(grhip_nlog10_ff *h, int mode);
+GRHIP_API int grhip_nlog10_ff_set_streams(grhip_nlog10_ff *h, int nstreams);
+GRHIP_API int grhip_nlog10_ff_work(grhip_nlog10_ff *h, int noutput_items, const void *in, void *out);
+GRHIP_API int grhip_nlog10_ff_work_device(grhip_nlog10_ff *h, int noutput_items, const void *d_in, void *d_out,
+                                          void *stream);
+
+/* ======================================================================
+ * gr_keep_one_in_n
+ *   replaces gr_make_keep_one_in_n(size_t item_size, int n)
+ *   general/gr_keep_one_in_n.cc:52-65 (set_n), 67-105 (general_work)
+ * A countdown starts at n, drops by one per input item, and the item at which it reaches 0 is
+ * copied out and reloads it.  set_n clamps n to >= 1 and reloads the countdown; the countdown
+ * carries across calls.  work / work_device take n_in input items (per stream) and return the items
+ * produced; `out` needs room for grhip_keep_one_in_n_produced(h, n_in) items, which tells the count
+ * without changing the state.  The streams share the countdown.  Tags are out of scope.
+ * ====================================================================== */
+typedef struct grhip_keep_one_in_n grhip_keep_one_in_n;
+GRHIP_API int grhip_keep_one_in_n_create(grhip_keep_one_in_n **h, size_t item_size, int n, int device);
+GRHIP_API void grhip_keep_one_in_n_destroy(grhip_keep_one_in_n *h);
+GRHIP_API int grhip_keep_one_in_n_set_n(grhip_keep_one_in_n *h, int n);
+GRHIP_API int grhip_keep_one_in_n_set_streams(grhip_keep_one_in_n *h, int nstreams);
+GRHIP_API int grhip_keep_one_in_n_produced(grhip_keep_one_in_n *h, int n_in);
+GRHIP_API int grhip_keep_one_in_n_work(grhip_keep_one_in_n *h, int n_in, const void *in, void *out);
+GRHIP_API int grhip_keep_one_in_n_work_device(grhip_keep_one_in_n *h, int n_in, const void *d_in, void *d_out,
+                                              void *stream);
+
+/* ======================================================================
  * gr_pfb_channelizer_ccf
  *   replaces gr_make_pfb_channelizer_ccf(unsigned numchans,
  *       const std::vector<float>& taps, float oversample_rate)
