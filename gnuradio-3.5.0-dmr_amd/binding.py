@@ -19,6 +19,7 @@ __all__ = [
     "dc_blocker_ff", "dc_blocker_cc", "moving_average_ff", "moving_average_cc", "moving_average_ss", "moving_average_ii",
     "integrate_ff", "integrate_cc", "integrate_ss", "integrate_ii",
     "complex_to_mag_squared", "single_pole_iir_filter_ff", "nlog10_ff", "keep_one_in_n",
+    "logpwrfft_c", "logpwrfft_f", "window_blackmanharris",
     "WIN_HAMMING", "WIN_HANN", "WIN_BLACKMAN", "WIN_RECTANGULAR", "WIN_KAISER", "WIN_BLACKMAN_hARRIS",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
     "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
@@ -1795,6 +1796,118 @@ class keep_one_in_n(_Block):
         L = lib()
         L.grhip_keep_one_in_n_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         return _check(L.grhip_keep_one_in_n_work_device(self._h, int(n_in), _devptr(d_in), _devptr(d_out), _stream(stream)))
+
+# ----------------------------------------------------------------------------
+# blks2.logpwrfft_c / logpwrfft_f (blks2impl/logpwrfft.py:26-154) and window.blackmanharris (gnuradio/window.py:166-176)
+# ----------------------------------------------------------------------------
+def window_blackmanharris(fft_size):
+    """window.blackmanharris(fft_size): the doubles of the reference's closure; host arithmetic only, no device needed"""
+    fft_size = int(fft_size)
+    if fft_size < 0 or fft_size > (1 << 26):
+        raise ValueError("fft_size out of range")
+    out = np.zeros(max(fft_size, 1), dtype=np.float64)
+    L = lib()
+    L.grhip_window_blackmanharris.argtypes = [C.c_int, C.c_void_p]
+    _raise_like_reference(L.grhip_window_blackmanharris(fft_size, _ptr(out)))
+    return out[:fft_size]
+
+
+class _logpwrfft(_Block):
+    """blks2.logpwrfft_X(sample_rate, fft_size, ref_scale, frame_rate, avg_alpha, average, win=None): win is the
+    reference's window FUNCTION (called with fft_size) or the sequence of doubles it would return.  work takes whole
+    frames of fft_size samples (streams back to back) and returns the kept frames' fft_size floats of dB each."""
+    _name = None
+    _in = None
+
+    def __init__(self, sample_rate, fft_size, ref_scale, frame_rate, avg_alpha, average, win=None, device=0):
+        _Block.__init__(self)
+        self._destroy = "grhip_%s_destroy" % self._name
+        self._n = int(fft_size)
+        self._streams = 1
+        if callable(win):
+            win = win(self._n)
+        w = None if win is None else np.ascontiguousarray(win, dtype=np.float64).reshape(-1)
+        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
+                                C.c_void_p, C.c_size_t, C.c_int])
+        _check(f(C.byref(self._h), float(sample_rate), self._n, float(ref_scale), float(frame_rate), float(avg_alpha),
+                 int(bool(average)), None if w is None else _ptr(w), 0 if w is None else len(w), int(device)))
+
+    def _fn(self, name, argtypes=None, restype=C.c_int):
+        f = getattr(lib(), "grhip_%s_%s" % (self._name, name))
+        if argtypes is not None:
+            f.argtypes = argtypes
+        f.restype = restype
+        return f
+
+    def set_mode(self, mode):
+        _check(self._fn("set_mode", [C.c_void_p, C.c_int])(self._h, int(mode)))
+
+    def set_streams(self, nstreams):
+        """work / work_device then take nstreams streams of n_frames each, back to back; restarts state and countdown"""
+        _check(self._fn("set_streams", [C.c_void_p, C.c_int])(self._h, int(nstreams)))
+        self._streams = int(nstreams)
+
+    def set_decimation(self, decim):
+        _check(self._fn("set_decimation", [C.c_void_p, C.c_double])(self._h, float(decim)))
+
+    def set_vec_rate(self, vec_rate):
+        _check(self._fn("set_vec_rate", [C.c_void_p, C.c_double])(self._h, float(vec_rate)))
+
+    def set_sample_rate(self, sample_rate):
+        _check(self._fn("set_sample_rate", [C.c_void_p, C.c_double])(self._h, float(sample_rate)))
+
+    def set_average(self, average):
+        _check(self._fn("set_average", [C.c_void_p, C.c_int])(self._h, int(bool(average))))
+
+    def set_avg_alpha(self, avg_alpha):
+        _check(self._fn("set_avg_alpha", [C.c_void_p, C.c_double])(self._h, float(avg_alpha)))
+
+    def sample_rate(self):
+        return self._fn("sample_rate", [C.c_void_p], C.c_double)(self._h)
+
+    def decimation(self):
+        return _check(self._fn("decimation", [C.c_void_p])(self._h))
+
+    def frame_rate(self):
+        return self._fn("frame_rate", [C.c_void_p], C.c_double)(self._h)
+
+    def average(self):
+        return bool(_check(self._fn("average", [C.c_void_p])(self._h)))
+
+    def avg_alpha(self):
+        return self._fn("avg_alpha", [C.c_void_p], C.c_double)(self._h)
+
+    def produced(self, n_frames):
+        return _check(self._fn("produced", [C.c_void_p, C.c_int])(self._h, int(n_frames)))
+
+    def state(self):
+        """the averaging filter's state: streams x fft_size floats of linear power"""
+        out = np.zeros(self._streams * self._n, dtype=np.float32)
+        _check(self._fn("state", [C.c_void_p, C.c_void_p])(self._h, _ptr(out)))
+        return out
+
+    def work(self, n_frames, input_items):
+        x = np.ascontiguousarray(input_items, dtype=self._in).reshape(-1)
+        need = n_frames * self._streams * self._n
+        if len(x) < need:
+            raise ValueError("work needs %d input samples, got %d" % (need, len(x)))
+        out = np.zeros(max(self.produced(n_frames), 1) * self._streams * self._n, dtype=np.float32)
+        r = _check(self._fn("work", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])(self._h, int(n_frames), _ptr(x), _ptr(out)))
+        return out[:r * self._streams * self._n]
+
+    def work_device(self, n_frames, d_in, d_out, stream=None):
+        f = self._fn("work_device", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+        return _check(f(self._h, int(n_frames), _devptr(d_in), _devptr(d_out), _stream(stream)))
+
+
+class logpwrfft_c(_logpwrfft):
+    _name = "logpwrfft_c"
+    _in = np.complex64
+
+
+class logpwrfft_f(_logpwrfft):
+    _name = "logpwrfft_f"
+    _in = np.float32
 
 # ----------------------------------------------------------------------------
 # gr.interp_fir_filter_XXX / gr.rational_resampler_base_XXX  (filter/gr_interp_fir_filter_XXX.i.t,

@@ -29,21 +29,6 @@ int check_alpha(double alpha)
 
 bool aligned(const void *p, size_t a) { return !((uintptr_t)p & (a - 1)); }
 
-// gr_keep_one_in_n.cc:80-90 in closed form.  count is the countdown before the call (1 .. n): the kept items are
-// count - 1, count - 1 + n, ...
-struct KeepOne {
-    long long n = 1, count = 1;
-    void set_n(long long v) { n = v < 1 ? 1 : v; count = n; }
-    long long first() const { return count - 1; }
-    long long produced(long long n_in) const { return n_in > first() ? (n_in - first() - 1) / n + 1 : 0; }
-    void advance(long long n_in)
-    {
-        const long long p = produced(n_in);
-        if (!p) count -= n_in;
-        else count = n - (n_in - 1 - (first() + (p - 1) * n));
-    }
-};
-
 }  // namespace
 
 // ---- the element-wise blocks and the IIR: items of vlen floats (mag^2: vlen complex in) ------------------------------

@@ -1,6 +1,7 @@
 // fft_kernels.h -- launchers for gr_fft_vcc and gr_pfb_channelizer_ccf (internal).
 #pragma once
 #include "grhip_internal.h"
+#include "logpwr_plan.h"
 #include <hip/hip_runtime.h>
 #include <memory>
 
@@ -16,6 +17,23 @@ bool fft_size_supported(int N);
 // gr_fft_vfc: the forward transform of N floats per item (no shift), the same kernels reading the floats directly
 int launch_fft_real(int N, const float *window, const float2 *twiddle, const float *in, float2 *out, long long nvec,
                     hipStream_t st);
+
+// What the register kernels (N = 32 ... 8192) store per bin, and the kept-frame addressing of the power / dB path:
+// blks2.logpwrfft's stream_to_vector_decimator, transform and complex_to_mag_squared (and, with FFT_OUT_DB, its
+// nlog10_ff(10, N, k)) in one pass (blks2impl/logpwrfft.py:47-63, stream_to_vector_decimator.py:45-48).
+enum FftOut { FFT_OUT_COMPLEX = 0, FFT_OUT_POWER = 1, FFT_OUT_DB = 2 };
+struct FftFrames {
+    long long n_frames = 0;     // frames per stream in the input
+    int n_out = 0;              // kept frames per stream
+    long long first = 0, n = 1; // kept frame o of a stream is its frame first + o n (keep_one_launch's convention)
+    float k = 0.f;              // FFT_OUT_DB: 10 log10f(max(power, 1e-18f)) + k
+    float *state = nullptr;     // FFT_OUT_DB: [S][N], receives the power of every stream's last kept frame (or null)
+};
+// Forward, windowed (window: device float[N], not null), no shift.  Output vector o of stream s is the transform of the
+// N samples (float2, or float with real_in) at ((s n_frames + first + o n) N) and goes to out + (s n_out + o) N as
+// N floats: power (two products and one add, as complex_to_mag_squared) or dB.  Only for shapes logpwr_fused_ok accepts.
+int launch_fft_power(int N, bool real_in, bool db, const float *window, const float2 *twiddle, const void *in, float *out,
+                     int nstreams, const FftFrames &fr, hipStream_t st);
 
 // A transform of ANY size the reference's gri_fft_complex accepts (general/gri_fft.cc:97-123), on top of launch_fft:
 // fft_any.hip.  `forward` is fixed at build time for the Bluestein kind (its transformed chirp depends on the sign);

@@ -6,6 +6,7 @@
 
 #include "device_math.h"
 #include "grhip_internal.h"
+#include "spectrum_math.h"
 
 namespace grhip {
 
@@ -230,10 +231,34 @@ __device__ __forceinline__ void dft16(float2 (&v)[16])
 // HBM latency runs under passes 2 and 3 and the stores.
 // (the window's sixteen values per lane are resident too: three workgroups per CU then, four otherwise)
 constexpr int fft4096_wg_per_cu(int mode) { return (mode & 1) ? 3 : 4; }
-template <bool FWD, int MODE, bool RIN = false>
-__global__ void __launch_bounds__(256, fft4096_wg_per_cu(MODE))
-fft4096_kernel(const float *__restrict__ window, const float2 *__restrict__ twiddle,
-               const float2 *__restrict__ in, float2 *__restrict__ out, int nvec)
+
+// ---- the power / dB store path of the three register families (blks2.logpwrfft, logpwrfft.py:47-63) ----------------------
+// OUT = FFT_OUT_POWER: a bin leaves as re * re + im * im, one float (mag_squared_val: what complex_to_mag_squared forms from
+// the stored complex point); FFT_OUT_DB: as nlog10_val(power, 10, k).  The input is then addressed by KEPT frame
+// (stream_to_vector_decimator.py:45-48 in front of the transform): output vector ov = s n_out + o reads the frame
+// s n_frames + first + o n and is stored at ov N floats.  FFT_OUT_DB with a state pointer: the lanes that transform the
+// last kept frame of a stream also leave its power in state[s][N] -- the single-pole IIR with taps 1.0.
+__device__ __forceinline__ long long fft_kept_frame(int ov, const FftFrames &f, int &s, int &o)
+{
+    s = ov / f.n_out;
+    o = ov - s * f.n_out;
+    return (long long)s * f.n_frames + f.first + (long long)o * f.n;
+}
+template <int OUT>
+__device__ __forceinline__ float fft_power_out(f32x2_t v, float k, float *state_bin)
+{
+    float p = mag_squared_val(v.x, v.y);
+    if (OUT == FFT_OUT_DB) {
+        if (state_bin) *state_bin = p;
+        p = nlog10_val(p, 10.f, k);
+    }
+    return p;
+}
+
+template <bool FWD, int MODE, bool RIN, int OUT>
+__device__ __forceinline__ void
+fft4096_body(const float *__restrict__ window, const float2 *__restrict__ twiddle,
+             const float2 *__restrict__ in, float2 *__restrict__ out, int nvec, const FftFrames &fr)
 {
     constexpr int N = 4096;
     __shared__ f32x2_t S[N + N / 16];
@@ -261,16 +286,18 @@ fft4096_kernel(const float *__restrict__ window, const float2 *__restrict__ twid
     // instruction's scalar offset): no 64-bit address registers beside the thirty-two points in flight
     typedef unsigned int fft_u32x2 __attribute__((ext_vector_type(2)));
     f32x2_t pre[16];
-    auto request = [&](int vec) __attribute__((always_inline)) {
+    auto request = [&](int vec_) __attribute__((always_inline)) {
+        int ks, ko;
+        const long long vec = OUT != FFT_OUT_COMPLEX ? fft_kept_frame(vec_, fr, ks, ko) : (long long)vec_;
         if (RIN) {                          // N floats per item (gr_fft_vfc.cc:85-94): 4 B per sample from HBM, (x, 0) in registers
             const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<float *>(reinterpret_cast<const float *>(in) + (long long)vec * N), 0, N * 4, 0x00020000);
+                const_cast<float *>(reinterpret_cast<const float *>(in) + vec * N), 0, N * 4, 0x00020000);
 #pragma unroll
             for (int q = 0; q < 16; ++q)
                 pre[q] = f32x2_t{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, 4 * t, 1024 * (q ^ SW_IN), 0)), 0.f};
             return;
         }
-        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(in + (long long)vec * N), 0, N * 8, 0x00020000);
+        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(in + vec * N), 0, N * 8, 0x00020000);
 #pragma unroll
         for (int q = 0; q < 16; ++q) {      // dst[k] = in[(k + N/2) mod N] when shifting
             // (bit-cast the whole vector: clang's __builtin_bit_cast of a vector ELEMENT reads element 0)
@@ -323,12 +350,39 @@ fft4096_kernel(const float *__restrict__ window, const float2 *__restrict__ twid
 #ifdef GRHIP_FFT_NOPRE
             if (vec + (int)gridDim.x < nvec) request(vec + gridDim.x);
 #endif
+            if (OUT != FFT_OUT_COMPLEX) {       // lane t holds X[t + 256 m]: 4-byte stores at 4 t + 1024 m, coalesced
+                const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float *>(out) + (long long)vec * N, 0, N * 4, 0x00020000);
+                int ks, ko;
+                (void)fft_kept_frame(vec, fr, ks, ko);
+                float *sb = (OUT == FFT_OUT_DB && fr.state && ko == fr.n_out - 1) ? fr.state + (long long)ks * N + t : nullptr;
+#pragma unroll
+                for (int m = 0; m < 16; ++m)
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, fft_power_out<OUT>(v[m], fr.k, sb ? sb + 256 * m : nullptr)),
+                                                          rp, 4 * t, 1024 * m, 0);
+                continue;
+            }
             const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(out + (long long)vec * N, 0, N * 8, 0x00020000);
 #pragma unroll
             for (int m = 0; m < 16; ++m)        // out[k] = fft[(k + N/2) mod N] when shifting
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(fft_u32x2, v[m]), r, 8 * t, 2048 * (m ^ SW_OUT), 0);
         }
     }
+}
+
+template <bool FWD, int MODE, bool RIN = false>
+__global__ void __launch_bounds__(256, fft4096_wg_per_cu(MODE))
+fft4096_kernel(const float *__restrict__ window, const float2 *__restrict__ twiddle,
+               const float2 *__restrict__ in, float2 *__restrict__ out, int nvec)
+{
+    fft4096_body<FWD, MODE, RIN, FFT_OUT_COMPLEX>(window, twiddle, in, out, nvec, FftFrames{});
+}
+// forward, windowed, no shift; nvec = streams x kept frames
+template <bool RIN, int OUT>
+__global__ void __launch_bounds__(256, fft4096_wg_per_cu(1))
+fft4096_power_kernel(const float *__restrict__ window, const float2 *__restrict__ twiddle,
+                     const float2 *__restrict__ in, float2 *__restrict__ out, int nvec, const FftFrames fr)
+{
+    fft4096_body<true, 1, RIN, OUT>(window, twiddle, in, out, nvec, fr);
 }
 
 template <bool FWD>
@@ -1289,10 +1343,10 @@ __device__ __forceinline__ void dft8(f32x2_t &x0, f32x2_t &x1, f32x2_t &x2, f32x
     x3 = e3 + o3; x7 = e3 - o3;
 }
 
-template <int N, bool FWD, int MODE, bool RIN = false>
-__global__ void __launch_bounds__(256, 3)
-fft16x_kernel(const float *__restrict__ window, const float2 *__restrict__ twiddle, const float2 *__restrict__ in,
-              float2 *__restrict__ out, int nvec)
+template <int N, bool FWD, int MODE, bool RIN, int OUT>
+__device__ __forceinline__ void
+fft16x_body(const float *__restrict__ window, const float2 *__restrict__ twiddle, const float2 *__restrict__ in,
+            float2 *__restrict__ out, int nvec, const FftFrames &fr)
 {
     constexpr int LPV = N / 16;                 // lanes per vector
     constexpr int VPG = 256 / LPV;              // vectors per workgroup step
@@ -1335,6 +1389,29 @@ fft16x_kernel(const float *__restrict__ window, const float2 *__restrict__ twidd
     const long long ngroups = ((long long)nvec + VPG - 1) / VPG;
     f32x2_t pre[16];
     auto request = [&](long long grp) __attribute__((always_inline)) {
+        if (OUT != FFT_OUT_COMPLEX) {
+            // Kept frames: the vectors of a group are n frames apart and the group may run over the end of a stream.  The
+            // descriptor starts at the group's first frame and ends behind its last valid one (both wave-uniform); a lane's
+            // offset is its own frame's distance from the first.  logpwr_fused_ok (logpwr_plan.h) has made sure that the
+            // range is below 2^31 bytes, so no offset wraps; a lane past the last vector gets the range itself as its
+            // offset and reads zeros.
+            constexpr int ITEM = RIN ? 4 : 8;
+            const int ov0 = (int)(grp * VPG), ovl = ov0 + VPG - 1 < nvec - 1 ? ov0 + VPG - 1 : nvec - 1;
+            int ks, ko;
+            const long long f0 = fft_kept_frame(ov0, fr, ks, ko), fl = fft_kept_frame(ovl, fr, ks, ko);
+            const unsigned range = (unsigned)((fl - f0 + 1) * (long long)(N * ITEM));
+            const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<char *>(reinterpret_cast<const char *>(in) + f0 * (long long)(N * ITEM)), 0, (int)range, 0x00020000);
+            const int ov = ov0 + vl;
+            unsigned voff = range;
+            if (ov <= ovl) voff = (unsigned)((fft_kept_frame(ov, fr, ks, ko) - f0) * (long long)(N * ITEM)) + ITEM * l;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                if (RIN) pre[q] = f32x2_t{__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rk, voff, 4 * LPV * q, 0)), 0.f};
+                else pre[q] = __builtin_bit_cast(f32x2_t, __builtin_amdgcn_raw_buffer_load_b64(rk, voff, 8 * LPV * q, 0));
+            }
+            return;
+        }
         const long long vec = grp * VPG + vl;
         // (a whole group through one descriptor: vectors past nvec are out of its range)
         const long long left = ((long long)nvec - grp * VPG) * (long long)(N * 8);
@@ -1387,6 +1464,23 @@ fft16x_kernel(const float *__restrict__ window, const float2 *__restrict__ twidd
                                                                            (int)(left < (long long)VPG * N * 8 ? left : (long long)VPG * N * 8), 0x00020000);
         (void)vec;
         const int j2 = (l - (l & 15)) * 16 + (l & 15);          // pass 2 writes element j2 + 16 m
+        // power / dB: the group's output vectors are contiguous floats, 4-byte stores through a descriptor clipped as yr is
+        const long long leftp = ((long long)nvec - grp * VPG) * (long long)(N * 4);
+        const __amdgpu_buffer_rsrc_t yp = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float *>(out) + grp * VPG * (long long)N, 0,
+                                                                           (int)(leftp < (long long)VPG * N * 4 ? leftp : (long long)VPG * N * 4), 0x00020000);
+        float *sb = nullptr;            // this lane's vector is the last kept frame of its stream: its power is the IIR's state
+        if (OUT == FFT_OUT_DB && fr.state && vec < nvec) {
+            int ks, ko;
+            (void)fft_kept_frame((int)vec, fr, ks, ko);
+            if (ko == fr.n_out - 1) sb = fr.state + (long long)ks * N;
+        }
+        if (OUT != FFT_OUT_COMPLEX && TWO && R3 == 1) {
+#pragma unroll
+            for (int m = 0; m < 16; ++m)
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, fft_power_out<OUT>(v[m], fr.k, sb ? sb + j2 + 16 * m : nullptr)),
+                                                      yp, 4 * (vl * N + j2), 4 * 16 * m, 0);
+            continue;
+        }
         if (TWO && R3 == 1) {
             // N = 256: pass 2 is the last one; a shift by N / 2 = 128 = 16 * 8 is m ^ 8
 #pragma unroll
@@ -1415,12 +1509,34 @@ fft16x_kernel(const float *__restrict__ window, const float2 *__restrict__ twidd
             if (R3 == 8) dft8<FWD>(v[b], v[b + NB3], v[b + 2 * NB3], v[b + 3 * NB3], v[b + 4 * NB3], v[b + 5 * NB3], v[b + 6 * NB3], v[b + 7 * NB3]);
             // output m of the butterfly is element j + P3 m, i = l + LPV b, k = i mod P3, j = (i - k) R3 + k
             const int i = l + LPV * b, k = i & (P3 - 1), j = (i - k) * R3 + k;
+            if (OUT != FFT_OUT_COMPLEX) {
+#pragma unroll
+                for (int m = 0; m < R3; ++m)
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, fft_power_out<OUT>(v[b + NB3 * m], fr.k, sb ? sb + j + P3 * m : nullptr)),
+                                                          yp, 4 * (vl * N + j), 4 * P3 * m, 0);
+                continue;
+            }
 #pragma unroll
             for (int m = 0; m < R3; ++m)
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, v[b + NB3 * m]), yr, 8 * (vl * N + j),
                                                       8 * P3 * (m ^ (SHIFT_OUT ? R3 / 2 : 0)), 0);
         }
     }
+}
+
+template <int N, bool FWD, int MODE, bool RIN = false>
+__global__ void __launch_bounds__(256, 3)
+fft16x_kernel(const float *__restrict__ window, const float2 *__restrict__ twiddle, const float2 *__restrict__ in,
+              float2 *__restrict__ out, int nvec)
+{
+    fft16x_body<N, FWD, MODE, RIN, FFT_OUT_COMPLEX>(window, twiddle, in, out, nvec, FftFrames{});
+}
+template <int N, bool RIN, int OUT>
+__global__ void __launch_bounds__(256, 3)
+fft16x_power_kernel(const float *__restrict__ window, const float2 *__restrict__ twiddle, const float2 *__restrict__ in,
+                    float2 *__restrict__ out, int nvec, const FftFrames fr)
+{
+    fft16x_body<N, true, 1, RIN, OUT>(window, twiddle, in, out, nvec, fr);
 }
 
 template <int N, bool FWD>
@@ -1469,10 +1585,12 @@ static int launch_fft16x(int N, int forward, int shift, const float *window, con
 // twiddles (table entries 2m) and the sixteen combine twiddles W^{t + 256 m} of the lane resident.
 // MODE as fft4096_kernel: bit 0 window, bit 1 shift (a shift by N/2 swaps the two output halves / is q ^ 8 on the way in).
 // ===========================================================================
-template <bool FWD, int MODE, bool RIN = false>
+// (OUT and fr: the power / dB store path, see fft4096_body; here the kernel itself carries them -- behind a wrapper the
+// windowed complex instantiations came out four registers larger)
+template <bool FWD, int MODE, bool RIN = false, int OUT = FFT_OUT_COMPLEX>
 __global__ void __launch_bounds__(256, (MODE & 1) ? 2 : 3)      // (the window's values in flight beside the points: two per CU)
 fft8192_kernel(const float *__restrict__ window, const float2 *__restrict__ twiddle, const float2 *__restrict__ in,
-               float2 *__restrict__ out, int nvec)
+               float2 *__restrict__ out, int nvec, const FftFrames fr)
 {
     constexpr int N = 8192, H = 4096;
     __shared__ f32x2_t S[H + H / 16];
@@ -1493,9 +1611,11 @@ fft8192_kernel(const float *__restrict__ window, const float2 *__restrict__ twid
         W2[(t >> 4) * 17 + (t & 15)] = f32x2_t{w.x, w.y};              // visible after the first barrier of the loop
     }
     for (int vec = blockIdx.x; vec < nvec; vec += gridDim.x) {
+        int ks = 0, ko = 0;
+        const long long vin = OUT != FFT_OUT_COMPLEX ? fft_kept_frame(vec, fr, ks, ko) : (long long)vec;
         const __amdgpu_buffer_rsrc_t xr = RIN
-            ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(reinterpret_cast<const float *>(in) + (long long)vec * N), 0, N * 4, 0x00020000)
-            : __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(in + (long long)vec * N), 0, N * 8, 0x00020000);
+            ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(reinterpret_cast<const float *>(in) + vin * N), 0, N * 4, 0x00020000)
+            : __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(in + vin * N), 0, N * 8, 0x00020000);
         f32x2_t ve[16], vo[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) {       // samples 2j, 2j + 1, j = t + 256 (q ^ SW_IN)
@@ -1518,6 +1638,18 @@ fft8192_kernel(const float *__restrict__ window, const float2 *__restrict__ twid
         fft4096_mid_passes<FWD>(ve, S, W2, w3, t);          // ve[m] = E[t + 256 m]
         dft16<FWD>(vo);
         fft4096_mid_passes<FWD>(vo, S, W2, w3, t);          // vo[m] = O[t + 256 m]
+        if (OUT != FFT_OUT_COMPLEX) {
+            const __amdgpu_buffer_rsrc_t yp = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float *>(out) + (long long)vec * N, 0, N * 4, 0x00020000);
+            float *sb = (OUT == FFT_OUT_DB && fr.state && ko == fr.n_out - 1) ? fr.state + (long long)ks * N + t : nullptr;
+#pragma unroll
+            for (int m = 0; m < 16; ++m) {
+                const f32x2_t p = cmul_pk(vo[m], wc[m]);
+                const f32x2_t lo = ve[m] + p, hi = ve[m] - p;   // X[k], X[k + 4096], k = t + 256 m
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, fft_power_out<OUT>(lo, fr.k, sb ? sb + 256 * m : nullptr)), yp, 4 * t, 1024 * m, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, fft_power_out<OUT>(hi, fr.k, sb ? sb + H + 256 * m : nullptr)), yp, 4 * t + 4 * H, 1024 * m, 0);
+            }
+            continue;
+        }
         const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(out + (long long)vec * N, 0, N * 8, 0x00020000);
 #pragma unroll
         for (int m = 0; m < 16; ++m) {
@@ -1537,10 +1669,10 @@ static void launch_fft8192_t(int shift, const float *window, const float2 *twidd
     const dim3 grid((unsigned)(nvec < cap ? nvec : cap));
     const int nv = (int)nvec;
     switch ((window ? 1 : 0) | (shift ? 2 : 0)) {
-    case 0: hipLaunchKernelGGL((fft8192_kernel<FWD, 0>), grid, dim3(256), 0, st, window, twiddle, in, out, nv); break;
-    case 1: hipLaunchKernelGGL((fft8192_kernel<FWD, 1>), grid, dim3(256), 0, st, window, twiddle, in, out, nv); break;
-    case 2: hipLaunchKernelGGL((fft8192_kernel<FWD, 2>), grid, dim3(256), 0, st, window, twiddle, in, out, nv); break;
-    default: hipLaunchKernelGGL((fft8192_kernel<FWD, 3>), grid, dim3(256), 0, st, window, twiddle, in, out, nv); break;
+    case 0: hipLaunchKernelGGL((fft8192_kernel<FWD, 0>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, FftFrames{}); break;
+    case 1: hipLaunchKernelGGL((fft8192_kernel<FWD, 1>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, FftFrames{}); break;
+    case 2: hipLaunchKernelGGL((fft8192_kernel<FWD, 2>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, FftFrames{}); break;
+    default: hipLaunchKernelGGL((fft8192_kernel<FWD, 3>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, FftFrames{}); break;
     }
 }
 
@@ -1567,8 +1699,8 @@ int launch_fft_real(int N, const float *window, const float2 *twiddle, const flo
     if (N == 8192) {
         const long long cap = (window ? 2LL : 3LL) * device_cus();
         const dim3 grid((unsigned)(nvec < cap ? nvec : cap));
-        if (window) hipLaunchKernelGGL((fft8192_kernel<true, 1, true>), grid, dim3(256), 0, st, window, twiddle, in, out, nv);
-        else hipLaunchKernelGGL((fft8192_kernel<true, 0, true>), grid, dim3(256), 0, st, window, twiddle, in, out, nv);
+        if (window) hipLaunchKernelGGL((fft8192_kernel<true, 1, true>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, FftFrames{});
+        else hipLaunchKernelGGL((fft8192_kernel<true, 0, true>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, FftFrames{});
     } else if (N == 4096) {
         const long long cap = (long long)fft4096_wg_per_cu(window ? 1 : 0) * device_cus();
         const dim3 grid((unsigned)(nvec < cap ? nvec : cap));
@@ -1595,6 +1727,54 @@ int launch_fft_real(int N, const float *window, const float2 *twiddle, const flo
         if (int rc = allow_lds((const void *)fft_kernel<true, true>, lds)) return rc;
         hipLaunchKernelGGL((fft_kernel<true, true>), dim3((unsigned)nvec), dim3(64), lds, st, N, 0, window, twiddle, in, out);
     }
+    GRHIP_HIP(hipGetLastError());
+    return GRHIP_OK;
+}
+
+// blks2.logpwrfft's transform with the stages around it folded in (logpwrfft.py:47-63): kept frames in, power or dB out.
+// Only what that block can reach exists: forward, windowed, no shift, N = 32 ... 8192.  The caller has asked
+// logpwr_fused_ok about the addressing.
+int launch_fft_power(int N, bool real_in, bool db, const float *window, const float2 *twiddle, const void *in_v, float *out_f,
+                     int nstreams, const FftFrames &fr, hipStream_t st)
+{
+    const long long nvec = (long long)nstreams * fr.n_out;
+    if (nvec <= 0) return GRHIP_OK;
+    if (!window || !logpwr_native_size(N)) return fail(GRHIP_EINVAL, "fft_power: no kernel for this shape");
+    if (!logpwr_fused_ok(N, real_in ? 4 : 8, nstreams, fr.n_frames, fr.n_out, fr.n))
+        return fail(GRHIP_EINVAL, "fft_power: kept frames out of the kernels' reach");
+    const float2 *in = reinterpret_cast<const float2 *>(in_v);
+    float2 *out = reinterpret_cast<float2 *>(out_f);
+    const int nv = (int)nvec;
+#define GRHIP_FFT_POWER(KERNEL, ...) do { \
+        if (real_in) { if (db) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ true, FFT_OUT_DB>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, fr); \
+                       else hipLaunchKernelGGL((KERNEL<__VA_ARGS__ true, FFT_OUT_POWER>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, fr); } \
+        else { if (db) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, FFT_OUT_DB>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, fr); \
+               else hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, FFT_OUT_POWER>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, fr); } } while (0)
+    if (N == 8192) {
+        const long long cap = 2LL * device_cus();
+        const dim3 grid((unsigned)(nvec < cap ? nvec : cap));
+        if (real_in) { if (db) hipLaunchKernelGGL((fft8192_kernel<true, 1, true, FFT_OUT_DB>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, fr);
+                       else hipLaunchKernelGGL((fft8192_kernel<true, 1, true, FFT_OUT_POWER>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, fr); }
+        else { if (db) hipLaunchKernelGGL((fft8192_kernel<true, 1, false, FFT_OUT_DB>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, fr);
+               else hipLaunchKernelGGL((fft8192_kernel<true, 1, false, FFT_OUT_POWER>), grid, dim3(256), 0, st, window, twiddle, in, out, nv, fr); }
+    } else if (N == 4096) {
+        const long long cap = (long long)fft4096_wg_per_cu(1) * device_cus();
+        const dim3 grid((unsigned)(nvec < cap ? nvec : cap));
+        GRHIP_FFT_POWER(fft4096_power_kernel, );
+    } else {
+        const long long vpg = 4096 / N, ngroups = (nvec + vpg - 1) / vpg, cap = 3LL * device_cus();
+        const dim3 grid((unsigned)(ngroups < cap ? ngroups : cap));
+        switch (N) {
+        case 32: GRHIP_FFT_POWER(fft16x_power_kernel, 32,); break;
+        case 64: GRHIP_FFT_POWER(fft16x_power_kernel, 64,); break;
+        case 128: GRHIP_FFT_POWER(fft16x_power_kernel, 128,); break;
+        case 256: GRHIP_FFT_POWER(fft16x_power_kernel, 256,); break;
+        case 512: GRHIP_FFT_POWER(fft16x_power_kernel, 512,); break;
+        case 1024: GRHIP_FFT_POWER(fft16x_power_kernel, 1024,); break;
+        default: GRHIP_FFT_POWER(fft16x_power_kernel, 2048,); break;
+        }
+    }
+#undef GRHIP_FFT_POWER
     GRHIP_HIP(hipGetLastError());
     return GRHIP_OK;
 }

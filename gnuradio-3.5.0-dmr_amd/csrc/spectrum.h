@@ -23,6 +23,21 @@ int nlog10_launch(const float *in, float *out, long long count, float n, float k
 int keep_one_launch(const void *in, void *out, size_t item_size, long long n_in, long long n_out, long long first,
                     long long n, int nstreams, hipStream_t st);
 
+// gr_keep_one_in_n.cc:80-90 in closed form.  count is the countdown before the call (1 .. n): the kept items are
+// count - 1, count - 1 + n, ...
+struct KeepOne {
+    long long n = 1, count = 1;
+    void set_n(long long v) { n = v < 1 ? 1 : v; count = n; }
+    long long first() const { return count - 1; }
+    long long produced(long long n_in) const { return n_in > first() ? (n_in - first() - 1) / n + 1 : 0; }
+    void advance(long long n_in)
+    {
+        const long long p = produced(n_in);
+        if (!p) count -= n_in;
+        else count = n - (n_in - 1 - (first() + (p - 1) * n));
+    }
+};
+
 // y = (float)(alpha * (double)x + (1.0 - alpha) * (double)y_prev) along the item axis of [S][n][vlen], one float of
 // state per (stream, element) (filter/gr_single_pole_iir.h:87-97); in may be out.
 struct IirLaunch {
@@ -32,6 +47,9 @@ struct IirLaunch {
     int nstreams, vlen;
     double alpha;
     float *state;           // [S][vlen]
+    // the outputs written as log_n * log10f(max(y, 1e-18f)) + log_k (gr_nlog10_ff.cc:60-61) instead of y; the state stays y
+    bool log = false;
+    float log_n = 1.f, log_k = 0.f;
 };
 // chunked: cut the item axis (FAST with few lanes); scratch then holds the chunks' end values and carries
 bool iir_chunked(bool fast, const IirLaunch &a);

@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "spectrum.h"
+#include "spectrum_math.h"
 
 namespace grhip {
 
@@ -21,18 +22,12 @@ unsigned blocks_for(long long n)
     return (unsigned)(b < 1 ? 1 : b > MAX_BLOCKS ? MAX_BLOCKS : b);
 }
 
-__device__ __forceinline__ float nlog10_val(float x, float n, float k)
-{
-    const float m = x < 1e-18f ? 1e-18f : x;            // std::max(in, 1e-18f): a NaN input stays NaN
-    return __fadd_rn(__fmul_rn(n, log10f(m)), k);
-}
-
 __global__ void __launch_bounds__(THREADS)
 mag_squared_kernel(const float2 *__restrict__ in, float *__restrict__ out, long long n)
 {
     for (long long i = blockIdx.x * (long long)THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * THREADS) {
         const float2 v = in[i];
-        out[i] = __fadd_rn(__fmul_rn(v.x, v.x), __fmul_rn(v.y, v.y));
+        out[i] = mag_squared_val(v.x, v.y);
     }
 }
 
@@ -61,10 +56,12 @@ keep_one_kernel(const W *__restrict__ in, W *__restrict__ out, long long words, 
 //   ENDS: start from 0, write nothing but the value after the chunk (ends[chunk][lane]): the chunk's local answer.
 //   else: start from start[chunk][lane] (the state itself when there is one chunk), write every y, and the last chunk
 //         stores the state.
-template <bool ENDS>
+//   LOG (not with ENDS): what is written is nlog10_val(y, log_n, log_k) of every y (the last two stages of
+//         blks2.logpwrfft in one pass, logpwrfft.py:58-63); the recurrence and the stored state stay linear.
+template <bool ENDS, bool LOG = false>
 __global__ void __launch_bounds__(THREADS)
 iir_walk_kernel(const float *in, float *out, long long n, int lanes, int vlen, long long chunk, int nchunks,
-                double alpha, double oma, const float *start, float *ends, float *state)
+                double alpha, double oma, const float *start, float *ends, float *state, float log_n, float log_k)
 {
     const long long id = blockIdx.x * (long long)THREADS + threadIdx.x;
     if (id >= (long long)lanes * nchunks) return;
@@ -86,7 +83,7 @@ iir_walk_kernel(const float *in, float *out, long long n, int lanes, int vlen, l
         for (int i = 0; i < 4; ++i) {
             if (j + i < j1) {
                 y = (float)__dadd_rn(__dmul_rn(alpha, (double)xa[i]), __dmul_rn(oma, (double)y));
-                if (!ENDS) q[(long long)i * vlen] = y;
+                if (!ENDS) q[(long long)i * vlen] = LOG ? nlog10_val(y, log_n, log_k) : y;
             }
         }
         q += 4LL * vlen;
@@ -157,8 +154,12 @@ static int walk(const IirLaunch &a, int lanes, long long chunk, int nchunks, con
 {
     const long long blocks = ((long long)lanes * nchunks + THREADS - 1) / THREADS;
     if (blocks > 0x7fffffffLL) return fail(GRHIP_EINVAL, "single_pole_iir: too many lanes in one call");
-    hipLaunchKernelGGL((iir_walk_kernel<ENDS>), dim3((unsigned)blocks), dim3(THREADS), 0, st, a.in, a.out, a.n, lanes,
-                       a.vlen, chunk, nchunks, a.alpha, 1.0 - a.alpha, start, ends, a.state);
+    if (!ENDS && a.log)
+        hipLaunchKernelGGL((iir_walk_kernel<false, true>), dim3((unsigned)blocks), dim3(THREADS), 0, st, a.in, a.out, a.n, lanes,
+                           a.vlen, chunk, nchunks, a.alpha, 1.0 - a.alpha, start, ends, a.state, a.log_n, a.log_k);
+    else
+        hipLaunchKernelGGL((iir_walk_kernel<ENDS>), dim3((unsigned)blocks), dim3(THREADS), 0, st, a.in, a.out, a.n, lanes,
+                           a.vlen, chunk, nchunks, a.alpha, 1.0 - a.alpha, start, ends, a.state, 0.f, 0.f);
     GRHIP_HIP(hipGetLastError());
     return GRHIP_OK;
 }

@@ -27,6 +27,7 @@
 //   gr_make_complex_to_mag_squared, gr_make_single_pole_iir_filter_ff, gr_make_nlog10_ff, gr_make_keep_one_in_n
 //                                            <- the factories of the same names (general/gr_complex_to_xxx.h,
 //                                               filter/gr_single_pole_iir_filter_ff.h, general/gr_nlog10_ff.h, general/gr_keep_one_in_n.h)
+//   gr_make_logpwrfft_c / _f                 <- blks2.logpwrfft_c / _f (python/gnuradio/blks2impl/logpwrfft.py:26-154)
 //
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
@@ -1294,3 +1295,73 @@ inline grhip_keep_one_in_n_sptr gr_make_keep_one_in_n(size_t item_size, int n, i
 {
     return gnuradio::get_initial_sptr(new grhip_keep_one_in_n_blk(item_size, n, device));
 }
+
+// ---------------------------------------------------------------------------
+// blks2.logpwrfft_c / logpwrfft_f (blks2impl/logpwrfft.py:26-154; a hier block there: stream_to_vector_decimator ->
+// fft_vcc | fft_vfc -> complex_to_mag_squared -> single_pole_iir_filter_ff -> nlog10_ff), here one gr_block: items of one
+// sample in, fft_size floats out, relative rate 1 / (fft_size decimation).  The reference's argument order and its
+// setter and getter names; `win` is what the reference's window function returns for fft_size (doubles; empty: the
+// default, window.blackmanharris).
+// ---------------------------------------------------------------------------
+#define GRHIP_LOGPWRFFT_BLK(NAME, IN_T)                                                                                \
+    class grhip_##NAME##_blk;                                                                                          \
+    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                 \
+    class grhip_##NAME##_blk : public gr_block {                                                                       \
+        grhip_##NAME *d_h = nullptr;                                                                                   \
+        int d_fft_size;                                                                                                \
+        grhip_##NAME##_blk(double sample_rate, int fft_size, double ref_scale, double frame_rate, double avg_alpha,    \
+                           bool average, const std::vector<double> &win, int device)                                   \
+            : gr_block(#NAME, gr_make_io_signature(1, 1, sizeof(IN_T)),                                                \
+                       gr_make_io_signature(1, 1, sizeof(float) * (fft_size > 0 ? fft_size : 1))),                     \
+              d_fft_size(fft_size)                                                                                     \
+        {                                                                                                              \
+            grhip_detail::check(grhip_##NAME##_create(&d_h, sample_rate, fft_size, ref_scale, frame_rate, avg_alpha,   \
+                                                      average, win.data(), win.size(), device));                       \
+            update_rate();                                                                                             \
+        }                                                                                                              \
+        void update_rate() { set_relative_rate(1.0 / ((double)d_fft_size * decimation())); }                           \
+        friend grhip_##NAME##_sptr gr_make_##NAME(double, int, double, double, double, bool, const std::vector<double> &, int); \
+    public:                                                                                                            \
+        ~grhip_##NAME##_blk() { grhip_##NAME##_destroy(d_h); }                                                         \
+        void set_mode(int mode) { grhip_detail::check(grhip_##NAME##_set_mode(d_h, mode)); }                           \
+        void set_decimation(double decim) { grhip_detail::check(grhip_##NAME##_set_decimation(d_h, decim)); update_rate(); } \
+        void set_vec_rate(double r) { grhip_detail::check(grhip_##NAME##_set_vec_rate(d_h, r)); update_rate(); }       \
+        void set_sample_rate(double r) { grhip_detail::check(grhip_##NAME##_set_sample_rate(d_h, r)); update_rate(); } \
+        void set_average(bool average) { grhip_detail::check(grhip_##NAME##_set_average(d_h, average)); }              \
+        void set_avg_alpha(double a) { grhip_detail::check(grhip_##NAME##_set_avg_alpha(d_h, a)); }                    \
+        double sample_rate() const { return grhip_##NAME##_sample_rate(d_h); }                                         \
+        int decimation() const { return grhip_##NAME##_decimation(d_h); }                                              \
+        double frame_rate() const { return grhip_##NAME##_frame_rate(d_h); }                                           \
+        bool average() const { return grhip_##NAME##_average(d_h) != 0; }                                              \
+        double avg_alpha() const { return grhip_##NAME##_avg_alpha(d_h); }                                             \
+        /* one whole frame per output at least (stream_to_vector is a decimator by fft_size) */                        \
+        void forecast(int noutput_items, gr_vector_int &req) override                                                  \
+        {                                                                                                              \
+            for (size_t i = 0; i < req.size(); i++) req[i] = noutput_items * d_fft_size;                               \
+        }                                                                                                              \
+        /* as many whole frames as there are, cut so that no more than noutput_items come out (gr_keep_one_in_n.cc:80) */ \
+        int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,                \
+                         gr_vector_void_star &out) override                                                            \
+        {                                                                                                              \
+            const int n = decimation();                                                                                \
+            int nf = ninput_items[0] / d_fft_size;                                                                     \
+            while (nf > 0 && grhip_##NAME##_produced(d_h, nf) > noutput_items) {                                       \
+                const int over = grhip_##NAME##_produced(d_h, nf) - noutput_items;                                     \
+                nf -= over > 1 ? (over - 1) * n : 1;                                                                   \
+            }                                                                                                          \
+            int r = nf > 0 ? grhip_##NAME##_work(d_h, nf, in[0], out[0]) : 0;                                          \
+            grhip_detail::check(r);                                                                                    \
+            consume_each(nf > 0 ? nf * d_fft_size : 0);                                                                \
+            return r;                                                                                                  \
+        }                                                                                                              \
+    };                                                                                                                 \
+    inline grhip_##NAME##_sptr gr_make_##NAME(double sample_rate, int fft_size, double ref_scale, double frame_rate,   \
+                                              double avg_alpha, bool average,                                          \
+                                              const std::vector<double> &win = std::vector<double>(), int device = 0)  \
+    {                                                                                                                  \
+        return gnuradio::get_initial_sptr(                                                                             \
+            new grhip_##NAME##_blk(sample_rate, fft_size, ref_scale, frame_rate, avg_alpha, average, win, device));    \
+    }
+GRHIP_LOGPWRFFT_BLK(logpwrfft_c, gr_complex)
+GRHIP_LOGPWRFFT_BLK(logpwrfft_f, float)
+#undef GRHIP_LOGPWRFFT_BLK

@@ -1312,6 +1312,99 @@ GRHIP_API int grhip_keep_one_in_n_work_device(grhip_keep_one_in_n *h, int n_in, 
                                               void *stream);
 
 /* ======================================================================
+ * blks2.logpwrfft_c / blks2.logpwrfft_f
+ *   replaces logpwrfft_c(sample_rate, fft_size, ref_scale, frame_rate, avg_alpha, average, win=None)
+ *   gnuradio-core/src/python/gnuradio/blks2impl/logpwrfft.py:26-154,
+ *   blks2impl/stream_to_vector_decimator.py:24-93, gnuradio/window.py:166-176,
+ *   general/gr_keep_one_in_n.cc:52-105
+ * The hier block stream_to_vector -> keep_one_in_n(decim) -> fft_vcc | fft_vfc (forward, windowed)
+ * -> complex_to_mag_squared -> single_pole_iir_filter_ff -> nlog10_ff(10, fft_size, k) in one
+ * transform kernel (plus one in-place averaging pass when averaging is on).  Results are bit for bit
+ * those of this library's own blocks run in that order, in every mode (set_mode selects the IIR's
+ * GENERIC / FAST form as for single_pole_iir_filter_ff).
+ *   decim = max(1, (int)round(sample_rate / fft_size / frame_rate)), round half away from zero;
+ *   k = -20 log10(fft_size) - 10 log10(window_power / fft_size) - 20 log10(ref_scale / 2), in double,
+ *       narrowed to float; window_power = the sum of squares of the window's doubles, in order.
+ * `window` holds the DOUBLES the reference's win(fft_size) returns; NULL / 0 is the default,
+ * grhip_window_blackmanharris.  The transform gets them narrowed to float.  A window whose length
+ * is neither 0 nor fft_size is refused by gr_fft_vcc::set_window and the refusal ignored, as in the
+ * reference: the transform runs unwindowed while k comes from the given values.
+ * All arithmetic is true division; Python 2's integer division of all-integer arguments is not
+ * reproduced.
+ * Averaging off means IIR taps of exactly 1.0: the kernel stores dB directly and leaves the power of
+ * every stream's last kept frame in the filter's state.  The reference computes
+ * (float)(1.0 x + 0.0 y_prev), which is x for every finite y_prev; after a non-finite state the two
+ * differ.  Non-finite input is out of scope.
+ * work / work_device: the input is nstreams x n_frames whole frames of fft_size samples (gr_complex
+ * for _c, float for _f), streams back to back; the output is nstreams x produced frames of fft_size
+ * floats; the return value is the frames produced per stream (grhip_logpwrfft_X_produced tells it
+ * without changing anything).  A call that keeps nothing returns 0 and advances the countdown.
+ * set_streams restarts state and countdown (the streams share the countdown); set_decimation,
+ * set_vec_rate and set_sample_rate reload the countdown; set_average and set_avg_alpha keep the
+ * filter's state.
+ * GRHIP_ERANGE: fft_size <= 0, avg_alpha outside [0, 1].  GRHIP_EINVAL: ref_scale <= 0, a window of
+ * power zero, fft_size == 1 with the default window (the reference's ValueError /
+ * ZeroDivisionError), a decimation that is not finite.  All refused before any device work.
+ * ====================================================================== */
+typedef struct grhip_logpwrfft_c grhip_logpwrfft_c;
+GRHIP_API int grhip_logpwrfft_c_create(grhip_logpwrfft_c **h, double sample_rate, int fft_size, double ref_scale,
+                                       double frame_rate, double avg_alpha, int average, const double *window,
+                                       size_t window_len, int device);
+GRHIP_API void grhip_logpwrfft_c_destroy(grhip_logpwrfft_c *h);
+GRHIP_API int grhip_logpwrfft_c_set_mode(grhip_logpwrfft_c *h, int mode);
+GRHIP_API int grhip_logpwrfft_c_set_streams(grhip_logpwrfft_c *h, int nstreams);
+/* logpwrfft.py:70-108; set_decimation is stream_to_vector_decimator.py:66-72 */
+GRHIP_API int grhip_logpwrfft_c_set_decimation(grhip_logpwrfft_c *h, double decim);
+GRHIP_API int grhip_logpwrfft_c_set_vec_rate(grhip_logpwrfft_c *h, double vec_rate);
+GRHIP_API int grhip_logpwrfft_c_set_sample_rate(grhip_logpwrfft_c *h, double sample_rate);
+GRHIP_API int grhip_logpwrfft_c_set_average(grhip_logpwrfft_c *h, int average);
+GRHIP_API int grhip_logpwrfft_c_set_avg_alpha(grhip_logpwrfft_c *h, double avg_alpha);
+/* logpwrfft.py:110-138, stream_to_vector_decimator.py:77-93 (NaN for a null handle) */
+GRHIP_API double grhip_logpwrfft_c_sample_rate(grhip_logpwrfft_c *h);
+GRHIP_API int grhip_logpwrfft_c_decimation(grhip_logpwrfft_c *h);
+GRHIP_API double grhip_logpwrfft_c_frame_rate(grhip_logpwrfft_c *h);
+GRHIP_API int grhip_logpwrfft_c_average(grhip_logpwrfft_c *h);
+GRHIP_API double grhip_logpwrfft_c_avg_alpha(grhip_logpwrfft_c *h);
+GRHIP_API int grhip_logpwrfft_c_produced(grhip_logpwrfft_c *h, int n_frames);
+/* the averaging filter's state, nstreams x fft_size floats of linear power, after the work queued so far */
+GRHIP_API int grhip_logpwrfft_c_state(grhip_logpwrfft_c *h, float *out);
+GRHIP_API int grhip_logpwrfft_c_work(grhip_logpwrfft_c *h, int n_frames, const void *in, void *out);
+GRHIP_API int grhip_logpwrfft_c_work_device(grhip_logpwrfft_c *h, int n_frames, const void *d_in, void *d_out,
+                                            void *stream);
+
+typedef struct grhip_logpwrfft_f grhip_logpwrfft_f;
+GRHIP_API int grhip_logpwrfft_f_create(grhip_logpwrfft_f **h, double sample_rate, int fft_size, double ref_scale,
+                                       double frame_rate, double avg_alpha, int average, const double *window,
+                                       size_t window_len, int device);
+GRHIP_API void grhip_logpwrfft_f_destroy(grhip_logpwrfft_f *h);
+GRHIP_API int grhip_logpwrfft_f_set_mode(grhip_logpwrfft_f *h, int mode);
+GRHIP_API int grhip_logpwrfft_f_set_streams(grhip_logpwrfft_f *h, int nstreams);
+/* logpwrfft.py:70-108; set_decimation is stream_to_vector_decimator.py:66-72 */
+GRHIP_API int grhip_logpwrfft_f_set_decimation(grhip_logpwrfft_f *h, double decim);
+GRHIP_API int grhip_logpwrfft_f_set_vec_rate(grhip_logpwrfft_f *h, double vec_rate);
+GRHIP_API int grhip_logpwrfft_f_set_sample_rate(grhip_logpwrfft_f *h, double sample_rate);
+GRHIP_API int grhip_logpwrfft_f_set_average(grhip_logpwrfft_f *h, int average);
+GRHIP_API int grhip_logpwrfft_f_set_avg_alpha(grhip_logpwrfft_f *h, double avg_alpha);
+/* logpwrfft.py:110-138, stream_to_vector_decimator.py:77-93 (NaN for a null handle) */
+GRHIP_API double grhip_logpwrfft_f_sample_rate(grhip_logpwrfft_f *h);
+GRHIP_API int grhip_logpwrfft_f_decimation(grhip_logpwrfft_f *h);
+GRHIP_API double grhip_logpwrfft_f_frame_rate(grhip_logpwrfft_f *h);
+GRHIP_API int grhip_logpwrfft_f_average(grhip_logpwrfft_f *h);
+GRHIP_API double grhip_logpwrfft_f_avg_alpha(grhip_logpwrfft_f *h);
+GRHIP_API int grhip_logpwrfft_f_produced(grhip_logpwrfft_f *h, int n_frames);
+/* the averaging filter's state, nstreams x fft_size floats of linear power, after the work queued so far */
+GRHIP_API int grhip_logpwrfft_f_state(grhip_logpwrfft_f *h, float *out);
+GRHIP_API int grhip_logpwrfft_f_work(grhip_logpwrfft_f *h, int n_frames, const void *in, void *out);
+GRHIP_API int grhip_logpwrfft_f_work_device(grhip_logpwrfft_f *h, int n_frames, const void *d_in, void *d_out,
+                                            void *stream);
+
+/* window.blackmanharris(fft_size) (gnuradio/window.py:166-176): out[i] = sum over c of
+ * (-1)**c * coeff[c] * cos(2.0 * c * pi * (i + 0.5) / (fft_size - 1)), accumulated from 0 in
+ * coefficient order, coeff = (0.35875, 0.48829, 0.14128, 0.01168).  Host arithmetic only, no device
+ * needed.  GRHIP_EINVAL for fft_size == 1 (division by zero there) and negative sizes. */
+GRHIP_API int grhip_window_blackmanharris(int fft_size, double *out);
+
+/* ======================================================================
  * gr_pfb_channelizer_ccf
  *   replaces gr_make_pfb_channelizer_ccf(unsigned numchans,
  *       const std::vector<float>& taps, float oversample_rate)
