@@ -20,6 +20,7 @@ __all__ = [
     "integrate_ff", "integrate_cc", "integrate_ss", "integrate_ii",
     "complex_to_mag_squared", "single_pole_iir_filter_ff", "nlog10_ff", "keep_one_in_n",
     "logpwrfft_c", "logpwrfft_f", "window_blackmanharris",
+    "pwr_squelch_cc", "pwr_squelch_ff", "simple_squelch_cc",
     "WIN_HAMMING", "WIN_HANN", "WIN_BLACKMAN", "WIN_RECTANGULAR", "WIN_KAISER", "WIN_BLACKMAN_hARRIS",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
     "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
@@ -1755,6 +1756,130 @@ class nlog10_ff(_spectrum):
         _spectrum.__init__(self, vlen)
         f = self._fn("create", [C.POINTER(C.c_void_p), C.c_float, C.c_int, C.c_float, C.c_int])
         _check(f(C.byref(self._h), float(n), int(vlen), float(k), int(device)))
+
+
+class _squelch(_Block):
+    """gr.pwr_squelch_cc / _ff and gr.simple_squelch_cc (general/gr_pwr_squelch_cc.i, gr_pwr_squelch_ff.i,
+    gr_simple_squelch_cc.i).  work(x) takes streams x n_in items back to back and returns every stream's produced
+    items (one array for one stream, a list otherwise); the detector and the ramp machine carry across calls."""
+    _name = None
+    _dtype = np.complex64
+
+    def __init__(self):
+        _Block.__init__(self)
+        self._destroy = "grhip_%s_destroy" % self._name
+        self._streams = 1
+
+    def _fn(self, name, argtypes=None, restype=None):
+        f = getattr(lib(), "grhip_%s_%s" % (self._name, name))
+        if argtypes is not None:
+            f.argtypes = argtypes
+        if restype is not None:
+            f.restype = restype
+        return f
+
+    def set_mode(self, mode):
+        _check(self._fn("set_mode", [C.c_void_p, C.c_int])(self._h, int(mode)))
+
+    def set_streams(self, nstreams):
+        """restarts every stream from the reference's initial state"""
+        _check(self._fn("set_streams", [C.c_void_p, C.c_int])(self._h, int(nstreams)))
+        self._streams = int(nstreams)
+
+    def threshold(self):
+        return self._fn("threshold", [C.c_void_p], C.c_double)(self._h)
+
+    def set_threshold(self, db):
+        _check(self._fn("set_threshold", [C.c_void_p, C.c_double])(self._h, float(db)))
+
+    def set_alpha(self, alpha):
+        _check(self._fn("set_alpha", [C.c_void_p, C.c_double])(self._h, float(alpha)))
+
+    def unmuted(self, stream=0):
+        return bool(_check(self._fn("unmuted", [C.c_void_p, C.c_int])(self._h, int(stream))))
+
+    def state(self, stream=0):
+        """(state, ramped, envelope, detector output) of one stream; state 0 muted, 1 attack, 2 unmuted, 3 decay"""
+        st, r, e, y = C.c_int(0), C.c_int(0), C.c_double(0), C.c_double(0)
+        f = self._fn("state", [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                               C.POINTER(C.c_double)])
+        _check(f(self._h, int(stream), C.byref(st), C.byref(r), C.byref(e), C.byref(y)))
+        return st.value, r.value, e.value, y.value
+
+    @staticmethod
+    def squelch_range():
+        return [-50.0, 50.0, 1.0]
+
+    def work_into(self, n_in, input_items, out):
+        """the raw call: `out` (streams x n_in items, C-contiguous) is written up to every stream's count; returns the counts"""
+        x = np.ascontiguousarray(input_items, dtype=self._dtype).reshape(-1)
+        if len(x) < n_in * self._streams or out.size < n_in * self._streams or out.dtype != self._dtype:
+            raise ValueError("work needs %d items in and room for as many out" % (n_in * self._streams))
+        produced = np.zeros(self._streams, dtype=np.int32)
+        f = self._fn("work", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+        _check(f(self._h, int(n_in), _ptr(x), _ptr(out), _ptr(produced)))
+        if n_in == 0:
+            produced[:] = 0
+        return produced
+
+    def work(self, input_items, n_in=None):
+        x = np.ascontiguousarray(input_items, dtype=self._dtype).reshape(-1)
+        if n_in is None:
+            n_in = len(x) // self._streams
+        out = np.zeros(max(n_in * self._streams, 1), dtype=self._dtype)
+        p = self.work_into(n_in, x, out)
+        res = [out[s * n_in:s * n_in + int(p[s])] for s in range(self._streams)]
+        return res[0] if self._streams == 1 else res
+
+    def work_device(self, n_in, d_in, d_out, d_produced, stream=None):
+        """device buffers; d_produced holds streams int32 counts; does not synchronise"""
+        f = self._fn("work_device", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+        return _check(f(self._h, int(n_in), _devptr(d_in), _devptr(d_out), _devptr(d_produced), _stream(stream)))
+
+    @staticmethod
+    def chunk():
+        """samples per chunk of the FAST detector's cut of the item axis"""
+        return lib().grhip_pwr_squelch_chunk()
+
+
+class _pwr_squelch(_squelch):
+    def __init__(self, db, alpha=0.0001, ramp=0, gate=False, device=0):
+        _squelch.__init__(self)
+        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_int, C.c_int, C.c_int])
+        _check(f(C.byref(self._h), float(db), float(alpha), int(ramp), int(bool(gate)), int(device)))
+
+    def ramp(self):
+        return _check(self._fn("ramp", [C.c_void_p])(self._h))
+
+    def set_ramp(self, ramp):
+        _check(self._fn("set_ramp", [C.c_void_p, C.c_int])(self._h, int(ramp)))
+
+    def gate(self):
+        return bool(_check(self._fn("gate", [C.c_void_p])(self._h)))
+
+    def set_gate(self, gate):
+        _check(self._fn("set_gate", [C.c_void_p, C.c_int])(self._h, int(bool(gate))))
+
+
+class pwr_squelch_cc(_pwr_squelch):
+    """gr.pwr_squelch_cc(db, alpha=0.0001, ramp=0, gate=False)"""
+    _name = "pwr_squelch_cc"
+
+
+class pwr_squelch_ff(_pwr_squelch):
+    """gr.pwr_squelch_ff(db, alpha=0.0001, ramp=0, gate=False)"""
+    _name = "pwr_squelch_ff"
+    _dtype = np.float32
+
+
+class simple_squelch_cc(_squelch):
+    """gr.simple_squelch_cc(threshold_db, alpha): out = in where the detector is at or above the threshold, else 0"""
+    _name = "simple_squelch_cc"
+
+    def __init__(self, threshold_db, alpha=0.0001, device=0):
+        _squelch.__init__(self)
+        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_int])
+        _check(f(C.byref(self._h), float(threshold_db), float(alpha), int(device)))
 
 
 class keep_one_in_n(_Block):

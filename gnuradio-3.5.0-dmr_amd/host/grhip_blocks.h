@@ -28,6 +28,9 @@
 //                                            <- the factories of the same names (general/gr_complex_to_xxx.h,
 //                                               filter/gr_single_pole_iir_filter_ff.h, general/gr_nlog10_ff.h, general/gr_keep_one_in_n.h)
 //   gr_make_logpwrfft_c / _f                 <- blks2.logpwrfft_c / _f (python/gnuradio/blks2impl/logpwrfft.py:26-154)
+//   gr_make_pwr_squelch_cc / _ff, gr_make_simple_squelch_cc
+//                                            <- the factories of the same names (general/gr_pwr_squelch_cc.h,
+//                                               general/gr_pwr_squelch_ff.h, general/gr_simple_squelch_cc.h)
 //
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
@@ -1365,3 +1368,103 @@ inline grhip_keep_one_in_n_sptr gr_make_keep_one_in_n(size_t item_size, int n, i
 GRHIP_LOGPWRFFT_BLK(logpwrfft_c, gr_complex)
 GRHIP_LOGPWRFFT_BLK(logpwrfft_f, float)
 #undef GRHIP_LOGPWRFFT_BLK
+
+// ---------------------------------------------------------------------------
+// gr_pwr_squelch_cc / _ff (db, alpha = 0.0001, ramp = 0, gate = false): gr_block; general_work takes noutput_items
+// inputs, consumes them all and returns the items produced, fewer with gating (general/gr_squelch_base_cc.cc:42-93,
+// gr_pwr_squelch_cc.h:30-62).  gr_simple_squelch_cc (threshold_db, alpha = 0.0001): gr_sync_block
+// (general/gr_simple_squelch_cc.h:30-63).
+// ---------------------------------------------------------------------------
+namespace grhip_detail {
+inline std::vector<float> squelch_range()
+{
+    std::vector<float> r(3);
+    r[0] = -50.0;
+    r[1] = +50.0;
+    r[2] = (r[1] - r[0]) / 100;
+    return r;
+}
+}  // namespace grhip_detail
+
+#define GRHIP_PWR_SQUELCH_BLK(NAME, ITEM)                                                                              \
+    class grhip_##NAME##_blk;                                                                                          \
+    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                 \
+    class grhip_##NAME##_blk : public gr_block {                                                                       \
+        grhip_##NAME *d_h = nullptr;                                                                                   \
+        grhip_##NAME##_blk(double db, double alpha, int ramp, bool gate, int device)                                   \
+            : gr_block(#NAME, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM)))      \
+        {                                                                                                              \
+            grhip_detail::check(grhip_##NAME##_create(&d_h, db, alpha, ramp, gate, device));                           \
+        }                                                                                                              \
+        friend grhip_##NAME##_sptr gr_make_##NAME(double, double, int, bool, int);                                     \
+    public:                                                                                                            \
+        ~grhip_##NAME##_blk() { grhip_##NAME##_destroy(d_h); }                                                         \
+        void set_mode(int mode) { grhip_detail::check(grhip_##NAME##_set_mode(d_h, mode)); }                           \
+        double threshold() const { return grhip_##NAME##_threshold(d_h); }                                             \
+        void set_threshold(double db) { grhip_detail::check(grhip_##NAME##_set_threshold(d_h, db)); }                  \
+        void set_alpha(double alpha) { grhip_detail::check(grhip_##NAME##_set_alpha(d_h, alpha)); }                    \
+        int ramp() const { return grhip_##NAME##_ramp(d_h); }                                                          \
+        void set_ramp(int ramp) { grhip_detail::check(grhip_##NAME##_set_ramp(d_h, ramp)); }                           \
+        bool gate() const { return grhip_##NAME##_gate(d_h) != 0; }                                                    \
+        void set_gate(bool gate) { grhip_detail::check(grhip_##NAME##_set_gate(d_h, gate)); }                          \
+        bool unmuted() const                                                                                           \
+        {                                                                                                              \
+            int r = grhip_##NAME##_unmuted(d_h, 0);                                                                    \
+            grhip_detail::check(r);                                                                                    \
+            return r != 0;                                                                                             \
+        }                                                                                                              \
+        std::vector<float> squelch_range() const { return grhip_detail::squelch_range(); }                             \
+        int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,                \
+                         gr_vector_void_star &out) override                                                            \
+        {                                                                                                              \
+            const int n = noutput_items < ninput_items[0] ? noutput_items : ninput_items[0];                           \
+            int produced = 0;                                                                                          \
+            grhip_detail::check(grhip_##NAME##_work(d_h, n, in[0], out[0], &produced));                                \
+            consume_each(n);                                    /* use all the inputs, report the outputs copied */     \
+            return produced;                                                                                           \
+        }                                                                                                              \
+    };                                                                                                                 \
+    inline grhip_##NAME##_sptr gr_make_##NAME(double db, double alpha = 0.0001, int ramp = 0, bool gate = false,       \
+                                              int device = 0)                                                          \
+    {                                                                                                                  \
+        return gnuradio::get_initial_sptr(new grhip_##NAME##_blk(db, alpha, ramp, gate, device));                      \
+    }
+GRHIP_PWR_SQUELCH_BLK(pwr_squelch_cc, gr_complex)
+GRHIP_PWR_SQUELCH_BLK(pwr_squelch_ff, float)
+#undef GRHIP_PWR_SQUELCH_BLK
+
+class grhip_simple_squelch_cc_blk;
+typedef boost::shared_ptr<grhip_simple_squelch_cc_blk> grhip_simple_squelch_cc_sptr;
+class grhip_simple_squelch_cc_blk : public gr_sync_block {
+    grhip_simple_squelch_cc *d_h = nullptr;
+    grhip_simple_squelch_cc_blk(double threshold_db, double alpha, int device)
+        : gr_sync_block("simple_squelch_cc", gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                        gr_make_io_signature(1, 1, sizeof(gr_complex)))
+    {
+        grhip_detail::check(grhip_simple_squelch_cc_create(&d_h, threshold_db, alpha, device));
+    }
+    friend grhip_simple_squelch_cc_sptr gr_make_simple_squelch_cc(double, double, int);
+public:
+    ~grhip_simple_squelch_cc_blk() { grhip_simple_squelch_cc_destroy(d_h); }
+    void set_mode(int mode) { grhip_detail::check(grhip_simple_squelch_cc_set_mode(d_h, mode)); }
+    bool unmuted() const
+    {
+        int r = grhip_simple_squelch_cc_unmuted(d_h, 0);
+        grhip_detail::check(r);
+        return r != 0;
+    }
+    void set_alpha(double alpha) { grhip_detail::check(grhip_simple_squelch_cc_set_alpha(d_h, alpha)); }
+    void set_threshold(double decibels) { grhip_detail::check(grhip_simple_squelch_cc_set_threshold(d_h, decibels)); }
+    double threshold() const { return grhip_simple_squelch_cc_threshold(d_h); }
+    std::vector<float> squelch_range() const { return grhip_detail::squelch_range(); }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int produced = 0;
+        grhip_detail::check(grhip_simple_squelch_cc_work(d_h, noutput_items, in[0], out[0], &produced));
+        return noutput_items ? produced : 0;
+    }
+};
+inline grhip_simple_squelch_cc_sptr gr_make_simple_squelch_cc(double threshold_db, double alpha = 0.0001, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_simple_squelch_cc_blk(threshold_db, alpha, device));
+}

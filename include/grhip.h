@@ -1405,6 +1405,103 @@ GRHIP_API int grhip_logpwrfft_f_work_device(grhip_logpwrfft_f *h, int n_frames, 
 GRHIP_API int grhip_window_blackmanharris(int fft_size, double *out);
 
 /* ======================================================================
+ * The power squelch blocks.  A handle takes S streams back to back in `in` ([S][n_in], S = 1 after
+ * create); stream s writes its items from out + s * n_in items and produced[s] tells how many: n_in
+ * without gating, fewer with it, and what lies behind them in `out` is not touched.  `out` may not
+ * overlap `in`.  work / work_device return GRHIP_OK; n_in == 0 is a successful no-op; work_device
+ * (device buffers, d_produced S ints on the device) does not synchronise.  Finite inputs only.
+ * Per stream the block remembers the detector's output, the machine's state, the ramp position and
+ * the envelope, on the device and across calls.  set_streams resizes that and restarts every stream
+ * from the reference's initial state; every other setter keeps it and holds from the next work call.
+ * unmuted(h, s) is 1 or 0; state(h, s, ...) reads one stream's state (0 muted, 1 attack, 2 unmuted,
+ * 3 decay: the reference's enum order); both wait for the handle's queued work.
+ * GRHIP_ERANGE for alpha outside [0, 1]; GRHIP_EINVAL for ramp < 0 (or past 2^24), S < 1, n_in < 0.
+ *
+ * gr_pwr_squelch_cc
+ *   replaces gr_make_pwr_squelch_cc(double db, double alpha = 0.0001, int ramp = 0, bool gate = false)
+ *   general/gr_pwr_squelch_cc.h:58 (set_threshold: pow(10.0, db / 10)), :57 (threshold: 10 log10),
+ *   general/gr_pwr_squelch_cc.cc:52-55 (update_state), gr_pwr_squelch_cc.h:52 (mute: y < threshold),
+ *   general/gr_squelch_base_cc.cc:42-93 (general_work: the machine, the envelope, gating)
+ * Detector: re * re + im * im in float (two rounded products, one rounded add), widened to double,
+ * y = alpha * p + (1.0 - alpha) * y with two double products and one double add.  The machine runs
+ * per sample after the detector and the output uses the state after it: MUTED and not mute ->
+ * ATTACK (ramp 0: UNMUTED); UNMUTED and mute -> DECAY (ramp 0: MUTED); ATTACK: ++ramped, envelope
+ * 0.5 - cos(M_PI * ramped / ramp) / 2.0, UNMUTED with envelope 1.0 once ramped >= ramp; DECAY:
+ * --ramped, the same formula, MUTED at 0.  Not MUTED: in * gr_complex(envelope, 0.0), the envelope
+ * narrowed to float and the whole complex product formed in float; MUTED: a zero, or with gating
+ * nothing.  The envelope values come from a table made by the host's cos in double.
+ * GRHIP_MODE_GENERIC: one lane per stream walks the detector in order.  Every other mode: the FAST
+ * form, chunks of grhip_pwr_squelch_chunk() samples chained through the recurrence's affine form;
+ * its y differs from the serial one by parts in 1e14, so the outputs are the same wherever the
+ * detector stays that far from the threshold, and the machine, the envelope and
+ * the products are the same code in both modes.
+ * Deviations: set_ramp(0) while a stream is in ATTACK or DECAY is refused with GRHIP_ERANGE (the
+ * reference divides by zero there and emits NaN); a stream that became UNMUTED without a ramp
+ * (ramped == 0) and is given one later decays over the whole ramp (the reference counts down from
+ * 0 and never ends that decay).
+ * ====================================================================== */
+typedef struct grhip_pwr_squelch_cc grhip_pwr_squelch_cc;
+GRHIP_API int grhip_pwr_squelch_cc_create(grhip_pwr_squelch_cc **h, double db, double alpha, int ramp, int gate, int device);
+GRHIP_API void grhip_pwr_squelch_cc_destroy(grhip_pwr_squelch_cc *h);
+GRHIP_API int grhip_pwr_squelch_cc_set_mode(grhip_pwr_squelch_cc *h, int mode);
+GRHIP_API int grhip_pwr_squelch_cc_set_streams(grhip_pwr_squelch_cc *h, int nstreams);
+GRHIP_API double grhip_pwr_squelch_cc_threshold(grhip_pwr_squelch_cc *h);
+GRHIP_API int grhip_pwr_squelch_cc_set_threshold(grhip_pwr_squelch_cc *h, double db);
+GRHIP_API int grhip_pwr_squelch_cc_set_alpha(grhip_pwr_squelch_cc *h, double alpha);
+GRHIP_API int grhip_pwr_squelch_cc_ramp(grhip_pwr_squelch_cc *h);
+GRHIP_API int grhip_pwr_squelch_cc_set_ramp(grhip_pwr_squelch_cc *h, int ramp);
+GRHIP_API int grhip_pwr_squelch_cc_gate(grhip_pwr_squelch_cc *h);
+GRHIP_API int grhip_pwr_squelch_cc_set_gate(grhip_pwr_squelch_cc *h, int gate);
+GRHIP_API int grhip_pwr_squelch_cc_unmuted(grhip_pwr_squelch_cc *h, int s);
+GRHIP_API int grhip_pwr_squelch_cc_state(grhip_pwr_squelch_cc *h, int s, int *state, int *ramped, double *envelope, double *y);
+GRHIP_API int grhip_pwr_squelch_cc_work(grhip_pwr_squelch_cc *h, int n_in, const void *in, void *out, int *produced);
+GRHIP_API int grhip_pwr_squelch_cc_work_device(grhip_pwr_squelch_cc *h, int n_in, const void *d_in, void *d_out, int *d_produced,
+                                     void *stream);
+
+/* gr_pwr_squelch_ff
+ *   replaces gr_make_pwr_squelch_ff(double db, double alpha = 0.0001, int ramp = 0, bool gate = false)
+ *   general/gr_pwr_squelch_ff.{h,cc} (detector: x * x in float), general/gr_squelch_base_ff.cc:42-93
+ * As pwr_squelch_cc on floats; the output is (float)((double)in * envelope), the product in double. */
+typedef struct grhip_pwr_squelch_ff grhip_pwr_squelch_ff;
+GRHIP_API int grhip_pwr_squelch_ff_create(grhip_pwr_squelch_ff **h, double db, double alpha, int ramp, int gate, int device);
+GRHIP_API void grhip_pwr_squelch_ff_destroy(grhip_pwr_squelch_ff *h);
+GRHIP_API int grhip_pwr_squelch_ff_set_mode(grhip_pwr_squelch_ff *h, int mode);
+GRHIP_API int grhip_pwr_squelch_ff_set_streams(grhip_pwr_squelch_ff *h, int nstreams);
+GRHIP_API double grhip_pwr_squelch_ff_threshold(grhip_pwr_squelch_ff *h);
+GRHIP_API int grhip_pwr_squelch_ff_set_threshold(grhip_pwr_squelch_ff *h, double db);
+GRHIP_API int grhip_pwr_squelch_ff_set_alpha(grhip_pwr_squelch_ff *h, double alpha);
+GRHIP_API int grhip_pwr_squelch_ff_ramp(grhip_pwr_squelch_ff *h);
+GRHIP_API int grhip_pwr_squelch_ff_set_ramp(grhip_pwr_squelch_ff *h, int ramp);
+GRHIP_API int grhip_pwr_squelch_ff_gate(grhip_pwr_squelch_ff *h);
+GRHIP_API int grhip_pwr_squelch_ff_set_gate(grhip_pwr_squelch_ff *h, int gate);
+GRHIP_API int grhip_pwr_squelch_ff_unmuted(grhip_pwr_squelch_ff *h, int s);
+GRHIP_API int grhip_pwr_squelch_ff_state(grhip_pwr_squelch_ff *h, int s, int *state, int *ramped, double *envelope, double *y);
+GRHIP_API int grhip_pwr_squelch_ff_work(grhip_pwr_squelch_ff *h, int n_in, const void *in, void *out, int *produced);
+GRHIP_API int grhip_pwr_squelch_ff_work_device(grhip_pwr_squelch_ff *h, int n_in, const void *d_in, void *d_out, int *d_produced,
+                                     void *stream);
+
+/* gr_simple_squelch_cc
+ *   replaces gr_make_simple_squelch_cc(double threshold_db, double alpha = 0.0001)
+ *   general/gr_simple_squelch_cc.cc:53-71 (work), :74-93 (set_threshold, threshold, set_alpha)
+ * The same detector; out = (y >= threshold) ? in : 0, no ramp, no gating, produced[s] == n_in;
+ * unmuted() is y_last >= threshold after the call. */
+typedef struct grhip_simple_squelch_cc grhip_simple_squelch_cc;
+GRHIP_API int grhip_simple_squelch_cc_create(grhip_simple_squelch_cc **h, double threshold_db, double alpha, int device);
+GRHIP_API void grhip_simple_squelch_cc_destroy(grhip_simple_squelch_cc *h);
+GRHIP_API int grhip_simple_squelch_cc_set_mode(grhip_simple_squelch_cc *h, int mode);
+GRHIP_API int grhip_simple_squelch_cc_set_streams(grhip_simple_squelch_cc *h, int nstreams);
+GRHIP_API double grhip_simple_squelch_cc_threshold(grhip_simple_squelch_cc *h);
+GRHIP_API int grhip_simple_squelch_cc_set_threshold(grhip_simple_squelch_cc *h, double db);
+GRHIP_API int grhip_simple_squelch_cc_set_alpha(grhip_simple_squelch_cc *h, double alpha);
+GRHIP_API int grhip_simple_squelch_cc_unmuted(grhip_simple_squelch_cc *h, int s);
+GRHIP_API int grhip_simple_squelch_cc_state(grhip_simple_squelch_cc *h, int s, int *state, int *ramped, double *envelope, double *y);
+GRHIP_API int grhip_simple_squelch_cc_work(grhip_simple_squelch_cc *h, int n_in, const void *in, void *out, int *produced);
+GRHIP_API int grhip_simple_squelch_cc_work_device(grhip_simple_squelch_cc *h, int n_in, const void *d_in, void *d_out, int *d_produced,
+                                     void *stream);
+/* samples per chunk of the FAST detector */
+GRHIP_API int grhip_pwr_squelch_chunk(void);
+
+/* ======================================================================
  * gr_pfb_channelizer_ccf
  *   replaces gr_make_pfb_channelizer_ccf(unsigned numchans,
  *       const std::vector<float>& taps, float oversample_rate)
