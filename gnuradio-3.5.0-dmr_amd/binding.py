@@ -641,6 +641,12 @@ class unpack_k_bits_bb(_Block):
         n = _check(L.grhip_unpack_k_bits_bb_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
         return out[:n]
 
+    def work_device(self, noutput_items, d_in, d_out, stream=None):
+        L = lib()
+        L.grhip_unpack_k_bits_bb_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        return _check(L.grhip_unpack_k_bits_bb_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
+                                                           _stream(stream)))
+
 
 class clock_recovery_mm_cc(_Block):
     """digital.clock_recovery_mm_cc(omega, gain_omega, mu, gain_mu, omega_relative_limit)"""
@@ -692,6 +698,17 @@ class clock_recovery_mm_cc(_Block):
         n = _check(L.grhip_clock_recovery_mm_cc_general_work(self._h, int(noutput_items), len(x), _ptr(x), _ptr(out),
                                                              _ptr(err) if want_error else None, C.byref(consumed)))
         return out[:n], (err[:n] if want_error else None), consumed.value
+
+    def general_work_device(self, noutput_items, ninput_items, d_in, d_out, d_err=None, stream=None):
+        """device buffers (d_err may be None: no error output, clip limit 1.0); returns (produced, consumed)"""
+        consumed = C.c_int(0)
+        L = lib()
+        L.grhip_clock_recovery_mm_cc_general_work_device.argtypes = [
+            C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
+        n = _check(L.grhip_clock_recovery_mm_cc_general_work_device(
+            self._h, int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out), _devptr(d_err),
+            C.byref(consumed), _stream(stream)))
+        return n, consumed.value
 
 
 class _copy_adapter(_Block):

@@ -53,6 +53,7 @@ int corr_set_code(CorrParams &p, unsigned long long &flag_bit, const char *code,
 struct grhip_clock_recovery_mm_ff : HandleBase {
     const DeviceTables *tabs = nullptr;
     DevBuf d_state, d_counts;
+    bool ended = false;          // a host call has left the loop before its first sample: later host calls produce nothing
     int read_state(MMState &s)
     {
         GRHIP_HIP(hipMemcpy(&s, d_state.p, sizeof(s), hipMemcpyDeviceToHost));
@@ -142,6 +143,10 @@ int grhip_clock_recovery_mm_ff_general_work(grhip_clock_recovery_mm_ff *h, int n
     if (noutput_items < 0 || ninput_items < 0) return fail(GRHIP_EINVAL, "negative item count");
     int rc = h->bind();
     if (rc) return rc;
+    if (h->ended) {
+        if (consumed) *consumed = 0;
+        return 0;
+    }
     if ((rc = h->stage_in.reserve((size_t)(ninput_items > 0 ? ninput_items : 1) * 4))) return rc;
     if ((rc = h->stage_out.reserve((size_t)(noutput_items > 0 ? noutput_items : 1) * 4))) return rc;
     hipStream_t st = h->own_stream;
@@ -155,6 +160,7 @@ int grhip_clock_recovery_mm_ff_general_work(grhip_clock_recovery_mm_ff *h, int n
     if (counts[0] > 0)
         GRHIP_HIP(hipMemcpy(out, h->stage_out.p, (size_t)counts[0] * 4, hipMemcpyDeviceToHost));
     if (consumed) *consumed = counts[1];
+    if (counts[1] < 0) h->ended = true;      // (the reference would read before its buffer from here on: see grhip.h)
     return counts[0];
 }
 

@@ -280,6 +280,13 @@ GRHIP_API int grhip_xlating_demod_run_captures_device(grhip_xlating_demod *h, in
  * general_work contract: consumes *consumed items (consume_each), returns
  * items produced; uses at most ninput_items - 8 inputs (.cc:113).
  * GRHIP_ERANGE if omega < 1 or a gain is negative (.cc:58-61).
+ * Deviation: a loop whose timing error drives its sample position below 0
+ * (a step back before the first item of the call's buffer) ends there: the
+ * reference goes on and reads before its buffer.  The symbols up to that
+ * point are the reference's, *consumed is the negative position, and the
+ * handle stays ended: later general_work calls produce and consume nothing.
+ * The device form reports the negative position in d_counts[1] and leaves
+ * stopping to the caller.
  * ====================================================================== */
 typedef struct grhip_clock_recovery_mm_ff grhip_clock_recovery_mm_ff;
 GRHIP_API int grhip_clock_recovery_mm_ff_create(grhip_clock_recovery_mm_ff **h, float omega,

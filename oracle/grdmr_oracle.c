@@ -587,6 +587,47 @@ ORC_API int orc_mmcc_general_work(orc_mmcc *s, int noutput_items, int ninput_ite
     return oo;
 }
 
+/* the same loop, written out a second time for the tests of the loop's irregular regimes: pos[oo] is the sample
+ * position ii the symbol oo was interpolated at, pos[n] the position the call ends at, *nclamp how often line
+ * .cc:165-166 (ii < 0 -> 0) applied.  tests/test_mm_trace_cpu.py pins it to orc_mmcc_general_work bit for bit. */
+ORC_API int orc_mmcc_general_work_trace(orc_mmcc *s, int noutput_items, int ninput_items, const float *in, float *out,
+                                        float *foptr, int *consumed, int *pos, int *nclamp)
+{
+    if (!mmse_ready) mmse_init();
+    int ii = 0, oo = 0, clamps = 0;
+    int ni = ninput_items - MMSE_NTAPS - 16;
+    const float lim = foptr ? 4.0f : 1.0f;
+    while (oo < noutput_items && ii < ni) {
+        pos[oo] = ii;
+        s->p_2T[0] = s->p_1T[0]; s->p_2T[1] = s->p_1T[1];
+        s->p_1T[0] = s->p_0T[0]; s->p_1T[1] = s->p_0T[1];
+        int imu = (int)rint(s->mu * MMSE_NSTEPS);
+        fir_ccf_one(mmse_rev[imu], MMSE_NTAPS, in + 2 * (size_t)ii, s->p_0T);
+        s->c_2T[0] = s->c_1T[0]; s->c_2T[1] = s->c_1T[1];
+        s->c_1T[0] = s->c_0T[0]; s->c_1T[1] = s->c_0T[1];
+        s->c_0T[0] = s->p_0T[0] > 0 ? 1.0f : 0.0f;
+        s->c_0T[1] = s->p_0T[1] > 0 ? 1.0f : 0.0f;
+        float xr, xi, yr, yi;
+        cmul(s->c_0T[0] - s->c_2T[0], s->c_0T[1] - s->c_2T[1], s->p_1T[0], -s->p_1T[1], &xr, &xi);
+        cmul(s->p_0T[0] - s->p_2T[0], s->p_0T[1] - s->p_2T[1], s->c_1T[0], -s->c_1T[1], &yr, &yi);
+        float mm_val = yr - xr;
+        out[2 * oo] = s->p_0T[0]; out[2 * oo + 1] = s->p_0T[1];
+        oo++;
+        mm_val = orc_branchless_clip(mm_val, lim);
+        s->omega = s->omega + s->gain_omega * mm_val;
+        s->omega = s->omega_mid + orc_branchless_clip(s->omega - s->omega_mid, s->omega_relative_limit);
+        s->mu = s->mu + s->omega + s->gain_mu * mm_val;
+        ii += (int)floor(s->mu);
+        s->mu -= floor(s->mu);
+        if (foptr) foptr[oo - 1] = mm_val;
+        if (ii < 0) { ii = 0; clamps++; }
+    }
+    pos[oo] = ii;
+    if (nclamp) *nclamp = clamps;
+    if (consumed) *consumed = ii > 0 ? ii : 0;
+    return oo;
+}
+
 /* ------------------------------------------------------------------ */
 /* gr_framer_sink_1 (general/gr_framer_sink_1.cc:34-66 state entries,     */
 /* 90-190 work; general/gr_framer_sink_1.h:62-98 state, header_ok,       */

@@ -291,6 +291,24 @@ class ClockRecoveryMMcc:
                                     err.ctypes.data if want_error else None, C.byref(consumed))
         return out[:n].copy(), (err[:n].copy() if want_error else None), consumed.value
 
+    def general_work_trace(self, nout, x, want_error=False):
+        """general_work that also reports where the loop went: returns (out[:n], err[:n] or None, consumed,
+        pos[:n + 1], clamps) -- pos[k] is the sample position of symbol k, pos[n] where the call ended, clamps the
+        number of times the position was brought back to 0"""
+        o = _need()
+        x = np.ascontiguousarray(x, dtype=np.complex64)
+        out = np.zeros(max(nout, 1), dtype=np.complex64)
+        err = np.zeros(max(nout, 1), dtype=np.float32) if want_error else None
+        pos = np.zeros(max(nout, 0) + 1, dtype=np.int32)
+        consumed, clamps = C.c_int(0), C.c_int(0)
+        o.orc_mmcc_general_work_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int)]
+        n = o.orc_mmcc_general_work_trace(self.s, nout, len(x), x.ctypes.data, out.ctypes.data,
+                                          err.ctypes.data if want_error else None, C.byref(consumed),
+                                          pos.ctypes.data, C.byref(clamps))
+        return (out[:n].copy(), (err[:n].copy() if want_error else None), consumed.value, pos[:n + 1].copy(),
+                clamps.value)
+
     def mu(self):
         o = _need()
         o.orc_mmcc_mu.restype = C.c_float

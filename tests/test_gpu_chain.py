@@ -171,7 +171,9 @@ def test_chain_eight_captures_per_wave(gpu, po, wl, decim, ntaps, n_out, omega):
     """the clock recovery with eight captures per wavefront (the shape of batches beyond a thousand captures, forced here on
     11 captures: one full wave and one with three of its eight groups in use): bit-exact on its input like the one-capture
     form, and the two forms produce identical chains.  Symbol clocks from 2 to 150 samples per symbol: many symbols per
-    ring top-up, few, and (150 > the ring's chunk) a ring re-seeded at every symbol; time-sliced and single-slice runs."""
+    ring top-up and few.  A step of 150 samples is longer than the 64-sample chunk of the thirty-two-captures form only
+    (several chunks accepted per symbol there); the chunks of this form are 256 and 512 samples, so its ring is never
+    re-seeded after start-up here -- tests/test_gpu_mm_dynamics.py drives that.  Time-sliced and single-slice runs."""
     import ctypes
     torch = _torch()
     c, c4 = wl.CFG2, wl.CFG4
