@@ -20,7 +20,7 @@ __all__ = [
     "integrate_ff", "integrate_cc", "integrate_ss", "integrate_ii",
     "complex_to_mag_squared", "single_pole_iir_filter_ff", "nlog10_ff", "keep_one_in_n",
     "logpwrfft_c", "logpwrfft_f", "window_blackmanharris",
-    "pwr_squelch_cc", "pwr_squelch_ff", "simple_squelch_cc",
+    "pwr_squelch_cc", "pwr_squelch_ff", "simple_squelch_cc", "ctcss_squelch_ff",
     "WIN_HAMMING", "WIN_HANN", "WIN_BLACKMAN", "WIN_RECTANGULAR", "WIN_KAISER", "WIN_BLACKMAN_hARRIS",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
     "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
@@ -1775,10 +1775,9 @@ class nlog10_ff(_spectrum):
         _check(f(C.byref(self._h), float(n), int(vlen), float(k), int(device)))
 
 
-class _squelch(_Block):
-    """gr.pwr_squelch_cc / _ff and gr.simple_squelch_cc (general/gr_pwr_squelch_cc.i, gr_pwr_squelch_ff.i,
-    gr_simple_squelch_cc.i).  work(x) takes streams x n_in items back to back and returns every stream's produced
-    items (one array for one stream, a list otherwise); the detector and the ramp machine carry across calls."""
+class _squelch_streams(_Block):
+    """what every squelch block shares: work(x) takes streams x n_in items back to back and returns every stream's
+    produced items (one array for one stream, a list otherwise); the detector and the ramp machine carry across calls."""
     _name = None
     _dtype = np.complex64
 
@@ -1803,29 +1802,8 @@ class _squelch(_Block):
         _check(self._fn("set_streams", [C.c_void_p, C.c_int])(self._h, int(nstreams)))
         self._streams = int(nstreams)
 
-    def threshold(self):
-        return self._fn("threshold", [C.c_void_p], C.c_double)(self._h)
-
-    def set_threshold(self, db):
-        _check(self._fn("set_threshold", [C.c_void_p, C.c_double])(self._h, float(db)))
-
-    def set_alpha(self, alpha):
-        _check(self._fn("set_alpha", [C.c_void_p, C.c_double])(self._h, float(alpha)))
-
     def unmuted(self, stream=0):
         return bool(_check(self._fn("unmuted", [C.c_void_p, C.c_int])(self._h, int(stream))))
-
-    def state(self, stream=0):
-        """(state, ramped, envelope, detector output) of one stream; state 0 muted, 1 attack, 2 unmuted, 3 decay"""
-        st, r, e, y = C.c_int(0), C.c_int(0), C.c_double(0), C.c_double(0)
-        f = self._fn("state", [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
-                               C.POINTER(C.c_double)])
-        _check(f(self._h, int(stream), C.byref(st), C.byref(r), C.byref(e), C.byref(y)))
-        return st.value, r.value, e.value, y.value
-
-    @staticmethod
-    def squelch_range():
-        return [-50.0, 50.0, 1.0]
 
     def work_into(self, n_in, input_items, out):
         """the raw call: `out` (streams x n_in items, C-contiguous) is written up to every stream's count; returns the counts"""
@@ -1853,17 +1831,9 @@ class _squelch(_Block):
         f = self._fn("work_device", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
         return _check(f(self._h, int(n_in), _devptr(d_in), _devptr(d_out), _devptr(d_produced), _stream(stream)))
 
-    @staticmethod
-    def chunk():
-        """samples per chunk of the FAST detector's cut of the item axis"""
-        return lib().grhip_pwr_squelch_chunk()
 
-
-class _pwr_squelch(_squelch):
-    def __init__(self, db, alpha=0.0001, ramp=0, gate=False, device=0):
-        _squelch.__init__(self)
-        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_int, C.c_int, C.c_int])
-        _check(f(C.byref(self._h), float(db), float(alpha), int(ramp), int(bool(gate)), int(device)))
+class _ramp_gate(object):
+    """ramp() / gate() and their setters (general/gr_squelch_base_cc.h:45-48)"""
 
     def ramp(self):
         return _check(self._fn("ramp", [C.c_void_p])(self._h))
@@ -1876,6 +1846,44 @@ class _pwr_squelch(_squelch):
 
     def set_gate(self, gate):
         _check(self._fn("set_gate", [C.c_void_p, C.c_int])(self._h, int(bool(gate))))
+
+
+class _squelch(_squelch_streams):
+    """gr.pwr_squelch_cc / _ff and gr.simple_squelch_cc (general/gr_pwr_squelch_cc.i, gr_pwr_squelch_ff.i,
+    gr_simple_squelch_cc.i): the power detector's accessors"""
+
+    def threshold(self):
+        return self._fn("threshold", [C.c_void_p], C.c_double)(self._h)
+
+    def set_threshold(self, db):
+        _check(self._fn("set_threshold", [C.c_void_p, C.c_double])(self._h, float(db)))
+
+    def set_alpha(self, alpha):
+        _check(self._fn("set_alpha", [C.c_void_p, C.c_double])(self._h, float(alpha)))
+
+    def state(self, stream=0):
+        """(state, ramped, envelope, detector output) of one stream; state 0 muted, 1 attack, 2 unmuted, 3 decay"""
+        st, r, e, y = C.c_int(0), C.c_int(0), C.c_double(0), C.c_double(0)
+        f = self._fn("state", [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                               C.POINTER(C.c_double)])
+        _check(f(self._h, int(stream), C.byref(st), C.byref(r), C.byref(e), C.byref(y)))
+        return st.value, r.value, e.value, y.value
+
+    @staticmethod
+    def squelch_range():
+        return [-50.0, 50.0, 1.0]
+
+    @staticmethod
+    def chunk():
+        """samples per chunk of the FAST detector's cut of the item axis"""
+        return lib().grhip_pwr_squelch_chunk()
+
+
+class _pwr_squelch(_squelch, _ramp_gate):
+    def __init__(self, db, alpha=0.0001, ramp=0, gate=False, device=0):
+        _squelch.__init__(self)
+        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_int, C.c_int, C.c_int])
+        _check(f(C.byref(self._h), float(db), float(alpha), int(ramp), int(bool(gate)), int(device)))
 
 
 class pwr_squelch_cc(_pwr_squelch):
@@ -1897,6 +1905,56 @@ class simple_squelch_cc(_squelch):
         _squelch.__init__(self)
         f = self._fn("create", [C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_int])
         _check(f(C.byref(self._h), float(threshold_db), float(alpha), int(device)))
+
+
+class ctcss_squelch_ff(_squelch_streams, _ramp_gate):
+    """gr.ctcss_squelch_ff(rate, freq, level=0.01, len=0, ramp=0, gate=False) (general/gr_ctcss_squelch_ff.i): mutes
+    unless the tone at freq stands above level and above its two guard tones, decided once per len samples (len 0:
+    rate / 10).  work() as the power squelch blocks; blocks of len samples run across calls."""
+    _name = "ctcss_squelch_ff"
+    _dtype = np.float32
+
+    def __init__(self, rate, freq, level=0.01, len=0, ramp=0, gate=False, device=0):
+        _squelch_streams.__init__(self)
+        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int])
+        _check(f(C.byref(self._h), int(rate), float(freq), float(level), int(len), int(ramp), int(bool(gate)), int(device)))
+
+    def level(self):
+        return self._fn("level", [C.c_void_p], C.c_float)(self._h)
+
+    def set_level(self, level):
+        _check(self._fn("set_level", [C.c_void_p, C.c_float])(self._h, float(level)))
+
+    def len(self):
+        return _check(self._fn("len", [C.c_void_p])(self._h))
+
+    @staticmethod
+    def squelch_range():
+        r = (C.c_float * 3)()
+        _check(lib().grhip_ctcss_squelch_ff_squelch_range(r))
+        return [r[0], r[1], r[2]]
+
+    def state(self, stream=0):
+        """(state, ramped, envelope, d_mute, samples of the unfinished block) of one stream"""
+        st, r, e, m, p = C.c_int(0), C.c_int(0), C.c_double(0), C.c_int(0), C.c_int(0)
+        f = self._fn("state", [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                               C.POINTER(C.c_int), C.POINTER(C.c_int)])
+        _check(f(self._h, int(stream), C.byref(st), C.byref(r), C.byref(e), C.byref(m), C.byref(p)))
+        return st.value, r.value, e.value, bool(m.value), p.value
+
+    def tones(self):
+        """(left guard, tone, right guard) in Hz, as float32"""
+        v = [C.c_float(0), C.c_float(0), C.c_float(0)]
+        f = self._fn("tones", [C.c_void_p] + [C.POINTER(C.c_float)] * 3)
+        _check(f(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2])))
+        return tuple(np.float32(x.value) for x in v)
+
+    def last_magnitudes(self, n_blocks, stream=0):
+        """|l|, |c|, |r| of the blocks the last work call completed, [blocks][3] float32 (for tests)"""
+        out = np.zeros((max(int(n_blocks), 1), 3), dtype=np.float32)
+        f = self._fn("last_magnitudes", [C.c_void_p, C.c_int, C.c_void_p, C.c_int])
+        got = _check(f(self._h, int(stream), _ptr(out), int(n_blocks)))
+        return out[:got]
 
 
 class keep_one_in_n(_Block):

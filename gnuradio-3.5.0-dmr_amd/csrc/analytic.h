@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+
 namespace grhip {
 
 constexpr int AN_THREADS = 256;                 // lanes per workgroup of the tile kernels
@@ -30,6 +32,28 @@ constexpr int GZ_WG_LEN = 2048;                 // FAST: from this block length 
 
 // GENERIC: gri_goertzel::batch per block, bit-exact.  FAST: the closed form against tab[n] =
 // (cos((len - n) w') / len, wi U_(len-1-n) / len), len entries built in double by the host.
+// gri_goertzel::gri_setparms (gri_goertzel.cc:41-52): w in double, stored to float; cos and sin in float
+inline void goertzel_setparms(int rate, float freq, float *wr, float *wi)
+{
+    const float w = 2.0 * M_PI * freq / rate;
+    *wr = 2.0 * cosf(w);
+    *wi = sinf(w);
+}
+
+// the FAST table of one tone, len entries, in double and rounded once (goertzel_fc; three of them for ctcss_squelch_ff)
+inline void goertzel_build_table(int len, float wr, float wi, float2 *tab)
+{
+    double c = 0.5 * (double)wr;
+    c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
+    const double wp = acos(c), s = sin(wp), inv = 1.0 / (double)len;
+    const bool flat = !(fabs(s) > 1e-300);                      // wr = +-2: U_k = (k + 1) (+-1)^k
+    for (int n = 0; n < len; ++n) {
+        const int k = len - 1 - n;
+        const double u = flat ? (double)(k + 1) * ((c < 0 && (k & 1)) ? -1.0 : 1.0) : sin((double)(k + 1) * wp) / s;
+        tab[n] = make_float2((float)(cos((double)(len - n) * wp) * inv), (float)((double)wi * u * inv));
+    }
+}
+
 int goertzel_launch_generic(const float *in, float2 *out, long long nblocks, int len, float wr, float wi, hipStream_t st);
 int goertzel_launch_fast(const float *in, float2 *out, long long nblocks, int len, const float2 *tab, hipStream_t st);
 

@@ -215,24 +215,14 @@ struct grhip_goertzel_fc : HandleBase {
     // gri_goertzel::gri_setparms (gri_goertzel.cc:41-52)
     void setparms()
     {
-        const float w = 2.0 * M_PI * freq / rate;
-        wr = 2.0 * cosf(w);
-        wi = sinf(w);
+        goertzel_setparms(rate, freq, &wr, &wi);
         tab_valid = false;
     }
 
     int build_tab(hipStream_t st)
     {
         std::vector<float2> tab((size_t)len);
-        double c = 0.5 * (double)wr;
-        c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
-        const double wp = acos(c), s = sin(wp), inv = 1.0 / (double)len;
-        const bool flat = !(fabs(s) > 1e-300);                      // wr = +-2: U_k = (k + 1) (+-1)^k
-        for (int n = 0; n < len; ++n) {
-            const int k = len - 1 - n;
-            const double u = flat ? (double)(k + 1) * ((c < 0 && (k & 1)) ? -1.0 : 1.0) : sin((double)(k + 1) * wp) / s;
-            tab[n] = make_float2((float)(cos((double)(len - n) * wp) * inv), (float)((double)wi * u * inv));
-        }
+        goertzel_build_table(len, wr, wi, tab.data());
         int rc = drain(st);                                         // a launch may still read the old table
         if (rc) return rc;
         if ((rc = d_tab.reserve(tab.size() * sizeof(float2)))) return rc;

@@ -47,4 +47,11 @@ struct SquelchLaunch {
 size_t squelch_scratch_bytes(bool fast, const SquelchLaunch &a);
 int squelch_launch(bool fast, const SquelchLaunch &a, void *scratch, hipStream_t st);
 
+// The tail of a call on its own, for a block with another detector (ctcss.hip): walk or scan, then emit.  The caller has
+// written the mute bits of sample i of stream s to bit (i & 63) of word s * nwords + (i >> 6), nwords = (n + 63) / 64, at the
+// head of `scratch` (squelch_tail_scratch_bytes of it: the words, then the entries), and, where there is neither ramp
+// nor gating, state[s].state (the last flag) and produced[s] = n, which nothing downstream would write.
+size_t squelch_tail_scratch_bytes(const SquelchLaunch &a);
+int squelch_tail_launch(const SquelchLaunch &a, void *scratch, hipStream_t st);
+
 }  // namespace grhip

@@ -371,6 +371,7 @@ int emit(const SquelchLaunch &a, const Plan &p, const u64 *flags, const SquelchE
 }  // namespace
 
 size_t squelch_scratch_bytes(bool fast, const SquelchLaunch &a) { return a.n > 0 ? plan(fast, a).total : 0; }
+size_t squelch_tail_scratch_bytes(const SquelchLaunch &a) { return squelch_scratch_bytes(false, a); }
 
 int squelch_launch(bool fast, const SquelchLaunch &a, void *scratch, hipStream_t st)
 {
@@ -378,7 +379,6 @@ int squelch_launch(bool fast, const SquelchLaunch &a, void *scratch, hipStream_t
     const Plan p = plan(fast, a);
     char *sc = (char *)scratch;
     u64 *flags = (u64 *)(sc + p.flags_off);
-    SquelchEntry *entries = (SquelchEntry *)(sc + p.entries_off);
     double *ends = (double *)(sc + p.ends_off), *start = (double *)(sc + p.start_off);
     const int finish = !p.ramp_path && !a.gate;
     int rc;
@@ -392,6 +392,18 @@ int squelch_launch(bool fast, const SquelchLaunch &a, void *scratch, hipStream_t
     const double *from = p.chunked ? start : nullptr;
     if ((rc = a.cc ? detect<true, false>(a, p, from, nullptr, flags, finish, st) : detect<false, false>(a, p, from, nullptr, flags, finish, st)))
         return rc;
+    return squelch_tail_launch(a, scratch, st);
+}
+
+// From the flag words at the head of `scratch` to the outputs.  Without a ramp and without gating there is nothing to
+// walk: the detector that wrote the flags has stored the state (the last flag) and produced[s] = n itself.
+int squelch_tail_launch(const SquelchLaunch &a, void *scratch, hipStream_t st)
+{
+    if (a.n <= 0) return GRHIP_OK;
+    const Plan p = plan(false, a);
+    char *sc = (char *)scratch;
+    u64 *flags = (u64 *)(sc + p.flags_off);
+    SquelchEntry *entries = (SquelchEntry *)(sc + p.entries_off);
     if (p.ramp_path) {
         hipLaunchKernelGGL(sq_walk_kernel, dim3(a.nstreams), dim3(WAVE), 0, st, flags, entries, a.state, a.produced, a.n, p.nwords,
                            a.ramp, a.gate ? 1 : 0, a.table);

@@ -31,6 +31,7 @@
 //   gr_make_pwr_squelch_cc / _ff, gr_make_simple_squelch_cc
 //                                            <- the factories of the same names (general/gr_pwr_squelch_cc.h,
 //                                               general/gr_pwr_squelch_ff.h, general/gr_simple_squelch_cc.h)
+//   gr_make_ctcss_squelch_ff                 <- gr_make_ctcss_squelch_ff (general/gr_ctcss_squelch_ff.h)
 //
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
@@ -1467,4 +1468,57 @@ public:
 inline grhip_simple_squelch_cc_sptr gr_make_simple_squelch_cc(double threshold_db, double alpha = 0.0001, int device = 0)
 {
     return gnuradio::get_initial_sptr(new grhip_simple_squelch_cc_blk(threshold_db, alpha, device));
+}
+
+// ---------------------------------------------------------------------------
+// gr_ctcss_squelch_ff(rate, freq, level = 0.01, len = 0, ramp = 0, gate = false): gr_block over gr_squelch_base_ff;
+// general_work consumes every input and returns the items produced (general/gr_ctcss_squelch_ff.h:33-66,
+// gr_squelch_base_ff.cc:42-93).  The blocks of len samples run across general_work calls.
+// ---------------------------------------------------------------------------
+class grhip_ctcss_squelch_ff_blk;
+typedef boost::shared_ptr<grhip_ctcss_squelch_ff_blk> grhip_ctcss_squelch_ff_sptr;
+class grhip_ctcss_squelch_ff_blk : public gr_block {
+    grhip_ctcss_squelch_ff *d_h = nullptr;
+    grhip_ctcss_squelch_ff_blk(int rate, float freq, float level, int len, int ramp, bool gate, int device)
+        : gr_block("ctcss_squelch_ff", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(float)))
+    {
+        grhip_detail::check(grhip_ctcss_squelch_ff_create(&d_h, rate, freq, level, len, ramp, gate, device));
+    }
+    friend grhip_ctcss_squelch_ff_sptr gr_make_ctcss_squelch_ff(int, float, float, int, int, bool, int);
+public:
+    ~grhip_ctcss_squelch_ff_blk() { grhip_ctcss_squelch_ff_destroy(d_h); }
+    void set_mode(int mode) { grhip_detail::check(grhip_ctcss_squelch_ff_set_mode(d_h, mode)); }
+    float level() const { return grhip_ctcss_squelch_ff_level(d_h); }
+    void set_level(float level) { grhip_detail::check(grhip_ctcss_squelch_ff_set_level(d_h, level)); }
+    int len() const { return grhip_ctcss_squelch_ff_len(d_h); }
+    int ramp() const { return grhip_ctcss_squelch_ff_ramp(d_h); }
+    void set_ramp(int ramp) { grhip_detail::check(grhip_ctcss_squelch_ff_set_ramp(d_h, ramp)); }
+    bool gate() const { return grhip_ctcss_squelch_ff_gate(d_h) != 0; }
+    void set_gate(bool gate) { grhip_detail::check(grhip_ctcss_squelch_ff_set_gate(d_h, gate)); }
+    bool unmuted() const
+    {
+        int r = grhip_ctcss_squelch_ff_unmuted(d_h, 0);
+        grhip_detail::check(r);
+        return r != 0;
+    }
+    std::vector<float> squelch_range() const
+    {
+        std::vector<float> r(3);
+        grhip_detail::check(grhip_ctcss_squelch_ff_squelch_range(r.data()));
+        return r;
+    }
+    int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
+                     gr_vector_void_star &out) override
+    {
+        const int n = noutput_items < ninput_items[0] ? noutput_items : ninput_items[0];
+        int produced = 0;
+        grhip_detail::check(grhip_ctcss_squelch_ff_work(d_h, n, in[0], out[0], &produced));
+        consume_each(n);                                        /* use all the inputs, report the outputs copied */
+        return produced;
+    }
+};
+inline grhip_ctcss_squelch_ff_sptr gr_make_ctcss_squelch_ff(int rate, float freq, float level = 0.01, int len = 0, int ramp = 0,
+                                                            bool gate = false, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_ctcss_squelch_ff_blk(rate, freq, level, len, ramp, gate, device));
 }

@@ -1509,6 +1509,64 @@ GRHIP_API int grhip_simple_squelch_cc_work_device(grhip_simple_squelch_cc *h, in
 GRHIP_API int grhip_pwr_squelch_chunk(void);
 
 /* ======================================================================
+ * gr_ctcss_squelch_ff
+ *   replaces gr_make_ctcss_squelch_ff(int rate, float freq, float level = 0.01, int len = 0,
+ *       int ramp = 0, bool gate = false)
+ *   general/gr_ctcss_squelch_ff.cc:53-85 (constructor: len == 0 is (int)(rate / 10.0); the guards are
+ *   the adjacent tones of the 38 standard ones, found by an exact float compare, or freq * 0.98 /
+ *   freq * 1.02, formed in double and stored to float, for a non-standard tone and on the outer side
+ *   of the first and the last; d_mute starts true), :97-112 (update_state),
+ *   filter/gri_goertzel.cc:36-75 (the filters), general/gr_squelch_base_ff.cc:42-93 (the machine)
+ * Streams, buffers, produced[], the overlap rule, work / work_device, unmuted and the machine are
+ * those of the power squelch blocks above.  The detector: three Goertzel filters (left guard,
+ * tone, right guard) take every sample, y = (x + wr * d1) - d2 in float and unfused; after every
+ * len samples their outputs ((0.5 * wr * d1 - d2) / len in double, (wi * d1) / len in float) give
+ * |l|, |c|, |r| as (float)sqrt((double)re * re + (double)im * im), the filters are cleared and
+ * d_mute = c < level || c < l || c < r (a NaN level never mutes); the sample that completes a block
+ * already sees its decision and the decision holds until the next block ends.  Blocks run across
+ * calls: a stream keeps the raw samples of its unfinished block (at most len - 1) and its last
+ * decision on the device, and a block is evaluated whole, from a zero start, in the call that
+ * completes it, so in each mode a stream's outputs depend on the concatenated input alone and never
+ * on where the calls cut it.  After set_mode a block in progress is evaluated in the mode in force
+ * when it completes.
+ * GRHIP_MODE_GENERIC: the float recurrences in the reference's order, bit for bit.  Every other
+ * mode: the closed form sum_n x[n] tab[n] against three tables built in double (goertzel_fc's FAST
+ * form); its magnitudes differ from the recurrence's by what the float recurrence itself loses
+ * (DESIGN.md 4.18), so the flags are the same wherever no comparison is that close to a tie.
+ * state(): the machine's state, ramp position and envelope, d_mute, and the length of the
+ * unfinished block.  tones(): the three frequencies.  last_magnitudes(): |l|, |c|, |r| of the
+ * blocks of stream s that the last work call completed (3 floats each, cap_blocks of room);
+ * returns their number; for tests.  set_streams restarts every stream (muted, d_mute true, nothing
+ * carried); set_level, set_ramp, set_gate and set_mode keep everything and hold from the next call.
+ * GRHIP_EINVAL: rate <= 0, a non-finite freq, len < 0, ramp < 0 (or past 2^24), S < 1, n_in < 0;
+ * GRHIP_ERANGE: the effective len outside 1 .. 2^20, set_ramp(0) while a stream is in a ramp.
+ * Deviations: finite samples only (hypotf special-cases the others); len is capped at 2^20; the
+ * reference accepts len < 1 and then never decides; set_ramp(0) inside a ramp as above.
+ * ====================================================================== */
+typedef struct grhip_ctcss_squelch_ff grhip_ctcss_squelch_ff;
+GRHIP_API int grhip_ctcss_squelch_ff_create(grhip_ctcss_squelch_ff **h, int rate, float freq, float level, int len, int ramp,
+                                            int gate, int device);
+GRHIP_API void grhip_ctcss_squelch_ff_destroy(grhip_ctcss_squelch_ff *h);
+GRHIP_API int grhip_ctcss_squelch_ff_set_mode(grhip_ctcss_squelch_ff *h, int mode);
+GRHIP_API int grhip_ctcss_squelch_ff_set_streams(grhip_ctcss_squelch_ff *h, int nstreams);
+GRHIP_API float grhip_ctcss_squelch_ff_level(grhip_ctcss_squelch_ff *h);
+GRHIP_API int grhip_ctcss_squelch_ff_set_level(grhip_ctcss_squelch_ff *h, float level);
+GRHIP_API int grhip_ctcss_squelch_ff_len(grhip_ctcss_squelch_ff *h);
+GRHIP_API int grhip_ctcss_squelch_ff_ramp(grhip_ctcss_squelch_ff *h);
+GRHIP_API int grhip_ctcss_squelch_ff_set_ramp(grhip_ctcss_squelch_ff *h, int ramp);
+GRHIP_API int grhip_ctcss_squelch_ff_gate(grhip_ctcss_squelch_ff *h);
+GRHIP_API int grhip_ctcss_squelch_ff_set_gate(grhip_ctcss_squelch_ff *h, int gate);
+GRHIP_API int grhip_ctcss_squelch_ff_squelch_range(float *range);
+GRHIP_API int grhip_ctcss_squelch_ff_unmuted(grhip_ctcss_squelch_ff *h, int s);
+GRHIP_API int grhip_ctcss_squelch_ff_state(grhip_ctcss_squelch_ff *h, int s, int *state, int *ramped, double *envelope, int *mute,
+                                           int *pending);
+GRHIP_API int grhip_ctcss_squelch_ff_tones(grhip_ctcss_squelch_ff *h, float *f_l, float *f_c, float *f_r);
+GRHIP_API int grhip_ctcss_squelch_ff_last_magnitudes(grhip_ctcss_squelch_ff *h, int s, float *out, int cap_blocks);
+GRHIP_API int grhip_ctcss_squelch_ff_work(grhip_ctcss_squelch_ff *h, int n_in, const void *in, void *out, int *produced);
+GRHIP_API int grhip_ctcss_squelch_ff_work_device(grhip_ctcss_squelch_ff *h, int n_in, const void *d_in, void *d_out,
+                                                 int *d_produced, void *stream);
+
+/* ======================================================================
  * gr_pfb_channelizer_ccf
  *   replaces gr_make_pfb_channelizer_ccf(unsigned numchans,
  *       const std::vector<float>& taps, float oversample_rate)
