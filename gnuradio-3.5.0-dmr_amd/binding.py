@@ -21,6 +21,7 @@ __all__ = [
     "complex_to_mag_squared", "single_pole_iir_filter_ff", "nlog10_ff", "keep_one_in_n",
     "logpwrfft_c", "logpwrfft_f", "window_blackmanharris",
     "pwr_squelch_cc", "pwr_squelch_ff", "simple_squelch_cc", "ctcss_squelch_ff",
+    "agc_cc", "agc_ff", "agc2_cc", "agc2_ff",
     "WIN_HAMMING", "WIN_HANN", "WIN_BLACKMAN", "WIN_RECTANGULAR", "WIN_KAISER", "WIN_BLACKMAN_hARRIS",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
     "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
@@ -1955,6 +1956,144 @@ class ctcss_squelch_ff(_squelch_streams, _ramp_gate):
         f = self._fn("last_magnitudes", [C.c_void_p, C.c_int, C.c_void_p, C.c_int])
         got = _check(f(self._h, int(stream), _ptr(out), int(n_blocks)))
         return out[:got]
+
+
+class _agc(_Block):
+    """what the four gain loops share: work(x) takes streams x n_in items back to back and returns as many; every
+    stream's gain carries across calls.  The setters act at once (they hold from the next work call), as the
+    reference's do; set_gain sets every stream's gain."""
+    _name = None
+    _dtype = np.complex64
+
+    def __init__(self):
+        _Block.__init__(self)
+        self._destroy = "grhip_%s_destroy" % self._name
+        self._streams = 1
+
+    def _fn(self, name, argtypes=None, restype=None):
+        f = getattr(lib(), "grhip_%s_%s" % (self._name, name))
+        if argtypes is not None:
+            f.argtypes = argtypes
+        if restype is not None:
+            f.restype = restype
+        return f
+
+    def _get(self, name):
+        return self._fn(name, [C.c_void_p], C.c_float)(self._h)
+
+    def _set(self, name, v):
+        _check(self._fn("set_" + name, [C.c_void_p, C.c_float])(self._h, float(v)))
+
+    def set_mode(self, mode):
+        _check(self._fn("set_mode", [C.c_void_p, C.c_int])(self._h, int(mode)))
+
+    def set_streams(self, nstreams):
+        """sets every stream's gain to the constructor's"""
+        _check(self._fn("set_streams", [C.c_void_p, C.c_int])(self._h, int(nstreams)))
+        self._streams = int(nstreams)
+
+    def history(self):
+        return 1
+
+    def reference(self):
+        return self._get("reference")
+
+    def set_reference(self, reference):
+        self._set("reference", reference)
+
+    def max_gain(self):
+        return self._get("max_gain")
+
+    def set_max_gain(self, max_gain):
+        self._set("max_gain", max_gain)
+
+    def gain(self, stream=0):
+        v = C.c_float(0)
+        _check(self._fn("gain", [C.c_void_p, C.c_int, C.POINTER(C.c_float)])(self._h, int(stream), C.byref(v)))
+        return np.float32(v.value)
+
+    def set_gain(self, gain):
+        self._set("gain", gain)
+
+    def work(self, input_items, n_in=None):
+        x = np.ascontiguousarray(input_items, dtype=self._dtype).reshape(-1)
+        if n_in is None:
+            n_in = len(x) // self._streams
+        if len(x) < n_in * self._streams:
+            raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
+        out = np.zeros(max(n_in * self._streams, 1), dtype=self._dtype)
+        _check(self._fn("work", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])(self._h, int(n_in), _ptr(x), _ptr(out)))
+        return out[:n_in * self._streams]
+
+    def work_device(self, n_in, d_in, d_out, stream=None):
+        """device buffers; does not synchronise"""
+        f = self._fn("work_device", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
+        return _check(f(self._h, int(n_in), _devptr(d_in), _devptr(d_out), _stream(stream)))
+
+    @staticmethod
+    def chunk():
+        """items per chunk of the chunked form of agc_cc / agc_ff"""
+        return lib().grhip_agc_chunk()
+
+
+class _agc1(_agc):
+    def __init__(self, rate=1e-4, reference=1.0, gain=1.0, max_gain=0.0, device=0):
+        _agc.__init__(self)
+        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_float, C.c_float, C.c_float, C.c_float, C.c_int])
+        _check(f(C.byref(self._h), float(rate), float(reference), float(gain), float(max_gain), int(device)))
+
+    def rate(self):
+        return self._get("rate")
+
+    def set_rate(self, rate):
+        self._set("rate", rate)
+
+
+class _agc2(_agc):
+    def __init__(self, attack_rate=1e-1, decay_rate=1e-2, reference=1.0, gain=1.0, max_gain=0.0, device=0):
+        _agc.__init__(self)
+        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int])
+        _check(f(C.byref(self._h), float(attack_rate), float(decay_rate), float(reference), float(gain), float(max_gain),
+                 int(device)))
+
+    def attack_rate(self):
+        return self._get("attack_rate")
+
+    def set_attack_rate(self, rate):
+        self._set("attack_rate", rate)
+
+    def decay_rate(self):
+        return self._get("decay_rate")
+
+    def set_decay_rate(self, rate):
+        self._set("decay_rate", rate)
+
+
+class agc_cc(_agc1):
+    """gr.agc_cc(rate=1e-4, reference=1.0, gain=1.0, max_gain=0.0) (general/gr_agc_cc.i): out = in * gain, then
+    gain += rate * (reference - |out|), clamped to max_gain where that is positive.  MODE_GENERIC is the reference's
+    float recurrence bit for bit; every other mode runs calls of more than chunk() items in chunks."""
+    _name = "agc_cc"
+
+
+class agc_ff(_agc1):
+    """gr.agc_ff(rate=1e-4, reference=1.0, gain=1.0, max_gain=0.0) (general/gr_agc_ff.i): agc_cc on floats"""
+    _name = "agc_ff"
+    _dtype = np.float32
+
+
+class agc2_cc(_agc2):
+    """gr.agc2_cc(attack_rate=1e-1, decay_rate=1e-2, reference=1.0, gain=1.0, max_gain=0.0) (general/gr_agc2_cc.i):
+    the rate is attack_rate where |out| - reference exceeds the gain and decay_rate otherwise; a negative gain
+    becomes 10e-5.  Every mode is the reference's recurrence bit for bit."""
+    _name = "agc2_cc"
+
+
+class agc2_ff(_agc2):
+    """gr.agc2_ff(attack_rate=1e-1, decay_rate=1e-2, reference=1.0, gain=1.0, max_gain=0.0) (general/gr_agc2_ff.i):
+    agc2_cc on floats, with the rate test on the magnitude of |out| - reference as the reference has it"""
+    _name = "agc2_ff"
+    _dtype = np.float32
 
 
 class keep_one_in_n(_Block):

@@ -32,6 +32,9 @@
 //                                            <- the factories of the same names (general/gr_pwr_squelch_cc.h,
 //                                               general/gr_pwr_squelch_ff.h, general/gr_simple_squelch_cc.h)
 //   gr_make_ctcss_squelch_ff                 <- gr_make_ctcss_squelch_ff (general/gr_ctcss_squelch_ff.h)
+//   gr_make_agc_cc / _ff, gr_make_agc2_cc / _ff
+//                                            <- the factories of the same names (general/gr_agc_cc.h, gr_agc_ff.h,
+//                                               gr_agc2_cc.h, gr_agc2_ff.h)
 //
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
@@ -1522,3 +1525,84 @@ inline grhip_ctcss_squelch_ff_sptr gr_make_ctcss_squelch_ff(int rate, float freq
 {
     return gnuradio::get_initial_sptr(new grhip_ctcss_squelch_ff_blk(rate, freq, level, len, ramp, gate, device));
 }
+
+// ---------------------------------------------------------------------------
+// gr_agc_cc / _ff (rate = 1e-4, reference = 1.0, gain = 1.0, max_gain = 0.0) and gr_agc2_cc / _ff (attack_rate = 1e-1,
+// decay_rate = 1e-2, reference = 1.0, gain = 1.0, max_gain = 0.0): gr_sync_blocks, history 1, with the accessors and
+// setters of gri_agc_cc / gri_agc2_cc that the reference's blocks inherit (general/gr_agc_cc.h:33-52,
+// gr_agc2_cc.h:34-54).  The gain carries across work calls; the setters act at once.
+// ---------------------------------------------------------------------------
+#define GRHIP_AGC_BLK_COMMON(NAME, ITEM)                                                                                 \
+    public:                                                                                                              \
+        ~grhip_##NAME##_blk() { grhip_##NAME##_destroy(d_h); }                                                           \
+        void set_mode(int mode) { grhip_detail::check(grhip_##NAME##_set_mode(d_h, mode)); }                             \
+        float reference() const { return grhip_##NAME##_reference(d_h); }                                                \
+        float max_gain() const { return grhip_##NAME##_max_gain(d_h); }                                                  \
+        float gain() const                                                                                               \
+        {                                                                                                                \
+            float g = 0.f;                                                                                               \
+            grhip_detail::check(grhip_##NAME##_gain(d_h, 0, &g));                                                        \
+            return g;                                                                                                    \
+        }                                                                                                                \
+        void set_reference(float reference) { grhip_detail::check(grhip_##NAME##_set_reference(d_h, reference)); }       \
+        void set_gain(float gain) { grhip_detail::check(grhip_##NAME##_set_gain(d_h, gain)); }                           \
+        void set_max_gain(float max_gain) { grhip_detail::check(grhip_##NAME##_set_max_gain(d_h, max_gain)); }           \
+        int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override                    \
+        {                                                                                                                \
+            grhip_detail::check(grhip_##NAME##_work(d_h, noutput_items, in[0], out[0]));                                 \
+            return noutput_items;                                                                                        \
+        }                                                                                                                \
+    }
+
+#define GRHIP_AGC_BLK(NAME, ITEM)                                                                                        \
+    class grhip_##NAME##_blk;                                                                                            \
+    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                   \
+    class grhip_##NAME##_blk : public gr_sync_block {                                                                    \
+        grhip_##NAME *d_h = nullptr;                                                                                     \
+        grhip_##NAME##_blk(float rate, float reference, float gain, float max_gain, int device)                          \
+            : gr_sync_block(#NAME, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM)))   \
+        {                                                                                                                \
+            grhip_detail::check(grhip_##NAME##_create(&d_h, rate, reference, gain, max_gain, device));                   \
+        }                                                                                                                \
+        friend grhip_##NAME##_sptr gr_make_##NAME(float, float, float, float, int);                                      \
+    public:                                                                                                              \
+        float rate() const { return grhip_##NAME##_rate(d_h); }                                                          \
+        void set_rate(float rate) { grhip_detail::check(grhip_##NAME##_set_rate(d_h, rate)); }                           \
+    GRHIP_AGC_BLK_COMMON(NAME, ITEM);                                                                                    \
+    inline grhip_##NAME##_sptr gr_make_##NAME(float rate = 1e-4, float reference = 1.0, float gain = 1.0,                \
+                                              float max_gain = 0.0, int device = 0)                                      \
+    {                                                                                                                    \
+        return gnuradio::get_initial_sptr(new grhip_##NAME##_blk(rate, reference, gain, max_gain, device));              \
+    }
+
+#define GRHIP_AGC2_BLK(NAME, ITEM)                                                                                       \
+    class grhip_##NAME##_blk;                                                                                            \
+    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                   \
+    class grhip_##NAME##_blk : public gr_sync_block {                                                                    \
+        grhip_##NAME *d_h = nullptr;                                                                                     \
+        grhip_##NAME##_blk(float attack_rate, float decay_rate, float reference, float gain, float max_gain, int device) \
+            : gr_sync_block(#NAME, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM)))   \
+        {                                                                                                                \
+            grhip_detail::check(grhip_##NAME##_create(&d_h, attack_rate, decay_rate, reference, gain, max_gain, device)); \
+        }                                                                                                                \
+        friend grhip_##NAME##_sptr gr_make_##NAME(float, float, float, float, float, int);                               \
+    public:                                                                                                              \
+        float attack_rate() const { return grhip_##NAME##_attack_rate(d_h); }                                            \
+        float decay_rate() const { return grhip_##NAME##_decay_rate(d_h); }                                              \
+        void set_attack_rate(float rate) { grhip_detail::check(grhip_##NAME##_set_attack_rate(d_h, rate)); }             \
+        void set_decay_rate(float rate) { grhip_detail::check(grhip_##NAME##_set_decay_rate(d_h, rate)); }               \
+    GRHIP_AGC_BLK_COMMON(NAME, ITEM);                                                                                    \
+    inline grhip_##NAME##_sptr gr_make_##NAME(float attack_rate = 1e-1, float decay_rate = 1e-2, float reference = 1.0,  \
+                                              float gain = 1.0, float max_gain = 0.0, int device = 0)                    \
+    {                                                                                                                    \
+        return gnuradio::get_initial_sptr(new grhip_##NAME##_blk(attack_rate, decay_rate, reference, gain, max_gain,     \
+                                                                 device));                                               \
+    }
+
+GRHIP_AGC_BLK(agc_cc, gr_complex)
+GRHIP_AGC_BLK(agc_ff, float)
+GRHIP_AGC2_BLK(agc2_cc, gr_complex)
+GRHIP_AGC2_BLK(agc2_ff, float)
+#undef GRHIP_AGC_BLK
+#undef GRHIP_AGC2_BLK
+#undef GRHIP_AGC_BLK_COMMON

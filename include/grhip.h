@@ -1567,6 +1567,129 @@ GRHIP_API int grhip_ctcss_squelch_ff_work_device(grhip_ctcss_squelch_ff *h, int 
                                                  int *d_produced, void *stream);
 
 /* ======================================================================
+ * The gain loops.  A handle takes S streams back to back in `in` ([S][n_in], S = 1 after create);
+ * stream s reads from in + s * n_in items and writes as many items from out + s * n_in (sync blocks,
+ * history 1).  `out` may not overlap `in`.  work / work_device return GRHIP_OK; n_in == 0 is a
+ * successful no-op; work_device (device buffers) does not synchronise.  Per stream the block
+ * remembers its gain, one float on the device, across calls.  set_streams resizes that and sets
+ * every stream's gain to the constructor's; set_gain sets every stream's gain (the reference's block
+ * has one); gain(h, s, &g) reads one stream's and waits for the handle's queued work.  The other
+ * setters act at once, as the reference's do: they hold from the next work call.  All state and
+ * all parameters are float.  Nothing is refused at construction, the reference checks nothing; NaN
+ * and infinities go through the arithmetic as they do there.
+ * GRHIP_EINVAL: S < 1, n_in < 0, a null pointer, overlapping buffers.
+ *
+ * gr_agc_cc
+ *   replaces gr_make_agc_cc(float rate = 1e-4, float reference = 1.0, float gain = 1.0,
+ *       float max_gain = 0.0)
+ *   general/gri_agc_cc.h:53-61 (scale), :43-51 (accessors), general/gr_agc_cc.cc:47-56 (work)
+ * out = in * g (two rounded float products), then g += rate * (reference - sqrtf(re * re + im * im))
+ * on the OUTPUT's parts, every product, the add and the square root rounded once, then
+ * if (max_gain > 0 && g > max_gain) g = max_gain.
+ * GRHIP_MODE_GENERIC: that recurrence in order, one wavefront per stream, bit for bit.  Every other
+ * mode, for calls of more than grhip_agc_chunk() items: with g >= 0 a step is
+ * g' = min(a g + b, M), a = 1 - rate |x|, b = rate reference, and such maps compose; the call is cut
+ * into chunks of grhip_agc_chunk() items from its first item, every chunk's composed map is formed in
+ * double and chained, and the reference's float steps then run again from every chunk's start gain
+ * (rounded to float).  A chunk holding a sample with rate |x| > 1, an infinity or a NaN, and a chunk
+ * entered with a negative gain, is walked sample by sample in the float arithmetic instead, so such
+ * input costs time and never correctness.  The gain then deviates from the float64 recurrence by no
+ * more than the serial float recurrence itself does; within that the result
+ * depends on where the calls cut the input.  The serial walk runs whatever the mode for calls of at
+ * most one chunk and where rate < 0, reference < 0 or rate, reference or max_gain is not finite.
+ * ====================================================================== */
+typedef struct grhip_agc_cc grhip_agc_cc;
+GRHIP_API int grhip_agc_cc_create(grhip_agc_cc **h, float rate, float reference, float gain, float max_gain, int device);
+GRHIP_API void grhip_agc_cc_destroy(grhip_agc_cc *h);
+GRHIP_API int grhip_agc_cc_set_mode(grhip_agc_cc *h, int mode);
+GRHIP_API int grhip_agc_cc_set_streams(grhip_agc_cc *h, int nstreams);
+GRHIP_API float grhip_agc_cc_rate(grhip_agc_cc *h);
+GRHIP_API float grhip_agc_cc_reference(grhip_agc_cc *h);
+GRHIP_API float grhip_agc_cc_max_gain(grhip_agc_cc *h);
+GRHIP_API int grhip_agc_cc_gain(grhip_agc_cc *h, int s, float *gain);
+GRHIP_API int grhip_agc_cc_set_rate(grhip_agc_cc *h, float rate);
+GRHIP_API int grhip_agc_cc_set_reference(grhip_agc_cc *h, float reference);
+GRHIP_API int grhip_agc_cc_set_max_gain(grhip_agc_cc *h, float max_gain);
+GRHIP_API int grhip_agc_cc_set_gain(grhip_agc_cc *h, float gain);
+GRHIP_API int grhip_agc_cc_work(grhip_agc_cc *h, int n_in, const void *in, void *out);
+GRHIP_API int grhip_agc_cc_work_device(grhip_agc_cc *h, int n_in, const void *d_in, void *d_out, void *stream);
+
+/* gr_agc_ff
+ *   replaces gr_make_agc_ff(float rate = 1e-4, float reference = 1.0, float gain = 1.0,
+ *       float max_gain = 0.0)
+ *   general/gri_agc_ff.h:51-57 (scale), general/gr_agc_ff.cc:45-54 (work)
+ * As agc_cc on floats: g += (reference - fabsf(out)) * rate, the same clamp, the same two modes. */
+typedef struct grhip_agc_ff grhip_agc_ff;
+GRHIP_API int grhip_agc_ff_create(grhip_agc_ff **h, float rate, float reference, float gain, float max_gain, int device);
+GRHIP_API void grhip_agc_ff_destroy(grhip_agc_ff *h);
+GRHIP_API int grhip_agc_ff_set_mode(grhip_agc_ff *h, int mode);
+GRHIP_API int grhip_agc_ff_set_streams(grhip_agc_ff *h, int nstreams);
+GRHIP_API float grhip_agc_ff_rate(grhip_agc_ff *h);
+GRHIP_API float grhip_agc_ff_reference(grhip_agc_ff *h);
+GRHIP_API float grhip_agc_ff_max_gain(grhip_agc_ff *h);
+GRHIP_API int grhip_agc_ff_gain(grhip_agc_ff *h, int s, float *gain);
+GRHIP_API int grhip_agc_ff_set_rate(grhip_agc_ff *h, float rate);
+GRHIP_API int grhip_agc_ff_set_reference(grhip_agc_ff *h, float reference);
+GRHIP_API int grhip_agc_ff_set_max_gain(grhip_agc_ff *h, float max_gain);
+GRHIP_API int grhip_agc_ff_set_gain(grhip_agc_ff *h, float gain);
+GRHIP_API int grhip_agc_ff_work(grhip_agc_ff *h, int n_in, const void *in, void *out);
+GRHIP_API int grhip_agc_ff_work_device(grhip_agc_ff *h, int n_in, const void *d_in, void *d_out, void *stream);
+
+/* gr_agc2_cc
+ *   replaces gr_make_agc2_cc(float attack_rate = 1e-1, float decay_rate = 1e-2,
+ *       float reference = 1.0, float gain = 1.0, float max_gain = 0.0)
+ *   general/gri_agc2_cc.h:54-76 (scale), general/gr_agc2_cc.cc:47-56 (work)
+ * out = in * g; tmp = -reference + sqrtf(re * re + im * im) on the output; rate = (tmp > g) ?
+ * attack_rate : decay_rate; g -= tmp * rate; if (g < 0) g = 10e-5; then the clamp of agc_cc.  The
+ * rate switches on a comparison with the gain, so there is no composed form: every mode runs the
+ * serial walk, one wavefront per stream, bit for bit the reference. */
+typedef struct grhip_agc2_cc grhip_agc2_cc;
+GRHIP_API int grhip_agc2_cc_create(grhip_agc2_cc **h, float attack_rate, float decay_rate, float reference, float gain,
+                                   float max_gain, int device);
+GRHIP_API void grhip_agc2_cc_destroy(grhip_agc2_cc *h);
+GRHIP_API int grhip_agc2_cc_set_mode(grhip_agc2_cc *h, int mode);
+GRHIP_API int grhip_agc2_cc_set_streams(grhip_agc2_cc *h, int nstreams);
+GRHIP_API float grhip_agc2_cc_attack_rate(grhip_agc2_cc *h);
+GRHIP_API float grhip_agc2_cc_decay_rate(grhip_agc2_cc *h);
+GRHIP_API float grhip_agc2_cc_reference(grhip_agc2_cc *h);
+GRHIP_API float grhip_agc2_cc_max_gain(grhip_agc2_cc *h);
+GRHIP_API int grhip_agc2_cc_gain(grhip_agc2_cc *h, int s, float *gain);
+GRHIP_API int grhip_agc2_cc_set_attack_rate(grhip_agc2_cc *h, float rate);
+GRHIP_API int grhip_agc2_cc_set_decay_rate(grhip_agc2_cc *h, float rate);
+GRHIP_API int grhip_agc2_cc_set_reference(grhip_agc2_cc *h, float reference);
+GRHIP_API int grhip_agc2_cc_set_max_gain(grhip_agc2_cc *h, float max_gain);
+GRHIP_API int grhip_agc2_cc_set_gain(grhip_agc2_cc *h, float gain);
+GRHIP_API int grhip_agc2_cc_work(grhip_agc2_cc *h, int n_in, const void *in, void *out);
+GRHIP_API int grhip_agc2_cc_work_device(grhip_agc2_cc *h, int n_in, const void *d_in, void *d_out, void *stream);
+
+/* gr_agc2_ff
+ *   replaces gr_make_agc2_ff(float attack_rate = 1e-1, float decay_rate = 1e-2,
+ *       float reference = 1.0, float gain = 1.0, float max_gain = 0.0)
+ *   general/gri_agc2_ff.h:55-75 (scale), general/gr_agc2_ff.cc:48-57 (work)
+ * As agc2_cc on floats with tmp = fabsf(out) - reference and the rate test fabsf(tmp) > g (the
+ * reference's two agc2 blocks differ in this test, and so do these). */
+typedef struct grhip_agc2_ff grhip_agc2_ff;
+GRHIP_API int grhip_agc2_ff_create(grhip_agc2_ff **h, float attack_rate, float decay_rate, float reference, float gain,
+                                   float max_gain, int device);
+GRHIP_API void grhip_agc2_ff_destroy(grhip_agc2_ff *h);
+GRHIP_API int grhip_agc2_ff_set_mode(grhip_agc2_ff *h, int mode);
+GRHIP_API int grhip_agc2_ff_set_streams(grhip_agc2_ff *h, int nstreams);
+GRHIP_API float grhip_agc2_ff_attack_rate(grhip_agc2_ff *h);
+GRHIP_API float grhip_agc2_ff_decay_rate(grhip_agc2_ff *h);
+GRHIP_API float grhip_agc2_ff_reference(grhip_agc2_ff *h);
+GRHIP_API float grhip_agc2_ff_max_gain(grhip_agc2_ff *h);
+GRHIP_API int grhip_agc2_ff_gain(grhip_agc2_ff *h, int s, float *gain);
+GRHIP_API int grhip_agc2_ff_set_attack_rate(grhip_agc2_ff *h, float rate);
+GRHIP_API int grhip_agc2_ff_set_decay_rate(grhip_agc2_ff *h, float rate);
+GRHIP_API int grhip_agc2_ff_set_reference(grhip_agc2_ff *h, float reference);
+GRHIP_API int grhip_agc2_ff_set_max_gain(grhip_agc2_ff *h, float max_gain);
+GRHIP_API int grhip_agc2_ff_set_gain(grhip_agc2_ff *h, float gain);
+GRHIP_API int grhip_agc2_ff_work(grhip_agc2_ff *h, int n_in, const void *in, void *out);
+GRHIP_API int grhip_agc2_ff_work_device(grhip_agc2_ff *h, int n_in, const void *d_in, void *d_out, void *stream);
+/* items per chunk of the chunked form of agc_cc / agc_ff */
+GRHIP_API int grhip_agc_chunk(void);
+
+/* ======================================================================
  * gr_pfb_channelizer_ccf
  *   replaces gr_make_pfb_channelizer_ccf(unsigned numchans,
  *       const std::vector<float>& taps, float oversample_rate)
