@@ -23,6 +23,15 @@
  *  - *_work_device(..., stream): same contract with DEVICE pointers; enqueues
  *    on `stream` (a hipStream_t passed as void*; NULL = the handle's own
  *    stream) and returns without synchronising.
+ *  - device pointers need the natural alignment of their item (1, 2, 4 or 8
+ *    bytes; a gr_buffer's read and write pointers advance by whole items) and
+ *    nothing more, and a stream stride is any item count.  Wider alignment, or
+ *    a stride that keeps every stream on a 16-byte boundary, only selects a
+ *    faster path; the results are the same.  A pointer that is not aligned to
+ *    its item is the caller's error: some entries return GRHIP_EINVAL for it,
+ *    at the others the behaviour is undefined.  Exceptions are stated at the entry
+ *    (tests/test_gpu_device_offsets.py lists them and runs every other entry
+ *    at every item offset).
  *  - setters latch a new value that takes effect at the next work call, which
  *    then returns 0 items once, exactly as the reference does
  *    (filter/gr_fir_filter_XXX.cc.t:74-79,
@@ -264,8 +273,12 @@ GRHIP_API int grhip_xlating_demod_work_device(grhip_xlating_demod *h, int noutpu
  * n_samples items each; output s at d_out + s*out_stride_items floats,
  * n_samples/decimation items.  Does not touch the handle's streaming state.
  * FAST modes: every shape a batched engine takes.  GRHIP_MODE_GENERIC (bit-exact against the reference's generic
- * build): decimation 1 / 2 / 4 with at least 8 taps and 2048 outputs per capture, 16-byte aligned d_in and an even
- * in_stride_items; other shapes return GRHIP_EINVAL (run them a capture at a time through work_device). */
+ * build): decimation 1 / 2 / 4 with at least 8 taps and a tile that fits local memory,
+ * decimation * (1024 + ntaps / decimation + 3) * 8 + ntaps * 8 + 64 <= 150 KiB (about 9000 taps at decimation 1, 7500
+ * at 4), and with more than one capture an even in_stride_items (an exception to the common rule on strides: every
+ * capture must sit at the same offset from a 16-byte boundary; d_in itself needs only a complex item's alignment);
+ * other shapes, an odd in_stride_items among them, return GRHIP_EINVAL and write nothing (run them a capture at a
+ * time through work_device). */
 GRHIP_API int grhip_xlating_demod_run_captures_device(grhip_xlating_demod *h, int n_streams,
                                                       size_t n_samples, const void *d_in,
                                                       size_t in_stride_items, void *d_out,
