@@ -1,7 +1,11 @@
-"""ctypes binding of libgrhip.so.  See include/grhip.h for the contract."""
+"""ctypes binding of libgrhip.so.  See include/grhip.h for the contract.
+
+The header is also where every C signature comes from: signatures() parses its GRHIP_API prototypes and lib()
+applies them to the loaded library once.  A new block needs no signature code here."""
 import ctypes as C
 import math
 import os
+import re
 
 import numpy as np
 
@@ -36,6 +40,7 @@ MODE_FAST_REFTAPS = 3  # FAST + the reference's tap-angle quantisation reproduce
 WORK_DONE = 0x7fffffff  # GRHIP_WORK_DONE: not an error, not an item count
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+_HEADER = os.path.join(_HERE, "..", "include", "grhip.h")      # where the Makefile finds it too
 _LIB = None
 
 
@@ -43,6 +48,55 @@ class GrhipError(RuntimeError):
     def __init__(self, code, detail=""):
         self.code = code
         RuntimeError.__init__(self, "grhip error %d (%s): %s" % (code, strerror(code), detail))
+
+
+# ----------------------------------------------------------------------------
+# the C signatures, read from include/grhip.h
+# ----------------------------------------------------------------------------
+_CTYPES = {"int": C.c_int, "unsigned": C.c_uint, "short": C.c_short, "long long": C.c_longlong,
+           "unsigned long": C.c_ulong, "unsigned long long": C.c_ulonglong, "size_t": C.c_size_t,
+           "float": C.c_float, "double": C.c_double}
+_PROTOTYPE = re.compile(r"GRHIP_API\s+([\w\s*]+?)(\w+)\s*\(([^()]*)\)\s*;")
+
+
+def _ctype(text, decl, returned=False):
+    """the ctypes twin of one parameter (type and optional name) or of a return type"""
+    words = [w for w in text.replace("*", " * ").split() if w != "const"]
+    if "*" in words:                            # every pointer parameter travels as an address
+        if not returned:
+            return C.c_void_p
+        if words == ["char", "*"]:
+            return C.c_char_p
+    elif returned and words == ["void"]:
+        return None
+    else:
+        for t in [words] if returned else [words, words[:-1]]:
+            if " ".join(t) in _CTYPES:
+                return _CTYPES[" ".join(t)]
+    raise ValueError("grhip.h: no ctypes mapping for '%s' in: %s" % (" ".join(text.split()), decl))
+
+
+def signatures(header_text=None):
+    """{name: (restype, [argtypes])} of every GRHIP_API prototype of include/grhip.h (or of header_text).  Pure: it
+    does not load the library.  A GRHIP_API that does not parse, or a type without a mapping, is an error."""
+    if header_text is None:
+        try:
+            with open(_HEADER) as f:
+                header_text = f.read()
+        except OSError:
+            raise ImportError("the C header of libgrhip.so is missing: %s" % os.path.normpath(_HEADER))
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header_text, flags=re.S)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", "", text, flags=re.M)
+    table = {}
+    for m in re.finditer(r"\bGRHIP_API\b", text):
+        decl = " ".join(text[m.start():].partition(";")[0].split()) + ";"
+        p = _PROTOTYPE.match(text, m.start())
+        if p is None or p.group(2) in table:
+            raise ValueError("grhip.h: not one well-formed prototype: %s" % decl)
+        ret, name, params = p.groups()
+        params = [a for a in params.split(",") if a.split() not in ([], ["void"])]
+        table[name] = (_ctype(ret, decl, True), [_ctype(a, decl) for a in params])
+    return table
 
 
 def lib_path():
@@ -68,13 +122,12 @@ def lib():
         if not os.path.exists(p):
             raise ImportError("libgrhip.so not built (%s): run __graft_entry__.build(); "
                               "there is no CPU fallback" % p)
-        _LIB = C.CDLL(p)
-        _LIB.grhip_strerror.restype = C.c_char_p
-        _LIB.grhip_last_error.restype = C.c_char_p
-        _LIB.grhip_version.restype = C.c_char_p
-        for n in ("grhip_clock_recovery_mm_ff_mu", "grhip_clock_recovery_mm_ff_omega",
-                  "grhip_clock_recovery_mm_ff_gain_mu", "grhip_clock_recovery_mm_ff_gain_omega"):
-            getattr(_LIB, n).restype = C.c_float
+        L = C.CDLL(p)
+        # the one place that sets a signature: every entry gets the header's, before anything can call it
+        for name, (restype, argtypes) in signatures().items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+        _LIB = L
     return _LIB
 
 
@@ -86,15 +139,8 @@ def strerror(code):
 
 
 def _check(rc):
-    if rc < 0:
-        raise GrhipError(rc, lib().grhip_last_error().decode())
-    return rc
-
-
-def _raise_like_reference(rc):
-    """map status codes to the exception types the reference's SWIG layer
-    surfaces for the same precondition (RuntimeError via %exception,
-    gnuradio-core/src/lib/swig/gnuradio.i:33-44)."""
+    """a negative status becomes a GrhipError (a RuntimeError, the type the reference's SWIG layer surfaces for the
+    same preconditions: gnuradio-core/src/lib/swig/gnuradio.i:33-44)"""
     if rc < 0:
         raise GrhipError(rc, lib().grhip_last_error().decode())
     return rc
@@ -134,25 +180,49 @@ def _stream(s):
 
 
 class _Block(object):
-    _destroy = None
+    """one C handle.  Its entries are grhip_<_name>_<entry>; what most blocks share is spelled once here."""
+    _name = None
 
     def __init__(self):
         self._h = C.c_void_p(0)
+        self._streams = 1
 
     def __del__(self):
         try:
-            if self._h and self._destroy:
-                getattr(lib(), self._destroy)(self._h)
+            if self._h:
+                self._fn("destroy")(self._h)
                 self._h = C.c_void_p(0)
         except Exception:
             pass
+
+    def _fn(self, name):
+        return getattr(lib(), "grhip_%s_%s" % (self._name, name))
+
+    def _create(self, *args):
+        _check(self._fn("create")(C.byref(self._h), *args))
+
+    def _call(self, name, *args):
+        return _check(self._fn(name)(self._h, *args))
+
+    def set_mode(self, mode):
+        self._call("set_mode", int(mode))
+
+    def set_streams(self, nstreams):
+        """work / work_device then take nstreams streams back to back, each of the item count they are given; restarts
+        every stream from the block's initial state"""
+        self._call("set_streams", int(nstreams))
+        self._streams = int(nstreams)
+
+    def work_device(self, n, d_in, d_out, stream=None):
+        """work on device buffers (addresses or tensors), queued on `stream`"""
+        return self._call("work_device", int(n), _devptr(d_in), _devptr(d_out), _stream(stream))
 
 
 # ----------------------------------------------------------------------------
 # gr.fir_filter_XXX  (filter/gr_fir_filter_XXX.i.t:28-41)
 # ----------------------------------------------------------------------------
 class _fir_filter(_Block):
-    _destroy = "grhip_fir_filter_destroy"
+    _name = "fir_filter"
     _kind = None
     _in = np.complex64
     _out = np.complex64
@@ -161,26 +231,17 @@ class _fir_filter(_Block):
     def __init__(self, decimation, taps, device=0):
         _Block.__init__(self)
         t = np.ascontiguousarray(taps, dtype=self._tap)
-        L = lib()
-        L.grhip_fir_filter_create.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_void_p,
-                                              C.c_size_t, C.c_int]
-        _check(L.grhip_fir_filter_create(C.byref(self._h), self._kind.encode(), int(decimation),
-                                         _ptr(t), len(t), int(device)))
+        self._create(self._kind.encode(), int(decimation), _ptr(t), len(t), int(device))
 
     def set_taps(self, taps):
         t = np.ascontiguousarray(taps, dtype=self._tap)
-        L = lib()
-        L.grhip_fir_filter_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        _check(L.grhip_fir_filter_set_taps(self._h, _ptr(t), len(t)))
-
-    def set_mode(self, mode):
-        _check(lib().grhip_fir_filter_set_mode(self._h, int(mode)))
+        self._call("set_taps", _ptr(t), len(t))
 
     def history(self):
-        return _check(lib().grhip_fir_filter_history(self._h))
+        return self._call("history")
 
     def decimation(self):
-        return _check(lib().grhip_fir_filter_decimation(self._h))
+        return self._call("decimation")
 
     def work(self, noutput_items, input_items):
         """input_items: numpy array with history()-1 old items in front."""
@@ -189,29 +250,19 @@ class _fir_filter(_Block):
         if len(x) < need:
             raise ValueError("work needs %d input items, got %d" % (need, len(x)))
         out = np.zeros(noutput_items, dtype=self._out)
-        L = lib()
-        L.grhip_fir_filter_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_fir_filter_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n]
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_fir_filter_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_fir_filter_work_device(self._h, int(noutput_items), _devptr(d_in),
-                                                     _devptr(d_out), _stream(stream)))
 
     def filterNdec(self, x, n, decimate):
         x = np.ascontiguousarray(x, dtype=self._in)
         out = np.zeros(n, dtype=self._out)
-        L = lib()
-        L.grhip_fir_filterNdec.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulong, C.c_uint]
-        _check(L.grhip_fir_filterNdec(self._h, _ptr(out), _ptr(x), n, decimate))
+        _check(lib().grhip_fir_filterNdec(self._h, _ptr(out), _ptr(x), n, decimate))
         return out
 
 
 class fir_filter_with_buffer(_Block):
     """gri_fir_filter_with_buffer_{ccf,ccc,fff}: the FIR kernel object that keeps its own delay line"""
-    _destroy = "grhip_fir_filter_with_buffer_destroy"
+    _name = "fir_filter_with_buffer"
 
     def __init__(self, kind, taps, device=0):
         _Block.__init__(self)
@@ -219,41 +270,28 @@ class fir_filter_with_buffer(_Block):
         self._tap = np.complex64 if kind == "ccc" else np.float32
         self._io = np.float32 if kind == "fff" else np.complex64
         t = np.ascontiguousarray(taps, dtype=self._tap)
-        L = lib()
-        L.grhip_fir_filter_with_buffer_create.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_void_p, C.c_size_t, C.c_int]
-        _check(L.grhip_fir_filter_with_buffer_create(C.byref(self._h), kind.encode(), _ptr(t), len(t), int(device)))
+        self._create(kind.encode(), _ptr(t), len(t), int(device))
 
     def set_taps(self, taps):
         t = np.ascontiguousarray(taps, dtype=self._tap)
-        L = lib()
-        L.grhip_fir_filter_with_buffer_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        _check(L.grhip_fir_filter_with_buffer_set_taps(self._h, _ptr(t), len(t)))
-
-    def set_mode(self, mode):
-        _check(lib().grhip_fir_filter_with_buffer_set_mode(self._h, int(mode)))
+        self._call("set_taps", _ptr(t), len(t))
 
     def ntaps(self):
-        return _check(lib().grhip_fir_filter_with_buffer_ntaps(self._h))
+        return self._call("ntaps")
 
     def filterNdec(self, x, n, decimate=1):
         x = np.ascontiguousarray(x, dtype=self._io)
         if len(x) < n * decimate:
             raise ValueError("filterNdec needs %d items" % (n * decimate))
         out = np.zeros(n, dtype=self._io)
-        L = lib()
-        L.grhip_fir_filter_with_buffer_filterNdec.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulong, C.c_ulong]
-        _check(L.grhip_fir_filter_with_buffer_filterNdec(self._h, _ptr(out), _ptr(x), n, decimate))
+        self._call("filterNdec", _ptr(out), _ptr(x), n, decimate)
         return out
 
     def filterN(self, x, n):
         return self.filterNdec(x, n, 1)
 
     def filterNdec_device(self, d_out, d_in, n, decimate=1, stream=None):
-        L = lib()
-        L.grhip_fir_filter_with_buffer_filterNdec_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulong,
-                                                                     C.c_ulong, C.c_void_p]
-        _check(L.grhip_fir_filter_with_buffer_filterNdec_device(self._h, _devptr(d_out), _devptr(d_in), n, decimate,
-                                                                _stream(stream)))
+        self._call("filterNdec_device", _devptr(d_out), _devptr(d_in), n, decimate, _stream(stream))
 
 
 class fir_filter_ccf(_fir_filter):
@@ -297,45 +335,30 @@ class fir_filter_fsf(_fir_filter):
 # (filter/gr_freq_xlating_fir_filter_XXX.i.t)
 # ----------------------------------------------------------------------------
 class _freq_xlating_fir_filter(_Block):
-    _sym = "grhip_freq_xlating_fir_filter"     # prefix of the C entries
-    _destroy = _sym + "_destroy"
+    _name = "freq_xlating_fir_filter"
     _kind = None
     _in = np.complex64
     _tap = np.float32
-
-    def _fn(self, name):
-        return getattr(lib(), self._sym + name)
 
     def __init__(self, decimation, taps, center_freq, sampling_freq, device=0):
         _Block.__init__(self)
         t = np.ascontiguousarray(taps, dtype=self._tap)
         self._decim = int(decimation)
-        create = self._fn("_create")
         kind = [self._kind.encode()] if self._kind else []      # the _ccc entry takes no kind
-        create.argtypes = ([C.POINTER(C.c_void_p)] + [C.c_char_p] * len(kind) +
-                           [C.c_int, C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_int])
-        _check(create(C.byref(self._h), *kind, self._decim, _ptr(t), len(t), float(center_freq), float(sampling_freq),
-                      int(device)))
+        self._create(*kind, self._decim, _ptr(t), len(t), float(center_freq), float(sampling_freq), int(device))
 
     def set_center_freq(self, center_freq):
-        f = self._fn("_set_center_freq")
-        f.argtypes = [C.c_void_p, C.c_double]
-        _check(f(self._h, float(center_freq)))
+        self._call("set_center_freq", float(center_freq))
 
     def set_taps(self, taps):
         t = np.ascontiguousarray(taps, dtype=self._tap)
-        f = self._fn("_set_taps")
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        _check(f(self._h, _ptr(t), len(t)))
-
-    def set_mode(self, mode):
-        _check(self._fn("_set_mode")(self._h, int(mode)))
+        self._call("set_taps", _ptr(t), len(t))
 
     def reset(self):
-        _check(self._fn("_reset")(self._h))
+        self._call("reset")
 
     def history(self):
-        return _check(self._fn("_history")(self._h))
+        return self._call("history")
 
     def decimation(self):
         return self._decim
@@ -346,21 +369,13 @@ class _freq_xlating_fir_filter(_Block):
         if len(x) < need:
             raise ValueError("work needs %d input items, got %d" % (need, len(x)))
         out = np.zeros(noutput_items, dtype=np.complex64)
-        f = self._fn("_work")
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(f(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n]
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        f = self._fn("_work_device")
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(f(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out), _stream(stream)))
 
 
 class freq_xlating_fir_filter_ccc(_freq_xlating_fir_filter):
     # the family handle of kind "ccc" behind gr.freq_xlating_fir_filter_ccc's own C entries
-    _sym = "grhip_freq_xlating_fir_filter_ccc"
-    _destroy = _sym + "_destroy"
+    _name = "freq_xlating_fir_filter_ccc"
     _tap = np.complex64
 
 
@@ -394,13 +409,11 @@ class freq_xlating_fir_filter_scc(_freq_xlating_fir_filter):
 # gr.quadrature_demod_cf
 # ----------------------------------------------------------------------------
 class quadrature_demod_cf(_Block):
-    _destroy = "grhip_quadrature_demod_cf_destroy"
+    _name = "quadrature_demod_cf"
 
     def __init__(self, gain, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_quadrature_demod_cf_create.argtypes = [C.POINTER(C.c_void_p), C.c_float, C.c_int]
-        _check(L.grhip_quadrature_demod_cf_create(C.byref(self._h), float(gain), int(device)))
+        self._create(float(gain), int(device))
 
     def history(self):
         return 2
@@ -413,44 +426,27 @@ class quadrature_demod_cf(_Block):
         if len(x) < noutput_items + 1:
             raise ValueError("work needs %d input items" % (noutput_items + 1))
         out = np.zeros(noutput_items, dtype=np.float32)
-        L = lib()
-        L.grhip_quadrature_demod_cf_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_quadrature_demod_cf_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n]
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_quadrature_demod_cf_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                                            C.c_void_p]
-        return _check(L.grhip_quadrature_demod_cf_work_device(self._h, int(noutput_items), _devptr(d_in),
-                                                              _devptr(d_out), _stream(stream)))
 
 
 # ----------------------------------------------------------------------------
 # fused hier block xlating -> quad_demod
 # ----------------------------------------------------------------------------
 class xlating_demod(_Block):
-    _destroy = "grhip_xlating_demod_destroy"
+    _name = "xlating_demod"
 
     def __init__(self, decimation, taps, center_freq, sampling_freq, gain, device=0):
         _Block.__init__(self)
         t = np.ascontiguousarray(taps, dtype=np.complex64)
         self._decim = int(decimation)
-        L = lib()
-        L.grhip_xlating_demod_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_size_t,
-                                                 C.c_double, C.c_double, C.c_float, C.c_int]
-        _check(L.grhip_xlating_demod_create(C.byref(self._h), self._decim, _ptr(t), len(t),
-                                            float(center_freq), float(sampling_freq), float(gain),
-                                            int(device)))
-
-    def set_mode(self, mode):
-        _check(lib().grhip_xlating_demod_set_mode(self._h, int(mode)))
+        self._create(self._decim, _ptr(t), len(t), float(center_freq), float(sampling_freq), float(gain), int(device))
 
     def reset(self):
-        _check(lib().grhip_xlating_demod_reset(self._h))
+        self._call("reset")
 
     def history(self):
-        return _check(lib().grhip_xlating_demod_history(self._h))
+        return self._call("history")
 
     def decimation(self):
         return self._decim
@@ -461,105 +457,76 @@ class xlating_demod(_Block):
         if len(x) < need:
             raise ValueError("work needs %d input items, got %d" % (need, len(x)))
         out = np.zeros(noutput_items, dtype=np.float32)
-        L = lib()
-        L.grhip_xlating_demod_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_xlating_demod_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n]
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_xlating_demod_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_xlating_demod_work_device(self._h, int(noutput_items), _devptr(d_in),
-                                                        _devptr(d_out), _stream(stream)))
 
     def run_captures_device(self, n_streams, n_samples, d_in, in_stride_items, d_out, out_stride_items,
                             stream=None):
         """n_streams fresh-state captures (no history in front) in one launch"""
-        L = lib()
-        L.grhip_xlating_demod_run_captures_device.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p,
-                                                              C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-        return _check(L.grhip_xlating_demod_run_captures_device(
-            self._h, int(n_streams), int(n_samples), _devptr(d_in), int(in_stride_items), _devptr(d_out),
-            int(out_stride_items), _stream(stream)))
+        return self._call("run_captures_device", int(n_streams), int(n_samples), _devptr(d_in), int(in_stride_items),
+                          _devptr(d_out), int(out_stride_items), _stream(stream))
 
 
 # ----------------------------------------------------------------------------
 # digital.clock_recovery_mm_ff
 # ----------------------------------------------------------------------------
 class clock_recovery_mm_ff(_Block):
-    _destroy = "grhip_clock_recovery_mm_ff_destroy"
+    _name = "clock_recovery_mm_ff"
 
     def __init__(self, omega, gain_omega, mu, gain_mu, omega_relative_limit, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_clock_recovery_mm_ff_create.argtypes = [C.POINTER(C.c_void_p)] + [C.c_float] * 5 + [C.c_int]
-        _check(L.grhip_clock_recovery_mm_ff_create(C.byref(self._h), omega, gain_omega, mu, gain_mu,
-                                                   omega_relative_limit, int(device)))
+        self._create(omega, gain_omega, mu, gain_mu, omega_relative_limit, int(device))
 
     def forecast(self, noutput_items):
-        return _check(lib().grhip_clock_recovery_mm_ff_forecast(self._h, int(noutput_items)))
+        return self._call("forecast", int(noutput_items))
 
     def general_work(self, noutput_items, input_items):
         """returns (out, consumed)"""
         x = np.ascontiguousarray(input_items, dtype=np.float32)
         out = np.zeros(max(int(noutput_items), 1), dtype=np.float32)
         consumed = C.c_int(0)
-        L = lib()
-        L.grhip_clock_recovery_mm_ff_general_work.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                                              C.c_void_p, C.POINTER(C.c_int)]
-        n = _check(L.grhip_clock_recovery_mm_ff_general_work(self._h, int(noutput_items), len(x), _ptr(x),
-                                                             _ptr(out), C.byref(consumed)))
+        n = self._call("general_work", int(noutput_items), len(x), _ptr(x), _ptr(out), C.byref(consumed))
         return out[:n].copy(), consumed.value
 
     def general_work_device(self, noutput_items, ninput_items, d_in, d_out, d_counts, stream=None):
-        L = lib()
-        L.grhip_clock_recovery_mm_ff_general_work_device.argtypes = [
-            C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_clock_recovery_mm_ff_general_work_device(
-            self._h, int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out),
-            _devptr(d_counts), _stream(stream)))
+        return self._call("general_work_device", int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out),
+                          _devptr(d_counts), _stream(stream))
 
+    # the getters return the float itself, not a status
     def mu(self):
-        return lib().grhip_clock_recovery_mm_ff_mu(self._h)
+        return self._fn("mu")(self._h)
 
     def omega(self):
-        return lib().grhip_clock_recovery_mm_ff_omega(self._h)
+        return self._fn("omega")(self._h)
 
     def gain_mu(self):
-        return lib().grhip_clock_recovery_mm_ff_gain_mu(self._h)
+        return self._fn("gain_mu")(self._h)
 
     def gain_omega(self):
-        return lib().grhip_clock_recovery_mm_ff_gain_omega(self._h)
-
-    def _setf(self, name, v):
-        f = getattr(lib(), "grhip_clock_recovery_mm_ff_set_" + name)
-        f.argtypes = [C.c_void_p, C.c_float]
-        _check(f(self._h, float(v)))
+        return self._fn("gain_omega")(self._h)
 
     def set_gain_mu(self, v):
-        self._setf("gain_mu", v)
+        self._call("set_gain_mu", float(v))
 
     def set_gain_omega(self, v):
-        self._setf("gain_omega", v)
+        self._call("set_gain_omega", float(v))
 
     def set_mu(self, v):
-        self._setf("mu", v)
+        self._call("set_mu", float(v))
 
     def set_omega(self, v):
-        self._setf("omega", v)
+        self._call("set_omega", float(v))
 
 
 # ----------------------------------------------------------------------------
 # digital.binary_slicer_fb / digital.correlate_access_code_bb
 # ----------------------------------------------------------------------------
 class binary_slicer_fb(_Block):
-    _destroy = "grhip_binary_slicer_fb_destroy"
+    _name = "binary_slicer_fb"
 
     def __init__(self, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_binary_slicer_fb_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
-        _check(L.grhip_binary_slicer_fb_create(C.byref(self._h), int(device)))
+        self._create(int(device))
 
     def history(self):
         return 1
@@ -570,27 +537,17 @@ class binary_slicer_fb(_Block):
     def work(self, noutput_items, input_items):
         x = np.ascontiguousarray(input_items, dtype=np.float32)
         out = np.zeros(noutput_items, dtype=np.uint8)
-        L = lib()
-        L.grhip_binary_slicer_fb_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_binary_slicer_fb_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n]
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_binary_slicer_fb_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_binary_slicer_fb_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
-                                                           _stream(stream)))
 
 
 class pager_slicer_fb(_Block):
     """pager.slicer_fb(alpha): DC-tracking 4-level slicer (gr-pager/lib/pager_slicer_fb.cc)"""
-    _destroy = "grhip_pager_slicer_fb_destroy"
+    _name = "pager_slicer_fb"
 
     def __init__(self, alpha, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_pager_slicer_fb_create.argtypes = [C.POINTER(C.c_void_p), C.c_float, C.c_int]
-        _check(L.grhip_pager_slicer_fb_create(C.byref(self._h), float(alpha), int(device)))
+        self._create(float(alpha), int(device))
 
     def history(self):
         return 1
@@ -601,34 +558,22 @@ class pager_slicer_fb(_Block):
     def work(self, noutput_items, input_items):
         x = np.ascontiguousarray(input_items, dtype=np.float32)
         out = np.zeros(noutput_items, dtype=np.uint8)
-        L = lib()
-        L.grhip_pager_slicer_fb_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_pager_slicer_fb_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n]
 
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_pager_slicer_fb_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_pager_slicer_fb_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
-                                                          _stream(stream)))
-
     def dc_offset(self):
-        L = lib()
         v = C.c_float(0)
-        L.grhip_pager_slicer_fb_dc_offset.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        _check(L.grhip_pager_slicer_fb_dc_offset(self._h, C.byref(v)))
+        self._call("dc_offset", C.byref(v))
         return np.float32(v.value)
 
 
 class unpack_k_bits_bb(_Block):
     """gr.unpack_k_bits_bb(k): k output bytes (one bit each, MSB first) per input byte"""
-    _destroy = "grhip_unpack_k_bits_bb_destroy"
+    _name = "unpack_k_bits_bb"
 
     def __init__(self, k, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_unpack_k_bits_bb_create.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_int]
-        _check(L.grhip_unpack_k_bits_bb_create(C.byref(self._h), int(k), int(device)))
+        self._create(int(k), int(device))
         self.k = int(k)
 
     def interpolation(self):
@@ -637,55 +582,37 @@ class unpack_k_bits_bb(_Block):
     def work(self, noutput_items, input_items):
         x = np.ascontiguousarray(input_items, dtype=np.uint8)
         out = np.zeros(noutput_items, dtype=np.uint8)
-        L = lib()
-        L.grhip_unpack_k_bits_bb_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_unpack_k_bits_bb_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n]
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_unpack_k_bits_bb_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_unpack_k_bits_bb_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
-                                                           _stream(stream)))
 
 
 class clock_recovery_mm_cc(_Block):
     """digital.clock_recovery_mm_cc(omega, gain_omega, mu, gain_mu, omega_relative_limit)"""
-    _destroy = "grhip_clock_recovery_mm_cc_destroy"
+    _name = "clock_recovery_mm_cc"
 
     def __init__(self, omega, gain_omega, mu, gain_mu, omega_relative_limit, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_clock_recovery_mm_cc_create.argtypes = [C.POINTER(C.c_void_p)] + [C.c_float] * 5 + [C.c_int]
-        _raise_like_reference(L.grhip_clock_recovery_mm_cc_create(C.byref(self._h), omega, gain_omega, mu, gain_mu,
-                                                                  omega_relative_limit, int(device)))
+        self._create(omega, gain_omega, mu, gain_mu, omega_relative_limit, int(device))
 
     def forecast(self, noutput_items):
-        return _check(lib().grhip_clock_recovery_mm_cc_forecast(self._h, int(noutput_items)))
+        return self._call("forecast", int(noutput_items))
 
     def history(self):
-        return _check(lib().grhip_clock_recovery_mm_cc_history(self._h))
+        return self._call("history")
 
-    def _get(self, name):
+    def _out_float(self, name):
         v = C.c_float(0)
-        f = getattr(lib(), "grhip_clock_recovery_mm_cc_" + name)
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        _check(f(self._h, C.byref(v)))
+        self._call(name, C.byref(v))
         return np.float32(v.value)
 
-    def _set(self, name, v):
-        f = getattr(lib(), "grhip_clock_recovery_mm_cc_set_" + name)
-        f.argtypes = [C.c_void_p, C.c_float]
-        _check(f(self._h, float(v)))
-
-    def mu(self): return self._get("mu")
-    def omega(self): return self._get("omega")
-    def gain_mu(self): return self._get("gain_mu")
-    def gain_omega(self): return self._get("gain_omega")
-    def set_mu(self, v): self._set("mu", v)
-    def set_omega(self, v): self._set("omega", v)
-    def set_gain_mu(self, v): self._set("gain_mu", v)
-    def set_gain_omega(self, v): self._set("gain_omega", v)
+    def mu(self): return self._out_float("mu")
+    def omega(self): return self._out_float("omega")
+    def gain_mu(self): return self._out_float("gain_mu")
+    def gain_omega(self): return self._out_float("gain_omega")
+    def set_mu(self, v): self._call("set_mu", float(v))
+    def set_omega(self, v): self._call("set_omega", float(v))
+    def set_gain_mu(self, v): self._call("set_gain_mu", float(v))
+    def set_gain_omega(self, v): self._call("set_gain_omega", float(v))
 
     def general_work(self, noutput_items, input_items, want_error=False):
         """returns (out[:n], err[:n] or None, consumed)"""
@@ -693,43 +620,31 @@ class clock_recovery_mm_cc(_Block):
         out = np.zeros(max(noutput_items, 1), dtype=np.complex64)
         err = np.zeros(max(noutput_items, 1), dtype=np.float32) if want_error else None
         consumed = C.c_int(0)
-        L = lib()
-        L.grhip_clock_recovery_mm_cc_general_work.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                                             C.c_void_p, C.POINTER(C.c_int)]
-        n = _check(L.grhip_clock_recovery_mm_cc_general_work(self._h, int(noutput_items), len(x), _ptr(x), _ptr(out),
-                                                             _ptr(err) if want_error else None, C.byref(consumed)))
+        n = self._call("general_work", int(noutput_items), len(x), _ptr(x), _ptr(out),
+                       _ptr(err) if want_error else None, C.byref(consumed))
         return out[:n], (err[:n] if want_error else None), consumed.value
 
     def general_work_device(self, noutput_items, ninput_items, d_in, d_out, d_err=None, stream=None):
         """device buffers (d_err may be None: no error output, clip limit 1.0); returns (produced, consumed)"""
         consumed = C.c_int(0)
-        L = lib()
-        L.grhip_clock_recovery_mm_cc_general_work_device.argtypes = [
-            C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
-        n = _check(L.grhip_clock_recovery_mm_cc_general_work_device(
-            self._h, int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out), _devptr(d_err),
-            C.byref(consumed), _stream(stream)))
+        n = self._call("general_work_device", int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out),
+                       _devptr(d_err), C.byref(consumed), _stream(stream))
         return n, consumed.value
 
 
 class _copy_adapter(_Block):
-    _destroy = "grhip_copy_adapter_destroy"
+    _name = "copy_adapter"          # stream_to_vector and head have a create entry each and share the rest
 
     def work(self, noutput_items, input_items):
         x = np.ascontiguousarray(input_items)
         out = np.zeros(max(noutput_items, 1) * self.out_bytes, dtype=np.uint8)
-        L = lib()
-        L.grhip_copy_adapter_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_copy_adapter_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))   # negative: always an error
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))   # negative: always an error
         if n == WORK_DONE:
             return None
         return out[:n * self.out_bytes].view(x.dtype)
 
     def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_copy_adapter_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_copy_adapter_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
-                                                    _stream(stream)))
+        n = _Block.work_device(self, noutput_items, d_in, d_out, stream)
         return None if n == WORK_DONE else n
 
 
@@ -738,9 +653,7 @@ class stream_to_vector(_copy_adapter):
 
     def __init__(self, item_size, nitems_per_block, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_stream_to_vector_create.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_size_t, C.c_int]
-        _check(L.grhip_stream_to_vector_create(C.byref(self._h), int(item_size), int(nitems_per_block), int(device)))
+        _check(lib().grhip_stream_to_vector_create(C.byref(self._h), int(item_size), int(nitems_per_block), int(device)))
         self.out_bytes = int(item_size) * int(nitems_per_block)
 
 
@@ -749,9 +662,7 @@ class head(_copy_adapter):
 
     def __init__(self, sizeof_stream_item, nitems, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_head_create.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_ulonglong, C.c_int]
-        _check(L.grhip_head_create(C.byref(self._h), int(sizeof_stream_item), int(nitems), int(device)))
+        _check(lib().grhip_head_create(C.byref(self._h), int(sizeof_stream_item), int(nitems), int(device)))
         self.out_bytes = int(sizeof_stream_item)
 
     def reset(self):
@@ -761,35 +672,26 @@ class head(_copy_adapter):
 class framer_sink_1_batch(_Block):
     """multi-capture gr.framer_sink_1: run_device() frames n_streams item streams in one go (every stream from
     the search state); messages() -> [[(whitener_offset, payload bytes), ...] per stream]"""
-    _destroy = "grhip_framer_sink_1_batch_destroy"
+    _name = "framer_sink_1_batch"
 
     def __init__(self, n_streams, max_items_per_stream, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_framer_sink_1_batch_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_size_t, C.c_int]
-        _check(L.grhip_framer_sink_1_batch_create(C.byref(self._h), int(n_streams), int(max_items_per_stream), int(device)))
+        self._create(int(n_streams), int(max_items_per_stream), int(device))
         self.n_streams = int(n_streams)
 
     def run_device(self, d_in, stream_stride_items, d_nitems, n_items_max, stream=None, nitems_stride=1):
-        L = lib()
-        L.grhip_framer_sink_1_batch_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
-                                                           C.c_size_t, C.c_void_p]
-        _check(L.grhip_framer_sink_1_batch_run_device(self._h, _devptr(d_in), int(stream_stride_items), _devptr(d_nitems),
-                                                      int(nitems_stride), int(n_items_max), _stream(stream)))
+        self._call("run_device", _devptr(d_in), int(stream_stride_items), _devptr(d_nitems), int(nitems_stride),
+                   int(n_items_max), _stream(stream))
 
     def messages(self, stream=None):
-        L = lib()
-        L.grhip_framer_sink_1_batch_fetch.argtypes = [C.c_void_p, C.c_void_p]
-        L.grhip_framer_sink_1_batch_count.argtypes = [C.c_void_p, C.c_int]
-        L.grhip_framer_sink_1_batch_get.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_int]
-        _check(L.grhip_framer_sink_1_batch_fetch(self._h, _stream(stream)))
+        self._call("fetch", _stream(stream))
         buf = np.zeros(4096, np.uint8)
         out = []
         for s in range(self.n_streams):
             msgs = []
-            for i in range(_check(L.grhip_framer_sink_1_batch_count(self._h, s))):
+            for i in range(self._call("count", s)):
                 w = C.c_int(0)
-                ln = _check(L.grhip_framer_sink_1_batch_get(self._h, s, i, C.byref(w), _ptr(buf), 4096))
+                ln = self._call("get", s, i, C.byref(w), _ptr(buf), 4096)
                 msgs.append((w.value, buf[:ln].tobytes()))
             out.append(msgs)
         return out
@@ -799,46 +701,35 @@ class framer_sink_1(_Block):
     """gr.framer_sink_1(msgq): header + payload extraction after the correlator's flag bit.
     The reference inserts gr.message objects into `msgq`; here work() / work_device() collect them
     and messages() returns (and removes) [(whitener_offset, payload bytes), ...] in order."""
-    _destroy = "grhip_framer_sink_1_destroy"
+    _name = "framer_sink_1"
 
     def __init__(self, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_framer_sink_1_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
-        _check(L.grhip_framer_sink_1_create(C.byref(self._h), int(device)))
+        self._create(int(device))
 
     def work(self, noutput_items, input_items):
         x = np.ascontiguousarray(input_items, dtype=np.uint8)
-        L = lib()
-        L.grhip_framer_sink_1_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        return _check(L.grhip_framer_sink_1_work(self._h, int(noutput_items), _ptr(x)))
+        return self._call("work", int(noutput_items), _ptr(x))
 
     def set_segment_items(self, items):
         """tuning: items per segment of the parallel walk of long calls (0 = automatic); results do not depend on it"""
-        L = lib()
-        L.grhip_framer_sink_1_set_segment_items.argtypes = [C.c_void_p, C.c_longlong]
-        _check(L.grhip_framer_sink_1_set_segment_items(self._h, int(items)))
+        self._call("set_segment_items", int(items))
 
     def work_device(self, noutput_items, d_in, stream=None):
-        L = lib()
-        L.grhip_framer_sink_1_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_framer_sink_1_work_device(self._h, int(noutput_items), _devptr(d_in), _stream(stream)))
+        return self._call("work_device", int(noutput_items), _devptr(d_in), _stream(stream))
 
     def messages(self, stream=None):
-        L = lib()
-        L.grhip_framer_sink_1_message_count.argtypes = [C.c_void_p, C.c_void_p]
-        L.grhip_framer_sink_1_drain.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        n = _check(L.grhip_framer_sink_1_message_count(self._h, _stream(stream)))
+        n = self._call("message_count", _stream(stream))
         out = []
         while n > 0:
             k = min(n, 1 << 16)
             woff = np.zeros(k, dtype=np.int32)
             lens = np.zeros(k, dtype=np.int32)
             buf = np.zeros(k * 4096 if k < 64 else max(k * 256, 1 << 20), dtype=np.uint8)
-            got = _check(L.grhip_framer_sink_1_drain(self._h, k, _ptr(woff), _ptr(lens), _ptr(buf), buf.size))
+            got = self._call("drain", k, _ptr(woff), _ptr(lens), _ptr(buf), buf.size)
             if got == 0:                                   # a single payload larger than the share of the buffer
                 buf = np.zeros(4096, dtype=np.uint8)
-                got = _check(L.grhip_framer_sink_1_drain(self._h, 1, _ptr(woff), _ptr(lens), _ptr(buf), buf.size))
+                got = self._call("drain", 1, _ptr(woff), _ptr(lens), _ptr(buf), buf.size)
             ends = np.cumsum(lens[:got])
             raw = buf.tobytes()
             for i in range(got):
@@ -848,27 +739,21 @@ class framer_sink_1(_Block):
 
 
 class _stream_adapter(_Block):
-    _destroy = "grhip_stream_adapter_destroy"
+    _name = "stream_adapter"
     _split = 1
 
     def __init__(self, item_size, nstreams, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_stream_adapter_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_size_t, C.c_size_t, C.c_int]
-        _check(L.grhip_stream_adapter_create(C.byref(self._h), self._split, int(item_size), int(nstreams), int(device)))
+        self._create(self._split, int(item_size), int(nstreams), int(device))
         self.item_size, self.nstreams = int(item_size), int(nstreams)
 
     def _work(self, n, single, streams):
-        L = lib()
         arr = (C.c_void_p * self.nstreams)(*[s.ctypes.data for s in streams])
-        L.grhip_stream_adapter_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
-        return _check(L.grhip_stream_adapter_work(self._h, int(n), single.ctypes.data, arr))
+        return self._call("work", int(n), single.ctypes.data, arr)
 
     def work_device(self, n_items_per_stream, d_single, d_streams, stream_stride_items, stream=None):
-        L = lib()
-        L.grhip_stream_adapter_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        return _check(L.grhip_stream_adapter_work_device(self._h, int(n_items_per_stream), _devptr(d_single),
-                                                         _devptr(d_streams), int(stream_stride_items), _stream(stream)))
+        return self._call("work_device", int(n_items_per_stream), _devptr(d_single), _devptr(d_streams),
+                          int(stream_stride_items), _stream(stream))
 
 
 class stream_to_streams(_stream_adapter):
@@ -901,22 +786,16 @@ class streams_to_stream(_stream_adapter):
 
 
 class correlate_access_code_bb(_Block):
-    _destroy = "grhip_correlate_access_code_bb_destroy"
+    _name = "correlate_access_code_bb"
 
     def __init__(self, access_code, threshold, device=0):
         _Block.__init__(self)
         code = access_code.encode("latin-1") if isinstance(access_code, str) else bytes(access_code)
-        L = lib()
-        L.grhip_correlate_access_code_bb_create.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t,
-                                                            C.c_int, C.c_int]
-        _check(L.grhip_correlate_access_code_bb_create(C.byref(self._h), code, len(code), int(threshold),
-                                                       int(device)))
+        self._create(code, len(code), int(threshold), int(device))
 
     def set_access_code(self, access_code):
         code = access_code.encode("latin-1") if isinstance(access_code, str) else bytes(access_code)
-        L = lib()
-        L.grhip_correlate_access_code_bb_set_access_code.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-        rc = L.grhip_correlate_access_code_bb_set_access_code(self._h, code, len(code))
+        rc = self._fn("set_access_code")(self._h, code, len(code))
         return rc == 0   # bool like the reference (digital_correlate_access_code_bb.cc:64-68)
 
     def history(self):
@@ -928,40 +807,26 @@ class correlate_access_code_bb(_Block):
     def work(self, noutput_items, input_items):
         x = np.ascontiguousarray(input_items, dtype=np.uint8)
         out = np.zeros(noutput_items, dtype=np.uint8)
-        L = lib()
-        L.grhip_correlate_access_code_bb_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_correlate_access_code_bb_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n]
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_correlate_access_code_bb_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                                                 C.c_void_p]
-        return _check(L.grhip_correlate_access_code_bb_work_device(
-            self._h, int(noutput_items), _devptr(d_in), _devptr(d_out), _stream(stream)))
 
 
 # ----------------------------------------------------------------------------
 # gr.fft_vcc
 # ----------------------------------------------------------------------------
 class fft_vcc(_Block):
-    _destroy = "grhip_fft_vcc_destroy"
+    _name = "fft_vcc"
 
     def __init__(self, fft_size, forward, window, shift=False, device=0):
         _Block.__init__(self)
         w = np.ascontiguousarray(window if window is not None else [], dtype=np.float32)
         self.fft_size = int(fft_size)
-        L = lib()
-        L.grhip_fft_vcc_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
-                                           C.c_int, C.c_int]
-        _check(L.grhip_fft_vcc_create(C.byref(self._h), self.fft_size, int(bool(forward)),
-                                      _ptr(w) if len(w) else None, len(w), int(bool(shift)), int(device)))
+        self._create(self.fft_size, int(bool(forward)), _ptr(w) if len(w) else None, len(w), int(bool(shift)),
+                     int(device))
 
     def set_window(self, window):
         w = np.ascontiguousarray(window, dtype=np.float32)
-        L = lib()
-        L.grhip_fft_vcc_set_window.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        return bool(_check(L.grhip_fft_vcc_set_window(self._h, _ptr(w) if len(w) else None, len(w))))
+        return bool(self._call("set_window", _ptr(w) if len(w) else None, len(w)))
 
     def work(self, noutput_items, input_items):
         """items are vectors: input_items has noutput_items*fft_size complex."""
@@ -969,126 +834,74 @@ class fft_vcc(_Block):
         if len(x) < noutput_items * self.fft_size:
             raise ValueError("not enough input")
         out = np.zeros(noutput_items * self.fft_size, dtype=np.complex64)
-        L = lib()
-        L.grhip_fft_vcc_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_fft_vcc_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n * self.fft_size]
 
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_fft_vcc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_fft_vcc_work_device(self._h, int(noutput_items), _devptr(d_in),
-                                                  _devptr(d_out), _stream(stream)))
-
 
 # ----------------------------------------------------------------------------
-# gr.pfb_channelizer_ccf
+# gr.fft_filter_ccc / gr.fft_filter_fff / gr.fft_vfc
 # ----------------------------------------------------------------------------
-class fft_filter_ccc(_Block):
-    """gr.fft_filter_ccc(decimation, taps): overlap-add fast convolution (history 1, output multiple nsamples)"""
-    _destroy = "grhip_fft_filter_ccc_destroy"
+class _fft_filter(_Block):
+    _dtype = None
 
     def __init__(self, decimation, taps, device=0):
         _Block.__init__(self)
-        L = lib()
-        t = np.ascontiguousarray(taps, dtype=np.complex64)
-        L.grhip_fft_filter_ccc_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_size_t, C.c_int]
-        _check(L.grhip_fft_filter_ccc_create(C.byref(self._h), int(decimation), _ptr(t), len(t), int(device)))
+        t = np.ascontiguousarray(taps, dtype=self._dtype)
+        self._create(int(decimation), _ptr(t), len(t), int(device))
 
     def history(self):
         return 1
 
     def decimation(self):
-        return _check(lib().grhip_fft_filter_ccc_decimation(self._h))
+        return self._call("decimation")
 
     def nsamples(self):
         """the block's output multiple"""
-        return _check(lib().grhip_fft_filter_ccc_nsamples(self._h))
+        return self._call("nsamples")
 
     def set_taps(self, taps):
-        t = np.ascontiguousarray(taps, dtype=np.complex64)
-        L = lib()
-        L.grhip_fft_filter_ccc_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        _check(L.grhip_fft_filter_ccc_set_taps(self._h, _ptr(t), len(t)))
+        t = np.ascontiguousarray(taps, dtype=self._dtype)
+        self._call("set_taps", _ptr(t), len(t))
 
     def work(self, noutput_items, input_items):
-        x = np.ascontiguousarray(input_items, dtype=np.complex64)
-        out = np.zeros(noutput_items, dtype=np.complex64)
-        L = lib()
-        L.grhip_fft_filter_ccc_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_fft_filter_ccc_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        x = np.ascontiguousarray(input_items, dtype=self._dtype)
+        out = np.zeros(noutput_items, dtype=self._dtype)
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n]
 
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_fft_filter_ccc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_fft_filter_ccc_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
-                                                         _stream(stream)))
+
+class fft_filter_ccc(_fft_filter):
+    """gr.fft_filter_ccc(decimation, taps): overlap-add fast convolution (history 1, output multiple nsamples)"""
+    _name = "fft_filter_ccc"
+    _dtype = np.complex64
 
 
-class fft_filter_fff(_Block):
+class fft_filter_fff(_fft_filter):
     """gr.fft_filter_fff(decimation, taps): fast convolution of a float stream with float taps (history 1, output
     multiple nsamples); two consecutive blocks share one complex transform"""
-    _destroy = "grhip_fft_filter_fff_destroy"
-
-    def __init__(self, decimation, taps, device=0):
-        _Block.__init__(self)
-        L = lib()
-        t = np.ascontiguousarray(taps, dtype=np.float32)
-        L.grhip_fft_filter_fff_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_size_t, C.c_int]
-        _check(L.grhip_fft_filter_fff_create(C.byref(self._h), int(decimation), _ptr(t), len(t), int(device)))
-
-    def history(self):
-        return 1
-
-    def decimation(self):
-        return _check(lib().grhip_fft_filter_fff_decimation(self._h))
-
-    def nsamples(self):
-        """the block's output multiple"""
-        return _check(lib().grhip_fft_filter_fff_nsamples(self._h))
-
-    def set_taps(self, taps):
-        t = np.ascontiguousarray(taps, dtype=np.float32)
-        L = lib()
-        L.grhip_fft_filter_fff_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        _check(L.grhip_fft_filter_fff_set_taps(self._h, _ptr(t), len(t)))
+    _name = "fft_filter_fff"
+    _dtype = np.float32
 
     def work(self, noutput_items, input_items):
         x = np.ascontiguousarray(input_items, dtype=np.float32)
         if len(x) < noutput_items * self.decimation():
             raise ValueError("not enough input")
-        out = np.zeros(noutput_items, dtype=np.float32)
-        L = lib()
-        L.grhip_fft_filter_fff_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_fft_filter_fff_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
-        return out[:n]
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_fft_filter_fff_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_fft_filter_fff_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
-                                                         _stream(stream)))
+        return _fft_filter.work(self, noutput_items, x)
 
 
 class fft_vfc(_Block):
     """gr.fft_vfc(fft_size, forward, window): items of fft_size floats in, fft_size complex out; forward only"""
-    _destroy = "grhip_fft_vfc_destroy"
+    _name = "fft_vfc"
 
     def __init__(self, fft_size, forward, window, device=0):
         _Block.__init__(self)
         w = np.ascontiguousarray(window if window is not None else [], dtype=np.float32)
         self.fft_size = int(fft_size)
-        L = lib()
-        L.grhip_fft_vfc_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int]
-        _check(L.grhip_fft_vfc_create(C.byref(self._h), self.fft_size, int(bool(forward)),
-                                      _ptr(w) if len(w) else None, len(w), int(device)))
+        self._create(self.fft_size, int(bool(forward)), _ptr(w) if len(w) else None, len(w), int(device))
 
     def set_window(self, window):
         w = np.ascontiguousarray(window, dtype=np.float32)
-        L = lib()
-        L.grhip_fft_vfc_set_window.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        return bool(_check(L.grhip_fft_vfc_set_window(self._h, _ptr(w) if len(w) else None, len(w))))
+        return bool(self._call("set_window", _ptr(w) if len(w) else None, len(w)))
 
     def work(self, noutput_items, input_items):
         """items are vectors: input_items has noutput_items*fft_size floats."""
@@ -1096,42 +909,31 @@ class fft_vfc(_Block):
         if len(x) < noutput_items * self.fft_size:
             raise ValueError("not enough input")
         out = np.zeros(noutput_items * self.fft_size, dtype=np.complex64)
-        L = lib()
-        L.grhip_fft_vfc_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_fft_vfc_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n * self.fft_size]
 
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_fft_vfc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_fft_vfc_work_device(self._h, int(noutput_items), _devptr(d_in),
-                                                  _devptr(d_out), _stream(stream)))
 
-
+# ----------------------------------------------------------------------------
+# gr.pfb_channelizer_ccf / gr.pfb_decimator_ccf
+# ----------------------------------------------------------------------------
 class pfb_channelizer_ccf(_Block):
-    _destroy = "grhip_pfb_channelizer_ccf_destroy"
+    _name = "pfb_channelizer_ccf"
 
     def __init__(self, numchans, taps, oversample_rate=1, device=0):
         _Block.__init__(self)
         t = np.ascontiguousarray(taps, dtype=np.float32)
         self.numchans = int(numchans)
-        L = lib()
-        L.grhip_pfb_channelizer_ccf_create.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_void_p,
-                                                       C.c_size_t, C.c_float, C.c_int]
-        _check(L.grhip_pfb_channelizer_ccf_create(C.byref(self._h), self.numchans, _ptr(t), len(t),
-                                                  float(oversample_rate), int(device)))
+        self._create(self.numchans, _ptr(t), len(t), float(oversample_rate), int(device))
 
     def set_taps(self, taps):
         t = np.ascontiguousarray(taps, dtype=np.float32)
-        L = lib()
-        L.grhip_pfb_channelizer_ccf_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        _check(L.grhip_pfb_channelizer_ccf_set_taps(self._h, _ptr(t), len(t)))
+        self._call("set_taps", _ptr(t), len(t))
 
     def history(self):
-        return _check(lib().grhip_pfb_channelizer_ccf_history(self._h))
+        return self._call("history")
 
     def output_multiple(self):
-        return _check(lib().grhip_pfb_channelizer_ccf_output_multiple(self._h))
+        return self._call("output_multiple")
 
     def general_work(self, noutput_items, streams):
         """streams: list of numchans complex arrays each with history()-1 old
@@ -1140,117 +942,75 @@ class pfb_channelizer_ccf(_Block):
         ptrs = (C.c_void_p * self.numchans)(*[a.ctypes.data for a in arrs])
         out = np.zeros((max(noutput_items, 1), self.numchans), dtype=np.complex64)
         consumed = C.c_int(0)
-        L = lib()
-        L.grhip_pfb_channelizer_ccf_general_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                                             C.POINTER(C.c_int)]
-        n = _check(L.grhip_pfb_channelizer_ccf_general_work(self._h, int(noutput_items), ptrs, _ptr(out),
-                                                            C.byref(consumed)))
+        n = self._call("general_work", int(noutput_items), ptrs, _ptr(out), C.byref(consumed))
         return out[:n], consumed.value
 
     def general_work_device(self, noutput_items, d_in, stream_stride_items, d_out, stream=None):
-        L = lib()
-        L.grhip_pfb_channelizer_ccf_general_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p,
-                                                                    C.c_size_t, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_pfb_channelizer_ccf_general_work_device(
-            self._h, int(noutput_items), _devptr(d_in), int(stream_stride_items), _devptr(d_out),
-            _stream(stream)))
+        return self._call("general_work_device", int(noutput_items), _devptr(d_in), int(stream_stride_items),
+                          _devptr(d_out), _stream(stream))
 
-
-def _pfb_hier_work_device(self, noutput_items, d_in, d_out, out_stride_items, stream=None):
-    """blks2.pfb_channelizer_ccf (hier block) in one call: one interleaved stream in (taps_per_filter * numchans history
-    items in front), numchans streams out (channel k at d_out + k * out_stride_items)"""
-    L = lib()
-    L.grhip_pfb_channelizer_ccf_hier_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
-                                                             C.c_void_p]
-    return _check(L.grhip_pfb_channelizer_ccf_hier_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
-                                                               int(out_stride_items), _stream(stream)))
-
-
-pfb_channelizer_ccf.hier_work_device = _pfb_hier_work_device
+    def hier_work_device(self, noutput_items, d_in, d_out, out_stride_items, stream=None):
+        """blks2.pfb_channelizer_ccf (hier block) in one call: one interleaved stream in (taps_per_filter * numchans history
+        items in front), numchans streams out (channel k at d_out + k * out_stride_items)"""
+        return self._call("hier_work_device", int(noutput_items), _devptr(d_in), _devptr(d_out), int(out_stride_items),
+                          _stream(stream))
 
 
 class pfb_decimator_ccf(_Block):
     """gr.pfb_decimator_ccf(decim, taps, channel)"""
-    _destroy = "grhip_pfb_decimator_ccf_destroy"
+    _name = "pfb_decimator_ccf"
 
     def __init__(self, decim, taps, channel=0, device=0):
         _Block.__init__(self)
         t = np.ascontiguousarray(taps, dtype=np.float32)
         self.decim = int(decim)
-        L = lib()
-        L.grhip_pfb_decimator_ccf_create.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_void_p, C.c_size_t,
-                                                     C.c_uint, C.c_int]
-        _check(L.grhip_pfb_decimator_ccf_create(C.byref(self._h), self.decim, _ptr(t), len(t), int(channel),
-                                                int(device)))
+        self._create(self.decim, _ptr(t), len(t), int(channel), int(device))
 
     def set_taps(self, taps):
         t = np.ascontiguousarray(taps, dtype=np.float32)
-        L = lib()
-        L.grhip_pfb_decimator_ccf_set_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        _check(L.grhip_pfb_decimator_ccf_set_taps(self._h, _ptr(t), len(t)))
+        self._call("set_taps", _ptr(t), len(t))
 
     def history(self):
-        return _check(lib().grhip_pfb_decimator_ccf_history(self._h))
+        return self._call("history")
 
     def work(self, noutput_items, streams):
         arrs = [np.ascontiguousarray(s, dtype=np.complex64) for s in streams]
         ptrs = (C.c_void_p * self.decim)(*[a.ctypes.data for a in arrs])
         out = np.zeros(max(noutput_items, 1), dtype=np.complex64)
-        L = lib()
-        L.grhip_pfb_decimator_ccf_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_pfb_decimator_ccf_work(self._h, int(noutput_items), ptrs, _ptr(out)))
+        n = self._call("work", int(noutput_items), ptrs, _ptr(out))
         return out[:n]
 
     def work_device(self, noutput_items, d_in, stream_stride_items, d_out, stream=None):
-        L = lib()
-        L.grhip_pfb_decimator_ccf_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
-                                                          C.c_void_p]
-        return _check(L.grhip_pfb_decimator_ccf_work_device(self._h, int(noutput_items), _devptr(d_in),
-                                                            int(stream_stride_items), _devptr(d_out), _stream(stream)))
+        return self._call("work_device", int(noutput_items), _devptr(d_in), int(stream_stride_items), _devptr(d_out),
+                          _stream(stream))
 
 
 # ----------------------------------------------------------------------------
 # What the schedule-driven general_work blocks share (csrc/sched_block.h): their C entry points differ only in the
-# symbol prefix, their buffers only in the item type.
+# block's name, their buffers only in the item type.  The resamplers below have the same entries.
 # ----------------------------------------------------------------------------
 class _sched_block(_Block):
-    _prefix = None      # C symbol prefix up to the signature suffix
-    _kind = None
     _dtype = None
 
-    def __init__(self):
-        _Block.__init__(self)
-        self._destroy = "%s_%s_destroy" % (self._prefix, self._kind)
-
-    def _fn(self, name):
-        return getattr(lib(), "%s_%s_%s" % (self._prefix, self._kind, name))
-
-    def set_mode(self, mode):
-        _check(self._fn("set_mode")(self._h, int(mode)))
-
     def history(self):
-        return _check(self._fn("history")(self._h))
+        return self._call("history")
 
     def forecast(self, noutput_items):
-        return _check(self._fn("forecast")(self._h, int(noutput_items)))
+        return self._call("forecast", int(noutput_items))
 
     def general_work(self, noutput_items, input_items):
         """returns (out, consumed)"""
         x = np.ascontiguousarray(input_items, dtype=self._dtype)
         out = np.zeros(max(int(noutput_items), 1), dtype=self._dtype)
         consumed = C.c_int(0)
-        f = self._fn("general_work")
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        n = _check(f(self._h, int(noutput_items), len(x), _ptr(x), _ptr(out), C.byref(consumed)))
+        n = self._call("general_work", int(noutput_items), len(x), _ptr(x), _ptr(out), C.byref(consumed))
         return out[:n].copy(), consumed.value
 
     def general_work_device(self, noutput_items, ninput_items, d_in, d_out, stream=None):
         """returns (produced, consumed); the outputs are in d_out once `stream` has run"""
         consumed = C.c_int(0)
-        f = self._fn("general_work_device")
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
-        n = _check(f(self._h, int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out),
-                     C.byref(consumed), _stream(stream)))
+        n = self._call("general_work_device", int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out),
+                       C.byref(consumed), _stream(stream))
         return n, consumed.value
 
     def run_captures_device(self, n_streams, n_samples, d_in, in_stride_items, d_out, out_stride_items,
@@ -1258,11 +1018,8 @@ class _sched_block(_Block):
         """n_streams fresh-state captures in one launch; returns the outputs per capture.  d_out=None only returns
         that number."""
         n_out = C.c_size_t(0)
-        f = self._fn("run_captures_device")
-        f.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                      C.POINTER(C.c_size_t), C.c_void_p]
-        _check(f(self._h, int(n_streams), int(n_samples), _devptr(d_in), int(in_stride_items), _devptr(d_out),
-                 int(out_stride_items), C.byref(n_out), _stream(stream)))
+        self._call("run_captures_device", int(n_streams), int(n_samples), _devptr(d_in), int(in_stride_items),
+                   _devptr(d_out), int(out_stride_items), C.byref(n_out), _stream(stream))
         return n_out.value
 
     def captures_nout(self, n_samples):
@@ -1274,22 +1031,16 @@ class _sched_block(_Block):
 # gr.pfb_arb_resampler_ccf / gr.pfb_arb_resampler_fff  (filter/gr_pfb_arb_resampler_ccf.i)
 # ----------------------------------------------------------------------------
 class _pfb_arb_resampler(_sched_block):
-    _prefix = "grhip_pfb_arb_resampler"
-
     def __init__(self, rate, taps, filter_size=32, device=0):
-        _sched_block.__init__(self)
+        _Block.__init__(self)
         t = np.ascontiguousarray(taps, dtype=np.float32)
-        f = self._fn("create")
-        f.argtypes = [C.POINTER(C.c_void_p), C.c_float, C.c_void_p, C.c_size_t, C.c_uint, C.c_int]
-        _check(f(C.byref(self._h), float(rate), _ptr(t), len(t), int(filter_size), int(device)))
+        self._create(float(rate), _ptr(t), len(t), int(filter_size), int(device))
 
     def set_rate(self, rate):
-        f = self._fn("set_rate")
-        f.argtypes = [C.c_void_p, C.c_float]
-        _check(f(self._h, float(rate)))
+        self._call("set_rate", float(rate))
 
     def taps_per_filter(self):
-        return _check(self._fn("taps_per_filter")(self._h))
+        return self._call("taps_per_filter")
 
     # the two overrides below only carry this block's wording of the docstrings
     def general_work(self, noutput_items, input_items):
@@ -1306,13 +1057,13 @@ class _pfb_arb_resampler(_sched_block):
 
 class pfb_arb_resampler_ccf(_pfb_arb_resampler):
     """gr.pfb_arb_resampler_ccf(rate, taps, filter_size=32)"""
-    _kind = "ccf"
+    _name = "pfb_arb_resampler_ccf"
     _dtype = np.complex64
 
 
 class pfb_arb_resampler_fff(_pfb_arb_resampler):
     """gr.pfb_arb_resampler_fff(rate, taps, filter_size=32)"""
-    _kind = "fff"
+    _name = "pfb_arb_resampler_fff"
     _dtype = np.float32
 
 
@@ -1320,47 +1071,32 @@ class pfb_arb_resampler_fff(_pfb_arb_resampler):
 # gr.fractional_interpolator_ff / gr.fractional_interpolator_cc  (filter/gr_fractional_interpolator_ff.i)
 # ----------------------------------------------------------------------------
 class _fractional_interpolator(_sched_block):
-    _prefix = "grhip_fractional_interpolator"
-
     def __init__(self, phase_shift, interp_ratio, device=0):
-        _sched_block.__init__(self)
-        f = self._fn("create")
-        f.argtypes = [C.POINTER(C.c_void_p), C.c_float, C.c_float, C.c_int]
-        _check(f(C.byref(self._h), float(phase_shift), float(interp_ratio), int(device)))
-
-    def _getf(self, name):
-        f = self._fn(name)
-        f.argtypes = [C.c_void_p]
-        f.restype = C.c_float
-        return float(f(self._h))
-
-    def _setf(self, name, v):
-        f = self._fn(name)
-        f.argtypes = [C.c_void_p, C.c_float]
-        _check(f(self._h, float(v)))
+        _Block.__init__(self)
+        self._create(float(phase_shift), float(interp_ratio), int(device))
 
     def mu(self):
-        return self._getf("mu")
+        return self._fn("mu")(self._h)
 
     def interp_ratio(self):
-        return self._getf("interp_ratio")
+        return self._fn("interp_ratio")(self._h)
 
     def set_mu(self, mu):
-        self._setf("set_mu", mu)
+        self._call("set_mu", float(mu))
 
     def set_interp_ratio(self, interp_ratio):
-        self._setf("set_interp_ratio", interp_ratio)
+        self._call("set_interp_ratio", float(interp_ratio))
 
 
 class fractional_interpolator_ff(_fractional_interpolator):
     """gr.fractional_interpolator_ff(phase_shift, interp_ratio)"""
-    _kind = "ff"
+    _name = "fractional_interpolator_ff"
     _dtype = np.float32
 
 
 class fractional_interpolator_cc(_fractional_interpolator):
     """gr.fractional_interpolator_cc(phase_shift, interp_ratio)"""
-    _kind = "cc"
+    _name = "fractional_interpolator_cc"
     _dtype = np.complex64
 
 
@@ -1378,39 +1114,27 @@ def firdes_hilbert(ntaps, window=WIN_RECTANGULAR, beta=6.76):
     if ntaps < 0 or ntaps > (1 << 24):
         raise ValueError("ntaps out of range")
     out = np.zeros(max(ntaps, 1), dtype=np.float32)
-    L = lib()
-    L.grhip_firdes_hilbert.argtypes = [C.c_uint, C.c_int, C.c_double, C.c_void_p]
-    _raise_like_reference(L.grhip_firdes_hilbert(ntaps, int(window), float(beta), _ptr(out)))
+    _check(lib().grhip_firdes_hilbert(ntaps, int(window), float(beta), _ptr(out)))
     return out[:ntaps]
 
 
 class _analytic(_Block):
-    _name = None
-
-    def _fn(self, name):
-        return getattr(lib(), "grhip_%s_%s" % (self._name, name))
-
-    def set_mode(self, mode):
-        _check(self._fn("set_mode")(self._h, int(mode)))
-
     def history(self):
-        return _check(self._fn("history")(self._h))
+        return self._call("history")
 
     def decimation(self):
         return 1
 
     def ntaps(self):
-        return _check(self._fn("ntaps")(self._h))
+        return self._call("ntaps")
 
     def is_sparse(self):
         """True when FAST mode runs the kernel that uses the Hilbert structure of the taps"""
-        return bool(_check(self._fn("is_sparse")(self._h)))
+        return bool(self._call("is_sparse"))
 
     def taps(self):
         out = np.zeros(self.ntaps(), dtype=np.float32)
-        f = self._fn("taps")
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        n = _check(f(self._h, _ptr(out), len(out)))
+        n = self._call("taps", _ptr(out), len(out))
         return out[:n]
 
     def _input(self, noutput_items, a):
@@ -1423,104 +1147,70 @@ class _analytic(_Block):
 
 class hilbert_fc(_analytic):
     """gr.hilbert_fc(ntaps): real stream -> analytic signal; history ntaps | 1"""
-    _destroy = "grhip_hilbert_fc_destroy"
     _name = "hilbert_fc"
 
     def __init__(self, ntaps, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_hilbert_fc_create.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_int]
         if int(ntaps) < 0:
             raise GrhipError(-1, "negative ntaps %d" % int(ntaps))
-        _check(L.grhip_hilbert_fc_create(C.byref(self._h), int(ntaps), int(device)))
+        self._create(int(ntaps), int(device))
 
     def work(self, noutput_items, input_items):
         x = self._input(noutput_items, input_items)
         out = np.zeros(noutput_items, dtype=np.complex64)
-        L = lib()
-        L.grhip_hilbert_fc_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_hilbert_fc_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n]
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_hilbert_fc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_hilbert_fc_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
-                                                     _stream(stream)))
 
 
 class filter_delay_fc(_analytic):
     """gr.filter_delay_fc(taps): out = (in0 delayed by ntaps/2, taps * in1); one input: in1 = in0"""
-    _destroy = "grhip_filter_delay_fc_destroy"
     _name = "filter_delay_fc"
 
     def __init__(self, taps, device=0):
         _Block.__init__(self)
         t = np.ascontiguousarray(taps, dtype=np.float32)
-        L = lib()
-        L.grhip_filter_delay_fc_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_int]
-        _check(L.grhip_filter_delay_fc_create(C.byref(self._h), _ptr(t) if len(t) else None, len(t), int(device)))
+        self._create(_ptr(t) if len(t) else None, len(t), int(device))
 
     def work(self, noutput_items, input_items, input_items1=None):
         x0 = self._input(noutput_items, input_items)
         x1 = None if input_items1 is None else self._input(noutput_items, input_items1)
         out = np.zeros(noutput_items, dtype=np.complex64)
-        L = lib()
-        L.grhip_filter_delay_fc_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_filter_delay_fc_work(self._h, int(noutput_items), _ptr(x0),
-                                                None if x1 is None else _ptr(x1), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x0), None if x1 is None else _ptr(x1), _ptr(out))
         return out[:n]
 
     def work_device(self, noutput_items, d_in0, d_in1, d_out, stream=None):
-        L = lib()
-        L.grhip_filter_delay_fc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                        C.c_void_p]
-        return _check(L.grhip_filter_delay_fc_work_device(self._h, int(noutput_items), _devptr(d_in0), _devptr(d_in1),
-                                                          _devptr(d_out), _stream(stream)))
+        return self._call("work_device", int(noutput_items), _devptr(d_in0), _devptr(d_in1), _devptr(d_out),
+                          _stream(stream))
 
 
 class goertzel_fc(_Block):
     """gr.goertzel_fc(rate, len, freq): one DFT bin per block of len floats (a sync decimator by len)"""
-    _destroy = "grhip_goertzel_fc_destroy"
+    _name = "goertzel_fc"
 
     def __init__(self, rate, len, freq, device=0):
         _Block.__init__(self)
-        L = lib()
-        L.grhip_goertzel_fc_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_float, C.c_int]
-        _check(L.grhip_goertzel_fc_create(C.byref(self._h), int(rate), int(len), float(freq), int(device)))
+        self._create(int(rate), int(len), float(freq), int(device))
 
     def set_freq(self, freq):
-        L = lib()
-        L.grhip_goertzel_fc_set_freq.argtypes = [C.c_void_p, C.c_float]
-        _check(L.grhip_goertzel_fc_set_freq(self._h, float(freq)))
+        self._call("set_freq", float(freq))
 
     def set_rate(self, rate):
-        _check(lib().grhip_goertzel_fc_set_rate(self._h, int(rate)))
-
-    def set_mode(self, mode):
-        _check(lib().grhip_goertzel_fc_set_mode(self._h, int(mode)))
+        self._call("set_rate", int(rate))
 
     def history(self):
         return 1
 
     def decimation(self):
-        return _check(lib().grhip_goertzel_fc_decimation(self._h))
+        return self._call("decimation")
 
     def work(self, noutput_items, input_items):
         x = np.ascontiguousarray(input_items, dtype=np.float32)
         if len(x) < noutput_items * self.decimation():
             raise ValueError("not enough input")
         out = np.zeros(noutput_items, dtype=np.complex64)
-        L = lib()
-        L.grhip_goertzel_fc_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        n = _check(L.grhip_goertzel_fc_work(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        n = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:n]
 
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_goertzel_fc_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_goertzel_fc_work_device(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out),
-                                                      _stream(stream)))
 
 # ----------------------------------------------------------------------------
 # gr.dc_blocker_ff / _cc, gr.moving_average_XX, gr.integrate_XX  (filter/gr_dc_blocker_ff.i, gengen/gr_moving_average_XX.i.t,
@@ -1530,55 +1220,31 @@ _RUNSUM_DTYPE = {"ff": np.float32, "cc": np.complex64, "ss": np.int16, "ii": np.
 
 
 class _runsum(_Block):
-    _name = None
-
-    def __init__(self):
-        _Block.__init__(self)
-        self._dtype = _RUNSUM_DTYPE[self._name[-2:]]
-        self._destroy = "grhip_%s_destroy" % self._name
-
-    def _fn(self, name, argtypes=None):
-        f = getattr(lib(), "grhip_%s_%s" % (self._name, name))
-        if argtypes is not None:
-            f.argtypes = argtypes
-        return f
-
-    def set_mode(self, mode):
-        _check(self._fn("set_mode", [C.c_void_p, C.c_int])(self._h, int(mode)))
+    _dtype = property(lambda self: _RUNSUM_DTYPE[self._name[-2:]])
 
     def _work(self, n, x, nout):
         out = np.zeros(nout, dtype=self._dtype)
-        r = _check(self._fn("work", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])(self._h, int(n), _ptr(x), _ptr(out)))
+        r = self._call("work", int(n), _ptr(x), _ptr(out))
         return out, r
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        f = self._fn("work_device", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
-        return _check(f(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out), _stream(stream)))
 
 
 class _dc_blocker(_runsum):
     """gr.dc_blocker_XX(D=32, long_form=True): the input delayed by get_group_delay() minus 2 or 4 cascaded D-point
-    moving averages of it.  The state lives in the block and carries across work calls."""
+    moving averages of it.  The state lives in the block and carries across work calls; set_streams restarts the
+    filter."""
 
     def __init__(self, D=32, long_form=True, device=0):
-        _runsum.__init__(self)
-        self._streams = 1
-        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int])
-        _check(f(C.byref(self._h), int(D), 1 if long_form else 0, int(device)))
+        _Block.__init__(self)
+        self._create(int(D), 1 if long_form else 0, int(device))
 
     def get_group_delay(self):
-        return _check(self._fn("group_delay", [C.c_void_p])(self._h))
+        return self._call("group_delay")
 
     def history(self):
         return 1
 
     def decimation(self):
         return 1
-
-    def set_streams(self, nstreams):
-        """work / work_device then take nstreams streams of noutput_items each, back to back; restarts the filter"""
-        _check(self._fn("set_streams", [C.c_void_p, C.c_int])(self._h, int(nstreams)))
-        self._streams = int(nstreams)
 
     def work(self, noutput_items, input_items):
         x = np.ascontiguousarray(input_items, dtype=self._dtype).reshape(-1)
@@ -1603,29 +1269,24 @@ class _moving_average(_runsum):
     def _scale_args(self, scale):
         k = self._name[-2:]
         if k == "ff":
-            return [C.c_float], [float(scale)]
+            return [float(scale)]
         if k == "cc":
             z = complex(scale)
-            return [C.c_float, C.c_float], [z.real, z.imag]
-        if k == "ss":
-            return [C.c_short], [int(scale)]
-        return [C.c_int], [int(scale)]
+            return [z.real, z.imag]
+        return [int(scale)]
 
     def __init__(self, length, scale, max_iter=4096, device=0):
-        _runsum.__init__(self)
-        t, v = self._scale_args(scale)
-        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_int] + t + [C.c_int, C.c_int])
-        _check(f(C.byref(self._h), int(length), *(v + [int(max_iter), int(device)])))
+        _Block.__init__(self)
+        self._create(int(length), *(self._scale_args(scale) + [int(max_iter), int(device)]))
 
     def set_length_and_scale(self, length, scale):
-        t, v = self._scale_args(scale)
-        _check(self._fn("set_length_and_scale", [C.c_void_p, C.c_int] + t)(self._h, int(length), *v))
+        self._call("set_length_and_scale", int(length), *self._scale_args(scale))
 
     def history(self):
-        return _check(self._fn("history", [C.c_void_p])(self._h))
+        return self._call("history")
 
     def max_iter(self):
-        return _check(self._fn("max_iter", [C.c_void_p])(self._h))
+        return self._call("max_iter")
 
     def decimation(self):
         return 1
@@ -1659,14 +1320,14 @@ class _integrate(_runsum):
     """gr.integrate_XX(decim): out[i] = sum of in[i decim .. i decim + decim - 1] (a sync decimator by decim)"""
 
     def __init__(self, decim, device=0):
-        _runsum.__init__(self)
-        _check(self._fn("create", [C.POINTER(C.c_void_p), C.c_int, C.c_int])(C.byref(self._h), int(decim), int(device)))
+        _Block.__init__(self)
+        self._create(int(decim), int(device))
 
     def history(self):
         return 1
 
     def decimation(self):
-        return _check(self._fn("decimation", [C.c_void_p])(self._h))
+        return self._call("decimation")
 
     def work(self, noutput_items, input_items):
         x = np.ascontiguousarray(input_items, dtype=self._dtype)
@@ -1691,33 +1352,17 @@ class integrate_ss(_integrate):
 class integrate_ii(_integrate):
     _name = "integrate_ii"
 
+
 # ----------------------------------------------------------------------------
 # gr.complex_to_mag_squared, gr.single_pole_iir_filter_ff, gr.nlog10_ff, gr.keep_one_in_n (general/gr_complex_to_xxx.i,
 # filter/gr_single_pole_iir_filter_ff.i, general/gr_nlog10_ff.i, general/gr_keep_one_in_n.i)
 # ----------------------------------------------------------------------------
 class _spectrum(_Block):
-    _name = None
     _in = np.float32
 
     def __init__(self, vlen):
         _Block.__init__(self)
-        self._destroy = "grhip_%s_destroy" % self._name
         self._vlen = int(vlen)
-        self._streams = 1
-
-    def _fn(self, name, argtypes=None):
-        f = getattr(lib(), "grhip_%s_%s" % (self._name, name))
-        if argtypes is not None:
-            f.argtypes = argtypes
-        return f
-
-    def set_mode(self, mode):
-        _check(self._fn("set_mode", [C.c_void_p, C.c_int])(self._h, int(mode)))
-
-    def set_streams(self, nstreams):
-        """work / work_device then take nstreams streams of noutput_items each, back to back; restarts the block"""
-        _check(self._fn("set_streams", [C.c_void_p, C.c_int])(self._h, int(nstreams)))
-        self._streams = int(nstreams)
 
     def history(self):
         return 1
@@ -1729,12 +1374,8 @@ class _spectrum(_Block):
         if len(x) < need:
             raise ValueError("work needs %d input elements, got %d" % (need, len(x)))
         out = np.zeros(need, dtype=np.float32)
-        r = _check(self._fn("work", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])(self._h, int(noutput_items), _ptr(x), _ptr(out)))
+        r = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
         return out[:r * self._streams * self._vlen]
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        f = self._fn("work_device", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
-        return _check(f(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out), _stream(stream)))
 
 
 class complex_to_mag_squared(_spectrum):
@@ -1744,7 +1385,7 @@ class complex_to_mag_squared(_spectrum):
 
     def __init__(self, vlen=1, device=0):
         _spectrum.__init__(self, vlen)
-        _check(self._fn("create", [C.POINTER(C.c_void_p), C.c_int, C.c_int])(C.byref(self._h), int(vlen), int(device)))
+        self._create(int(vlen), int(device))
 
 
 class single_pole_iir_filter_ff(_spectrum):
@@ -1754,11 +1395,10 @@ class single_pole_iir_filter_ff(_spectrum):
 
     def __init__(self, alpha, vlen=1, device=0):
         _spectrum.__init__(self, vlen)
-        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_double, C.c_int, C.c_int])
-        _check(f(C.byref(self._h), float(alpha), int(vlen), int(device)))
+        self._create(float(alpha), int(vlen), int(device))
 
     def set_taps(self, alpha):
-        _check(self._fn("set_taps", [C.c_void_p, C.c_double])(self._h, float(alpha)))
+        self._call("set_taps", float(alpha))
 
     @staticmethod
     def chunk():
@@ -1772,39 +1412,17 @@ class nlog10_ff(_spectrum):
 
     def __init__(self, n=1, vlen=1, k=0, device=0):
         _spectrum.__init__(self, vlen)
-        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_float, C.c_int, C.c_float, C.c_int])
-        _check(f(C.byref(self._h), float(n), int(vlen), float(k), int(device)))
+        self._create(float(n), int(vlen), float(k), int(device))
 
 
 class _squelch_streams(_Block):
     """what every squelch block shares: work(x) takes streams x n_in items back to back and returns every stream's
-    produced items (one array for one stream, a list otherwise); the detector and the ramp machine carry across calls."""
-    _name = None
+    produced items (one array for one stream, a list otherwise); the detector and the ramp machine carry across calls.
+    set_streams restarts every stream from the reference's initial state."""
     _dtype = np.complex64
 
-    def __init__(self):
-        _Block.__init__(self)
-        self._destroy = "grhip_%s_destroy" % self._name
-        self._streams = 1
-
-    def _fn(self, name, argtypes=None, restype=None):
-        f = getattr(lib(), "grhip_%s_%s" % (self._name, name))
-        if argtypes is not None:
-            f.argtypes = argtypes
-        if restype is not None:
-            f.restype = restype
-        return f
-
-    def set_mode(self, mode):
-        _check(self._fn("set_mode", [C.c_void_p, C.c_int])(self._h, int(mode)))
-
-    def set_streams(self, nstreams):
-        """restarts every stream from the reference's initial state"""
-        _check(self._fn("set_streams", [C.c_void_p, C.c_int])(self._h, int(nstreams)))
-        self._streams = int(nstreams)
-
     def unmuted(self, stream=0):
-        return bool(_check(self._fn("unmuted", [C.c_void_p, C.c_int])(self._h, int(stream))))
+        return bool(self._call("unmuted", int(stream)))
 
     def work_into(self, n_in, input_items, out):
         """the raw call: `out` (streams x n_in items, C-contiguous) is written up to every stream's count; returns the counts"""
@@ -1812,8 +1430,7 @@ class _squelch_streams(_Block):
         if len(x) < n_in * self._streams or out.size < n_in * self._streams or out.dtype != self._dtype:
             raise ValueError("work needs %d items in and room for as many out" % (n_in * self._streams))
         produced = np.zeros(self._streams, dtype=np.int32)
-        f = self._fn("work", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
-        _check(f(self._h, int(n_in), _ptr(x), _ptr(out), _ptr(produced)))
+        self._call("work", int(n_in), _ptr(x), _ptr(out), _ptr(produced))
         if n_in == 0:
             produced[:] = 0
         return produced
@@ -1829,24 +1446,23 @@ class _squelch_streams(_Block):
 
     def work_device(self, n_in, d_in, d_out, d_produced, stream=None):
         """device buffers; d_produced holds streams int32 counts; does not synchronise"""
-        f = self._fn("work_device", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
-        return _check(f(self._h, int(n_in), _devptr(d_in), _devptr(d_out), _devptr(d_produced), _stream(stream)))
+        return self._call("work_device", int(n_in), _devptr(d_in), _devptr(d_out), _devptr(d_produced), _stream(stream))
 
 
 class _ramp_gate(object):
     """ramp() / gate() and their setters (general/gr_squelch_base_cc.h:45-48)"""
 
     def ramp(self):
-        return _check(self._fn("ramp", [C.c_void_p])(self._h))
+        return self._call("ramp")
 
     def set_ramp(self, ramp):
-        _check(self._fn("set_ramp", [C.c_void_p, C.c_int])(self._h, int(ramp)))
+        self._call("set_ramp", int(ramp))
 
     def gate(self):
-        return bool(_check(self._fn("gate", [C.c_void_p])(self._h)))
+        return bool(self._call("gate"))
 
     def set_gate(self, gate):
-        _check(self._fn("set_gate", [C.c_void_p, C.c_int])(self._h, int(bool(gate))))
+        self._call("set_gate", int(bool(gate)))
 
 
 class _squelch(_squelch_streams):
@@ -1854,20 +1470,18 @@ class _squelch(_squelch_streams):
     gr_simple_squelch_cc.i): the power detector's accessors"""
 
     def threshold(self):
-        return self._fn("threshold", [C.c_void_p], C.c_double)(self._h)
+        return self._fn("threshold")(self._h)
 
     def set_threshold(self, db):
-        _check(self._fn("set_threshold", [C.c_void_p, C.c_double])(self._h, float(db)))
+        self._call("set_threshold", float(db))
 
     def set_alpha(self, alpha):
-        _check(self._fn("set_alpha", [C.c_void_p, C.c_double])(self._h, float(alpha)))
+        self._call("set_alpha", float(alpha))
 
     def state(self, stream=0):
         """(state, ramped, envelope, detector output) of one stream; state 0 muted, 1 attack, 2 unmuted, 3 decay"""
         st, r, e, y = C.c_int(0), C.c_int(0), C.c_double(0), C.c_double(0)
-        f = self._fn("state", [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
-                               C.POINTER(C.c_double)])
-        _check(f(self._h, int(stream), C.byref(st), C.byref(r), C.byref(e), C.byref(y)))
+        self._call("state", int(stream), C.byref(st), C.byref(r), C.byref(e), C.byref(y))
         return st.value, r.value, e.value, y.value
 
     @staticmethod
@@ -1882,9 +1496,8 @@ class _squelch(_squelch_streams):
 
 class _pwr_squelch(_squelch, _ramp_gate):
     def __init__(self, db, alpha=0.0001, ramp=0, gate=False, device=0):
-        _squelch.__init__(self)
-        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_int, C.c_int, C.c_int])
-        _check(f(C.byref(self._h), float(db), float(alpha), int(ramp), int(bool(gate)), int(device)))
+        _Block.__init__(self)
+        self._create(float(db), float(alpha), int(ramp), int(bool(gate)), int(device))
 
 
 class pwr_squelch_cc(_pwr_squelch):
@@ -1903,9 +1516,8 @@ class simple_squelch_cc(_squelch):
     _name = "simple_squelch_cc"
 
     def __init__(self, threshold_db, alpha=0.0001, device=0):
-        _squelch.__init__(self)
-        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_int])
-        _check(f(C.byref(self._h), float(threshold_db), float(alpha), int(device)))
+        _Block.__init__(self)
+        self._create(float(threshold_db), float(alpha), int(device))
 
 
 class ctcss_squelch_ff(_squelch_streams, _ramp_gate):
@@ -1916,18 +1528,17 @@ class ctcss_squelch_ff(_squelch_streams, _ramp_gate):
     _dtype = np.float32
 
     def __init__(self, rate, freq, level=0.01, len=0, ramp=0, gate=False, device=0):
-        _squelch_streams.__init__(self)
-        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int])
-        _check(f(C.byref(self._h), int(rate), float(freq), float(level), int(len), int(ramp), int(bool(gate)), int(device)))
+        _Block.__init__(self)
+        self._create(int(rate), float(freq), float(level), int(len), int(ramp), int(bool(gate)), int(device))
 
     def level(self):
-        return self._fn("level", [C.c_void_p], C.c_float)(self._h)
+        return self._fn("level")(self._h)
 
     def set_level(self, level):
-        _check(self._fn("set_level", [C.c_void_p, C.c_float])(self._h, float(level)))
+        self._call("set_level", float(level))
 
     def len(self):
-        return _check(self._fn("len", [C.c_void_p])(self._h))
+        return self._call("len")
 
     @staticmethod
     def squelch_range():
@@ -1938,82 +1549,51 @@ class ctcss_squelch_ff(_squelch_streams, _ramp_gate):
     def state(self, stream=0):
         """(state, ramped, envelope, d_mute, samples of the unfinished block) of one stream"""
         st, r, e, m, p = C.c_int(0), C.c_int(0), C.c_double(0), C.c_int(0), C.c_int(0)
-        f = self._fn("state", [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
-                               C.POINTER(C.c_int), C.POINTER(C.c_int)])
-        _check(f(self._h, int(stream), C.byref(st), C.byref(r), C.byref(e), C.byref(m), C.byref(p)))
+        self._call("state", int(stream), C.byref(st), C.byref(r), C.byref(e), C.byref(m), C.byref(p))
         return st.value, r.value, e.value, bool(m.value), p.value
 
     def tones(self):
         """(left guard, tone, right guard) in Hz, as float32"""
         v = [C.c_float(0), C.c_float(0), C.c_float(0)]
-        f = self._fn("tones", [C.c_void_p] + [C.POINTER(C.c_float)] * 3)
-        _check(f(self._h, C.byref(v[0]), C.byref(v[1]), C.byref(v[2])))
+        self._call("tones", C.byref(v[0]), C.byref(v[1]), C.byref(v[2]))
         return tuple(np.float32(x.value) for x in v)
 
     def last_magnitudes(self, n_blocks, stream=0):
         """|l|, |c|, |r| of the blocks the last work call completed, [blocks][3] float32 (for tests)"""
         out = np.zeros((max(int(n_blocks), 1), 3), dtype=np.float32)
-        f = self._fn("last_magnitudes", [C.c_void_p, C.c_int, C.c_void_p, C.c_int])
-        got = _check(f(self._h, int(stream), _ptr(out), int(n_blocks)))
+        got = self._call("last_magnitudes", int(stream), _ptr(out), int(n_blocks))
         return out[:got]
 
 
 class _agc(_Block):
     """what the four gain loops share: work(x) takes streams x n_in items back to back and returns as many; every
     stream's gain carries across calls.  The setters act at once (they hold from the next work call), as the
-    reference's do; set_gain sets every stream's gain."""
-    _name = None
+    reference's do; set_gain sets every stream's gain, and set_streams sets it to the constructor's.  work_device
+    does not synchronise.  The float getters return the value itself, not a status."""
     _dtype = np.complex64
-
-    def __init__(self):
-        _Block.__init__(self)
-        self._destroy = "grhip_%s_destroy" % self._name
-        self._streams = 1
-
-    def _fn(self, name, argtypes=None, restype=None):
-        f = getattr(lib(), "grhip_%s_%s" % (self._name, name))
-        if argtypes is not None:
-            f.argtypes = argtypes
-        if restype is not None:
-            f.restype = restype
-        return f
-
-    def _get(self, name):
-        return self._fn(name, [C.c_void_p], C.c_float)(self._h)
-
-    def _set(self, name, v):
-        _check(self._fn("set_" + name, [C.c_void_p, C.c_float])(self._h, float(v)))
-
-    def set_mode(self, mode):
-        _check(self._fn("set_mode", [C.c_void_p, C.c_int])(self._h, int(mode)))
-
-    def set_streams(self, nstreams):
-        """sets every stream's gain to the constructor's"""
-        _check(self._fn("set_streams", [C.c_void_p, C.c_int])(self._h, int(nstreams)))
-        self._streams = int(nstreams)
 
     def history(self):
         return 1
 
     def reference(self):
-        return self._get("reference")
+        return self._fn("reference")(self._h)
 
     def set_reference(self, reference):
-        self._set("reference", reference)
+        self._call("set_reference", float(reference))
 
     def max_gain(self):
-        return self._get("max_gain")
+        return self._fn("max_gain")(self._h)
 
     def set_max_gain(self, max_gain):
-        self._set("max_gain", max_gain)
+        self._call("set_max_gain", float(max_gain))
 
     def gain(self, stream=0):
         v = C.c_float(0)
-        _check(self._fn("gain", [C.c_void_p, C.c_int, C.POINTER(C.c_float)])(self._h, int(stream), C.byref(v)))
+        self._call("gain", int(stream), C.byref(v))
         return np.float32(v.value)
 
     def set_gain(self, gain):
-        self._set("gain", gain)
+        self._call("set_gain", float(gain))
 
     def work(self, input_items, n_in=None):
         x = np.ascontiguousarray(input_items, dtype=self._dtype).reshape(-1)
@@ -2022,13 +1602,8 @@ class _agc(_Block):
         if len(x) < n_in * self._streams:
             raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
         out = np.zeros(max(n_in * self._streams, 1), dtype=self._dtype)
-        _check(self._fn("work", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])(self._h, int(n_in), _ptr(x), _ptr(out)))
+        self._call("work", int(n_in), _ptr(x), _ptr(out))
         return out[:n_in * self._streams]
-
-    def work_device(self, n_in, d_in, d_out, stream=None):
-        """device buffers; does not synchronise"""
-        f = self._fn("work_device", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
-        return _check(f(self._h, int(n_in), _devptr(d_in), _devptr(d_out), _stream(stream)))
 
     @staticmethod
     def chunk():
@@ -2038,35 +1613,32 @@ class _agc(_Block):
 
 class _agc1(_agc):
     def __init__(self, rate=1e-4, reference=1.0, gain=1.0, max_gain=0.0, device=0):
-        _agc.__init__(self)
-        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_float, C.c_float, C.c_float, C.c_float, C.c_int])
-        _check(f(C.byref(self._h), float(rate), float(reference), float(gain), float(max_gain), int(device)))
+        _Block.__init__(self)
+        self._create(float(rate), float(reference), float(gain), float(max_gain), int(device))
 
     def rate(self):
-        return self._get("rate")
+        return self._fn("rate")(self._h)
 
     def set_rate(self, rate):
-        self._set("rate", rate)
+        self._call("set_rate", float(rate))
 
 
 class _agc2(_agc):
     def __init__(self, attack_rate=1e-1, decay_rate=1e-2, reference=1.0, gain=1.0, max_gain=0.0, device=0):
-        _agc.__init__(self)
-        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int])
-        _check(f(C.byref(self._h), float(attack_rate), float(decay_rate), float(reference), float(gain), float(max_gain),
-                 int(device)))
+        _Block.__init__(self)
+        self._create(float(attack_rate), float(decay_rate), float(reference), float(gain), float(max_gain), int(device))
 
     def attack_rate(self):
-        return self._get("attack_rate")
+        return self._fn("attack_rate")(self._h)
 
     def set_attack_rate(self, rate):
-        self._set("attack_rate", rate)
+        self._call("set_attack_rate", float(rate))
 
     def decay_rate(self):
-        return self._get("decay_rate")
+        return self._fn("decay_rate")(self._h)
 
     def set_decay_rate(self, rate):
-        self._set("decay_rate", rate)
+        self._call("set_decay_rate", float(rate))
 
 
 class agc_cc(_agc1):
@@ -2099,25 +1671,18 @@ class agc2_ff(_agc2):
 class keep_one_in_n(_Block):
     """gr.keep_one_in_n(item_size, n): work takes the input items as an array whose itemsize is item_size (or as bytes)
     and returns the kept ones; the countdown carries across calls"""
-    _destroy = "grhip_keep_one_in_n_destroy"
+    _name = "keep_one_in_n"
 
     def __init__(self, item_size, n, device=0):
         _Block.__init__(self)
         self._item = int(item_size)
-        self._streams = 1
-        L = lib()
-        L.grhip_keep_one_in_n_create.argtypes = [C.POINTER(C.c_void_p), C.c_size_t, C.c_int, C.c_int]
-        _check(L.grhip_keep_one_in_n_create(C.byref(self._h), self._item, int(n), int(device)))
+        self._create(self._item, int(n), int(device))
 
     def set_n(self, n):
-        _check(lib().grhip_keep_one_in_n_set_n(self._h, int(n)))
-
-    def set_streams(self, nstreams):
-        _check(lib().grhip_keep_one_in_n_set_streams(self._h, int(nstreams)))
-        self._streams = int(nstreams)
+        self._call("set_n", int(n))
 
     def produced(self, n_in):
-        return _check(lib().grhip_keep_one_in_n_produced(self._h, int(n_in)))
+        return self._call("produced", int(n_in))
 
     def work(self, n_in, input_items):
         x = np.ascontiguousarray(input_items)
@@ -2125,16 +1690,10 @@ class keep_one_in_n(_Block):
         if len(raw) < n_in * self._streams * self._item:
             raise ValueError("work needs %d input bytes, got %d" % (n_in * self._streams * self._item, len(raw)))
         out = np.zeros(max(self.produced(n_in), 1) * self._streams * self._item, dtype=np.uint8)
-        L = lib()
-        L.grhip_keep_one_in_n_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        r = _check(L.grhip_keep_one_in_n_work(self._h, int(n_in), _ptr(raw), _ptr(out)))
+        r = self._call("work", int(n_in), _ptr(raw), _ptr(out))
         out = out[:r * self._streams * self._item]
         return out.view(x.dtype) if self._item % x.dtype.itemsize == 0 else out
 
-    def work_device(self, n_in, d_in, d_out, stream=None):
-        L = lib()
-        L.grhip_keep_one_in_n_work_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_keep_one_in_n_work_device(self._h, int(n_in), _devptr(d_in), _devptr(d_out), _stream(stream)))
 
 # ----------------------------------------------------------------------------
 # blks2.logpwrfft_c / logpwrfft_f (blks2impl/logpwrfft.py:26-154) and window.blackmanharris (gnuradio/window.py:166-176)
@@ -2145,84 +1704,63 @@ def window_blackmanharris(fft_size):
     if fft_size < 0 or fft_size > (1 << 26):
         raise ValueError("fft_size out of range")
     out = np.zeros(max(fft_size, 1), dtype=np.float64)
-    L = lib()
-    L.grhip_window_blackmanharris.argtypes = [C.c_int, C.c_void_p]
-    _raise_like_reference(L.grhip_window_blackmanharris(fft_size, _ptr(out)))
+    _check(lib().grhip_window_blackmanharris(fft_size, _ptr(out)))
     return out[:fft_size]
 
 
 class _logpwrfft(_Block):
     """blks2.logpwrfft_X(sample_rate, fft_size, ref_scale, frame_rate, avg_alpha, average, win=None): win is the
     reference's window FUNCTION (called with fft_size) or the sequence of doubles it would return.  work takes whole
-    frames of fft_size samples (streams back to back) and returns the kept frames' fft_size floats of dB each."""
-    _name = None
+    frames of fft_size samples (streams back to back) and returns the kept frames' fft_size floats of dB each.
+    set_streams restarts the averaging state and the frame countdown."""
     _in = None
 
     def __init__(self, sample_rate, fft_size, ref_scale, frame_rate, avg_alpha, average, win=None, device=0):
         _Block.__init__(self)
-        self._destroy = "grhip_%s_destroy" % self._name
         self._n = int(fft_size)
-        self._streams = 1
         if callable(win):
             win = win(self._n)
         w = None if win is None else np.ascontiguousarray(win, dtype=np.float64).reshape(-1)
-        f = self._fn("create", [C.POINTER(C.c_void_p), C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
-                                C.c_void_p, C.c_size_t, C.c_int])
-        _check(f(C.byref(self._h), float(sample_rate), self._n, float(ref_scale), float(frame_rate), float(avg_alpha),
-                 int(bool(average)), None if w is None else _ptr(w), 0 if w is None else len(w), int(device)))
-
-    def _fn(self, name, argtypes=None, restype=C.c_int):
-        f = getattr(lib(), "grhip_%s_%s" % (self._name, name))
-        if argtypes is not None:
-            f.argtypes = argtypes
-        f.restype = restype
-        return f
-
-    def set_mode(self, mode):
-        _check(self._fn("set_mode", [C.c_void_p, C.c_int])(self._h, int(mode)))
-
-    def set_streams(self, nstreams):
-        """work / work_device then take nstreams streams of n_frames each, back to back; restarts state and countdown"""
-        _check(self._fn("set_streams", [C.c_void_p, C.c_int])(self._h, int(nstreams)))
-        self._streams = int(nstreams)
+        self._create(float(sample_rate), self._n, float(ref_scale), float(frame_rate), float(avg_alpha),
+                     int(bool(average)), None if w is None else _ptr(w), 0 if w is None else len(w), int(device))
 
     def set_decimation(self, decim):
-        _check(self._fn("set_decimation", [C.c_void_p, C.c_double])(self._h, float(decim)))
+        self._call("set_decimation", float(decim))
 
     def set_vec_rate(self, vec_rate):
-        _check(self._fn("set_vec_rate", [C.c_void_p, C.c_double])(self._h, float(vec_rate)))
+        self._call("set_vec_rate", float(vec_rate))
 
     def set_sample_rate(self, sample_rate):
-        _check(self._fn("set_sample_rate", [C.c_void_p, C.c_double])(self._h, float(sample_rate)))
+        self._call("set_sample_rate", float(sample_rate))
 
     def set_average(self, average):
-        _check(self._fn("set_average", [C.c_void_p, C.c_int])(self._h, int(bool(average))))
+        self._call("set_average", int(bool(average)))
 
     def set_avg_alpha(self, avg_alpha):
-        _check(self._fn("set_avg_alpha", [C.c_void_p, C.c_double])(self._h, float(avg_alpha)))
+        self._call("set_avg_alpha", float(avg_alpha))
 
     def sample_rate(self):
-        return self._fn("sample_rate", [C.c_void_p], C.c_double)(self._h)
+        return self._fn("sample_rate")(self._h)
 
     def decimation(self):
-        return _check(self._fn("decimation", [C.c_void_p])(self._h))
+        return self._call("decimation")
 
     def frame_rate(self):
-        return self._fn("frame_rate", [C.c_void_p], C.c_double)(self._h)
+        return self._fn("frame_rate")(self._h)
 
     def average(self):
-        return bool(_check(self._fn("average", [C.c_void_p])(self._h)))
+        return bool(self._call("average"))
 
     def avg_alpha(self):
-        return self._fn("avg_alpha", [C.c_void_p], C.c_double)(self._h)
+        return self._fn("avg_alpha")(self._h)
 
     def produced(self, n_frames):
-        return _check(self._fn("produced", [C.c_void_p, C.c_int])(self._h, int(n_frames)))
+        return self._call("produced", int(n_frames))
 
     def state(self):
         """the averaging filter's state: streams x fft_size floats of linear power"""
         out = np.zeros(self._streams * self._n, dtype=np.float32)
-        _check(self._fn("state", [C.c_void_p, C.c_void_p])(self._h, _ptr(out)))
+        self._call("state", _ptr(out))
         return out
 
     def work(self, n_frames, input_items):
@@ -2231,12 +1769,8 @@ class _logpwrfft(_Block):
         if len(x) < need:
             raise ValueError("work needs %d input samples, got %d" % (need, len(x)))
         out = np.zeros(max(self.produced(n_frames), 1) * self._streams * self._n, dtype=np.float32)
-        r = _check(self._fn("work", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p])(self._h, int(n_frames), _ptr(x), _ptr(out)))
+        r = self._call("work", int(n_frames), _ptr(x), _ptr(out))
         return out[:r * self._streams * self._n]
-
-    def work_device(self, n_frames, d_in, d_out, stream=None):
-        f = self._fn("work_device", [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
-        return _check(f(self._h, int(n_frames), _devptr(d_in), _devptr(d_out), _stream(stream)))
 
 
 class logpwrfft_c(_logpwrfft):
@@ -2248,48 +1782,42 @@ class logpwrfft_f(_logpwrfft):
     _name = "logpwrfft_f"
     _in = np.float32
 
+
 # ----------------------------------------------------------------------------
 # gr.interp_fir_filter_XXX / gr.rational_resampler_base_XXX  (filter/gr_interp_fir_filter_XXX.i.t,
 # filter/gr_rational_resampler_base_XXX.i.t) and blks2.rational_resampler_XXX
 # (python/gnuradio/blks2impl/rational_resampler.py)
 # ----------------------------------------------------------------------------
-_RS_CAPTURES_ARGS = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                     C.POINTER(C.c_size_t), C.c_void_p]
+def _uint_arg(v):
+    """a rate factor for a C unsigned: a negative one is out of range, as 0 is"""
+    v = int(v)
+    if v < 0:
+        raise GrhipError(-2, "negative rate factor %d" % v)
+    return v
 
 
 class _rs_block(_Block):
-    _prefix = None
     _kind = None
     _dtype = np.complex64
     _tap = np.float32
 
-    def _fn(self, name):
-        return getattr(lib(), "%s_%s" % (self._prefix, name))
-
     def set_taps(self, taps):
         t = np.ascontiguousarray(taps, dtype=self._tap)
-        f = self._fn("set_taps")
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        _check(f(self._h, _ptr(t), len(t)))
-
-    def set_mode(self, mode):
-        _check(self._fn("set_mode")(self._h, int(mode)))
+        self._call("set_taps", _ptr(t), len(t))
 
     def history(self):
-        return _check(self._fn("history")(self._h))
+        return self._call("history")
 
     def interpolation(self):
-        return _check(self._fn("interpolation")(self._h))
+        return self._call("interpolation")
 
     def run_captures_device(self, n_streams, n_samples, d_in, in_stride_items, d_out, out_stride_items,
                             stream=None):
         """n_streams fresh captures in one launch; returns the outputs per capture.  d_out=None only returns that
         number."""
         n_out = C.c_size_t(0)
-        f = self._fn("run_captures_device")
-        f.argtypes = _RS_CAPTURES_ARGS
-        _check(f(self._h, int(n_streams), int(n_samples), _devptr(d_in), int(in_stride_items), _devptr(d_out),
-                 int(out_stride_items), C.byref(n_out), _stream(stream)))
+        self._call("run_captures_device", int(n_streams), int(n_samples), _devptr(d_in), int(in_stride_items),
+                   _devptr(d_out), int(out_stride_items), C.byref(n_out), _stream(stream))
         return n_out.value
 
     def captures_nout(self, n_samples):
@@ -2298,15 +1826,12 @@ class _rs_block(_Block):
 
 
 class _interp_fir_filter(_rs_block):
-    _prefix = "grhip_interp_fir_filter"
-    _destroy = "grhip_interp_fir_filter_destroy"
+    _name = "interp_fir_filter"
 
     def __init__(self, interpolation, taps, device=0):
         _Block.__init__(self)
         t = np.ascontiguousarray(taps, dtype=self._tap)
-        f = self._fn("create")
-        f.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_uint, C.c_void_p, C.c_size_t, C.c_int]
-        _check(f(C.byref(self._h), self._kind.encode(), _uint_arg(interpolation), _ptr(t), len(t), int(device)))
+        self._create(self._kind.encode(), _uint_arg(interpolation), _ptr(t), len(t), int(device))
 
     def output_multiple(self):
         return self.interpolation()
@@ -2320,64 +1845,42 @@ class _interp_fir_filter(_rs_block):
         if n >= 0 and n % I == 0 and len(x) < n // I + self.history() - 1:
             raise ValueError("work: %d outputs need %d input items, got %d" % (n, n // I + self.history() - 1, len(x)))
         out = np.zeros(max(n, 1), dtype=self._dtype)
-        f = self._fn("work")
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        r = _check(f(self._h, n, _ptr(x), _ptr(out)))
+        r = self._call("work", n, _ptr(x), _ptr(out))
         return out[:r].copy()
-
-    def work_device(self, noutput_items, d_in, d_out, stream=None):
-        f = self._fn("work_device")
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        return _check(f(self._h, int(noutput_items), _devptr(d_in), _devptr(d_out), _stream(stream)))
 
 
 class _rational_resampler_base(_rs_block):
-    _prefix = "grhip_rational_resampler_base"
-    _destroy = "grhip_rational_resampler_base_destroy"
+    _name = "rational_resampler_base"
 
     def __init__(self, interpolation, decimation, taps, device=0):
         _Block.__init__(self)
         t = np.ascontiguousarray(taps, dtype=self._tap)
-        f = self._fn("create")
-        f.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.c_int]
-        _check(f(C.byref(self._h), self._kind.encode(), _uint_arg(interpolation), _uint_arg(decimation), _ptr(t),
-                 len(t), int(device)))
+        self._create(self._kind.encode(), _uint_arg(interpolation), _uint_arg(decimation), _ptr(t), len(t),
+                     int(device))
 
     def decimation(self):
-        return _check(self._fn("decimation")(self._h))
+        return self._call("decimation")
 
     def relative_rate(self):
         return 1.0 * self.interpolation() / self.decimation()
 
     def forecast(self, noutput_items):
-        return _check(self._fn("forecast")(self._h, int(noutput_items)))
+        return self._call("forecast", int(noutput_items))
 
     def general_work(self, noutput_items, input_items):
         """returns (out, consumed); no history in front of input_items (the scheduler sees history 1)"""
         x = np.ascontiguousarray(input_items, dtype=self._dtype)
         out = np.zeros(max(int(noutput_items), 1), dtype=self._dtype)
         consumed = C.c_int(0)
-        f = self._fn("general_work")
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-        n = _check(f(self._h, int(noutput_items), len(x), _ptr(x), _ptr(out), C.byref(consumed)))
+        n = self._call("general_work", int(noutput_items), len(x), _ptr(x), _ptr(out), C.byref(consumed))
         return out[:n].copy(), consumed.value
 
     def general_work_device(self, noutput_items, ninput_items, d_in, d_out, stream=None):
         """returns (produced, consumed); the outputs are in d_out once `stream` has run"""
         consumed = C.c_int(0)
-        f = self._fn("general_work_device")
-        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]
-        n = _check(f(self._h, int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out),
-                     C.byref(consumed), _stream(stream)))
+        n = self._call("general_work_device", int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out),
+                       C.byref(consumed), _stream(stream))
         return n, consumed.value
-
-
-def _uint_arg(v):
-    """a rate factor for a C unsigned: a negative one is out of range, as 0 is"""
-    v = int(v)
-    if v < 0:
-        raise GrhipError(-2, "negative rate factor %d" % v)
-    return v
 
 
 class interp_fir_filter_ccf(_interp_fir_filter):
@@ -2512,6 +2015,7 @@ class rational_resampler_ccc(_rational_resampler):
     _base = rational_resampler_base_ccc
 
 
+
 # ----------------------------------------------------------------------------
 # gr.pfb_interpolator_ccf / gr.pfb_synthesis_filterbank_ccf  (filter/gr_pfb_interpolator_ccf.i,
 # filter/gr_pfb_synthesis_filterbank_ccf.i)
@@ -2519,15 +2023,12 @@ class rational_resampler_ccc(_rational_resampler):
 class pfb_interpolator_ccf(_interp_fir_filter):
     """gr.pfb_interpolator_ccf(interp, taps): gr_interp_fir_filter's schedule with the zeros behind the taps.
     (blks2.pfb_interpolator_ccf designs default taps with optfir; here the taps are required.)"""
-    _prefix = "grhip_pfb_interpolator_ccf"
-    _destroy = "grhip_pfb_interpolator_ccf_destroy"
+    _name = "pfb_interpolator_ccf"
 
     def __init__(self, interp, taps, device=0):
         _Block.__init__(self)
         t = np.ascontiguousarray(taps, dtype=np.float32)
-        f = self._fn("create")
-        f.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_void_p, C.c_size_t, C.c_int]
-        _check(f(C.byref(self._h), _uint_arg(interp), _ptr(t), len(t), int(device)))
+        self._create(_uint_arg(interp), _ptr(t), len(t), int(device))
 
     def taps_per_filter(self):
         return self.history()
@@ -2542,30 +2043,23 @@ class pfb_interpolator_ccf(_interp_fir_filter):
 class pfb_synthesis_filterbank_ccf(_Block):
     """gr.pfb_synthesis_filterbank_ccf(numchans, taps): 1..numchans complex streams in, one stream out at numchans
     times the rate"""
-    _destroy = "grhip_pfb_synthesis_filterbank_ccf_destroy"
+    _name = "pfb_synthesis_filterbank_ccf"
 
     def __init__(self, numchans, taps, device=0):
         _Block.__init__(self)
         t = np.ascontiguousarray(taps, dtype=np.float32)
         self.numchans = int(numchans)
-        f = lib().grhip_pfb_synthesis_filterbank_ccf_create
-        f.argtypes = [C.POINTER(C.c_void_p), C.c_uint, C.c_void_p, C.c_size_t, C.c_int]
-        _check(f(C.byref(self._h), _uint_arg(numchans), _ptr(t), len(t), int(device)))
+        self._create(_uint_arg(numchans), _ptr(t), len(t), int(device))
 
     def set_taps(self, taps):
         t = np.ascontiguousarray(taps, dtype=np.float32)
-        f = lib().grhip_pfb_synthesis_filterbank_ccf_set_taps
-        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        _check(f(self._h, _ptr(t), len(t)))
-
-    def set_mode(self, mode):
-        _check(lib().grhip_pfb_synthesis_filterbank_ccf_set_mode(self._h, int(mode)))
+        self._call("set_taps", _ptr(t), len(t))
 
     def history(self):
-        return _check(lib().grhip_pfb_synthesis_filterbank_ccf_history(self._h))
+        return self._call("history")
 
     def taps_per_filter(self):
-        return _check(lib().grhip_pfb_synthesis_filterbank_ccf_taps_per_filter(self._h))
+        return self._call("taps_per_filter")
 
     def output_multiple(self):
         return self.numchans
@@ -2584,17 +2078,13 @@ class pfb_synthesis_filterbank_ccf(_Block):
                     raise ValueError("work: %d outputs need %d items per stream, got %d" % (n, need, len(a)))
         ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
         out = np.zeros(max(n, 1), dtype=np.complex64)
-        f = lib().grhip_pfb_synthesis_filterbank_ccf_work
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        r = _check(f(self._h, n, ptrs, len(arrs), _ptr(out)))
+        r = self._call("work", n, ptrs, len(arrs), _ptr(out))
         return out[:r].copy()
 
     def work_device(self, noutput_items, d_in, stream_stride_items, numsigs, d_out, stream=None):
         """stream s at d_in + s*stream_stride_items; the outputs are in d_out once `stream` has run"""
-        f = lib().grhip_pfb_synthesis_filterbank_ccf_work_device
-        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]
-        return _check(f(self._h, int(noutput_items), _devptr(d_in), int(stream_stride_items), int(numsigs),
-                        _devptr(d_out), _stream(stream)))
+        return self._call("work_device", int(noutput_items), _devptr(d_in), int(stream_stride_items), int(numsigs),
+                          _devptr(d_out), _stream(stream))
 
 
 # ----------------------------------------------------------------------------
@@ -2609,7 +2099,7 @@ class _ChainParams(C.Structure):
 
 
 class dmr_chain(_Block):
-    _destroy = "grhip_dmr_chain_destroy"
+    _name = "dmr_chain"
 
     def __init__(self, decimation, taps, center_freq, sampling_freq, demod_gain, omega, gain_omega, mu,
                  gain_mu, omega_relative_limit, access_code, threshold, n_streams, max_samples, device=0):
@@ -2621,47 +2111,27 @@ class dmr_chain(_Block):
                          float(sampling_freq), float(demod_gain), float(omega), float(gain_omega), float(mu),
                          float(gain_mu), float(omega_relative_limit), code, len(code), int(threshold))
         self.n_streams = int(n_streams)
-        L = lib()
-        L.grhip_dmr_chain_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(_ChainParams), C.c_int,
-                                             C.c_size_t, C.c_int]
-        _check(L.grhip_dmr_chain_create(C.byref(self._h), C.byref(p), self.n_streams, int(max_samples),
-                                        int(device)))
-
-    def set_mode(self, mode):
-        _check(lib().grhip_dmr_chain_set_mode(self._h, int(mode)))
+        self._create(C.byref(p), self.n_streams, int(max_samples), int(device))
 
     def set_captures_per_wave(self, captures):
-        L = lib()
-        L.grhip_dmr_chain_set_captures_per_wave.argtypes = [C.c_void_p, C.c_int]
-        _check(L.grhip_dmr_chain_set_captures_per_wave(self._h, int(captures)))
+        self._call("set_captures_per_wave", int(captures))
 
     def set_max_symbols(self, max_symbols):
         """noutput_items of the clock recovery per capture (0: unbounded)"""
-        L = lib()
-        L.grhip_dmr_chain_set_max_symbols.argtypes = [C.c_void_p, C.c_size_t]
-        _check(L.grhip_dmr_chain_set_max_symbols(self._h, int(max_symbols)))
+        self._call("set_max_symbols", int(max_symbols))
 
     def set_four_level(self, enable, pager_alpha=0.001):
         """4FSK tail: pager.slicer_fb(alpha) -> unpack_k_bits_bb(2) -> correlator; two output items per symbol"""
-        L = lib()
-        L.grhip_dmr_chain_set_four_level.argtypes = [C.c_void_p, C.c_int, C.c_float]
-        _check(L.grhip_dmr_chain_set_four_level(self._h, int(bool(enable)), float(pager_alpha)))
+        self._call("set_four_level", int(bool(enable)), float(pager_alpha))
 
     def run_device(self, d_in, n_samples, stream_stride_items, d_bits, bits_stride, d_nbits, stream=None):
-        L = lib()
-        L.grhip_dmr_chain_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
-                                                 C.c_size_t, C.c_void_p, C.c_void_p]
-        return _check(L.grhip_dmr_chain_run_device(self._h, _devptr(d_in), int(n_samples),
-                                                   int(stream_stride_items), _devptr(d_bits),
-                                                   int(bits_stride), _devptr(d_nbits), _stream(stream)))
+        return self._call("run_device", _devptr(d_in), int(n_samples), int(stream_stride_items), _devptr(d_bits),
+                          int(bits_stride), _devptr(d_nbits), _stream(stream))
 
     def intermediate(self, which):
         p = C.c_void_p(0)
         stride = C.c_size_t(0)
-        L = lib()
-        L.grhip_dmr_chain_intermediate.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p),
-                                                   C.POINTER(C.c_size_t)]
-        _check(L.grhip_dmr_chain_intermediate(self._h, int(which), C.byref(p), C.byref(stride)))
+        self._call("intermediate", int(which), C.byref(p), C.byref(stride))
         return p.value, stride.value
 
 

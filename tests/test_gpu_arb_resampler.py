@@ -260,7 +260,6 @@ def test_capture_past_float_precision(gpu, mode):
 
 def test_bad_arguments_einval(gpu):
     g = gpu
-    import ctypes as C
     L = g.lib()
     taps = np.ones(64, np.float32)
     blk = g.pfb_arb_resampler_ccf(0.5, taps, 32)
@@ -274,8 +273,6 @@ def test_bad_arguments_einval(gpu):
     with pytest.raises(g.GrhipError) as e:
         blk.forecast(-1)
     assert e.value.code == -1
-    L.grhip_pfb_arb_resampler_ccf_general_work.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                                           C.c_void_p]
     x = np.zeros(100, np.complex64)
     out = np.zeros(100, np.complex64)
     assert L.grhip_pfb_arb_resampler_ccf_general_work(blk._h, 10, 100, x.ctypes.data, out.ctypes.data, None) == -1

@@ -172,10 +172,8 @@ def test_fft_filter_fff_refusals(gpu):
     with pytest.raises(gpu.GrhipError):
         gpu.fft_filter_fff(1, [])
     L = gpu.lib()
-    L.grhip_fft_filter_fff_work.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     buf = np.zeros(8, np.float32)
     assert L.grhip_fft_filter_fff_work(None, 2, C.c_void_p(buf.ctypes.data), C.c_void_p(buf.ctypes.data)) < 0
-    L.grhip_fft_filter_fff_nsamples.argtypes = [C.c_void_p]
     assert L.grhip_fft_filter_fff_nsamples(None) < 0
 
 

@@ -94,9 +94,6 @@ def test_create_refusals_before_any_device(g):
     L = g.lib()
     h = C.c_void_p(0)
     taps = np.ones(16, np.float32)
-    L.grhip_fir_filter_create.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int]
-    L.grhip_freq_xlating_fir_filter_create.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_int, C.c_void_p, C.c_size_t,
-                                                       C.c_double, C.c_double, C.c_int]
     fc, xc = L.grhip_fir_filter_create, L.grhip_freq_xlating_fir_filter_create
     for k in (b"fcc", b"scc", b"fsf"):
         assert fc(C.byref(h), k, 0, taps.ctypes.data, 8, 0) == -1

@@ -156,10 +156,6 @@ def test_create_refusals_before_any_device(g, kind):
     L = _lib(g)
     h = C.c_void_p(0)
     taps = np.ones(8, np.complex64 if kind == "ccc" else np.float32)
-    L.grhip_rational_resampler_base_create.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_uint, C.c_uint,
-                                                       C.c_void_p, C.c_size_t, C.c_int]
-    L.grhip_interp_fir_filter_create.argtypes = [C.POINTER(C.c_void_p), C.c_char_p, C.c_uint, C.c_void_p,
-                                                 C.c_size_t, C.c_int]
     rs = L.grhip_rational_resampler_base_create
     ip = L.grhip_interp_fir_filter_create
     assert rs(C.byref(h), kind.encode(), 0, 2, taps.ctypes.data, 8, 0) == -2
