@@ -156,7 +156,8 @@ int grhip_dmr_chain_create(grhip_dmr_chain **h, const grhip_dmr_chain_params *p,
         c->core.center_freq = p->center_freq; c->core.sampling_freq = p->sampling_freq;
         c->core.for_demod = true;           // decimations other than 1/2/4: the direct kernel with the fused demodulator
         if ((rc = c->core.build(device))) return rc;
-        if (!c->core.use_tiled && !c->core.use_mfma && !(c->core.use_hidec && c->core.hidec_premix))
+        // (whatever the mode of a later run: GENERIC has its own batched kernel or runs capture by capture)
+        if (!fir_has_batched_engine(c->core.eng.plan, GRHIP_MODE_FAST))
             return fail(GRHIP_EINVAL, "dmr_chain needs a decimation/tap count a batched FIR engine supports");
         hipError_t e = hipStreamCreateWithFlags(c->st2.put(), hipStreamNonBlocking);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(c->st3.put(), hipStreamNonBlocking);

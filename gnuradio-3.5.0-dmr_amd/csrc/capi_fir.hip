@@ -14,22 +14,6 @@ typedef std::complex<float> cf;
 
 namespace grhip {
 
-// ---- tap packing for the tiled kernel ---------------------------------------
-// c[k] multiplies x[nD + k]; hp[p*Tq + q] = c[qD + p], zero padded.
-static int pack_phase_major(const float *c, int T, int tw, int D, std::vector<float> &hp)
-{
-    int R = tiled_R();
-    int per = (T + D - 1) / D;
-    int Tq = ((per + R - 1) / R) * R;
-    if (Tq == 0) Tq = R;
-    hp.assign(((size_t)D * Tq + R) * tw, 0.f);     // + R taps: the kernel prefetches one iteration ahead
-    for (int k = 0; k < T; ++k) {
-        int p = k % D, q = k / D;
-        for (int w = 0; w < tw; ++w) hp[((size_t)p * Tq + q) * tw + w] = c[(size_t)k * tw + w];
-    }
-    return Tq;
-}
-
 static int upload(DevBuf &b, const void *src, size_t bytes)
 {
     int rc = b.reserve(bytes ? bytes : 16);
@@ -38,62 +22,208 @@ static int upload(DevBuf &b, const void *src, size_t bytes)
     return GRHIP_OK;
 }
 
-// ---- operand tables of the matrix-core engine (mfma_tables.h) ---------------------
-// real taps c[k] multiplying x[nD + k]; both alignment parities
-// fwT0 != 0: freq_xlating's pre-mix form -- the table carries the correction band G of the reference's tap-angle
-// quantisation behind A (mfma_tables.h); 0: plain real taps (gr_fir_ccf), G all zero
-static int build_mfma_taps(const float *c, int T, int D, DevBuf (&dA)[2], int *kexp, float fwT0 = 0.f)
+template <class A> static A zeroed() { A a; memset(&a, 0, sizeof(a)); return a; }
+
+// ============================================================================
+// FirEngines (fir_engines.h): every engine of the family packed and launched here
+// ============================================================================
+// taps per phase of the tiled kernel, padded to its R outputs per lane
+static int tiled_Tq(int T, int D)
 {
-    const int KS = mf::ksteps_inst(D, T);
-    *kexp = mf::tap_scale_exp(c, T);
+    const int R = tiled_R(), per = (T + D - 1) / D;
+    return per ? ((per + R - 1) / R) * R : R;
+}
+
+// c[k] multiplies x[nD + k]; hp[p*Tq + q] = c[qD + p], zero padded.
+static int pack_phase_major(const float *c, int T, int tw, int D, std::vector<float> &hp)
+{
+    const int R = tiled_R(), Tq = tiled_Tq(T, D);
+    hp.assign(((size_t)D * Tq + R) * tw, 0.f);     // + R taps: the kernel prefetches one iteration ahead
+    for (int k = 0; k < T; ++k) {
+        int p = k % D, q = k / D;
+        for (int w = 0; w < tw; ++w) hp[((size_t)p * Tq + q) * tw + w] = c[(size_t)k * tw + w];
+    }
+    return Tq;
+}
+
+FirCaps FirEngines::caps(int ntaps, int decim, int tiled_decim)
+{
+    FirCaps c;
+    c.tiled_real = c.tiled_cplx = tiled_decim > 0 && tiled_supported(tiled_decim, tiled_Tq(ntaps, tiled_decim));
+    c.mfma = mfma_supported(decim, ntaps); c.hidec = hidec_supported(decim, ntaps); c.realin = realin_supported(decim, ntaps);
+    return c;
+}
+
+FirTuning FirEngines::tuning()
+{
+    FirTuning tn;
+#ifdef GRHIP_DIAG       // diagnostic builds only (tools/bench_decim.py, tools/bench_ols_crossover.py)
+    if (const char *e = getenv("GRHIP_HIDEC")) tn.hidec = atoi(e);
+    if (const char *e = getenv("GRHIP_OLS_MIN")) tn.ols_min = atoi(e);
+#endif
+    return tn;
+}
+
+int FirEngines::build_tiled(const float *c, int tw)
+{
+    std::vector<float> hp;
+    Tq = pack_phase_major(c, ntaps, tw, plan.tiled_decim, hp);
+    return upload(d_hp, hp.data(), hp.size() * sizeof(float));
+}
+
+// operand tables of the matrix-core engine (mfma_tables.h): real taps, both alignment parities.  The pre-mix form's table
+// carries the correction band G of the reference's tap-angle quantisation behind A; plain real taps (gr_fir_ccf): G all zero
+int FirEngines::build_mfma(const float *c, float fwT0)
+{
+    const int KS = mf::ksteps_inst(decim, ntaps);
+    mf_kexp = mf::tap_scale_exp(c, ntaps);
     for (int off = 0; off < 2; ++off) {
         std::vector<uint16_t> A;
-        mf::build_A(c, T, D, KS, off, *kexp, A);
-        mf::build_G(c, T, D, KS, off, *kexp, fwT0, A);
-        int rc = upload(dA[off], A.data(), A.size() * sizeof(uint16_t));
+        mf::build_A(c, ntaps, decim, KS, off, mf_kexp, A);
+        mf::build_G(c, ntaps, decim, KS, off, mf_kexp, fwT0, A);
+        int rc = upload(d_mf_A[off], A.data(), A.size() * sizeof(uint16_t));
         if (rc) return rc;
     }
     return GRHIP_OK;
 }
 
+// the engine convolves: h[k] = c[ntaps-1-k] multiplies x[i-k], as complex taps
+int FirEngines::build_ols(const float *c, int tw)
+{
+    std::vector<float> h((size_t)ntaps * 2);
+    for (int k = 0; k < ntaps; ++k) {
+        const float *t = c + (size_t)(ntaps - 1 - k) * tw;
+        h[2 * k] = t[0];
+        h[2 * k + 1] = tw == 2 ? t[1] : 0.f;
+    }
+    return ols_build(h.data(), ntaps, decim, d_ols_tw, d_ols_H, &ols_L, &ols_fold);
+}
+
+int FirEngines::build_hidec(const float *c, int tw)
+{
+    std::vector<float> hp;
+    hidec_pad_taps(c, ntaps, tw, decim, hp);
+    return upload(d_hidec_taps, hp.data(), hp.size() * sizeof(float));
+}
+
+int FirEngines::build_realin(const float *c)
+{
+    std::vector<float> hp;
+    ri_Tq = realin_pack_taps(c, ntaps, decim, hp);
+    return upload(d_ri_hp, hp.data(), hp.size() * sizeof(float));
+}
+
+int FirEngines::build_plain(FirKind kind, int decimation, const float *rev, int n)
+{
+    ntaps = n; decim = decimation;
+    const int tw = fir_kind_ctaps(kind) ? 2 : 1;
+    plan = fir_plan_plain(kind, decim, ntaps, caps(ntaps, decim, fir_tiled_decim(kind, decim)), tuning());
+    int rc = GRHIP_OK;
+    if (plan.use_realin) rc = build_realin(rev);
+    if (!rc && plan.use_tiled) rc = build_tiled(rev, tw);
+    if (!rc && plan.use_mfma) rc = build_mfma(rev);
+    if (!rc && plan.use_ols) rc = build_ols(rev, tw);
+    if (!rc && plan.use_hidec) rc = build_hidec(rev, tw);
+    return rc;
+}
+
+int FirEngines::launch_mfma(FirMfmaArgs a, const FirIo &io, bool premix, int epi, hipStream_t st)
+{
+    a.x = (const float2 *)io.x; a.x_stride = io.x_stride; a.n_in = io.n_in; a.n_lo = io.n_lo; a.n_out = io.n_out;
+    a.n_streams = io.n_streams;
+    a.off = io.parity();
+    a.A = d_mf_A[a.off].p; a.kexp = mf_kexp;
+    const bool demod = epi == EPI_DEMOD;
+    if (demod) a.d_out = (float *)io.out; else a.y_out = (float2 *)io.out;
+    a.y_stride = io.out_stride; a.d_stride = io.out_stride;
+    a.vec_store = (((uintptr_t)io.out) & (demod ? 7 : 15)) == 0 && !(io.out_stride & 1);
+    a.sched = mf_sched.get();
+    return launch_fir_mfma(decim, ntaps, premix, epi, a, st);
+}
+
+int FirEngines::launch_tiled(FirTiledArgs a, const FirIo &io, bool ctaps, bool premix, int epi, hipStream_t st)
+{
+    a.x = (const float2 *)io.x; a.x_stride = io.x_stride; a.n_in = io.n_in; a.n_lo = io.n_lo; a.n_out = io.n_out;
+    a.hp = d_hp.as<float>(); a.Tq = Tq;
+    const bool demod = epi == EPI_DEMOD;
+    if (demod) a.d_out = (float *)io.out; else a.y_out = (float2 *)io.out;
+    a.y_stride = io.out_stride; a.d_stride = io.out_stride;
+    a.vec_store = (((uintptr_t)io.out) & 15) == 0 && ((io.out_stride * (demod ? 4 : 8)) & 15) == 0;
+    a.sched = sched.get();
+    return launch_fir_tiled(plan.tiled_decim, ctaps, premix, epi, a, io.n_streams, st);
+}
+
+int FirEngines::launch_hidec(bool ctaps, const FirIo &io, const float2 *gtab, const float2 *etab, const float2 *vtab, hipStream_t st)
+{
+    return launch_fir_hidec(ctaps, d_hidec_taps.as<float>(), ntaps, decim, (const float2 *)io.x, (io.n_out - 1) * decim + ntaps,
+                            (float2 *)io.out, io.n_out, gtab, st, etab, vtab);
+}
+
+// y[n] = sum_k taps[k] x[nD + ntaps-1-k]: the ntaps-1 history items in front of io.x are the engine's "previous call"
+// samples, the rest is the stream (the scheduler guarantees (n-1)*D + ntaps items: nothing past the last needed sample is read)
+int FirEngines::launch_ols(bool real_data, const FirIo &io, hipStream_t st)
+{
+    const long long nin = (io.n_out - 1) * decim + 1;
+    if (real_data) {
+        const float *xf = (const float *)io.x;
+        return launch_fftfilt4096_real(xf + (ntaps - 1), nin, xf, ntaps, d_ols_tw.as<float2>(), d_ols_H.as<float2>(),
+                                       (float *)io.out, io.n_out, decim, ols_L, ols_fold, st);
+    }
+    const float2 *x = (const float2 *)io.x;
+    return launch_fftfilt4096(x + (ntaps - 1), nin, x, ntaps, d_ols_tw.as<float2>(), d_ols_H.as<float2>(), (float2 *)io.out,
+                              io.n_out, decim, ols_L, ols_fold, st);
+}
+
+int FirEngines::launch_realin(bool in_short, const FirIo &io, const float2 *gtab, hipStream_t st)
+{
+    return launch_fir_realin(in_short, decim, d_ri_hp.as<float>(), ri_Tq, io.x, io.n_in, (float2 *)io.out, io.n_out, gtab, st);
+}
+
+int FirEngines::run_plain(FirKind ekind, int mode, const float *taps_rev, const void *d_in, void *d_out, long long n, int dec,
+                          hipStream_t st)
+{
+    if (n <= 0) return GRHIP_OK;
+    FirCall c;
+    c.mode = mode; c.same_decim = dec == decim; c.n = n;
+    c.in_aligned = !(((uintptr_t)d_in) & (ekind == FIR_SCC ? 1 : 3));
+    c.out_aligned = !(((uintptr_t)d_out) & 7);
+    FirIo io{d_in, (n - 1) * dec + ntaps, n, d_out};
+    switch (fir_route(plan, c).engine) {
+    case ENG_REALIN: return launch_realin(ekind == FIR_SCC, io, nullptr, st);
+    case ENG_MFMA: return launch_mfma(zeroed<FirMfmaArgs>(), io, false, EPI_NONE, st);
+    case ENG_TILED: {
+        FirTiledArgs a = zeroed<FirTiledArgs>();
+        if (ekind != FIR_FFF) return launch_tiled(a, io, ekind == FIR_CCC, false, EPI_NONE, st);
+        // gr_fir_fff: output pairs (y[2j], y[2j+1]); an odd last output goes through the generic kernel
+        a.fpair = dec;
+        io.n_out = n / 2;
+        int rc = launch_tiled(a, io, false, false, EPI_NONE, st);
+        if (rc || !(n & 1)) return rc;
+        return launch_fir_generic(ekind, taps_rev, ntaps, (const float *)d_in + (n - 1) * dec, (float *)d_out + (n - 1), 1, dec,
+                                  nullptr, st);
+    }
+    case ENG_HIDEC: return launch_hidec(ekind == FIR_CCC, io, nullptr, nullptr, nullptr, st);
+    case ENG_OLS: return launch_ols(ekind == FIR_FFF, io, st);
+    default: return launch_fir_generic(ekind, taps_rev, ntaps, d_in, d_out, n, dec, nullptr, st);
+    }
+}
+
 // ============================================================================
 // XlatingCore
 // ============================================================================
-// the high-decimation direct kernel where it beats (or replaces) the overlap-save engine
-static bool hidec_wanted(int decim, int ntaps, bool ctaps, bool have_ols)
+// v[i] = e^{j angle(i)}, the angle in double
+template <class Angle>
+static std::vector<cf> phasors(int n, Angle &&angle)
 {
-    if (!hidec_supported(decim, ntaps)) return false;
-#ifdef GRHIP_DIAG       // diagnostic builds only: GRHIP_HIDEC=0 / 1 = never / whenever supported (tools/bench_decim.py)
-    static int knob = -1;
-    if (knob < 0) { const char *e = getenv("GRHIP_HIDEC"); knob = e ? 2 + atoi(e) : 0; }
-    if (knob == 2) return false;
-    if (knob == 3) return true;
-#endif
-    if (!have_ols) return true;
-    // MACs per input sample (complex taps count twice) against what the engine delivers for the shape
-    // (profiles/r02_decim_engines.log, round 2's kernels on both sides): the direct kernel runs at roughly 400 Gsamples/s
-    // at 8 MACs, 320-400 at 20, 250 at 40, 130-200 at 80; the engine at 330-400 where its inverse folds (decimation 8, 16),
-    // 210-250 elsewhere up to ~500 taps, less for longer filters.
-    const double w = (double)ntaps / decim * (ctaps ? 2.0 : 1.0);
-    if (decim == 8 || decim == 16) return w <= 16.0;
-    if (w <= 32.0) return true;
-    return w <= 48.0 && ntaps <= 512 && decim >= 5;
+    std::vector<cf> v(n);
+    for (int i = 0; i < n; ++i) {
+        const double ang = angle(i);
+        v[i] = cf((float)cos(ang), (float)sin(ang));
+    }
+    return v;
 }
 
-// Taps per polyphase component above which the overlap-save engine takes over from the tiled vector kernel (single-stream
-// calls).  Measured on MI355X (tools/bench_ols_crossover.py, profiles/r02_ols_crossover.log): the tiled kernel runs at
-// about 15000 / (taps per phase) Gsamples/s with real taps and half that with complex taps, the engine (round 2:
-// persistent, resident twiddles) at 230-290 whatever the filter.
-static int ols_crossover(bool complex_taps, int decim)
-{
-#ifdef GRHIP_DIAG       // diagnostic builds only: GRHIP_OLS_MIN = threshold for both kinds (0 = engine wherever it can, 9999 = never)
-    if (const char *e = getenv("GRHIP_OLS_MIN")) return atoi(e);
-#endif
-    // measured crossovers (taps per phase): real taps 48 / 60 / 28 at decimation 1 / 2 / 4, complex taps 40 / 40 / 26
-    // (the engine's folded inverse makes it fastest at 4, the full-size inverse of decimation 1 comes next)
-    if (complex_taps) return decim >= 4 ? 26 : 40;
-    return decim >= 4 ? 28 : decim == 2 ? 60 : 48;
-}
+static int upload(DevBuf &b, const std::vector<cf> &v) { return upload(b, v.data(), v.size() * sizeof(cf)); }
 
 int XlatingCore::build(int device)
 {
@@ -101,10 +231,12 @@ int XlatingCore::build(int device)
     ntaps = (int)proto.size();
     ctaps.resize(ntaps);
     float fwT0 = 2 * M_PI * center_freq / sampling_freq;
+    bool real_proto = true;
     for (unsigned i = 0; i < (unsigned)ntaps; i++) {
         cf e = std::exp(cf(0, i * fwT0));
         // complex product in libgcc order (ac - bd, ad + bc)
         float a = proto[i].real(), b = proto[i].imag(), c = e.real(), d = e.imag();
+        if (b != 0.0f) real_proto = false;
         if (real_tap_type) { ctaps[i] = cf(a * c, a * d); continue; }       // float * complex
         float ac = a * c, bd = b * d, ad = a * d, bc = b * c;
         ctaps[i] = cf(ac - bd, ad + bc);
@@ -114,149 +246,52 @@ int XlatingCore::build(int device)
     float mag = hypotf(inc.real(), inc.imag());
     incr = cf(inc.real() / mag, inc.imag() / mag);
     omega = (double)fwT0;
-
-    // device copies
-    // generic kernel wants d_taps order; after reverse(reverse()) that is ctaps itself
-    int rc = upload(d_taps_generic, ctaps.data(), sizeof(cf) * ntaps);
-    if (rc) return rc;
-    if (in_kind != 0) {
-        // real items: gr_fir_fcc / gr_fir_scc over the composite taps (c[k] multiplies x[nD + k]: ctaps itself)
-        use_tiled = premix = use_mfma = use_ols = prefer_ols = use_hidec = hidec_premix = false;
-        use_realin = realin_supported(decim, ntaps);
-        if (use_realin) {
-            std::vector<float> hp;
-            ri_Tq = realin_pack_taps((const float *)ctaps.data(), ntaps, decim, hp);
-            rc = upload(d_ri_hp, hp.data(), hp.size() * sizeof(float));
-            if (rc) return rc;
-        }
-        reset();
-        (void)device;
-        return GRHIP_OK;
-    }
-
-    bool real_proto = true;
-    for (auto &t : proto) if (t.imag() != 0.0f) real_proto = false;
-    std::vector<float> hp;
-    use_tiled = false; premix = false;
-    if (ntaps > 0) {
-        if (real_proto) {
-            std::vector<float> pr(ntaps);
-            for (int i = 0; i < ntaps; ++i) pr[i] = proto[i].real();
-            Tq = pack_phase_major(pr.data(), ntaps, 1, decim, hp);
-            if (tiled_supported(decim, Tq)) { use_tiled = true; premix = true; }
-        }
-        if (!use_tiled) {
-            Tq = pack_phase_major((const float *)ctaps.data(), ntaps, 2, decim, hp);
-            if (tiled_supported(decim, Tq)) use_tiled = true;
-        }
-    }
-    if (use_tiled) {
-        rc = upload(d_hp, hp.data(), hp.size() * sizeof(float));
-        if (rc) return rc;
-        if (premix) {
-            // phasor tables of the pre-mix form, computed in double (see fir_tiled.hip)
-            const int NT = tiled_NT();
-            std::vector<cf> W(tiled_wtab_len()), V(NT + 1), S(tiled_stab_len());
-            for (int v = -1; v < (int)W.size() - 1; ++v) {
-                double ang = omega * (double)(v - decim);
-                W[v + 1] = cf((float)cos(ang), (float)sin(ang));
-            }
-            for (int i = 0; i < (int)S.size(); ++i) {
-                double ang = omega * (double)tiled_load_span() * (double)i;
-                S[i] = cf((float)cos(ang), (float)sin(ang));
-            }
-            for (int j = 0; j < NT; ++j) {
-                double ang = -omega * (double)j * (double)decim;
-                V[j] = cf((float)cos(ang), (float)sin(ang));
-            }
-            V[NT] = cf((float)cos(omega * decim), (float)sin(omega * decim));
-            rc = upload(d_stab, S.data(), S.size() * sizeof(cf));
-            if (rc) return rc;
-            rc = upload(d_wtab, W.data(), W.size() * sizeof(cf));
-            if (rc) return rc;
-            rc = upload(d_vtab, V.data(), V.size() * sizeof(cf));
-            if (rc) return rc;
-        }
-    }
-    use_mfma = false;
-    if (real_proto && mfma_supported(decim, ntaps) && ntaps / decim >= 24) {
-        // pre-mix form on the matrix cores: x'[u] = x[u] e^{jw(u - off)}, real prototype taps
-        std::vector<float> pr(ntaps);
-        for (int i = 0; i < ntaps; ++i) pr[i] = proto[i].real();
-        rc = build_mfma_taps(pr.data(), ntaps, decim, d_mf_A, &mf_kexp, fwT0);
-        if (rc) return rc;
-        const int KS = mf::ksteps_inst(decim, ntaps);
-        for (int off = 0; off < 2; ++off) {
-            std::vector<cf> W(2 * mf::THREADS);         // 256 staging lanes (fir_mfma_kernel) or 512 (fir_mfma_rs_kernel)
-            for (int t = 0; t < 2 * mf::THREADS; ++t) {
-                double ang = omega * (double)(2 * t - off);
-                W[t] = cf((float)cos(ang), (float)sin(ang));
-            }
-            rc = upload(d_mf_wlane[off], W.data(), W.size() * sizeof(cf));
-            if (rc) return rc;
-        }
-        std::vector<cf> S(mf::rounds(decim, KS)), V(mf::NTC + 2);
-        for (int i = 0; i < (int)S.size(); ++i) {
-            double ang = omega * (double)mf::ROUND * (double)i;
-            S[i] = cf((float)cos(ang), (float)sin(ang));
-        }
-        for (int j = 0; j < (int)V.size(); ++j) {
-            double ang = -omega * (double)j * (double)decim;
-            V[j] = cf((float)cos(ang), (float)sin(ang));
-        }
-        mf_wstep[0] = (float)cos(omega); mf_wstep[1] = (float)sin(omega);
-        rc = upload(d_mf_stab, S.data(), S.size() * sizeof(cf));
-        if (!rc) rc = upload(d_mf_vtab, V.data(), V.size() * sizeof(cf));
-        if (rc) return rc;
-        use_mfma = true;
-    }
-    use_ols = false;
-    if (ntaps >= 48 && ntaps <= OLS_MAX_TAPS && (OLS_N - (ntaps - 1)) / decim >= 1) {
-        // convolution taps h[k] = ctaps[ntaps-1-k] (the composite FIR is set with gr_reverse(ctaps), .cc.t:80)
-        std::vector<float> h((size_t)ntaps * 2);
-        for (int k = 0; k < ntaps; ++k) {
-            h[2 * k] = ctaps[ntaps - 1 - k].real();
-            h[2 * k + 1] = ctaps[ntaps - 1 - k].imag();
-        }
-        rc = ols_build(h.data(), ntaps, decim, d_ols_tw, d_ols_H, &ols_L, &ols_fold);
-        if (rc) return rc;
-        use_ols = true;
-    }
-    // single-stream calls only, batched launches stay tiled.  Not gr_fir_filter's crossover: behind the engine this block
-    // still needs the rotator-table multiply and (fused form) the stand-alone demodulator as passes of their own, which
-    // the tiled kernel does in its epilogue -- the round-1 crossover stays for real prototypes (the matrix-core engine
-    // comes first there anyway); complex prototypes cost the tiled kernel twice the FMAs: measured 190 (tiled) against
-    // 226 Gsamples/s (engine + rotator pass) at 64 taps per phase, D = 4
-    prefer_ols = use_ols && (!use_tiled || ntaps / decim > (real_proto ? 120 : 56));
-    // real prototype: pre-mix form, half the FMAs for one more multiply per staged sample -- pays from about 16
-    // taps per polyphase component (tools/bench_decim.py)
-    hidec_premix = real_proto && ntaps > 0 && ntaps / decim >= 16;
-    use_hidec = !use_tiled && hidec_wanted(decim, ntaps, !hidec_premix, use_ols);
-    if (for_demod && real_proto && ntaps > 0) {
-        // a demodulating handle: whatever engine has the fused demodulator (see xlating_core.h)
-        if (use_tiled && premix) prefer_ols = false;
-        // (up to 1024 taps: beyond, the f32 direct sum of the pre-mixed products leaves the 1e-5 tolerance -- 1.04e-5 measured
-        // at 1200 taps -- and the engine, with its host-side rotator phases, stays)
-        else if (!use_tiled && ntaps <= 1024 && hidec_supported(decim, ntaps)) { hidec_premix = true; use_hidec = true; }
-    }
-    if (use_hidec) {
-        std::vector<float> hp2;
-        if (hidec_premix) {
-            std::vector<float> pr(ntaps), et, vt;
-            for (int i = 0; i < ntaps; ++i) pr[i] = proto[i].real();
-            hidec_pad_taps(pr.data(), ntaps, 1, decim, hp2);
-            hidec_premix_tables(omega, decim, et, vt);
-            rc = upload(d_hidec_etab, et.data(), et.size() * sizeof(float));
-            if (!rc) rc = upload(d_hidec_vtab, vt.data(), vt.size() * sizeof(float));
-            if (rc) return rc;
-        } else {
-            hidec_pad_taps((const float *)ctaps.data(), ntaps, 2, decim, hp2);
-        }
-        rc = upload(d_hidec_taps, hp2.data(), hp2.size() * sizeof(float));
-        if (rc) return rc;
-    }
-    reset();
     (void)device;
+
+    // generic kernel wants d_taps order; after reverse(reverse()) that is ctaps itself
+    int rc = upload(d_taps_generic, ctaps);
+    if (rc) return rc;
+    eng.ntaps = ntaps; eng.decim = decim;
+    eng.plan = fir_plan_xlating(in_kind, real_proto, for_demod, decim, ntaps, FirEngines::caps(ntaps, decim, decim),
+                                FirEngines::tuning());
+    const FirPlan &p = eng.plan;
+    // the engines' taps, c[k] multiplying x[nD + k]: the composite taps, or the real prototype under the pre-mix forms
+    const float *cc = (const float *)ctaps.data();
+    std::vector<float> pr(ntaps);
+    for (int i = 0; i < ntaps; ++i) pr[i] = proto[i].real();
+    if (p.use_realin) rc = eng.build_realin(cc);
+    if (!rc && p.use_tiled) rc = p.premix ? eng.build_tiled(pr.data(), 1) : eng.build_tiled(cc, 2);
+    if (!rc && p.premix) {
+        // phasor tables of the pre-mix form, computed in double (see fir_tiled.hip): W[v+1] = e^{jw(v-D)}, S[i] = e^{jw 512 i},
+        // V[j] = e^{-jw j D} with V[NT] = e^{+jwD}
+        const int NT = tiled_NT();
+        std::vector<cf> V = phasors(NT + 1, [&](int j) { return -omega * (double)j * (double)decim; });
+        V[NT] = cf((float)cos(omega * decim), (float)sin(omega * decim));
+        rc = upload(d_stab, phasors(tiled_stab_len(), [&](int i) { return omega * (double)tiled_load_span() * (double)i; }));
+        if (!rc) rc = upload(d_wtab, phasors(tiled_wtab_len(), [&](int i) { return omega * (double)(i - 1 - decim); }));
+        if (!rc) rc = upload(d_vtab, V);
+    }
+    if (!rc && p.use_mfma) {
+        // pre-mix form on the matrix cores: x'[u] = x[u] e^{jw(u - off)}, real prototype taps
+        rc = eng.build_mfma(pr.data(), fwT0);
+        // 256 staging lanes (fir_mfma_kernel) or 512 (fir_mfma_rs_kernel): e^{jw(2t - off)}
+        for (int off = 0; off < 2 && !rc; ++off)
+            rc = upload(d_mf_wlane[off], phasors(2 * mf::THREADS, [&](int t) { return omega * (double)(2 * t - off); }));
+        mf_wstep[0] = (float)cos(omega); mf_wstep[1] = (float)sin(omega);
+        if (!rc) rc = upload(d_mf_stab, phasors(mf::rounds(decim, mf::ksteps_inst(decim, ntaps)),
+                                                [&](int i) { return omega * (double)mf::ROUND * (double)i; }));
+        if (!rc) rc = upload(d_mf_vtab, phasors(mf::NTC + 2, [&](int j) { return -omega * (double)j * (double)decim; }));
+    }
+    if (!rc && p.use_ols) rc = eng.build_ols(cc, 2);
+    if (!rc && p.use_hidec) {
+        rc = p.hidec_premix ? eng.build_hidec(pr.data(), 1) : eng.build_hidec(cc, 2);
+        std::vector<float> et, vt;
+        if (p.hidec_premix) hidec_premix_tables(omega, decim, et, vt);
+        if (!rc && p.hidec_premix) rc = upload(d_hidec_etab, et.data(), et.size() * sizeof(float));
+        if (!rc && p.hidec_premix) rc = upload(d_hidec_vtab, vt.data(), vt.size() * sizeof(float));
+    }
+    if (rc) return rc;
+    reset();
     return GRHIP_OK;
 }
 
@@ -341,6 +376,29 @@ int XlatingCore::phase_before_pos(std::complex<float> *g)
     return GRHIP_OK;
 }
 
+template <class Fir>
+int XlatingCore::demod_second(const FirIo &io, float gain, const float2 *y_prev, float2 *y_last, const float *atan_tab,
+                              hipStream_t st, Fir &&fir)
+{
+    const long long ys = io.n_out + 1;
+    int rc = scratch_y.reserve((size_t)ys * io.n_streams * sizeof(float2));
+    if (rc) return rc;
+    float2 *sy = scratch_y.as<float2>();
+    if (y_prev) GRHIP_HIP(hipMemcpy2DAsync(sy, ys * sizeof(float2), y_prev, sizeof(float2), sizeof(float2), io.n_streams,
+                                           hipMemcpyDeviceToDevice, st));
+    else GRHIP_HIP(hipMemset2DAsync(sy, ys * sizeof(float2), 0, sizeof(float2), io.n_streams, st));
+    FirIo o = io;
+    o.out = sy + 1; o.out_stride = ys;
+    if ((rc = fir(o))) return rc;
+    for (int s = 0; s < io.n_streams; ++s) {
+        rc = launch_quad_demod(sy + s * ys, (float *)io.out + s * io.out_stride, io.n_out, gain, atan_tab, st);
+        if (rc) return rc;
+    }
+    if (y_last) GRHIP_HIP(hipMemcpy2DAsync(y_last, sizeof(float2), sy + io.n_out, ys * sizeof(float2), sizeof(float2),
+                                           io.n_streams, hipMemcpyDeviceToDevice, st));
+    return GRHIP_OK;
+}
+
 // run the FIR + rotator (+ demod) for n_out outputs on device pointers.
 // d_in item 0 = input[0] of output 0; n_in readable items.
 int XlatingCore::run(int mode, const float2 *d_in, long long n_in, long long n_out, float2 *d_y,
@@ -349,154 +407,72 @@ int XlatingCore::run(int mode, const float2 *d_in, long long n_in, long long n_o
                      long long n_lo, long long out_stride)
 {
     if (n_out <= 0) return GRHIP_OK;
+    const bool demod = d_demod != nullptr, sh = in_kind == 2;
+    FirCall c;
+    c.mode = mode; c.demod = demod; c.batched = !(n_streams == 1 && n_lo == 0);
+    c.in_aligned = !(((uintptr_t)d_in) & (sh ? 1 : 3)); c.out_aligned = !(((uintptr_t)d_y) & 7);
+    c.odd_stride_multi = n_streams != 1 && (x_stride & 1);
+    FirRoute r = fir_route(eng.plan, c);
     const float2 *gtab = nullptr;
-    if (in_kind != 0) {
-        // real items: inner FIR with the rotator epilogue, one stream with its history in front
-        if (d_demod || n_streams != 1 || n_lo != 0) return fail(GRHIP_EINVAL, "real-input xlating: one stream, no demodulator");
-        int rc = ensure_rot(n_out, &gtab, st);
-        if (rc) return rc;
-        const bool sh = in_kind == 2;
-        if (mode_fast(mode) && use_realin && !(((uintptr_t)d_y) & 7) && !(((uintptr_t)d_in) & (sh ? 1 : 3)))
-            rc = launch_fir_realin(sh, decim, d_ri_hp.as<float>(), ri_Tq, d_in, n_in, d_y, n_out, gtab, st);
-        else
-            rc = launch_fir_generic(sh ? FIR_SCC : FIR_FCC, d_taps_generic.as<float>(), ntaps, d_in, d_y, n_out, decim, gtab, st);
-        if (rc) return rc;
-        pos += n_out;
-        return GRHIP_OK;
-    }
-    const bool demod = d_demod != nullptr;
-    const bool batched = !(n_streams == 1 && n_lo == 0);
-    const bool mfma_now = mode_matrix(mode) && use_mfma && (n_streams == 1 || !(x_stride & 1));
-    // fused demodulator of the high-decimation direct kernel (pre-mix form): no rotator phases either
-    const bool hidec_direct = !mfma_now && demod && mode_fast(mode) && use_hidec && hidec_premix;
-    const bool direct = mfma_now ? demod
-                                 : (hidec_direct || (demod && mode_fast(mode) && use_tiled && premix && (batched || !prefer_ols)));
     int rc = GRHIP_OK;
-    if (!direct) {          // the direct demodulator epilogue needs no rotator phases
-        rc = ensure_rot(n_out, &gtab, st);
-        if (rc) return rc;
+    if (r.need_rot && (rc = ensure_rot(n_out, &gtab, st))) return rc;
+    if (r.engine == ENG_GENERIC_DEMOD) {
+        rc = launch_fir_generic_demod(d_taps_generic.as<float>(), ntaps, d_in, d_demod, n_out, decim, gtab, gain, atan_tab,
+                                      y_prev, y_last, st, n_streams, x_stride, out_stride, n_lo);
+        if (rc == GRHIP_OK) pos += n_out;
+        if (rc != 1) return rc;
+        c.generic_fused = false;            // no such kernel for this shape: the two kernels, one stream
+        r = fir_route(eng.plan, c);
     }
-    if (mfma_now) {
-        FirMfmaArgs a;
-        memset(&a, 0, sizeof(a));
-        a.x = d_in; a.x_stride = x_stride; a.n_in = n_in; a.n_lo = n_lo; a.n_out = n_out; a.n_streams = n_streams;
-        a.off = (int)((((uintptr_t)d_in) >> 3) & 1);
-        a.A = d_mf_A[a.off].p; a.kexp = mf_kexp;
-        a.wlane = d_mf_wlane[a.off].as<float2>(); a.wstep = make_float2(mf_wstep[0], mf_wstep[1]);
-        a.stab = d_mf_stab.as<float>(); a.vtab = d_mf_vtab.as<float2>(); a.gtab = gtab;
-        a.y_out = d_y; a.d_out = d_demod; a.y_stride = out_stride; a.d_stride = out_stride;
-        a.gain = gain; a.y_prev = y_prev; a.y_last = y_last; a.atan_tab = atan_tab;
-        a.ctaps = d_taps_generic.as<float2>(); a.T = ntaps;
-        const uintptr_t o = demod ? (uintptr_t)d_demod : (uintptr_t)d_y;
-        a.vec_store = demod ? ((o & 7) == 0 && !(out_stride & 1)) : ((o & 15) == 0 && !(out_stride & 1));
-        a.sched = mf_sched.get();
-        a.max_wg_per_cu = mf_wg_cap;
-        a.max_cus = mf_cu_cap;
-        a.omega = omega;
-        a.tapq = mode == GRHIP_MODE_FAST_REFTAPS;
-        rc = launch_fir_mfma(decim, ntaps, true, demod ? EPI_DEMOD : EPI_ROTATE, a, st);
-        if (rc) return rc;
-        pos += n_out;
-        return GRHIP_OK;
-    }
-    if (hidec_direct) {
-        rc = launch_fir_hidec_demod(d_hidec_taps.as<float>(), ntaps, decim, d_in, batched ? n_in : (n_out - 1) * decim + ntaps,
-                                    d_demod, n_out, gain, y_prev, y_last, atan_tab, d_hidec_etab.as<float2>(),
-                                    d_hidec_vtab.as<float2>(), st, n_streams, x_stride, out_stride, n_lo, mf_wg_cap, mf_cu_cap);
-        if (rc) return rc;
-        pos += n_out;
-        return GRHIP_OK;
-    }
-    const bool ols_now = mode_fast(mode) && (prefer_ols || (use_hidec && !use_tiled)) && !batched;
-    if (mode_fast(mode) && use_tiled && !ols_now) {
-        FirTiledArgs a;
-        memset(&a, 0, sizeof(a));
-        a.x = d_in; a.x_stride = x_stride; a.n_in = n_in; a.n_lo = n_lo;
-        a.hp = d_hp.as<float>(); a.Tq = Tq; a.n_out = n_out;
-        a.wtab = d_wtab.as<float2>(); a.stab = d_stab.as<float2>(); a.vtab = d_vtab.as<float2>(); a.gtab = gtab;
-        a.gain = gain; a.atan_tab = atan_tab;
-        a.sched = sched.get();
-        if (direct || !demod) {
-            a.y_out = d_y; a.d_out = d_demod;
-            a.y_stride = out_stride; a.d_stride = out_stride;
-            a.y_prev = y_prev; a.y_last = y_last;
-            uintptr_t o = demod ? (uintptr_t)d_demod : (uintptr_t)d_y;
-            a.vec_store = (o & 15) == 0 && ((out_stride * (demod ? 4 : 8)) & 15) == 0;
-            rc = launch_fir_tiled(decim, !premix, premix, direct ? EPI_DEMOD : EPI_ROTATE, a, n_streams, st);
-            if (rc) return rc;
-        } else {
-            // complex prototype taps: the tiled kernel writes y (with one slot in front of every
-            // stream for the demodulator's previous sample), the demodulator is a second kernel
-            const long long ys = n_out + 1;
-            rc = scratch_y.reserve((size_t)ys * n_streams * sizeof(float2));
-            if (rc) return rc;
-            float2 *sy = scratch_y.as<float2>();
-            if (y_prev) GRHIP_HIP(hipMemcpy2DAsync(sy, ys * sizeof(float2), y_prev, sizeof(float2), sizeof(float2),
-                                                   n_streams, hipMemcpyDeviceToDevice, st));
-            else GRHIP_HIP(hipMemset2DAsync(sy, ys * sizeof(float2), 0, sizeof(float2), n_streams, st));
-            a.y_out = sy + 1; a.y_stride = ys;
-            a.vec_store = 0;
-            rc = launch_fir_tiled(decim, true, false, EPI_ROTATE, a, n_streams, st);
-            if (rc) return rc;
-            for (int s = 0; s < n_streams; ++s) {
-                rc = launch_quad_demod(sy + s * ys, d_demod + s * out_stride, n_out, gain, atan_tab, st);
-                if (rc) return rc;
-            }
-            if (y_last) GRHIP_HIP(hipMemcpy2DAsync(y_last, sizeof(float2), sy + n_out, ys * sizeof(float2), sizeof(float2),
-                                                   n_streams, hipMemcpyDeviceToDevice, st));
+    if (r.engine == ENG_EINVAL)
+        return fail(GRHIP_EINVAL, eng.plan.real_in ? "real-input xlating: one stream, no demodulator"
+                                                   : "generic-order path: this shape runs one stream with explicit history");
+    const FirPlan &p = eng.plan;
+    const int epi = r.epilogue == EPILOGUE_DEMOD_FUSED ? EPI_DEMOD : EPI_ROTATE;
+    // the route's FIR: o.out receives y times the rotator's phases, or the fused demodulator's output
+    auto fir = [&](const FirIo &o) -> int {
+        switch (r.engine) {
+        case ENG_REALIN: return eng.launch_realin(sh, o, gtab, st);
+        case ENG_MFMA: {
+            FirMfmaArgs a = zeroed<FirMfmaArgs>();
+            a.wlane = d_mf_wlane[o.parity()].as<float2>(); a.wstep = make_float2(mf_wstep[0], mf_wstep[1]);
+            a.stab = d_mf_stab.as<float>(); a.vtab = d_mf_vtab.as<float2>(); a.gtab = gtab;
+            a.gain = gain; a.y_prev = y_prev; a.y_last = y_last; a.atan_tab = atan_tab;
+            a.ctaps = d_taps_generic.as<float2>(); a.T = ntaps;
+            a.max_wg_per_cu = mf_wg_cap; a.max_cus = mf_cu_cap;
+            a.omega = omega; a.tapq = mode == GRHIP_MODE_FAST_REFTAPS;
+            return eng.launch_mfma(a, o, true, epi, st);
         }
-    } else if (ols_now) {
-        // overlap-save FIR (history in front of d_in = the engine's previous samples), rotator table
-        // multiply, stand-alone demodulator
-        float2 *y = d_y;
-        if (demod) {
-            rc = scratch_y.reserve((size_t)(n_out + 1) * sizeof(float2));
-            if (rc) return rc;
-            y = scratch_y.as<float2>() + 1;
-            GRHIP_HIP(hipMemcpyAsync(scratch_y.p, y_prev, sizeof(float2), hipMemcpyDeviceToDevice, st));
+        case ENG_TILED: {
+            FirTiledArgs a = zeroed<FirTiledArgs>();
+            a.wtab = d_wtab.as<float2>(); a.stab = d_stab.as<float2>(); a.vtab = d_vtab.as<float2>(); a.gtab = gtab;
+            a.gain = gain; a.atan_tab = atan_tab;
+            if (r.epilogue != EPILOGUE_DEMOD_SECOND) { a.y_prev = y_prev; a.y_last = y_last; }
+            // (demodulator as a second kernel: complex prototype taps, the tiled kernel writes y)
+            return eng.launch_tiled(a, o, !p.premix, p.premix, epi, st);
         }
-        if (use_hidec) {
-            rc = launch_fir_hidec(!hidec_premix, d_hidec_taps.as<float>(), ntaps, decim, d_in, (n_out - 1) * decim + ntaps, y,
-                                  n_out, gtab, st,           // rotator multiply inside
-                                  hidec_premix ? d_hidec_etab.as<float2>() : nullptr,
-                                  hidec_premix ? d_hidec_vtab.as<float2>() : nullptr);
-        } else {
-            rc = launch_fftfilt4096(d_in + (ntaps - 1), (n_out - 1) * decim + 1, d_in, ntaps, d_ols_tw.as<float2>(),
-                                    d_ols_H.as<float2>(), y, n_out, decim, ols_L, ols_fold, st);
-            if (!rc) rc = launch_rotate(y, gtab, n_out, st);
+        case ENG_HIDEC:
+            if (epi == EPI_DEMOD)
+                return launch_fir_hidec_demod(eng.d_hidec_taps.as<float>(), ntaps, decim, d_in,
+                                              c.batched ? n_in : (n_out - 1) * decim + ntaps, d_demod, n_out, gain, y_prev, y_last,
+                                              atan_tab, d_hidec_etab.as<float2>(), d_hidec_vtab.as<float2>(), st, n_streams,
+                                              x_stride, out_stride, n_lo, mf_wg_cap, mf_cu_cap);
+            return eng.launch_hidec(!p.hidec_premix, o, gtab,            // rotator multiply inside
+                                    p.hidec_premix ? d_hidec_etab.as<float2>() : nullptr,
+                                    p.hidec_premix ? d_hidec_vtab.as<float2>() : nullptr, st);
+        case ENG_OLS: {
+            // overlap-save FIR, then the rotator table multiply
+            int rc = eng.launch_ols(false, o, st);
+            return rc ? rc : launch_rotate((float2 *)o.out, gtab, n_out, st);
         }
-        if (rc) return rc;
-        if (demod) {
-            rc = launch_quad_demod(scratch_y.as<float2>(), d_demod, n_out, gain, atan_tab, st);
-            if (rc) return rc;
-            GRHIP_HIP(hipMemcpyAsync(y_last, y + (n_out - 1), sizeof(float2), hipMemcpyDeviceToDevice, st));
+        default:    // generic order (bit-exact) FIR + rotate
+            return launch_fir_generic(in_kind == 0 ? FIR_CCC : sh ? FIR_SCC : FIR_FCC, d_taps_generic.as<float>(), ntaps, d_in,
+                                      o.out, n_out, decim, gtab, st);
         }
-    } else {
-        // generic order (bit-exact) FIR + rotate; the demodulator in the same kernel where there is one (that kernel also
-        // takes several streams and synthesises a fresh capture's history), else as a second kernel over y
-        if (demod) {
-            rc = launch_fir_generic_demod(d_taps_generic.as<float>(), ntaps, d_in, d_demod, n_out, decim, gtab, gain, atan_tab,
-                                          y_prev, y_last, st, n_streams, x_stride, out_stride, n_lo);
-            if (rc == GRHIP_OK) { pos += n_out; return GRHIP_OK; }
-            if (rc != 1) return rc;
-        }
-        if (n_streams != 1 || n_lo != 0)
-            return fail(GRHIP_EINVAL, "generic-order path: this shape runs one stream with explicit history");
-        float2 *y = d_y;
-        if (demod) {
-            rc = scratch_y.reserve((size_t)(n_out + 1) * sizeof(float2));
-            if (rc) return rc;
-            y = scratch_y.as<float2>() + 1;
-            GRHIP_HIP(hipMemcpyAsync(scratch_y.p, y_prev, sizeof(float2), hipMemcpyDeviceToDevice, st));
-        }
-        rc = launch_fir_generic(FIR_CCC, d_taps_generic.as<float>(), ntaps, d_in, y, n_out, decim, gtab, st);
-        if (rc) return rc;
-        if (demod) {
-            rc = launch_quad_demod(scratch_y.as<float2>(), d_demod, n_out, gain, atan_tab, st);
-            if (rc) return rc;
-            GRHIP_HIP(hipMemcpyAsync(y_last, y + (n_out - 1), sizeof(float2), hipMemcpyDeviceToDevice, st));
-        }
-    }
+    };
+    const FirIo io{d_in, n_in, n_out, demod ? (void *)d_demod : (void *)d_y, n_streams, x_stride, n_lo, out_stride};
+    rc = r.epilogue == EPILOGUE_DEMOD_SECOND ? demod_second(io, gain, y_prev, y_last, atan_tab, st, fir) : fir(io);
+    if (rc) return rc;
     pos += n_out;
     return GRHIP_OK;
 }
@@ -506,6 +482,24 @@ int XlatingCore::run(int mode, const float2 *d_in, long long n_in, long long n_o
 // ============================================================================
 // gr_fir_filter_XXX
 // ============================================================================
+// the body of every set_mode entry
+template <class H>
+static int set_mode_of(H *h, int mode)
+{
+    if (!h || !mode_valid(mode)) return fail(GRHIP_EINVAL, "bad mode");
+    h->mode = mode;
+    return GRHIP_OK;
+}
+
+// the taps in d_taps order on the device (rev[k] = taps[ntaps-1-k]: correlation order, rev[k] multiplies x[nD + k])
+static int upload_reversed(DevBuf &d_taps_rev, const std::vector<float> &taps, int ntaps, int tw, std::vector<float> &rev)
+{
+    rev.resize(taps.size());
+    for (int k = 0; k < ntaps; ++k)
+        for (int w = 0; w < tw; ++w) rev[(size_t)k * tw + w] = taps[(size_t)(ntaps - 1 - k) * tw + w];
+    return upload(d_taps_rev, rev.data(), rev.size() * sizeof(float));
+}
+
 struct grhip_fir_filter : HandleBase {
     FirKind kind;
     int decim = 1;
@@ -514,27 +508,8 @@ struct grhip_fir_filter : HandleBase {
     std::vector<float> new_taps;    // latched by set_taps
     bool updated = false;
     int ntaps = 0;
-    DevBuf d_taps_rev, d_hp;
-    SchedBuf sched;
-    int Tq = 0;
-    bool use_tiled = false;
-    // FAST mode for the shapes the tiled kernel does not take (decimation other than 1/2/4, more
-    // than 1024 taps): the overlap-save engine of gr_fft_filter_ccc (fft_kernels.hip), any decimation
-    bool use_ols = false, prefer_ols = false;
-    int ols_L = 0, ols_fold = 0;
-    DevBuf d_ols_tw, d_ols_H;
-    // ... and the high-decimation direct kernel where a polyphase component has few taps (fir_kernels.hip)
-    bool use_hidec = false;
-    DevBuf d_hidec_taps;
-    // ... and the matrix-core engine for long real-tap filters on complex data (fir_mfma.hip)
-    bool use_mfma = false;
-    int mf_kexp = 0;
-    DevBuf d_mf_A[2];
-    SchedBuf mf_sched;
-
-    // real input (fir_realin.hip): fcc / scc FAST; fsf runs the fff engines (ekind) and converts
-    FirKind ekind;                  // the kind whose engines run: kind, or FIR_FFF for FIR_FSF
-    bool use_realin = false;
+    DevBuf d_taps_rev;
+    FirEngines eng;                 // FAST mode (fir_plan.h)
     DevBuf d_scratch;               // fsf: the float outputs before the conversion
 
     int tw() const { return fir_kind_ctaps(kind) ? 2 : 1; }
@@ -545,132 +520,33 @@ struct grhip_fir_filter : HandleBase {
     {
         taps = t;
         ntaps = (int)(taps.size() / tw());
-        std::vector<float> rev(taps.size());
-        for (int k = 0; k < ntaps; ++k)
-            for (int w = 0; w < tw(); ++w) rev[(size_t)k * tw() + w] = taps[(size_t)(ntaps - 1 - k) * tw() + w];
-        int rc = upload(d_taps_rev, rev.data(), rev.size() * sizeof(float));
-        if (rc) return rc;
-        if (kind == FIR_FCC || kind == FIR_SCC) {
-            use_tiled = use_mfma = use_ols = prefer_ols = use_hidec = false;
-            use_realin = realin_supported(decim, ntaps);
-            if (use_realin) {
-                std::vector<float> hp;
-                Tq = realin_pack_taps(rev.data(), ntaps, decim, hp);
-                rc = upload(d_hp, hp.data(), hp.size() * sizeof(float));
-            }
-            return rc;
-        }
-        use_tiled = false;
-        if (ntaps > 0 && (ekind != FIR_FFF || decim <= 2)) {
-            // float data runs the complex kernel on overlapped pairs at twice the decimation
-            const int dk = ekind == FIR_FFF ? 2 * decim : decim;
-            std::vector<float> hp;
-            Tq = pack_phase_major(rev.data(), ntaps, tw(), dk, hp);
-            if (tiled_supported(dk, Tq)) {
-                rc = upload(d_hp, hp.data(), hp.size() * sizeof(float));
-                if (rc) return rc;
-                use_tiled = true;
-            }
-        }
-        use_mfma = false;
-        if (ekind == FIR_CCF && mfma_supported(decim, ntaps) && ntaps / decim >= 24) {
-            rc = build_mfma_taps(rev.data(), ntaps, decim, d_mf_A, &mf_kexp);
-            if (rc) return rc;
-            use_mfma = true;
-        }
-        use_ols = false;
-        if (ntaps >= 48 && ntaps <= OLS_MAX_TAPS && (OLS_N - (ntaps - 1)) / decim >= 1) {
-            std::vector<float> ct((size_t)ntaps * 2);
-            for (int k = 0; k < ntaps; ++k) {
-                ct[2 * k] = ekind == FIR_CCC ? taps[2 * k] : taps[k];
-                ct[2 * k + 1] = ekind == FIR_CCC ? taps[2 * k + 1] : 0.f;
-            }
-            rc = ols_build(ct.data(), ntaps, decim, d_ols_tw, d_ols_H, &ols_L, &ols_fold);
-            if (rc) return rc;
-            use_ols = true;
-        }
-        // (crossover between the tiled kernel and the overlap-save engine: ols_crossover above)
-        use_hidec = !use_tiled && ekind != FIR_FFF && hidec_wanted(decim, ntaps, ekind == FIR_CCC, use_ols);
-        if (use_hidec) {
-            std::vector<float> hp2;
-            hidec_pad_taps(rev.data(), ntaps, tw(), decim, hp2);
-            rc = upload(d_hidec_taps, hp2.data(), hp2.size() * sizeof(float));
-            if (rc) return rc;
-        }
-        // (float data: the tiled kernel's float-pair mode runs at about 50000 / taps Gsamples/s, the real-data engine at
-        // 250-290: the engine where the float-pair mode does not reach, and from 176 taps per phase on)
-        prefer_ols = use_ols && (!use_tiled || ntaps / decim > (ekind == FIR_FFF ? 176 : ols_crossover(ekind == FIR_CCC, decim)));
-        return GRHIP_OK;
+        std::vector<float> rev;
+        int rc = upload_reversed(d_taps_rev, taps, ntaps, tw(), rev);
+        return rc ? rc : eng.build_plain(kind, decim, rev.data(), ntaps);
     }
 
     int run(const void *d_in, void *d_out, long long n, int dec, hipStream_t st)
     {
         if (n <= 0) return GRHIP_OK;
-        if (kind == FIR_FCC || kind == FIR_SCC) {
-            if (mode_fast(mode) && use_realin && dec == decim && !(((uintptr_t)d_out) & 7) &&
-                !(((uintptr_t)d_in) & (kind == FIR_SCC ? 1 : 3)))
-                return launch_fir_realin(kind == FIR_SCC, dec, d_hp.as<float>(), Tq, d_in, (n - 1) * dec + ntaps, (float2 *)d_out,
-                                         n, nullptr, st);
-            return launch_fir_generic(kind, d_taps_rev.as<float>(), ntaps, d_in, d_out, n, dec, nullptr, st);
-        }
-        if (kind == FIR_FSF) {
-            if (!mode_fast(mode)) return launch_fir_generic(kind, d_taps_rev.as<float>(), ntaps, d_in, d_out, n, dec, nullptr, st);
-            int rc = d_scratch.reserve((size_t)n * sizeof(float));
-            if (!rc) rc = run_engines(d_in, d_scratch.p, n, dec, st);
-            if (!rc) rc = launch_f2s(d_scratch.as<float>(), (short *)d_out, n, st);
-            return rc;
-        }
-        return run_engines(d_in, d_out, n, dec, st);
+        if (kind != FIR_FSF) return eng.run_plain(kind, mode, d_taps_rev.as<float>(), d_in, d_out, n, dec, st);
+        // fsf: the generic kernel converts itself; FAST runs the fff engines and converts in a pass of its own
+        if (!mode_fast(mode)) return launch_fir_generic(kind, d_taps_rev.as<float>(), ntaps, d_in, d_out, n, dec, nullptr, st);
+        int rc = d_scratch.reserve((size_t)n * sizeof(float));
+        if (!rc) rc = eng.run_plain(FIR_FFF, mode, d_taps_rev.as<float>(), d_in, d_scratch.p, n, dec, st);
+        if (!rc) rc = launch_f2s(d_scratch.as<float>(), (short *)d_out, n, st);
+        return rc;
     }
 
-    // the engines of fff / ccf / ccc (ekind)
-    int run_engines(const void *d_in, void *d_out, long long n, int dec, hipStream_t st)
+    // host buffers: n outputs at decimation dec from (n - 1) * dec + ntaps items; returns n or the error
+    long long host_run(const void *in, void *out, long long n, int dec)
     {
-        if (mode_matrix(mode) && use_mfma && dec == decim) {
-            FirMfmaArgs a;
-            memset(&a, 0, sizeof(a));
-            a.x = (const float2 *)d_in; a.n_in = (n - 1) * dec + ntaps; a.n_out = n; a.n_streams = 1;
-            a.off = (int)((((uintptr_t)d_in) >> 3) & 1);
-            a.A = d_mf_A[a.off].p; a.kexp = mf_kexp;
-            a.y_out = (float2 *)d_out;
-            a.vec_store = (((uintptr_t)d_out) & 15) == 0;
-            a.sched = mf_sched.get();
-            return launch_fir_mfma(dec, ntaps, false, EPI_NONE, a, st);
-        }
-        if (mode_fast(mode) && use_tiled && !prefer_ols && dec == decim && (ekind != FIR_FFF || n >= 2)) {
-            FirTiledArgs a;
-            memset(&a, 0, sizeof(a));
-            a.x = (const float2 *)d_in; a.n_in = (n - 1) * dec + ntaps;
-            a.hp = d_hp.as<float>(); a.Tq = Tq; a.n_out = n;
-            a.y_out = (float2 *)d_out;
-            a.vec_store = (((uintptr_t)d_out) & 15) == 0;
-            a.sched = sched.get();
-            if (ekind != FIR_FFF) return launch_fir_tiled(dec, ekind == FIR_CCC, false, EPI_NONE, a, 1, st);
-            // gr_fir_fff: output pairs (y[2j], y[2j+1]); an odd last output goes through the generic kernel
-            a.fpair = dec;
-            a.n_out = n / 2;
-            int rc = launch_fir_tiled(2 * dec, false, false, EPI_NONE, a, 1, st);
-            if (rc || !(n & 1)) return rc;
-            return launch_fir_generic(ekind, d_taps_rev.as<float>(), ntaps, (const float *)d_in + (n - 1) * dec,
-                                      (float *)d_out + (n - 1), 1, dec, nullptr, st);
-        }
-        if (mode_fast(mode) && use_hidec && dec == decim)
-            return launch_fir_hidec(ekind == FIR_CCC, d_hidec_taps.as<float>(), ntaps, dec, (const float2 *)d_in,
-                                    (n - 1) * dec + ntaps, (float2 *)d_out, n, nullptr, st);
-        if (mode_fast(mode) && use_ols && (prefer_ols || !use_tiled) && dec == decim) {
-            // y[n] = sum_k taps[k] x[nD + ntaps-1-k]: the ntaps-1 history items in front of d_in are the
-            // engine's "previous call" samples, the rest is the stream
-            if (ekind == FIR_FFF) {
-                const float *xf = (const float *)d_in;
-                return launch_fftfilt4096_real(xf + (ntaps - 1), (n - 1) * dec + 1, xf, ntaps, d_ols_tw.as<float2>(),
-                                               d_ols_H.as<float2>(), (float *)d_out, n, dec, ols_L, ols_fold, st);
-            }
-            const float2 *x = (const float2 *)d_in;
-            // (the scheduler guarantees (n-1)*dec + ntaps items: nothing past the last needed sample is read)
-            return launch_fftfilt4096(x + (ntaps - 1), (n - 1) * dec + 1, x, ntaps, d_ols_tw.as<float2>(),
-                                      d_ols_H.as<float2>(), (float2 *)d_out, n, dec, ols_L, ols_fold, st);
-        }
-        return launch_fir_generic(ekind, d_taps_rev.as<float>(), ntaps, d_in, d_out, n, dec, nullptr, st);
+        size_t n_in = (size_t)((n - 1) * dec + ntaps);
+        if (n_in == 0) n_in = 1;
+        return host_call(in, n_in * in_item(), n_in * in_item() + 16, (size_t)n * out_item(), out, out_item(),
+                         [&](void *d_in, void *d_out, hipStream_t st) {
+                             int rc = run(d_in, d_out, n, dec, st);
+                             return rc ? (long long)rc : n;
+                         });
     }
 };
 
@@ -682,17 +558,11 @@ int grhip_fir_filter_create(grhip_fir_filter **h, const char *kind, int decimati
     if (!h || !kind) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
     FirKind k;
-    if (!strcmp(kind, "ccf")) k = FIR_CCF;
-    else if (!strcmp(kind, "fff")) k = FIR_FFF;
-    else if (!strcmp(kind, "ccc")) k = FIR_CCC;
-    else if (!strcmp(kind, "fcc")) k = FIR_FCC;
-    else if (!strcmp(kind, "scc")) k = FIR_SCC;
-    else if (!strcmp(kind, "fsf")) k = FIR_FSF;
-    else return fail(GRHIP_EINVAL, "unknown FIR kind '%s'", kind);
+    if (!fir_kind_parse(kind, &k)) return fail(GRHIP_EINVAL, "unknown FIR kind '%s'", kind);
     if (decimation < 1) return fail(GRHIP_EINVAL, "decimation must be >= 1");
     if (ntaps && !taps) return fail(GRHIP_EINVAL, "taps is NULL");
     return make_handle(h, [&](grhip_fir_filter *f) {
-        f->kind = k; f->ekind = k == FIR_FSF ? FIR_FFF : k; f->decim = decimation; f->mode = default_mode();
+        f->kind = k; f->decim = decimation; f->mode = default_mode();
         int rc = f->init_device(device);
         if (!rc) rc = f->install(std::vector<float>(taps, taps + ntaps * f->tw()));
         return rc;
@@ -713,12 +583,7 @@ int grhip_fir_filter_set_taps(grhip_fir_filter *h, const float *taps, size_t nta
     return GRHIP_OK;
 }
 
-int grhip_fir_filter_set_mode(grhip_fir_filter *h, int mode)
-{
-    if (!h || !mode_valid(mode)) return fail(GRHIP_EINVAL, "bad mode");
-    h->mode = mode;
-    return GRHIP_OK;
-}
+int grhip_fir_filter_set_mode(grhip_fir_filter *h, int mode) { return set_mode_of(h, mode); }
 
 int grhip_fir_filter_history(const grhip_fir_filter *h)
 {
@@ -765,14 +630,7 @@ int grhip_fir_filter_work(grhip_fir_filter *h, int noutput_items, const void *in
     if (rc < 0) return rc;
     if (rc == 1) return 0;
     if (noutput_items == 0) return 0;
-    long long n = noutput_items;
-    size_t n_in = (size_t)((n - 1) * h->decim + (h->ntaps > 0 ? h->ntaps : 0));
-    if (n_in == 0) n_in = 1;
-    return (int)h->host_call(in, n_in * h->in_item(), n_in * h->in_item() + 16, (size_t)n * h->out_item(), out, h->out_item(),
-                             [&](void *d_in, void *d_out, hipStream_t st) {
-                                 rc = h->run(d_in, d_out, n, h->decim, st);
-                                 return rc ? rc : noutput_items;
-                             });
+    return (int)h->host_run(in, out, noutput_items, h->decim);
 }
 
 int grhip_fir_filterNdec(grhip_fir_filter *h, void *output, const void *input, unsigned long n,
@@ -783,13 +641,7 @@ int grhip_fir_filterNdec(grhip_fir_filter *h, void *output, const void *input, u
     int rc = h->bind();
     if (rc) return rc;
     if (n == 0) return GRHIP_OK;
-    size_t n_in = (size_t)((n - 1) * decimate + h->ntaps);
-    if (n_in == 0) n_in = 1;
-    const long long r = h->host_call(input, n_in * h->in_item(), n_in * h->in_item() + 16, (size_t)n * h->out_item(), output,
-                                     h->out_item(), [&](void *d_in, void *d_out, hipStream_t st) {
-                                         rc = h->run(d_in, d_out, (long long)n, (int)decimate, st);
-                                         return rc ? (long long)rc : (long long)n;
-                                     });
+    const long long r = h->host_run(input, output, (long long)n, (int)decimate);
     return r < 0 ? (int)r : GRHIP_OK;
 }
 
@@ -807,32 +659,33 @@ int grhip_fir_filterNdec(grhip_fir_filter *h, void *output, const void *input, u
 struct grhip_fir_filter_with_buffer : HandleBase {
     FirKind kind = FIR_CCF;
     int mode = GRHIP_MODE_FAST;
-    std::vector<float> taps;            // forward taps (x2 floats for ccc)
+    std::vector<float> rev;             // reversed taps (x2 floats for ccc)
     int ntaps = 0;
-    grhip_fir_filter *inner = nullptr;  // engines of the FIR family at the decimation last used
-    unsigned inner_dec = 0;
+    DevBuf d_taps_rev;
+    FirEngines eng;                     // FAST mode: engines of the FIR family at the decimation last used
+    int eng_dec = 0;                    // (0: none built yet)
     DevBuf d_hist, d_both;
-    ~grhip_fir_filter_with_buffer() { grhip_fir_filter_destroy(inner); }     // before the delay line
     size_t item() const { return kind == FIR_FFF ? 4 : 8; }
     int tw() const { return kind == FIR_CCC ? 2 : 1; }
-    const char *kind_name() const { return kind == FIR_FFF ? "fff" : kind == FIR_CCF ? "ccf" : "ccc"; }
-    int ensure_inner(unsigned dec)
+    // new taps, delay line zeroed (memset(d_buffer, 0), .cc.t:55-57); nothing of the handle is in flight
+    int install(const float *taps, size_t n)
     {
-        if (inner && inner_dec == dec) return GRHIP_OK;
-        if (inner) grhip_fir_filter_destroy(inner);
-        inner = nullptr;
-        int rc = grhip_fir_filter_create(&inner, kind_name(), (int)dec, taps.data(), (size_t)ntaps, device);
-        if (rc) return rc;
-        inner_dec = dec;
-        return GRHIP_OK;
-    }
-    int reset_line()
-    {
+        ntaps = (int)n;
+        eng_dec = 0;
+        int rc = upload_reversed(d_taps_rev, std::vector<float>(taps, taps + n * tw()), ntaps, tw(), rev);
         const size_t bytes = (size_t)(ntaps > 1 ? ntaps - 1 : 1) * item();
-        int rc = d_hist.reserve(bytes);
-        if (rc) return rc;
-        if ((rc = zero_device(d_hist.p, bytes))) return rc;             // memset(d_buffer, 0), .cc.t:55-57
-        return GRHIP_OK;
+        if (!rc) rc = d_hist.reserve(bytes);
+        return rc ? rc : zero_device(d_hist.p, bytes);
+    }
+    // `st`: the stream of the coming call.  A rebuild rewrites the operands an earlier launch may still be reading
+    int ensure_engines(int dec, hipStream_t st)
+    {
+        if (eng_dec == dec) return GRHIP_OK;
+        int rc = eng_dec ? drain(st) : GRHIP_OK;
+        eng_dec = 0;
+        if (!rc) rc = eng.build_plain(kind, dec, rev.data(), ntaps);
+        if (!rc) eng_dec = dec;
+        return rc;
     }
 };
 
@@ -844,19 +697,14 @@ int grhip_fir_filter_with_buffer_create(grhip_fir_filter_with_buffer **h, const 
     if (!h || !kind) return fail(GRHIP_EINVAL, "null argument");
     *h = nullptr;
     FirKind k;
-    if (!strcmp(kind, "ccf")) k = FIR_CCF;
-    else if (!strcmp(kind, "fff")) k = FIR_FFF;
-    else if (!strcmp(kind, "ccc")) k = FIR_CCC;
-    else return fail(GRHIP_EINVAL, "unknown FIR kind '%s'", kind);
+    if (!fir_kind_parse(kind, &k) || !(k == FIR_CCF || k == FIR_FFF || k == FIR_CCC))
+        return fail(GRHIP_EINVAL, "unknown FIR kind '%s'", kind);
     if (ntaps && !taps) return fail(GRHIP_EINVAL, "taps is NULL");
     return make_handle(h, [&](grhip_fir_filter_with_buffer *f) {
         f->kind = k; f->mode = default_mode();
         int rc = f->init_device(device);
         if (rc) return rc;
-        f->taps.assign(taps, taps + ntaps * f->tw());
-        f->ntaps = (int)ntaps;
-        if ((rc = f->reset_line())) return rc;
-        return f->ensure_inner(1);
+        return f->install(taps, ntaps);
     });
 }
 
@@ -872,21 +720,11 @@ int grhip_fir_filter_with_buffer_set_taps(grhip_fir_filter_with_buffer *h, const
     if (!h || (ntaps && !taps)) return fail(GRHIP_EINVAL, "null argument");
     int rc = h->bind();
     if (rc) return rc;
-    GRHIP_HIP(hipStreamSynchronize(h->own_stream));
-    h->taps.assign(taps, taps + ntaps * h->tw());
-    h->ntaps = (int)ntaps;
-    if (h->inner) { grhip_fir_filter_destroy(h->inner); h->inner = nullptr; h->inner_dec = 0; }
-    rc = h->reset_line();
-    if (!rc) rc = h->ensure_inner(1);
-    return rc;
+    GRHIP_HIP(hipDeviceSynchronize());      // no launch may still be reading the taps or the delay line
+    return h->install(taps, ntaps);
 }
 
-int grhip_fir_filter_with_buffer_set_mode(grhip_fir_filter_with_buffer *h, int mode)
-{
-    if (!h || !mode_valid(mode)) return fail(GRHIP_EINVAL, "bad mode");
-    h->mode = mode;
-    return GRHIP_OK;
-}
+int grhip_fir_filter_with_buffer_set_mode(grhip_fir_filter_with_buffer *h, int mode) { return set_mode_of(h, mode); }
 
 int grhip_fir_filter_with_buffer_ntaps(const grhip_fir_filter_with_buffer *h) { return h ? h->ntaps : GRHIP_EINVAL; }
 
@@ -911,15 +749,11 @@ int grhip_fir_filter_with_buffer_filterNdec_device(grhip_fir_filter_with_buffer 
     if (H) GRHIP_HIP(hipMemcpyAsync(both, h->d_hist.p, H * it, hipMemcpyDeviceToDevice, st));
     GRHIP_HIP(hipMemcpyAsync(both + H * it, d_input, nin * it, hipMemcpyDeviceToDevice, st));
     const void *first = both + (decimate - 1) * it;         // window of output 0 ends at new item decimate - 1
-    if (!mode_fast(h->mode)) {
-        if ((rc = h->ensure_inner(h->inner_dec ? h->inner_dec : 1))) return rc;      // (its reversed taps on the device)
-        rc = launch_fir_generic(h->kind, h->inner->d_taps_rev.as<float>(), (int)T, first, d_output, (long long)n, (int)decimate,
+    if (!mode_fast(h->mode))        // (GENERIC needs no engines: the reference's order, one accumulator)
+        rc = launch_fir_generic(h->kind, h->d_taps_rev.as<float>(), (int)T, first, d_output, (long long)n, (int)decimate,
                                 nullptr, st, true);
-    } else {
-        if ((rc = h->ensure_inner((unsigned)decimate))) return rc;
-        h->inner->mode = h->mode;
-        rc = h->inner->run(first, d_output, (long long)n, (int)decimate, st);
-    }
+    else if (!(rc = h->ensure_engines((int)decimate, st)))
+        rc = h->eng.run_plain(h->kind, h->mode, h->d_taps_rev.as<float>(), first, d_output, (long long)n, (int)decimate, st);
     if (rc) return rc;
     if (H) GRHIP_HIP(hipMemcpyAsync(h->d_hist.p, both + nin * it, H * it, hipMemcpyDeviceToDevice, st));   // the last ntaps - 1 items
     return GRHIP_OK;
@@ -1048,12 +882,7 @@ void grhip_xlating_demod_destroy(grhip_xlating_demod *h)
     destroy_handle(h);
 }
 
-int grhip_xlating_demod_set_mode(grhip_xlating_demod *h, int mode)
-{
-    if (!h || !mode_valid(mode)) return fail(GRHIP_EINVAL, "bad mode");
-    h->mode = mode;
-    return GRHIP_OK;
-}
+int grhip_xlating_demod_set_mode(grhip_xlating_demod *h, int mode) { return set_mode_of(h, mode); }
 
 int grhip_xlating_demod_reset(grhip_xlating_demod *h)
 {
@@ -1111,8 +940,7 @@ int grhip_xlating_demod_run_captures_device(grhip_xlating_demod *h, int n_stream
     const long long n_out = (long long)(n_samples / (size_t)h->core.decim);
     if (n_out <= 0) return GRHIP_OK;
     // (GRHIP_MODE_GENERIC: the fused generic-order kernel takes batches at decimation 1 / 2 / 4; run() says so otherwise)
-    if (mode_fast(h->mode) && !(h->core.use_tiled || (mode_matrix(h->mode) && h->core.use_mfma) ||
-                                (h->core.use_hidec && h->core.hidec_premix)))
+    if (mode_fast(h->mode) && !fir_has_batched_engine(h->core.eng.plan, h->mode))
         return fail(GRHIP_EINVAL, "run_captures needs a batched engine (FAST mode, supported decimation)");
     if (h->core.tab_start != 0 && !h->core.demod_is_direct(h->mode, true, true))
         return fail(GRHIP_EINVAL, "handle has streamed past its cached rotator table; use a fresh handle");
@@ -1234,12 +1062,7 @@ int grhip_freq_xlating_fir_filter_set_taps(grhip_freq_xlating_fir_filter *h, con
     return GRHIP_OK;
 }
 
-int grhip_freq_xlating_fir_filter_set_mode(grhip_freq_xlating_fir_filter *h, int mode)
-{
-    if (!h || !mode_valid(mode)) return fail(GRHIP_EINVAL, "bad mode");
-    h->mode = mode;
-    return GRHIP_OK;
-}
+int grhip_freq_xlating_fir_filter_set_mode(grhip_freq_xlating_fir_filter *h, int mode) { return set_mode_of(h, mode); }
 
 int grhip_freq_xlating_fir_filter_history(const grhip_freq_xlating_fir_filter *h)
 {

@@ -83,8 +83,7 @@ int launch_pfb(const PfbArgs &a, hipStream_t st);
 // the shape has no fused kernel (the caller then runs the three blocks)
 int launch_pfb_hier(const PfbArgs &a, hipStream_t st);
 
-// gr_fft_filter_ccc, fused overlap-save on 4096-point blocks (ntaps <= 2049)
-constexpr int OLS_N = 4096, OLS_MAX_TAPS = 2049;
+// gr_fft_filter_ccc, fused overlap-save on 4096-point blocks (OLS_N, OLS_MAX_TAPS: fir_plan.h)
 // twiddle table and transformed taps (scaled by 1/4096) for launch_fftfilt4096; taps = ntaps complex floats
 // (interleaved), h[k] multiplies x[i-k].  L = outputs per block at full rate, a multiple of `decim`.
 int ols_build(const float *taps_cplx, int ntaps, int decim, DevBuf &d_tw, DevBuf &d_H, int *L, int *fold);

@@ -4,11 +4,9 @@
 
 #include <vector>
 
-namespace grhip {
+#include "fir_plan.h"       // FirKind
 
-enum FirKind { FIR_FFF = 0, FIR_CCF = 1, FIR_CCC = 2, FIR_FCC = 3, FIR_SCC = 4, FIR_FSF = 5 };
-// complex taps (interleaved): ccc and the real-input kinds with complex output
-inline bool fir_kind_ctaps(FirKind k) { return k == FIR_CCC || k == FIR_FCC || k == FIR_SCC; }
+namespace grhip {
 
 // ---- (A) generic-order kernel: bit-exact gr_fir_XXX_generic -----------------
 // taps_rev: device, d_taps order (reversed forward taps); complex interleaved

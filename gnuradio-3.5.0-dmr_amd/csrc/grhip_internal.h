@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/grhip.h"
+#include "fir_plan.h"
 
 namespace grhip {
 
@@ -216,9 +217,7 @@ int make_handle(H **h, Init &&init)
 }
 
 int default_mode();
-inline bool mode_valid(int m) { return m == GRHIP_MODE_FAST || m == GRHIP_MODE_GENERIC || m == GRHIP_MODE_FAST_VALU || m == GRHIP_MODE_FAST_REFTAPS; }
-inline bool mode_fast(int m) { return m != GRHIP_MODE_GENERIC; }          // FAST, FAST_VALU or FAST_REFTAPS
-inline bool mode_matrix(int m) { return m == GRHIP_MODE_FAST || m == GRHIP_MODE_FAST_REFTAPS; }   // matrix cores allowed
+// (mode_valid / mode_fast / mode_matrix: fir_plan.h)
 
 // shared read-only device tables (per device, created on first use)
 struct DeviceTables {

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "fir_engines.h"
 #include "grhip_internal.h"
 
 namespace grhip {
@@ -23,9 +24,8 @@ struct XlatingCore {
     std::vector<std::complex<float>> proto;
     double center_freq = 0, sampling_freq = 1;
 
-    // set before build(): the handle only ever demodulates (xlating_demod, dmr_chain).  Its FAST dispatch then prefers the
-    // engines with a fused demodulator -- they need no rotator phases, whose exact recurrence is computed on the host at
-    // ~3 ns per output and bounds a STREAMING block on any other path (measured: 1-8 Gsamples/s against 200-320)
+    // set before build(): the handle only ever demodulates (xlating_demod, dmr_chain).  Its plan then prefers the
+    // engines with a fused demodulator (fir_plan_xlating)
     bool for_demod = false;
     // set before build(): the items the handle reads -- 0 complex (ccc, ccf), 1 float (fcf, fcc), 2 int16 (scf, scc).
     // Real items run the inner gr_fir_fcc / gr_fir_scc (fir_realin.hip, or the generic-order kernel) + rotator table;
@@ -33,34 +33,21 @@ struct XlatingCore {
     int in_kind = 0;
     // set before build(): the prototype taps are float (?cf kinds), so proto[i] * exp(...) is float * complex = (a*c, a*d)
     bool real_tap_type = false;
-    bool use_realin = false;
-    int ri_Tq = 0;
-    DevBuf d_ri_hp;
     // built by build()
     int ntaps = 0;
     std::vector<std::complex<float>> ctaps;     // composite taps, reference arithmetic
     std::complex<float> incr{1.f, 0.f};         // normalised d_phase_incr
     double omega = 0;                           // (double)(float)fwT0
     DevBuf d_taps_generic;                      // ctaps (d_taps order of the inner gr_fir_ccc)
-    DevBuf d_hp, d_wtab, d_stab, d_vtab;        // tiled kernel operands
-    int Tq = 0;
-    bool use_tiled = false, premix = false;
-    // FAST mode for the shapes the tiled kernel does not take (other decimations, long prototypes):
-    // overlap-save engine (fft_kernels.hip) + rotator table multiply
-    bool use_ols = false, prefer_ols = false, use_hidec = false;
-    int ols_L = 0, ols_fold = 0;
-    DevBuf d_ols_tw, d_ols_H, d_hidec_taps, d_hidec_etab, d_hidec_vtab;
-    bool hidec_premix = false;
-    // FAST mode, real prototype, decimation 2 / 4, up to ~260 taps: matrix-core engine (fir_mfma.hip)
-    bool use_mfma = false;
-    int mf_kexp = 0;
-    float mf_wstep[2] = {1.f, 0.f};
-    DevBuf d_mf_A[2], d_mf_wlane[2], d_mf_stab, d_mf_vtab;     // [alignment parity]
-    SchedBuf mf_sched;
+    FirEngines eng;                             // the plan and the fast engines' operands
+    // what only a frequency-translating filter has: the phasor tables of the pre-mix forms (real prototype)
+    DevBuf d_wtab, d_stab, d_vtab;              // tiled kernel
+    DevBuf d_hidec_etab, d_hidec_vtab;          // high-decimation kernel
+    float mf_wstep[2] = {1.f, 0.f};             // matrix-core engine
+    DevBuf d_mf_wlane[2], d_mf_stab, d_mf_vtab; // [alignment parity]
     int mf_cu_cap = 0;                          // FirMfmaArgs::max_cus of the next launches (the chain's masked FIR stream)
     int mf_wg_cap = 0;                          // FirMfmaArgs::max_wg_per_cu of the next launches (the chain's pipeline sets 1)
     DevBuf scratch_y;
-    SchedBuf sched;                             // tile queue of the tiled kernel (one launch at a time per handle)
 
     // rotator table: phases of outputs [tab_start, tab_start+tab_len)
     long long pos = 0;                          // outputs produced since construction/reset
@@ -95,15 +82,18 @@ struct XlatingCore {
     void reset();
     int ensure_rot(long long n, const float2 **gtab, hipStream_t st);
     int phase_before_pos(std::complex<float> *g);
-    // fused demodulator on the pre-mixed accumulators (EPI_DEMOD): FAST mode, real prototype taps
-    // (single-stream calls of a long filter go through the overlap-save engine instead; batched
-    // launches -- several streams, or history supplied by range check -- always take the tiled kernel)
+    // the frame of the demodulator's carried sample, chosen before pointers or lengths are known: true = the fused
+    // demodulator on the pre-mixed accumulators (EPILOGUE_DEMOD_FUSED, composite frame)
     bool demod_is_direct(int mode, bool demod, bool batched = false) const
     {
-        if (demod && mode_matrix(mode) && use_mfma) return true;
-        if (demod && mode_fast(mode) && use_hidec && hidec_premix) return true;     // the direct kernel's fused demodulator
-        return demod && mode_fast(mode) && use_tiled && premix && (batched || !prefer_ols);
+        FirCall c;
+        c.mode = mode; c.demod = demod; c.batched = batched;
+        return fir_route(eng.plan, c).epilogue == EPILOGUE_DEMOD_FUSED;
     }
+    // the demodulator as a second kernel: fir(y, y_stride) writes the FIR's outputs behind one carried sample per stream
+    template <class Fir>
+    int demod_second(const FirIo &io, float gain, const float2 *y_prev, float2 *y_last, const float *atan_tab, hipStream_t st,
+                     Fir &&fir);
     // d_in item 0 = input[0] of output 0 (oldest history item); items with index
     // < n_lo or >= n_in read as zero.  n_streams > 1: stream s at d_in + s*x_stride,
     // outputs at d_y/d_demod + s*out_stride, y_prev[s] / y_last[s].

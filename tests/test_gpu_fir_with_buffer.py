@@ -48,6 +48,29 @@ def test_fast_mode_tolerance(gpu, po, kind, ntaps, dec):
         assert rel_err_max(blk.filterNdec(part, n, dec), ref.filterNdec(part, n, dec)) <= 1e-5
 
 
+@pytest.mark.parametrize("kind,ntaps", [("ccf", 64), ("ccc", 100), ("fff", 31)])
+def test_fast_mode_across_decimation_changes(gpu, po, kind, ntaps):
+    """One handle in FAST mode while the decimation changes from call to call (its engines are rebuilt each time), with
+    a GENERIC call in between: the delay line carries through all of them."""
+    rng = np.random.default_rng(ntaps + 7 * len(kind))
+    taps = _data(rng, kind, ntaps, kind == "ccc")
+    calls = [(gpu.MODE_FAST, 1500, 1), (gpu.MODE_FAST, 1500, 4), (gpu.MODE_FAST, 1501, 1), (gpu.MODE_FAST, 1500, 7),
+             (gpu.MODE_GENERIC, 500, 2), (gpu.MODE_FAST, 1499, 2), (gpu.MODE_FAST, 1500, 4)]
+    x = _data(rng, kind, sum(n * dec for _, n, dec in calls), kind != "fff")
+    blk = gpu.fir_filter_with_buffer(kind, taps)
+    ref = po.FirFilterWithBuffer(kind, taps)
+    pos = 0
+    for mode, n, dec in calls:
+        seg = x[pos:pos + n * dec]
+        pos += n * dec
+        blk.set_mode(mode)
+        got, want = blk.filterNdec(seg, n, dec), ref.filterNdec(seg, n, dec)
+        if mode == gpu.MODE_GENERIC:
+            assert bits_equal(got, want), (n, dec)
+        else:
+            assert rel_err_max(got, want) <= 1e-5, (n, dec)
+
+
 def test_device_entry(gpu, po):
     import torch
     rng = np.random.default_rng(1)

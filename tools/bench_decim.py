@@ -1,5 +1,6 @@
 """Decimating filters at shapes the tiled kernel does not take: which engine wins where.
-usage: python tools/bench_decim.py   (GRHIP_NO_HIDEC=1 forces the overlap-save engine)"""
+usage: python tools/bench_decim.py   (with a -DGRHIP_DIAG build of the library, GRHIP_HIDEC=0 forces the overlap-save
+engine and GRHIP_HIDEC=1 the high-decimation kernel wherever it is supported)"""
 import json
 import os
 import sys
