@@ -26,6 +26,7 @@ __all__ = [
     "logpwrfft_c", "logpwrfft_f", "window_blackmanharris",
     "pwr_squelch_cc", "pwr_squelch_ff", "simple_squelch_cc", "ctcss_squelch_ff",
     "agc_cc", "agc_ff", "agc2_cc", "agc2_ff",
+    "iir_filter_ffd", "fm_deemph", "fm_deemph_taps", "firdes_low_pass", "fm_demod_cf", "nbfm_rx",
     "WIN_HAMMING", "WIN_HANN", "WIN_BLACKMAN", "WIN_RECTANGULAR", "WIN_KAISER", "WIN_BLACKMAN_hARRIS",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
     "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
@@ -1666,6 +1667,150 @@ class agc2_ff(_agc2):
     agc2_cc on floats, with the rate test on the magnitude of |out| - reference as the reference has it"""
     _name = "agc2_ff"
     _dtype = np.float32
+
+
+# ----------------------------------------------------------------------------
+# gr.iir_filter_ffd, blks2.fm_deemph, gr.firdes.low_pass  (filter/gr_iir_filter_ffd.i, blks2impl/fm_emph.py,
+# general/gr_firdes.i)
+# ----------------------------------------------------------------------------
+def _taps_d(taps):
+    t = np.ascontiguousarray(taps, dtype=np.float64).reshape(-1)
+    return t, (_ptr(t) if len(t) else C.c_void_p(0)), len(t)
+
+
+class iir_filter_ffd(_Block):
+    """gr.iir_filter_ffd(fftaps, fbtaps): y[t] = sum ff[i] x[t-i] + sum_{i>=1} fb[i] y[t-i] in double (the feedback is
+    added, fbtaps[0] is never read), float in and out.  work(x) takes streams x n_in items back to back and returns
+    as many; the delay lines carry across calls.  MODE_GENERIC is the reference's recurrence bit for bit; every other
+    mode runs calls of more than chunk() items in chunks where the taps allow it (chunked()).  set_taps is latched:
+    it holds, with zeroed delay lines, from the next work call.  work_device does not synchronise."""
+    _name = "iir_filter_ffd"
+
+    def __init__(self, fftaps, fbtaps, device=0):
+        _Block.__init__(self)
+        f, pf, n = _taps_d(fftaps)          # f and b own the memory until the call returns
+        b, pb, m = _taps_d(fbtaps)
+        self._create(pf, n, pb, m, int(device))
+
+    def history(self):
+        return 1
+
+    def set_taps(self, fftaps, fbtaps):
+        f, pf, n = _taps_d(fftaps)
+        b, pb, m = _taps_d(fbtaps)
+        self._call("set_taps", pf, n, pb, m)
+
+    def chunked(self):
+        """True if the next call of more than chunk() items takes the chunked form"""
+        return bool(self._call("chunked"))
+
+    def work(self, input_items, n_in=None):
+        x = np.ascontiguousarray(input_items, dtype=np.float32).reshape(-1)
+        if n_in is None:
+            n_in = len(x) // self._streams
+        if len(x) < n_in * self._streams:
+            raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
+        out = np.zeros(max(n_in * self._streams, 1), dtype=np.float32)
+        self._call("work", int(n_in), _ptr(x), _ptr(out))
+        return out[:n_in * self._streams]
+
+    @staticmethod
+    def chunk():
+        """items per chunk of the chunked form"""
+        return lib().grhip_iir_filter_ffd_chunk()
+
+
+def fm_deemph_taps(fs, tau=75e-6):
+    """(btaps, ataps) of blks2.fm_deemph(fs, tau), two float64 each: host arithmetic only, no device needed"""
+    b = np.zeros(2, np.float64)
+    a = np.zeros(2, np.float64)
+    _check(lib().grhip_fm_deemph_taps(float(fs), float(tau), _ptr(b), _ptr(a)))
+    return b, a
+
+
+class fm_deemph(iir_filter_ffd):
+    """blks2.fm_deemph(fs, tau=75e-6) (blks2impl/fm_emph.py:44-72): gr.iir_filter_ffd over fm_deemph_taps(fs, tau)"""
+
+    def __init__(self, fs, tau=75e-6, device=0):
+        b, a = fm_deemph_taps(fs, tau)
+        iir_filter_ffd.__init__(self, b, a, device)
+
+
+def firdes_low_pass(gain, sampling_freq, cutoff_freq, transition_width, window=0, beta=6.76):
+    """gr.firdes.low_pass(gain, sampling_freq, cutoff_freq, transition_width, window=WIN_HAMMING, beta=6.76): host
+    arithmetic only, no device needed.  A failed argument check is a GrhipError."""
+    args = (float(gain), float(sampling_freq), float(cutoff_freq), float(transition_width), int(window), float(beta))
+    n = C.c_size_t(0)
+    rc = lib().grhip_firdes_low_pass(*(args + (C.c_void_p(0), 0, C.byref(n))))
+    if rc != -2:                                    # GRHIP_ERANGE: the size query's answer
+        _check(rc)
+    out = np.zeros(max(n.value, 1), dtype=np.float32)
+    _check(lib().grhip_firdes_low_pass(*(args + (_ptr(out), n.value, C.byref(n)))))
+    return out[:n.value]
+
+
+class fm_demod_cf(_Block):
+    """blks2.fm_demod_cf (blks2impl/fm_demod.py:51-72) as one handle: quadrature_demod_cf(channel_rate / (2 pi deviation))
+    -> fm_deemph(channel_rate, tau) (tau=None: none) -> fir_filter_fff(audio_decim, audio_taps).  The reference designs
+    its audio taps with optfir.low_pass (remez), which the library does not have: they are given.  work(x) takes
+    streams x n_in NEW complex items back to back (no history in front) and returns streams x produced floats, stream
+    s from s * produced; every inner block starts from a zero history and carries its state across calls.
+    MODE_GENERIC is the reference's chain bit for bit; every other mode runs one fused kernel where engine() is 1."""
+    _name = "fm_demod_cf"
+
+    def __init__(self, channel_rate, audio_decim, deviation, audio_taps, tau=75e-6, device=0):
+        _Block.__init__(self)
+        k = channel_rate / (2 * math.pi * deviation)
+        b, a = fm_deemph_taps(channel_rate, tau) if tau is not None else ((), ())
+        f, pf, n = _taps_d(b)
+        fb, pb, m = _taps_d(a)
+        t = np.ascontiguousarray(audio_taps, dtype=np.float32).reshape(-1)
+        if int(audio_decim) != audio_decim:
+            raise ValueError("audio_decim must be an integer")
+        self._create(float(k), pf, n, pb, m, int(audio_decim), _ptr(t), len(t), int(device))
+        self.audio_taps, self.audio_decim, self.k = t, int(audio_decim), float(np.float32(k))
+
+    def produced(self, n_in):
+        """outputs per stream of the next work call of n_in items"""
+        return self._call("produced", int(n_in))
+
+    def engine(self):
+        """1: the fused kernel runs the next call; 0: the three blocks in a row"""
+        return self._call("engine")
+
+    @staticmethod
+    def tile():
+        """input samples per workgroup of the fused kernel"""
+        return lib().grhip_fm_demod_cf_tile()
+
+    def work(self, input_items, n_in=None):
+        x = np.ascontiguousarray(input_items, dtype=np.complex64).reshape(-1)
+        if n_in is None:
+            n_in = len(x) // self._streams
+        if len(x) < n_in * self._streams:
+            raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
+        got = C.c_int(0)
+        out = np.zeros(max(self.produced(n_in) * self._streams, 1), dtype=np.float32)
+        self._call("work", int(n_in), _ptr(x) if len(x) else C.c_void_p(0), _ptr(out), C.byref(got))
+        return out[:got.value * self._streams]
+
+    def work_device(self, n_in, d_in, d_out, d_produced=None, stream=None):
+        """work on device buffers, queued on `stream`; d_produced: a device int that receives the count, or None"""
+        return self._call("work_device", int(n_in), _devptr(d_in), _devptr(d_out), _devptr(d_produced), _stream(stream))
+
+
+class nbfm_rx(fm_demod_cf):
+    """blks2.nbfm_rx(audio_rate, quad_rate, tau=75e-6, max_dev=5e3) (blks2impl/nbfm_rx.py:28-88): the rates as
+    integers, quad_rate a multiple of audio_rate (ValueError otherwise), k = quad_rate / (2 pi max_dev), the
+    de-emphasis at quad_rate, and the audio taps of firdes.low_pass(1.0, quad_rate, 2.7e3, 0.5e3, WIN_HAMMING)"""
+
+    def __init__(self, audio_rate, quad_rate, tau=75e-6, max_dev=5e3, device=0):
+        audio_rate = int(audio_rate)
+        quad_rate = int(quad_rate)
+        if quad_rate % audio_rate != 0:
+            raise ValueError("quad_rate is not an integer multiple of audio_rate")
+        taps = firdes_low_pass(1.0, quad_rate, 2.7e3, 0.5e3, WIN_HAMMING)
+        fm_demod_cf.__init__(self, quad_rate, quad_rate // audio_rate, max_dev, taps, tau, device)
 
 
 class keep_one_in_n(_Block):

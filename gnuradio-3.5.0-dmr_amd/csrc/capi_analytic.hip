@@ -291,6 +291,57 @@ int grhip_firdes_hilbert(unsigned ntaps, int window_type, double beta, float *ou
     return GRHIP_OK;
 }
 
+// general/gr_firdes.cc:104-148, compute_ntaps :680-695, sanity_check_1f :783-796
+int grhip_firdes_low_pass(double gain, double fs, double cutoff, double transition, int window_type, double beta, float *out,
+                          size_t cap, size_t *ntaps_out)
+{
+    static const float width_factor[5] = {3.3, 3.1, 5.5, 2.0, 10.0};
+    if (!ntaps_out) return fail(GRHIP_EINVAL, "null argument");
+    if (!std::isfinite(gain) || !std::isfinite(fs) || !std::isfinite(cutoff) || !std::isfinite(transition) || !std::isfinite(beta))
+        return fail(GRHIP_EINVAL, "firdes_low_pass: an argument is not finite");
+    if (fs <= 0.0) return fail(GRHIP_EINVAL, "gr_firdes check failed: sampling_freq > 0");
+    if (cutoff <= 0.0 || cutoff > fs / 2) return fail(GRHIP_EINVAL, "gr_firdes check failed: 0 < fa <= sampling_freq / 2");
+    if (transition <= 0) return fail(GRHIP_EINVAL, "gr_firdes check failed: transition_width > 0");
+    if (window_type < 0 || window_type > WIN_KAISER) return fail(GRHIP_EINVAL, "firdes_low_pass: window type outside 0 .. 4");
+    const double delta_f = transition / fs;
+    const double want = width_factor[window_type] / delta_f + 0.5;
+    if (!(want < (double)(1 << 24))) return fail(GRHIP_EINVAL, "firdes_low_pass: too many taps");
+    int ntaps = (int)want;
+    if ((ntaps & 1) == 0) ntaps++;
+    *ntaps_out = (size_t)ntaps;
+    if (cap < (size_t)ntaps || !out) return fail(GRHIP_ERANGE, "firdes_low_pass: %d taps, room for %zu", ntaps, out ? cap : (size_t)0);
+    std::vector<float> w;
+    firdes_window(window_type, ntaps, beta, w);
+    std::vector<float> taps((size_t)ntaps);
+    const int M = (ntaps - 1) / 2;
+    const double fwT0 = 2 * M_PI * cutoff / fs;
+    for (int n = -M; n <= M; n++) {
+        if (n == 0) taps[n + M] = (float)(fwT0 / M_PI * w[n + M]);
+        else taps[n + M] = (float)(sin(n * fwT0) / (n * M_PI) * w[n + M]);
+    }
+    double fmax = taps[0 + M];
+    for (int n = 1; n <= M; n++) fmax += 2 * taps[n + M];
+    gain /= fmax;
+    for (int i = 0; i < ntaps; i++) taps[i] = (float)(taps[i] * gain);
+    memcpy(out, taps.data(), taps.size() * sizeof(float));
+    return GRHIP_OK;
+}
+
+// blks2impl/fm_emph.py:55-63
+int grhip_fm_deemph_taps(double fs, double tau, double *b, double *a)
+{
+    if (!b || !a) return fail(GRHIP_EINVAL, "null argument");
+    if (!std::isfinite(fs) || !std::isfinite(tau) || fs == 0.0 || tau == 0.0)
+        return fail(GRHIP_EINVAL, "fm_deemph: fs and tau must be finite and not zero");
+    const double w_p = 1 / tau;
+    const double w_pp = tan(w_p / (fs * 2));
+    a[0] = 1;
+    a[1] = (w_pp - 1) / (w_pp + 1);
+    b[0] = w_pp / (1 + w_pp);
+    b[1] = b[0];
+    return GRHIP_OK;
+}
+
 int grhip_hilbert_fc_create(grhip_hilbert_fc **h, unsigned ntaps, int device)
 {
     if (!h) return fail(GRHIP_EINVAL, "null argument");

@@ -35,6 +35,8 @@
 //   gr_make_agc_cc / _ff, gr_make_agc2_cc / _ff
 //                                            <- the factories of the same names (general/gr_agc_cc.h, gr_agc_ff.h,
 //                                               gr_agc2_cc.h, gr_agc2_ff.h)
+//   gr_make_iir_filter_ffd, gr_make_fm_deemph <- gr_make_iir_filter_ffd (filter/gr_iir_filter_ffd.h), blks2.fm_deemph
+//   gr_make_fm_demod_cf, gr_make_nbfm_rx     <- blks2.fm_demod_cf / blks2.nbfm_rx (blks2impl/fm_demod.py, nbfm_rx.py), one block
 //
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
@@ -47,6 +49,7 @@
 // fewer than one multiple of outputs can no longer be requested and that tail is dropped
 // (runtime/gr_block_executor.cc:335-348).
 #pragma once
+#include <cmath>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -1606,3 +1609,117 @@ GRHIP_AGC2_BLK(agc2_ff, float)
 #undef GRHIP_AGC_BLK
 #undef GRHIP_AGC2_BLK
 #undef GRHIP_AGC_BLK_COMMON
+
+// ---------------------------------------------------------------------------
+// gr_iir_filter_ffd (fftaps, fbtaps in double; filter/gr_iir_filter_ffd.h:62-85): a gr_sync_block, history 1, float in
+// and out.  set_taps is latched until the next work call, as the reference's is.  fm_deemph_taps and
+// gr_make_fm_deemph are blks2.fm_deemph (blks2impl/fm_emph.py:44-72), one gr_iir_filter_ffd.
+// ---------------------------------------------------------------------------
+class grhip_iir_filter_ffd_blk;
+typedef boost::shared_ptr<grhip_iir_filter_ffd_blk> grhip_iir_filter_ffd_sptr;
+class grhip_iir_filter_ffd_blk : public gr_sync_block {
+    grhip_iir_filter_ffd *d_h = nullptr;
+    grhip_iir_filter_ffd_blk(const std::vector<double> &fftaps, const std::vector<double> &fbtaps, int device)
+        : gr_sync_block("iir_filter_ffd", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(float)))
+    {
+        grhip_detail::check(grhip_iir_filter_ffd_create(&d_h, fftaps.data(), fftaps.size(), fbtaps.data(), fbtaps.size(), device));
+    }
+    friend grhip_iir_filter_ffd_sptr gr_make_iir_filter_ffd(const std::vector<double> &, const std::vector<double> &, int);
+public:
+    ~grhip_iir_filter_ffd_blk() { grhip_iir_filter_ffd_destroy(d_h); }
+    void set_mode(int mode) { grhip_detail::check(grhip_iir_filter_ffd_set_mode(d_h, mode)); }
+    void set_taps(const std::vector<double> &fftaps, const std::vector<double> &fbtaps)
+    {
+        grhip_detail::check(grhip_iir_filter_ffd_set_taps(d_h, fftaps.data(), fftaps.size(), fbtaps.data(), fbtaps.size()));
+    }
+    bool chunked() const { return grhip_iir_filter_ffd_chunked(d_h) == 1; }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(grhip_iir_filter_ffd_work(d_h, noutput_items, in[0], out[0]));
+        return noutput_items;
+    }
+};
+inline grhip_iir_filter_ffd_sptr gr_make_iir_filter_ffd(const std::vector<double> &fftaps, const std::vector<double> &fbtaps,
+                                                        int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_iir_filter_ffd_blk(fftaps, fbtaps, device));
+}
+
+// (btaps, ataps) of blks2.fm_deemph(fs, tau)
+inline void fm_deemph_taps(double fs, double tau, std::vector<double> &btaps, std::vector<double> &ataps)
+{
+    btaps.assign(2, 0.0);
+    ataps.assign(2, 0.0);
+    grhip_detail::check(grhip_fm_deemph_taps(fs, tau, btaps.data(), ataps.data()));
+}
+inline grhip_iir_filter_ffd_sptr gr_make_fm_deemph(double fs, double tau = 75e-6, int device = 0)
+{
+    std::vector<double> b, a;
+    fm_deemph_taps(fs, tau, b, a);
+    return gr_make_iir_filter_ffd(b, a, device);
+}
+
+// gr_firdes::low_pass(gain, sampling_freq, cutoff_freq, transition_width, window = WIN_HAMMING (0), beta = 6.76)
+inline std::vector<float> grhip_firdes_low_pass_taps(double gain, double sampling_freq, double cutoff_freq, double transition_width,
+                                                     int window = 0, double beta = 6.76)
+{
+    size_t n = 0;
+    const int rc = grhip_firdes_low_pass(gain, sampling_freq, cutoff_freq, transition_width, window, beta, nullptr, 0, &n);
+    if (rc != GRHIP_ERANGE) grhip_detail::check(rc);            // GRHIP_ERANGE: the size query's answer
+    std::vector<float> taps(n);
+    grhip_detail::check(grhip_firdes_low_pass(gain, sampling_freq, cutoff_freq, transition_width, window, beta, taps.data(), n, &n));
+    return taps;
+}
+
+// ---------------------------------------------------------------------------
+// blks2.fm_demod_cf / blks2.nbfm_rx (blks2impl/fm_demod.py:51-72, nbfm_rx.py:28-88) as ONE block: a gr_sync_decimator by
+// audio_decim, complex in and float out, history 1 (the handle takes new items only and keeps every inner block's
+// history itself).  The audio taps are given: the reference designs them with optfir, which the library does not have.
+// ---------------------------------------------------------------------------
+class grhip_fm_demod_cf_blk;
+typedef boost::shared_ptr<grhip_fm_demod_cf_blk> grhip_fm_demod_cf_sptr;
+class grhip_fm_demod_cf_blk : public gr_sync_decimator {
+    grhip_fm_demod_cf *d_h = nullptr;
+    grhip_fm_demod_cf_blk(float k, const std::vector<double> &fftaps, const std::vector<double> &fbtaps, int audio_decim,
+                          const std::vector<float> &audio_taps, int device)
+        : gr_sync_decimator("fm_demod_cf", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(float)),
+                            audio_decim < 1 ? 1u : (unsigned)audio_decim)
+    {
+        grhip_detail::check(grhip_fm_demod_cf_create(&d_h, k, fftaps.data(), fftaps.size(), fbtaps.data(), fbtaps.size(), audio_decim,
+                                                     audio_taps.data(), audio_taps.size(), device));
+    }
+    friend grhip_fm_demod_cf_sptr grhip_make_fm_demod_cf(float, const std::vector<double> &, const std::vector<double> &, int,
+                                                         const std::vector<float> &, int);
+public:
+    ~grhip_fm_demod_cf_blk() { grhip_fm_demod_cf_destroy(d_h); }
+    void set_mode(int mode) { grhip_detail::check(grhip_fm_demod_cf_set_mode(d_h, mode)); }
+    int engine() const { return grhip_fm_demod_cf_engine(d_h); }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int produced = 0;
+        grhip_detail::check(grhip_fm_demod_cf_work(d_h, noutput_items * (int)decimation(), in[0], out[0], &produced));
+        return produced;
+    }
+};
+// the chain on given taps: quadrature_demod_cf(k) -> iir_filter_ffd(fftaps, fbtaps) (both empty: none) -> fir_filter_fff
+inline grhip_fm_demod_cf_sptr grhip_make_fm_demod_cf(float k, const std::vector<double> &fftaps, const std::vector<double> &fbtaps,
+                                                     int audio_decim, const std::vector<float> &audio_taps, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_fm_demod_cf_blk(k, fftaps, fbtaps, audio_decim, audio_taps, device));
+}
+// blks2.fm_demod_cf(channel_rate, audio_decim, deviation, ..., tau) on given audio taps; tau <= 0: no de-emphasis
+inline grhip_fm_demod_cf_sptr gr_make_fm_demod_cf(double channel_rate, int audio_decim, double deviation,
+                                                  const std::vector<float> &audio_taps, double tau = 75e-6, int device = 0)
+{
+    std::vector<double> b, a;
+    if (tau > 0) fm_deemph_taps(channel_rate, tau, b, a);
+    return grhip_make_fm_demod_cf((float)(channel_rate / (2 * M_PI * deviation)), b, a, audio_decim, audio_taps, device);
+}
+// blks2.nbfm_rx(audio_rate, quad_rate, tau = 75e-6, max_dev = 5e3)
+inline grhip_fm_demod_cf_sptr gr_make_nbfm_rx(int audio_rate, int quad_rate, double tau = 75e-6, double max_dev = 5e3, int device = 0)
+{
+    if (audio_rate <= 0 || quad_rate % audio_rate != 0)
+        throw std::invalid_argument("quad_rate is not an integer multiple of audio_rate");
+    return gr_make_fm_demod_cf(quad_rate, quad_rate / audio_rate, max_dev, grhip_firdes_low_pass_taps(1.0, quad_rate, 2.7e3, 0.5e3),
+                               tau, device);
+}

@@ -1008,6 +1008,21 @@ GRHIP_API int grhip_fft_vfc_work_device(grhip_fft_vfc *h, int noutput_items, con
  * ====================================================================== */
 GRHIP_API int grhip_firdes_hilbert(unsigned ntaps, int window_type, double beta, float *out);
 
+/* gr_firdes::low_pass  -- host only, no device needed
+ *   replaces gr_firdes::low_pass(double gain, double sampling_freq, double cutoff_freq,
+ *       double transition_width, win_type window, double beta)
+ *   general/gr_firdes.cc:104-148 with compute_ntaps, :680-695, and gr_firdes::window as above
+ * *ntaps receives the tap count, (int)(width_factor[window] / (transition / fs) + 0.5) made odd, and
+ * out, of `cap` floats, the taps; with cap too small (out may then be null) only *ntaps is written
+ * and the call returns GRHIP_ERANGE, so a first call with cap = 0 asks for the size.  The arithmetic
+ * is the reference's: the ideal response and the window product in double, narrowed to float per
+ * tap, the sum for the gain in double over those floats, the scaling a double product narrowed again.
+ * GRHIP_EINVAL where the reference throws (fs <= 0, cutoff <= 0 or > fs / 2, transition <= 0), and,
+ * a deviation, for an argument that is not finite, a window type outside 0 .. 4 (the reference
+ * reads past its width_factor table for type 5) and a tap count above 2^24. */
+GRHIP_API int grhip_firdes_low_pass(double gain, double fs, double cutoff, double transition, int window_type, double beta,
+                                    float *out, size_t cap, size_t *ntaps);
+
 /* ======================================================================
  * gr_hilbert_fc
  *   replaces gr_make_hilbert_fc(unsigned int ntaps)
@@ -1701,6 +1716,111 @@ GRHIP_API int grhip_agc2_ff_work(grhip_agc2_ff *h, int n_in, const void *in, voi
 GRHIP_API int grhip_agc2_ff_work_device(grhip_agc2_ff *h, int n_in, const void *d_in, void *d_out, void *stream);
 /* items per chunk of the chunked form of agc_cc / agc_ff */
 GRHIP_API int grhip_agc_chunk(void);
+
+/* ======================================================================
+ * gr_iir_filter_ffd
+ *   replaces gr_make_iir_filter_ffd(const std::vector<double> &fftaps,
+ *       const std::vector<double> &fbtaps)
+ *   filter/gr_iir_filter_ffd.cc:56-82 (work), filter/gri_iir.h:90-163 (set_taps, filter)
+ * Float in, float out, n feed-forward and m feedback taps in double (the counts may differ).  The
+ * handle takes S streams back to back as the gain loops do ([S][n_in], S = 1 after create; `out` may
+ * not overlap `in`; work / work_device return GRHIP_OK, n_in == 0 is a successful no-op, work_device
+ * does not synchronise).  One output is
+ *     acc = ff[0] x[t];  acc += ff[i] x[t-i], i = 1 .. n-1;  acc += fb[i] y[t-i], i = 1 .. m-1;
+ *     out[t] = (float)acc,   y[t] = acc
+ * in double, every product and every add rounded once, nothing contracted, in that order.  fb[0] is
+ * never read and the feedback is ADDED (the reference's convention: a pole at +p has fb[1] = +p; the
+ * taps of fm_deemph carry a negative a1 for that reason, and stay as they are).  Per stream the
+ * device holds the last n - 1 inputs as float and the last m - 1 accumulators as DOUBLE (the
+ * reference's d_prev_output is of tap_type); both start at zero and carry across calls.  n == 0
+ * writes zeros and touches no state.  set_taps is latched: it takes effect at the start of the next
+ * work call and zeroes both delay lines (gri_iir::set_taps); set_streams zeroes them too.
+ * Deviations: n > 0 with m == 0 is GRHIP_EINVAL (the reference writes past an empty vector there);
+ * more than 64 taps on either side is GRHIP_EINVAL.  Taps that are not finite are accepted and run
+ * serially.  GRHIP_EINVAL also: S < 1, n_in < 0, a null pointer, overlapping buffers.
+ * GRHIP_MODE_GENERIC: the recurrence in order, one wavefront per stream, bit for bit the reference.
+ * Every other mode, for calls of more than grhip_iir_filter_ffd_chunk() = 256 items, where
+ * K = m - 1 <= 8, every tap is finite and max over j = 1 .. 256 of ||C^j||_inf <= 64 (C the K x K
+ * companion matrix of fb: the zero-input response does not grow): the call is cut into chunks of 256
+ * items from its first item; every chunk is walked from zero accumulators (its inputs in front are
+ * the real ones), the chunks are chained in double, start of the next = C^256 start + end, and every
+ * chunk is walked again from its true start in the arithmetic above.  Both forms work in double and
+ * differ by the rounding of that chain alone: every output is within ulp_float(|y|) + 2^-40 peak of
+ * GENERIC's, peak the largest |y| of the call and its carried state (the chain's error is at most
+ * 256 * 64 * 2^-53 of it); within that the result depends on where the calls cut the input.  Samples
+ * that are not finite spread through the chain as NaN.  Anything else -- K > 8, unstable or
+ * non-finite taps, a call of at most one chunk -- runs the serial walk whatever the mode: such
+ * input costs time, never correctness.  chunked(h) is 1 if the next call of more than one chunk
+ * would take the chunked form (a latched set_taps counted), else 0.
+ * ====================================================================== */
+typedef struct grhip_iir_filter_ffd grhip_iir_filter_ffd;
+GRHIP_API int grhip_iir_filter_ffd_create(grhip_iir_filter_ffd **h, const double *fftaps, size_t n, const double *fbtaps,
+                                          size_t m, int device);
+GRHIP_API void grhip_iir_filter_ffd_destroy(grhip_iir_filter_ffd *h);
+GRHIP_API int grhip_iir_filter_ffd_set_taps(grhip_iir_filter_ffd *h, const double *fftaps, size_t n, const double *fbtaps,
+                                            size_t m);
+GRHIP_API int grhip_iir_filter_ffd_set_mode(grhip_iir_filter_ffd *h, int mode);
+GRHIP_API int grhip_iir_filter_ffd_set_streams(grhip_iir_filter_ffd *h, int nstreams);
+GRHIP_API int grhip_iir_filter_ffd_chunked(grhip_iir_filter_ffd *h);
+GRHIP_API int grhip_iir_filter_ffd_work(grhip_iir_filter_ffd *h, int n_in, const void *in, void *out);
+GRHIP_API int grhip_iir_filter_ffd_work_device(grhip_iir_filter_ffd *h, int n_in, const void *d_in, void *d_out, void *stream);
+/* items per chunk of the chunked form of iir_filter_ffd */
+GRHIP_API int grhip_iir_filter_ffd_chunk(void);
+
+/* The taps of blks2.fm_deemph(fs, tau) (blks2impl/fm_emph.py:55-63) in double, host arithmetic only:
+ * w_pp = tan((1 / tau) / (fs * 2)), a = [1, (w_pp - 1) / (w_pp + 1)], b0 = b1 = w_pp / (1 + w_pp).
+ * fm_deemph is gr.iir_filter_ffd(b, a): b and a (two doubles each) are the fftaps and fbtaps of
+ * grhip_iir_filter_ffd_create as they stand.  GRHIP_EINVAL: a null pointer, fs or tau zero or not
+ * finite (the reference divides by them). */
+GRHIP_API int grhip_fm_deemph_taps(double fs, double tau, double *b, double *a);
+
+/* ======================================================================
+ * blks2.fm_demod_cf / blks2.nbfm_rx  (hier block)
+ *   blks2impl/fm_demod.py:51-72, nbfm_rx.py:67-88, fm_emph.py:44-72:
+ *   gr_quadrature_demod_cf(k) -> fm_deemph, one gr_iir_filter_ffd(fftaps, fbtaps)
+ *       -> gr_fir_filter_fff(audio_decim, audio_taps)
+ * n == m == 0 means no de-emphasis (tau = None in the reference); taps on one side only are
+ * GRHIP_EINVAL, as are more than 64 of them, audio_decim outside 1 .. 65536 and ntaps outside
+ * 1 .. 65536.  The handle is the hier block as the scheduler runs it, NEW ITEMS ONLY: complex in as
+ * [S][n_in] (S = 1 after create), float out, every inner block from a zero history -- the
+ * demodulator's x[-1] = 0, the IIR's delay lines zero, the FIR's ntaps - 1 delay line zero -- so
+ * output j is the FIR over the de-emphasised samples j D - (ntaps - 1) .. j D of the whole stream.
+ * Per stream the device keeps the last complex sample, the IIR's state and the last ntaps - 1
+ * de-emphasised floats across calls; the handle keeps the stream position modulo D (one for all
+ * streams).  produced(h, n_in) is the number of j with j D inside the next call of n_in items;
+ * stream s writes that many floats from out + s * produced.  work's *produced and work_device's
+ * *d_produced (a device int; either may be null) receive it.  n_in == 0 is a successful no-op;
+ * work_device does not synchronise; `out` may not overlap `in`.  set_streams restarts every stream.
+ * GRHIP_MODE_GENERIC: the three blocks one after the other inside the handle -- the demodulator of
+ * grhip_quadrature_demod_cf, the serial walk of grhip_iir_filter_ffd, the generic-order FIR of
+ * grhip_fir_filter (fff) -- bit for bit the reference's chain; the outputs depend on the
+ * concatenated input alone, never on where the calls cut it.
+ * Every other mode: one fused kernel (engine(h) == 1) where n <= 2 and m <= 2, |a1| < 1 (a1 =
+ * fbtaps[1]), W0 = ceil(60 ln 2 / -ln |a1|) <= tile() / 8 and ntaps <= 1025 (any audio_decim): one
+ * workgroup per stream and tile of tile() = 8192 input samples demodulates the tile and the
+ * W0 + ntaps - 1 samples in front of it into LDS (the demodulator is grhip_quadrature_demod_cf's,
+ * which has one form), runs the de-emphasis over it in double as an affine scan over the lanes'
+ * sub-chunks, narrows to float and forms the decimated outputs with f32 FMAs: 8 + 4 / D bytes of
+ * memory traffic per input sample.  A tile that does not reach the call's start begins from a zero
+ * accumulator W0 samples early: the truncation is at most 2^-60 of the peak.  Every other shape
+ * (engine(h) == 0) runs the three blocks in a row, the IIR in its chunked form where
+ * grhip_iir_filter_ffd would chunk it.  Either way every output is within 1e-5 of the output's peak
+ * of the float64 chain over the same demodulator output (the FIR family's FAST contract); within
+ * that the result depends on where the calls cut the input.  (For 75 us, W0 is 97 at 32 kHz and
+ * 998 at 320 kHz.)
+ * ====================================================================== */
+typedef struct grhip_fm_demod_cf grhip_fm_demod_cf;
+GRHIP_API int grhip_fm_demod_cf_create(grhip_fm_demod_cf **h, float k, const double *fftaps, size_t n, const double *fbtaps,
+                                       size_t m, int audio_decim, const float *audio_taps, size_t ntaps, int device);
+GRHIP_API void grhip_fm_demod_cf_destroy(grhip_fm_demod_cf *h);
+GRHIP_API int grhip_fm_demod_cf_set_mode(grhip_fm_demod_cf *h, int mode);
+GRHIP_API int grhip_fm_demod_cf_set_streams(grhip_fm_demod_cf *h, int nstreams);
+GRHIP_API int grhip_fm_demod_cf_produced(grhip_fm_demod_cf *h, int n_in);
+GRHIP_API int grhip_fm_demod_cf_engine(grhip_fm_demod_cf *h);
+GRHIP_API int grhip_fm_demod_cf_tile(void);
+GRHIP_API int grhip_fm_demod_cf_work(grhip_fm_demod_cf *h, int n_in, const void *in, void *out, int *produced);
+GRHIP_API int grhip_fm_demod_cf_work_device(grhip_fm_demod_cf *h, int n_in, const void *d_in, void *d_out, int *d_produced,
+                                            void *stream);
 
 /* ======================================================================
  * gr_pfb_channelizer_ccf
