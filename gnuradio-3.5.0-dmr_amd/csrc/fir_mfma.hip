@@ -46,12 +46,6 @@
 #ifndef GRHIP_LG_W2
 #define GRHIP_LG_W2 0
 #endif
-#ifndef GRHIP_LG_ACC3
-#define GRHIP_LG_ACC3 0
-#endif
-#ifndef GRHIP_LG_ORDER
-#define GRHIP_LG_ORDER 1
-#endif
 #ifndef GRHIP_MF_WGS
 #define GRHIP_MF_WGS 2            // workgroups per CU the shipped kernel is compiled and launched for (experiment: 3 with GRHIP_MF_NBLK=2)
 #endif
@@ -72,9 +66,6 @@
 #define GRHIP_LG_LEAN 0           // 1: the lean demodulator of device_math.h (seven vector instructions fewer per output, same values on cfg2) in the
                                   // shipped kernel's epilogue: 1.225 / 1.228 ms against 1.220 / 1.239 (same box, interleaved) -- no lever, like every
                                   // other cut of the vector work: the kernel is not bound by the vector pipe's throughput alone (profiles/r03_notes.md)
-#endif
-#ifndef GRHIP_LG_SPREAD
-#define GRHIP_LG_SPREAD 0
 #endif
 
 
@@ -110,7 +101,8 @@ template <int D, int KS> struct Geo {
     static constexpr int OFF_ATAN = 4 * PL;
     static constexpr int OFF_MISC = OFF_ATAN + 256 * 8;
     static constexpr int OFF_G = OFF_MISC + 32;      // 4 wave maxima, the queue's hand-over slot; then the correction band G (freq_xlating)
-    static constexpr int LDS = OFF_G + mf::NG * 64 * 16;
+    static constexpr int OFF_WL = OFF_G + mf::NG * 64 * 16;     // the lanes' pre-mix phasors of round 0 (8 bytes per lane)
+    static constexpr int LDS = OFF_WL + mf::THREADS * 8;
     static_assert((1 << LOGQ) == Q, "segment stride must be a power of two");
     static_assert(HALO >= 0 && HALO % 32 == 0, "halo");
     static_assert(mf::NBLK != 4 || mf::plane_pos(mf::WAVE_NEW * D - 1, D) + 2 - mf::plane_pos(HALO, D) >= SCR_WAVE * 4, "a wave's own stretch of a plane must hold one accumulator tile");
@@ -247,12 +239,23 @@ __global__ void __launch_bounds__(mf::THREADS, GRHIP_MF_WGS) fir_mfma_kernel(con
     }
     const float tq_sgn = __builtin_amdgcn_ldexpf((lane & 8) ? 1.0f : -1.0f, -mf::G_EXTRA_EXP);
     // pre-mix phasors of the lane's two samples of round 0: e^{jw(2t - off)}, e^{jw(2t + 1 - off)}
-    f32x2 wl{1.f, 0.f}, wl1{1.f, 0.f};
+    // (kept in LDS, each lane's in a slot of its own, and read back at the top of every staging: they are needed for a
+    // third of the tile period, and the four registers are what the matrix phase and the epilogue lacked)
     if (PREMIX) {
         const float2 v = a.wlane[t];
-        wl = f32x2{v.x, v.y};
-        wl1 = cmul_pk(wl, f32x2{a.wstep.x, a.wstep.y});
+        reinterpret_cast<f32x2 *>(smem + G::OFF_WL)[t] = f32x2{v.x, v.y};
     }
+    auto lane_phasors = [&](f32x2 &wl, f32x2 &wl1) __attribute__((always_inline)) {
+        wl = f32x2{1.f, 0.f};
+        wl1 = wl;
+        if (PREMIX) {
+            // (the offset goes through an empty asm, or the loop-invariant read is hoisted out of the tile loop)
+            unsigned woff = (unsigned)(G::OFF_WL + 8 * t);
+            asm volatile("" : "+v"(woff));
+            wl = *reinterpret_cast<const __attribute__((address_space(3))) f32x2 *>(woff);
+            wl1 = cmul_pk(wl, f32x2{a.wstep.x, a.wstep.y});
+        }
+    };
     const cfloat_cp stab = (cfloat_cp)a.stab;
     if (DEMOD) {
         f32x2 *at = reinterpret_cast<f32x2 *>(smem + G::OFF_ATAN);
@@ -290,24 +293,46 @@ __global__ void __launch_bounds__(mf::THREADS, GRHIP_MF_WGS) fir_mfma_kernel(con
         rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2 *>(x), 0, (int)bytes, 0x00020000);
         voff = (int)(g0 * 8) + 16 * t;              // negative = before the stream: out of range, zeros
     };
-    // part < 0: all rounds; else the part-th quarter
-    auto fetch = [&](__amdgpu_buffer_rsrc_t rsrc, int voff, int part_) __attribute__((always_inline)) {
-        constexpr int PER = (NI + NBLK - 1) / NBLK;       // (a share of the next tile's loads per block)
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            if (part_ >= 0 && i / PER != part_) continue;
-            int vo = voff + i * (16 * mf::THREADS);
-            if ((i + 1) * mf::ROUND > SP && 2 * t + i * mf::ROUND >= SP) vo = 0x7ffff000;   // past the tile: no traffic
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo, 0, 0);
-            pf[i] = __builtin_bit_cast(f32x4, v);
-        }
-    };
-
-    [[maybe_unused]] auto fetch_one = [&](__amdgpu_buffer_rsrc_t rsrc, int voff, int i) __attribute__((always_inline)) {
+    // round i of a tile (16 bytes per lane)
+    auto fetch_one = [&](__amdgpu_buffer_rsrc_t rsrc, int voff, int i) __attribute__((always_inline)) {
         int vo = voff + i * (16 * mf::THREADS);
-        if ((i + 1) * mf::ROUND > SP && 2 * t + i * mf::ROUND >= SP) vo = 0x7ffff000;
+        if ((i + 1) * mf::ROUND > SP && 2 * t + i * mf::ROUND >= SP) vo = 0x7ffff000;   // past the tile: no traffic
         const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo, 0, 0);
         pf[i] = __builtin_bit_cast(f32x4, v);
+    };
+    // ---- block floating point: the largest |component| of the tile in pf, this wave's share, into wmax[w].
+    // Taken at the end of the tile before (the first tile's in front of the loop), behind the wait for the loads and
+    // in front of the output stores: see the end of the tile loop.
+    auto tile_maxima = [&]() __attribute__((always_inline)) {
+        // (four running maxima: one would be a chain of 2 NI dependent instructions)
+        float m = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            if (GRHIP_LG_MAX4 && (i & 1)) {
+                asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m2) : "v"(pf[i][0]), "v"(pf[i][1]));
+                asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m3) : "v"(pf[i][2]), "v"(pf[i][3]));
+            } else {
+                asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(pf[i][0]), "v"(pf[i][1]));
+                asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(GRHIP_LG_MAX4 ? m1 : m) : "v"(pf[i][2]), "v"(pf[i][3]));
+            }
+        }
+        if (GRHIP_LG_MAX4) {
+            asm("v_max3_f32 %0, %1, %2, %0" : "+v"(m) : "v"(m1), "v"(m2));   // (the same instruction: a non-finite sample is treated
+            asm("v_max3_f32 %0, %1, %1, %0" : "+v"(m) : "v"(m3));            // as in the single chain)
+        }
+        m = wave_max_nonneg(m);
+        if (!(m < __builtin_inff())) {          // an Inf / NaN sample: the scale comes from the finite ones (see fir_mfma_rs_kernel)
+            float mf = 0.f;
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float av = __builtin_fabsf(pf[i][e]);
+                    mf = av < __builtin_inff() ? __builtin_fmaxf(mf, av) : mf;
+                }
+            m = wave_max_nonneg(mf);
+        }
+        if (lane == 0) wmax[w] = m;
     };
     const unsigned total_tiles = (unsigned)tiles_per_stream * (unsigned)a.n_streams;
     const unsigned Gd = gridDim.x;
@@ -321,7 +346,9 @@ __global__ void __launch_bounds__(mf::THREADS, GRHIP_MF_WGS) fir_mfma_kernel(con
     if (cur < total_tiles) {
         __amdgpu_buffer_rsrc_t rsrc; int voff;
         tile_geom(s, bidx, rsrc, voff);
-        fetch(rsrc, voff, -1);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) fetch_one(rsrc, voff, i);
+        tile_maxima();
     }
     unsigned nn_q = 0;          // the queue's raw answer (ticket number): valid in lane 0 of the workgroup only
     int voff_cur = 0;
@@ -340,39 +367,8 @@ __global__ void __launch_bounds__(mf::THREADS, GRHIP_MF_WGS) fir_mfma_kernel(con
         f32x2 Sa_first{0.f, 0.f}, Sb_first{0.f, 0.f};
         if (PREMIX && GRHIP_LG_SPF) { Sa_first = f32x2{stab[0], stab[1]}; Sb_first = f32x2{stab[2], stab[3]}; }
 #endif
-        // ---- block floating point: the tile's largest |component| ---------------------
-        {
-            // (four running maxima: one would be a chain of 2 NI dependent instructions at the top of every tile)
-            float m = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f;
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                if (GRHIP_LG_MAX4 && (i & 1)) {
-                    asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m2) : "v"(pf[i][0]), "v"(pf[i][1]));
-                    asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m3) : "v"(pf[i][2]), "v"(pf[i][3]));
-                } else {
-                    asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(pf[i][0]), "v"(pf[i][1]));
-                    asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(GRHIP_LG_MAX4 ? m1 : m) : "v"(pf[i][2]), "v"(pf[i][3]));
-                }
-            }
-            if (GRHIP_LG_MAX4) {
-                asm("v_max3_f32 %0, %1, %2, %0" : "+v"(m) : "v"(m1), "v"(m2));   // (the same instruction: a non-finite sample is treated
-                asm("v_max3_f32 %0, %1, %1, %0" : "+v"(m) : "v"(m3));            // as in the single chain)
-            }
-            m = wave_max_nonneg(m);
-            if (!(m < __builtin_inff())) {          // an Inf / NaN sample: the scale comes from the finite ones (see fir_mfma_rs_kernel)
-                float mf = 0.f;
-#pragma unroll
-                for (int i = 0; i < NI; ++i)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float av = __builtin_fabsf(pf[i][e]);
-                        mf = av < __builtin_inff() ? __builtin_fmaxf(mf, av) : mf;
-                    }
-                m = wave_max_nonneg(mf);
-            }
-            if (lane == 0) wmax[w] = m;
-            if (a.sched && t == 0) sched_slot[0] = nn_q + 2u * Gd;    // the queue's answer for the tile after next
-        }
+        // (the tile's maxima are in wmax already: tile_maxima() ran at the end of the tile before)
+        if (a.sched && t == 0) sched_slot[0] = nn_q + 2u * Gd;    // the queue's answer for the tile after next
         MF_STAMP(0);
         __syncthreads();        // planes free (previous tile's operand reads done), maxima and slot visible
         MF_STAMP(1);
@@ -412,6 +408,8 @@ __global__ void __launch_bounds__(mf::THREADS, GRHIP_MF_WGS) fir_mfma_kernel(con
         // instruction's operands are four issues old; the round phasors come as scalar pairs.
         if (PREMIX) MF_EXP_SKIP(2)
         {
+            f32x2 wl, wl1;
+            lane_phasors(wl, wl1);
             const f32x2 ws0 = wl * scale, ws1 = wl1 * scale;
             unsigned char *dst = smem + st_off;
             auto store_round = [&](int i, unsigned rh, unsigned rlo, unsigned ih, unsigned ilo) __attribute__((always_inline)) {
@@ -487,6 +485,8 @@ __global__ void __launch_bounds__(mf::THREADS, GRHIP_MF_WGS) fir_mfma_kernel(con
 #endif
         MF_EXP_SKIP(2)
         {
+            f32x2 wl, wl1;
+            lane_phasors(wl, wl1);
             const f32x2 ws0 = wl * scale, ws1 = wl1 * scale;
             unsigned char *dst = smem + st_off;
 #pragma unroll
@@ -569,9 +569,9 @@ __global__ void __launch_bounds__(mf::THREADS, GRHIP_MF_WGS) fir_mfma_kernel(con
         const int n_base = bidx * NTE - BLK + jt;          // stream index of that output (block 0); < 2^28
         const bool first_of_stream = bidx == 0 && t == 7;   // lane (segment 0, rows 14/15) of wave 0
         float ypendx = 0.f, ypendy = 0.f;           // first output of the segment, waits for its predecessor
-        float d1_pend = 0.f;
         float y1x = 0.f, y1y = 0.f;
         const float ypfx = ypf.x, ypfy = ypf.y;
+        f32x4 res[NBLK];            // what each block stores: (d0, d1) of the demodulator, or two complex outputs
 
         // one 16-output block: two consecutive outputs per lane (v: re0, im0, re1, im1) -> demodulator / store
         // (plain floats for everything that is selected per lane: a select between members of two float2 objects
@@ -601,10 +601,7 @@ __global__ void __launch_bounds__(mf::THREADS, GRHIP_MF_WGS) fir_mfma_kernel(con
                 const float2 prev = make_float2(px, py), y1 = make_float2(y1x, y1y);
                 const float d0 = GRHIP_LG_LEAN ? quad_demod_lean(y0, prev, a.gain, s_atan) : quad_demod_fast(y0, prev, a.gain, s_atan);
                 const float d1 = GRHIP_LG_LEAN ? quad_demod_lean(y1, y0, a.gain, s_atan) : quad_demod_fast(y1, y0, a.gain, s_atan);
-                if (b == 0) d1_pend = d1;
-                const bool st_ok = own && !(b == 0 && r8 == 0);     // (a segment's first pair waits for its predecessor)
-                const f32x2 dd{d0, d1};
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, dd), orsrc, st_ok ? 4 * n : OOB, 0, 0);
+                res[b] = f32x4{d0, d1, 0.f, 0.f};
             } else {
                 float2 o0 = y0, o1 = make_float2(y1x, y1y);
                 if (PREMIX) {
@@ -619,113 +616,145 @@ __global__ void __launch_bounds__(mf::THREADS, GRHIP_MF_WGS) fir_mfma_kernel(con
                     o0 = cmul_ref(o0, make_float2(gq[0], gq[1]));                   // gr_rotator: z = in * d_phase
                     o1 = cmul_ref(o1, make_float2(gq[2], gq[3]));
                 }
-                const f32x2 oa{o0.x, o0.y}, ob{o1.x, o1.y};
+                res[b] = f32x4{o0.x, o0.y, o1.x, o1.y};
+            }
+        };
+        // ... and its stores, issued behind the next tile's maxima (end of the tile loop)
+        auto store_block = [&](int b) __attribute__((always_inline)) {
+            const int n = n_base + BLK * b;
+            const bool own = !(b == 0 && rsl == 0) && n >= 0;
+            if (DEMOD) {
+                const f32x2 dd{res[b][0], res[b][1]};
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, dd), orsrc, own ? 4 * n : OOB, 0, 0);
+            } else {
+                const f32x2 oa{res[b][0], res[b][1]}, ob{res[b][2], res[b][3]};
                 const int so = own ? 8 * n : OOB;
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, oa), orsrc, so, 0, 0);
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, ob), orsrc, so + 8, 0, 0);
             }
         };
 
-        // ---- matrix phase, block by block (30 MFMAs each) ----
-        // Operand chunks are read one chunk ahead of their use (an LDS round trip is ~100 cycles).
+        // ---- matrix phase, CHUNK-major (the schedule: mfma_tables.h) ----
+        // The wave walks the NCH chunks of its segments once.  Chunk c is k-step c - CB b of every block b whose band
+        // covers it (up to four blocks, three MFMAs each), so each chunk is read from LDS once -- into a ring of
+        // mf::RING chunk pairs (24 VGPRs), two chunk steps ahead of its MFMAs (a step is ~120 cycles of MFMAs, an LDS
+        // round trip 100-200).  The ring BOUNDS the operand footprint: left to itself hipcc 7.2 merged the block-major
+        // form's repeated reads, kept the chunks in ~100 registers and so pushed the next tile's loads (whose
+        // destinations those registers are) behind the last block.  Here pf is live through the whole phase and one
+        // of the next tile's loads is requested per chunk step, from step 0 on.
+        // The order is pinned with sched_barrier(0): [reads of chunk c + 2, G operands, load(s)] | [MFMAs of chunk c].
+        // The reads are plain LDS loads, so the compiler counts lgkmcnt itself (the MFMAs of step c wait for all but
+        // the four youngest reads); nothing is hand-waited.
+        // Two accumulator tiles per block, added once behind the block's last chunk: `am` takes the high-half products
+        // of the four k-steps round the band's middle (the large taps of a low-pass), `ae` everything else -- the edge
+        // sum stays small, so only those four accumulations and the one addition round at the output's magnitude
+        // (what taking the k-steps from the band's ends inwards did for the block-major form; a single sweep cannot
+        // keep that order for every block).  mfma_tables.h has the assignment, DESIGN 4.0 the measurements.
         auto chunk_ptr = [&](int c) __attribute__((always_inline)) {
             const int u = rd_u + mf::CHUNK * c;
             return smem + rd_plane + 2 * u + 32 * (u >> LOGQ);
         };
+        constexpr int NCH = G::NCH;
+        static_assert(CB == mf::sched_cb(D), "chunks between block starts");
+        static_assert(KS / 2 - 2 >= 1 && KS / 2 + 1 < KS, "k-step 0 opens the edge tile");
         f32x4 acc[NBLK];
 #if defined(GRHIP_DIAG) && defined(GRHIP_MF_EXP) && (GRHIP_MF_EXP & 1)
 #pragma unroll
         for (int b = 0; b < NBLK; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) fetch(rsrc_n, voff_n, q);
+        for (int i = 0; i < NI; ++i) fetch_one(rsrc_n, voff_n, i);
         if (exp_off)
 #endif
         {
-        h16x8 Bh_n = *reinterpret_cast<const h16x8 *>(chunk_ptr(0));
-        h16x8 Bl_n = *reinterpret_cast<const h16x8 *>(chunk_ptr(0) + PL);
+        h16x8 Bh[mf::RING], Bl[mf::RING];
+        f32x4 ae[NBLK], am[NBLK], tq[NBLK];
+        h16x8 Gop[NBLK];
+        auto read_chunk = [&](int c) __attribute__((always_inline)) {
+            const unsigned char *src = chunk_ptr(c);
+            Bh[mf::ring_slot(c)] = *reinterpret_cast<const h16x8 *>(src);
+            Bl[mf::ring_slot(c)] = *reinterpret_cast<const h16x8 *>(src + PL);
+        };
+        // behind chunk `cdone`: the correction band's sum T of the blocks that have just had its last k-step joins their
+        // edge tile (one FMA per register: T is ~2^-18 of the output, and it leaves its four registers three k-steps
+        // before the block ends); the tiles of the blocks whose last chunk it was are added, edge + middle
+        auto finish_blocks = [&](int cdone) __attribute__((always_inline)) {
 #pragma unroll
-        for (int b = 0; b < NBLK; ++b) {
-#if GRHIP_LG_ACC3
-            // three accumulator tiles per block, added once at its end: the high-half products of the even and of the
-            // odd k-steps and the two low-half products.  An output then sees a third of the f32 accumulation roundings
-            // at about half the partial-sum magnitude: the FAST demodulator's per-element deviation from the reference
-            // went from 2.40e-5 to 1.74e-5 on cfg2 (round 3)
-            f32x4 m0{0.f, 0.f, 0.f, 0.f}, m1{0.f, 0.f, 0.f, 0.f}, lo{0.f, 0.f, 0.f, 0.f};
-#else
-            acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
-            f32x4 tq{0.f, 0.f, 0.f, 0.f};
-            // The k-steps of a block are taken from the band's ends towards its middle (0, KS-1, 1, KS-2, ...): a low-pass
-            // has its large taps in the middle, so the partial sum stays small until the last two or three k-steps and
-            // only those accumulations round at the output's magnitude (in index order every accumulation from the
-            // middle on does).  Same MFMAs, same registers; the FAST demodulator's largest per-element deviation from
-            // the reference on cfg2: 2.40e-5 in index order (round 3).
-            auto kstep = [](int q) constexpr { return GRHIP_LG_ORDER ? ((q & 1) ? KS - 1 - (q >> 1) : (q >> 1)) : q; };
-            h16x8 Gcur{}, Gnext{};
+            for (int b = 0; b < NBLK; ++b) {
+                if (TAPQ && mf::sched_k(D, cdone, b) == JG0 + mf::NG - 1) {
 #pragma unroll
-            for (int jq = 0; jq < KS; ++jq) {
-                const int j = kstep(jq);
-                const h16x8 Bh = Bh_n, Bl = Bl_n;
-                if (TAPQ) {
-                    // the correction band's operand of the NEXT k-step that needs one, a k-step ahead of its MFMA (read at the
-                    // point of use it cost an LDS round trip per middle k-step: 1.44 against 1.22 ms).  The address goes through
-                    // an empty asm: a plain loop-invariant LDS read is hoisted out of the tile loop, and G is back in sixteen
-                    // registers the kernel does not have.
-                    Gcur = Gnext;
-                    const int jn = jq + 1 < KS ? kstep(jq + 1) : (b + 1 < NBLK ? kstep(0) : -1);
-                    if (jn >= JG0 && jn < JG0 + mf::NG) {
-                        // (an LDS OFFSET goes through the asm and comes back as an LDS pointer: a laundered generic pointer
-                        // is read with flat_load, whose wait is vmcnt(0) -- it drained the tile prefetch: 1.38 against 1.21 ms)
-                        unsigned goff = (unsigned)(G::OFF_G + 16 * lane + (jn - JG0) * 1024);
-                        asm volatile("" : "+v"(goff));
-                        Gnext = *reinterpret_cast<const __attribute__((address_space(3))) h16x8 *>(goff);
-                    }
+                    for (int e = 0; e < 4; ++e) ae[b][e] = __builtin_fmaf(tq_sgn, tq[b][e], ae[b][e]);
                 }
-                const int cn = jq + 1 < KS ? CB * b + kstep(jq + 1) : CB * (b + 1) + kstep(0);       // next chunk: this block's, or the next block's first
-                if (jq + 1 < KS || b + 1 < NBLK) {
-                    const unsigned char *src = chunk_ptr(cn);
-                    Bh_n = *reinterpret_cast<const h16x8 *>(src);
-                    Bl_n = *reinterpret_cast<const h16x8 *>(src + PL);
+                if (mf::sched_last_chunk(D, KS, b) == cdone) acc[b] = ae[b] + am[b];
+            }
+        };
+        const f32x4 zero4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < mf::READ_AHEAD && c < NCH; ++c) read_chunk(c);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            // -- issue: what this step requests --
+            if (TAPQ) {
+                // the correction band's operands of this step's middle k-steps, in front of the chunk reads (LDS answers
+                // in order: their MFMAs, last in the step, then wait for nothing younger).  The address goes through an
+                // empty asm: a plain loop-invariant LDS read is hoisted out of the tile loop, and G is back in sixteen
+                // registers the kernel does not have.  (An LDS OFFSET goes through the asm and comes back as an LDS
+                // pointer: a laundered generic pointer is read with flat_load, whose wait is vmcnt(0) -- it drained
+                // the tile prefetch.)
+#pragma unroll
+                for (int b = 0; b < NBLK; ++b) {
+                    const int k = mf::sched_k(D, c, b);
+                    if (k < JG0 || k >= JG0 + mf::NG || k >= KS) continue;
+                    unsigned goff = (unsigned)(G::OFF_G + 16 * lane + (k - JG0) * 1024);
+                    asm volatile("" : "+v"(goff));
+                    Gop[b] = *reinterpret_cast<const __attribute__((address_space(3))) h16x8 *>(goff);
                 }
-#if GRHIP_LG_ACC3
-                // (the even / odd split only where the registers hold it without spilling: the headline shape and the short bands)
-                constexpr bool EVEN_ODD = GRHIP_LG_ACC3 == 1 && (KS <= 6 || (D == 4 && EPI == EPI_DEMOD));
-                if (EVEN_ODD && (j & 1)) m1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[j], Bh, m1, 0, 0, 0);
-                else m0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[j], Bh, m0, 0, 0, 0);
-                lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[j], Bl, lo, 0, 0, 0);
-                lo = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[j], Bh, lo, 0, 0, 0);
-#else
-                acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[j], Bh, acc[b], 0, 0, 0);
-                acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[j], Bl, acc[b], 0, 0, 0);
-                acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[j], Bh, acc[b], 0, 0, 0);
-#endif
-                if (TAPQ && j >= JG0 && j < JG0 + mf::NG) {
-                    // the other part's chunk of the same segment sits in the lane 8 places round the row of 16 (column ^ 8)
-                    const u32x4 bw = __builtin_bit_cast(u32x4, Bh);
+            }
+            if (c + mf::READ_AHEAD < NCH) read_chunk(c + mf::READ_AHEAD);
+#pragma unroll
+            for (int i = mf::loads_begin(NI, NCH, c); i < mf::loads_begin(NI, NCH, c + 1); ++i) fetch_one(rsrc_n, voff_n, i);
+            finish_blocks(c - 1);
+            __builtin_amdgcn_sched_barrier(0);
+            // -- multiply: chunk c against every block it belongs to --
+            const h16x8 bh = Bh[mf::ring_slot(c)], bl = Bl[mf::ring_slot(c)];
+#pragma unroll
+            for (int pass = 0; pass < mf::PASSES; ++pass) {       // Ah Xh of every block, then Ah Xl, then Al Xh: neighbours are independent
+#pragma unroll
+                for (int b = 0; b < NBLK; ++b) {
+                    if (!mf::sched_uses(D, KS, c, b)) continue;
+                    const int k = mf::sched_k(D, c, b);
+                    const bool mid = mf::sched_acc(KS, k, pass) == mf::ACC_MID;
+                    // a tile's first product: the edge tile's is k-step 0 (KS / 2 - 2 >= 1), the middle tile's the first of its k-steps
+                    const bool first = pass == 0 && (k == 0 || (mid && !mf::k_is_mid(KS, k - 1)));
+                    const h16x8 av = pass == 2 ? Al[k] : Ah[k], bv = pass == 1 ? bl : bh;
+                    if (mid) am[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, first ? zero4 : am[b], 0, 0, 0);
+                    else ae[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, first ? zero4 : ae[b], 0, 0, 0);
+                }
+            }
+            if (TAPQ) {
+                // the other part's chunk of the same segment sits in the lane 8 places round the row of 16 (column ^ 8)
+                bool any = false;
+#pragma unroll
+                for (int b = 0; b < NBLK; ++b) {
+                    const int k = mf::sched_k(D, c, b);
+                    if (k >= JG0 && k < JG0 + mf::NG && k < KS) any = true;
+                }
+                if (any) {
+                    const u32x4 bw = __builtin_bit_cast(u32x4, bh);
                     u32x4 sw;
 #pragma unroll
                     for (int e = 0; e < 4; ++e)          // row_ror:8 (every lane has a source: `old` is never used, and naming the source saves a move of zero)
                         sw[e] = (unsigned)__builtin_amdgcn_update_dpp((int)bw[e], (int)bw[e], 0x128, 0xf, 0xf, false);
-                    tq = __builtin_amdgcn_mfma_f32_16x16x32_f16(Gcur, __builtin_bit_cast(h16x8, sw), tq, 0, 0, 0);
-                }
-#if GRHIP_LG_SPREAD
-                {   // one of the next tile's loads behind every second k-step (instead of a quarter of them per block)
-                    constexpr int STEP = (NBLK * KS) / NI > 0 ? (NBLK * KS) / NI : 1;
-                    const int pos = b * KS + jq;
-                    if (pos % STEP == 0 && pos / STEP < NI) fetch_one(rsrc_n, voff_n, pos / STEP);
-                }
-#else
-                if (jq == 1) fetch(rsrc_n, voff_n, b);       // a quarter of the next tile's loads per block
-#endif
-            }
-#if GRHIP_LG_ACC3
-            acc[b] = GRHIP_LG_ACC3 == 1 ? (m0 + m1) + lo : m0 + lo;
-#endif
-            if (TAPQ) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc[b][e] = __builtin_fmaf(tq_sgn, tq[e], acc[b][e]);
+                    for (int b = 0; b < NBLK; ++b) {
+                        const int k = mf::sched_k(D, c, b);
+                        if (k < JG0 || k >= JG0 + mf::NG || k >= KS) continue;
+                        tq[b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Gop[b], __builtin_bit_cast(h16x8, sw), k == JG0 ? zero4 : tq[b], 0, 0, 0);
+                    }
+                }
             }
+            __builtin_amdgcn_sched_barrier(0);
         }
+        finish_blocks(NCH - 1);
         }
         MF_STAMP(4);
         MF_EXP_SKIP(5)
@@ -769,9 +798,34 @@ __global__ void __launch_bounds__(mf::THREADS, GRHIP_MF_WGS) fir_mfma_kernel(con
             const float px = __shfl_up(y1x, 1), py = __shfl_up(y1y, 1);
             const float dp = GRHIP_LG_LEAN ? quad_demod_lean(make_float2(ypendx, ypendy), make_float2(px, py), a.gain, s_atan)
                                            : quad_demod_fast(make_float2(ypendx, ypendy), make_float2(px, py), a.gain, s_atan);
-            const bool st_ok = r8 == 0 && rsl != 0 && n_base >= 0;
-            const f32x2 dd{dp, d1_pend};
-            __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, dd), orsrc, st_ok ? 4 * n_base : OOB, 0, 0);
+            // (that pair goes where block 0's pair of the same lane would: the lanes r8 == 0 of block 0 store nothing of their
+            // own, and the pair's second half is their block-0 d1 -- one store instruction for both)
+            res[0][0] = r8 == 0 ? dp : res[0][0];
+        }
+        // (the results are pinned here: tile_maxima() has a branch, and what only the stores behind it use would be
+        // sunk past it -- a third of the last demodulator ran behind the wait for the loads)
+#pragma unroll
+        for (int b = 0; b < NBLK; ++b) {
+            if (DEMOD) asm volatile("" : "+v"(res[b][0]), "+v"(res[b][1]));
+            else asm volatile("" : "+v"(res[b]));
+        }
+        }
+        MF_STAMP(5);
+        // ---- the NEXT tile's maxima, between this tile's last demodulator and its output stores ----
+        // The next tile's loads have had the matrix phase and the epilogue to land, and no store is pending yet: loads
+        // and stores share the wave's in-order counter (vmcnt), so a wait for the loads behind the stores would wait
+        // for the stores' acknowledgements too (it did, at the loop top).  The results of the five store
+        // instructions wait in registers meanwhile.  wmax[w] is free: every wave read this tile's maxima before the
+        // barrier behind the staging, and no wave gets here before that barrier; the barrier at the loop top makes
+        // the new ones visible.
+        __builtin_amdgcn_sched_barrier(0);
+        tile_maxima();
+        __builtin_amdgcn_sched_barrier(0);
+        MF_EXP_SKIP(5)
+        {
+#pragma unroll
+        for (int b = 0; b < NBLK; ++b) store_block(b);
+        if (DEMOD) {
             // carry for the next call: the composite FIR output of the stream's last output, computed
             // directly (f32, composite taps) by the first wave of the workgroup that owns the last tile
             if (a.y_last && bidx == tiles_per_stream - 1 && w == 0) {
@@ -779,7 +833,11 @@ __global__ void __launch_bounds__(mf::THREADS, GRHIP_MF_WGS) fir_mfma_kernel(con
                 __amdgpu_buffer_rsrc_t xr; int vdummy;
                 tile_geom(s, bidx, xr, vdummy);
                 float sx = 0.f, sy = 0.f;
-                for (int i = lane; i < a.T; i += 64) {
+                // (the lane index goes through an empty asm: the address of the lane's first tap is loop invariant, and
+                // hoisted out of the tile loop it held two registers, or a spill slot, for the whole launch)
+                int i0 = lane;
+                asm volatile("" : "+v"(i0));
+                for (int i = i0; i < a.T; i += 64) {
                     const long long it = item0 + i;
                     const int vo = (it < 0 || (lead && it == 0)) ? OOB : (int)(it * 8);
                     const u32x2 xv = __builtin_amdgcn_raw_buffer_load_b64(xr, vo, 0, 0);
@@ -792,9 +850,8 @@ __global__ void __launch_bounds__(mf::THREADS, GRHIP_MF_WGS) fir_mfma_kernel(con
                 if (lane == 0) a.y_last[s] = make_float2(sx, sy);
             }
         }
-
         }
-        MF_STAMP(5);
+        MF_STAMP(6);
         cur = nxt;
         if (!a.sched) nxt = nxt + Gd;
         s = s_nxt; bidx = b_nxt;

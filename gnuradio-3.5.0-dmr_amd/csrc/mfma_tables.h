@@ -128,6 +128,53 @@ inline void build_A(const float *h, int T, int D, int KS, int off, int kexp, std
             }
 }
 
+// ---- schedule of the matrix phase (fir_mfma.hip unrolls from these; tests/test_mfma_schedule.py checks them) --------
+// The wave walks the chunks c = 0 .. NCH-1 of its segments ONCE ("chunk step" c).  Chunk c is k-step k = c - CB b of every
+// block b with 0 <= k < KS (up to NBLK blocks, three MFMAs each), so every chunk is read from LDS once.  The operands
+// live in a ring of RING chunk pairs (high and low halves, 8 VGPRs a pair): chunk c sits in slot c % RING and is read
+// READ_AHEAD steps before the step that uses it (steps -READ_AHEAD .. -1 are the reads in front of the first MFMA), an
+// LDS round trip being longer than one step's MFMAs.  At the MFMAs of step c the chunks c .. c + READ_AHEAD are resident.
+// Each block has two accumulator tiles, added once behind the block's last k-step.  ACC_MID takes the high-half
+// products (Ah Xh) of the two middle k-steps of the band and of their two neighbours (a low-pass has its large taps
+// there); ACC_EDGE takes everything else: all three products of the outer k-steps and the low-half products (2^-11 of
+// their high-half ones) of the middle ones.  The edge sum stays small, so four accumulations and that one addition
+// round at the output's magnitude.  (Measured on the demodulator's per-element deviation from the reference, DESIGN
+// 4.0: with all three products of only the two middle k-steps in ACC_MID the shoulders of the main lobe sit in the
+// edge tile and every later accumulation rounds at their magnitude.)
+// One of the next tile's NI loads is requested per chunk step (loads_begin(c) .. loads_begin(c + 1) - 1 in step c).
+constexpr int RING = 3;
+constexpr int READ_AHEAD = RING - 1;
+constexpr int ACC_EDGE = 0, ACC_MID = 1;
+constexpr int PASSES = 3;                                                       // the three products of a k-step: Ah Xh, Ah Xl, Al Xh
+constexpr int sched_cb(int D) { return BLK * D / CHUNK; }                       // chunks between block starts
+constexpr int sched_k(int D, int c, int b) { return c - sched_cb(D) * b; }      // k-step of block b that chunk c is
+constexpr bool sched_uses(int D, int KS, int c, int b) { return sched_k(D, c, b) >= 0 && sched_k(D, c, b) < KS; }
+// the k-steps whose high-half product goes to the middle tile: the two middle ones and their neighbours
+constexpr bool k_is_mid(int KS, int k) { return k >= KS / 2 - 2 && k <= KS / 2 + 1; }
+constexpr int sched_acc(int KS, int k, int pass) { return pass == 0 && k_is_mid(KS, k) ? ACC_MID : ACC_EDGE; }
+constexpr int sched_last_chunk(int D, int KS, int b) { return sched_cb(D) * b + KS - 1; }   // the block's tiles are added behind it
+constexpr int ring_slot(int c) { return c % RING; }
+constexpr int read_step(int c) { return c - READ_AHEAD; }                       // the step in front of whose MFMAs chunk c is read
+constexpr int loads_begin(int NI, int NCH, int c) { return c <= 0 ? 0 : (c >= NCH ? NI : c * NI / NCH); }
+
+struct SchedMfma { int step, chunk, block, k, pass, acc, slot; };
+struct SchedRead { int step, chunk, slot; };
+// the whole schedule in issue order, as the kernel unrolls it
+inline void build_schedule(int D, int KS, std::vector<SchedRead> &reads, std::vector<SchedMfma> &mfmas)
+{
+    const int NCH = chunks_per_seg(D, KS);
+    reads.clear();
+    mfmas.clear();
+    for (int c = 0; c < READ_AHEAD && c < NCH; ++c) reads.push_back({read_step(c), c, ring_slot(c)});
+    for (int c = 0; c < NCH; ++c) {
+        if (c + READ_AHEAD < NCH) reads.push_back({c, c + READ_AHEAD, ring_slot(c + READ_AHEAD)});
+        for (int pass = 0; pass < PASSES; ++pass)
+            for (int b = 0; b < NBLK; ++b)
+                if (sched_uses(D, KS, c, b))
+                    mfmas.push_back({c, c, b, sched_k(D, c, b), pass, sched_acc(KS, sched_k(D, c, b), pass), ring_slot(c)});
+    }
+}
+
 // ---- the reference's tap-angle quantisation (freq_xlating only) -----------------------------------------
 // gr_freq_xlating_fir_filter builds its composite taps as proto[i] * exp(j * (float)(i * fwT0)) with the product i * fwT0
 // rounded to binary32 (filter/gr_freq_xlating_fir_filter_XXX.cc.t:79): tap i carries an angle error e_i of up to half an
