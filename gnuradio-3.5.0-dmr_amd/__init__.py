@@ -8,7 +8,9 @@ gr.pfb_channelizer_ccf, gr.pfb_arb_resampler_ccf / _fff, gr.fractional_interpola
 gr.filter_delay_fc, gr.goertzel_fc, gr.firdes.hilbert, gr.dc_blocker_ff / _cc, gr.moving_average_XX,
 gr.integrate_XX, gr.complex_to_mag_squared, gr.single_pole_iir_filter_ff, gr.nlog10_ff, gr.keep_one_in_n,
 gr.pwr_squelch_cc / _ff, gr.simple_squelch_cc, gr.ctcss_squelch_ff, gr.agc_cc / _ff, gr.agc2_cc / _ff,
-gr.iir_filter_ffd, blks2.fm_deemph, blks2.fm_demod_cf, blks2.nbfm_rx, gr.firdes.low_pass, gr.interp_fir_filter_XXX,
+gr.iir_filter_ffd, blks2.fm_deemph, blks2.fm_demod_cf, blks2.nbfm_rx, gr.firdes.low_pass, gr.remez, optfir.low_pass /
+high_pass / band_pass / band_reject (as optfir_*), gr.complex_to_mag, blks2.am_demod_cf, blks2.demod_10k0a3e_cf,
+blks2.demod_20k0f3e_cf, blks2.demod_200kf3e_cf, gr.interp_fir_filter_XXX,
 gr.rational_resampler_base_XXX, blks2.rational_resampler_XXX, gr.pfb_interpolator_ccf,
 gr.pfb_synthesis_filterbank_ccf) with the same
 constructor arguments; `work()` takes/returns numpy arrays with the

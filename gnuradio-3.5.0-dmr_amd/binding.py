@@ -27,6 +27,8 @@ __all__ = [
     "pwr_squelch_cc", "pwr_squelch_ff", "simple_squelch_cc", "ctcss_squelch_ff",
     "agc_cc", "agc_ff", "agc2_cc", "agc2_ff",
     "iir_filter_ffd", "fm_deemph", "fm_deemph_taps", "firdes_low_pass", "fm_demod_cf", "nbfm_rx",
+    "remez", "optfir_low_pass", "optfir_high_pass", "optfir_band_pass", "optfir_band_reject", "optfir_spec",
+    "complex_to_mag", "am_demod_cf", "demod_10k0a3e_cf", "demod_20k0f3e_cf", "demod_200kf3e_cf",
     "WIN_HAMMING", "WIN_HANN", "WIN_BLACKMAN", "WIN_RECTANGULAR", "WIN_KAISER", "WIN_BLACKMAN_hARRIS",
     "interp_fir_filter_ccf", "interp_fir_filter_fff", "interp_fir_filter_ccc",
     "rational_resampler_base_ccf", "rational_resampler_base_fff", "rational_resampler_base_ccc",
@@ -1389,6 +1391,16 @@ class complex_to_mag_squared(_spectrum):
         self._create(int(vlen), int(device))
 
 
+class complex_to_mag(_spectrum):
+    """gr.complex_to_mag(vlen=1): (float)sqrt((double)re * re + (double)im * im), the same in every mode"""
+    _name = "complex_to_mag"
+    _in = np.complex64
+
+    def __init__(self, vlen=1, device=0):
+        _spectrum.__init__(self, vlen)
+        self._create(int(vlen), int(device))
+
+
 class single_pole_iir_filter_ff(_spectrum):
     """gr.single_pole_iir_filter_ff(alpha, vlen=1): y = alpha x + (1 - alpha) y_prev per element, taps in double, state
     in float; the state carries across work calls and set_taps keeps it"""
@@ -1752,7 +1764,8 @@ def firdes_low_pass(gain, sampling_freq, cutoff_freq, transition_width, window=0
 class fm_demod_cf(_Block):
     """blks2.fm_demod_cf (blks2impl/fm_demod.py:51-72) as one handle: quadrature_demod_cf(channel_rate / (2 pi deviation))
     -> fm_deemph(channel_rate, tau) (tau=None: none) -> fir_filter_fff(audio_decim, audio_taps).  The reference designs
-    its audio taps with optfir.low_pass (remez), which the library does not have: they are given.  work(x) takes
+    its audio taps with optfir.low_pass; this constructor takes them as given, and design(...) designs them as the
+    reference does (optfir_low_pass).  work(x) takes
     streams x n_in NEW complex items back to back (no history in front) and returns streams x produced floats, stream
     s from s * produced; every inner block starts from a zero history and carries its state across calls.
     MODE_GENERIC is the reference's chain bit for bit; every other mode runs one fused kernel where engine() is 1."""
@@ -1769,6 +1782,16 @@ class fm_demod_cf(_Block):
             raise ValueError("audio_decim must be an integer")
         self._create(float(k), pf, n, pb, m, int(audio_decim), _ptr(t), len(t), int(device))
         self.audio_taps, self.audio_decim, self.k = t, int(audio_decim), float(np.float32(k))
+
+    @classmethod
+    def design(cls, channel_rate, audio_decim, deviation, audio_pass, audio_stop, gain=1.0, tau=75e-6, device=0):
+        """blks2.fm_demod_cf(channel_rate, audio_decim, deviation, audio_pass, audio_stop, gain, tau) with the
+        reference's own audio filter: optfir.low_pass(gain, channel_rate, audio_pass, audio_stop, 0.1, 60), narrowed
+        to float per tap (blks2impl/fm_demod.py:60-66)"""
+        taps = optfir_low_pass(gain, channel_rate, audio_pass, audio_stop, 0.1, 60).astype(np.float32)
+        blk = cls.__new__(cls)
+        fm_demod_cf.__init__(blk, channel_rate, audio_decim, deviation, taps, tau, device)
+        return blk
 
     def produced(self, n_in):
         """outputs per stream of the next work call of n_in items"""
@@ -1811,6 +1834,166 @@ class nbfm_rx(fm_demod_cf):
             raise ValueError("quad_rate is not an integer multiple of audio_rate")
         taps = firdes_low_pass(1.0, quad_rate, 2.7e3, 0.5e3, WIN_HAMMING)
         fm_demod_cf.__init__(self, quad_rate, quad_rate // audio_rate, max_dev, taps, tau, device)
+
+
+def demod_20k0f3e_cf(channel_rate, audio_decim, device=0):
+    """blks2.demod_20k0f3e_cf (blks2impl/fm_demod.py:74-91): NBFM, 5 kHz deviation, audio 3 kHz / 4.5 kHz"""
+    return fm_demod_cf.design(channel_rate, audio_decim, 5000, 3000, 4500, device=device)
+
+
+def demod_200kf3e_cf(channel_rate, audio_decim, device=0):
+    """blks2.demod_200kf3e_cf (blks2impl/fm_demod.py:93-111): WFM, 75 kHz deviation, audio 15 kHz / 16 kHz, gain 20.
+    At the receiver's shape (320 kHz, audio_decim 10) the designed filter has 1164 taps, more than the fused FM kernel
+    takes: engine() is 0 there and the three blocks run in a row."""
+    return fm_demod_cf.design(channel_rate, audio_decim, 75000, 15000, 16000, 20.0, device=device)
+
+
+# ----------------------------------------------------------------------------
+# gr.remez and gnuradio.optfir (general/gr_remez.i, python/gnuradio/optfir.py): host arithmetic only
+# ----------------------------------------------------------------------------
+_REMEZ_TYPES = {"bandpass": 1, "differentiator": 2, "hilbert": 3}
+
+
+def _sized_doubles(call):
+    """the size query of the tap designers: call(out, cap, ntaps) once for the size, once for the taps"""
+    n = C.c_size_t(0)
+    rc = call(C.c_void_p(0), 0, C.byref(n))
+    if rc != -2 or n.value == 0:                    # GRHIP_ERANGE with a count: the size query's answer
+        _check(rc)
+    out = np.zeros(max(n.value, 1), dtype=np.float64)
+    _check(call(_ptr(out), n.value, C.byref(n)))
+    return out[:n.value]
+
+
+def remez(order, bands, ampl, error_weight=(), filter_type="bandpass", grid_density=16):
+    """gr.remez(order, bands, ampl, error_weight, filter_type="bandpass", grid_density=16): order + 1 float64 taps, the
+    reference's bit for bit.  A refused argument or a failed exchange is a GrhipError with the reference's message."""
+    b, pb, nb = _taps_d(bands)
+    a, pa, na = _taps_d(ampl)
+    w, pw, nw = _taps_d(error_weight)
+    if na != nb:
+        raise GrhipError(-1, "gr_remez: must have one response magnitude for each band edge")
+    if filter_type not in _REMEZ_TYPES:
+        raise GrhipError(-1, "gr_remez: unknown ftype '%s'" % (filter_type,))
+    order, kind, density = int(order), _REMEZ_TYPES[filter_type], int(grid_density)
+    return _sized_doubles(lambda out, cap, n: lib().grhip_remez(order, pb, nb, pa, pw, nw, kind, density, out, cap, n))
+
+
+def _optfir(name, args, nextra_taps):
+    args = tuple(float(v) for v in args) + (int(nextra_taps),)
+    fn = getattr(lib(), "grhip_optfir_" + name)
+    return _sized_doubles(lambda out, cap, n: fn(*(args + (out, cap, n))))
+
+
+def optfir_low_pass(gain, Fs, freq1, freq2, passband_ripple_db, stopband_atten_db, nextra_taps=2):
+    """optfir.low_pass: float64 taps as gr.remez returns them"""
+    return _optfir("low_pass", (gain, Fs, freq1, freq2, passband_ripple_db, stopband_atten_db), nextra_taps)
+
+
+def optfir_high_pass(gain, Fs, freq1, freq2, passband_ripple_db, stopband_atten_db, nextra_taps=2):
+    """optfir.high_pass: an odd number of taps; the gain is not used, as in the reference"""
+    return _optfir("high_pass", (gain, Fs, freq1, freq2, passband_ripple_db, stopband_atten_db), nextra_taps)
+
+
+def optfir_band_pass(gain, Fs, freq_sb1, freq_pb1, freq_pb2, freq_sb2, passband_ripple_db, stopband_atten_db, nextra_taps=2):
+    """optfir.band_pass"""
+    return _optfir("band_pass", (gain, Fs, freq_sb1, freq_pb1, freq_pb2, freq_sb2, passband_ripple_db, stopband_atten_db),
+                   nextra_taps)
+
+
+def optfir_band_reject(gain, Fs, freq_pb1, freq_sb1, freq_sb2, freq_pb2, passband_ripple_db, stopband_atten_db, nextra_taps=2):
+    """optfir.band_reject: an odd number of taps"""
+    return _optfir("band_reject", (gain, Fs, freq_pb1, freq_sb1, freq_sb2, freq_pb2, passband_ripple_db, stopband_atten_db),
+                   nextra_taps)
+
+
+def optfir_spec(kind, gain, Fs, freqs, passband_ripple_db, stopband_atten_db, nextra_taps=2):
+    """(order, bands, ampl, weights) that optfir.<kind> hands to gr.remez; kind is "low_pass", "high_pass",
+    "band_pass" or "band_reject", freqs its band edges in the reference's order"""
+    k = ("low_pass", "high_pass", "band_pass", "band_reject").index(kind)
+    f, pf, nf = _taps_d(freqs)
+    order, nb = C.c_int(0), C.c_size_t(0)
+    bands, ampl, weight = np.zeros(6), np.zeros(6), np.zeros(3)
+    _check(lib().grhip_optfir_spec(k, float(gain), float(Fs), pf, nf, float(passband_ripple_db), float(stopband_atten_db),
+                                   int(nextra_taps), C.byref(order), _ptr(bands), _ptr(ampl), _ptr(weight), C.byref(nb)))
+    return order.value, bands[:2 * nb.value], ampl[:2 * nb.value], weight[:nb.value]
+
+
+# ----------------------------------------------------------------------------
+# blks2.am_demod_cf / demod_10k0a3e_cf (blks2impl/am_demod.py)
+# ----------------------------------------------------------------------------
+class am_demod_cf(_Block):
+    """blks2.am_demod_cf(channel_rate, audio_decim, audio_pass, audio_stop) (blks2impl/am_demod.py:42-58) as one handle:
+    complex_to_mag -> add_const_ff(-1) -> fir_filter_fff(audio_decim, audio_taps), the taps those of
+    optfir_low_pass(0.5, channel_rate, audio_pass, audio_stop, 0.1, 60) narrowed to float.  work(x) takes streams x n_in
+    NEW complex items back to back and returns streams x produced floats, stream s from s * produced; the FIR starts
+    from a zero delay line and carries it across calls.  MODE_GENERIC is the reference's chain bit for bit; every
+    other mode runs one fused kernel where engine() is 1."""
+    _name = "am_demod_cf"
+
+    def __init__(self, channel_rate, audio_decim, audio_pass, audio_stop, device=0):
+        taps = optfir_low_pass(0.5, channel_rate, audio_pass, audio_stop, 0.1, 60).astype(np.float32)
+        self._init_taps(audio_decim, taps, device)
+
+    @classmethod
+    def from_taps(cls, audio_decim, taps, device=0):
+        """the same block over given audio taps"""
+        blk = cls.__new__(cls)
+        am_demod_cf._init_taps(blk, audio_decim, taps, device)
+        return blk
+
+    def _init_taps(self, audio_decim, taps, device):
+        _Block.__init__(self)
+        t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        if int(audio_decim) != audio_decim:
+            raise ValueError("audio_decim must be an integer")
+        self._create(int(audio_decim), _ptr(t) if len(t) else C.c_void_p(0), len(t), int(device))
+        self.audio_taps, self.audio_decim = t, int(audio_decim)
+
+    def produced(self, n_in):
+        """outputs per stream of the next work call of n_in items"""
+        return self._call("produced", int(n_in))
+
+    def engine(self):
+        """1: the fused kernel runs the next call; 0: the three blocks in a row"""
+        return self._call("engine")
+
+    @staticmethod
+    def tile():
+        """input samples per workgroup of the fused kernel"""
+        return lib().grhip_am_demod_cf_tile()
+
+    @staticmethod
+    def outputs_per_lane():
+        """adjacent outputs a lane of the fused kernel forms with audio_decim == 1"""
+        return lib().grhip_am_demod_cf_outputs_per_lane()
+
+    @staticmethod
+    def max_taps():
+        """the longest filter the fused kernel takes"""
+        return lib().grhip_am_demod_cf_max_taps()
+
+    def work(self, input_items, n_in=None):
+        x = np.ascontiguousarray(input_items, dtype=np.complex64).reshape(-1)
+        if n_in is None:
+            n_in = len(x) // self._streams
+        if len(x) < n_in * self._streams:
+            raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
+        got = C.c_int(0)
+        out = np.zeros(max(self.produced(n_in) * self._streams, 1), dtype=np.float32)
+        self._call("work", int(n_in), _ptr(x) if len(x) else C.c_void_p(0), _ptr(out), C.byref(got))
+        return out[:got.value * self._streams]
+
+    def work_device(self, n_in, d_in, d_out, d_produced=None, stream=None):
+        """work on device buffers, queued on `stream`; d_produced: a device int that receives the count, or None"""
+        return self._call("work_device", int(n_in), _devptr(d_in), _devptr(d_out), _devptr(d_produced), _stream(stream))
+
+
+class demod_10k0a3e_cf(am_demod_cf):
+    """blks2.demod_10k0a3e_cf(channel_rate, audio_decim) (blks2impl/am_demod.py:60-76): AM, audio 5 kHz / 5.5 kHz"""
+
+    def __init__(self, channel_rate, audio_decim, device=0):
+        am_demod_cf.__init__(self, channel_rate, audio_decim, 5000, 5500, device)
 
 
 class keep_one_in_n(_Block):

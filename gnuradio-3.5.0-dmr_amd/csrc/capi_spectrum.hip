@@ -96,6 +96,14 @@ struct grhip_complex_to_mag_squared : SpectrumBlock {
     }
 };
 
+struct grhip_complex_to_mag : SpectrumBlock {
+    size_t in_elem() const override { return 8; }
+    int launch(int n, const void *d_in, void *d_out, hipStream_t st) override
+    {
+        return mag_launch((const float2 *)d_in, (float *)d_out, (long long)nstreams * n * vlen, st);
+    }
+};
+
 struct grhip_nlog10_ff : SpectrumBlock {
     float n = 1.f, k = 0.f;
     int launch(int count, const void *d_in, void *d_out, hipStream_t st) override
@@ -212,6 +220,13 @@ int grhip_complex_to_mag_squared_create(grhip_complex_to_mag_squared **h, int vl
     return create_vlen(h, vlen, device, [](grhip_complex_to_mag_squared *) {});
 }
 GRHIP_SPECTRUM_VLEN(complex_to_mag_squared)
+
+// ---- gr_complex_to_mag (gr_complex_to_xxx.cc, the std::abs loop) --------------------------------------------------------
+int grhip_complex_to_mag_create(grhip_complex_to_mag **h, int vlen, int device)
+{
+    return create_vlen(h, vlen, device, [](grhip_complex_to_mag *) {});
+}
+GRHIP_SPECTRUM_VLEN(complex_to_mag)
 
 // ---- gr_single_pole_iir_filter_ff (gr_single_pole_iir_filter_ff.cc:32-81) ----------------------------------------------
 int grhip_single_pole_iir_filter_ff_create(grhip_single_pole_iir_filter_ff **h, double alpha, int vlen, int device)

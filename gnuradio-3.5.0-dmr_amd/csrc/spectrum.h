@@ -1,4 +1,4 @@
-// spectrum.h -- launchers of the spectrum-estimate blocks (internal): gr_complex_to_mag_squared,
+// spectrum.h -- launchers of the spectrum-estimate blocks (internal): gr_complex_to_mag_squared, gr_complex_to_mag,
 // gr_single_pole_iir_filter_ff, gr_nlog10_ff and gr_keep_one_in_n.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,6 +14,10 @@ constexpr int IIR_FILL_LANES = 65536;
 
 // out[i] = re * re + im * im: two rounded products, one rounded add (general/gr_complex_to_xxx.cc:180-203)
 int mag_squared_launch(const float2 *in, float *out, long long n, hipStream_t st);
+
+// out[i] = (float)sqrt((double)re * re + (double)im * im), mag_val of spectrum_math.h (the std::abs loop of
+// general/gr_complex_to_xxx.cc)
+int mag_launch(const float2 *in, float *out, long long n, hipStream_t st);
 
 // out[i] = n * log10f(max(in[i], 1e-18f)) + k (general/gr_nlog10_ff.cc:60-61); in may be out
 int nlog10_launch(const float *in, float *out, long long count, float n, float k, hipStream_t st);

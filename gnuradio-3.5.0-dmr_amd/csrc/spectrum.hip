@@ -32,6 +32,15 @@ mag_squared_kernel(const float2 *__restrict__ in, float *__restrict__ out, long 
 }
 
 __global__ void __launch_bounds__(THREADS)
+mag_kernel(const float2 *__restrict__ in, float *__restrict__ out, long long n)
+{
+    for (long long i = blockIdx.x * (long long)THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * THREADS) {
+        const float2 v = in[i];
+        out[i] = mag_val(v.x, v.y);
+    }
+}
+
+__global__ void __launch_bounds__(THREADS)
 nlog10_kernel(const float *in, float *out, long long count, float n, float k)
 {
     for (long long i = blockIdx.x * (long long)THREADS + threadIdx.x; i < count; i += (long long)gridDim.x * THREADS)
@@ -115,6 +124,14 @@ int mag_squared_launch(const float2 *in, float *out, long long n, hipStream_t st
 {
     if (n <= 0) return GRHIP_OK;
     hipLaunchKernelGGL(mag_squared_kernel, dim3(blocks_for(n)), dim3(THREADS), 0, st, in, out, n);
+    GRHIP_HIP(hipGetLastError());
+    return GRHIP_OK;
+}
+
+int mag_launch(const float2 *in, float *out, long long n, hipStream_t st)
+{
+    if (n <= 0) return GRHIP_OK;
+    hipLaunchKernelGGL(mag_kernel, dim3(blocks_for(n)), dim3(THREADS), 0, st, in, out, n);
     GRHIP_HIP(hipGetLastError());
     return GRHIP_OK;
 }

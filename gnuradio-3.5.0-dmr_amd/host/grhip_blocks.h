@@ -37,6 +37,10 @@
 //                                               gr_agc2_cc.h, gr_agc2_ff.h)
 //   gr_make_iir_filter_ffd, gr_make_fm_deemph <- gr_make_iir_filter_ffd (filter/gr_iir_filter_ffd.h), blks2.fm_deemph
 //   gr_make_fm_demod_cf, gr_make_nbfm_rx     <- blks2.fm_demod_cf / blks2.nbfm_rx (blks2impl/fm_demod.py, nbfm_rx.py), one block
+//   grhip_optfir_low_pass_taps               <- optfir.low_pass (gnuradio/optfir.py:45-54), host arithmetic
+//   gr_make_complex_to_mag                   <- gr_complex_to_mag
+//   gr_make_am_demod_cf, gr_make_demod_10k0a3e_cf   <- blks2.am_demod_cf / demod_10k0a3e_cf (blks2impl/am_demod.py), one block
+//   gr_make_demod_20k0f3e_cf, gr_make_demod_200kf3e_cf   <- the FM presets of blks2impl/fm_demod.py:74-111
 //
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
@@ -1250,6 +1254,12 @@ inline grhip_complex_to_mag_squared_sptr gr_make_complex_to_mag_squared(unsigned
 {
     return gnuradio::get_initial_sptr(new grhip_complex_to_mag_squared_blk(vlen, device));
 }
+// gr_complex_to_mag (vlen = 1): general/gr_complex_to_xxx.cc:143-171
+GRHIP_SPECTRUM_BLK(complex_to_mag, gr_complex, (unsigned int, int), (unsigned int vlen, int device), (&d_h, (int)vlen, device), )
+inline grhip_complex_to_mag_sptr gr_make_complex_to_mag(unsigned int vlen = 1, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_complex_to_mag_blk(vlen, device));
+}
 GRHIP_SPECTRUM_BLK(single_pole_iir_filter_ff, float, (double, unsigned int, int), (double alpha, unsigned int vlen, int device),
                    (&d_h, alpha, (int)vlen, device),
                    void set_taps(double alpha) { grhip_detail::check(grhip_single_pole_iir_filter_ff_set_taps(d_h, alpha)); })
@@ -1674,7 +1684,7 @@ inline std::vector<float> grhip_firdes_low_pass_taps(double gain, double samplin
 // ---------------------------------------------------------------------------
 // blks2.fm_demod_cf / blks2.nbfm_rx (blks2impl/fm_demod.py:51-72, nbfm_rx.py:28-88) as ONE block: a gr_sync_decimator by
 // audio_decim, complex in and float out, history 1 (the handle takes new items only and keeps every inner block's
-// history itself).  The audio taps are given: the reference designs them with optfir, which the library does not have.
+// history itself).  gr_make_fm_demod_cf takes the audio taps as given; the presets below design them as the reference does.
 // ---------------------------------------------------------------------------
 class grhip_fm_demod_cf_blk;
 typedef boost::shared_ptr<grhip_fm_demod_cf_blk> grhip_fm_demod_cf_sptr;
@@ -1722,4 +1732,87 @@ inline grhip_fm_demod_cf_sptr gr_make_nbfm_rx(int audio_rate, int quad_rate, dou
         throw std::invalid_argument("quad_rate is not an integer multiple of audio_rate");
     return gr_make_fm_demod_cf(quad_rate, quad_rate / audio_rate, max_dev, grhip_firdes_low_pass_taps(1.0, quad_rate, 2.7e3, 0.5e3),
                                tau, device);
+}
+
+// optfir.low_pass(gain, Fs, freq1, freq2, passband_ripple_db, stopband_atten_db, nextra_taps = 2): doubles, as gr.remez
+inline std::vector<double> grhip_optfir_low_pass_taps(double gain, double Fs, double freq1, double freq2, double passband_ripple_db,
+                                                      double stopband_atten_db, int nextra_taps = 2)
+{
+    size_t n = 0;
+    const int rc = grhip_optfir_low_pass(gain, Fs, freq1, freq2, passband_ripple_db, stopband_atten_db, nextra_taps, nullptr, 0, &n);
+    if (rc != GRHIP_ERANGE || n == 0) grhip_detail::check(rc);  // GRHIP_ERANGE with a count: the size query's answer
+    std::vector<double> taps(n);
+    grhip_detail::check(grhip_optfir_low_pass(gain, Fs, freq1, freq2, passband_ripple_db, stopband_atten_db, nextra_taps, taps.data(), n, &n));
+    return taps;
+}
+inline std::vector<float> grhip_optfir_low_pass_taps_f(double gain, double Fs, double freq1, double freq2)
+{
+    const std::vector<double> d = grhip_optfir_low_pass_taps(gain, Fs, freq1, freq2, 0.1, 60);
+    return std::vector<float>(d.begin(), d.end());              // narrowed per tap, as gr.fir_filter_fff takes them
+}
+
+// blks2.fm_demod_cf(channel_rate, audio_decim, deviation, audio_pass, audio_stop, gain = 1.0, tau = 75e-6) with the
+// reference's own audio filter, optfir.low_pass(gain, channel_rate, audio_pass, audio_stop, 0.1, 60) (fm_demod.py:60-66)
+inline grhip_fm_demod_cf_sptr gr_make_fm_demod_cf(double channel_rate, int audio_decim, double deviation, double audio_pass,
+                                                  double audio_stop, double gain = 1.0, double tau = 75e-6, int device = 0)
+{
+    return gr_make_fm_demod_cf(channel_rate, audio_decim, deviation, grhip_optfir_low_pass_taps_f(gain, channel_rate, audio_pass, audio_stop),
+                               tau, device);
+}
+// blks2.demod_20k0f3e_cf (fm_demod.py:74-91): NBFM, 5 kHz deviation
+inline grhip_fm_demod_cf_sptr gr_make_demod_20k0f3e_cf(double channel_rate, int audio_decim, int device = 0)
+{
+    return gr_make_fm_demod_cf(channel_rate, audio_decim, 5000, 3000, 4500, 1.0, 75e-6, device);
+}
+// blks2.demod_200kf3e_cf (fm_demod.py:93-111): WFM, 75 kHz deviation, audio gain 20.  At 320 kHz and audio_decim 10 the
+// filter has 1164 taps, more than the fused FM kernel takes: engine() is 0 and the three blocks run in a row.
+inline grhip_fm_demod_cf_sptr gr_make_demod_200kf3e_cf(double channel_rate, int audio_decim, int device = 0)
+{
+    return gr_make_fm_demod_cf(channel_rate, audio_decim, 75000, 15000, 16000, 20.0, 75e-6, device);
+}
+
+// ---------------------------------------------------------------------------
+// blks2.am_demod_cf / blks2.demod_10k0a3e_cf (blks2impl/am_demod.py:42-76) as ONE block: a gr_sync_decimator by audio_decim,
+// complex in and float out, history 1 (the handle takes new items only and keeps the FIR's delay line itself).
+// ---------------------------------------------------------------------------
+class grhip_am_demod_cf_blk;
+typedef boost::shared_ptr<grhip_am_demod_cf_blk> grhip_am_demod_cf_sptr;
+class grhip_am_demod_cf_blk : public gr_sync_decimator {
+    grhip_am_demod_cf *d_h = nullptr;
+    std::vector<float> d_taps;
+    grhip_am_demod_cf_blk(int audio_decim, const std::vector<float> &audio_taps, int device)
+        : gr_sync_decimator("am_demod_cf", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(float)),
+                            audio_decim < 1 ? 1u : (unsigned)audio_decim),
+          d_taps(audio_taps)
+    {
+        grhip_detail::check(grhip_am_demod_cf_create(&d_h, audio_decim, audio_taps.data(), audio_taps.size(), device));
+    }
+    friend grhip_am_demod_cf_sptr grhip_make_am_demod_cf(int, const std::vector<float> &, int);
+public:
+    ~grhip_am_demod_cf_blk() { grhip_am_demod_cf_destroy(d_h); }
+    void set_mode(int mode) { grhip_detail::check(grhip_am_demod_cf_set_mode(d_h, mode)); }
+    int engine() const { return grhip_am_demod_cf_engine(d_h); }
+    const std::vector<float> &audio_taps() const { return d_taps; }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int produced = 0;
+        grhip_detail::check(grhip_am_demod_cf_work(d_h, noutput_items * (int)decimation(), in[0], out[0], &produced));
+        return produced;
+    }
+};
+// the chain on given taps: complex_to_mag -> add_const_ff(-1) -> fir_filter_fff(audio_decim, audio_taps)
+inline grhip_am_demod_cf_sptr grhip_make_am_demod_cf(int audio_decim, const std::vector<float> &audio_taps, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_am_demod_cf_blk(audio_decim, audio_taps, device));
+}
+// blks2.am_demod_cf(channel_rate, audio_decim, audio_pass, audio_stop)
+inline grhip_am_demod_cf_sptr gr_make_am_demod_cf(double channel_rate, int audio_decim, double audio_pass, double audio_stop,
+                                                  int device = 0)
+{
+    return grhip_make_am_demod_cf(audio_decim, grhip_optfir_low_pass_taps_f(0.5, channel_rate, audio_pass, audio_stop), device);
+}
+// blks2.demod_10k0a3e_cf(channel_rate, audio_decim): audio 5 kHz / 5.5 kHz
+inline grhip_am_demod_cf_sptr gr_make_demod_10k0a3e_cf(double channel_rate, int audio_decim, int device = 0)
+{
+    return gr_make_am_demod_cf(channel_rate, audio_decim, 5000, 5500, device);
 }

@@ -1023,6 +1023,68 @@ GRHIP_API int grhip_firdes_hilbert(unsigned ntaps, int window_type, double beta,
 GRHIP_API int grhip_firdes_low_pass(double gain, double fs, double cutoff, double transition, int window_type, double beta,
                                     float *out, size_t cap, size_t *ntaps);
 
+/* gr_remez  -- host only, no device needed
+ *   replaces gr_remez(int order, const std::vector<double> &bands, const std::vector<double> &ampl,
+ *       const std::vector<double> &error_weight, const std::string filter_type, int grid_density)
+ *   general/gr_remez.cc:98-867 (CreateDenseGrid, InitialGuess, CalcParms, ComputeA, CalcError, Search,
+ *   FreqSample, isDone, remez and the argument checks of gr_remez())
+ * The Parks-McClellan exchange in double, restated statement for statement: the same operation
+ * order, the same Pi literal, GRIDDENSITY 16, MAXITERATIONS 40.  The taps of a design are the
+ * reference's bit for bit (tests/test_optfir_cpu.py).  bands holds nbands2 edges on [0, 1] (1 is
+ * Nyquist), ampl one response per edge (nbands2 of them), weight one per band or none (nweight ==
+ * 0: all 1).  filter_type: 1 bandpass, 2 differentiator, 3 hilbert.  grid_density: 16 is the
+ * reference's default.  *ntaps receives order + 1 and out, of `cap` doubles, the taps; with cap too
+ * small (out may then be null) only *ntaps is written and the call returns GRHIP_ERANGE, as
+ * grhip_firdes_low_pass.  The arguments are checked before the size is answered.
+ * GRHIP_EINVAL where the reference throws on an argument: order < 3 (fewer than 4 taps), an odd
+ * number of band edges or none, decreasing edges, edges outside [0, 1], nweight neither 0 nor
+ * nbands2 / 2, grid_density < 16, an unknown filter_type.
+ * GRHIP_ERUNTIME where the exchange fails; grhip_last_error() is the reference's message:
+ * "gr_remez: failed to converge", "gr_remez: insufficient extremals -- cannot continue" or
+ * "gr_remez: too many extremals -- cannot continue".
+ * Stated deviations: an argument that is not finite, more than 64 bands, a grid_density above 1024
+ * and bands so narrow that the dense grid has fewer than two points are GRHIP_EINVAL; more than 4096
+ * taps are GRHIP_ERANGE (the reference computes i * (gridsize - 1) / r in int, which overflows from
+ * about 23 000 taps, and then reads outside its grid).  Every array is sized by what is written into
+ * it and no path reads or writes outside one: the reference writes one point past its grid for a
+ * hilbert transformer or differentiator whose first edge lies above the first grid step, and
+ * Grid[-1] for an empty first band; here those designs run on arrays that hold the point, with the
+ * arithmetic otherwise unchanged.  Nothing is leaked on the error paths (the reference leaks its
+ * work arrays there). */
+GRHIP_API int grhip_remez(int order, const double *bands, size_t nbands2, const double *ampl, const double *weight,
+                          size_t nweight, int filter_type, int grid_density, double *out, size_t cap, size_t *ntaps);
+
+/* optfir.low_pass / high_pass / band_pass / band_reject  -- host only, no device needed
+ *   replaces gnuradio/optfir.py:45-78, :116-156 with remezord, lporder, stopband_atten_to_dev and
+ *   passband_ripple_to_dev, :160-310
+ * Every argument a double, the taps in double as gr.remez returns them, the size query as above.
+ * Kept literally: the order int(ceil(l)) - 1 + nextra_taps (the reference's default for nextra_taps
+ * is 2); one more where high_pass or band_reject would get an even number of taps; high_pass
+ * ignoring its gain (desired_ampls = (0, 1)); the relative deviations devs[i] / mags[i]; the weights
+ * max_dev / devs[i]; max(l, l1, l2) over the two transitions of a three-band design.  The band edges
+ * are in the reference's order: (freq1, freq2), band_pass (sb1, pb1, pb2, sb2), band_reject (pb1,
+ * sb1, sb2, pb2).
+ * Stated deviations: -atten_db / 20 is a true division (Python 2 floors it for two integers; the
+ * two agree for every caller in the reference, 60 and 0.1); arguments that are not finite, fs == 0
+ * and an order estimate that is not finite are GRHIP_EINVAL; the limits of grhip_remez hold.
+ * complex_band_pass and bporder (unused in the reference) are not built.
+ * grhip_optfir_spec returns what the designer `kind` (0 low_pass, 1 high_pass, 2 band_pass, 3
+ * band_reject; freqs: its 2 or 4 band edges) hands to gr.remez: the order, 2 * *nbands band edges
+ * and amplitudes (room for 6 each) and *nbands weights (room for 3). */
+GRHIP_API int grhip_optfir_low_pass(double gain, double fs, double freq1, double freq2, double passband_ripple_db,
+                                    double stopband_atten_db, int nextra_taps, double *out, size_t cap, size_t *ntaps);
+GRHIP_API int grhip_optfir_high_pass(double gain, double fs, double freq1, double freq2, double passband_ripple_db,
+                                     double stopband_atten_db, int nextra_taps, double *out, size_t cap, size_t *ntaps);
+GRHIP_API int grhip_optfir_band_pass(double gain, double fs, double freq_sb1, double freq_pb1, double freq_pb2, double freq_sb2,
+                                     double passband_ripple_db, double stopband_atten_db, int nextra_taps, double *out,
+                                     size_t cap, size_t *ntaps);
+GRHIP_API int grhip_optfir_band_reject(double gain, double fs, double freq_pb1, double freq_sb1, double freq_sb2, double freq_pb2,
+                                       double passband_ripple_db, double stopband_atten_db, int nextra_taps, double *out,
+                                       size_t cap, size_t *ntaps);
+GRHIP_API int grhip_optfir_spec(int kind, double gain, double fs, const double *freqs, size_t nfreqs, double passband_ripple_db,
+                                double stopband_atten_db, int nextra_taps, int *order, double *bands, double *ampl,
+                                double *weight, size_t *nbands);
+
 /* ======================================================================
  * gr_hilbert_fc
  *   replaces gr_make_hilbert_fc(unsigned int ntaps)
@@ -1278,6 +1340,27 @@ GRHIP_API int grhip_complex_to_mag_squared_work(grhip_complex_to_mag_squared *h,
                                                 void *out);
 GRHIP_API int grhip_complex_to_mag_squared_work_device(grhip_complex_to_mag_squared *h, int noutput_items,
                                                        const void *d_in, void *d_out, void *stream);
+
+/* ======================================================================
+ * gr_complex_to_mag
+ *   replaces gr_make_complex_to_mag(unsigned int vlen = 1)
+ *   general/gr_complex_to_xxx.cc:143-171 (the std::abs loop)
+ * Items of vlen gr_complex in, vlen floats out, S streams back to back as above.  One form in every
+ * mode: (float)sqrt((double)re * re + (double)im * im) -- two rounded double products, one rounded
+ * add, a correctly rounded double square root, one narrowing, never contracted.  As hypotf, an
+ * infinite part gives +inf whatever the other part is.  std::abs(gr_complex) is glibc's hypotf; this
+ * form equals the hypotf of glibc 2.35 on the recorded set of tests/golden/ref_complex_to_mag.npz
+ * (normals over 60 decades, zeros, denormals, axis-aligned values, squares that overflow a float,
+ * infinities and NaNs) bit for bit, and on x86-64 it did on 20 000 000 random pairs.
+ * ====================================================================== */
+typedef struct grhip_complex_to_mag grhip_complex_to_mag;
+GRHIP_API int grhip_complex_to_mag_create(grhip_complex_to_mag **h, int vlen, int device);
+GRHIP_API void grhip_complex_to_mag_destroy(grhip_complex_to_mag *h);
+GRHIP_API int grhip_complex_to_mag_set_mode(grhip_complex_to_mag *h, int mode);
+GRHIP_API int grhip_complex_to_mag_set_streams(grhip_complex_to_mag *h, int nstreams);
+GRHIP_API int grhip_complex_to_mag_work(grhip_complex_to_mag *h, int noutput_items, const void *in, void *out);
+GRHIP_API int grhip_complex_to_mag_work_device(grhip_complex_to_mag *h, int noutput_items, const void *d_in, void *d_out,
+                                               void *stream);
 
 /* ======================================================================
  * gr_single_pole_iir_filter_ff
@@ -1820,6 +1903,48 @@ GRHIP_API int grhip_fm_demod_cf_engine(grhip_fm_demod_cf *h);
 GRHIP_API int grhip_fm_demod_cf_tile(void);
 GRHIP_API int grhip_fm_demod_cf_work(grhip_fm_demod_cf *h, int n_in, const void *in, void *out, int *produced);
 GRHIP_API int grhip_fm_demod_cf_work_device(grhip_fm_demod_cf *h, int n_in, const void *d_in, void *d_out, int *d_produced,
+                                            void *stream);
+
+/* ======================================================================
+ * blks2.am_demod_cf / blks2.demod_10k0a3e_cf  (hier block)
+ *   blks2impl/am_demod.py:42-58, :60-76:
+ *   gr_complex_to_mag -> gr_add_const_ff(-1.0) -> gr_fir_filter_fff(audio_decim, audio_taps)
+ * (the reference designs audio_taps with optfir.low_pass(0.5, channel_rate, audio_pass, audio_stop,
+ * 0.1, 60): grhip_optfir_low_pass, narrowed to float per tap.)  GRHIP_EINVAL: null taps, audio_decim
+ * outside 1 .. 65536, ntaps outside 1 .. 65536.  The handle is the hier block as the scheduler runs
+ * it, NEW ITEMS ONLY: complex in as [S][n_in] (S = 1 after create), float out,
+ *     out[j] = sum_k taps[k] v[j D - k],  v[i] = (float)(|x[i]| - 1.0f) for i >= 0, a rounded float
+ * add on grhip_complex_to_mag's magnitude, and v[i] = 0 for i < 0: the FIR's delay line starts as
+ * zeros of ITS input, it is not |0| - 1 = -1.  Per stream the device keeps the last ntaps - 1 values
+ * of v across calls; the handle keeps the stream position modulo D (one for all streams).
+ * produced(h, n_in), *produced, *d_produced, n_in == 0, the output layout (stream s from out + s *
+ * produced), overlap and set_streams are grhip_fm_demod_cf's.
+ * GRHIP_MODE_GENERIC: the three steps one after the other inside the handle, the FIR the generic-
+ * order one of grhip_fir_filter (fff): bit for bit the reference's chain; the outputs depend on the
+ * concatenated input alone, never on where the calls cut it.
+ * Every other mode: one fused kernel (engine(h) == 1) for ntaps <= max_taps() = 1025 and any
+ * audio_decim: one workgroup per stream and tile of tile() = 4096 input samples forms v of the tile
+ * and of the ntaps - 1 samples in front of it once per sample into LDS (the carried delay line where
+ * those lie in front of the call) and the decimated outputs with f32 FMAs, taps ascending: 8 + 4 / D
+ * bytes of memory traffic per input sample.  With audio_decim == 1 a lane forms outputs_per_lane()
+ * = 8 adjacent outputs from a register window, one LDS word read per 8 FMAs; other decimations take
+ * the plain step of the FM kernel (one read per FMA).  Longer filters (engine(h) == 0) run the three
+ * steps in a row.  v is the same in every mode; every output is within 1e-5 of the output's peak of
+ * the float64 FIR over the same float v (the FIR family's FAST contract).
+ * ====================================================================== */
+typedef struct grhip_am_demod_cf grhip_am_demod_cf;
+GRHIP_API int grhip_am_demod_cf_create(grhip_am_demod_cf **h, int audio_decim, const float *audio_taps, size_t ntaps,
+                                       int device);
+GRHIP_API void grhip_am_demod_cf_destroy(grhip_am_demod_cf *h);
+GRHIP_API int grhip_am_demod_cf_set_mode(grhip_am_demod_cf *h, int mode);
+GRHIP_API int grhip_am_demod_cf_set_streams(grhip_am_demod_cf *h, int nstreams);
+GRHIP_API int grhip_am_demod_cf_produced(grhip_am_demod_cf *h, int n_in);
+GRHIP_API int grhip_am_demod_cf_engine(grhip_am_demod_cf *h);
+GRHIP_API int grhip_am_demod_cf_tile(void);
+GRHIP_API int grhip_am_demod_cf_outputs_per_lane(void);
+GRHIP_API int grhip_am_demod_cf_max_taps(void);
+GRHIP_API int grhip_am_demod_cf_work(grhip_am_demod_cf *h, int n_in, const void *in, void *out, int *produced);
+GRHIP_API int grhip_am_demod_cf_work_device(grhip_am_demod_cf *h, int n_in, const void *d_in, void *d_out, int *d_produced,
                                             void *stream);
 
 /* ======================================================================
