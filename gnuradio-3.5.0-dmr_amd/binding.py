@@ -26,6 +26,7 @@ __all__ = [
     "logpwrfft_c", "logpwrfft_f", "window_blackmanharris",
     "pwr_squelch_cc", "pwr_squelch_ff", "simple_squelch_cc", "ctcss_squelch_ff",
     "agc_cc", "agc_ff", "agc2_cc", "agc2_ff",
+    "costas_loop_cc", "pll_freqdet_cf", "pll_refout_cc", "pll_carriertracking_cc",
     "iir_filter_ffd", "fm_deemph", "fm_deemph_taps", "firdes_low_pass", "fm_demod_cf", "nbfm_rx",
     "remez", "optfir_low_pass", "optfir_high_pass", "optfir_band_pass", "optfir_band_reject", "optfir_spec",
     "complex_to_mag", "am_demod_cf", "demod_10k0a3e_cf", "demod_20k0f3e_cf", "demod_200kf3e_cf",
@@ -1679,6 +1680,139 @@ class agc2_ff(_agc2):
     agc2_cc on floats, with the rate test on the magnitude of |out| - reference as the reference has it"""
     _name = "agc2_ff"
     _dtype = np.float32
+
+
+# ----------------------------------------------------------------------------
+# digital.costas_loop_cc, gr.pll_freqdet_cf, gr.pll_refout_cc, gr.pll_carriertracking_cc  (gr-digital/swig/
+# digital_costas_loop_cc.i, general/gr_pll_*.i, general/gri_control_loop.i)
+# ----------------------------------------------------------------------------
+class _control_loop(_Block):
+    """what the four carrier loops share: gri_control_loop's setters and getters under their own names, and
+    work(x), which takes streams x n_in complex items back to back.  Phase and frequency are per stream and carry
+    across calls; a setter acts at once on every stream.  A value the reference refuses with std::out_of_range
+    raises GrhipError (code -1).  work_device does not synchronise."""
+    _out = np.complex64
+
+    def history(self):
+        return 1
+
+    def set_loop_bandwidth(self, bw):
+        self._call("set_loop_bandwidth", float(bw))
+
+    def set_damping_factor(self, df):
+        self._call("set_damping_factor", float(df))
+
+    def set_alpha(self, alpha):
+        self._call("set_alpha", float(alpha))
+
+    def set_beta(self, beta):
+        self._call("set_beta", float(beta))
+
+    def set_frequency(self, freq):
+        self._call("set_frequency", float(freq))
+
+    def set_phase(self, phase):
+        self._call("set_phase", float(phase))
+
+    def get_loop_bandwidth(self):
+        return self._fn("get_loop_bandwidth")(self._h)
+
+    def get_damping_factor(self):
+        return self._fn("get_damping_factor")(self._h)
+
+    def get_alpha(self):
+        return self._fn("get_alpha")(self._h)
+
+    def get_beta(self):
+        return self._fn("get_beta")(self._h)
+
+    def _stream_float(self, name, stream):
+        v = C.c_float(0)
+        self._call(name, int(stream), C.byref(v))
+        return np.float32(v.value)
+
+    def get_frequency(self, stream=0):
+        return self._stream_float("get_frequency", stream)
+
+    def get_phase(self, stream=0):
+        return self._stream_float("get_phase", stream)
+
+    def _items(self, input_items, n_in):
+        x = np.ascontiguousarray(input_items, dtype=np.complex64).reshape(-1)
+        if n_in is None:
+            n_in = len(x) // self._streams
+        if len(x) < n_in * self._streams:
+            raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
+        return x, n_in
+
+    def work(self, input_items, n_in=None):
+        x, n_in = self._items(input_items, n_in)
+        out = np.zeros(max(n_in * self._streams, 1), dtype=self._out)
+        self._call("work", int(n_in), _ptr(x), _ptr(out))
+        return out[:n_in * self._streams]
+
+
+class _pll(_control_loop):
+    def __init__(self, loop_bw, max_freq, min_freq, device=0):
+        _Block.__init__(self)
+        self._create(float(loop_bw), float(max_freq), float(min_freq), int(device))
+
+
+class pll_freqdet_cf(_pll):
+    """gr.pll_freqdet_cf(loop_bw, max_freq, min_freq) (general/gr_pll_freqdet_cf.i): the loop's frequency in front of
+    every sample, in rad/sample.  Bit for bit the reference in every mode."""
+    _name = "pll_freqdet_cf"
+    _out = np.float32
+
+
+class pll_refout_cc(_pll):
+    """gr.pll_refout_cc(loop_bw, max_freq, min_freq) (general/gr_pll_refout_cc.i): (cos, sin) of the loop's phase in
+    front of every sample.  The state is the reference's bit for bit, the outputs within one float ulp."""
+    _name = "pll_refout_cc"
+
+
+class pll_carriertracking_cc(_pll):
+    """gr.pll_carriertracking_cc(loop_bw, max_freq, min_freq) (general/gr_pll_carriertracking_cc.i): the input mixed
+    down by the loop's phase, a lock signal, and an optional squelch on it."""
+    _name = "pll_carriertracking_cc"
+
+    def lock_detector(self, stream=0):
+        v = C.c_int(0)
+        self._call("lock_detector", int(stream), C.byref(v))
+        return bool(v.value)
+
+    def locksig(self, stream=0):
+        return self._stream_float("locksig", stream)
+
+    def squelch_enable(self, enable):
+        self._call("squelch_enable", int(bool(enable)))
+        return bool(enable)
+
+    def set_lock_threshold(self, threshold):
+        self._call("set_lock_threshold", float(threshold))
+        return float(threshold)
+
+
+class costas_loop_cc(_control_loop):
+    """digital.costas_loop_cc(loop_bw, order) (gr-digital/swig/digital_costas_loop_cc.i), order 2, 4 or 8.
+    work(x) returns the derotated samples; work(x, freq=True) returns (out, freq) with the loop's frequency behind
+    every sample.  MODE_GENERIC runs the float-rounded double sine and cosine in the NCO, every other mode a float
+    polynomial; neither is the reference's sincosf to the bit (include/grhip.h)."""
+    _name = "costas_loop_cc"
+
+    def __init__(self, loop_bw, order, device=0):
+        _Block.__init__(self)
+        self._create(float(loop_bw), int(order), int(device))
+
+    def work(self, input_items, n_in=None, freq=False):
+        x, n_in = self._items(input_items, n_in)
+        out = np.zeros(max(n_in * self._streams, 1), dtype=np.complex64)
+        f = np.zeros(max(n_in * self._streams, 1), dtype=np.float32) if freq else None
+        self._call("work", int(n_in), _ptr(x), _ptr(out), _ptr(f) if freq else C.c_void_p(0))
+        return (out[:n_in * self._streams], f[:n_in * self._streams]) if freq else out[:n_in * self._streams]
+
+    def work_device(self, n, d_in, d_out, d_freq_out=None, stream=None):
+        return self._call("work_device", int(n), _devptr(d_in), _devptr(d_out), _devptr(d_freq_out), _stream(stream))
 
 
 # ----------------------------------------------------------------------------

@@ -1,0 +1,344 @@
+// capi_carrier.hip -- C ABI of digital_costas_loop_cc, gr_pll_freqdet_cf, gr_pll_refout_cc and gr_pll_carriertracking_cc.
+//
+// Reference: general/gri_control_loop.{h,cc} (the parameters, their setters and getters), general/gr_pll_freqdet_cf.cc,
+// gr_pll_refout_cc.cc, gr_pll_carriertracking_cc.cc and gr-digital/lib/digital_costas_loop_cc.cc (work).
+//
+// A handle takes S streams back to back ([S][n_in]).  What a stream remembers is its phase, its frequency and, for
+// carrier tracking, its lock signal: one CarrierState on the device.  The loop gains and limits are kernel arguments: a
+// setter holds from the next work call, launches already queued keep theirs.
+#include <cmath>
+#include <vector>
+
+#include "carrier.h"
+#include "control_loop.h"
+#include "grhip_internal.h"
+
+using namespace grhip;
+
+namespace {
+
+enum { CARRIER_COSTAS = -1 };       // otherwise a PLL_* kind
+
+struct CarrierBlock : HandleBase {
+    int kind = PLL_FREQDET;
+    int order = 2;
+    ControlLoop cl;
+    float lock_threshold = 0.f;         // gr_pll_carriertracking_cc.cc:50
+    int squelch = 0;
+    int nstreams = 1;
+    int mode = GRHIP_MODE_FAST;
+    const DeviceTables *tabs = nullptr;
+    DevBuf d_state;
+
+    size_t out_item() const { return kind == PLL_FREQDET ? sizeof(float) : 2 * sizeof(float); }
+
+    // every stream's state = v; streams drained, under setter_mutex
+    int fill_state(const CarrierState &v)
+    {
+        int rc = d_state.reserve((size_t)nstreams * sizeof(CarrierState));
+        if (rc) return rc;
+        std::vector<CarrierState> t((size_t)nstreams, v);
+        GRHIP_HIP(hipMemcpy(d_state.p, t.data(), t.size() * sizeof(CarrierState), hipMemcpyHostToDevice));
+        return GRHIP_OK;
+    }
+
+    int init(int which, int ord, float loop_bw, float max_freq, float min_freq, int dev)
+    {
+        kind = which; order = ord;
+        if (which == CARRIER_COSTAS && ord != 2 && ord != 4 && ord != 8)
+            return fail(GRHIP_EINVAL, "costas_loop_cc: order must be 2, 4, or 8");          // digital_costas_loop_cc.cc:63-65
+        if (!ControlLoop::limits_ok(max_freq, min_freq))
+            return fail(GRHIP_EINVAL, "control loop: max_freq and min_freq must be finite and within +-%g rad/sample", (double)CL_FREQ_CAP);
+        if (!cl.init(loop_bw, max_freq, min_freq))
+            return fail(GRHIP_EINVAL, "gri_control_loop: invalid bandwidth. Must be >= 0 (and leave finite gains).");
+        mode = default_mode();
+        int rc = init_device(dev);
+        if (rc) return rc;
+        if (which != CARRIER_COSTAS && (rc = get_device_tables(dev, &tabs))) return rc;
+        return fill_state(CarrierState{0.f, 0.f, 0.f, 0.f});                                 // gri_control_loop.cc:35
+    }
+
+    int set_mode(int m)
+    {
+        if (!mode_valid(m)) return fail(GRHIP_EINVAL, "bad mode %d", m);
+        std::lock_guard<std::mutex> lk(setter_mutex);
+        mode = m;
+        return GRHIP_OK;
+    }
+
+    int set_streams(int S)
+    {
+        if (S < 1 || S > 65535) return fail(GRHIP_EINVAL, "1 .. 65535 streams");
+        int rc = bind();
+        if (rc) return rc;
+        std::lock_guard<std::mutex> lk(setter_mutex);
+        if ((rc = drain(own_stream))) return rc;
+        nstreams = S;
+        return fill_state(CarrierState{0.f, 0.f, 0.f, 0.f});
+    }
+
+    // a setter of the loop's parameters (control_loop.h): false is the reference's std::out_of_range
+    int set_param(bool (ControlLoop::*set)(float), float v, const char *what)
+    {
+        std::lock_guard<std::mutex> lk(setter_mutex);
+        if (!(cl.*set)(v)) return fail(GRHIP_EINVAL, "gri_control_loop: invalid %s", what);
+        return GRHIP_OK;
+    }
+
+    float get_param(float ControlLoop::*which)
+    {
+        std::lock_guard<std::mutex> lk(setter_mutex);
+        return cl.*which;
+    }
+
+    // one float of every stream's state = v
+    int set_state(float CarrierState::*which, float v)
+    {
+        int rc = bind();
+        if (rc) return rc;
+        std::lock_guard<std::mutex> lk(setter_mutex);
+        if ((rc = drain(own_stream))) return rc;
+        std::vector<CarrierState> t((size_t)nstreams);
+        GRHIP_HIP(hipMemcpy(t.data(), d_state.p, t.size() * sizeof(CarrierState), hipMemcpyDeviceToHost));
+        for (CarrierState &e : t) e.*which = v;
+        GRHIP_HIP(hipMemcpy(d_state.p, t.data(), t.size() * sizeof(CarrierState), hipMemcpyHostToDevice));
+        return GRHIP_OK;
+    }
+
+    int set_frequency(float f)              // gri_control_loop.cc:126-135
+    {
+        float v;
+        {
+            std::lock_guard<std::mutex> lk(setter_mutex);
+            v = cl.set_frequency(f);
+        }
+        return set_state(&CarrierState::freq, v);
+    }
+
+    int set_phase(float ph)                 // gri_control_loop.cc:137-145
+    {
+        if (!ControlLoop::phase_ok(ph)) return fail(GRHIP_EINVAL, "control loop: the phase must be finite and within +-2^20 rad");
+        return set_state(&CarrierState::phase, ControlLoop::set_phase(ph));
+    }
+
+    int get_state(int s, CarrierState *v)
+    {
+        if (s < 0 || s >= nstreams) return fail(GRHIP_EINVAL, "stream %d of %d", s, nstreams);
+        int rc = bind();
+        if (rc) return rc;
+        std::lock_guard<std::mutex> lk(setter_mutex);
+        if ((rc = drain(own_stream))) return rc;
+        GRHIP_HIP(hipMemcpy(v, d_state.as<CarrierState>() + s, sizeof(CarrierState), hipMemcpyDeviceToHost));
+        return GRHIP_OK;
+    }
+
+    int get_float(int s, float CarrierState::*which, float *v)
+    {
+        if (!v) return fail(GRHIP_EINVAL, "null argument");
+        CarrierState t;
+        int rc = get_state(s, &t);
+        if (!rc) *v = t.*which;
+        return rc;
+    }
+
+    int lock_detector(int s, int *locked)   // gr_pll_carriertracking_cc.cc:74-78
+    {
+        if (!locked) return fail(GRHIP_EINVAL, "null argument");
+        CarrierState t;
+        int rc = get_state(s, &t);
+        if (rc) return rc;
+        std::lock_guard<std::mutex> lk(setter_mutex);
+        *locked = fabsf(t.locksig) > lock_threshold ? 1 : 0;
+        return GRHIP_OK;
+    }
+
+    int squelch_enable(int on)              // gr_pll_carriertracking_cc.cc:80-84
+    {
+        std::lock_guard<std::mutex> lk(setter_mutex);
+        squelch = on ? 1 : 0;
+        return GRHIP_OK;
+    }
+
+    int set_lock_threshold(float thr)       // :86-90
+    {
+        std::lock_guard<std::mutex> lk(setter_mutex);
+        lock_threshold = thr;
+        return GRHIP_OK;
+    }
+
+    int work_device(int n_in, const void *d_in, void *d_out, void *d_freq, void *stream)
+    {
+        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
+        if (n_in == 0) return GRHIP_OK;
+        if (!d_in || !d_out) return fail(GRHIP_EINVAL, "null buffer");
+        if (((uintptr_t)d_in & 7) || ((uintptr_t)d_out & (out_item() - 1)) || ((uintptr_t)d_freq & 3))
+            return fail(GRHIP_EINVAL, "items not naturally aligned");
+        const char *a = (const char *)d_in, *b = (const char *)d_out, *c = (const char *)d_freq;
+        const size_t items = (size_t)nstreams * (size_t)n_in;
+        const size_t in_bytes = items * 8, out_bytes = items * out_item(), f_bytes = items * 4;
+        if (a < b + out_bytes && b < a + in_bytes) return fail(GRHIP_EINVAL, "carrier loop: the output may not overlap the input");
+        if (c && ((a < c + f_bytes && c < a + in_bytes) || (b < c + f_bytes && c < b + out_bytes)))
+            return fail(GRHIP_EINVAL, "carrier loop: the frequency output may not overlap the other buffers");
+        int rc = bind();
+        if (rc) return rc;
+        hipStream_t st = pick(stream);
+        std::lock_guard<std::mutex> lk(setter_mutex);
+        CarrierLaunch l;
+        l.in = (const float2 *)d_in; l.out = d_out; l.freq_out = (float *)d_freq; l.n = n_in; l.nstreams = nstreams;
+        l.p = CarrierParams{cl.alpha, cl.beta, cl.max_freq, cl.min_freq, lock_threshold, squelch};
+        l.state = d_state.as<CarrierState>();
+        if (kind == CARRIER_COSTAS) return costas_launch(order, mode_fast(mode), l, st);
+        return pll_launch(kind, l, tabs->atan_tab, st);
+    }
+
+    int work(int n_in, const void *in, void *out, void *freq_out)
+    {
+        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
+        if (n_in == 0) return GRHIP_OK;
+        if (!in || !out) return fail(GRHIP_EINVAL, "null buffer");
+        int rc = bind();
+        if (rc) return rc;
+        const size_t items = (size_t)nstreams * (size_t)n_in;
+        const size_t in_bytes = items * 8, out_bytes = items * out_item();
+        const size_t f_off = (out_bytes + 15) & ~(size_t)15, f_bytes = freq_out ? items * 4 : 0;
+        const long long r = host_call(in, in_bytes, in_bytes + 16, f_off + f_bytes + 16, out, out_item(), [&](void *d_in, void *d_out, hipStream_t st) {
+            const int e = work_device(n_in, d_in, d_out, freq_out ? (char *)d_out + f_off : nullptr, st);
+            return e ? (long long)e : (long long)items;
+        });
+        if (r < 0) return (int)r;
+        if (freq_out) {     // host_call has synchronised; the staged frequencies are still there
+            GRHIP_D2H(this, freq_out, (char *)stage_out.p + f_off, f_bytes, own_stream);
+            GRHIP_HIP(hipStreamSynchronize(own_stream));
+        }
+        return GRHIP_OK;
+    }
+};
+
+}  // namespace
+
+struct grhip_costas_loop_cc : CarrierBlock {};
+struct grhip_pll_freqdet_cf : CarrierBlock {};
+struct grhip_pll_refout_cc : CarrierBlock {};
+struct grhip_pll_carriertracking_cc : CarrierBlock {};
+
+extern "C" {
+
+#define GRHIP_CL_NULL(h) if (!(h)) return fail(GRHIP_EINVAL, "null handle")
+#define GRHIP_CL_GET(NAME, ENTRY, FIELD)                                                                              \
+    float grhip_##NAME##_##ENTRY(grhip_##NAME *h)                                                                     \
+    {                                                                                                                 \
+        if (!h) return (float)fail(GRHIP_EINVAL, "null handle");                                                      \
+        return h->get_param(&ControlLoop::FIELD);                                                                     \
+    }
+
+// what the four blocks share: gri_control_loop.h:99-200
+#define GRHIP_CL_COMMON(NAME)                                                                                         \
+    void grhip_##NAME##_destroy(grhip_##NAME *h) { destroy_handle(h); }                                               \
+    int grhip_##NAME##_set_mode(grhip_##NAME *h, int mode) { GRHIP_CL_NULL(h); return h->set_mode(mode); }            \
+    int grhip_##NAME##_set_streams(grhip_##NAME *h, int nstreams) { GRHIP_CL_NULL(h); return h->set_streams(nstreams); } \
+    int grhip_##NAME##_set_loop_bandwidth(grhip_##NAME *h, float bw)                                                  \
+    {                                                                                                                 \
+        GRHIP_CL_NULL(h);                                                                                             \
+        return h->set_param(&ControlLoop::set_loop_bandwidth, bw, "bandwidth. Must be >= 0 (and leave finite gains).");  \
+    }                                                                                                                 \
+    int grhip_##NAME##_set_damping_factor(grhip_##NAME *h, float df)                                                  \
+    {                                                                                                                 \
+        GRHIP_CL_NULL(h);                                                                                             \
+        return h->set_param(&ControlLoop::set_damping_factor, df, "damping factor. Must be in [0,1].");               \
+    }                                                                                                                 \
+    int grhip_##NAME##_set_alpha(grhip_##NAME *h, float alpha)                                                        \
+    {                                                                                                                 \
+        GRHIP_CL_NULL(h);                                                                                             \
+        return h->set_param(&ControlLoop::set_alpha, alpha, "alpha. Must be in [0,1].");                              \
+    }                                                                                                                 \
+    int grhip_##NAME##_set_beta(grhip_##NAME *h, float beta)                                                          \
+    {                                                                                                                 \
+        GRHIP_CL_NULL(h);                                                                                             \
+        return h->set_param(&ControlLoop::set_beta, beta, "beta. Must be in [0,1].");                                 \
+    }                                                                                                                 \
+    int grhip_##NAME##_set_frequency(grhip_##NAME *h, float freq) { GRHIP_CL_NULL(h); return h->set_frequency(freq); } \
+    int grhip_##NAME##_set_phase(grhip_##NAME *h, float phase) { GRHIP_CL_NULL(h); return h->set_phase(phase); }      \
+    GRHIP_CL_GET(NAME, get_loop_bandwidth, loop_bw)                                                                   \
+    GRHIP_CL_GET(NAME, get_damping_factor, damping)                                                                   \
+    GRHIP_CL_GET(NAME, get_alpha, alpha)                                                                              \
+    GRHIP_CL_GET(NAME, get_beta, beta)                                                                                \
+    int grhip_##NAME##_get_frequency(grhip_##NAME *h, int s, float *freq)                                             \
+    {                                                                                                                 \
+        GRHIP_CL_NULL(h);                                                                                             \
+        return h->get_float(s, &CarrierState::freq, freq);                                                            \
+    }                                                                                                                 \
+    int grhip_##NAME##_get_phase(grhip_##NAME *h, int s, float *phase)                                                \
+    {                                                                                                                 \
+        GRHIP_CL_NULL(h);                                                                                             \
+        return h->get_float(s, &CarrierState::phase, phase);                                                          \
+    }
+
+// gr_pll_freqdet_cf.h:33-34 and its two siblings
+#define GRHIP_CL_PLL(NAME, KIND)                                                                                      \
+    int grhip_##NAME##_create(grhip_##NAME **h, float loop_bw, float max_freq, float min_freq, int device)            \
+    {                                                                                                                 \
+        if (!h) return fail(GRHIP_EINVAL, "null argument");                                                           \
+        return make_handle(h, [&](grhip_##NAME *b) { return b->init(KIND, 0, loop_bw, max_freq, min_freq, device); }); \
+    }                                                                                                                 \
+    int grhip_##NAME##_work(grhip_##NAME *h, int n_in, const void *in, void *out)                                     \
+    {                                                                                                                 \
+        GRHIP_CL_NULL(h);                                                                                             \
+        return h->work(n_in, in, out, nullptr);                                                                       \
+    }                                                                                                                 \
+    int grhip_##NAME##_work_device(grhip_##NAME *h, int n_in, const void *d_in, void *d_out, void *stream)            \
+    {                                                                                                                 \
+        GRHIP_CL_NULL(h);                                                                                             \
+        return h->work_device(n_in, d_in, d_out, nullptr, stream);                                                    \
+    }                                                                                                                 \
+    GRHIP_CL_COMMON(NAME)
+
+GRHIP_CL_PLL(pll_freqdet_cf, PLL_FREQDET)
+GRHIP_CL_PLL(pll_refout_cc, PLL_REFOUT)
+GRHIP_CL_PLL(pll_carriertracking_cc, PLL_CARRIERTRACKING)
+
+// gr_pll_carriertracking_cc.h:84-90
+int grhip_pll_carriertracking_cc_locksig(grhip_pll_carriertracking_cc *h, int s, float *locksig)
+{
+    GRHIP_CL_NULL(h);
+    return h->get_float(s, &CarrierState::locksig, locksig);
+}
+int grhip_pll_carriertracking_cc_lock_detector(grhip_pll_carriertracking_cc *h, int s, int *locked)
+{
+    GRHIP_CL_NULL(h);
+    return h->lock_detector(s, locked);
+}
+int grhip_pll_carriertracking_cc_squelch_enable(grhip_pll_carriertracking_cc *h, int enable)
+{
+    GRHIP_CL_NULL(h);
+    return h->squelch_enable(enable);
+}
+int grhip_pll_carriertracking_cc_set_lock_threshold(grhip_pll_carriertracking_cc *h, float threshold)
+{
+    GRHIP_CL_NULL(h);
+    return h->set_lock_threshold(threshold);
+}
+
+// digital_costas_loop_cc.h:61-63; the loop's limits are +-1.0 (digital_costas_loop_cc.cc:46)
+int grhip_costas_loop_cc_create(grhip_costas_loop_cc **h, float loop_bw, int order, int device)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null argument");
+    return make_handle(h, [&](grhip_costas_loop_cc *b) { return b->init(CARRIER_COSTAS, order, loop_bw, 1.0f, -1.0f, device); });
+}
+int grhip_costas_loop_cc_work(grhip_costas_loop_cc *h, int n_in, const void *in, void *out, void *freq_out)
+{
+    GRHIP_CL_NULL(h);
+    return h->work(n_in, in, out, freq_out);
+}
+int grhip_costas_loop_cc_work_device(grhip_costas_loop_cc *h, int n_in, const void *d_in, void *d_out, void *d_freq_out, void *stream)
+{
+    GRHIP_CL_NULL(h);
+    return h->work_device(n_in, d_in, d_out, d_freq_out, stream);
+}
+GRHIP_CL_COMMON(costas_loop_cc)
+
+#undef GRHIP_CL_PLL
+#undef GRHIP_CL_COMMON
+#undef GRHIP_CL_GET
+#undef GRHIP_CL_NULL
+
+}  // extern "C"

@@ -60,14 +60,20 @@ class gr_io_signature {
     std::vector<int> d_sizeof;
 public:
     gr_io_signature(int mn, int mx, int size) : d_min(mn), d_max(mx), d_sizeof(1, size) {}
+    gr_io_signature(int mn, int mx, int size1, int size2) : d_min(mn), d_max(mx), d_sizeof{size1, size2} {}
     int min_streams() const { return d_min; }
     int max_streams() const { return d_max; }
-    int sizeof_stream_item(int) const { return d_sizeof[0]; }
+    // gr_io_signature.cc:76-83: the last size stands for every further stream
+    int sizeof_stream_item(int i) const { return d_sizeof[std::min((size_t)std::max(i, 0), d_sizeof.size() - 1)]; }
 };
 typedef boost::shared_ptr<gr_io_signature> gr_io_signature_sptr;
 inline gr_io_signature_sptr gr_make_io_signature(int mn, int mx, int size)
 {
     return gr_io_signature_sptr(new gr_io_signature(mn, mx, size));
+}
+inline gr_io_signature_sptr gr_make_io_signature2(int mn, int mx, int size1, int size2)
+{
+    return gr_io_signature_sptr(new gr_io_signature(mn, mx, size1, size2));
 }
 
 class gr_block {

@@ -32,6 +32,9 @@
 //                                            <- the factories of the same names (general/gr_pwr_squelch_cc.h,
 //                                               general/gr_pwr_squelch_ff.h, general/gr_simple_squelch_cc.h)
 //   gr_make_ctcss_squelch_ff                 <- gr_make_ctcss_squelch_ff (general/gr_ctcss_squelch_ff.h)
+//   digital_make_costas_loop_cc, gr_make_pll_freqdet_cf / _refout_cc / _carriertracking_cc
+//                                            <- the factories of the same names (gr-digital/include/
+//                                               digital_costas_loop_cc.h, general/gr_pll_*.h)
 //   gr_make_agc_cc / _ff, gr_make_agc2_cc / _ff
 //                                            <- the factories of the same names (general/gr_agc_cc.h, gr_agc_ff.h,
 //                                               gr_agc2_cc.h, gr_agc2_ff.h)
@@ -1619,6 +1622,119 @@ GRHIP_AGC2_BLK(agc2_ff, float)
 #undef GRHIP_AGC_BLK
 #undef GRHIP_AGC2_BLK
 #undef GRHIP_AGC_BLK_COMMON
+
+// ---------------------------------------------------------------------------
+// digital_costas_loop_cc (loop_bw, order; 1 input, 1..2 outputs: gr-digital/include/digital_costas_loop_cc.h:61-112) and
+// gr_pll_freqdet_cf, gr_pll_refout_cc, gr_pll_carriertracking_cc (loop_bw, max_freq, min_freq;
+// general/gr_pll_freqdet_cf.h:33-34 and siblings): gr_sync_blocks, history 1, with gri_control_loop's setters and
+// getters under their names (general/gri_control_loop.h:99-200).  Phase and frequency carry across work calls; the
+// setters act at once.  A value the reference refuses (std::out_of_range, std::invalid_argument) throws
+// std::invalid_argument here.
+// ---------------------------------------------------------------------------
+#define GRHIP_LOOP_BLK_COMMON(NAME)                                                                                      \
+    public:                                                                                                              \
+        ~grhip_##NAME##_blk() { grhip_##NAME##_destroy(d_h); }                                                           \
+        void set_mode(int mode) { grhip_detail::check(grhip_##NAME##_set_mode(d_h, mode)); }                             \
+        void set_loop_bandwidth(float bw) { grhip_detail::check(grhip_##NAME##_set_loop_bandwidth(d_h, bw)); }           \
+        void set_damping_factor(float df) { grhip_detail::check(grhip_##NAME##_set_damping_factor(d_h, df)); }           \
+        void set_alpha(float alpha) { grhip_detail::check(grhip_##NAME##_set_alpha(d_h, alpha)); }                       \
+        void set_beta(float beta) { grhip_detail::check(grhip_##NAME##_set_beta(d_h, beta)); }                           \
+        void set_frequency(float freq) { grhip_detail::check(grhip_##NAME##_set_frequency(d_h, freq)); }                 \
+        void set_phase(float phase) { grhip_detail::check(grhip_##NAME##_set_phase(d_h, phase)); }                       \
+        float get_loop_bandwidth() const { return grhip_##NAME##_get_loop_bandwidth(d_h); }                              \
+        float get_damping_factor() const { return grhip_##NAME##_get_damping_factor(d_h); }                              \
+        float get_alpha() const { return grhip_##NAME##_get_alpha(d_h); }                                                \
+        float get_beta() const { return grhip_##NAME##_get_beta(d_h); }                                                  \
+        float get_frequency() const                                                                                      \
+        {                                                                                                                \
+            float v = 0.f;                                                                                               \
+            grhip_detail::check(grhip_##NAME##_get_frequency(d_h, 0, &v));                                               \
+            return v;                                                                                                    \
+        }                                                                                                                \
+        float get_phase() const                                                                                          \
+        {                                                                                                                \
+            float v = 0.f;                                                                                               \
+            grhip_detail::check(grhip_##NAME##_get_phase(d_h, 0, &v));                                                   \
+            return v;                                                                                                    \
+        }
+
+#define GRHIP_PLL_BLK(NAME, OUT_ITEM)                                                                                    \
+    class grhip_##NAME##_blk;                                                                                            \
+    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                   \
+    class grhip_##NAME##_blk : public gr_sync_block {                                                                    \
+    protected:                                                                                                           \
+        grhip_##NAME *d_h = nullptr;                                                                                     \
+        grhip_##NAME##_blk(float loop_bw, float max_freq, float min_freq, int device)                                    \
+            : gr_sync_block(#NAME, gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(OUT_ITEM))) \
+        {                                                                                                                \
+            grhip_detail::check(grhip_##NAME##_create(&d_h, loop_bw, max_freq, min_freq, device));                       \
+        }                                                                                                                \
+        friend grhip_##NAME##_sptr gr_make_##NAME(float, float, float, int);                                             \
+    GRHIP_LOOP_BLK_COMMON(NAME)                                                                                          \
+        int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override                    \
+        {                                                                                                                \
+            grhip_detail::check(grhip_##NAME##_work(d_h, noutput_items, in[0], out[0]));                                 \
+            return noutput_items;                                                                                        \
+        }
+
+GRHIP_PLL_BLK(pll_freqdet_cf, float)
+};
+GRHIP_PLL_BLK(pll_refout_cc, gr_complex)
+};
+GRHIP_PLL_BLK(pll_carriertracking_cc, gr_complex)
+    // general/gr_pll_carriertracking_cc.h:84-90
+    bool lock_detector()
+    {
+        int locked = 0;
+        grhip_detail::check(grhip_pll_carriertracking_cc_lock_detector(d_h, 0, &locked));
+        return locked != 0;
+    }
+    bool squelch_enable(bool enable)
+    {
+        grhip_detail::check(grhip_pll_carriertracking_cc_squelch_enable(d_h, enable ? 1 : 0));
+        return enable;
+    }
+    float set_lock_threshold(float threshold)
+    {
+        grhip_detail::check(grhip_pll_carriertracking_cc_set_lock_threshold(d_h, threshold));
+        return threshold;
+    }
+};
+#define GRHIP_PLL_MAKE(NAME)                                                                                             \
+    inline grhip_##NAME##_sptr gr_make_##NAME(float loop_bw, float max_freq, float min_freq, int device = 0)             \
+    {                                                                                                                    \
+        return gnuradio::get_initial_sptr(new grhip_##NAME##_blk(loop_bw, max_freq, min_freq, device));                  \
+    }
+GRHIP_PLL_MAKE(pll_freqdet_cf)
+GRHIP_PLL_MAKE(pll_refout_cc)
+GRHIP_PLL_MAKE(pll_carriertracking_cc)
+#undef GRHIP_PLL_MAKE
+#undef GRHIP_PLL_BLK
+
+class grhip_costas_loop_cc_blk;
+typedef boost::shared_ptr<grhip_costas_loop_cc_blk> grhip_costas_loop_cc_sptr;
+class grhip_costas_loop_cc_blk : public gr_sync_block {
+    grhip_costas_loop_cc *d_h = nullptr;
+    grhip_costas_loop_cc_blk(float loop_bw, int order, int device)
+        : gr_sync_block("costas_loop_cc", gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                        gr_make_io_signature2(1, 2, sizeof(gr_complex), sizeof(float)))     // digital_costas_loop_cc.cc:43-45
+    {
+        grhip_detail::check(grhip_costas_loop_cc_create(&d_h, loop_bw, order, device));
+    }
+    friend grhip_costas_loop_cc_sptr digital_make_costas_loop_cc(float, int, int);
+GRHIP_LOOP_BLK_COMMON(costas_loop_cc)
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        // the second output is optional (digital_costas_loop_cc.cc:119)
+        grhip_detail::check(grhip_costas_loop_cc_work(d_h, noutput_items, in[0], out[0], out.size() >= 2 ? out[1] : nullptr));
+        return noutput_items;
+    }
+};
+inline grhip_costas_loop_cc_sptr digital_make_costas_loop_cc(float loop_bw, int order, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_costas_loop_cc_blk(loop_bw, order, device));
+}
+#undef GRHIP_LOOP_BLK_COMMON
 
 // ---------------------------------------------------------------------------
 // gr_iir_filter_ffd (fftaps, fbtaps in double; filter/gr_iir_filter_ffd.h:62-85): a gr_sync_block, history 1, float in

@@ -1801,6 +1801,169 @@ GRHIP_API int grhip_agc2_ff_work_device(grhip_agc2_ff *h, int n_in, const void *
 GRHIP_API int grhip_agc_chunk(void);
 
 /* ======================================================================
+ * The carrier loops: the four blocks built on gri_control_loop (general/gri_control_loop.{h,cc}).  A
+ * handle takes S streams back to back as the gain loops do ([S][n_in], S = 1 after create; stream s
+ * at s * n_in items of every buffer; buffers may not overlap; work / work_device return GRHIP_OK,
+ * n_in == 0 is a successful no-op, work_device does not synchronise).  Per stream the device holds
+ * d_phase and d_freq (and carrier tracking's d_locksig), all float, zero after create and after
+ * set_streams, carried across calls.  Per sample every block forms an error from the sample and the
+ * phase, then
+ *     freq += beta * error;  phase = phase + freq + alpha * error          (advance_loop, :56-61)
+ *     while (phase > 2 pi) phase -= 2 pi;  while (phase < -2 pi) phase += 2 pi  (phase_wrap, :64-71:
+ *         the comparison against the double (2.0f*M_PI), the subtraction in double, narrowed)
+ *     if (freq > max_freq) freq = max_freq; else if (freq < min_freq) freq = min_freq  (:73-80)
+ * with every float operation rounded once.  One wavefront per stream walks this in order.
+ * The setters are gri_control_loop's and act at once on every stream (they hold from the next work
+ * call); where the reference throws std::out_of_range they return GRHIP_EINVAL and change nothing:
+ *   set_loop_bandwidth   :86-95    bw < 0 is refused; damping stays, the gains are recomputed
+ *   set_damping_factor   :97-106   outside [0, 1] is refused; the gains are recomputed
+ *   set_alpha, set_beta  :108-124  outside [0, 1] is refused
+ *   set_frequency        :126-135  freq > max_freq stores MIN_freq, freq < min_freq stores MAX_freq
+ *   set_phase            :137-145  stored after the reference's wrap loops
+ * The gains are :49-54: float denom = 1.0 + 2.0 * damping * bw + bw * bw (a double expression around
+ * the float product bw * bw), alpha = (4 * damping * bw) / denom and beta = (4 * bw * bw) / denom in
+ * float; damping starts as sqrtf(2.0f) / 2.0f (:38).  get_loop_bandwidth, get_damping_factor,
+ * get_alpha and get_beta return the value (:153-175); get_frequency and get_phase (:177-187) read
+ * one stream's and wait for the handle's queued work.
+ * Deviations, all so that the walk ends for every argument (the reference's phase_wrap does not end
+ * once phase - 2 pi rounds back to phase):
+ *   * create refuses max_freq / min_freq that are not finite or above 1024 rad/sample in magnitude;
+ *   * a bandwidth or damping factor whose gains come out not finite (bw = NaN, bw above 9e18) is
+ *     refused, and so is a NaN alpha or beta, which passes the reference's comparisons;
+ *   * set_phase refuses values that are not finite or above 2^20 in magnitude;
+ *   * samples must be finite.  A NaN goes through the arithmetic; where the reference then reads
+ *     outside its arctangent table, the device clamps the index.  The kernels terminate and stay in
+ *     bounds for every bit pattern (csrc/carrier.hip states why).
+ * GRHIP_EINVAL: the above, S < 1, n_in < 0, a null pointer, overlapping buffers.
+ * set_mode: the three PLLs run one engine in every mode; costas_loop_cc see below.
+ *
+ * gr_pll_freqdet_cf
+ *   replaces gr_make_pll_freqdet_cf(float loop_bw, float max_freq, float min_freq)
+ *   general/gr_pll_freqdet_cf.cc:69-90 (work), :50-67 (mod_2pi, phase_detector)
+ * Complex in, float out: out = d_freq BEFORE the sample's update (:81); error =
+ * mod_2pi(gr_fast_atan2f(im, re) - phase), mod_2pi comparing against the double M_PI and adding
+ * -+(2.0f*M_PI) in double.  Output and state are the reference's bit for bit in every mode.
+ * ====================================================================== */
+typedef struct grhip_pll_freqdet_cf grhip_pll_freqdet_cf;
+GRHIP_API int grhip_pll_freqdet_cf_create(grhip_pll_freqdet_cf **h, float loop_bw, float max_freq, float min_freq, int device);
+GRHIP_API void grhip_pll_freqdet_cf_destroy(grhip_pll_freqdet_cf *h);
+GRHIP_API int grhip_pll_freqdet_cf_set_mode(grhip_pll_freqdet_cf *h, int mode);
+GRHIP_API int grhip_pll_freqdet_cf_set_streams(grhip_pll_freqdet_cf *h, int nstreams);
+GRHIP_API int grhip_pll_freqdet_cf_set_loop_bandwidth(grhip_pll_freqdet_cf *h, float bw);
+GRHIP_API int grhip_pll_freqdet_cf_set_damping_factor(grhip_pll_freqdet_cf *h, float df);
+GRHIP_API int grhip_pll_freqdet_cf_set_alpha(grhip_pll_freqdet_cf *h, float alpha);
+GRHIP_API int grhip_pll_freqdet_cf_set_beta(grhip_pll_freqdet_cf *h, float beta);
+GRHIP_API int grhip_pll_freqdet_cf_set_frequency(grhip_pll_freqdet_cf *h, float freq);
+GRHIP_API int grhip_pll_freqdet_cf_set_phase(grhip_pll_freqdet_cf *h, float phase);
+GRHIP_API float grhip_pll_freqdet_cf_get_loop_bandwidth(grhip_pll_freqdet_cf *h);
+GRHIP_API float grhip_pll_freqdet_cf_get_damping_factor(grhip_pll_freqdet_cf *h);
+GRHIP_API float grhip_pll_freqdet_cf_get_alpha(grhip_pll_freqdet_cf *h);
+GRHIP_API float grhip_pll_freqdet_cf_get_beta(grhip_pll_freqdet_cf *h);
+GRHIP_API int grhip_pll_freqdet_cf_get_frequency(grhip_pll_freqdet_cf *h, int s, float *freq);
+GRHIP_API int grhip_pll_freqdet_cf_get_phase(grhip_pll_freqdet_cf *h, int s, float *phase);
+GRHIP_API int grhip_pll_freqdet_cf_work(grhip_pll_freqdet_cf *h, int n_in, const void *in, void *out);
+GRHIP_API int grhip_pll_freqdet_cf_work_device(grhip_pll_freqdet_cf *h, int n_in, const void *d_in, void *d_out, void *stream);
+
+/* gr_pll_refout_cc
+ *   replaces gr_make_pll_refout_cc(float loop_bw, float max_freq, float min_freq)
+ *   general/gr_pll_refout_cc.cc:70-93 (work)
+ * Complex in, complex out: out = (cos, sin) of the phase BEFORE the update (:83-84), the same error
+ * and loop.  The state is the reference's bit for bit.  Sine and cosine are (float)sin((double)phase)
+ * and (float)cos((double)phase) where the reference calls sincosf: within one float ulp of it. */
+typedef struct grhip_pll_refout_cc grhip_pll_refout_cc;
+GRHIP_API int grhip_pll_refout_cc_create(grhip_pll_refout_cc **h, float loop_bw, float max_freq, float min_freq, int device);
+GRHIP_API void grhip_pll_refout_cc_destroy(grhip_pll_refout_cc *h);
+GRHIP_API int grhip_pll_refout_cc_set_mode(grhip_pll_refout_cc *h, int mode);
+GRHIP_API int grhip_pll_refout_cc_set_streams(grhip_pll_refout_cc *h, int nstreams);
+GRHIP_API int grhip_pll_refout_cc_set_loop_bandwidth(grhip_pll_refout_cc *h, float bw);
+GRHIP_API int grhip_pll_refout_cc_set_damping_factor(grhip_pll_refout_cc *h, float df);
+GRHIP_API int grhip_pll_refout_cc_set_alpha(grhip_pll_refout_cc *h, float alpha);
+GRHIP_API int grhip_pll_refout_cc_set_beta(grhip_pll_refout_cc *h, float beta);
+GRHIP_API int grhip_pll_refout_cc_set_frequency(grhip_pll_refout_cc *h, float freq);
+GRHIP_API int grhip_pll_refout_cc_set_phase(grhip_pll_refout_cc *h, float phase);
+GRHIP_API float grhip_pll_refout_cc_get_loop_bandwidth(grhip_pll_refout_cc *h);
+GRHIP_API float grhip_pll_refout_cc_get_damping_factor(grhip_pll_refout_cc *h);
+GRHIP_API float grhip_pll_refout_cc_get_alpha(grhip_pll_refout_cc *h);
+GRHIP_API float grhip_pll_refout_cc_get_beta(grhip_pll_refout_cc *h);
+GRHIP_API int grhip_pll_refout_cc_get_frequency(grhip_pll_refout_cc *h, int s, float *freq);
+GRHIP_API int grhip_pll_refout_cc_get_phase(grhip_pll_refout_cc *h, int s, float *phase);
+GRHIP_API int grhip_pll_refout_cc_work(grhip_pll_refout_cc *h, int n_in, const void *in, void *out);
+GRHIP_API int grhip_pll_refout_cc_work_device(grhip_pll_refout_cc *h, int n_in, const void *d_in, void *d_out, void *stream);
+
+/* gr_pll_carriertracking_cc
+ *   replaces gr_make_pll_carriertracking_cc(float loop_bw, float max_freq, float min_freq)
+ *   general/gr_pll_carriertracking_cc.cc:92-120 (work), :74-90 (lock_detector, squelch_enable,
+ *   set_lock_threshold)
+ * Complex in, complex out: out = in * (cos, -sin) of the phase before the update (:104-105), the same
+ * error and loop (state bit for bit), then locksig = locksig * (1.0 - alpha) + alpha * (re * cos +
+ * im * sin) in the reference's float/double mix (:113-114).  With the squelch enabled, output n is
+ * zero unless fabsf(locksig) > threshold AFTER sample n's update (:116-117).  Sine and cosine as in
+ * pll_refout_cc, so outputs and lock signal follow the reference to a few ulps, not
+ * bit for bit.  locksig(h, s, &v) and lock_detector(h, s, &locked) read one stream's; squelch_enable
+ * and set_lock_threshold (both start as 0) act on every stream. */
+typedef struct grhip_pll_carriertracking_cc grhip_pll_carriertracking_cc;
+GRHIP_API int grhip_pll_carriertracking_cc_create(grhip_pll_carriertracking_cc **h, float loop_bw, float max_freq, float min_freq, int device);
+GRHIP_API void grhip_pll_carriertracking_cc_destroy(grhip_pll_carriertracking_cc *h);
+GRHIP_API int grhip_pll_carriertracking_cc_set_mode(grhip_pll_carriertracking_cc *h, int mode);
+GRHIP_API int grhip_pll_carriertracking_cc_set_streams(grhip_pll_carriertracking_cc *h, int nstreams);
+GRHIP_API int grhip_pll_carriertracking_cc_set_loop_bandwidth(grhip_pll_carriertracking_cc *h, float bw);
+GRHIP_API int grhip_pll_carriertracking_cc_set_damping_factor(grhip_pll_carriertracking_cc *h, float df);
+GRHIP_API int grhip_pll_carriertracking_cc_set_alpha(grhip_pll_carriertracking_cc *h, float alpha);
+GRHIP_API int grhip_pll_carriertracking_cc_set_beta(grhip_pll_carriertracking_cc *h, float beta);
+GRHIP_API int grhip_pll_carriertracking_cc_set_frequency(grhip_pll_carriertracking_cc *h, float freq);
+GRHIP_API int grhip_pll_carriertracking_cc_set_phase(grhip_pll_carriertracking_cc *h, float phase);
+GRHIP_API float grhip_pll_carriertracking_cc_get_loop_bandwidth(grhip_pll_carriertracking_cc *h);
+GRHIP_API float grhip_pll_carriertracking_cc_get_damping_factor(grhip_pll_carriertracking_cc *h);
+GRHIP_API float grhip_pll_carriertracking_cc_get_alpha(grhip_pll_carriertracking_cc *h);
+GRHIP_API float grhip_pll_carriertracking_cc_get_beta(grhip_pll_carriertracking_cc *h);
+GRHIP_API int grhip_pll_carriertracking_cc_get_frequency(grhip_pll_carriertracking_cc *h, int s, float *freq);
+GRHIP_API int grhip_pll_carriertracking_cc_get_phase(grhip_pll_carriertracking_cc *h, int s, float *phase);
+GRHIP_API int grhip_pll_carriertracking_cc_work(grhip_pll_carriertracking_cc *h, int n_in, const void *in, void *out);
+GRHIP_API int grhip_pll_carriertracking_cc_work_device(grhip_pll_carriertracking_cc *h, int n_in, const void *d_in, void *d_out, void *stream);
+GRHIP_API int grhip_pll_carriertracking_cc_locksig(grhip_pll_carriertracking_cc *h, int s, float *locksig);
+GRHIP_API int grhip_pll_carriertracking_cc_lock_detector(grhip_pll_carriertracking_cc *h, int s, int *locked);
+GRHIP_API int grhip_pll_carriertracking_cc_squelch_enable(grhip_pll_carriertracking_cc *h, int enable);
+GRHIP_API int grhip_pll_carriertracking_cc_set_lock_threshold(grhip_pll_carriertracking_cc *h, float threshold);
+
+/* digital_costas_loop_cc
+ *   replaces digital_make_costas_loop_cc(float loop_bw, int order)
+ *   gr-digital/lib/digital_costas_loop_cc.cc:110-153 (work), :69-108 (the detectors), :41-67
+ * Complex in, complex out and, optionally, float out.  Per sample: nco = gr_expj(-phase); out = in *
+ * nco (four products, a difference and a sum); error = the detector of `order` on out (order 2:
+ * re * im in float; orders 4 and 8 in double, narrowed once, K = (float)(sqrt(2.0) - 1));
+ * error = gr_branchless_clip(error, 1.0); then the loop above with max_freq = 1.0 and min_freq =
+ * -1.0 (:46).  freq_out, where given, is d_freq AFTER the update (:137); out is the same with and
+ * without it.  An order other than 2, 4 or 8 is refused with GRHIP_EINVAL (the reference throws
+ * std::invalid_argument).
+ * The NCO sits inside the loop, so the result depends on the sine and cosine to the bit, and the
+ * reference's sincosf is not reproduced.  GRHIP_MODE_GENERIC: sine and cosine are
+ * (float)sin((double)-phase) and (float)cos((double)-phase), everything else as the reference writes
+ * it.  Every other mode: a float polynomial NCO (absolute error below 2e-7) off the double pipe.  In
+ * both the phase stays as close to the float64 recurrence as the reference's own does, and outputs
+ * are within 1e-5 of the input's peak of that recurrence's.
+ * work: freq_out NULL or n_in floats per stream. */
+typedef struct grhip_costas_loop_cc grhip_costas_loop_cc;
+GRHIP_API int grhip_costas_loop_cc_create(grhip_costas_loop_cc **h, float loop_bw, int order, int device);
+GRHIP_API void grhip_costas_loop_cc_destroy(grhip_costas_loop_cc *h);
+GRHIP_API int grhip_costas_loop_cc_set_mode(grhip_costas_loop_cc *h, int mode);
+GRHIP_API int grhip_costas_loop_cc_set_streams(grhip_costas_loop_cc *h, int nstreams);
+GRHIP_API int grhip_costas_loop_cc_set_loop_bandwidth(grhip_costas_loop_cc *h, float bw);
+GRHIP_API int grhip_costas_loop_cc_set_damping_factor(grhip_costas_loop_cc *h, float df);
+GRHIP_API int grhip_costas_loop_cc_set_alpha(grhip_costas_loop_cc *h, float alpha);
+GRHIP_API int grhip_costas_loop_cc_set_beta(grhip_costas_loop_cc *h, float beta);
+GRHIP_API int grhip_costas_loop_cc_set_frequency(grhip_costas_loop_cc *h, float freq);
+GRHIP_API int grhip_costas_loop_cc_set_phase(grhip_costas_loop_cc *h, float phase);
+GRHIP_API float grhip_costas_loop_cc_get_loop_bandwidth(grhip_costas_loop_cc *h);
+GRHIP_API float grhip_costas_loop_cc_get_damping_factor(grhip_costas_loop_cc *h);
+GRHIP_API float grhip_costas_loop_cc_get_alpha(grhip_costas_loop_cc *h);
+GRHIP_API float grhip_costas_loop_cc_get_beta(grhip_costas_loop_cc *h);
+GRHIP_API int grhip_costas_loop_cc_get_frequency(grhip_costas_loop_cc *h, int s, float *freq);
+GRHIP_API int grhip_costas_loop_cc_get_phase(grhip_costas_loop_cc *h, int s, float *phase);
+GRHIP_API int grhip_costas_loop_cc_work(grhip_costas_loop_cc *h, int n_in, const void *in, void *out, void *freq_out);
+GRHIP_API int grhip_costas_loop_cc_work_device(grhip_costas_loop_cc *h, int n_in, const void *d_in, void *d_out, void *d_freq_out,
+                                               void *stream);
+
+/* ======================================================================
  * gr_iir_filter_ffd
  *   replaces gr_make_iir_filter_ffd(const std::vector<double> &fftaps,
  *       const std::vector<double> &fbtaps)
