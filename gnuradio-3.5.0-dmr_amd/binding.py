@@ -27,6 +27,10 @@ __all__ = [
     "pwr_squelch_cc", "pwr_squelch_ff", "simple_squelch_cc", "ctcss_squelch_ff",
     "agc_cc", "agc_ff", "agc2_cc", "agc2_ff",
     "costas_loop_cc", "pll_freqdet_cf", "pll_refout_cc", "pll_carriertracking_cc",
+    "constellation", "constellation_bpsk", "constellation_qpsk", "constellation_dqpsk", "constellation_8psk",
+    "constellation_calcdist", "constellation_psk", "constellation_rect", "psk_constellation", "qam_constellation",
+    "gray_code", "invert_code", "constellation_decoder_cb", "diff_decoder_bb", "map_bb", "constellation_receiver_cb",
+    "constellation_demod_cb",
     "iir_filter_ffd", "fm_deemph", "fm_deemph_taps", "firdes_low_pass", "fm_demod_cf", "nbfm_rx",
     "remez", "optfir_low_pass", "optfir_high_pass", "optfir_band_pass", "optfir_band_reject", "optfir_spec",
     "complex_to_mag", "am_demod_cf", "demod_10k0a3e_cf", "demod_20k0f3e_cf", "demod_200kf3e_cf",
@@ -1813,6 +1817,304 @@ class costas_loop_cc(_control_loop):
 
     def work_device(self, n, d_in, d_out, d_freq_out=None, stream=None):
         return self._call("work_device", int(n), _devptr(d_in), _devptr(d_out), _devptr(d_freq_out), _stream(stream))
+
+
+# ----------------------------------------------------------------------------
+# digital.constellation_* and the blocks behind timing recovery (gr-digital/swig/digital_constellation.i,
+# digital_constellation_receiver_cb.i, digital_constellation_decoder_cb.i, general/gr_diff_decoder_bb.i, gr_map_bb.i,
+# gr-digital/python/generic_mod_demod.py:296-313, psk.py, qam.py, utils/gray_code.py, utils/mod_codes.py)
+# ----------------------------------------------------------------------------
+def _points(points):
+    p = np.ascontiguousarray(points, dtype=np.complex64).reshape(-1)
+    return p, (_ptr(p) if len(p) else C.c_void_p(0)), len(p)
+
+
+def _code(code):
+    c = np.ascontiguousarray(code, dtype=np.uint32).reshape(-1)
+    return c, (_ptr(c) if len(c) else C.c_void_p(0)), len(c)
+
+
+class constellation(object):
+    """a digital_constellation: a host object, no device needed.  Made by constellation_bpsk() ... constellation_rect()."""
+
+    def __init__(self, kind, *args):
+        self._h = C.c_void_p(0)
+        _check(getattr(lib(), "grhip_constellation_create_" + kind)(C.byref(self._h), *args))
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().grhip_constellation_destroy(self._h)
+                self._h = C.c_void_p(0)
+        except Exception:
+            pass
+
+    def _int(self, name):
+        return _check(getattr(lib(), "grhip_constellation_" + name)(self._h))
+
+    def _array(self, name, dtype, width=1):
+        n = _check(getattr(lib(), "grhip_constellation_" + name)(self._h, C.c_void_p(0), 0))
+        a = np.zeros(max(n * width, 1), dtype)
+        _check(getattr(lib(), "grhip_constellation_" + name)(self._h, _ptr(a), n))
+        return a[:n * width]
+
+    def base(self):
+        return self
+
+    def arity(self):
+        return self._int("arity")
+
+    def dimensionality(self):
+        return self._int("dimensionality")
+
+    def rotational_symmetry(self):
+        return self._int("rotational_symmetry")
+
+    def bits_per_symbol(self):
+        return self._int("bits_per_symbol")
+
+    def apply_pre_diff_code(self):
+        return bool(self._int("apply_pre_diff_code"))
+
+    def points(self):
+        return self._array("points", np.float32, 2).view(np.complex64)
+
+    def pre_diff_code(self):
+        return [int(v) for v in self._array("pre_diff_code", np.uint32)]
+
+    def sector_values(self):
+        return self._array("sector_values", np.uint32)
+
+    def decision_maker(self, sample):
+        """the symbols of items of dimensionality() samples each (one item, or an array of them)"""
+        return self.decision_maker_pe(sample, errors=False)
+
+    def decision_maker_pe(self, sample, errors=True):
+        x = np.ascontiguousarray(sample, dtype=np.complex64).reshape(-1, self.dimensionality())
+        idx, pe = np.zeros(len(x), np.uint32), np.zeros(len(x), np.float32)
+        k, e = C.c_uint(0), C.c_float(0)
+        L = lib()
+        for i in range(len(x)):
+            if errors:
+                _check(L.grhip_constellation_decision_maker_pe(self._h, x[i].ctypes.data, C.byref(k), C.byref(e)))
+                pe[i] = e.value
+            else:
+                _check(L.grhip_constellation_decision_maker(self._h, x[i].ctypes.data, C.byref(k)))
+            idx[i] = k.value
+        scalar = np.ndim(sample) == 0 or (self.dimensionality() > 1 and np.ndim(sample) == 1 and len(x) == 1)
+        if not errors:
+            return int(idx[0]) if scalar else idx
+        return (int(idx[0]), np.float32(pe[0])) if scalar else (idx, pe)
+
+
+def constellation_bpsk():
+    return constellation("bpsk")
+
+
+def constellation_qpsk():
+    return constellation("qpsk")
+
+
+def constellation_dqpsk():
+    return constellation("dqpsk")
+
+
+def constellation_8psk():
+    return constellation("8psk")
+
+
+def constellation_calcdist(points, pre_diff_code, rotational_symmetry, dimensionality):
+    p, pp, n = _points(points)
+    c, pc, m = _code(pre_diff_code)
+    return constellation("calcdist", pp, n, pc, m, int(rotational_symmetry), int(dimensionality))
+
+
+def constellation_psk(points, pre_diff_code, n_sectors):
+    p, pp, n = _points(points)
+    c, pc, m = _code(pre_diff_code)
+    return constellation("psk", pp, n, pc, m, int(n_sectors))
+
+
+def constellation_rect(points, pre_diff_code, rotational_symmetry, real_sectors, imag_sectors, width_real_sectors,
+                       width_imag_sectors):
+    p, pp, n = _points(points)
+    c, pc, m = _code(pre_diff_code)
+    return constellation("rect", pp, n, pc, m, int(rotational_symmetry), int(real_sectors), int(imag_sectors),
+                         float(width_real_sectors), float(width_imag_sectors))
+
+
+def gray_code(length):
+    """utils/gray_code.py: the first `length` Gray code words"""
+    gcs, lp2, np2, i = [0, 1], 2, 4, 2
+    while len(gcs) < length:
+        gcs.append(i + i // 2 if i == lp2 else gcs[2 * lp2 - 1 - i] + lp2)
+        i += 1
+        if i == np2:
+            lp2, np2 = i, i * 2
+    return gcs[:length]
+
+
+def invert_code(code):
+    """utils/mod_codes.py invert_code"""
+    return [a for (b, a) in sorted((b, a) for (a, b) in enumerate(code))]
+
+
+def psk_constellation(m=4, mod_code="gray"):
+    """psk.py psk_constellation: m points on the unit circle, m sectors; mod_code 'gray' or 'none'"""
+    k = math.log(m) / math.log(2.0)
+    if k != int(k):
+        raise ValueError("Number of constellation points must be a power of two.")
+    if mod_code not in ("gray", "none"):
+        raise ValueError("That modulation code is not implemented for this constellation.")
+    points = [complex(np.exp(2 * math.pi * 1j * i / m)) for i in range(m)]
+    return constellation_psk(points, gray_code(m) if mod_code == "gray" else [], m)
+
+
+def qam_constellation(constellation_points=16, differential=True, mod_code="none"):
+    """qam.py qam_constellation: a square grid decided by constellation_rect; mod_code 'gray' or 'none'"""
+    if mod_code not in ("gray", "none"):
+        raise ValueError("Mod code is not implemented for QAM")
+    m, gray = int(constellation_points), mod_code == "gray"
+    k = int(math.log(m) / math.log(2.0))
+    if m < 4 or 4 ** (k // 2) != m:
+        raise ValueError("m must be a power of 4 integer.")
+
+    def bits(x, n, w):
+        return (x >> n) % (2 ** w)
+    if differential:        # make_differential_constellation: the quadrant bits differential, the rest Gray or plain
+        side = int(pow(m, 0.5) / 2)
+        i_gcs = dict((v, key) for key, v in enumerate(gray_code(side))) if gray else dict((i, i) for i in range(side))
+        step = 1 / (side - 0.5)
+        g = [(i_gcs[gc] + 0.5) * step for gc in range(side)]
+        quad = (lambda x, y: complex(g[x], g[y]), lambda x, y: complex(-g[y], g[x]), lambda x, y: complex(-g[x], -g[y]),
+                lambda x, y: complex(g[y], -g[x]))
+        h = (k - 2) // 2
+        points = [quad[bits(i, k - 2, 2)](bits(i, h, h), bits(i, 0, h)) for i in range(m)]
+    else:                   # make_non_differential_constellation
+        side = int(pow(m, 0.5))
+        i_gcs = invert_code(gray_code(side)) if gray else list(range(side))
+        step = 2.0 / (side - 1)
+        g = [-1 + i_gcs[gc] * step for gc in range(side)]
+        points = [complex(g[bits(i, k // 2, k // 2)], g[bits(i, 0, k // 2)]) for i in range(m)]
+    side = int(math.sqrt(m))
+    width = 2.0 / (side - 1)
+    return constellation_rect(points, [], 4, side, side, width, width)
+
+
+class _byte_block(_Block):
+    """streams x n items back to back in, as many bytes out"""
+    _in = np.uint8
+    _per_out = 1            # input items per output item
+
+    def history(self):
+        return 1
+
+    def work(self, input_items, n=None):
+        x = np.ascontiguousarray(input_items, dtype=self._in).reshape(-1)
+        if n is None:
+            n = len(x) // (self._streams * self._per_out)
+        if len(x) < n * self._streams * self._per_out:
+            raise ValueError("work needs %d items, got %d" % (n * self._streams * self._per_out, len(x)))
+        out = np.zeros(max(n * self._streams, 1), dtype=np.uint8)
+        self._call("work", int(n), _ptr(x), _ptr(out))
+        return out[:n * self._streams]
+
+
+class constellation_decoder_cb(_byte_block):
+    """digital.constellation_decoder_cb(constellation): one symbol byte per dimensionality() complex items, the
+    constellation's decision_maker byte for byte"""
+    _name = "constellation_decoder_cb"
+    _in = np.complex64
+
+    def __init__(self, constellation, device=0):
+        _Block.__init__(self)
+        self._per_out = constellation.dimensionality()
+        self._create(constellation._h, int(device))
+
+
+class diff_decoder_bb(_byte_block):
+    """gr.diff_decoder_bb(modulus): (in[i] - in[i-1]) % modulus with the reference's int-to-unsigned conversion; the
+    last byte of a call is kept per stream (0 at the start)"""
+    _name = "diff_decoder_bb"
+
+    def __init__(self, modulus, device=0):
+        _Block.__init__(self)
+        self._create(int(modulus), int(device))
+
+    def history(self):
+        return 2
+
+
+class map_bb(_byte_block):
+    """gr.map_bb(map): out = map[in], the identity behind the entries given"""
+    _name = "map_bb"
+
+    def __init__(self, map, device=0):
+        _Block.__init__(self)
+        m = np.ascontiguousarray(map, dtype=np.int32).reshape(-1)
+        self._create(_ptr(m) if len(m) else C.c_void_p(0), len(m), int(device))
+
+
+class constellation_receiver_cb(_control_loop):
+    """digital.constellation_receiver_cb(constellation, loop_bw, fmin, fmax): the decision-directed carrier loop.
+    work(x) returns the symbols; work(x, floats=True) returns (symbols, error, phase, freq), phase and frequency after
+    each sample's update.  form() says how decision and error are formed: 0 the reference's statements (MODE_GENERIC),
+    1 cartesian (rect, calcdist), 2 on the sample's angle (bpsk, qpsk, dqpsk, 8psk, psk)."""
+    _name = "constellation_receiver_cb"
+    FORM_GENERIC, FORM_CARTESIAN, FORM_ANGLE = 0, 1, 2
+
+    def __init__(self, constellation, loop_bw, fmin, fmax, device=0):
+        _Block.__init__(self)
+        self._create(constellation._h, float(loop_bw), float(fmin), float(fmax), int(device))
+
+    def form(self):
+        return self._call("form")
+
+    def work(self, input_items, n_in=None, floats=False):
+        x, n_in = self._items(input_items, n_in)
+        m = max(n_in * self._streams, 1)
+        sym = np.zeros(m, dtype=np.uint8)
+        f = [np.zeros(m, dtype=np.float32) for _ in range(3)] if floats else []
+        self._call("work", int(n_in), _ptr(x), _ptr(sym), *([_ptr(a) for a in f] if floats else [C.c_void_p(0)] * 3))
+        m = n_in * self._streams
+        return (sym[:m], f[0][:m], f[1][:m], f[2][:m]) if floats else sym[:m]
+
+    def work_device(self, n, d_in, d_symbols, d_error=None, d_phase=None, d_freq=None, stream=None):
+        return self._call("work_device", int(n), _devptr(d_in), _devptr(d_symbols), _devptr(d_error), _devptr(d_phase),
+                          _devptr(d_freq), _stream(stream))
+
+
+class constellation_demod_cb(_control_loop):
+    """generic_demod behind timing recovery (generic_mod_demod.py:296-313) as one block: constellation_receiver_cb ->
+    diff_decoder_bb(arity) if differential -> map_bb(invert_code(pre_diff_code)) if gray_coded and the constellation
+    applies one -> unpack_k_bits_bb(bits_per_symbol).  work(x): streams x n complex items in, n * bits_per_symbol()
+    bytes out per stream.  engine() 1 (the default) stores the bits from the receiver's walk, 0 runs the blocks in a
+    row; the bytes are the same."""
+    _name = "constellation_demod_cb"
+
+    def __init__(self, constellation, loop_bw, fmin, fmax, differential=True, gray_coded=True, device=0):
+        _Block.__init__(self)
+        self._create(constellation._h, float(loop_bw), float(fmin), float(fmax), int(bool(differential)), int(bool(gray_coded)),
+                     int(device))
+
+    def form(self):
+        return self._call("form")
+
+    def engine(self):
+        return self._call("engine")
+
+    def set_engine(self, engine):
+        self._call("set_engine", int(engine))
+
+    def bits_per_symbol(self):
+        return self._call("bits_per_symbol")
+
+    def work(self, input_items, n_in=None):
+        x, n_in = self._items(input_items, n_in)
+        m = n_in * self._streams * self.bits_per_symbol()
+        out = np.zeros(max(m, 1), dtype=np.uint8)
+        self._call("work", int(n_in), _ptr(x), _ptr(out))
+        return out[:m]
 
 
 # ----------------------------------------------------------------------------

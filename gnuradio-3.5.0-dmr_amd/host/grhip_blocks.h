@@ -35,6 +35,11 @@
 //   digital_make_costas_loop_cc, gr_make_pll_freqdet_cf / _refout_cc / _carriertracking_cc
 //                                            <- the factories of the same names (gr-digital/include/
 //                                               digital_costas_loop_cc.h, general/gr_pll_*.h)
+//   digital_make_constellation_bpsk / _qpsk / _dqpsk / _8psk / _calcdist / _psk / _rect, digital_make_constellation_decoder_cb,
+//   digital_make_constellation_receiver_cb, gr_make_diff_decoder_bb, gr_make_map_bb
+//                                            <- the factories of the same names (gr-digital/include/digital_constellation*.h,
+//                                               general/gr_diff_decoder_bb.h, gr_map_bb.h); grhip_make_constellation_demod_cb
+//                                               is generic_demod's tail behind timing recovery (generic_mod_demod.py:296-313)
 //   gr_make_agc_cc / _ff, gr_make_agc2_cc / _ff
 //                                            <- the factories of the same names (general/gr_agc_cc.h, gr_agc_ff.h,
 //                                               gr_agc2_cc.h, gr_agc2_ff.h)
@@ -1733,6 +1738,242 @@ GRHIP_LOOP_BLK_COMMON(costas_loop_cc)
 inline grhip_costas_loop_cc_sptr digital_make_costas_loop_cc(float loop_bw, int order, int device = 0)
 {
     return gnuradio::get_initial_sptr(new grhip_costas_loop_cc_blk(loop_bw, order, device));
+}
+// ---------------------------------------------------------------------------
+// digital_constellation and its kinds (gr-digital/include/digital_constellation.h), digital_constellation_decoder_cb
+// (constellation), digital_constellation_receiver_cb (constellation, loop_bw, fmin, fmax; 1 input, 1 or 4 outputs),
+// gr_diff_decoder_bb (modulus), gr_map_bb (map), and constellation_demod_cb, the tail of generic_demod
+// (gr-digital/python/generic_mod_demod.py:296-313) as one block.  A constellation is a host object; a block copies the
+// one it is made from.  What the reference refuses with std::runtime_error throws std::invalid_argument here.
+// ---------------------------------------------------------------------------
+class grhip_constellation_obj;
+typedef boost::shared_ptr<grhip_constellation_obj> grhip_constellation_sptr;
+class grhip_constellation_obj {
+    grhip_constellation *d_h = nullptr;
+public:
+    explicit grhip_constellation_obj(grhip_constellation *h) : d_h(h) {}
+    grhip_constellation_obj(const grhip_constellation_obj &) = delete;
+    grhip_constellation_obj &operator=(const grhip_constellation_obj &) = delete;
+    ~grhip_constellation_obj() { grhip_constellation_destroy(d_h); }
+    const grhip_constellation *handle() const { return d_h; }
+    std::vector<gr_complex> points() const
+    {
+        std::vector<gr_complex> p((size_t)grhip_constellation_points(d_h, nullptr, 0));
+        grhip_constellation_points(d_h, (float *)p.data(), p.size());
+        return p;
+    }
+    std::vector<unsigned int> pre_diff_code() const
+    {
+        std::vector<unsigned int> c((size_t)grhip_constellation_pre_diff_code(d_h, nullptr, 0));
+        grhip_constellation_pre_diff_code(d_h, c.data(), c.size());
+        return c;
+    }
+    bool apply_pre_diff_code() const { return grhip_constellation_apply_pre_diff_code(d_h) != 0; }
+    unsigned int rotational_symmetry() const { return (unsigned)grhip_constellation_rotational_symmetry(d_h); }
+    unsigned int dimensionality() const { return (unsigned)grhip_constellation_dimensionality(d_h); }
+    unsigned int arity() const { return (unsigned)grhip_constellation_arity(d_h); }
+    unsigned int bits_per_symbol() const { return (unsigned)grhip_constellation_bits_per_symbol(d_h); }
+    unsigned int decision_maker(const gr_complex *sample) const
+    {
+        unsigned k = 0;
+        grhip_detail::check(grhip_constellation_decision_maker(d_h, (const float *)sample, &k));
+        return k;
+    }
+    unsigned int decision_maker_pe(const gr_complex *sample, float *phase_error) const
+    {
+        unsigned k = 0;
+        grhip_detail::check(grhip_constellation_decision_maker_pe(d_h, (const float *)sample, &k, phase_error));
+        return k;
+    }
+};
+namespace grhip_detail {
+inline grhip_constellation_sptr constellation(int rc, grhip_constellation *h)
+{
+    check(rc);
+    return grhip_constellation_sptr(new grhip_constellation_obj(h));
+}
+}  // namespace grhip_detail
+#define GRHIP_CONSTELLATION_FIXED(KIND)                                                                                  \
+    inline grhip_constellation_sptr digital_make_constellation_##KIND()                                                  \
+    {                                                                                                                    \
+        grhip_constellation *h = nullptr;                                                                                \
+        const int rc = grhip_constellation_create_##KIND(&h);                                                            \
+        return grhip_detail::constellation(rc, h);                                                                       \
+    }
+GRHIP_CONSTELLATION_FIXED(bpsk)
+GRHIP_CONSTELLATION_FIXED(qpsk)
+GRHIP_CONSTELLATION_FIXED(dqpsk)
+GRHIP_CONSTELLATION_FIXED(8psk)
+#undef GRHIP_CONSTELLATION_FIXED
+inline grhip_constellation_sptr digital_make_constellation_calcdist(std::vector<gr_complex> constellation, std::vector<unsigned int> pre_diff_code,
+                                                                    unsigned int rotational_symmetry, unsigned int dimensionality)
+{
+    grhip_constellation *h = nullptr;
+    const int rc = grhip_constellation_create_calcdist(&h, (const float *)constellation.data(), constellation.size(), pre_diff_code.data(),
+                                                       pre_diff_code.size(), rotational_symmetry, dimensionality);
+    return grhip_detail::constellation(rc, h);
+}
+inline grhip_constellation_sptr digital_make_constellation_psk(std::vector<gr_complex> constellation, std::vector<unsigned int> pre_diff_code,
+                                                               unsigned int n_sectors)
+{
+    grhip_constellation *h = nullptr;
+    const int rc = grhip_constellation_create_psk(&h, (const float *)constellation.data(), constellation.size(), pre_diff_code.data(),
+                                                  pre_diff_code.size(), n_sectors);
+    return grhip_detail::constellation(rc, h);
+}
+inline grhip_constellation_sptr digital_make_constellation_rect(std::vector<gr_complex> constellation, std::vector<unsigned int> pre_diff_code,
+                                                                unsigned int rotational_symmetry, unsigned int real_sectors,
+                                                                unsigned int imag_sectors, float width_real_sectors, float width_imag_sectors)
+{
+    grhip_constellation *h = nullptr;
+    const int rc = grhip_constellation_create_rect(&h, (const float *)constellation.data(), constellation.size(), pre_diff_code.data(),
+                                                   pre_diff_code.size(), rotational_symmetry, real_sectors, imag_sectors, width_real_sectors,
+                                                   width_imag_sectors);
+    return grhip_detail::constellation(rc, h);
+}
+
+// digital_constellation_decoder_cb.cc:39-78: a gr_block, `dimensionality` complex items per output byte
+class grhip_constellation_decoder_cb_blk;
+typedef boost::shared_ptr<grhip_constellation_decoder_cb_blk> grhip_constellation_decoder_cb_sptr;
+class grhip_constellation_decoder_cb_blk : public gr_block {
+    grhip_constellation_decoder_cb *d_h = nullptr;
+    unsigned d_dim;
+    grhip_constellation_decoder_cb_blk(grhip_constellation_sptr c, int device)
+        : gr_block("constellation_decoder_cb", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(unsigned char))),
+          d_dim(c->dimensionality())
+    {
+        set_relative_rate(1.0 / ((double)d_dim));
+        grhip_detail::check(grhip_constellation_decoder_cb_create(&d_h, c->handle(), device));
+    }
+    friend grhip_constellation_decoder_cb_sptr digital_make_constellation_decoder_cb(grhip_constellation_sptr, int);
+public:
+    ~grhip_constellation_decoder_cb_blk() { grhip_constellation_decoder_cb_destroy(d_h); }
+    void forecast(int noutput_items, gr_vector_int &req) override
+    {
+        for (size_t i = 0; i < req.size(); i++) req[i] = noutput_items * d_dim;
+    }
+    int general_work(int noutput_items, gr_vector_int &, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(grhip_constellation_decoder_cb_work(d_h, noutput_items, in[0], out[0]));
+        consume_each(noutput_items * d_dim);
+        return noutput_items;
+    }
+};
+inline grhip_constellation_decoder_cb_sptr digital_make_constellation_decoder_cb(grhip_constellation_sptr constellation, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_constellation_decoder_cb_blk(constellation, device));
+}
+
+// gr_diff_decoder_bb.cc:36-61: a gr_sync_block with history 2.  in[0] is the byte in front of the first output's; the
+// handle keeps that byte itself (the last one of the call before, 0 at the start, which is what the scheduler's
+// history holds), so the work call hands it the items from in[1] on.
+class grhip_diff_decoder_bb_blk;
+typedef boost::shared_ptr<grhip_diff_decoder_bb_blk> grhip_diff_decoder_bb_sptr;
+class grhip_diff_decoder_bb_blk : public gr_sync_block {
+    grhip_diff_decoder_bb *d_h = nullptr;
+    grhip_diff_decoder_bb_blk(unsigned int modulus, int device)
+        : gr_sync_block("diff_decoder_bb", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(unsigned char)))
+    {
+        set_history(2);
+        grhip_detail::check(grhip_diff_decoder_bb_create(&d_h, modulus, device));
+    }
+    friend grhip_diff_decoder_bb_sptr gr_make_diff_decoder_bb(unsigned int, int);
+public:
+    ~grhip_diff_decoder_bb_blk() { grhip_diff_decoder_bb_destroy(d_h); }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(grhip_diff_decoder_bb_work(d_h, noutput_items, (const unsigned char *)in[0] + 1, out[0]));
+        return noutput_items;
+    }
+};
+inline grhip_diff_decoder_bb_sptr gr_make_diff_decoder_bb(unsigned int modulus, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_diff_decoder_bb_blk(modulus, device));
+}
+
+// gr_map_bb.cc:36-60
+class grhip_map_bb_blk;
+typedef boost::shared_ptr<grhip_map_bb_blk> grhip_map_bb_sptr;
+class grhip_map_bb_blk : public gr_sync_block {
+    grhip_map_bb *d_h = nullptr;
+    grhip_map_bb_blk(const std::vector<int> &map, int device)
+        : gr_sync_block("map_bb", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(unsigned char)))
+    {
+        grhip_detail::check(grhip_map_bb_create(&d_h, map.data(), map.size(), device));
+    }
+    friend grhip_map_bb_sptr gr_make_map_bb(const std::vector<int> &, int);
+public:
+    ~grhip_map_bb_blk() { grhip_map_bb_destroy(d_h); }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(grhip_map_bb_work(d_h, noutput_items, in[0], out[0]));
+        return noutput_items;
+    }
+};
+inline grhip_map_bb_sptr gr_make_map_bb(const std::vector<int> &map, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_map_bb_blk(map, device));
+}
+
+// digital_constellation_receiver_cb.cc:52-122: a gr_block with gri_control_loop's interface; outputs 2 .. 4 (error,
+// phase, frequency) are connected all three or not at all
+class grhip_constellation_receiver_cb_blk;
+typedef boost::shared_ptr<grhip_constellation_receiver_cb_blk> grhip_constellation_receiver_cb_sptr;
+class grhip_constellation_receiver_cb_blk : public gr_block {
+    grhip_constellation_receiver_cb *d_h = nullptr;
+    grhip_constellation_receiver_cb_blk(grhip_constellation_sptr c, float loop_bw, float fmin, float fmax, int device)
+        : gr_block("constellation_receiver_cb", gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                   gr_make_io_signature2(1, 4, sizeof(char), sizeof(float)))                    // :50-56
+    {
+        grhip_detail::check(grhip_constellation_receiver_cb_create(&d_h, c->handle(), loop_bw, fmin, fmax, device));
+    }
+    friend grhip_constellation_receiver_cb_sptr digital_make_constellation_receiver_cb(grhip_constellation_sptr, float, float, float, int);
+GRHIP_LOOP_BLK_COMMON(constellation_receiver_cb)
+    int form() const { return grhip_constellation_receiver_cb_form(d_h); }
+    int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        const int n = std::min(noutput_items, ninput_items[0]);                                 // :102
+        const bool four = out.size() == 4;                                                      // :96
+        grhip_detail::check(grhip_constellation_receiver_cb_work(d_h, n, in[0], out[0], four ? out[1] : nullptr, four ? out[2] : nullptr,
+                                                                 four ? out[3] : nullptr));
+        consume_each(n);
+        return n;
+    }
+};
+inline grhip_constellation_receiver_cb_sptr digital_make_constellation_receiver_cb(grhip_constellation_sptr constellation, float loop_bw,
+                                                                                   float fmin, float fmax, int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_constellation_receiver_cb_blk(constellation, loop_bw, fmin, fmax, device));
+}
+
+// the receiver, diff_decoder_bb(arity) if differential, map_bb(invert_code(pre_diff_code)) if gray_coded and the
+// constellation applies one, unpack_k_bits_bb(bits_per_symbol): bits_per_symbol bytes out per complex item in
+class grhip_constellation_demod_cb_blk;
+typedef boost::shared_ptr<grhip_constellation_demod_cb_blk> grhip_constellation_demod_cb_sptr;
+class grhip_constellation_demod_cb_blk : public gr_sync_interpolator {
+    grhip_constellation_demod_cb *d_h = nullptr;
+    grhip_constellation_demod_cb_blk(grhip_constellation_sptr c, float loop_bw, float fmin, float fmax, bool differential, bool gray_coded, int device)
+        : gr_sync_interpolator("constellation_demod_cb", gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                               gr_make_io_signature(1, 1, sizeof(unsigned char)), std::max(1u, c->bits_per_symbol()))
+    {
+        grhip_detail::check(grhip_constellation_demod_cb_create(&d_h, c->handle(), loop_bw, fmin, fmax, differential, gray_coded, device));
+    }
+    friend grhip_constellation_demod_cb_sptr grhip_make_constellation_demod_cb(grhip_constellation_sptr, float, float, float, bool, bool, int);
+GRHIP_LOOP_BLK_COMMON(constellation_demod_cb)
+    int form() const { return grhip_constellation_demod_cb_form(d_h); }
+    int engine() const { return grhip_constellation_demod_cb_engine(d_h); }
+    void set_engine(int engine) { grhip_detail::check(grhip_constellation_demod_cb_set_engine(d_h, engine)); }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(grhip_constellation_demod_cb_work(d_h, noutput_items / (int)interpolation(), in[0], out[0]));
+        return noutput_items;
+    }
+};
+inline grhip_constellation_demod_cb_sptr grhip_make_constellation_demod_cb(grhip_constellation_sptr constellation, float loop_bw, float fmin,
+                                                                           float fmax, bool differential = true, bool gray_coded = true,
+                                                                           int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_constellation_demod_cb_blk(constellation, loop_bw, fmin, fmax, differential, gray_coded, device));
 }
 #undef GRHIP_LOOP_BLK_COMMON
 

@@ -1964,6 +1964,169 @@ GRHIP_API int grhip_costas_loop_cc_work_device(grhip_costas_loop_cc *h, int n_in
                                                void *stream);
 
 /* ======================================================================
+ * digital_constellation and its kinds (host objects; no device is needed)
+ *   replaces digital_make_constellation_bpsk / _qpsk / _dqpsk / _8psk (), digital_make_constellation_calcdist
+ *       (constellation, pre_diff_code, rotational_symmetry, dimensionality), digital_make_constellation_psk
+ *       (constellation, pre_diff_code, n_sectors), digital_make_constellation_rect (constellation, pre_diff_code,
+ *       rotational_symmetry, real_sectors, imag_sectors, width_real_sectors, width_imag_sectors)
+ *   gr-digital/lib/digital_constellation.cc, gr-digital/include/digital_constellation.h
+ * Points travel as npoints (re, im) float pairs; a pre_diff_code of length 0 means none
+ * (apply_pre_diff_code() is then 0; constellation_qpsk has a code and does not apply it, as in the
+ * reference).  bpsk, qpsk, dqpsk and 8psk decide by the reference's closed forms; calcdist by
+ * get_closest_point (float norms, the first strict minimum); psk and rect through a sector table
+ * (get_sector, calc_sector_value).  decision_maker takes `dimensionality` samples and gives the
+ * symbol; decision_maker_pe also gives 0 + sum_d -arg(sample[d] * conj(points[index + d])), the
+ * complex product as g++ forms it without -ffast-math (C99 Annex G recovery included).  Both run on
+ * the host.  bits_per_symbol is floor(log(npoints) / dimensionality / log(2.0)).
+ * Refused with GRHIP_EINVAL (the reference throws std::runtime_error): a pre_diff_code whose length is
+ * neither 0 nor npoints; npoints that is no multiple of the dimensionality.
+ * Deviations: at most 256 symbols (a symbol is a byte at the blocks' outputs) and at least one; at most
+ * 16384 sectors and at least one; rect's widths finite and not zero, its points finite; a sample
+ * that is not finite gets a defined sector (a NaN position is sector 0, every index is clamped to the
+ * table; the reference converts such a double to int, which is undefined); arg, cos and sin of a float
+ * are the float-rounded double functions, within an ulp of glibc's atan2f / cosf / sinf but the same
+ * on host, device and in the tests.  Dimensionality above 1 exists for calcdist only; the receiver
+ * refuses it, the decoder takes it.
+ * points / pre_diff_code / sector_values copy at most `capacity` entries and return how many there are. */
+typedef struct grhip_constellation grhip_constellation;
+GRHIP_API int grhip_constellation_create_bpsk(grhip_constellation **h);
+GRHIP_API int grhip_constellation_create_qpsk(grhip_constellation **h);
+GRHIP_API int grhip_constellation_create_dqpsk(grhip_constellation **h);
+GRHIP_API int grhip_constellation_create_8psk(grhip_constellation **h);
+GRHIP_API int grhip_constellation_create_calcdist(grhip_constellation **h, const float *points_re_im, size_t npoints, const unsigned *pre_diff_code,
+                                                  size_t ncode, unsigned rotational_symmetry, unsigned dimensionality);
+GRHIP_API int grhip_constellation_create_psk(grhip_constellation **h, const float *points_re_im, size_t npoints, const unsigned *pre_diff_code,
+                                             size_t ncode, unsigned n_sectors);
+GRHIP_API int grhip_constellation_create_rect(grhip_constellation **h, const float *points_re_im, size_t npoints, const unsigned *pre_diff_code,
+                                              size_t ncode, unsigned rotational_symmetry, unsigned real_sectors, unsigned imag_sectors,
+                                              float width_real_sectors, float width_imag_sectors);
+GRHIP_API void grhip_constellation_destroy(grhip_constellation *h);
+GRHIP_API int grhip_constellation_arity(const grhip_constellation *h);
+GRHIP_API int grhip_constellation_dimensionality(const grhip_constellation *h);
+GRHIP_API int grhip_constellation_rotational_symmetry(const grhip_constellation *h);
+GRHIP_API int grhip_constellation_bits_per_symbol(const grhip_constellation *h);
+GRHIP_API int grhip_constellation_apply_pre_diff_code(const grhip_constellation *h);
+GRHIP_API int grhip_constellation_n_sectors(const grhip_constellation *h);
+GRHIP_API int grhip_constellation_points(const grhip_constellation *h, float *points_re_im, size_t capacity);
+GRHIP_API int grhip_constellation_pre_diff_code(const grhip_constellation *h, unsigned *code, size_t capacity);
+GRHIP_API int grhip_constellation_sector_values(const grhip_constellation *h, unsigned *values, size_t capacity);
+GRHIP_API int grhip_constellation_decision_maker(const grhip_constellation *h, const float *sample_re_im, unsigned *index);
+GRHIP_API int grhip_constellation_decision_maker_pe(const grhip_constellation *h, const float *sample_re_im, unsigned *index, float *phase_error);
+
+/* digital_constellation_decoder_cb, gr_diff_decoder_bb, gr_map_bb
+ *   replace digital_make_constellation_decoder_cb (constellation), gr_make_diff_decoder_bb (modulus),
+ *       gr_make_map_bb (map)
+ *   gr-digital/lib/digital_constellation_decoder_cb.cc:63-78, general/gr_diff_decoder_bb.cc:48-61,
+ *   general/gr_map_bb.cc:36-60
+ * Handles take S streams back to back as the carrier loops do; `out` may not overlap `in` (map_bb may
+ * run in place); n == 0 is a successful no-op; work_device does not synchronise.  A block copies its
+ * constellation, which may be destroyed before the block.
+ * constellation_decoder_cb: n outputs from n * dimensionality complex items per stream, byte for byte
+ * the host's decision_maker in every mode.
+ * diff_decoder_bb: out[i] = (unsigned)((int)in[i] - (int)in[i-1]) % modulus, so a negative difference
+ * wraps at 2^32 before the % (what the reference computes for a modulus that is no power of two); the
+ * byte in front of a call's first is the stream's last of the call before, 0 after create and
+ * set_streams.  modulus 0 is refused (the reference divides by it).
+ * map_bb: a 256-entry table, the identity behind the nmap entries given; at most 256 are taken, each
+ * narrowed to a byte. */
+typedef struct grhip_constellation_decoder_cb grhip_constellation_decoder_cb;
+GRHIP_API int grhip_constellation_decoder_cb_create(grhip_constellation_decoder_cb **h, const grhip_constellation *constellation, int device);
+GRHIP_API void grhip_constellation_decoder_cb_destroy(grhip_constellation_decoder_cb *h);
+GRHIP_API int grhip_constellation_decoder_cb_set_mode(grhip_constellation_decoder_cb *h, int mode);
+GRHIP_API int grhip_constellation_decoder_cb_set_streams(grhip_constellation_decoder_cb *h, int nstreams);
+GRHIP_API int grhip_constellation_decoder_cb_work(grhip_constellation_decoder_cb *h, int n, const void *in, void *out);
+GRHIP_API int grhip_constellation_decoder_cb_work_device(grhip_constellation_decoder_cb *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_diff_decoder_bb grhip_diff_decoder_bb;
+GRHIP_API int grhip_diff_decoder_bb_create(grhip_diff_decoder_bb **h, unsigned modulus, int device);
+GRHIP_API void grhip_diff_decoder_bb_destroy(grhip_diff_decoder_bb *h);
+GRHIP_API int grhip_diff_decoder_bb_set_mode(grhip_diff_decoder_bb *h, int mode);
+GRHIP_API int grhip_diff_decoder_bb_set_streams(grhip_diff_decoder_bb *h, int nstreams);
+GRHIP_API int grhip_diff_decoder_bb_work(grhip_diff_decoder_bb *h, int n, const void *in, void *out);
+GRHIP_API int grhip_diff_decoder_bb_work_device(grhip_diff_decoder_bb *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_map_bb grhip_map_bb;
+GRHIP_API int grhip_map_bb_create(grhip_map_bb **h, const int *map, size_t nmap, int device);
+GRHIP_API void grhip_map_bb_destroy(grhip_map_bb *h);
+GRHIP_API int grhip_map_bb_set_mode(grhip_map_bb *h, int mode);
+GRHIP_API int grhip_map_bb_set_streams(grhip_map_bb *h, int nstreams);
+GRHIP_API int grhip_map_bb_work(grhip_map_bb *h, int n, const void *in, void *out);
+GRHIP_API int grhip_map_bb_work_device(grhip_map_bb *h, int n, const void *d_in, void *d_out, void *stream);
+
+/* digital_constellation_receiver_cb
+ *   replaces digital_make_constellation_receiver_cb (constellation, loop_bw, fmin, fmax)
+ *   gr-digital/lib/digital_constellation_receiver_cb.cc:80-122
+ * Complex in; a symbol byte out and, all three or none, the phase error, the loop's phase and its
+ * frequency as floats, the last two AFTER the update (:113-115).  Per sample: nco = gr_expj(+phase);
+ * sample = nco * in; (symbol, error) = decision_maker_pe(sample); then gri_control_loop's advance_loop,
+ * phase_wrap, frequency_limit with max_freq = fmax, min_freq = fmin.  The loop's setters, getters and
+ * refusals are those of the carrier loops above.  A constellation of dimensionality above 1 is refused
+ * (the reference throws std::runtime_error), as is a call with one or two of the three float outputs.
+ * The decision sits inside the loop, so the result depends on sine, cosine and arctangent to the bit, and
+ * glibc's are not reproduced.  GRHIP_MODE_GENERIC: the reference's statements in order
+ * with the float-rounded double functions.  Every other mode, by the constellation's kind (form()
+ * says which: 0 GENERIC, 1 cartesian, 2 angle): bpsk, qpsk, dqpsk, 8psk and psk run on the sample's angle
+ * (theta = atan2f(im, re) off the serial chain; t = wrap(theta + phase); the decision from t; error =
+ * -wrap(t - angle of the decided point)); rect and calcdist keep the chain with a float polynomial
+ * NCO, rect's sector from one multiply-add per axis and atan2f.  In every mode the phase stays as close
+ * to the float64 recurrence as the reference's own does, and the symbols are the reference's wherever no
+ * derotated sample lies within 1e-3 of its magnitude of a decision border. */
+typedef struct grhip_constellation_receiver_cb grhip_constellation_receiver_cb;
+GRHIP_API int grhip_constellation_receiver_cb_create(grhip_constellation_receiver_cb **h, const grhip_constellation *constellation, float loop_bw,
+                                                     float fmin, float fmax, int device);
+GRHIP_API void grhip_constellation_receiver_cb_destroy(grhip_constellation_receiver_cb *h);
+GRHIP_API int grhip_constellation_receiver_cb_set_mode(grhip_constellation_receiver_cb *h, int mode);
+GRHIP_API int grhip_constellation_receiver_cb_set_streams(grhip_constellation_receiver_cb *h, int nstreams);
+GRHIP_API int grhip_constellation_receiver_cb_form(grhip_constellation_receiver_cb *h);
+GRHIP_API int grhip_constellation_receiver_cb_set_loop_bandwidth(grhip_constellation_receiver_cb *h, float bw);
+GRHIP_API int grhip_constellation_receiver_cb_set_damping_factor(grhip_constellation_receiver_cb *h, float df);
+GRHIP_API int grhip_constellation_receiver_cb_set_alpha(grhip_constellation_receiver_cb *h, float alpha);
+GRHIP_API int grhip_constellation_receiver_cb_set_beta(grhip_constellation_receiver_cb *h, float beta);
+GRHIP_API int grhip_constellation_receiver_cb_set_frequency(grhip_constellation_receiver_cb *h, float freq);
+GRHIP_API int grhip_constellation_receiver_cb_set_phase(grhip_constellation_receiver_cb *h, float phase);
+GRHIP_API float grhip_constellation_receiver_cb_get_loop_bandwidth(grhip_constellation_receiver_cb *h);
+GRHIP_API float grhip_constellation_receiver_cb_get_damping_factor(grhip_constellation_receiver_cb *h);
+GRHIP_API float grhip_constellation_receiver_cb_get_alpha(grhip_constellation_receiver_cb *h);
+GRHIP_API float grhip_constellation_receiver_cb_get_beta(grhip_constellation_receiver_cb *h);
+GRHIP_API int grhip_constellation_receiver_cb_get_frequency(grhip_constellation_receiver_cb *h, int s, float *freq);
+GRHIP_API int grhip_constellation_receiver_cb_get_phase(grhip_constellation_receiver_cb *h, int s, float *phase);
+GRHIP_API int grhip_constellation_receiver_cb_work(grhip_constellation_receiver_cb *h, int n_in, const void *in, void *symbols, void *error,
+                                                   void *phase, void *freq);
+GRHIP_API int grhip_constellation_receiver_cb_work_device(grhip_constellation_receiver_cb *h, int n_in, const void *d_in, void *d_symbols,
+                                                          void *d_error, void *d_phase, void *d_freq, void *stream);
+
+/* constellation_demod_cb: generic_demod behind timing recovery as one handle
+ *   gr-digital/python/generic_mod_demod.py:296-313
+ * constellation_receiver_cb -> diff_decoder_bb(arity) if differential -> map_bb(invert_code(pre_diff_code))
+ * if gray_coded and the constellation applies a pre-diff code -> unpack_k_bits_bb(bits_per_symbol).
+ * n complex items in, n * bits_per_symbol bytes out per stream (one bit each, most significant first).
+ * engine 1 (the default) stores the bits from the receiver's walk; engine 0 runs the library's own
+ * blocks in a row inside the handle; both give the same bytes and keep the same state, so the engine
+ * may change between calls.  A constellation of fewer than 2 points has no bits and is refused. */
+typedef struct grhip_constellation_demod_cb grhip_constellation_demod_cb;
+GRHIP_API int grhip_constellation_demod_cb_create(grhip_constellation_demod_cb **h, const grhip_constellation *constellation, float loop_bw,
+                                                  float fmin, float fmax, int differential, int gray_coded, int device);
+GRHIP_API void grhip_constellation_demod_cb_destroy(grhip_constellation_demod_cb *h);
+GRHIP_API int grhip_constellation_demod_cb_set_mode(grhip_constellation_demod_cb *h, int mode);
+GRHIP_API int grhip_constellation_demod_cb_set_streams(grhip_constellation_demod_cb *h, int nstreams);
+GRHIP_API int grhip_constellation_demod_cb_form(grhip_constellation_demod_cb *h);
+GRHIP_API int grhip_constellation_demod_cb_set_loop_bandwidth(grhip_constellation_demod_cb *h, float bw);
+GRHIP_API int grhip_constellation_demod_cb_set_damping_factor(grhip_constellation_demod_cb *h, float df);
+GRHIP_API int grhip_constellation_demod_cb_set_alpha(grhip_constellation_demod_cb *h, float alpha);
+GRHIP_API int grhip_constellation_demod_cb_set_beta(grhip_constellation_demod_cb *h, float beta);
+GRHIP_API int grhip_constellation_demod_cb_set_frequency(grhip_constellation_demod_cb *h, float freq);
+GRHIP_API int grhip_constellation_demod_cb_set_phase(grhip_constellation_demod_cb *h, float phase);
+GRHIP_API float grhip_constellation_demod_cb_get_loop_bandwidth(grhip_constellation_demod_cb *h);
+GRHIP_API float grhip_constellation_demod_cb_get_damping_factor(grhip_constellation_demod_cb *h);
+GRHIP_API float grhip_constellation_demod_cb_get_alpha(grhip_constellation_demod_cb *h);
+GRHIP_API float grhip_constellation_demod_cb_get_beta(grhip_constellation_demod_cb *h);
+GRHIP_API int grhip_constellation_demod_cb_get_frequency(grhip_constellation_demod_cb *h, int s, float *freq);
+GRHIP_API int grhip_constellation_demod_cb_get_phase(grhip_constellation_demod_cb *h, int s, float *phase);
+GRHIP_API int grhip_constellation_demod_cb_set_engine(grhip_constellation_demod_cb *h, int engine);
+GRHIP_API int grhip_constellation_demod_cb_engine(grhip_constellation_demod_cb *h);
+GRHIP_API int grhip_constellation_demod_cb_bits_per_symbol(grhip_constellation_demod_cb *h);
+GRHIP_API int grhip_constellation_demod_cb_work(grhip_constellation_demod_cb *h, int n_in, const void *in, void *bits);
+GRHIP_API int grhip_constellation_demod_cb_work_device(grhip_constellation_demod_cb *h, int n_in, const void *d_in, void *d_bits, void *stream);
+
+/* ======================================================================
  * gr_iir_filter_ffd
  *   replaces gr_make_iir_filter_ffd(const std::vector<double> &fftaps,
  *       const std::vector<double> &fbtaps)
