@@ -10,31 +10,20 @@
 
 #include "agc.h"
 #include "grhip_internal.h"
+#include "stream_block.h"
 
 using namespace grhip;
 
 namespace {
 
-struct AgcBlock : HandleBase {
+struct AgcBlock : StreamBlock {
     bool cc = true;
     int law = AGC_LAW_AGC;
     AgcParams p = {1e-4f, 1e-2f, 1.0f, 0.0f};
     float gain0 = 1.0f;                 // the constructor's gain: what set_streams restarts every stream from
-    int nstreams = 1;
-    int mode = GRHIP_MODE_FAST;
-    DevBuf d_gain, d_scratch;
+    DevBuf d_gain, d_scratch;           // d_gain: every stream's gain, one float
 
     size_t item() const { return cc ? 2 * sizeof(float) : sizeof(float); }
-
-    // every stream's gain = v; streams drained, under setter_mutex
-    int fill_gain(float v)
-    {
-        int rc = d_gain.reserve((size_t)nstreams * sizeof(float));
-        if (rc) return rc;
-        std::vector<float> g((size_t)nstreams, v);
-        GRHIP_HIP(hipMemcpy(d_gain.p, g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice));
-        return GRHIP_OK;
-    }
 
     int init(bool is_cc, int which, float rate, float decay, float reference, float gain, float max_gain, int dev)
     {
@@ -43,26 +32,12 @@ struct AgcBlock : HandleBase {
         gain0 = gain;
         mode = default_mode();
         int rc = init_device(dev);
-        return rc ? rc : fill_gain(gain0);
-    }
-
-    int set_mode(int m)
-    {
-        if (!mode_valid(m)) return fail(GRHIP_EINVAL, "bad mode %d", m);
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        mode = m;
-        return GRHIP_OK;
+        return rc ? rc : fill_state(d_gain, gain0);
     }
 
     int set_streams(int S)
     {
-        if (S < 1 || S > 65535) return fail(GRHIP_EINVAL, "1 .. 65535 streams");
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        nstreams = S;
-        return fill_gain(gain0);
+        return StreamBlock::set_streams(S, [&] { return fill_state(d_gain, gain0); });
     }
 
     // gri_agc_cc.h:50: the one gain of the reference's block; here every stream's
@@ -72,19 +47,13 @@ struct AgcBlock : HandleBase {
         if (rc) return rc;
         std::lock_guard<std::mutex> lk(setter_mutex);
         if ((rc = drain(own_stream))) return rc;
-        return fill_gain(v);
+        return fill_state(d_gain, v);
     }
 
     int get_gain(int s, float *v)
     {
         if (!v) return fail(GRHIP_EINVAL, "null argument");
-        if (s < 0 || s >= nstreams) return fail(GRHIP_EINVAL, "stream %d of %d", s, nstreams);
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        GRHIP_HIP(hipMemcpy(v, d_gain.as<float>() + s, sizeof(float), hipMemcpyDeviceToHost));
-        return GRHIP_OK;
+        return read_state(d_gain, s, v);
     }
 
     int set_param(float AgcParams::*which, float v)
@@ -102,15 +71,12 @@ struct AgcBlock : HandleBase {
 
     int work_device(int n_in, const void *d_in, void *d_out, void *stream)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_in == 0) return GRHIP_OK;
-        if (!d_in || !d_out) return fail(GRHIP_EINVAL, "null buffer");
-        if (((uintptr_t)d_in | (uintptr_t)d_out) & (item() - 1)) return fail(GRHIP_EINVAL, "items not naturally aligned");
-        const char *a = (const char *)d_in, *b = (const char *)d_out;
+        const int c = check_count(n_in);
+        if (c <= 0) return c;
         const size_t bytes = (size_t)nstreams * (size_t)n_in * item();
-        if (a < b + bytes && b < a + bytes) return fail(GRHIP_EINVAL, "agc: the output may not overlap the input");
-        int rc = bind();
-        if (rc) return rc;
+        int rc;
+        if ((rc = check_io(d_in, item(), d_out, item())) || (rc = check_apart("agc", d_in, bytes, d_out, bytes))) return rc;
+        if ((rc = bind())) return rc;
         hipStream_t st = pick(stream);
         std::lock_guard<std::mutex> lk(setter_mutex);
         AgcLaunch l;
@@ -123,17 +89,9 @@ struct AgcBlock : HandleBase {
 
     int work(int n_in, const void *in, void *out)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_in == 0) return GRHIP_OK;
-        if (!in || !out) return fail(GRHIP_EINVAL, "null buffer");
-        int rc = bind();
-        if (rc) return rc;
-        const size_t bytes = (size_t)nstreams * (size_t)n_in * item();
-        const long long r = host_call(in, bytes, bytes + 16, bytes + 16, out, item(), [&](void *d_in, void *d_out, hipStream_t st) {
-            const int e = work_device(n_in, d_in, d_out, st);
-            return e ? (long long)e : (long long)nstreams * n_in;
+        return host_work(n_in, item(), in, (size_t)n_in, item(), out, 0, [&](void *d_in, void *d_out, hipStream_t st) {
+            return work_device(n_in, d_in, d_out, st);
         });
-        return r < 0 ? (int)r : GRHIP_OK;
     }
 };
 

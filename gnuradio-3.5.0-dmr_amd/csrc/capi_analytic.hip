@@ -22,6 +22,7 @@
 
 #include "analytic.h"
 #include "grhip_internal.h"
+#include "stream_block.h"
 
 using namespace grhip;
 
@@ -106,11 +107,10 @@ int firdes_hilbert(unsigned ntaps, int window_type, double beta, std::vector<flo
 
 }  // namespace
 
-struct grhip_analytic_base : HandleBase {
+struct grhip_analytic_base : ModeBlock {
     std::vector<float> taps;                    // forward order, as given
     int ntaps = 0, delay = 0, nodd = 0;
     bool sparse = false;
-    int mode = GRHIP_MODE_FAST;
     DevBuf d_rev, d_odd;
 
     int install(const float *t, size_t n)
@@ -186,14 +186,6 @@ struct grhip_analytic_base : HandleBase {
                               });
     }
 
-    int set_mode(int m)
-    {
-        if (!mode_valid(m)) return fail(GRHIP_EINVAL, "bad mode %d", m);
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        mode = m;
-        return GRHIP_OK;
-    }
-
     int read_taps(float *out, size_t cap) const
     {
         if (!out || cap < (size_t)ntaps) return fail(GRHIP_EINVAL, "taps: room for %d floats needed", ntaps);
@@ -205,10 +197,9 @@ struct grhip_analytic_base : HandleBase {
 struct grhip_hilbert_fc : grhip_analytic_base {};
 struct grhip_filter_delay_fc : grhip_analytic_base {};
 
-struct grhip_goertzel_fc : HandleBase {
+struct grhip_goertzel_fc : ModeBlock {
     int rate = 1, len = 1;
     float freq = 0.f, wr = 0.f, wi = 0.f;
-    int mode = GRHIP_MODE_FAST;
     DevBuf d_tab;
     bool tab_valid = false;
 
@@ -236,7 +227,7 @@ struct grhip_goertzel_fc : HandleBase {
         if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
         if (noutput_items == 0) return 0;
         if (!d_in || !d_out) return fail(GRHIP_EINVAL, "null buffer");
-        if ((((uintptr_t)d_in) & 3) || (((uintptr_t)d_out) & 7)) return fail(GRHIP_EINVAL, "goertzel: items not naturally aligned");
+        if (!aligned(d_in, 4) || !aligned(d_out, 8)) return fail(GRHIP_EINVAL, "goertzel: items not naturally aligned");
         int rc = bind();
         if (rc) return rc;
         hipStream_t st = pick(stream);
@@ -451,11 +442,7 @@ int grhip_goertzel_fc_set_rate(grhip_goertzel_fc *h, int rate)
 
 int grhip_goertzel_fc_set_mode(grhip_goertzel_fc *h, int mode)
 {
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (!mode_valid(mode)) return fail(GRHIP_EINVAL, "bad mode %d", mode);
-    std::lock_guard<std::mutex> lk(h->setter_mutex);
-    h->mode = mode;
-    return GRHIP_OK;
+    return h ? h->set_mode(mode) : fail(GRHIP_EINVAL, "null handle");
 }
 
 int grhip_goertzel_fc_decimation(const grhip_goertzel_fc *h) { return h ? h->len : fail(GRHIP_EINVAL, "null handle"); }

@@ -12,6 +12,7 @@
 #include "carrier.h"
 #include "control_loop.h"
 #include "grhip_internal.h"
+#include "stream_block.h"
 
 using namespace grhip;
 
@@ -19,28 +20,18 @@ namespace {
 
 enum { CARRIER_COSTAS = -1 };       // otherwise a PLL_* kind
 
-struct CarrierBlock : HandleBase {
+struct CarrierBlock : StreamBlock {
     int kind = PLL_FREQDET;
     int order = 2;
     ControlLoop cl;
     float lock_threshold = 0.f;         // gr_pll_carriertracking_cc.cc:50
     int squelch = 0;
-    int nstreams = 1;
-    int mode = GRHIP_MODE_FAST;
     const DeviceTables *tabs = nullptr;
-    DevBuf d_state;
+    DevBuf d_state;                     // every stream's CarrierState
 
     size_t out_item() const { return kind == PLL_FREQDET ? sizeof(float) : 2 * sizeof(float); }
 
-    // every stream's state = v; streams drained, under setter_mutex
-    int fill_state(const CarrierState &v)
-    {
-        int rc = d_state.reserve((size_t)nstreams * sizeof(CarrierState));
-        if (rc) return rc;
-        std::vector<CarrierState> t((size_t)nstreams, v);
-        GRHIP_HIP(hipMemcpy(d_state.p, t.data(), t.size() * sizeof(CarrierState), hipMemcpyHostToDevice));
-        return GRHIP_OK;
-    }
+    int restart() { return fill_state(d_state, CarrierState{0.f, 0.f, 0.f, 0.f}); }          // gri_control_loop.cc:35
 
     int init(int which, int ord, float loop_bw, float max_freq, float min_freq, int dev)
     {
@@ -55,26 +46,12 @@ struct CarrierBlock : HandleBase {
         int rc = init_device(dev);
         if (rc) return rc;
         if (which != CARRIER_COSTAS && (rc = get_device_tables(dev, &tabs))) return rc;
-        return fill_state(CarrierState{0.f, 0.f, 0.f, 0.f});                                 // gri_control_loop.cc:35
-    }
-
-    int set_mode(int m)
-    {
-        if (!mode_valid(m)) return fail(GRHIP_EINVAL, "bad mode %d", m);
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        mode = m;
-        return GRHIP_OK;
+        return restart();
     }
 
     int set_streams(int S)
     {
-        if (S < 1 || S > 65535) return fail(GRHIP_EINVAL, "1 .. 65535 streams");
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        nstreams = S;
-        return fill_state(CarrierState{0.f, 0.f, 0.f, 0.f});
+        return StreamBlock::set_streams(S, [&] { return restart(); });
     }
 
     // a setter of the loop's parameters (control_loop.h): false is the reference's std::out_of_range
@@ -94,15 +71,7 @@ struct CarrierBlock : HandleBase {
     // one float of every stream's state = v
     int set_state(float CarrierState::*which, float v)
     {
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        std::vector<CarrierState> t((size_t)nstreams);
-        GRHIP_HIP(hipMemcpy(t.data(), d_state.p, t.size() * sizeof(CarrierState), hipMemcpyDeviceToHost));
-        for (CarrierState &e : t) e.*which = v;
-        GRHIP_HIP(hipMemcpy(d_state.p, t.data(), t.size() * sizeof(CarrierState), hipMemcpyHostToDevice));
-        return GRHIP_OK;
+        return edit_states<CarrierState>(d_state, [&](CarrierState &e) { e.*which = v; });
     }
 
     int set_frequency(float f)              // gri_control_loop.cc:126-135
@@ -121,22 +90,11 @@ struct CarrierBlock : HandleBase {
         return set_state(&CarrierState::phase, ControlLoop::set_phase(ph));
     }
 
-    int get_state(int s, CarrierState *v)
-    {
-        if (s < 0 || s >= nstreams) return fail(GRHIP_EINVAL, "stream %d of %d", s, nstreams);
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        GRHIP_HIP(hipMemcpy(v, d_state.as<CarrierState>() + s, sizeof(CarrierState), hipMemcpyDeviceToHost));
-        return GRHIP_OK;
-    }
-
     int get_float(int s, float CarrierState::*which, float *v)
     {
         if (!v) return fail(GRHIP_EINVAL, "null argument");
         CarrierState t;
-        int rc = get_state(s, &t);
+        int rc = read_state(d_state, s, &t);
         if (!rc) *v = t.*which;
         return rc;
     }
@@ -145,7 +103,7 @@ struct CarrierBlock : HandleBase {
     {
         if (!locked) return fail(GRHIP_EINVAL, "null argument");
         CarrierState t;
-        int rc = get_state(s, &t);
+        int rc = read_state(d_state, s, &t);
         if (rc) return rc;
         std::lock_guard<std::mutex> lk(setter_mutex);
         *locked = fabsf(t.locksig) > lock_threshold ? 1 : 0;
@@ -168,19 +126,17 @@ struct CarrierBlock : HandleBase {
 
     int work_device(int n_in, const void *d_in, void *d_out, void *d_freq, void *stream)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_in == 0) return GRHIP_OK;
-        if (!d_in || !d_out) return fail(GRHIP_EINVAL, "null buffer");
-        if (((uintptr_t)d_in & 7) || ((uintptr_t)d_out & (out_item() - 1)) || ((uintptr_t)d_freq & 3))
-            return fail(GRHIP_EINVAL, "items not naturally aligned");
-        const char *a = (const char *)d_in, *b = (const char *)d_out, *c = (const char *)d_freq;
+        const int c = check_count(n_in);
+        if (c <= 0) return c;
+        int rc = check_io(d_in, 8, d_out, out_item());
+        if (rc) return rc;
+        if (!aligned(d_freq, 4)) return fail(GRHIP_EINVAL, "items not naturally aligned");
         const size_t items = (size_t)nstreams * (size_t)n_in;
         const size_t in_bytes = items * 8, out_bytes = items * out_item(), f_bytes = items * 4;
-        if (a < b + out_bytes && b < a + in_bytes) return fail(GRHIP_EINVAL, "carrier loop: the output may not overlap the input");
-        if (c && ((a < c + f_bytes && c < a + in_bytes) || (b < c + f_bytes && c < b + out_bytes)))
+        if ((rc = check_apart("carrier loop", d_in, in_bytes, d_out, out_bytes))) return rc;
+        if (overlap(d_in, in_bytes, d_freq, f_bytes) || overlap(d_out, out_bytes, d_freq, f_bytes))
             return fail(GRHIP_EINVAL, "carrier loop: the frequency output may not overlap the other buffers");
-        int rc = bind();
-        if (rc) return rc;
+        if ((rc = bind())) return rc;
         hipStream_t st = pick(stream);
         std::lock_guard<std::mutex> lk(setter_mutex);
         CarrierLaunch l;
@@ -193,23 +149,16 @@ struct CarrierBlock : HandleBase {
 
     int work(int n_in, const void *in, void *out, void *freq_out)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_in == 0) return GRHIP_OK;
-        if (!in || !out) return fail(GRHIP_EINVAL, "null buffer");
-        int rc = bind();
-        if (rc) return rc;
-        const size_t items = (size_t)nstreams * (size_t)n_in;
-        const size_t in_bytes = items * 8, out_bytes = items * out_item();
+        // the frequencies are staged behind the output, 16-byte aligned
+        const size_t items = (size_t)nstreams * (size_t)n_in, out_bytes = items * out_item();
         const size_t f_off = (out_bytes + 15) & ~(size_t)15, f_bytes = freq_out ? items * 4 : 0;
-        const long long r = host_call(in, in_bytes, in_bytes + 16, f_off + f_bytes + 16, out, out_item(), [&](void *d_in, void *d_out, hipStream_t st) {
-            const int e = work_device(n_in, d_in, d_out, freq_out ? (char *)d_out + f_off : nullptr, st);
-            return e ? (long long)e : (long long)items;
+        int rc = host_work(n_in, 8, in, (size_t)n_in, out_item(), out, f_off - out_bytes + f_bytes, [&](void *d_in, void *d_out, hipStream_t st) {
+            return work_device(n_in, d_in, d_out, freq_out ? (char *)d_out + f_off : nullptr, st);
         });
-        if (r < 0) return (int)r;
-        if (freq_out) {     // host_call has synchronised; the staged frequencies are still there
-            GRHIP_D2H(this, freq_out, (char *)stage_out.p + f_off, f_bytes, own_stream);
-            GRHIP_HIP(hipStreamSynchronize(own_stream));
-        }
+        if (rc || n_in == 0 || !freq_out) return rc;
+        // host_work has synchronised; the staged frequencies are still there
+        GRHIP_D2H(this, freq_out, (char *)stage_out.p + f_off, f_bytes, own_stream);
+        GRHIP_HIP(hipStreamSynchronize(own_stream));
         return GRHIP_OK;
     }
 };

@@ -379,7 +379,7 @@ int grhip_dmr_chain_run_device(grhip_dmr_chain *h, const void *d_in, size_t n_sa
     return GRHIP_OK;
 }
 
-int grhip_dmr_chain_set_mode(grhip_dmr_chain *h, int mode)
+int grhip_dmr_chain_set_mode(grhip_dmr_chain *h, int mode)      // no lock, as the FIR handles' (capi_fir.hip set_mode_of)
 {
     if (!h || !mode_valid(mode)) return fail(GRHIP_EINVAL, "bad mode");
     h->mode = mode;

@@ -12,6 +12,7 @@
 #include "control_loop.h"
 #include "digital_kernels.h"
 #include "grhip_internal.h"
+#include "stream_block.h"
 
 using namespace grhip;
 
@@ -51,24 +52,6 @@ struct ConstOnDevice {
     }
 };
 
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    return a && b && (const char *)a < (const char *)b + nb && (const char *)b < (const char *)a + na;
-}
-
-struct StreamBlock : HandleBase {
-    int nstreams = 1;
-    int mode = GRHIP_MODE_FAST;
-
-    int set_mode(int m)
-    {
-        if (!mode_valid(m)) return fail(GRHIP_EINVAL, "bad mode %d", m);
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        mode = m;
-        return GRHIP_OK;
-    }
-};
-
 // ---- constellation_decoder_cb ------------------------------------------------------------------------------------------
 struct DecoderBlock : StreamBlock {
     ConstOnDevice tab;
@@ -83,38 +66,26 @@ struct DecoderBlock : StreamBlock {
     }
     int set_streams(int S)
     {
-        if (S < 1 || S > 65535) return fail(GRHIP_EINVAL, "1 .. 65535 streams");
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        nstreams = S;
-        return GRHIP_OK;
+        return StreamBlock::set_streams(S, [] { return GRHIP_OK; });        // nothing kept per stream
     }
     int work_device(int n_out, const void *d_in, void *d_out, void *stream)
     {
-        if (n_out < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_out == 0) return GRHIP_OK;
-        if (!d_in || !d_out) return fail(GRHIP_EINVAL, "null buffer");
-        if ((uintptr_t)d_in & 7) return fail(GRHIP_EINVAL, "items not naturally aligned");
-        int rc = bind();
+        const int c = check_count(n_out);
+        if (c <= 0) return c;
+        int rc = check_io(d_in, 8, d_out, 1);
         if (rc) return rc;
+        if ((rc = bind())) return rc;
         hipStream_t st = pick(stream);
         std::lock_guard<std::mutex> lk(setter_mutex);
         const size_t items = (size_t)nstreams * (size_t)n_out;
-        if (overlap(d_in, items * tab.dev.dim * 8, d_out, items)) return fail(GRHIP_EINVAL, "constellation_decoder_cb: the output may not overlap the input");
+        if ((rc = check_apart("constellation_decoder_cb", d_in, items * tab.dev.dim * 8, d_out, items))) return rc;
         return decoder_launch(tab.dev, (const float2 *)d_in, (unsigned char *)d_out, n_out, nstreams, st);
     }
-    int work(int n_out, const void *in, void *out)
+    int work(int n_out, const void *in, void *out)      // every output item takes dim complex items
     {
-        if (n_out < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_out == 0) return GRHIP_OK;
-        if (!in || !out) return fail(GRHIP_EINVAL, "null buffer");
-        int rc = bind();
-        if (rc) return rc;
-        const size_t items = (size_t)nstreams * (size_t)n_out, in_bytes = items * tab.dev.dim * 8;
-        const long long r = host_call(in, in_bytes, in_bytes + 16, items + 16, out, 1, [&](void *d_in, void *d_out, hipStream_t st) {
-            const int e = work_device(n_out, d_in, d_out, st);
-            return e ? (long long)e : (long long)items;
+        return host_work(n_out, (size_t)tab.dev.dim * 8, in, (size_t)n_out, 1, out, 0, [&](void *d_in, void *d_out, hipStream_t st) {
+            return work_device(n_out, d_in, d_out, st);
         });
-        return r < 0 ? (int)r : GRHIP_OK;
     }
 };
 
@@ -155,41 +126,28 @@ struct ByteBlock : StreamBlock {
     }
     int set_streams(int S)
     {
-        if (S < 1 || S > 65535) return fail(GRHIP_EINVAL, "1 .. 65535 streams");
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        nstreams = S;
-        return is_map ? GRHIP_OK : reset_prev();
+        return StreamBlock::set_streams(S, [&] { return is_map ? GRHIP_OK : reset_prev(); });
     }
     int work_device(int n, const void *d_in, void *d_out, void *stream)
     {
-        if (n < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n == 0) return GRHIP_OK;
-        if (!d_in || !d_out) return fail(GRHIP_EINVAL, "null buffer");
-        int rc = bind();
+        const int c = check_count(n);
+        if (c <= 0) return c;
+        int rc = check_io(d_in, 1, d_out, 1);
         if (rc) return rc;
+        if ((rc = bind())) return rc;
         hipStream_t st = pick(stream);
         std::lock_guard<std::mutex> lk(setter_mutex);
         const size_t items = (size_t)nstreams * (size_t)n;
+        // map_bb runs in place; diff_decoder_bb reads the byte in front of the one it writes
         if (is_map) return map_launch((const unsigned char *)d_in, (unsigned char *)d_out, (long long)items, d_aux.as<unsigned char>(), st);
-        if (overlap(d_in, items, d_out, items)) return fail(GRHIP_EINVAL, "diff_decoder_bb: the output may not overlap the input");
+        if ((rc = check_apart("diff_decoder_bb", d_in, items, d_out, items))) return rc;
         return diff_decoder_launch((const unsigned char *)d_in, (unsigned char *)d_out, n, nstreams, modulus, d_aux.as<unsigned>(), 1, st);
     }
     int work(int n, const void *in, void *out)
     {
-        if (n < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n == 0) return GRHIP_OK;
-        if (!in || !out) return fail(GRHIP_EINVAL, "null buffer");
-        int rc = bind();
-        if (rc) return rc;
-        const size_t items = (size_t)nstreams * (size_t)n;
-        const long long r = host_call(in, items, items + 16, items + 16, out, 1, [&](void *d_in, void *d_out, hipStream_t st) {
-            const int e = work_device(n, d_in, d_out, st);
-            return e ? (long long)e : (long long)items;
+        return host_work(n, 1, in, (size_t)n, 1, out, 0, [&](void *d_in, void *d_out, hipStream_t st) {
+            return work_device(n, d_in, d_out, st);
         });
-        return r < 0 ? (int)r : GRHIP_OK;
     }
 };
 
@@ -205,12 +163,7 @@ struct ReceiverBlock : StreamBlock {
     int engine = 1;
     DevBuf d_map, d_a, d_b;
 
-    int fill_state()
-    {
-        int rc = d_state.reserve((size_t)nstreams * sizeof(ConstState));
-        if (rc) return rc;
-        return zero_device(d_state.p, (size_t)nstreams * sizeof(ConstState));              // gri_control_loop.cc:35
-    }
+    int restart() { return fill_state(d_state, ConstState{}); }                 // gri_control_loop.cc:35
 
     int init(const grhip_constellation *cons, float loop_bw, float fmin, float fmax, int dev)
     {
@@ -226,7 +179,7 @@ struct ReceiverBlock : StreamBlock {
         int rc = init_device(dev);
         if (rc) return rc;
         if ((rc = tab.upload(c))) return rc;
-        return fill_state();
+        return restart();
     }
 
     int init_demod(const grhip_constellation *cons, float loop_bw, float fmin, float fmax, int diff, int gray_coded, int dev)
@@ -275,13 +228,7 @@ struct ReceiverBlock : StreamBlock {
 
     int set_streams(int S)
     {
-        if (S < 1 || S > 65535) return fail(GRHIP_EINVAL, "1 .. 65535 streams");
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        nstreams = S;
-        return fill_state();
+        return StreamBlock::set_streams(S, [&] { return restart(); });
     }
 
     // a setter of the loop's parameters (control_loop.h): false is the reference's std::out_of_range
@@ -298,15 +245,7 @@ struct ReceiverBlock : StreamBlock {
     }
     int set_state(float ConstState::*which, float v)
     {
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        std::vector<ConstState> t((size_t)nstreams);
-        GRHIP_HIP(hipMemcpy(t.data(), d_state.p, t.size() * sizeof(ConstState), hipMemcpyDeviceToHost));
-        for (ConstState &e : t) e.*which = v;
-        GRHIP_HIP(hipMemcpy(d_state.p, t.data(), t.size() * sizeof(ConstState), hipMemcpyHostToDevice));
-        return GRHIP_OK;
+        return edit_states<ConstState>(d_state, [&](ConstState &e) { e.*which = v; });
     }
     int set_frequency(float f)              // gri_control_loop.cc:126-135
     {
@@ -325,15 +264,10 @@ struct ReceiverBlock : StreamBlock {
     int get_float(int s, float ConstState::*which, float *v)
     {
         if (!v) return fail(GRHIP_EINVAL, "null argument");
-        if (s < 0 || s >= nstreams) return fail(GRHIP_EINVAL, "stream %d of %d", s, nstreams);
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
         ConstState t;
-        GRHIP_HIP(hipMemcpy(&t, d_state.as<ConstState>() + s, sizeof(ConstState), hipMemcpyDeviceToHost));
-        *v = t.*which;
-        return GRHIP_OK;
+        int rc = read_state(d_state, s, &t);
+        if (!rc) *v = t.*which;
+        return rc;
     }
 
     ReceiverLaunch launch_of(int n, const void *d_in, void *d_sym)
@@ -348,16 +282,16 @@ struct ReceiverBlock : StreamBlock {
     // the receiver: symbols and, all three or none, error, phase and frequency
     int work_device(int n, const void *d_in, void *d_sym, void *d_err, void *d_phase, void *d_freq, void *stream)
     {
-        if (n < 0) return fail(GRHIP_EINVAL, "negative item count");
+        const int go = check_count(n);
+        if (go < 0) return go;
         const int given = (d_err != nullptr) + (d_phase != nullptr) + (d_freq != nullptr);
         if (given != 0 && given != 3)
             return fail(GRHIP_EINVAL, "constellation_receiver_cb: the error, phase and frequency outputs come all three or not at all");
-        if (n == 0) return GRHIP_OK;
-        if (!d_in || !d_sym) return fail(GRHIP_EINVAL, "null buffer");
-        if (((uintptr_t)d_in & 7) || ((uintptr_t)d_err & 3) || ((uintptr_t)d_phase & 3) || ((uintptr_t)d_freq & 3))
-            return fail(GRHIP_EINVAL, "items not naturally aligned");
-        int rc = bind();
+        if (go == 0) return GRHIP_OK;
+        int rc = check_io(d_in, 8, d_sym, 1);
         if (rc) return rc;
+        if (!aligned(d_err, 4) || !aligned(d_phase, 4) || !aligned(d_freq, 4)) return fail(GRHIP_EINVAL, "items not naturally aligned");
+        if ((rc = bind())) return rc;
         hipStream_t st = pick(stream);
         std::lock_guard<std::mutex> lk(setter_mutex);
         const size_t items = (size_t)nstreams * (size_t)n;
@@ -373,43 +307,38 @@ struct ReceiverBlock : StreamBlock {
 
     int work(int n, const void *in, void *sym, void *err, void *phase, void *freq)
     {
-        if (n < 0) return fail(GRHIP_EINVAL, "negative item count");
+        const int go = check_count(n);
+        if (go < 0) return go;
         const int given = (err != nullptr) + (phase != nullptr) + (freq != nullptr);
         if (given != 0 && given != 3)
             return fail(GRHIP_EINVAL, "constellation_receiver_cb: the error, phase and frequency outputs come all three or not at all");
-        if (n == 0) return GRHIP_OK;
-        if (!in || !sym) return fail(GRHIP_EINVAL, "null buffer");
-        int rc = bind();
-        if (rc) return rc;
-        const size_t items = (size_t)nstreams * (size_t)n, in_bytes = items * 8;
+        // the three float outputs are staged behind the symbols, each 16-byte aligned
+        const size_t items = (size_t)nstreams * (size_t)n;
         const size_t f_off = (items + 15) & ~(size_t)15, f_bytes = items * 4, f_step = (f_bytes + 15) & ~(size_t)15;
-        const long long r = host_call(in, in_bytes, in_bytes + 16, f_off + (given ? 3 * f_step : 0) + 16, sym, 1, [&](void *d_in, void *d_out, hipStream_t st) {
+        int rc = host_work(n, 8, in, (size_t)n, 1, sym, f_off - items + (given ? 3 * f_step : 0), [&](void *d_in, void *d_out, hipStream_t st) {
             char *f = (char *)d_out + f_off;
-            const int e = work_device(n, d_in, d_out, given ? f : nullptr, given ? f + f_step : nullptr, given ? f + 2 * f_step : nullptr, st);
-            return e ? (long long)e : (long long)items;
+            return work_device(n, d_in, d_out, given ? f : nullptr, given ? f + f_step : nullptr, given ? f + 2 * f_step : nullptr, st);
         });
-        if (r < 0) return (int)r;
-        if (given) {        // host_call has synchronised; the staged floats are still there
-            void *dst[3] = {err, phase, freq};
-            for (int i = 0; i < 3; ++i) GRHIP_D2H(this, dst[i], (char *)stage_out.p + f_off + i * f_step, f_bytes, own_stream);
-            GRHIP_HIP(hipStreamSynchronize(own_stream));
-        }
+        if (rc || go == 0 || !given) return rc;
+        // host_work has synchronised; the staged floats are still there
+        void *dst[3] = {err, phase, freq};
+        for (int i = 0; i < 3; ++i) GRHIP_D2H(this, dst[i], (char *)stage_out.p + f_off + i * f_step, f_bytes, own_stream);
+        GRHIP_HIP(hipStreamSynchronize(own_stream));
         return GRHIP_OK;
     }
 
     // constellation_demod_cb: n complex items in, n * k bytes out per stream
     int demod_device(int n, const void *d_in, void *d_bits, void *stream)
     {
-        if (n < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n == 0) return GRHIP_OK;
-        if (!d_in || !d_bits) return fail(GRHIP_EINVAL, "null buffer");
-        if ((uintptr_t)d_in & 7) return fail(GRHIP_EINVAL, "items not naturally aligned");
-        int rc = bind();
+        const int go = check_count(n);
+        if (go <= 0) return go;
+        int rc = check_io(d_in, 8, d_bits, 1);
         if (rc) return rc;
+        if ((rc = bind())) return rc;
         hipStream_t st = pick(stream);
         std::lock_guard<std::mutex> lk(setter_mutex);
         const size_t items = (size_t)nstreams * (size_t)n;
-        if (overlap(d_in, items * 8, d_bits, items * k)) return fail(GRHIP_EINVAL, "constellation_demod_cb: the output may not overlap the input");
+        if ((rc = check_apart("constellation_demod_cb", d_in, items * 8, d_bits, items * k))) return rc;
         const unsigned char *map = use_map ? d_map.as<unsigned char>() : nullptr;
         if (engine == 1) {
             ReceiverLaunch l = launch_of(n, d_in, d_bits);
@@ -436,17 +365,9 @@ struct ReceiverBlock : StreamBlock {
 
     int demod_work(int n, const void *in, void *bits)
     {
-        if (n < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n == 0) return GRHIP_OK;
-        if (!in || !bits) return fail(GRHIP_EINVAL, "null buffer");
-        int rc = bind();
-        if (rc) return rc;
-        const size_t items = (size_t)nstreams * (size_t)n;
-        const long long r = host_call(in, items * 8, items * 8 + 16, items * k + 16, bits, 1, [&](void *d_in, void *d_out, hipStream_t st) {
-            const int e = demod_device(n, d_in, d_out, st);
-            return e ? (long long)e : (long long)(items * k);
+        return host_work(n, 8, in, (size_t)n * k, 1, bits, 0, [&](void *d_in, void *d_out, hipStream_t st) {
+            return demod_device(n, d_in, d_out, st);
         });
-        return r < 0 ? (int)r : GRHIP_OK;
     }
 };
 

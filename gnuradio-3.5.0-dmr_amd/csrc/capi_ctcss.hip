@@ -86,8 +86,8 @@ struct grhip_ctcss_squelch_ff : SquelchMachine {
 
     int work_device(int n_in, const void *d_in, void *d_out, int *d_produced, void *stream)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_in == 0) return GRHIP_OK;
+        const int c0 = check_count(n_in);
+        if (c0 <= 0) return c0;
         int rc = check_work(n_in, d_in, d_out, d_produced, sizeof(float));
         if (rc) return rc;
         if ((rc = bind())) return rc;
@@ -120,7 +120,7 @@ struct grhip_ctcss_squelch_ff : SquelchMachine {
 
     int set_streams(int S)
     {
-        return SquelchMachine::set_streams(S, [&] { return restart(); });
+        return StreamBlock::set_streams(S, [&] { return restart(); });
     }
 
     int set_level(float v)
@@ -132,14 +132,10 @@ struct grhip_ctcss_squelch_ff : SquelchMachine {
 
     int get_ctcss(int s, int *mute, int *pend)
     {
-        if (s < 0 || s >= nstreams) return fail(GRHIP_EINVAL, "stream %d of %d", s, nstreams);
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        unsigned char m = 0;
-        GRHIP_HIP(hipMemcpy(&m, d_mute.as<unsigned char>() + s, 1, hipMemcpyDeviceToHost));
+        unsigned char m = 0;                // d_mute: every stream's decision, one byte
+        if (int rc = read_state(d_mute, s, &m)) return rc;
         if (mute) *mute = m;
+        std::lock_guard<std::mutex> lk(setter_mutex);
         if (pend) *pend = pending;
         return GRHIP_OK;
     }

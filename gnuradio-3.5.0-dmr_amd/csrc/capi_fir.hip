@@ -482,7 +482,8 @@ int XlatingCore::run(int mode, const float2 *d_in, long long n_in, long long n_o
 // ============================================================================
 // gr_fir_filter_XXX
 // ============================================================================
-// the body of every set_mode entry
+// the body of every set_mode entry.  Not ModeBlock's (stream_block.h): these handles read the mode in work outside
+// setter_mutex, which guards only their latched taps, so the setter takes no lock either
 template <class H>
 static int set_mode_of(H *h, int mode)
 {

@@ -12,6 +12,7 @@
 #include "fm_demod.h"
 #include "grhip_internal.h"
 #include "iir.h"
+#include "stream_block.h"
 
 using namespace grhip;
 
@@ -20,13 +21,11 @@ namespace {
 constexpr int FMD_MAX_DECIM = 1 << 16;
 constexpr int FMD_MAX_TAPS = 1 << 16;
 
-struct FmDemodBlock : HandleBase {
+struct FmDemodBlock : StreamBlock {
     float k = 1.f;
     std::vector<double> ff, fb;         // the de-emphasis taps; both empty: none
     int D = 1;
     std::vector<float> taps;            // forward order
-    int nstreams = 1;
-    int mode = GRHIP_MODE_FAST;
     int pos = 0;                        // items taken so far, modulo D
     int cur = 0;                        // which copy of the state is current
     bool deemph = false, fused_ok = false, iir_chunk = false;
@@ -115,23 +114,9 @@ struct FmDemodBlock : HandleBase {
         return zero_state();
     }
 
-    int set_mode(int m)
-    {
-        if (!mode_valid(m)) return fail(GRHIP_EINVAL, "bad mode %d", m);
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        mode = m;
-        return GRHIP_OK;
-    }
-
     int set_streams(int S)
     {
-        if (S < 1 || S > 65535) return fail(GRHIP_EINVAL, "1 .. 65535 streams");
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        nstreams = S;
-        return zero_state();
+        return StreamBlock::set_streams(S, [&] { return zero_state(); });
     }
 
     int engine()
@@ -193,23 +178,21 @@ struct FmDemodBlock : HandleBase {
 
     int work_device(int n_in, const void *d_in, void *d_out, int *d_produced, void *stream)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
+        const int c = check_count(n_in);
+        if (c < 0) return c;
         int rc = bind();
         if (rc) return rc;
         hipStream_t st = pick(stream);
-        if (n_in == 0) {
+        if (c == 0) {       // nothing but the count, on the caller's stream
             if (d_produced) GRHIP_HIP(hipMemsetAsync(d_produced, 0, sizeof(int), st));
             return GRHIP_OK;
         }
-        if (!d_in || !d_out) return fail(GRHIP_EINVAL, "null buffer");
-        if (((uintptr_t)d_in & (sizeof(float2) - 1)) || ((uintptr_t)d_out & (sizeof(float) - 1)))
-            return fail(GRHIP_EINVAL, "items not naturally aligned");
+        if ((rc = check_io(d_in, sizeof(float2), d_out, sizeof(float)))) return rc;
         std::lock_guard<std::mutex> lk(setter_mutex);
         int o0;
-        const int np = produced_of(n_in, &o0);
-        const char *a = (const char *)d_in, *b = (const char *)d_out;
+        const int np = produced_of(n_in, &o0);      // depends on the position: under the lock
         const size_t in_bytes = (size_t)nstreams * (size_t)n_in * sizeof(float2), out_bytes = (size_t)nstreams * (size_t)np * sizeof(float);
-        if (a < b + out_bytes && b < a + in_bytes) return fail(GRHIP_EINVAL, "fm_demod_cf: the output may not overlap the input");
+        if ((rc = check_apart("fm_demod_cf", d_in, in_bytes, d_out, out_bytes))) return rc;
         const bool fast = mode_fast(mode);
         if (fast && fused_ok) {
             FmdFused f;
@@ -228,26 +211,20 @@ struct FmDemodBlock : HandleBase {
 
     int work(int n_in, const void *in, void *out, int *produced_out)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
+        const int c = check_count(n_in);
+        if (c < 0) return c;
         if (produced_out) *produced_out = 0;
-        if (n_in == 0) return GRHIP_OK;
-        if (!in || !out) return fail(GRHIP_EINVAL, "null buffer");
-        int rc = bind();
-        if (rc) return rc;
+        if (c == 0) return GRHIP_OK;
         int np;
         {
             std::lock_guard<std::mutex> lk(setter_mutex);
             np = produced_of(n_in, nullptr);
         }
-        const size_t in_bytes = (size_t)nstreams * (size_t)n_in * sizeof(float2);
-        const size_t out_bytes = (size_t)nstreams * (size_t)np * sizeof(float);
-        const long long r = host_call(in, in_bytes, in_bytes + 16, out_bytes + 16, out, sizeof(float), [&](void *d_in, void *d_out, hipStream_t st) {
-            const int e = work_device(n_in, d_in, d_out, nullptr, st);
-            return e ? (long long)e : (long long)nstreams * np;
+        const int rc = host_work(n_in, sizeof(float2), in, (size_t)np, sizeof(float), out, 0, [&](void *d_in, void *d_out, hipStream_t st) {
+            return work_device(n_in, d_in, d_out, nullptr, st);
         });
-        if (r < 0) return (int)r;
-        if (produced_out) *produced_out = np;
-        return GRHIP_OK;
+        if (!rc && produced_out) *produced_out = np;
+        return rc;
     }
 };
 

@@ -10,20 +10,19 @@
 #include <vector>
 
 #include "grhip_internal.h"
+#include "stream_block.h"
 #include "iir.h"
 
 using namespace grhip;
 
 namespace {
 
-struct IirBlock : HandleBase {
+struct IirBlock : StreamBlock {
     std::vector<double> ff, fb;             // the taps in force
     std::vector<double> new_ff, new_fb;     // latched by set_taps
     bool updated = false;
     bool can_chunk = false;                 // of the taps in force
     IirCarry carry = {};
-    int nstreams = 1;
-    int mode = GRHIP_MODE_FAST;
     DevBuf d_taps, d_x, d_y, d_scratch;
 
     static int check_taps(const double *fft, size_t n, const double *fbt, size_t m)
@@ -79,23 +78,9 @@ struct IirBlock : HandleBase {
         return GRHIP_OK;
     }
 
-    int set_mode(int m)
-    {
-        if (!mode_valid(m)) return fail(GRHIP_EINVAL, "bad mode %d", m);
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        mode = m;
-        return GRHIP_OK;
-    }
-
     int set_streams(int S)
     {
-        if (S < 1 || S > 65535) return fail(GRHIP_EINVAL, "1 .. 65535 streams");
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        nstreams = S;
-        return zero_state();
+        return StreamBlock::set_streams(S, [&] { return zero_state(); });
     }
 
     int chunked()
@@ -107,15 +92,13 @@ struct IirBlock : HandleBase {
 
     int work_device(int n_in, const void *d_in, void *d_out, void *stream)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_in == 0) return GRHIP_OK;
-        if (!d_in || !d_out) return fail(GRHIP_EINVAL, "null buffer");
-        if (((uintptr_t)d_in | (uintptr_t)d_out) & (sizeof(float) - 1)) return fail(GRHIP_EINVAL, "items not naturally aligned");
-        const char *a = (const char *)d_in, *b = (const char *)d_out;
+        const int c = check_count(n_in);
+        if (c <= 0) return c;
         const size_t bytes = (size_t)nstreams * (size_t)n_in * sizeof(float);
-        if (a < b + bytes && b < a + bytes) return fail(GRHIP_EINVAL, "iir_filter_ffd: the output may not overlap the input");
-        int rc = bind();
-        if (rc) return rc;
+        int rc;
+        if ((rc = check_io(d_in, sizeof(float), d_out, sizeof(float))) || (rc = check_apart("iir_filter_ffd", d_in, bytes, d_out, bytes)))
+            return rc;
+        if ((rc = bind())) return rc;
         hipStream_t st = pick(stream);
         std::lock_guard<std::mutex> lk(setter_mutex);
         if (updated) {                                                  // gr_iir_filter_ffd.cc:66-69
@@ -140,17 +123,9 @@ struct IirBlock : HandleBase {
 
     int work(int n_in, const void *in, void *out)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_in == 0) return GRHIP_OK;
-        if (!in || !out) return fail(GRHIP_EINVAL, "null buffer");
-        int rc = bind();
-        if (rc) return rc;
-        const size_t bytes = (size_t)nstreams * (size_t)n_in * sizeof(float);
-        const long long r = host_call(in, bytes, bytes + 16, bytes + 16, out, sizeof(float), [&](void *d_in, void *d_out, hipStream_t st) {
-            const int e = work_device(n_in, d_in, d_out, st);
-            return e ? (long long)e : (long long)nstreams * n_in;
+        return host_work(n_in, sizeof(float), in, (size_t)n_in, sizeof(float), out, 0, [&](void *d_in, void *d_out, hipStream_t st) {
+            return work_device(n_in, d_in, d_out, st);
         });
-        return r < 0 ? (int)r : GRHIP_OK;
     }
 };
 

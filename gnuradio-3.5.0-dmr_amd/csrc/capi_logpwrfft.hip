@@ -28,6 +28,7 @@
 #include "grhip_internal.h"
 #include "logpwr_plan.h"
 #include "spectrum.h"
+#include "stream_block.h"
 
 using namespace grhip;
 
@@ -61,9 +62,9 @@ int decimation_of(double decim, int *out)
 
 }  // namespace
 
-struct LogPwrFft : HandleBase {
+struct LogPwrFft : StreamBlock {
     bool real_in = false;
-    int N = 0, nstreams = 1, mode = GRHIP_MODE_FAST;
+    int N = 0;
     double sample_rate = 0, vec_rate = 0, avg_alpha = 1.0;
     bool average = false;
     int decim = 1;
@@ -96,12 +97,11 @@ struct LogPwrFft : HandleBase {
 
     int work_device(int n_frames, const void *d_in, void *d_out, void *stream)
     {
-        if (n_frames < 0) return fail(GRHIP_EINVAL, "negative frame count");
-        if (n_frames == 0) return 0;
-        if (!d_in || !d_out) return fail(GRHIP_EINVAL, "null buffer");
-        if (((uintptr_t)d_in & (item() - 1)) || ((uintptr_t)d_out & 3)) return fail(GRHIP_EINVAL, "items not naturally aligned");
-        int rc = bind();
+        const int c = check_count(n_frames);
+        if (c <= 0) return c;
+        int rc = check_io(d_in, item(), d_out, 4);
         if (rc) return rc;
+        if ((rc = bind())) return rc;
         std::lock_guard<std::mutex> lk(setter_mutex);
         return run(n_frames, d_in, d_out, pick(stream));
     }
@@ -146,12 +146,12 @@ struct LogPwrFft : HandleBase {
 
     int work(int n_frames, const void *in, void *out)
     {
-        if (n_frames < 0) return fail(GRHIP_EINVAL, "negative frame count");
-        if (n_frames == 0) return 0;
+        const int c = check_count(n_frames);
+        if (c <= 0) return c;
         if (!in || !out) return fail(GRHIP_EINVAL, "null buffer");
         int rc = bind();
         if (rc) return rc;
-        // one lock over the count that sizes the staging buffers and the launch that fills them: a setter cannot change
+        // not host_work: one lock over the count that sizes the staging buffers and the launch that fills them: a setter cannot change
         // the decimation in between
         std::lock_guard<std::mutex> lk(setter_mutex);
         const long long p = ctr.produced(n_frames);
@@ -251,19 +251,10 @@ int grhip_logpwrfft_f_create(grhip_logpwrfft_f **h, double sample_rate, int fft_
 
 #define GRHIP_LOGPWRFFT_ENTRIES(NAME)                                                                                  \
     void grhip_##NAME##_destroy(grhip_##NAME *h) { destroy_handle(h); }                                               \
-    GRHIP_LOGPWRFFT_SETTER(NAME, set_mode, (grhip_##NAME *h, int mode),                                                \
-        if (!mode_valid(mode)) return fail(GRHIP_EINVAL, "bad mode %d", mode);                                         \
-        h->mode = mode; return GRHIP_OK;)                                                                              \
+    int grhip_##NAME##_set_mode(grhip_##NAME *h, int mode) { return h ? h->set_mode(mode) : fail(GRHIP_EINVAL, "null handle"); } \
     int grhip_##NAME##_set_streams(grhip_##NAME *h, int nstreams)                                                      \
     {                                                                                                                  \
-        if (!h) return fail(GRHIP_EINVAL, "null handle");                                                              \
-        if (nstreams < 1 || nstreams > 65535) return fail(GRHIP_EINVAL, "1 .. 65535 streams");                         \
-        int rc = h->bind();                                                                                            \
-        if (rc) return rc;                                                                                             \
-        std::lock_guard<std::mutex> lk(h->setter_mutex);                                                               \
-        if ((rc = h->drain(h->own_stream))) return rc;                                                                 \
-        h->nstreams = nstreams;                                                                                        \
-        return h->restart();                                                                                           \
+        return h ? h->set_streams(nstreams, [&] { return h->restart(); }) : fail(GRHIP_EINVAL, "null handle");         \
     }                                                                                                                  \
     /* logpwrfft.py:70-108 */                                                                                          \
     GRHIP_LOGPWRFFT_SETTER(NAME, set_decimation, (grhip_##NAME *h, double decim), return h->set_decim(decim);)         \

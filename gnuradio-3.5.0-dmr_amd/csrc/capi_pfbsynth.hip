@@ -16,12 +16,12 @@
 
 #include "grhip_internal.h"
 #include "pfb_synth.h"
+#include "stream_block.h"
 
 using namespace grhip;
 
-struct grhip_pfb_synthesis_filterbank_ccf : HandleBase {
+struct grhip_pfb_synthesis_filterbank_ccf : ModeBlock {
     int M = 1, tpf = 1;
-    int mode = GRHIP_MODE_FAST;
     std::vector<float> new_taps;        // latched by set_taps
     bool updated = false;
     DevBuf d_taps, d_tw, d_state[2], d_scratch;
@@ -214,10 +214,7 @@ int grhip_pfb_synthesis_filterbank_ccf_set_taps(grhip_pfb_synthesis_filterbank_c
 int grhip_pfb_synthesis_filterbank_ccf_set_mode(grhip_pfb_synthesis_filterbank_ccf *h, int mode)
 {
     if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (!mode_valid(mode)) return fail(GRHIP_EINVAL, "bad mode %d", mode);
-    std::lock_guard<std::mutex> lk(h->setter_mutex);
-    h->mode = mode;
-    return GRHIP_OK;
+    return h->set_mode(mode);
 }
 
 int grhip_pfb_synthesis_filterbank_ccf_history(const grhip_pfb_synthesis_filterbank_ccf *h)

@@ -24,6 +24,7 @@
 
 #include "grhip_internal.h"
 #include "resampler.h"
+#include "stream_block.h"
 
 using namespace grhip;
 
@@ -51,13 +52,12 @@ int kind_of(const char *kind, RsKind *k)
 }  // namespace
 
 // what both blocks share: the polyphase bank, the latch of set_taps and the launch
-struct grhip_rs_core : HandleBase {
+struct grhip_rs_core : ModeBlock {
     RsKind kind = RS_CCF;
     bool interp = false;
     bool pad_end = false;               // gr_pfb_interpolator_ccf: the zeros go behind the taps
     unsigned long long I = 1, D = 1, P = 1, Dp = 1;
     int nt = 1, WP = 0;
-    int mode = GRHIP_MODE_FAST;
     unsigned long long ctr = 0;         // d_ctr (rational resampler)
     std::vector<float> new_taps;        // d_new_taps, front padded (floats; x2 for ccc)
     bool updated = false;
@@ -138,14 +138,6 @@ struct grhip_rs_core : HandleBase {
         std::lock_guard<std::mutex> lk(setter_mutex);
         new_taps.swap(padded);
         updated = true;
-        return GRHIP_OK;
-    }
-
-    int set_mode(int m)
-    {
-        if (!mode_valid(m)) return fail(GRHIP_EINVAL, "bad mode %d", m);
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        mode = m;
         return GRHIP_OK;
     }
 

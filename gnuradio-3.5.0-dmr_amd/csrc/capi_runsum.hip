@@ -10,6 +10,7 @@
 // the reference's initial state (all zeros).
 #include "grhip_internal.h"
 #include "running_sum.h"
+#include "stream_block.h"
 
 using namespace grhip;
 
@@ -17,15 +18,14 @@ namespace {
 
 bool aligned_items(const void *a, const void *b, int type)
 {
-    const uintptr_t m = rsum_item(type) - 1;        // the kernels load whole items: gr_complex as one float2
-    return !(((uintptr_t)a) & m) && !(((uintptr_t)b) & m);
+    const size_t item = rsum_item(type);            // the kernels load whole items: gr_complex as one float2
+    return aligned(a, item) && aligned(b, item);
 }
 
 }  // namespace
 
-struct grhip_dc_blocker : HandleBase {
-    int type = RSUM_F, D = 32, stages = 4, nstreams = 1;
-    int mode = GRHIP_MODE_FAST;
+struct grhip_dc_blocker : StreamBlock {
+    int type = RSUM_F, D = 32, stages = 4;
     DevBuf d_state, d_hist[2];
     int cur = 0;                                    // d_hist[cur]: the last inputs before the next call
 
@@ -44,12 +44,11 @@ struct grhip_dc_blocker : HandleBase {
 
     int work_device(int noutput_items, const void *d_in, void *d_out, void *stream)
     {
-        if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
-        if (noutput_items == 0) return 0;
-        if (!d_in || !d_out) return fail(GRHIP_EINVAL, "null buffer");
-        if (!aligned_items(d_in, d_out, type)) return fail(GRHIP_EINVAL, "dc_blocker: items not naturally aligned");
-        int rc = bind();
+        const int c = check_count(noutput_items);
+        if (c <= 0) return c;
+        int rc = check_io(d_in, rsum_item(type), d_out, rsum_item(type));
         if (rc) return rc;
+        if ((rc = bind())) return rc;
         std::lock_guard<std::mutex> lk(setter_mutex);
         DcLaunch a;
         a.in = d_in; a.out = d_out; a.n = noutput_items;
@@ -63,19 +62,15 @@ struct grhip_dc_blocker : HandleBase {
 
     int work(int noutput_items, const void *in, void *out)
     {
-        if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
-        if (noutput_items == 0) return 0;
-        if (!in || !out) return fail(GRHIP_EINVAL, "null buffer");
-        int rc = bind();
-        if (rc) return rc;
-        const size_t item = rsum_item(type), S = (size_t)nstreams, bytes = S * (size_t)noutput_items * item;
-        const long long r = host_call(in, bytes, bytes + 16, bytes + 16, out, item * S,
-                                      [&](void *d_in, void *d_out, hipStream_t s) -> long long {
-                                          return work_device(noutput_items, d_in, d_out, s);
-                                      });
-        return (int)r;
+        const size_t item = rsum_item(type);
+        const int rc = host_work(noutput_items, item, in, (size_t)noutput_items, item, out, 0, [&](void *d_in, void *d_out, hipStream_t s) {
+            const int r = work_device(noutput_items, d_in, d_out, s);
+            return r < 0 ? r : GRHIP_OK;
+        });
+        return rc ? rc : noutput_items;
     }
 
+    // not ModeBlock's: each mode keeps a state of its own, so a change of mode restarts the filter
     int set_mode(int m)
     {
         if (!mode_valid(m)) return fail(GRHIP_EINVAL, "bad mode %d", m);
@@ -89,24 +84,17 @@ struct grhip_dc_blocker : HandleBase {
 
     int set_streams(int S)
     {
-        if (S < 1 || S > 65535) return fail(GRHIP_EINVAL, "dc_blocker: 1 .. 65535 streams");
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        nstreams = S;
-        return clear();
+        return StreamBlock::set_streams(S, [&] { return clear(); });
     }
 };
 struct grhip_dc_blocker_ff : grhip_dc_blocker {};
 struct grhip_dc_blocker_cc : grhip_dc_blocker {};
 
-struct grhip_moving_average : HandleBase {
+struct grhip_moving_average : ModeBlock {
     int type = RSUM_F, length = 1, max_iter = 4096, new_length = 1;
     float2 scale = {0.f, 0.f}, new_scale = {0.f, 0.f};
     int iscale = 0, new_iscale = 0;
     bool updated = false;
-    int mode = GRHIP_MODE_FAST;
 
     static int check_length(int length)
     {
@@ -185,9 +173,8 @@ struct grhip_moving_average_cc : grhip_moving_average {};
 struct grhip_moving_average_ss : grhip_moving_average {};
 struct grhip_moving_average_ii : grhip_moving_average {};
 
-struct grhip_integrate : HandleBase {
+struct grhip_integrate : ModeBlock {
     int type = RSUM_F, decim = 1;
-    int mode = GRHIP_MODE_FAST;
 
     int work_device(int noutput_items, const void *d_in, void *d_out, void *stream)
     {
@@ -274,11 +261,7 @@ int create_integrate(H **h, int type, int decim, int device)
 template <class H>
 int set_plain_mode(H *h, int mode)
 {
-    if (!h) return fail(GRHIP_EINVAL, "null handle");
-    if (!mode_valid(mode)) return fail(GRHIP_EINVAL, "bad mode %d", mode);
-    std::lock_guard<std::mutex> lk(h->setter_mutex);
-    h->mode = mode;
-    return GRHIP_OK;
+    return h ? h->set_mode(mode) : fail(GRHIP_EINVAL, "null handle");
 }
 
 }  // namespace

@@ -11,15 +11,11 @@
 
 #include "grhip_internal.h"
 #include "spectrum.h"
+#include "stream_block.h"
 
 using namespace grhip;
 
 namespace {
-
-int check_streams(int S)
-{
-    return (S < 1 || S > 65535) ? fail(GRHIP_EINVAL, "1 .. 65535 streams") : GRHIP_OK;
-}
 
 int check_alpha(double alpha)
 {
@@ -27,26 +23,22 @@ int check_alpha(double alpha)
     return (alpha >= 0.0 && alpha <= 1.0) ? GRHIP_OK : fail(GRHIP_ERANGE, "Alpha must be in [0, 1]");
 }
 
-bool aligned(const void *p, size_t a) { return !((uintptr_t)p & (a - 1)); }
-
 }  // namespace
 
-// ---- the element-wise blocks and the IIR: items of vlen floats (mag^2: vlen complex in) ------------------------------
-struct SpectrumBlock : HandleBase {
-    int vlen = 1, nstreams = 1;
-    int mode = GRHIP_MODE_FAST;
+// ---- the element-wise blocks and the IIR: items of vlen floats (mag^2: vlen complex in); in-place calls are allowed ---
+struct SpectrumBlock : StreamBlock {
+    int vlen = 1;
     virtual ~SpectrumBlock() = default;
     virtual size_t in_elem() const { return 4; }
     virtual int launch(int n, const void *d_in, void *d_out, hipStream_t st) = 0;     // under setter_mutex
 
     int work_device(int noutput_items, const void *d_in, void *d_out, void *stream)
     {
-        if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
-        if (noutput_items == 0) return 0;
-        if (!d_in || !d_out) return fail(GRHIP_EINVAL, "null buffer");
-        if (!aligned(d_in, in_elem()) || !aligned(d_out, 4)) return fail(GRHIP_EINVAL, "items not naturally aligned");
-        int rc = bind();
+        const int c = check_count(noutput_items);
+        if (c <= 0) return c;
+        int rc = check_io(d_in, in_elem(), d_out, 4);
         if (rc) return rc;
+        if ((rc = bind())) return rc;
         std::lock_guard<std::mutex> lk(setter_mutex);
         if ((rc = launch(noutput_items, d_in, d_out, pick(stream)))) return rc;
         return noutput_items;
@@ -54,37 +46,19 @@ struct SpectrumBlock : HandleBase {
 
     int work(int noutput_items, const void *in, void *out)
     {
-        if (noutput_items < 0) return fail(GRHIP_EINVAL, "negative noutput_items");
-        if (noutput_items == 0) return 0;
-        if (!in || !out) return fail(GRHIP_EINVAL, "null buffer");
-        int rc = bind();
-        if (rc) return rc;
-        const size_t elems = (size_t)nstreams * (size_t)noutput_items * vlen;
-        return (int)host_call(in, elems * in_elem(), elems * in_elem() + 16, elems * 4 + 16, out, (size_t)nstreams * vlen * 4,
-                              [&](void *d_in, void *d_out, hipStream_t s) -> long long {
-                                  return work_device(noutput_items, d_in, d_out, s);
-                              });
-    }
-
-    int set_mode(int m)
-    {
-        if (!mode_valid(m)) return fail(GRHIP_EINVAL, "bad mode %d", m);
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        mode = m;
-        return GRHIP_OK;
+        const size_t in_item = (size_t)vlen * in_elem(), out_item = (size_t)vlen * 4;
+        const int rc = host_work(noutput_items, in_item, in, (size_t)noutput_items, out_item, out, 0, [&](void *d_in, void *d_out, hipStream_t s) {
+            const int r = work_device(noutput_items, d_in, d_out, s);
+            return r < 0 ? r : GRHIP_OK;
+        });
+        return rc ? rc : noutput_items;
     }
 
     virtual int restart() { return GRHIP_OK; }      // after nstreams changed, under setter_mutex, streams drained
 
     int set_streams(int S)
     {
-        if (int rc = check_streams(S)) return rc;
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        nstreams = S;
-        return restart();
+        return StreamBlock::set_streams(S, [&] { return restart(); });
     }
 };
 
@@ -140,18 +114,18 @@ struct grhip_single_pole_iir_filter_ff : SpectrumBlock {
     }
 };
 
-struct grhip_keep_one_in_n : HandleBase {
+// items of any size at any address (the launcher picks the word it copies by), in place or not; the mode is not used
+struct grhip_keep_one_in_n : StreamBlock {
     size_t item_size = 4;
-    int nstreams = 1;
     KeepOne ctr;
 
     int work_device(int n_in, const void *d_in, void *d_out, void *stream)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_in == 0) return 0;
-        if (!d_in || !d_out) return fail(GRHIP_EINVAL, "null buffer");
-        int rc = bind();
+        const int c = check_count(n_in);
+        if (c <= 0) return c;
+        int rc = check_io(d_in, 1, d_out, 1);
         if (rc) return rc;
+        if ((rc = bind())) return rc;
         std::lock_guard<std::mutex> lk(setter_mutex);
         const long long p = ctr.produced(n_in);
         if ((rc = keep_one_launch(d_in, d_out, item_size, n_in, p, ctr.first(), ctr.n, nstreams, pick(stream)))) return rc;
@@ -161,8 +135,9 @@ struct grhip_keep_one_in_n : HandleBase {
 
     int work(int n_in, const void *in, void *out)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_in == 0) return 0;
+        // not host_work: the call returns the count that work_device reports, known only under its lock
+        const int c = check_count(n_in);
+        if (c <= 0) return c;
         if (!in || !out) return fail(GRHIP_EINVAL, "null buffer");
         int rc = bind();
         if (rc) return rc;

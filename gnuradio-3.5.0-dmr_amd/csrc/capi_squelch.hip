@@ -36,8 +36,8 @@ struct SquelchBlock : SquelchMachine {
 
     int work_device(int n_in, const void *d_in, void *d_out, int *d_produced, void *stream)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_in == 0) return GRHIP_OK;
+        const int c = check_count(n_in);
+        if (c <= 0) return c;
         int rc = check_work(n_in, d_in, d_out, d_produced, item());
         if (rc) return rc;
         if ((rc = bind())) return rc;
@@ -59,7 +59,7 @@ struct SquelchBlock : SquelchMachine {
 
     int set_streams(int S)
     {
-        return SquelchMachine::set_streams(S, [&] { return restart(); });
+        return StreamBlock::set_streams(S, [&] { return restart(); });
     }
 
     int set_alpha(double a)

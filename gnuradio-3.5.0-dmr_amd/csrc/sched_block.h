@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "grhip_internal.h"
+#include "stream_block.h"
 
 namespace grhip {
 
@@ -54,19 +55,10 @@ struct WalkedSteps {
 // Base of a schedule-driven handle D, which supplies general_work_device(noutput_items, ninput_items, d_in, d_out,
 // consumed, stream).
 template <class D>
-struct SchedBlock : HandleBase {
+struct SchedBlock : ModeBlock {
     bool cplx = true;
-    int mode = GRHIP_MODE_FAST;
 
     size_t item() const { return cplx ? 8 : 4; }
-
-    int set_mode(int m)
-    {
-        if (!mode_valid(m)) return fail(GRHIP_EINVAL, "bad mode %d", m);
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        mode = m;
-        return GRHIP_OK;
-    }
 
     int general_work(int noutput_items, int ninput_items, const void *in, void *out, int *consumed)
     {

@@ -7,26 +7,19 @@
 
 #include "grhip_internal.h"
 #include "squelch.h"
+#include "stream_block.h"
 
 namespace grhip {
-
-inline int squelch_check_streams(int S)
-{
-    return (S < 1 || S > 65535) ? fail(GRHIP_EINVAL, "1 .. 65535 streams") : GRHIP_OK;
-}
 
 inline int squelch_check_ramp(int ramp)
 {
     return (ramp < 0 || ramp > SQ_MAX_RAMP) ? fail(GRHIP_EINVAL, "ramp must be 0 .. %d", SQ_MAX_RAMP) : GRHIP_OK;
 }
 
-inline bool squelch_aligned(const void *p, size_t a) { return !((uintptr_t)p & (a - 1)); }
-
-struct SquelchMachine : HandleBase {
+struct SquelchMachine : StreamBlock {
     bool gate = false;
-    int nstreams = 1, ramp = 0;
-    int mode = GRHIP_MODE_FAST;
-    DevBuf d_state, d_table, d_scratch, d_prod;
+    int ramp = 0;
+    DevBuf d_state, d_table, d_scratch, d_prod;     // d_state: every stream's SquelchState
 
     // the envelope of every ramp position a stream can be at: 0.5 - cos(M_PI * k / ramp) / 2.0 in the host's double
     // arithmetic (gr_squelch_base_cc.cc:69, its "FIXME: precalculate").  An attack that starts at or past the ramp's
@@ -43,20 +36,11 @@ struct SquelchMachine : HandleBase {
         return GRHIP_OK;
     }
 
-    int read_states(std::vector<SquelchState> &v)
-    {
-        v.resize(nstreams);
-        GRHIP_HIP(hipMemcpy(v.data(), d_state.p, v.size() * sizeof(SquelchState), hipMemcpyDeviceToHost));
-        return GRHIP_OK;
-    }
-
     // gr_squelch_base_cc.cc:36-39: muted, nothing ramped, the envelope 0 with a ramp and 1 without
     int restart_machine()
     {
-        std::vector<SquelchState> v(nstreams, SquelchState{0.0, ramp ? 0.0 : 1.0, SQ_MUTED, 0});
-        int rc = d_state.reserve(v.size() * sizeof(SquelchState));
+        int rc = fill_state(d_state, SquelchState{0.0, ramp ? 0.0 : 1.0, SQ_MUTED, 0});
         if (rc) return rc;
-        GRHIP_HIP(hipMemcpy(d_state.p, v.data(), v.size() * sizeof(SquelchState), hipMemcpyHostToDevice));
         if ((rc = d_prod.reserve((size_t)nstreams * sizeof(int)))) return rc;
         return build_table(0);
     }
@@ -64,13 +48,11 @@ struct SquelchMachine : HandleBase {
     // the checks every work_device makes before it binds the device; `item` is the size of one item
     int check_work(int n_in, const void *d_in, void *d_out, const int *d_produced, size_t item) const
     {
-        if (!d_in || !d_out || !d_produced) return fail(GRHIP_EINVAL, "null buffer");
-        if (!squelch_aligned(d_in, item) || !squelch_aligned(d_out, item) || !squelch_aligned(d_produced, 4))
-            return fail(GRHIP_EINVAL, "items not naturally aligned");
-        const char *a = (const char *)d_in, *b = (const char *)d_out;
+        if (!d_produced) return fail(GRHIP_EINVAL, "null buffer");
+        if (int rc = check_io(d_in, item, d_out, item)) return rc;
+        if (!aligned(d_produced, 4)) return fail(GRHIP_EINVAL, "items not naturally aligned");
         const size_t bytes = (size_t)nstreams * (size_t)n_in * item;
-        if (a < b + bytes && b < a + bytes) return fail(GRHIP_EINVAL, "squelch: the output may not overlap the input");
-        return GRHIP_OK;
+        return check_apart("squelch", d_in, bytes, d_out, bytes);
     }
 
     // The host-buffer call around work_device(n_in, d_in, d_out, d_produced, stream): every stream's produced[s] items,
@@ -78,8 +60,8 @@ struct SquelchMachine : HandleBase {
     template <class WorkDevice>
     int host_work(int n_in, const void *in, void *out, int *produced, size_t item, WorkDevice &&work_device)
     {
-        if (n_in < 0) return fail(GRHIP_EINVAL, "negative item count");
-        if (n_in == 0) return GRHIP_OK;
+        const int c = check_count(n_in);
+        if (c <= 0) return c;
         if (!in || !out || !produced) return fail(GRHIP_EINVAL, "null buffer");
         int rc = bind();
         if (rc) return rc;
@@ -101,27 +83,6 @@ struct SquelchMachine : HandleBase {
         return GRHIP_OK;
     }
 
-    int set_mode(int m)
-    {
-        if (!mode_valid(m)) return fail(GRHIP_EINVAL, "bad mode %d", m);
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        mode = m;
-        return GRHIP_OK;
-    }
-
-    // `restart` rebuilds what the handle keeps per stream (restart_machine and the detector's own)
-    template <class Restart>
-    int set_streams(int S, Restart &&restart)
-    {
-        if (int rc = squelch_check_streams(S)) return rc;
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        nstreams = S;
-        return restart();
-    }
-
     int set_gate(int g)
     {
         std::lock_guard<std::mutex> lk(setter_mutex);
@@ -139,7 +100,7 @@ struct SquelchMachine : HandleBase {
         std::lock_guard<std::mutex> lk(setter_mutex);
         if ((rc = drain(own_stream))) return rc;
         std::vector<SquelchState> v;
-        if ((rc = read_states(v))) return rc;
+        if ((rc = read_states(d_state, v))) return rc;
         int max_ramped = 0;
         for (const SquelchState &s : v) {
             if (r == 0 && (s.state == SQ_ATTACK || s.state == SQ_DECAY))
@@ -150,16 +111,7 @@ struct SquelchMachine : HandleBase {
         return build_table(max_ramped);
     }
 
-    int get_state(int s, SquelchState *out)
-    {
-        if (s < 0 || s >= nstreams) return fail(GRHIP_EINVAL, "stream %d of %d", s, nstreams);
-        int rc = bind();
-        if (rc) return rc;
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if ((rc = drain(own_stream))) return rc;
-        GRHIP_HIP(hipMemcpy(out, d_state.as<SquelchState>() + s, sizeof(SquelchState), hipMemcpyDeviceToHost));
-        return GRHIP_OK;
-    }
+    int get_state(int s, SquelchState *out) { return read_state(d_state, s, out); }
 };
 
 }  // namespace grhip
