@@ -148,6 +148,7 @@ struct Row {
     long long n;
     FirEngine engine;
     FirEpilogue epilogue;
+    bool batched = false, odd_stride = false;       // xlating: several captures in one launch, an odd number of items apart
 };
 
 const int FAST = GRHIP_MODE_FAST, VALU = GRHIP_MODE_FAST_VALU, GEN = GRHIP_MODE_GENERIC;
@@ -184,6 +185,32 @@ const Row ROWS[] = {
     {"fcc 64/8", false, FIR_FCC, false, false, 64, 8, FAST, false, 1500, ENG_REALIN, EPILOGUE_NONE},
     {"fcc 64/3", false, FIR_FCC, false, false, 64, 3, FAST, false, 1500, ENG_GENERIC, EPILOGUE_NONE},
     {"fcc 64/8 GENERIC", false, FIR_FCC, false, false, 64, 8, GEN, false, 1500, ENG_GENERIC, EPILOGUE_NONE},
+    // tests/test_gpu_fir_walk.py: one row per case of its WALK_CASES, by id -- the kernel whose tile walk the case is there for
+    {"walk tiled-ccf-32/1", false, FIR_CCF, false, false, 32, 1, FAST, false, 1500, ENG_TILED, EPILOGUE_NONE},
+    {"walk tiled-ccc-80/2", false, FIR_CCC, false, false, 80, 2, FAST, false, 1500, ENG_TILED, EPILOGUE_NONE},
+    {"walk tiled-ccf-92/4", false, FIR_CCF, false, false, 92, 4, FAST, false, 1500, ENG_TILED, EPILOGUE_NONE},
+    {"walk tiled-ccc-104/4", false, FIR_CCC, false, false, 104, 4, FAST, false, 1500, ENG_TILED, EPILOGUE_NONE},
+    {"walk tiled-ccf-120/2", false, FIR_CCF, false, false, 120, 2, VALU, false, 1500, ENG_TILED, EPILOGUE_NONE},
+    {"walk tiled-ccf-112/4", false, FIR_CCF, false, false, 112, 4, VALU, false, 1500, ENG_TILED, EPILOGUE_NONE},
+    {"walk tiled-fff-128/1", false, FIR_FFF, false, false, 128, 1, FAST, false, 1500, ENG_TILED, EPILOGUE_NONE},
+    {"walk tiled-fff-176/2", false, FIR_FFF, false, false, 176, 2, FAST, false, 1500, ENG_TILED, EPILOGUE_NONE},
+    {"walk tiled-xlating-real-256/4", true, 0, true, false, 256, 4, VALU, false, 1500, ENG_TILED, EPILOGUE_ROTATE},
+    {"walk tiled-xlating-complex-200/4", true, 0, false, false, 200, 4, FAST, false, 1500, ENG_TILED, EPILOGUE_ROTATE},
+    {"walk tiled-demod-256/4", true, 0, true, true, 256, 4, VALU, true, 1500, ENG_TILED, EPILOGUE_DEMOD_FUSED},
+    {"walk tiled-captures-even", true, 0, true, true, 256, 4, VALU, true, 1500, ENG_TILED, EPILOGUE_DEMOD_FUSED, true, false},
+    {"walk tiled-captures-odd", true, 0, true, true, 256, 4, FAST, true, 1500, ENG_TILED, EPILOGUE_DEMOD_FUSED, true, true},
+    {"walk hidec-ccf-64/8", false, FIR_CCF, false, false, 64, 8, FAST, false, 1500, ENG_HIDEC, EPILOGUE_NONE},
+    {"walk hidec-ccc-128/64", false, FIR_CCC, false, false, 128, 64, FAST, false, 1500, ENG_HIDEC, EPILOGUE_NONE},
+    {"walk hidec-xlating-real-64/8", true, 0, true, false, 64, 8, FAST, false, 1500, ENG_HIDEC, EPILOGUE_ROTATE},
+    {"walk hidec-xlating-complex-48/3", true, 0, false, false, 48, 3, FAST, false, 1500, ENG_HIDEC, EPILOGUE_ROTATE},
+    {"walk hidec-xlating-real-96/3", true, 0, true, false, 96, 3, FAST, false, 1500, ENG_HIDEC, EPILOGUE_ROTATE},
+    {"walk hidec-demod-64/8", true, 0, true, true, 64, 8, FAST, true, 1500, ENG_HIDEC, EPILOGUE_DEMOD_FUSED},
+    {"walk hidec-captures-200/5", true, 0, true, true, 200, 5, FAST, true, 1500, ENG_HIDEC, EPILOGUE_DEMOD_FUSED, true, true},
+    {"walk realin-fcc-64/8", false, FIR_FCC, false, false, 64, 8, FAST, false, 1500, ENG_REALIN, EPILOGUE_NONE},
+    {"walk realin-scc-64/4", false, FIR_SCC, false, false, 64, 4, FAST, false, 1500, ENG_REALIN, EPILOGUE_NONE},
+    {"walk realin-xlating-fcf-64/4", true, 1, true, false, 64, 4, FAST, false, 1500, ENG_REALIN, EPILOGUE_ROTATE},
+    {"walk gtiled-ccf-64/16", false, FIR_CCF, false, false, 64, 16, GEN, false, 1500, ENG_GENERIC, EPILOGUE_NONE},
+    {"walk gtiled-ccc-33/3", false, FIR_CCC, false, false, 33, 3, GEN, false, 1500, ENG_GENERIC, EPILOGUE_NONE},
 };
 
 bool table()
@@ -195,7 +222,7 @@ bool table()
             s.caps.tiled_real = s.caps.tiled_cplx = dk != 0 && documented(dk, w.T).tiled_real;
         }
         FirCall c;
-        c.mode = w.mode; c.demod = w.demod; c.n = w.n;
+        c.mode = w.mode; c.demod = w.demod; c.n = w.n; c.batched = w.batched; c.odd_stride_multi = w.odd_stride;
         const FirRoute r = fir_route(plan_of(s), c);
         if (r.engine != w.engine || r.epilogue != w.epilogue) {
             printf("FAIL %s: routed to %s (%s), expected %s (%s)\n", w.what, ENGINES[r.engine], EPILOGUES[r.epilogue], ENGINES[w.engine],

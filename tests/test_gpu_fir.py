@@ -440,12 +440,16 @@ def test_generic_xlating_demod_in_one_kernel(gpu, po, wl, decim, ntaps):
     assert bits_equal(np.concatenate(got), ref)
 
 
+@pytest.mark.parametrize("mode_name", ["MODE_FAST", "MODE_FAST_VALU"])
 @pytest.mark.parametrize("stride_pad,n", [(0, 2_000_000), (63, 1_900_001)])
-def test_run_captures_batched_vs_oracle(gpu, po, wl, stride_pad, n):
-    """one batched launch over 5 captures: more tiles than the static share of the
-    persistent grid (the tile queue hands out the rest), odd stream stride (the streams'
-    16-byte alignment parity alternates, so the pre-mix phasors are rebuilt between
-    tiles), capture length not a multiple of the decimation or the tile"""
+def test_run_captures_batched_vs_oracle(gpu, po, wl, stride_pad, n, mode_name):
+    """one batched launch over 5 captures, capture length not a multiple of the decimation or the tile, a stride that is
+    the capture length and one that is not.  MODE_FAST_VALU: 1240 / 1180 tiles on the tiled kernel -- more than the two
+    static tiles of each of 512 workgroups, the tile queue hands out the rest (tests/test_gpu_fir_walk.py sizes that from
+    the CU count).  MODE_FAST: the matrix-core engine (fir_plan.h: CFG2 in FAST).  Both strides are even (2 000 000 and
+    1 900 064 items), so the streams' 16-byte alignment parity never changes here: the odd stride, which keeps a batch off
+    the matrix cores and makes the tiled kernel rebuild its pre-mix phasors between tiles, is tiled-captures-odd of
+    tests/test_gpu_fir_walk.py"""
     import torch
     c = wl.CFG2
     S = 5
@@ -460,6 +464,7 @@ def test_run_captures_batched_vs_oracle(gpu, po, wl, stride_pad, n):
     ostride = ((nout + 3) // 4) * 4
     d_out = torch.zeros((S, ostride), dtype=torch.float32, device=dev)
     blk = gpu.xlating_demod(c["decim"], proto, c["center_freq"], c["fs"], c["demod_gain"])
+    blk.set_mode(getattr(gpu, mode_name))
     st = torch.cuda.Stream(device=dev)
     for rep in range(2):            # second launch: the queue re-armed itself
         d_out.zero_()

@@ -271,9 +271,11 @@ def test_run_captures_matches_single_stream(gpu, po, wl):
 
 @pytest.mark.parametrize("epi", ["none", "rotate", "demod"])
 def test_every_block_of_many_tiles(gpu, po, wl, epi):
-    """every output of several hundred tiles, each epilogue: a scheduling hazard around the MFMAs shows up as
-    a few wrong 16-output blocks per thousand (one did, in the rotate epilogue, while this engine was
-    written: fir_mfma.hip, the fence in front of the epilogues), not as a gross failure"""
+    """every output of several hundred tiles of the matrix-core engine (CFG2 in MODE_FAST: fir_mfma.hip, not the tiled
+    vector kernel), each epilogue: a scheduling hazard around the MFMAs shows up as a few wrong 16-output blocks per
+    thousand (one did, in the rotate epilogue, while this engine was written: fir_mfma.hip, the fence in front of the
+    epilogues), not as a gross failure.  202 tiles: on a device with more workgroups than that none takes a second tile;
+    the tile walk of this engine is tests/test_gpu_fir_mfma_ring.py's, that of the vector kernels tests/test_gpu_fir_walk.py's"""
     c = wl.CFG2
     n = 1_600_000
     nout = n // 4
