@@ -27,6 +27,7 @@ __all__ = [
     "pwr_squelch_cc", "pwr_squelch_ff", "simple_squelch_cc", "ctcss_squelch_ff",
     "agc_cc", "agc_ff", "agc2_cc", "agc2_ff",
     "costas_loop_cc", "pll_freqdet_cf", "pll_refout_cc", "pll_carriertracking_cc",
+    "fll_band_edge_cc", "fll_band_edge_taps", "firdes_root_raised_cosine",
     "constellation", "constellation_bpsk", "constellation_qpsk", "constellation_dqpsk", "constellation_8psk",
     "constellation_calcdist", "constellation_psk", "constellation_rect", "psk_constellation", "qam_constellation",
     "gray_code", "invert_code", "constellation_decoder_cb", "diff_decoder_bb", "map_bb", "constellation_receiver_cb",
@@ -1817,6 +1818,78 @@ class costas_loop_cc(_control_loop):
 
     def work_device(self, n, d_in, d_out, d_freq_out=None, stream=None):
         return self._call("work_device", int(n), _devptr(d_in), _devptr(d_out), _devptr(d_freq_out), _stream(stream))
+
+
+class fll_band_edge_cc(_control_loop):
+    """digital.fll_band_edge_cc(samps_per_sym, rolloff, filter_size, bandwidth) (gr-digital/swig/
+    digital_fll_band_edge_cc.i): the band-edge frequency-lock loop.  work(x) returns the derotated samples, delayed
+    by 2 * filter_size - 1 items; work(x, aux=True) returns (out, frq, phs, err) with the loop's frequency, phase and
+    error behind every step.  The handle takes new items only and keeps what it needs of the past per stream, so the
+    result depends on the concatenated input alone (include/grhip.h).  MODE_GENERIC is bit for bit the restatement in
+    tests/fll_ref.py; every other mode runs the float NCO, fused products and tree-order sums."""
+    _name = "fll_band_edge_cc"
+
+    def __init__(self, samps_per_sym, rolloff, filter_size, bandwidth, device=0):
+        _Block.__init__(self)
+        self._create(float(samps_per_sym), float(rolloff), int(filter_size), float(bandwidth), int(device))
+
+    def history(self):
+        return self.get_filter_size() + 1           # digital_fll_band_edge_cc.cc:187
+
+    def set_samples_per_symbol(self, sps):
+        self._call("set_samples_per_symbol", float(sps))
+
+    def set_rolloff(self, rolloff):
+        self._call("set_rolloff", float(rolloff))
+
+    def set_filter_size(self, filter_size):
+        """a new filter size also zeroes every stream's two histories (phase and frequency stay)"""
+        self._call("set_filter_size", int(filter_size))
+
+    def get_samples_per_symbol(self):
+        return self._fn("get_samples_per_symbol")(self._h)
+
+    def get_rolloff(self):
+        return self._fn("get_rolloff")(self._h)
+
+    def get_filter_size(self):
+        return self._call("get_filter_size")
+
+    def work(self, input_items, n_in=None, aux=False):
+        x, n_in = self._items(input_items, n_in)
+        m = max(n_in * self._streams, 1)
+        out = np.zeros(m, dtype=np.complex64)
+        f = [np.zeros(m, dtype=np.float32) for _ in range(3)] if aux else []
+        null = C.c_void_p(0)
+        self._call("work", int(n_in), _ptr(x), _ptr(out), *([_ptr(a) for a in f] if aux else [null, null, null]))
+        m = n_in * self._streams
+        return (out[:m], f[0][:m], f[1][:m], f[2][:m]) if aux else out[:m]
+
+    def work_device(self, n, d_in, d_out, d_frq=None, d_phs=None, d_err=None, stream=None):
+        return self._call("work_device", int(n), _devptr(d_in), _devptr(d_out), _devptr(d_frq), _devptr(d_phs), _devptr(d_err),
+                          _stream(stream))
+
+
+def fll_band_edge_taps(samps_per_sym, rolloff, filter_size):
+    """(lower, upper): digital_fll_band_edge_cc::design_filter's two tap sets as the reference stores them (reversed).
+    Host arithmetic only, no device needed.  A refused design is a GrhipError."""
+    n = max(int(filter_size), 1)
+    lower, upper = np.zeros(min(n, 1024), dtype=np.complex64), np.zeros(min(n, 1024), dtype=np.complex64)
+    _check(lib().grhip_fll_band_edge_taps(float(samps_per_sym), float(rolloff), int(filter_size), _ptr(lower), _ptr(upper)))
+    return lower, upper
+
+
+def firdes_root_raised_cosine(gain, sampling_freq, symbol_rate, alpha, ntaps):
+    """gr.firdes.root_raised_cosine(gain, sampling_freq, symbol_rate, alpha, ntaps): host arithmetic only, no device
+    needed.  A failed argument check is a GrhipError."""
+    args = (float(gain), float(sampling_freq), float(symbol_rate), float(alpha), int(ntaps))
+    n = C.c_size_t(0)
+    rc = lib().grhip_firdes_root_raised_cosine(*(args + (C.c_void_p(0), 0, C.byref(n))))
+    if rc != -2:                                    # GRHIP_ERANGE: the size query's answer
+        _check(rc)
+    out = np.zeros(max(n.value, 1), dtype=np.float32)
+    _check(lib().grhip_firdes_root_raised_cosine(*(args + (_ptr(out), n.value, C.byref(n)))))
+    return out[:n.value]
 
 
 # ----------------------------------------------------------------------------

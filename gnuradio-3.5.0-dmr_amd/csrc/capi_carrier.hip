@@ -12,7 +12,7 @@
 #include "carrier.h"
 #include "control_loop.h"
 #include "grhip_internal.h"
-#include "stream_block.h"
+#include "loop_block.h"
 
 using namespace grhip;
 
@@ -20,18 +20,16 @@ namespace {
 
 enum { CARRIER_COSTAS = -1 };       // otherwise a PLL_* kind
 
-struct CarrierBlock : StreamBlock {
+struct CarrierBlock : LoopBlock {
     int kind = PLL_FREQDET;
     int order = 2;
-    ControlLoop cl;
     float lock_threshold = 0.f;         // gr_pll_carriertracking_cc.cc:50
     int squelch = 0;
     const DeviceTables *tabs = nullptr;
-    DevBuf d_state;                     // every stream's CarrierState
 
     size_t out_item() const { return kind == PLL_FREQDET ? sizeof(float) : 2 * sizeof(float); }
 
-    int restart() { return fill_state(d_state, CarrierState{0.f, 0.f, 0.f, 0.f}); }          // gri_control_loop.cc:35
+    int restart() { return zero_loop_state(); }
 
     int init(int which, int ord, float loop_bw, float max_freq, float min_freq, int dev)
     {
@@ -52,51 +50,6 @@ struct CarrierBlock : StreamBlock {
     int set_streams(int S)
     {
         return StreamBlock::set_streams(S, [&] { return restart(); });
-    }
-
-    // a setter of the loop's parameters (control_loop.h): false is the reference's std::out_of_range
-    int set_param(bool (ControlLoop::*set)(float), float v, const char *what)
-    {
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        if (!(cl.*set)(v)) return fail(GRHIP_EINVAL, "gri_control_loop: invalid %s", what);
-        return GRHIP_OK;
-    }
-
-    float get_param(float ControlLoop::*which)
-    {
-        std::lock_guard<std::mutex> lk(setter_mutex);
-        return cl.*which;
-    }
-
-    // one float of every stream's state = v
-    int set_state(float CarrierState::*which, float v)
-    {
-        return edit_states<CarrierState>(d_state, [&](CarrierState &e) { e.*which = v; });
-    }
-
-    int set_frequency(float f)              // gri_control_loop.cc:126-135
-    {
-        float v;
-        {
-            std::lock_guard<std::mutex> lk(setter_mutex);
-            v = cl.set_frequency(f);
-        }
-        return set_state(&CarrierState::freq, v);
-    }
-
-    int set_phase(float ph)                 // gri_control_loop.cc:137-145
-    {
-        if (!ControlLoop::phase_ok(ph)) return fail(GRHIP_EINVAL, "control loop: the phase must be finite and within +-2^20 rad");
-        return set_state(&CarrierState::phase, ControlLoop::set_phase(ph));
-    }
-
-    int get_float(int s, float CarrierState::*which, float *v)
-    {
-        if (!v) return fail(GRHIP_EINVAL, "null argument");
-        CarrierState t;
-        int rc = read_state(d_state, s, &t);
-        if (!rc) *v = t.*which;
-        return rc;
     }
 
     int lock_detector(int s, int *locked)   // gr_pll_carriertracking_cc.cc:74-78
@@ -172,56 +125,6 @@ struct grhip_pll_carriertracking_cc : CarrierBlock {};
 
 extern "C" {
 
-#define GRHIP_CL_NULL(h) if (!(h)) return fail(GRHIP_EINVAL, "null handle")
-#define GRHIP_CL_GET(NAME, ENTRY, FIELD)                                                                              \
-    float grhip_##NAME##_##ENTRY(grhip_##NAME *h)                                                                     \
-    {                                                                                                                 \
-        if (!h) return (float)fail(GRHIP_EINVAL, "null handle");                                                      \
-        return h->get_param(&ControlLoop::FIELD);                                                                     \
-    }
-
-// what the four blocks share: gri_control_loop.h:99-200
-#define GRHIP_CL_COMMON(NAME)                                                                                         \
-    void grhip_##NAME##_destroy(grhip_##NAME *h) { destroy_handle(h); }                                               \
-    int grhip_##NAME##_set_mode(grhip_##NAME *h, int mode) { GRHIP_CL_NULL(h); return h->set_mode(mode); }            \
-    int grhip_##NAME##_set_streams(grhip_##NAME *h, int nstreams) { GRHIP_CL_NULL(h); return h->set_streams(nstreams); } \
-    int grhip_##NAME##_set_loop_bandwidth(grhip_##NAME *h, float bw)                                                  \
-    {                                                                                                                 \
-        GRHIP_CL_NULL(h);                                                                                             \
-        return h->set_param(&ControlLoop::set_loop_bandwidth, bw, "bandwidth. Must be >= 0 (and leave finite gains).");  \
-    }                                                                                                                 \
-    int grhip_##NAME##_set_damping_factor(grhip_##NAME *h, float df)                                                  \
-    {                                                                                                                 \
-        GRHIP_CL_NULL(h);                                                                                             \
-        return h->set_param(&ControlLoop::set_damping_factor, df, "damping factor. Must be in [0,1].");               \
-    }                                                                                                                 \
-    int grhip_##NAME##_set_alpha(grhip_##NAME *h, float alpha)                                                        \
-    {                                                                                                                 \
-        GRHIP_CL_NULL(h);                                                                                             \
-        return h->set_param(&ControlLoop::set_alpha, alpha, "alpha. Must be in [0,1].");                              \
-    }                                                                                                                 \
-    int grhip_##NAME##_set_beta(grhip_##NAME *h, float beta)                                                          \
-    {                                                                                                                 \
-        GRHIP_CL_NULL(h);                                                                                             \
-        return h->set_param(&ControlLoop::set_beta, beta, "beta. Must be in [0,1].");                                 \
-    }                                                                                                                 \
-    int grhip_##NAME##_set_frequency(grhip_##NAME *h, float freq) { GRHIP_CL_NULL(h); return h->set_frequency(freq); } \
-    int grhip_##NAME##_set_phase(grhip_##NAME *h, float phase) { GRHIP_CL_NULL(h); return h->set_phase(phase); }      \
-    GRHIP_CL_GET(NAME, get_loop_bandwidth, loop_bw)                                                                   \
-    GRHIP_CL_GET(NAME, get_damping_factor, damping)                                                                   \
-    GRHIP_CL_GET(NAME, get_alpha, alpha)                                                                              \
-    GRHIP_CL_GET(NAME, get_beta, beta)                                                                                \
-    int grhip_##NAME##_get_frequency(grhip_##NAME *h, int s, float *freq)                                             \
-    {                                                                                                                 \
-        GRHIP_CL_NULL(h);                                                                                             \
-        return h->get_float(s, &CarrierState::freq, freq);                                                            \
-    }                                                                                                                 \
-    int grhip_##NAME##_get_phase(grhip_##NAME *h, int s, float *phase)                                                \
-    {                                                                                                                 \
-        GRHIP_CL_NULL(h);                                                                                             \
-        return h->get_float(s, &CarrierState::phase, phase);                                                          \
-    }
-
 // gr_pll_freqdet_cf.h:33-34 and its two siblings
 #define GRHIP_CL_PLL(NAME, KIND)                                                                                      \
     int grhip_##NAME##_create(grhip_##NAME **h, float loop_bw, float max_freq, float min_freq, int device)            \
@@ -286,8 +189,5 @@ int grhip_costas_loop_cc_work_device(grhip_costas_loop_cc *h, int n_in, const vo
 GRHIP_CL_COMMON(costas_loop_cc)
 
 #undef GRHIP_CL_PLL
-#undef GRHIP_CL_COMMON
-#undef GRHIP_CL_GET
-#undef GRHIP_CL_NULL
 
 }  // extern "C"

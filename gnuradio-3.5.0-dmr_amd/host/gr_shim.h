@@ -61,6 +61,7 @@ class gr_io_signature {
 public:
     gr_io_signature(int mn, int mx, int size) : d_min(mn), d_max(mx), d_sizeof(1, size) {}
     gr_io_signature(int mn, int mx, int size1, int size2) : d_min(mn), d_max(mx), d_sizeof{size1, size2} {}
+    gr_io_signature(int mn, int mx, const std::vector<int> &sizes) : d_min(mn), d_max(mx), d_sizeof(sizes) {}
     int min_streams() const { return d_min; }
     int max_streams() const { return d_max; }
     // gr_io_signature.cc:76-83: the last size stands for every further stream
@@ -74,6 +75,10 @@ inline gr_io_signature_sptr gr_make_io_signature(int mn, int mx, int size)
 inline gr_io_signature_sptr gr_make_io_signature2(int mn, int mx, int size1, int size2)
 {
     return gr_io_signature_sptr(new gr_io_signature(mn, mx, size1, size2));
+}
+inline gr_io_signature_sptr gr_make_io_signaturev(int mn, int mx, const std::vector<int> &sizes)
+{
+    return gr_io_signature_sptr(new gr_io_signature(mn, mx, sizes));
 }
 
 class gr_block {

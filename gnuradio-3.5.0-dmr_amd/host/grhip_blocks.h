@@ -35,6 +35,7 @@
 //   digital_make_costas_loop_cc, gr_make_pll_freqdet_cf / _refout_cc / _carriertracking_cc
 //                                            <- the factories of the same names (gr-digital/include/
 //                                               digital_costas_loop_cc.h, general/gr_pll_*.h)
+//   digital_make_fll_band_edge_cc            <- digital_make_fll_band_edge_cc (gr-digital/include/digital_fll_band_edge_cc.h)
 //   digital_make_constellation_bpsk / _qpsk / _dqpsk / _8psk / _calcdist / _psk / _rect, digital_make_constellation_decoder_cb,
 //   digital_make_constellation_receiver_cb, gr_make_diff_decoder_bb, gr_make_map_bb
 //                                            <- the factories of the same names (gr-digital/include/digital_constellation*.h,
@@ -1738,6 +1739,67 @@ GRHIP_LOOP_BLK_COMMON(costas_loop_cc)
 inline grhip_costas_loop_cc_sptr digital_make_costas_loop_cc(float loop_bw, int order, int device = 0)
 {
     return gnuradio::get_initial_sptr(new grhip_costas_loop_cc_blk(loop_bw, order, device));
+}
+// ---------------------------------------------------------------------------
+// digital_fll_band_edge_cc (samps_per_sym, rolloff, filter_size, bandwidth; 1 input, 1 or 4 outputs: the derotated
+// samples and, with all four connected, the loop's frequency, phase and error; gr-digital/include/
+// digital_fll_band_edge_cc.h).  A gr_sync_block with history filter_size + 1, as the reference's: the scheduler hands
+// work the filter_size items before the new ones too, the handle keeps what it needs of the past itself and takes the
+// new items only (include/grhip.h states what is computed).  gr_firdes::root_raised_cosine comes with it.
+// ---------------------------------------------------------------------------
+class grhip_fll_band_edge_cc_blk;
+typedef boost::shared_ptr<grhip_fll_band_edge_cc_blk> grhip_fll_band_edge_cc_sptr;
+class grhip_fll_band_edge_cc_blk : public gr_sync_block {
+    grhip_fll_band_edge_cc *d_h = nullptr;
+    static std::vector<int> iosig() { return {(int)sizeof(gr_complex), (int)sizeof(float), (int)sizeof(float), (int)sizeof(float)}; }
+    grhip_fll_band_edge_cc_blk(float samps_per_sym, float rolloff, int filter_size, float bandwidth, int device)
+        : gr_sync_block("fll_band_edge_cc", gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                        gr_make_io_signaturev(1, 4, iosig()))                                // digital_fll_band_edge_cc.cc:51-57
+    {
+        grhip_detail::check(grhip_fll_band_edge_cc_create(&d_h, samps_per_sym, rolloff, filter_size, bandwidth, device));
+        set_history(filter_size + 1);                                                       // :187
+    }
+    friend grhip_fll_band_edge_cc_sptr digital_make_fll_band_edge_cc(float, float, int, float, int);
+GRHIP_LOOP_BLK_COMMON(fll_band_edge_cc)
+    void set_samples_per_symbol(float sps) { grhip_detail::check(grhip_fll_band_edge_cc_set_samples_per_symbol(d_h, sps)); }
+    void set_rolloff(float rolloff) { grhip_detail::check(grhip_fll_band_edge_cc_set_rolloff(d_h, rolloff)); }
+    void set_filter_size(int filter_size)
+    {
+        grhip_detail::check(grhip_fll_band_edge_cc_set_filter_size(d_h, filter_size));
+        set_history(filter_size + 1);
+    }
+    float get_samples_per_symbol() const { return grhip_fll_band_edge_cc_get_samples_per_symbol(d_h); }
+    float get_rolloff() const { return grhip_fll_band_edge_cc_get_rolloff(d_h); }
+    int get_filter_size() const
+    {
+        const int v = grhip_fll_band_edge_cc_get_filter_size(d_h);
+        grhip_detail::check(v);
+        return v;
+    }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        const gr_complex *fresh = (const gr_complex *)in[0] + (history() - 1);
+        const bool aux = out.size() == 4;                                                   // :219
+        grhip_detail::check(grhip_fll_band_edge_cc_work(d_h, noutput_items, fresh, out[0], aux ? out[1] : nullptr,
+                                                         aux ? out[2] : nullptr, aux ? out[3] : nullptr));
+        return noutput_items;
+    }
+};
+inline grhip_fll_band_edge_cc_sptr digital_make_fll_band_edge_cc(float samps_per_sym, float rolloff, int filter_size, float bandwidth,
+                                                                 int device = 0)
+{
+    return gnuradio::get_initial_sptr(new grhip_fll_band_edge_cc_blk(samps_per_sym, rolloff, filter_size, bandwidth, device));
+}
+
+// gr_firdes::root_raised_cosine(gain, sampling_freq, symbol_rate, alpha, ntaps)
+inline std::vector<float> grhip_firdes_root_raised_cosine_taps(double gain, double sampling_freq, double symbol_rate, double alpha, int ntaps)
+{
+    size_t n = 0;
+    const int rc = grhip_firdes_root_raised_cosine(gain, sampling_freq, symbol_rate, alpha, ntaps, nullptr, 0, &n);
+    if (rc != GRHIP_ERANGE) grhip_detail::check(rc);
+    std::vector<float> taps(n);
+    grhip_detail::check(grhip_firdes_root_raised_cosine(gain, sampling_freq, symbol_rate, alpha, ntaps, taps.data(), n, &n));
+    return taps;
 }
 // ---------------------------------------------------------------------------
 // digital_constellation and its kinds (gr-digital/include/digital_constellation.h), digital_constellation_decoder_cb

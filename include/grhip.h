@@ -1023,6 +1023,21 @@ GRHIP_API int grhip_firdes_hilbert(unsigned ntaps, int window_type, double beta,
 GRHIP_API int grhip_firdes_low_pass(double gain, double fs, double cutoff, double transition, int window_type, double beta,
                                     float *out, size_t cap, size_t *ntaps);
 
+/* gr_firdes::root_raised_cosine  -- host only, no device needed
+ *   replaces gr_firdes::root_raised_cosine(double gain, double sampling_freq, double symbol_rate,
+ *       double alpha, int ntaps)
+ *   general/gr_firdes.cc:601-650
+ * The reference's statements one for one: ntaps |= 1, both branches of |x3| >= 1e-6, the tap of -1
+ * for alpha == 1 on the singular branch (it stays out of the scale), every tap narrowed to float
+ * before it is added to the double scale, then taps[i] * gain / scale.  The taps are the reference's
+ * bit for bit (tests/test_fll_band_edge_cpu.py).  *ntaps receives ntaps | 1 and out, of `cap` floats,
+ * the taps; the size query is grhip_firdes_low_pass's (cap too small: only *ntaps, GRHIP_ERANGE).
+ * Deviations: GRHIP_EINVAL for an argument that is not finite, ntaps < 1 (the reference then throws
+ * from std::vector or writes nothing) and ntaps from 2^24 on.  A symbol_rate of 0 gives taps that are
+ * not finite, as in the reference. */
+GRHIP_API int grhip_firdes_root_raised_cosine(double gain, double fs, double symbol_rate, double alpha, int ntaps, float *out,
+                                              size_t cap, size_t *ntaps_out);
+
 /* gr_remez  -- host only, no device needed
  *   replaces gr_remez(int order, const std::vector<double> &bands, const std::vector<double> &ampl,
  *       const std::vector<double> &error_weight, const std::string filter_type, int grid_density)
@@ -1962,6 +1977,91 @@ GRHIP_API int grhip_costas_loop_cc_get_phase(grhip_costas_loop_cc *h, int s, flo
 GRHIP_API int grhip_costas_loop_cc_work(grhip_costas_loop_cc *h, int n_in, const void *in, void *out, void *freq_out);
 GRHIP_API int grhip_costas_loop_cc_work_device(grhip_costas_loop_cc *h, int n_in, const void *d_in, void *d_out, void *d_freq_out,
                                                void *stream);
+
+/* digital_fll_band_edge_cc
+ *   replaces digital_make_fll_band_edge_cc(float samps_per_sym, float rolloff, int filter_size,
+ *       float bandwidth)
+ *   gr-digital/lib/digital_fll_band_edge_cc.cc:208-259 (work), :148-188 (design_filter), :53-120
+ * Complex in; complex out and, optionally, three float outputs.  The loop above with max_freq =
+ * (float)(2 pi * (2.0 / sps)) and min_freq = -max_freq (:58).
+ *
+ * What is computed.  The reference's work (history = filter_size + 1) writes out[i + fs - 1] = in[i] *
+ * gr_expj(d_phase), fs - 1 items beyond noutput_items, filters out[i .. i + fs - 1] and returns
+ * noutput_items; in the runtime's double-mapped ring the items written ahead are the first items of
+ * the next call, so what a reader sees is a linear stream.  That stream is the contract here, with
+ * fs = filter_size:
+ *     xz   = fs zeros, then the input
+ *     d[j] = xz[j] * expj(phase before step j)          (ac - bd, ad + bc)
+ *     step j filters d[j-fs+1 .. j], tap k on d[j-fs+1+k], zeros before the start:
+ *         error = norm(sum lower[k] d) - norm(sum upper[k] d);  advance_loop, phase_wrap, frequency_limit
+ *     out[n] = d[n - (fs - 1)]: the input delayed by 2 fs - 1 items, the first 2 fs - 1 outputs zero
+ *     frq[n], phs[n], err[n] = d_freq, d_phase, error after step n
+ * The handle works on new items only (as am_demod_cf and fm_demod_cf do): per stream the device holds
+ * the last fs inputs, the last fs - 1 derotated samples, phase and frequency, zero after create and
+ * after set_streams.  THE RESULT DEPENDS ON THE CONCATENATED INPUT ALONE, never on where calls cut it.
+ * The reference agrees with this as long as its reader keeps up; when its downstream ring is full it
+ * overwrites unread items instead, which nothing here does.
+ *
+ * The filters.  grhip_fll_band_edge_taps(sps, rolloff, filter_size, lower, upper) is design_filter
+ * (host only, no device needed) and writes filter_size (re, im) float pairs to each of lower and upper,
+ * stored reversed as the reference stores them: float k = -M + i*2.0/sps with M = rint(size / sps), the
+ * two sincs (a double sine narrowed to float), the float running sum `power`, N = (size - 1.0)/2.0
+ * truncated, gr_expj of the double argument -+2 pi (1 + rolloff) k narrowed to float (sincosf on the
+ * host, as a Linux build of the reference calls it).  Bit for bit the reference's taps.
+ * GRHIP_EINVAL where the reference throws std::out_of_range (sps <= 0, rolloff outside [0, 1],
+ * filter_size <= 0) and, stated deviations: filter_size above 1024; taps that are not finite (the
+ * baseband taps sum to 0, so tap / power is not a number); an sps whose 2 pi 2 / sps exceeds the
+ * family's 1024 rad/sample (or is not finite).
+ *
+ * The setters of the loop are the family's (above).  set_samples_per_symbol, set_rolloff and
+ * set_filter_size (:92-120) redesign the filters and wait for the device; a refused value changes
+ * nothing.  set_samples_per_symbol leaves max_freq / min_freq as they are, as the reference does.
+ * set_filter_size zeroes the two per-stream histories, phase and frequency stay: a stated deviation
+ * (the reference leaves its ring as it is and returns 0 items once); the other two keep the histories.
+ *
+ * phase_wrap, a stated deviation: the error is a difference of two filter powers and unbounded, unlike
+ * every other loop of the family, and the reference's subtract loop does not end for a large phase.
+ * The kernel runs that loop for at most 256 trips each way and beyond that takes the exact double
+ * remainder fmod(phase, 2 pi), narrowed to float.  Only input of a scale where (alpha + beta) |error|
+ * passes about 570 reaches it.  The kernel ends and stays in bounds for every bit pattern
+ * (csrc/fll_band_edge.hip states why).
+ *
+ * GRHIP_MODE_GENERIC: sine and cosine are (float)sin((double)phase) and (float)cos((double)phase);
+ * every product and sum is rounded once, as g++ forms complex<float> arithmetic without contraction,
+ * and the two filter sums run in the reference's order k = 0 .. fs - 1.  Bit for bit the restatement
+ * in tests/fll_ref.py; not the reference's sincosf to the bit.  Every other mode: the
+ * float polynomial NCO of costas_loop_cc, fused multiply-adds and tree-order sums.
+ * work / work_device: frq, phs and err are n_in floats per stream each, all given or all NULL
+ * (GRHIP_EINVAL otherwise); out is the same either way.  No buffer may overlap another. */
+typedef struct grhip_fll_band_edge_cc grhip_fll_band_edge_cc;
+GRHIP_API int grhip_fll_band_edge_taps(float sps, float rolloff, int filter_size, void *lower, void *upper);
+GRHIP_API int grhip_fll_band_edge_cc_create(grhip_fll_band_edge_cc **h, float samps_per_sym, float rolloff, int filter_size,
+                                            float bandwidth, int device);
+GRHIP_API void grhip_fll_band_edge_cc_destroy(grhip_fll_band_edge_cc *h);
+GRHIP_API int grhip_fll_band_edge_cc_set_mode(grhip_fll_band_edge_cc *h, int mode);
+GRHIP_API int grhip_fll_band_edge_cc_set_streams(grhip_fll_band_edge_cc *h, int nstreams);
+GRHIP_API int grhip_fll_band_edge_cc_set_loop_bandwidth(grhip_fll_band_edge_cc *h, float bw);
+GRHIP_API int grhip_fll_band_edge_cc_set_damping_factor(grhip_fll_band_edge_cc *h, float df);
+GRHIP_API int grhip_fll_band_edge_cc_set_alpha(grhip_fll_band_edge_cc *h, float alpha);
+GRHIP_API int grhip_fll_band_edge_cc_set_beta(grhip_fll_band_edge_cc *h, float beta);
+GRHIP_API int grhip_fll_band_edge_cc_set_frequency(grhip_fll_band_edge_cc *h, float freq);
+GRHIP_API int grhip_fll_band_edge_cc_set_phase(grhip_fll_band_edge_cc *h, float phase);
+GRHIP_API float grhip_fll_band_edge_cc_get_loop_bandwidth(grhip_fll_band_edge_cc *h);
+GRHIP_API float grhip_fll_band_edge_cc_get_damping_factor(grhip_fll_band_edge_cc *h);
+GRHIP_API float grhip_fll_band_edge_cc_get_alpha(grhip_fll_band_edge_cc *h);
+GRHIP_API float grhip_fll_band_edge_cc_get_beta(grhip_fll_band_edge_cc *h);
+GRHIP_API int grhip_fll_band_edge_cc_get_frequency(grhip_fll_band_edge_cc *h, int s, float *freq);
+GRHIP_API int grhip_fll_band_edge_cc_get_phase(grhip_fll_band_edge_cc *h, int s, float *phase);
+GRHIP_API int grhip_fll_band_edge_cc_set_samples_per_symbol(grhip_fll_band_edge_cc *h, float sps);
+GRHIP_API int grhip_fll_band_edge_cc_set_rolloff(grhip_fll_band_edge_cc *h, float rolloff);
+GRHIP_API int grhip_fll_band_edge_cc_set_filter_size(grhip_fll_band_edge_cc *h, int filter_size);
+GRHIP_API float grhip_fll_band_edge_cc_get_samples_per_symbol(grhip_fll_band_edge_cc *h);
+GRHIP_API float grhip_fll_band_edge_cc_get_rolloff(grhip_fll_band_edge_cc *h);
+GRHIP_API int grhip_fll_band_edge_cc_get_filter_size(grhip_fll_band_edge_cc *h);
+GRHIP_API int grhip_fll_band_edge_cc_work(grhip_fll_band_edge_cc *h, int n_in, const void *in, void *out, void *frq, void *phs,
+                                          void *err);
+GRHIP_API int grhip_fll_band_edge_cc_work_device(grhip_fll_band_edge_cc *h, int n_in, const void *d_in, void *d_out, void *d_frq,
+                                                 void *d_phs, void *d_err, void *stream);
 
 /* ======================================================================
  * digital_constellation and its kinds (host objects; no device is needed)
