@@ -28,6 +28,7 @@ __all__ = [
     "agc_cc", "agc_ff", "agc2_cc", "agc2_ff",
     "costas_loop_cc", "pll_freqdet_cf", "pll_refout_cc", "pll_carriertracking_cc",
     "fll_band_edge_cc", "fll_band_edge_taps", "firdes_root_raised_cosine",
+    "pfb_clock_sync_ccf", "pfb_clock_sync_taps",
     "constellation", "constellation_bpsk", "constellation_qpsk", "constellation_dqpsk", "constellation_8psk",
     "constellation_calcdist", "constellation_psk", "constellation_rect", "psk_constellation", "qam_constellation",
     "gray_code", "invert_code", "constellation_decoder_cb", "diff_decoder_bb", "map_bb", "constellation_receiver_cb",
@@ -1890,6 +1891,124 @@ def firdes_root_raised_cosine(gain, sampling_freq, symbol_rate, alpha, ntaps):
     out = np.zeros(max(n.value, 1), dtype=np.float32)
     _check(lib().grhip_firdes_root_raised_cosine(*(args + (_ptr(out), n.value, C.byref(n)))))
     return out[:n.value]
+
+
+class pfb_clock_sync_ccf(_Block):
+    """gr.pfb_clock_sync_ccf(sps, loop_bw, taps, filter_size=32, init_phase=0, max_rate_deviation=1.5, osps=1)
+    (filter/gr_pfb_clock_sync_ccf.i): polyphase timing recovery.  work(x) returns one array of symbols per stream (a
+    single array for one stream); work(x, aux=True) returns (out, err, rate, k) likewise.  The handle takes new items
+    only and keeps what it needs of the past per stream, so the result depends on the concatenated input alone
+    (include/grhip.h).  MODE_GENERIC is bit for bit the restatement in tests/pfb_clock_sync_ref.py and through it the
+    reference; every other mode runs the same scalar loop with fused products and tree-order sums."""
+    _name = "pfb_clock_sync_ccf"
+
+    def __init__(self, sps, loop_bw, taps, filter_size=32, init_phase=0.0, max_rate_deviation=1.5, osps=1, device=0):
+        _Block.__init__(self)
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        self._create(float(sps), float(loop_bw), _ptr(t), len(t), int(filter_size), float(init_phase), float(max_rate_deviation),
+                     int(osps), int(device))
+
+    def set_loop_bandwidth(self, bw):
+        self._call("set_loop_bandwidth", float(bw))
+
+    def set_damping_factor(self, df):
+        self._call("set_damping_factor", float(df))
+
+    def set_alpha(self, alpha):
+        self._call("set_alpha", float(alpha))
+
+    def set_beta(self, beta):
+        self._call("set_beta", float(beta))
+
+    def set_max_rate_deviation(self, m):
+        self._call("set_max_rate_deviation", float(m))
+
+    def get_loop_bandwidth(self):
+        return self._fn("get_loop_bandwidth")(self._h)
+
+    def get_damping_factor(self):
+        return self._fn("get_damping_factor")(self._h)
+
+    def get_alpha(self):
+        return self._fn("get_alpha")(self._h)
+
+    def get_beta(self):
+        return self._fn("get_beta")(self._h)
+
+    def get_max_rate_deviation(self):
+        return self._fn("get_max_rate_deviation")(self._h)
+
+    def _stream_value(self, name, stream, ctype, dtype):
+        v = ctype(0)
+        self._call(name, int(stream), C.byref(v))
+        return dtype(v.value)
+
+    def get_clock_rate(self, stream=0):
+        return self._stream_value("get_clock_rate", stream, C.c_float, np.float32)
+
+    def k(self, stream=0):
+        return self._stream_value("k", stream, C.c_float, np.float32)
+
+    def error(self, stream=0):
+        return self._stream_value("error", stream, C.c_float, np.float32)
+
+    def slips(self, stream=0):
+        return self._stream_value("slips", stream, C.c_int, int)
+
+    def position(self, stream=0):
+        """the index into xz (tpf + floor(sps) - 1 zeros, then the stream) at which the next symbol starts"""
+        return self._stream_value("position", stream, C.c_longlong, int)
+
+    def _bank(self, name):
+        nf, tpf = C.c_int(0), C.c_int(0)
+        rc = self._fn(name)(self._h, C.c_void_p(0), 0, C.byref(nf), C.byref(tpf))
+        if rc != -2:                                    # GRHIP_ERANGE: the size query's answer
+            _check(rc)
+        b = np.zeros((nf.value, tpf.value), dtype=np.float32)
+        self._call(name, _ptr(b), b.size, C.byref(nf), C.byref(tpf))
+        return b
+
+    def get_taps(self):
+        return self._bank("get_taps")
+
+    def get_diff_taps(self):
+        return self._bank("get_diff_taps")
+
+    def max_produced(self, n_in):
+        return self._call("max_produced", int(n_in))
+
+    def work(self, input_items, n_in=None, aux=False):
+        x = np.ascontiguousarray(input_items, dtype=np.complex64).reshape(-1)
+        if n_in is None:
+            n_in = len(x) // self._streams
+        if len(x) < n_in * self._streams:
+            raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
+        cap = self.max_produced(n_in)
+        S = self._streams
+        out = np.zeros((S, cap), dtype=np.complex64)
+        f = [np.zeros((S, cap), dtype=np.float32) for _ in range(3)] if aux else []
+        prod = np.zeros(S, dtype=np.int32)
+        null = C.c_void_p(0)
+        if len(x) == 0:
+            x = np.zeros(1, np.complex64)
+        self._call("work", int(n_in), _ptr(x), cap, _ptr(out), *([_ptr(a) for a in f] if aux else [null, null, null]) + [_ptr(prod)])
+        rows = [tuple(a[s, :prod[s]].copy() for a in [out] + f) if aux else out[s, :prod[s]].copy() for s in range(S)]
+        return rows[0] if S == 1 else rows
+
+    def work_device(self, n, d_in, out_cap, d_out, d_produced, d_err=None, d_rate=None, d_k=None, stream=None):
+        return self._call("work_device", int(n), _devptr(d_in), int(out_cap), _devptr(d_out), _devptr(d_err), _devptr(d_rate),
+                          _devptr(d_k), _devptr(d_produced), _stream(stream))
+
+
+def pfb_clock_sync_taps(taps, filter_size):
+    """(bank, diff_bank): gr_pfb_clock_sync_ccf's two polyphase banks as get_taps() and get_diff_taps() return them,
+    [filter_size][taps per arm].  Host arithmetic only, no device needed.  A refused prototype is a GrhipError."""
+    t = np.ascontiguousarray(taps, dtype=np.float32)
+    tpf = C.c_int(0)
+    _check(lib().grhip_pfb_clock_sync_taps(_ptr(t), len(t), int(filter_size), C.c_void_p(0), C.c_void_p(0), C.byref(tpf)))
+    bank, dbank = np.zeros((int(filter_size), tpf.value), np.float32), np.zeros((int(filter_size), tpf.value), np.float32)
+    _check(lib().grhip_pfb_clock_sync_taps(_ptr(t), len(t), int(filter_size), _ptr(bank), _ptr(dbank), C.byref(tpf)))
+    return bank, dbank
 
 
 # ----------------------------------------------------------------------------

@@ -32,6 +32,26 @@ __device__ __forceinline__ float fir_fff_generic_sum(const float *taps_rev, cons
     return (acc0 + acc1 + acc2 + acc3);
 }
 
+// gr_fir_ccf_generic::filter's sums (filter/gr_fir_XXX_generic.cc.t:59-79) over products that are formed already: two
+// complex accumulators over the even and the odd taps, the rest of an odd count into the first, then acc0 + acc1;
+// unfused.  p[j] holds tap j's products of two such filters side by side, (re, im) of the one in .x, .y and of the
+// other in .z, .w; so does the result.  For a walk whose lanes form the products and whose sums must be uniform.
+__device__ __forceinline__ float4 fir_ccf_generic_sums(const float4 *p, int ntaps)
+{
+    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+    int j = 0;
+    for (; j + 1 < ntaps; j += 2) {
+        const float4 q0 = p[j], q1 = p[j + 1];
+        a0.x += q0.x; a0.y += q0.y; a0.z += q0.z; a0.w += q0.w;
+        a1.x += q1.x; a1.y += q1.y; a1.z += q1.z; a1.w += q1.w;
+    }
+    if (j < ntaps) {
+        const float4 q0 = p[j];
+        a0.x += q0.x; a0.y += q0.y; a0.z += q0.z; a0.w += q0.w;
+    }
+    return make_float4(a0.x + a1.x, a0.y + a1.y, a0.z + a1.z, a0.w + a1.w);
+}
+
 // fused form for the fast kernels
 __device__ __forceinline__ float2 cmul_fma(float2 a, float2 b)
 {

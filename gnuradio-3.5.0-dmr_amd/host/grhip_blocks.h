@@ -36,6 +36,7 @@
 //                                            <- the factories of the same names (gr-digital/include/
 //                                               digital_costas_loop_cc.h, general/gr_pll_*.h)
 //   digital_make_fll_band_edge_cc            <- digital_make_fll_band_edge_cc (gr-digital/include/digital_fll_band_edge_cc.h)
+//   gr_make_pfb_clock_sync_ccf               <- gr_make_pfb_clock_sync_ccf (filter/gr_pfb_clock_sync_ccf.h)
 //   digital_make_constellation_bpsk / _qpsk / _dqpsk / _8psk / _calcdist / _psk / _rect, digital_make_constellation_decoder_cb,
 //   digital_make_constellation_receiver_cb, gr_make_diff_decoder_bb, gr_make_map_bb
 //                                            <- the factories of the same names (gr-digital/include/digital_constellation*.h,
@@ -1789,6 +1790,106 @@ inline grhip_fll_band_edge_cc_sptr digital_make_fll_band_edge_cc(float samps_per
                                                                  int device = 0)
 {
     return gnuradio::get_initial_sptr(new grhip_fll_band_edge_cc_blk(samps_per_sym, rolloff, filter_size, bandwidth, device));
+}
+
+// ---------------------------------------------------------------------------
+// gr_pfb_clock_sync_ccf (sps, loop_bw, taps, filter_size = 32, init_phase = 0, max_rate_deviation = 1.5, osps = 1; 1 input,
+// 1 or 4 outputs: the symbols and, with all four connected, the loop's error, rate and phase; filter/
+// gr_pfb_clock_sync_ccf.h).  A gr_block with history taps_per_filter + floor(sps), as the reference's: the scheduler
+// hands general_work those items before the new ones too, the handle keeps what it needs of the past itself and takes
+// the new items only (include/grhip.h states what is computed).  general_work takes as many new items as noutput_items
+// surely holds the symbols of (osps (items + floor(sps)) <= noutput_items), consumes them all and returns the items
+// produced; a symbol whose last items have not arrived comes with a later call.  output_multiple() is osps (floor(sps) + 1),
+// so that a scheduler never offers less space than one new item may need.  set_taps is not offered.
+// ---------------------------------------------------------------------------
+class grhip_pfb_clock_sync_ccf_blk;
+typedef boost::shared_ptr<grhip_pfb_clock_sync_ccf_blk> grhip_pfb_clock_sync_ccf_sptr;
+class grhip_pfb_clock_sync_ccf_blk : public gr_block {
+    grhip_pfb_clock_sync_ccf *d_h = nullptr;
+    int d_nfilters = 0, d_tpf = 0, d_isps = 0, d_osps = 0;
+    static std::vector<int> iosig() { return {(int)sizeof(gr_complex), (int)sizeof(float), (int)sizeof(float), (int)sizeof(float)}; }
+    grhip_pfb_clock_sync_ccf_blk(double sps, float loop_bw, const std::vector<float> &taps, unsigned int filter_size, float init_phase,
+                                 float max_rate_deviation, int osps, int device)
+        : gr_block("pfb_clock_sync_ccf", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signaturev(1, 4, iosig()))  // .cc:58-60
+    {
+        grhip_detail::check(grhip_pfb_clock_sync_ccf_create(&d_h, sps, loop_bw, taps.data(), (int)taps.size(),
+                                                             filter_size > 0x7fffffffu ? -1 : (int)filter_size, init_phase,
+                                                             max_rate_deviation, osps, device));
+        grhip_detail::check(grhip_pfb_clock_sync_taps(taps.data(), (int)taps.size(), (int)filter_size, nullptr, nullptr, &d_tpf));
+        d_nfilters = (int)filter_size;
+        d_isps = (int)floor(sps);
+        d_osps = osps;
+        set_history(d_tpf + d_isps);                                                        // .cc:245
+        // the least output space that surely holds the symbols of one new item (general_work below); the reference
+        // sets none and leaves noutput_items - osps of its space unused instead (.cc:379)
+        set_output_multiple(d_osps * (d_isps + 1));
+    }
+    friend grhip_pfb_clock_sync_ccf_sptr gr_make_pfb_clock_sync_ccf(double, float, const std::vector<float> &, unsigned int, float, float, int, int);
+    float stream_float(int (*get)(grhip_pfb_clock_sync_ccf *, int, float *)) const
+    {
+        float v = 0;
+        grhip_detail::check(get(d_h, 0, &v));
+        return v;
+    }
+    std::vector<std::vector<float> > bank(int (*get)(grhip_pfb_clock_sync_ccf *, float *, size_t, int *, int *)) const
+    {
+        std::vector<float> flat((size_t)d_nfilters * d_tpf);
+        int nf = 0, tpf = 0;
+        grhip_detail::check(get(d_h, flat.data(), flat.size(), &nf, &tpf));
+        std::vector<std::vector<float> > b(nf);
+        for (int f = 0; f < nf; ++f) b[f].assign(flat.begin() + (size_t)f * tpf, flat.begin() + (size_t)(f + 1) * tpf);
+        return b;
+    }
+public:
+    ~grhip_pfb_clock_sync_ccf_blk() { grhip_pfb_clock_sync_ccf_destroy(d_h); }
+    void set_mode(int mode) { grhip_detail::check(grhip_pfb_clock_sync_ccf_set_mode(d_h, mode)); }
+    std::vector<std::vector<float> > get_taps() const { return bank(grhip_pfb_clock_sync_ccf_get_taps); }
+    std::vector<std::vector<float> > get_diff_taps() const { return bank(grhip_pfb_clock_sync_ccf_get_diff_taps); }
+    std::vector<float> get_channel_taps(int channel) const { return get_taps().at(channel); }
+    std::vector<float> get_diff_channel_taps(int channel) const { return get_diff_taps().at(channel); }
+    void set_loop_bandwidth(float bw) { grhip_detail::check(grhip_pfb_clock_sync_ccf_set_loop_bandwidth(d_h, bw)); }
+    void set_damping_factor(float df) { grhip_detail::check(grhip_pfb_clock_sync_ccf_set_damping_factor(d_h, df)); }
+    void set_alpha(float alpha) { grhip_detail::check(grhip_pfb_clock_sync_ccf_set_alpha(d_h, alpha)); }
+    void set_beta(float beta) { grhip_detail::check(grhip_pfb_clock_sync_ccf_set_beta(d_h, beta)); }
+    void set_max_rate_deviation(float m) { grhip_detail::check(grhip_pfb_clock_sync_ccf_set_max_rate_deviation(d_h, m)); }
+    float get_loop_bandwidth() const { return grhip_pfb_clock_sync_ccf_get_loop_bandwidth(d_h); }
+    float get_damping_factor() const { return grhip_pfb_clock_sync_ccf_get_damping_factor(d_h); }
+    float get_alpha() const { return grhip_pfb_clock_sync_ccf_get_alpha(d_h); }
+    float get_beta() const { return grhip_pfb_clock_sync_ccf_get_beta(d_h); }
+    float get_clock_rate() const { return stream_float(grhip_pfb_clock_sync_ccf_get_clock_rate); }
+    float k() const { return stream_float(grhip_pfb_clock_sync_ccf_k); }
+    float error() const { return stream_float(grhip_pfb_clock_sync_ccf_error); }
+    int slips() const
+    {
+        int v = 0;
+        grhip_detail::check(grhip_pfb_clock_sync_ccf_slips(d_h, 0, &v));
+        return v;
+    }
+    bool check_topology(int, int noutputs) { return noutputs == 1 || noutputs == 4; }       // .cc:108-112
+    int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        const int hist = (int)history() - 1;
+        const long long fresh_n = (long long)ninput_items[0] - hist, room = (long long)(noutput_items / d_osps) - d_isps;
+        const int n = (int)(fresh_n < room ? fresh_n : room);
+        if (n <= 0) {
+            consume_each(0);
+            return 0;
+        }
+        const gr_complex *fresh = (const gr_complex *)in[0] + hist;
+        const bool aux = out.size() == 4;                                                   // .cc:361
+        int produced = 0;
+        grhip_detail::check(grhip_pfb_clock_sync_ccf_work(d_h, n, fresh, noutput_items, out[0], aux ? out[1] : nullptr, aux ? out[2] : nullptr,
+                                                           aux ? out[3] : nullptr, &produced));
+        consume_each(n);
+        return produced;
+    }
+};
+inline grhip_pfb_clock_sync_ccf_sptr gr_make_pfb_clock_sync_ccf(double sps, float loop_bw, const std::vector<float> &taps,
+                                                                unsigned int filter_size = 32, float init_phase = 0,
+                                                                float max_rate_deviation = 1.5, int osps = 1, int device = 0)
+{
+    return gnuradio::get_initial_sptr(
+        new grhip_pfb_clock_sync_ccf_blk(sps, loop_bw, taps, filter_size, init_phase, max_rate_deviation, osps, device));
 }
 
 // gr_firdes::root_raised_cosine(gain, sampling_freq, symbol_rate, alpha, ntaps)

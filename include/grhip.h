@@ -2063,6 +2063,114 @@ GRHIP_API int grhip_fll_band_edge_cc_work(grhip_fll_band_edge_cc *h, int n_in, c
 GRHIP_API int grhip_fll_band_edge_cc_work_device(grhip_fll_band_edge_cc *h, int n_in, const void *d_in, void *d_out, void *d_frq,
                                                  void *d_phs, void *d_err, void *stream);
 
+/* gr_pfb_clock_sync_ccf
+ *   replaces gr_make_pfb_clock_sync_ccf(double sps, float loop_bw, const std::vector<float> &taps,
+ *       unsigned int filter_size, float init_phase, float max_rate_deviation, int osps)
+ *   gnuradio-core/src/lib/filter/gr_pfb_clock_sync_ccf.cc:351-427 (general_work), :208-274 (set_taps,
+ *   create_diff_taps), :200-205 (update_gains); filter/gr_fir_XXX_generic.cc.t:59-79; general/gr_math.h:63-69
+ * Complex in; complex out and, optionally, three float outputs.  Polyphase timing recovery: the
+ * prototype taps are split into nfilters = filter_size arms of tpf = ceil(ntaps / nfilters) taps (arm f's
+ * tap j is taps[f + j nfilters], zeros beyond the prototype), a second bank is built from the
+ * differentiated prototype, and per symbol the loop takes osps outputs of arm floor(k) and one output of
+ * the derivative arm, forms error = (out.im diff.im + out.re diff.re) / 2 and steps rate_f += beta error,
+ * k += alpha error.  A wrap of k over [0, nfilters) is a step of one item in the input: a carry.
+ *
+ * The stream.  With isps = (int)floor(sps), xz is tpf + isps - 1 zeros followed by the input: the
+ * reference's set_history(tpf + sps) as a reader of a linear stream sees it.  pos is an absolute index
+ * into xz and starts at 0.  An evaluation at pos reads xz[pos .. pos + tpf - 1]; tap j of arm f
+ * multiplies xz[pos + tpf - 1 - j] (gr_fir_ccf stores its taps reversed).
+ *
+ * One symbol, literally :379-423.  lo = max(pos - isps + 1, 0).  For kk = 0 .. osps - 1:
+ *     filtnum = (int)floor(k); the two wrap loops, each trip k -+= nfilters (float), pos +-= 1;
+ *     out[i + kk] = arm filtnum at pos + kk;   k = (k + rate_i) + rate_f
+ * then diff = derivative arm filtnum (the last one) at pos, error from out[i] (the first of the osps
+ * outputs), the step, rate_f = gr_branchless_clip(rate_f, max_dev), pos += isps.  Every float operation
+ * is rounded once and nothing is contracted; `/ 2.0` and `0.5 *` are done in double and narrowed;
+ * update_gains keeps its mix: float denom = 1.0 + 2.0 damping bw + (float)(bw bw) from a double
+ * expression, alpha = (4 damping bw) / denom and beta = (4 bw bw) / denom in float.
+ *
+ * Cuts.  The handle takes NEW ITEMS ONLY, S streams back to back, as fll_band_edge_cc does.  Per stream
+ * the device keeps k, rate_f, error, pos, the slips and the last need + isps items of xz, where
+ * need = osps PCS_CARRY + osps + tpf and PCS_CARRY = 8.  A symbol starts once pos + need items of xz
+ * have arrived: then every item it may read is there, whatever it turns out to carry, and no symbol is
+ * rolled back.  THE OUTPUT DEPENDS ON THE CONCATENATED INPUT ALONE, never on where the calls cut it.  The
+ * reference's `ninput - tpf - osps` and `noutput_items - osps` tests are other forms of the same
+ * rule and are not reproduced (its input test allows for no carry, so at the end of a stream it gives a few
+ * symbols more from the same items; a later call gives them here); its "return 0 once after
+ * set_taps" (d_updated) is not reproduced either.
+ *
+ * Three stated deviations keep the walk finite and the history bounded; each event is counted per
+ * stream in slips(s), which is 0 on every signal of a sane scale:
+ *   backward: after its wraps an evaluation may not stand before lo, one item behind the position at
+ *       which the symbol before took its derivative arm; it is put at lo.  So a symbol moves that
+ *       position on by at least one item and produced <= osps (n_in + isps).  (The reference there
+ *       reads in front of its window, and a net negative consume_each fails an assertion in gr_buffer.)
+ *   forward: at most PCS_CARRY forward carries move pos per evaluation; k is still wrapped fully.
+ *   the wrap loops run for at most 64 trips together and only for |k| < 2^29; beyond that k becomes
+ *       the exact double remainder fmod(k, nfilters) (made non-negative) and the carries it stands for
+ *       are cut as above.  A k that is not finite becomes 0, with a slip counted.
+ * The kernel ends and stays in bounds for every bit pattern of the input (csrc/pfb_clock_sync.hip
+ * states why).
+ *
+ * Refused with GRHIP_EINVAL where the reference throws (loop_bw < 0; set_damping_factor, set_alpha,
+ * set_beta outside [0, 1]) and, stated deviations: ntaps < 2 (create_diff_taps indexes with size() - 2,
+ * unsigned); filter_size < 1 or above 256; more than 256 taps per arm or 4096 taps in a padded bank;
+ * sps < 1 or >= 256; osps < 1 or above 8; any argument, tap or derivative tap that is not finite;
+ * gains that are not finite.  A refused setter changes nothing.  The setters act on the next symbol.
+ * set_taps after construction is not offered; pfb_clock_sync_fff (an older loop in this reference, with
+ * the arms assigned in reverse) is not built.
+ *
+ * grhip_pfb_clock_sync_taps(taps, ntaps, nfilters, bank, diff_bank, &tpf) needs no device: *tpf always,
+ * and nfilters * tpf floats to each of bank and diff_bank that is not NULL, arm by arm, as get_taps()
+ * and get_diff_taps() return them.  create_diff_taps is reproduced literally: its pwr gathers fabsf of
+ * the partial sums inside the j loop, and the derivative taps are multiplied by it.
+ *
+ * Outputs.  out holds out_cap complex items per stream, stream s at out + s * out_cap; err, rate and k
+ * (all three given or all NULL) hold out_cap floats per stream each.  produced[s] (S ints) tells the
+ * items written; for work_device it is on the device and the entry does not synchronise (the squelch
+ * blocks' convention).  grhip_pfb_clock_sync_ccf_max_produced(h, n_in) = osps (n_in + isps) tells an
+ * out_cap that always suffices; a smaller one is GRHIP_EINVAL, and so is one above 2^31 - 1.  Slot i
+ * of a symbol holds what the reference writes there: d_error and d_rate_f from before the step, d_k
+ * after the last phase advance;
+ * the osps - 1 slots behind it get the same values (the reference leaves them unwritten: a stated
+ * deviation).  n_in may be 0.  No buffer may overlap another.
+ *
+ * GRHIP_MODE_GENERIC: the arm sums run in gr_fir_ccf_generic's order (two complex accumulators over the
+ * even and the odd taps, the tail of an odd count into the first, acc0 + acc1), each product and sum
+ * rounded once: bit for bit the restatement in tests/pfb_clock_sync_ref.py and through it the
+ * reference (tests/golden/ref_pfb_clock_sync.npz).  Every other mode: the same scalar loop arithmetic,
+ * the dot products in fused multiply-adds and tree order.
+ * get_clock_rate, k, error, slips and position read stream s's state (they wait for the device). */
+typedef struct grhip_pfb_clock_sync_ccf grhip_pfb_clock_sync_ccf;
+GRHIP_API int grhip_pfb_clock_sync_taps(const float *taps, int ntaps, int nfilters, float *bank, float *diff_bank, int *tpf);
+GRHIP_API int grhip_pfb_clock_sync_ccf_create(grhip_pfb_clock_sync_ccf **h, double sps, float loop_bw, const float *taps, int ntaps,
+                                              int filter_size, float init_phase, float max_rate_deviation, int osps, int device);
+GRHIP_API void grhip_pfb_clock_sync_ccf_destroy(grhip_pfb_clock_sync_ccf *h);
+GRHIP_API int grhip_pfb_clock_sync_ccf_set_mode(grhip_pfb_clock_sync_ccf *h, int mode);
+GRHIP_API int grhip_pfb_clock_sync_ccf_set_streams(grhip_pfb_clock_sync_ccf *h, int nstreams);
+GRHIP_API int grhip_pfb_clock_sync_ccf_set_loop_bandwidth(grhip_pfb_clock_sync_ccf *h, float bw);
+GRHIP_API int grhip_pfb_clock_sync_ccf_set_damping_factor(grhip_pfb_clock_sync_ccf *h, float df);
+GRHIP_API int grhip_pfb_clock_sync_ccf_set_alpha(grhip_pfb_clock_sync_ccf *h, float alpha);
+GRHIP_API int grhip_pfb_clock_sync_ccf_set_beta(grhip_pfb_clock_sync_ccf *h, float beta);
+GRHIP_API int grhip_pfb_clock_sync_ccf_set_max_rate_deviation(grhip_pfb_clock_sync_ccf *h, float max_rate_deviation);
+GRHIP_API float grhip_pfb_clock_sync_ccf_get_loop_bandwidth(grhip_pfb_clock_sync_ccf *h);
+GRHIP_API float grhip_pfb_clock_sync_ccf_get_damping_factor(grhip_pfb_clock_sync_ccf *h);
+GRHIP_API float grhip_pfb_clock_sync_ccf_get_alpha(grhip_pfb_clock_sync_ccf *h);
+GRHIP_API float grhip_pfb_clock_sync_ccf_get_beta(grhip_pfb_clock_sync_ccf *h);
+GRHIP_API float grhip_pfb_clock_sync_ccf_get_max_rate_deviation(grhip_pfb_clock_sync_ccf *h);
+GRHIP_API int grhip_pfb_clock_sync_ccf_get_clock_rate(grhip_pfb_clock_sync_ccf *h, int s, float *rate);
+GRHIP_API int grhip_pfb_clock_sync_ccf_k(grhip_pfb_clock_sync_ccf *h, int s, float *k);
+GRHIP_API int grhip_pfb_clock_sync_ccf_error(grhip_pfb_clock_sync_ccf *h, int s, float *error);
+GRHIP_API int grhip_pfb_clock_sync_ccf_slips(grhip_pfb_clock_sync_ccf *h, int s, int *slips);
+GRHIP_API int grhip_pfb_clock_sync_ccf_position(grhip_pfb_clock_sync_ccf *h, int s, long long *pos);
+GRHIP_API int grhip_pfb_clock_sync_ccf_get_taps(grhip_pfb_clock_sync_ccf *h, float *bank, size_t cap, int *nfilters, int *tpf);
+GRHIP_API int grhip_pfb_clock_sync_ccf_get_diff_taps(grhip_pfb_clock_sync_ccf *h, float *bank, size_t cap, int *nfilters, int *tpf);
+GRHIP_API int grhip_pfb_clock_sync_ccf_max_produced(grhip_pfb_clock_sync_ccf *h, int n_in);
+GRHIP_API int grhip_pfb_clock_sync_ccf_work(grhip_pfb_clock_sync_ccf *h, int n_in, const void *in, long long out_cap, void *out, void *err,
+                                            void *rate, void *k, int *produced);
+GRHIP_API int grhip_pfb_clock_sync_ccf_work_device(grhip_pfb_clock_sync_ccf *h, int n_in, const void *d_in, long long out_cap, void *d_out,
+                                                   void *d_err, void *d_rate, void *d_k, int *d_produced, void *stream);
+
 /* ======================================================================
  * digital_constellation and its kinds (host objects; no device is needed)
  *   replaces digital_make_constellation_bpsk / _qpsk / _dqpsk / _8psk (), digital_make_constellation_calcdist
