@@ -52,6 +52,19 @@
 //   gr_make_am_demod_cf, gr_make_demod_10k0a3e_cf   <- blks2.am_demod_cf / demod_10k0a3e_cf (blks2impl/am_demod.py), one block
 //   gr_make_demod_20k0f3e_cf, gr_make_demod_200kf3e_cf   <- the FM presets of blks2impl/fm_demod.py:74-111
 //
+// Ownership.  A C handle has one owner, grhip_detail::handle: move-only, null until a create call has filled it, and
+// it calls the handle's destroy function exactly once.  A block derives from grhip_detail::block<GNU Radio base,
+// handle type, destroy, set_mode>, which holds that owner as the member d_h (so a constructor that throws after
+// create releases the handle, and no block can be copied), forwards the base's constructor arguments, and has
+// set_mode, checked() and the work / general_work / forecast shapes that several blocks share.  A block keeps its
+// constructor non-public, befriends grhip_detail::factory once, and its factory function calls factory::make.
+// A macro here pastes names only: typedefs, a table of the grhip_NAME_* functions a template asks for, a one-line
+// class with its constructor, the factory.  Code that does something lives in a template or a plain function.  Four
+// families of two to four blocks (dc_blocker, integrate, the spectrum blocks, pwr_squelch) are still stamped as whole
+// classes, where a template and its table would be longer: such a macro opens and closes its class itself, and every
+// member in it, work included, forwards one call.  The header needs C++17 (host/Makefile builds with -std=c++17) and,
+// of GNU Radio, only the constructors and members that gr_shim.h mirrors.
+//
 // output_multiple is the REFERENCE's for every block (1; nsamples for fft_filter_ccc; the
 // channeliser's own), so a finite flowgraph produces exactly the items the reference block
 // produces, tail included.  The scheduler then hands a block at most half a 64 KiB buffer per
@@ -64,9 +77,12 @@
 // (runtime/gr_block_executor.cc:335-348).
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/grhip.h"
@@ -85,7 +101,112 @@ inline void check(int rc)
     default: throw std::runtime_error(msg);
     }
 }
+
+// the one owner of a C handle: null until a create call fills it through out(), released exactly once
+template <class H, void (*DESTROY)(H *)> class handle {
+    H *d_p = nullptr;
+public:
+    handle() {}
+    explicit handle(H *p) : d_p(p) {}
+    handle(handle &&o) noexcept : d_p(o.d_p) { o.d_p = nullptr; }
+    handle &operator=(handle &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            d_p = o.d_p;
+            o.d_p = nullptr;
+        }
+        return *this;
+    }
+    handle(const handle &) = delete;
+    handle &operator=(const handle &) = delete;
+    ~handle() { reset(); }
+    void reset()
+    {
+        if (d_p) DESTROY(d_p);
+        d_p = nullptr;
+    }
+    H **out()                                       // what a create call takes; releases what was held before
+    {
+        reset();
+        return &d_p;
+    }
+    H *get() const { return d_p; }
+    operator H *() const { return d_p; }            // so that the C calls read grhip_xxx_work(d_h, ...)
+};
+
+// the one place that makes a block: every block class befriends it and keeps its constructor non-public
+struct factory {
+    template <class B, class... A> static boost::shared_ptr<B> make(A &&...a)
+    {
+        return gnuradio::get_initial_sptr(new B(std::forward<A>(a)...));
+    }
+};
+
+// as many units of input as there are, cut so that no more than noutput_items come out of a block that keeps one
+// unit in `every` (gr_keep_one_in_n.cc:80); produced(h, n) tells the count for n units without changing the state
+template <class H, class F> inline int cut_to_output(H *h, F produced, int n, int noutput_items, int every)
+{
+    while (n > 0 && produced(h, n) > noutput_items) {
+        const int over = produced(h, n) - noutput_items;
+        n -= over > 1 ? (over - 1) * every : 1;
+    }
+    return n;
+}
+
+// the base of every block: BASE is the GNU Radio class and gets the constructor's arguments, d_h owns the handle
+template <class BASE, class H, void (*DESTROY)(H *), auto SET_MODE = nullptr> class block : public BASE {
+protected:
+    handle<H, DESTROY> d_h;
+    template <class... A> explicit block(A &&...a) : BASE(std::forward<A>(a)...) {}
+    // the result of a C call, after check() has thrown for a failure
+    static int checked(int r)
+    {
+        check(r);
+        return r;
+    }
+    // forecast: every input needs the items that a C call answers for noutput_items
+    template <class F> void forecast_each(F forecast, int noutput_items, gr_vector_int &req)
+    {
+        const int n = checked(forecast(d_h, noutput_items));
+        for (size_t i = 0; i < req.size(); i++) req[i] = n;
+    }
+    // general_work over a C entry that reports the items it consumed
+    template <class F>
+    int work_consumed(F general_work, int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
+                      gr_vector_void_star &out)
+    {
+        int consumed = 0;
+        int r = checked(general_work(d_h, noutput_items, ninput_items[0], in[0], out[0], &consumed));
+        this->consume_each(consumed);
+        return r;
+    }
+    // general_work that uses all the inputs and reports the outputs copied (gr_squelch_base_cc.cc:42-93)
+    template <class F>
+    int work_all_inputs(F work, int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
+                        gr_vector_void_star &out)
+    {
+        const int n = noutput_items < ninput_items[0] ? noutput_items : ninput_items[0];
+        int produced = 0;
+        check(work(d_h, n, in[0], out[0], &produced));
+        this->consume_each(n);
+        return produced;
+    }
+public:
+    // numeric mode of the handle (GRHIP_MODE_*), for the blocks whose handle has one
+    template <class F = decltype(SET_MODE), class = typename std::enable_if<!std::is_same<F, std::nullptr_t>::value>::type>
+    void set_mode(int mode)
+    {
+        check(SET_MODE(d_h, mode));
+    }
+};
 }  // namespace grhip_detail
+
+// the base of the block over handle grhip_NAME, with and without the handle's set_mode
+#define GRHIP_BLOCK(GRBASE, NAME) grhip_detail::block<GRBASE, grhip_##NAME, grhip_##NAME##_destroy, grhip_##NAME##_set_mode>
+#define GRHIP_BLOCK_NO_MODE(GRBASE, NAME) grhip_detail::block<GRBASE, grhip_##NAME, grhip_##NAME##_destroy>
+// one entry of a table of C functions: T::create is grhip_NAME_create
+#define GRHIP_FN(NAME, F) static constexpr auto F = &grhip_##NAME##_##F
 
 // opt-in batching (see the header comment): work() calls of n times the block's own output multiple
 template <class BLOCK_SPTR> inline void grhip_set_batch_items(const BLOCK_SPTR &b, int n)
@@ -97,45 +218,39 @@ template <class BLOCK_SPTR> inline void grhip_set_batch_items(const BLOCK_SPTR &
 // ---------------------------------------------------------------------------
 // gr_fir_filter_XXX
 // ---------------------------------------------------------------------------
-template <class IN, class OUT, class TAP> class grhip_fir_filter_base : public gr_sync_decimator {
+template <class IN, class OUT, class TAP> class grhip_fir_filter_base : public GRHIP_BLOCK_NO_MODE(gr_sync_decimator, fir_filter) {
 protected:
-    grhip_fir_filter *d_h = nullptr;
     grhip_fir_filter_base(const char *name, const char *kind, int decimation, const std::vector<TAP> &taps,
                           int device)
-        : gr_sync_decimator(name, gr_make_io_signature(1, 1, sizeof(IN)), gr_make_io_signature(1, 1, sizeof(OUT)),
-                            decimation)
+        : block(name, gr_make_io_signature(1, 1, sizeof(IN)), gr_make_io_signature(1, 1, sizeof(OUT)), decimation)
     {
-        grhip_detail::check(grhip_fir_filter_create(&d_h, kind, decimation, (const float *)taps.data(), taps.size(),
+        grhip_detail::check(grhip_fir_filter_create(d_h.out(), kind, decimation, (const float *)taps.data(), taps.size(),
                                                     device));
         set_history(grhip_fir_filter_history(d_h));          // set_history(d_fir->ntaps()), .cc.t:51
     }
 public:
-    ~grhip_fir_filter_base() { grhip_fir_filter_destroy(d_h); }
     void set_taps(const std::vector<TAP> &taps)                // .cc.t:59-64
     {
         grhip_detail::check(grhip_fir_filter_set_taps(d_h, (const float *)taps.data(), taps.size()));
     }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_fir_filter_work(d_h, noutput_items, in[0], out[0]);
-        grhip_detail::check(r);
+        int r = checked(grhip_fir_filter_work(d_h, noutput_items, in[0], out[0]));
         if (r == 0) set_history(grhip_fir_filter_history(d_h));   // taps changed: history may have too
         return r;
     }
 };
 
 #define GRHIP_FIR_CLASS(NAME, KIND, IN, OUT, TAP)                                                          \
-    class NAME;                                                                                            \
-    typedef boost::shared_ptr<NAME> NAME##_sptr;                                                           \
-    NAME##_sptr grhip_make_##KIND(int decimation, const std::vector<TAP> &taps, int device);               \
     class NAME : public grhip_fir_filter_base<IN, OUT, TAP> {                                              \
-        friend NAME##_sptr grhip_make_##KIND(int, const std::vector<TAP> &, int);                          \
+        friend struct grhip_detail::factory;                                                               \
         NAME(int decimation, const std::vector<TAP> &taps, int device)                                     \
             : grhip_fir_filter_base<IN, OUT, TAP>(#KIND, &#KIND[11], decimation, taps, device) {}          \
     };                                                                                                     \
+    typedef boost::shared_ptr<NAME> NAME##_sptr;                                                           \
     inline NAME##_sptr grhip_make_##KIND(int decimation, const std::vector<TAP> &taps, int device = 0)     \
     {                                                                                                      \
-        return gnuradio::get_initial_sptr(new NAME(decimation, taps, device));                             \
+        return grhip_detail::factory::make<NAME>(decimation, taps, device);                                \
     }
 // &"fir_filter_ccf"[11] == "ccf"
 GRHIP_FIR_CLASS(grhip_fir_filter_ccf, fir_filter_ccf, gr_complex, gr_complex, float)
@@ -144,34 +259,31 @@ GRHIP_FIR_CLASS(grhip_fir_filter_ccc, fir_filter_ccc, gr_complex, gr_complex, gr
 GRHIP_FIR_CLASS(grhip_fir_filter_fcc, fir_filter_fcc, float, gr_complex, gr_complex)
 GRHIP_FIR_CLASS(grhip_fir_filter_scc, fir_filter_scc, short, gr_complex, gr_complex)
 GRHIP_FIR_CLASS(grhip_fir_filter_fsf, fir_filter_fsf, float, short, float)
+#undef GRHIP_FIR_CLASS
 
 // ---------------------------------------------------------------------------
 // gr_freq_xlating_fir_filter_{ccc,ccf,fcf,fcc,scf,scc}: one template over the family handle
 // (filter/gr_freq_xlating_fir_filter_XXX.h.t:64-99, .cc.t:38-123)
 // ---------------------------------------------------------------------------
-template <class IN, class TAP> class grhip_freq_xlating_fir_filter_blk : public gr_sync_decimator {
-    grhip_freq_xlating_fir_filter *d_h = nullptr;
+template <class IN, class TAP>
+class grhip_freq_xlating_fir_filter_blk : public GRHIP_BLOCK(gr_sync_decimator, freq_xlating_fir_filter) {
 public:
     grhip_freq_xlating_fir_filter_blk(const char *name, const char *kind, int decimation, const std::vector<TAP> &taps,
                                       double center_freq, double sampling_freq, int device)
-        : gr_sync_decimator(name, gr_make_io_signature(1, 1, sizeof(IN)), gr_make_io_signature(1, 1, sizeof(gr_complex)),
-                            decimation)
+        : block(name, gr_make_io_signature(1, 1, sizeof(IN)), gr_make_io_signature(1, 1, sizeof(gr_complex)), decimation)
     {
-        grhip_detail::check(grhip_freq_xlating_fir_filter_create(&d_h, kind, decimation, (const float *)taps.data(),
+        grhip_detail::check(grhip_freq_xlating_fir_filter_create(d_h.out(), kind, decimation, (const float *)taps.data(),
                                                                  taps.size(), center_freq, sampling_freq, device));
         set_history(grhip_freq_xlating_fir_filter_history(d_h));
     }
-    ~grhip_freq_xlating_fir_filter_blk() { grhip_freq_xlating_fir_filter_destroy(d_h); }
     void set_center_freq(double f) { grhip_detail::check(grhip_freq_xlating_fir_filter_set_center_freq(d_h, f)); }
     void set_taps(const std::vector<TAP> &taps)
     {
         grhip_detail::check(grhip_freq_xlating_fir_filter_set_taps(d_h, (const float *)taps.data(), taps.size()));
     }
-    void set_mode(int mode) { grhip_detail::check(grhip_freq_xlating_fir_filter_set_mode(d_h, mode)); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_freq_xlating_fir_filter_work(d_h, noutput_items, in[0], out[0]);
-        grhip_detail::check(r);
+        int r = checked(grhip_freq_xlating_fir_filter_work(d_h, noutput_items, in[0], out[0]));
         if (r == 0) set_history(grhip_freq_xlating_fir_filter_history(d_h));   // set_history(ntaps), return 0 (.cc.t:109-114)
         return r;
     }
@@ -182,8 +294,8 @@ public:
     inline grhip_freq_xlating_fir_filter_##SUF##_sptr grhip_make_freq_xlating_fir_filter_##SUF(                     \
         int decimation, const std::vector<TAP> &taps, double center_freq, double sampling_freq, int device = 0)     \
     {                                                                                                              \
-        return gnuradio::get_initial_sptr(new grhip_freq_xlating_fir_filter_##SUF##_blk(                          \
-            "freq_xlating_fir_filter_" #SUF, #SUF, decimation, taps, center_freq, sampling_freq, device));        \
+        return grhip_detail::factory::make<grhip_freq_xlating_fir_filter_##SUF##_blk>(                            \
+            "freq_xlating_fir_filter_" #SUF, #SUF, decimation, taps, center_freq, sampling_freq, device);         \
     }
 GRHIP_XLATING_CLASS(ccc, gr_complex, gr_complex)
 GRHIP_XLATING_CLASS(ccf, gr_complex, float)
@@ -191,68 +303,55 @@ GRHIP_XLATING_CLASS(fcf, float, float)
 GRHIP_XLATING_CLASS(fcc, float, gr_complex)
 GRHIP_XLATING_CLASS(scf, short, float)
 GRHIP_XLATING_CLASS(scc, short, gr_complex)
+#undef GRHIP_XLATING_CLASS
 
 // ---------------------------------------------------------------------------
 // gr_quadrature_demod_cf
 // ---------------------------------------------------------------------------
-class grhip_quadrature_demod_cf_blk;
-typedef boost::shared_ptr<grhip_quadrature_demod_cf_blk> grhip_quadrature_demod_cf_sptr;
-class grhip_quadrature_demod_cf_blk : public gr_sync_block {
-    grhip_quadrature_demod_cf *d_h = nullptr;
+class grhip_quadrature_demod_cf_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_block, quadrature_demod_cf) {
+    friend struct grhip_detail::factory;
     grhip_quadrature_demod_cf_blk(float gain, int device)
-        : gr_sync_block("quadrature_demod_cf", gr_make_io_signature(1, 1, sizeof(gr_complex)),
-                        gr_make_io_signature(1, 1, sizeof(float)))
+        : block("quadrature_demod_cf", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(float)))
     {
-        grhip_detail::check(grhip_quadrature_demod_cf_create(&d_h, gain, device));
+        grhip_detail::check(grhip_quadrature_demod_cf_create(d_h.out(), gain, device));
         set_history(2);                                        // gr_quadrature_demod_cf.cc:37
     }
-    friend grhip_quadrature_demod_cf_sptr grhip_make_quadrature_demod_cf(float, int);
 public:
-    ~grhip_quadrature_demod_cf_blk() { grhip_quadrature_demod_cf_destroy(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_quadrature_demod_cf_work(d_h, noutput_items, in[0], out[0]);
-        grhip_detail::check(r);
-        return r;
+        return checked(grhip_quadrature_demod_cf_work(d_h, noutput_items, in[0], out[0]));
     }
 };
+typedef boost::shared_ptr<grhip_quadrature_demod_cf_blk> grhip_quadrature_demod_cf_sptr;
 inline grhip_quadrature_demod_cf_sptr grhip_make_quadrature_demod_cf(float gain, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_quadrature_demod_cf_blk(gain, device));
+    return grhip_detail::factory::make<grhip_quadrature_demod_cf_blk>(gain, device);
 }
 
 // ---------------------------------------------------------------------------
 // digital_clock_recovery_mm_ff  (a gr_block: general_work + forecast + consume_each)
 // ---------------------------------------------------------------------------
-class grhip_clock_recovery_mm_ff_blk;
-typedef boost::shared_ptr<grhip_clock_recovery_mm_ff_blk> grhip_clock_recovery_mm_ff_sptr;
-class grhip_clock_recovery_mm_ff_blk : public gr_block {
-    grhip_clock_recovery_mm_ff *d_h = nullptr;
+class grhip_clock_recovery_mm_ff_blk : public GRHIP_BLOCK_NO_MODE(gr_block, clock_recovery_mm_ff) {
+    friend struct grhip_detail::factory;
     grhip_clock_recovery_mm_ff_blk(float omega, float gain_omega, float mu, float gain_mu,
                                    float omega_relative_limit, int device)
-        : gr_block("clock_recovery_mm_ff", gr_make_io_signature(1, 1, sizeof(float)),
-                   gr_make_io_signature(1, 1, sizeof(float)))
+        : block("clock_recovery_mm_ff", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(float)))
     {
-        grhip_detail::check(grhip_clock_recovery_mm_ff_create(&d_h, omega, gain_omega, mu, gain_mu,
+        grhip_detail::check(grhip_clock_recovery_mm_ff_create(d_h.out(), omega, gain_omega, mu, gain_mu,
                                                               omega_relative_limit, device));
         set_relative_rate(1.0 / omega);                        // .cc:64
     }
-    friend grhip_clock_recovery_mm_ff_sptr grhip_make_clock_recovery_mm_ff(float, float, float, float, float, int);
 public:
-    ~grhip_clock_recovery_mm_ff_blk() { grhip_clock_recovery_mm_ff_destroy(d_h); }
     void forecast(int noutput_items, gr_vector_int &req) override
     {
-        int n = grhip_clock_recovery_mm_ff_forecast(d_h, noutput_items);
-        grhip_detail::check(n);
-        for (size_t i = 0; i < req.size(); i++) req[i] = n;
+        forecast_each(grhip_clock_recovery_mm_ff_forecast, noutput_items, req);
     }
     int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
                      gr_vector_void_star &out) override
     {
         int consumed = 0;
-        int r = grhip_clock_recovery_mm_ff_general_work(d_h, noutput_items, ninput_items[0], (const float *)in[0],
-                                                        (float *)out[0], &consumed);
-        grhip_detail::check(r);
+        int r = checked(grhip_clock_recovery_mm_ff_general_work(d_h, noutput_items, ninput_items[0], (const float *)in[0],
+                                                                (float *)out[0], &consumed));
         consume_each(consumed);
         return r;
     }
@@ -265,60 +364,51 @@ public:
     void set_mu(float v) { grhip_detail::check(grhip_clock_recovery_mm_ff_set_mu(d_h, v)); }
     void set_omega(float v) { grhip_detail::check(grhip_clock_recovery_mm_ff_set_omega(d_h, v)); }
 };
+typedef boost::shared_ptr<grhip_clock_recovery_mm_ff_blk> grhip_clock_recovery_mm_ff_sptr;
 inline grhip_clock_recovery_mm_ff_sptr grhip_make_clock_recovery_mm_ff(float omega, float gain_omega, float mu,
                                                                        float gain_mu, float omega_relative_limit,
                                                                        int device = 0)
 {
-    return gnuradio::get_initial_sptr(
-        new grhip_clock_recovery_mm_ff_blk(omega, gain_omega, mu, gain_mu, omega_relative_limit, device));
+    return grhip_detail::factory::make<grhip_clock_recovery_mm_ff_blk>(omega, gain_omega, mu, gain_mu, omega_relative_limit,
+                                                                       device);
 }
 
 // ---------------------------------------------------------------------------
 // digital_binary_slicer_fb, digital_correlate_access_code_bb
 // ---------------------------------------------------------------------------
-class grhip_binary_slicer_fb_blk;
-typedef boost::shared_ptr<grhip_binary_slicer_fb_blk> grhip_binary_slicer_fb_sptr;
-class grhip_binary_slicer_fb_blk : public gr_sync_block {
-    grhip_binary_slicer_fb *d_h = nullptr;
+class grhip_binary_slicer_fb_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_block, binary_slicer_fb) {
+    friend struct grhip_detail::factory;
     explicit grhip_binary_slicer_fb_blk(int device)
-        : gr_sync_block("binary_slicer_fb", gr_make_io_signature(1, 1, sizeof(float)),
-                        gr_make_io_signature(1, 1, sizeof(unsigned char)))
+        : block("binary_slicer_fb", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(unsigned char)))
     {
-        grhip_detail::check(grhip_binary_slicer_fb_create(&d_h, device));
+        grhip_detail::check(grhip_binary_slicer_fb_create(d_h.out(), device));
     }
-    friend grhip_binary_slicer_fb_sptr grhip_make_binary_slicer_fb(int);
 public:
-    ~grhip_binary_slicer_fb_blk() { grhip_binary_slicer_fb_destroy(d_h); }
     int work(int n, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_binary_slicer_fb_work(d_h, n, (const float *)in[0], (unsigned char *)out[0]);
-        grhip_detail::check(r);
-        return r;
+        return checked(grhip_binary_slicer_fb_work(d_h, n, (const float *)in[0], (unsigned char *)out[0]));
     }
 };
+typedef boost::shared_ptr<grhip_binary_slicer_fb_blk> grhip_binary_slicer_fb_sptr;
 inline grhip_binary_slicer_fb_sptr grhip_make_binary_slicer_fb(int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_binary_slicer_fb_blk(device));
+    return grhip_detail::factory::make<grhip_binary_slicer_fb_blk>(device);
 }
 
 // digital_clock_recovery_mm_cc (gr-digital/include/digital_clock_recovery_mm_cc.h:44-110): one complex input,
 // one complex output and the optional float error output (the shim's io signature carries one item size, so the
 // second port is described by the comment only; general_work looks at out.size() like the reference)
-class grhip_clock_recovery_mm_cc_blk;
-typedef boost::shared_ptr<grhip_clock_recovery_mm_cc_blk> grhip_clock_recovery_mm_cc_sptr;
-class grhip_clock_recovery_mm_cc_blk : public gr_block {
-    grhip_clock_recovery_mm_cc *d_h = nullptr;
+class grhip_clock_recovery_mm_cc_blk : public GRHIP_BLOCK_NO_MODE(gr_block, clock_recovery_mm_cc) {
+    friend struct grhip_detail::factory;
     grhip_clock_recovery_mm_cc_blk(float omega, float gain_omega, float mu, float gain_mu, float omega_relative_limit,
                                    int device)
-        : gr_block("clock_recovery_mm_cc", gr_make_io_signature(1, 1, sizeof(gr_complex)),
-                   gr_make_io_signature(1, 2, sizeof(gr_complex)))
+        : block("clock_recovery_mm_cc", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 2, sizeof(gr_complex)))
     {
-        grhip_detail::check(grhip_clock_recovery_mm_cc_create(&d_h, omega, gain_omega, mu, gain_mu,
+        grhip_detail::check(grhip_clock_recovery_mm_cc_create(d_h.out(), omega, gain_omega, mu, gain_mu,
                                                               omega_relative_limit, device));
         set_relative_rate(1.0 / omega);                        // .cc:68
         set_history(3);                                        // .cc:69
     }
-    friend grhip_clock_recovery_mm_cc_sptr grhip_make_clock_recovery_mm_cc(float, float, float, float, float, int);
     float get(int (*f)(grhip_clock_recovery_mm_cc *, float *)) const
     {
         float v = 0;
@@ -326,20 +416,16 @@ class grhip_clock_recovery_mm_cc_blk : public gr_block {
         return v;
     }
 public:
-    ~grhip_clock_recovery_mm_cc_blk() { grhip_clock_recovery_mm_cc_destroy(d_h); }
     void forecast(int noutput_items, gr_vector_int &req) override
     {
-        int n = grhip_clock_recovery_mm_cc_forecast(d_h, noutput_items);
-        grhip_detail::check(n);
-        for (size_t i = 0; i < req.size(); i++) req[i] = n;
+        forecast_each(grhip_clock_recovery_mm_cc_forecast, noutput_items, req);
     }
     int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
                      gr_vector_void_star &out) override
     {
         int consumed = 0;
         float *err = out.size() >= 2 ? (float *)out[1] : nullptr;          // .cc:124-126
-        int r = grhip_clock_recovery_mm_cc_general_work(d_h, noutput_items, ninput_items[0], in[0], out[0], err, &consumed);
-        grhip_detail::check(r);
+        int r = checked(grhip_clock_recovery_mm_cc_general_work(d_h, noutput_items, ninput_items[0], in[0], out[0], err, &consumed));
         consume_each(consumed);
         return r;
     }
@@ -352,28 +438,24 @@ public:
     void set_mu(float v) { grhip_detail::check(grhip_clock_recovery_mm_cc_set_mu(d_h, v)); }
     void set_omega(float v) { grhip_detail::check(grhip_clock_recovery_mm_cc_set_omega(d_h, v)); }
 };
+typedef boost::shared_ptr<grhip_clock_recovery_mm_cc_blk> grhip_clock_recovery_mm_cc_sptr;
 inline grhip_clock_recovery_mm_cc_sptr grhip_make_clock_recovery_mm_cc(float omega, float gain_omega, float mu,
                                                                        float gain_mu, float omega_relative_limit,
                                                                        int device = 0)
 {
-    return gnuradio::get_initial_sptr(
-        new grhip_clock_recovery_mm_cc_blk(omega, gain_omega, mu, gain_mu, omega_relative_limit, device));
+    return grhip_detail::factory::make<grhip_clock_recovery_mm_cc_blk>(omega, gain_omega, mu, gain_mu, omega_relative_limit,
+                                                                       device);
 }
 
 // pager_slicer_fb (gr-pager/lib/pager_slicer_fb.h:30-58), gr_unpack_k_bits_bb (general/gr_unpack_k_bits_bb.h)
-class grhip_pager_slicer_fb_blk;
-typedef boost::shared_ptr<grhip_pager_slicer_fb_blk> grhip_pager_slicer_fb_sptr;
-class grhip_pager_slicer_fb_blk : public gr_sync_block {
-    grhip_pager_slicer_fb *d_h = nullptr;
+class grhip_pager_slicer_fb_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_block, pager_slicer_fb) {
+    friend struct grhip_detail::factory;
     grhip_pager_slicer_fb_blk(float alpha, int device)
-        : gr_sync_block("slicer_fb", gr_make_io_signature(1, 1, sizeof(float)),
-                        gr_make_io_signature(1, 1, sizeof(unsigned char)))
+        : block("slicer_fb", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(unsigned char)))
     {
-        grhip_detail::check(grhip_pager_slicer_fb_create(&d_h, alpha, device));
+        grhip_detail::check(grhip_pager_slicer_fb_create(d_h.out(), alpha, device));
     }
-    friend grhip_pager_slicer_fb_sptr grhip_make_pager_slicer_fb(float, int);
 public:
-    ~grhip_pager_slicer_fb_blk() { grhip_pager_slicer_fb_destroy(d_h); }
     float dc_offset() const
     {
         float v = 0;
@@ -382,68 +464,55 @@ public:
     }
     int work(int n, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_pager_slicer_fb_work(d_h, n, (const float *)in[0], (unsigned char *)out[0]);
-        grhip_detail::check(r);
-        return r;
+        return checked(grhip_pager_slicer_fb_work(d_h, n, (const float *)in[0], (unsigned char *)out[0]));
     }
 };
+typedef boost::shared_ptr<grhip_pager_slicer_fb_blk> grhip_pager_slicer_fb_sptr;
 inline grhip_pager_slicer_fb_sptr grhip_make_pager_slicer_fb(float alpha, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_pager_slicer_fb_blk(alpha, device));
+    return grhip_detail::factory::make<grhip_pager_slicer_fb_blk>(alpha, device);
 }
 
-class grhip_unpack_k_bits_bb_blk;
-typedef boost::shared_ptr<grhip_unpack_k_bits_bb_blk> grhip_unpack_k_bits_bb_sptr;
-class grhip_unpack_k_bits_bb_blk : public gr_sync_interpolator {
-    grhip_unpack_k_bits_bb *d_h = nullptr;
+class grhip_unpack_k_bits_bb_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_interpolator, unpack_k_bits_bb) {
+    friend struct grhip_detail::factory;
     grhip_unpack_k_bits_bb_blk(unsigned k, int device)
-        : gr_sync_interpolator("unpack_k_bits_bb", gr_make_io_signature(1, 1, sizeof(unsigned char)),
-                               gr_make_io_signature(1, 1, sizeof(unsigned char)), k)
+        : block("unpack_k_bits_bb", gr_make_io_signature(1, 1, sizeof(unsigned char)),
+                gr_make_io_signature(1, 1, sizeof(unsigned char)), k)
     {
         // the reference throws std::out_of_range("interpolation must be > 0") (.cc:45-46)
-        grhip_detail::check(grhip_unpack_k_bits_bb_create(&d_h, k, device));
+        grhip_detail::check(grhip_unpack_k_bits_bb_create(d_h.out(), k, device));
     }
-    friend grhip_unpack_k_bits_bb_sptr grhip_make_unpack_k_bits_bb(unsigned, int);
 public:
-    ~grhip_unpack_k_bits_bb_blk() { grhip_unpack_k_bits_bb_destroy(d_h); }
     int work(int n, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_unpack_k_bits_bb_work(d_h, n, (const unsigned char *)in[0], (unsigned char *)out[0]);
-        grhip_detail::check(r);
-        return r;
+        return checked(grhip_unpack_k_bits_bb_work(d_h, n, (const unsigned char *)in[0], (unsigned char *)out[0]));
     }
 };
+typedef boost::shared_ptr<grhip_unpack_k_bits_bb_blk> grhip_unpack_k_bits_bb_sptr;
 inline grhip_unpack_k_bits_bb_sptr grhip_make_unpack_k_bits_bb(unsigned k, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_unpack_k_bits_bb_blk(k, device));
+    return grhip_detail::factory::make<grhip_unpack_k_bits_bb_blk>(k, device);
 }
 
 // gr_framer_sink_1 (general/gr_framer_sink_1.h:34-107): same constructor argument, same messages in the same queue
-class grhip_framer_sink_1_blk;
-typedef boost::shared_ptr<grhip_framer_sink_1_blk> grhip_framer_sink_1_sptr;
-class grhip_framer_sink_1_blk : public gr_sync_block {
-    grhip_framer_sink_1 *d_h = nullptr;
+class grhip_framer_sink_1_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_block, framer_sink_1) {
+    friend struct grhip_detail::factory;
     gr_msg_queue_sptr d_target_queue;
     std::vector<unsigned char> d_buf;
     grhip_framer_sink_1_blk(gr_msg_queue_sptr target_queue, int device)
-        : gr_sync_block("framer_sink_1", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(0, 0, 0)),
+        : block("framer_sink_1", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(0, 0, 0)),
           d_target_queue(target_queue), d_buf(4096)
     {
-        grhip_detail::check(grhip_framer_sink_1_create(&d_h, device));
+        grhip_detail::check(grhip_framer_sink_1_create(d_h.out(), device));
     }
-    friend grhip_framer_sink_1_sptr grhip_make_framer_sink_1(gr_msg_queue_sptr, int);
 public:
-    ~grhip_framer_sink_1_blk() { grhip_framer_sink_1_destroy(d_h); }
     int work(int n, gr_vector_const_void_star &in, gr_vector_void_star &) override
     {
-        int r = grhip_framer_sink_1_work(d_h, n, (const unsigned char *)in[0]);
-        grhip_detail::check(r);
-        int m = grhip_framer_sink_1_message_count(d_h, nullptr);
-        grhip_detail::check(m);
+        int r = checked(grhip_framer_sink_1_work(d_h, n, (const unsigned char *)in[0]));
+        int m = checked(grhip_framer_sink_1_message_count(d_h, nullptr));
         for (int i = 0; i < m; i++) {
             int woff = 0;
-            int len = grhip_framer_sink_1_pop(d_h, &woff, d_buf.data(), (int)d_buf.size());
-            grhip_detail::check(len);
+            int len = checked(grhip_framer_sink_1_pop(d_h, &woff, d_buf.data(), (int)d_buf.size()));
             gr_message_sptr msg = gr_make_message(0, woff, 0, len);      // .cc:140-141, 168-170
             if (len) memcpy(msg->msg(), d_buf.data(), len);
             d_target_queue->insert_tail(msg);
@@ -451,41 +520,36 @@ public:
         return r;
     }
 };
+typedef boost::shared_ptr<grhip_framer_sink_1_blk> grhip_framer_sink_1_sptr;
 inline grhip_framer_sink_1_sptr grhip_make_framer_sink_1(gr_msg_queue_sptr target_queue, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_framer_sink_1_blk(target_queue, device));
+    return grhip_detail::factory::make<grhip_framer_sink_1_blk>(target_queue, device);
 }
 
-class grhip_correlate_access_code_bb_blk;
-typedef boost::shared_ptr<grhip_correlate_access_code_bb_blk> grhip_correlate_access_code_bb_sptr;
-class grhip_correlate_access_code_bb_blk : public gr_sync_block {
-    grhip_correlate_access_code_bb *d_h = nullptr;
+class grhip_correlate_access_code_bb_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_block, correlate_access_code_bb) {
+    friend struct grhip_detail::factory;
     grhip_correlate_access_code_bb_blk(const std::string &access_code, int threshold, int device)
-        : gr_sync_block("correlate_access_code_bb", gr_make_io_signature(1, 1, sizeof(char)),
-                        gr_make_io_signature(1, 1, sizeof(char)))
+        : block("correlate_access_code_bb", gr_make_io_signature(1, 1, sizeof(char)), gr_make_io_signature(1, 1, sizeof(char)))
     {
         // the reference throws std::out_of_range("access_code is > 64 bits") (.cc:54-57)
-        grhip_detail::check(grhip_correlate_access_code_bb_create(&d_h, access_code.data(), access_code.size(),
+        grhip_detail::check(grhip_correlate_access_code_bb_create(d_h.out(), access_code.data(), access_code.size(),
                                                                   threshold, device));
     }
-    friend grhip_correlate_access_code_bb_sptr grhip_make_correlate_access_code_bb(const std::string &, int, int);
 public:
-    ~grhip_correlate_access_code_bb_blk() { grhip_correlate_access_code_bb_destroy(d_h); }
     bool set_access_code(const std::string &code)             // .cc:64-85: false if longer than 64
     {
         return grhip_correlate_access_code_bb_set_access_code(d_h, code.data(), code.size()) == GRHIP_OK;
     }
     int work(int n, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_correlate_access_code_bb_work(d_h, n, (const unsigned char *)in[0], (unsigned char *)out[0]);
-        grhip_detail::check(r);
-        return r;
+        return checked(grhip_correlate_access_code_bb_work(d_h, n, (const unsigned char *)in[0], (unsigned char *)out[0]));
     }
 };
+typedef boost::shared_ptr<grhip_correlate_access_code_bb_blk> grhip_correlate_access_code_bb_sptr;
 inline grhip_correlate_access_code_bb_sptr grhip_make_correlate_access_code_bb(const std::string &access_code,
                                                                                int threshold, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_correlate_access_code_bb_blk(access_code, threshold, device));
+    return grhip_detail::factory::make<grhip_correlate_access_code_bb_blk>(access_code, threshold, device);
 }
 
 // ---------------------------------------------------------------------------
@@ -493,35 +557,30 @@ inline grhip_correlate_access_code_bb_sptr grhip_make_correlate_access_code_bb(c
 // direction and shift; its set_window() is not virtual and only stores the vector, so work() hands a changed
 // window to the device before it transforms (the FFTW subclass reads d_window in work() too, .cc:68-76).
 // ---------------------------------------------------------------------------
-class gr_fft_vcc_hip;
-typedef boost::shared_ptr<gr_fft_vcc_hip> gr_fft_vcc_hip_sptr;
-class gr_fft_vcc_hip : public gr_fft_vcc {
-    grhip_fft_vcc *d_h = nullptr;
+class gr_fft_vcc_hip : public GRHIP_BLOCK_NO_MODE(gr_fft_vcc, fft_vcc) {
+    friend struct grhip_detail::factory;
     std::vector<float> d_sent;
     gr_fft_vcc_hip(int fft_size, bool forward, const std::vector<float> &window, bool shift, int device)
-        : gr_fft_vcc("fft_vcc_hip", fft_size, forward, window, shift), d_sent(d_window)
+        : block("fft_vcc_hip", fft_size, forward, window, shift), d_sent(d_window)
     {
-        grhip_detail::check(grhip_fft_vcc_create(&d_h, fft_size, forward, d_window.data(), d_window.size(), shift, device));
+        grhip_detail::check(grhip_fft_vcc_create(d_h.out(), fft_size, forward, d_window.data(), d_window.size(), shift, device));
     }
-    friend gr_fft_vcc_hip_sptr gr_make_fft_vcc_hip(int, bool, const std::vector<float> &, bool, int);
 public:
-    ~gr_fft_vcc_hip() { grhip_fft_vcc_destroy(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         if (d_window != d_sent) {
             grhip_detail::check(grhip_fft_vcc_set_window(d_h, d_window.data(), d_window.size()));
             d_sent = d_window;
         }
-        int r = grhip_fft_vcc_work(d_h, noutput_items, in[0], out[0]);
-        grhip_detail::check(r);
-        return r;
+        return checked(grhip_fft_vcc_work(d_h, noutput_items, in[0], out[0]));
     }
 };
+typedef boost::shared_ptr<gr_fft_vcc_hip> gr_fft_vcc_hip_sptr;
 inline gr_fft_vcc_hip_sptr gr_make_fft_vcc_hip(int fft_size, bool forward, const std::vector<float> &window,
                                                bool shift = false, int device = 0)
 {
     if (fft_size <= 0) throw std::out_of_range("gr_fft_vcc_hip: invalid fft_size");      // gri_fft.cc:104-105
-    return gnuradio::get_initial_sptr(new gr_fft_vcc_hip(fft_size, forward, window, shift, device));
+    return grhip_detail::factory::make<gr_fft_vcc_hip>(fft_size, forward, window, shift, device);
 }
 
 // the block-level factory of round 1 keeps its name
@@ -537,122 +596,102 @@ inline grhip_fft_vcc_sptr grhip_make_fft_vcc(int fft_size, bool forward, const s
 // gr_pfb_channelizer_ccf  (numchans inputs, one output of numchans-complex vectors)
 // ---------------------------------------------------------------------------
 // gr_fft_filter_ccc (filter/gr_fft_filter_ccc.h): gr_sync_decimator, history 1, output multiple nsamples
-class grhip_fft_filter_ccc_blk;
-typedef boost::shared_ptr<grhip_fft_filter_ccc_blk> grhip_fft_filter_ccc_sptr;
-class grhip_fft_filter_ccc_blk : public gr_sync_decimator {
-    grhip_fft_filter_ccc *d_h = nullptr;
+class grhip_fft_filter_ccc_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_decimator, fft_filter_ccc) {
+    friend struct grhip_detail::factory;
     grhip_fft_filter_ccc_blk(int decimation, const std::vector<gr_complex> &taps, int device)
-        : gr_sync_decimator("fft_filter_ccc", gr_make_io_signature(1, 1, sizeof(gr_complex)),
-                            gr_make_io_signature(1, 1, sizeof(gr_complex)), decimation)
+        : block("fft_filter_ccc", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                decimation)
     {
-        grhip_detail::check(grhip_fft_filter_ccc_create(&d_h, decimation, (const float *)taps.data(), taps.size(), device));
+        grhip_detail::check(grhip_fft_filter_ccc_create(d_h.out(), decimation, (const float *)taps.data(), taps.size(), device));
         set_history(1);
         set_output_multiple(grhip_fft_filter_ccc_nsamples(d_h));          // gr_fft_filter_ccc.cc:69
     }
-    friend grhip_fft_filter_ccc_sptr grhip_make_fft_filter_ccc(int, const std::vector<gr_complex> &, int);
 public:
-    ~grhip_fft_filter_ccc_blk() { grhip_fft_filter_ccc_destroy(d_h); }
     void set_taps(const std::vector<gr_complex> &taps)
     {
         grhip_detail::check(grhip_fft_filter_ccc_set_taps(d_h, (const float *)taps.data(), taps.size()));
     }
     int work(int n, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_fft_filter_ccc_work(d_h, n, in[0], out[0]);
-        grhip_detail::check(r);
+        int r = checked(grhip_fft_filter_ccc_work(d_h, n, in[0], out[0]));
         if (r == 0) set_output_multiple(grhip_fft_filter_ccc_nsamples(d_h));   // .cc:113-118
         return r;
     }
 };
+typedef boost::shared_ptr<grhip_fft_filter_ccc_blk> grhip_fft_filter_ccc_sptr;
 inline grhip_fft_filter_ccc_sptr grhip_make_fft_filter_ccc(int decimation, const std::vector<gr_complex> &taps, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_fft_filter_ccc_blk(decimation, taps, device));
+    return grhip_detail::factory::make<grhip_fft_filter_ccc_blk>(decimation, taps, device);
 }
 
 // gr_fft_filter_fff (filter/gr_fft_filter_fff.h, .cc:44-97): gr_sync_decimator on floats, history 1, output multiple nsamples
-class grhip_fft_filter_fff_blk;
-typedef boost::shared_ptr<grhip_fft_filter_fff_blk> grhip_fft_filter_fff_sptr;
-class grhip_fft_filter_fff_blk : public gr_sync_decimator {
-    grhip_fft_filter_fff *d_h = nullptr;
+class grhip_fft_filter_fff_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_decimator, fft_filter_fff) {
+    friend struct grhip_detail::factory;
     grhip_fft_filter_fff_blk(int decimation, const std::vector<float> &taps, int device)
-        : gr_sync_decimator("fft_filter_fff", gr_make_io_signature(1, 1, sizeof(float)),
-                            gr_make_io_signature(1, 1, sizeof(float)), decimation)
+        : block("fft_filter_fff", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(float)), decimation)
     {
-        grhip_detail::check(grhip_fft_filter_fff_create(&d_h, decimation, taps.data(), taps.size(), device));
+        grhip_detail::check(grhip_fft_filter_fff_create(d_h.out(), decimation, taps.data(), taps.size(), device));
         set_history(1);                                                       // gr_fft_filter_fff.cc:51
         set_output_multiple(grhip_fft_filter_fff_nsamples(d_h));          // .cc:59-60
     }
-    friend grhip_fft_filter_fff_sptr grhip_make_fft_filter_fff(int, const std::vector<float> &, int);
 public:
-    ~grhip_fft_filter_fff_blk() { grhip_fft_filter_fff_destroy(d_h); }
     void set_taps(const std::vector<float> &taps)                             // .cc:69-73
     {
         grhip_detail::check(grhip_fft_filter_fff_set_taps(d_h, taps.data(), taps.size()));
     }
     int work(int n, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_fft_filter_fff_work(d_h, n, in[0], out[0]);
-        grhip_detail::check(r);
+        int r = checked(grhip_fft_filter_fff_work(d_h, n, in[0], out[0]));
         if (r == 0) set_output_multiple(grhip_fft_filter_fff_nsamples(d_h));   // .cc:83-88
         return r;
     }
 };
+typedef boost::shared_ptr<grhip_fft_filter_fff_blk> grhip_fft_filter_fff_sptr;
 inline grhip_fft_filter_fff_sptr grhip_make_fft_filter_fff(int decimation, const std::vector<float> &taps, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_fft_filter_fff_blk(decimation, taps, device));
+    return grhip_detail::factory::make<grhip_fft_filter_fff_blk>(decimation, taps, device);
 }
 
 // gr_fft_vfc (general/gr_fft_vfc.h, .cc:42-118): gr_sync_block, items of fft_size floats in, fft_size complex out; forward only
-class grhip_fft_vfc_blk;
-typedef boost::shared_ptr<grhip_fft_vfc_blk> grhip_fft_vfc_sptr;
-class grhip_fft_vfc_blk : public gr_sync_block {
-    grhip_fft_vfc *d_h = nullptr;
+class grhip_fft_vfc_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_block, fft_vfc) {
+    friend struct grhip_detail::factory;
     unsigned int d_fft_size;
     grhip_fft_vfc_blk(int fft_size, bool forward, const std::vector<float> &window, int device)
-        : gr_sync_block("fft_vfc", gr_make_io_signature(1, 1, fft_size * sizeof(float)),
-                        gr_make_io_signature(1, 1, fft_size * sizeof(gr_complex))),
+        : block("fft_vfc", gr_make_io_signature(1, 1, fft_size * sizeof(float)),
+                gr_make_io_signature(1, 1, fft_size * sizeof(gr_complex))),
           d_fft_size(fft_size)
     {
         if (!forward) throw std::invalid_argument("fft_vfc: forward must == true");     // .cc:54-57
-        grhip_detail::check(grhip_fft_vfc_create(&d_h, fft_size, forward, window.data(), window.size(), device));
+        grhip_detail::check(grhip_fft_vfc_create(d_h.out(), fft_size, forward, window.data(), window.size(), device));
     }
-    friend grhip_fft_vfc_sptr grhip_make_fft_vfc(int, bool, const std::vector<float> &, int);
 public:
-    ~grhip_fft_vfc_blk() { grhip_fft_vfc_destroy(d_h); }
     bool set_window(const std::vector<float> &window)                         // .cc:109-118
     {
-        int r = grhip_fft_vfc_set_window(d_h, window.data(), window.size());
-        grhip_detail::check(r);
-        return r == 1;
+        return checked(grhip_fft_vfc_set_window(d_h, window.data(), window.size())) == 1;
     }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_fft_vfc_work(d_h, noutput_items, in[0], out[0]);
-        grhip_detail::check(r);
-        return r;
+        return checked(grhip_fft_vfc_work(d_h, noutput_items, in[0], out[0]));
     }
 };
+typedef boost::shared_ptr<grhip_fft_vfc_blk> grhip_fft_vfc_sptr;
 inline grhip_fft_vfc_sptr grhip_make_fft_vfc(int fft_size, bool forward, const std::vector<float> &window, int device = 0)
 {
     if (fft_size <= 0) throw std::out_of_range("fft_vfc: invalid fft_size");            // gri_fft.cc:104-105
-    return gnuradio::get_initial_sptr(new grhip_fft_vfc_blk(fft_size, forward, window, device));
+    return grhip_detail::factory::make<grhip_fft_vfc_blk>(fft_size, forward, window, device);
 }
 
 // gr_pfb_decimator_ccf (filter/gr_pfb_decimator_ccf.h:100-140)
-class grhip_pfb_decimator_ccf_blk;
-typedef boost::shared_ptr<grhip_pfb_decimator_ccf_blk> grhip_pfb_decimator_ccf_sptr;
-class grhip_pfb_decimator_ccf_blk : public gr_sync_block {
-    grhip_pfb_decimator_ccf *d_h = nullptr;
+class grhip_pfb_decimator_ccf_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_block, pfb_decimator_ccf) {
+    friend struct grhip_detail::factory;
     grhip_pfb_decimator_ccf_blk(unsigned decim, const std::vector<float> &taps, unsigned channel, int device)
-        : gr_sync_block("pfb_decimator_ccf", gr_make_io_signature(decim, decim, sizeof(gr_complex)),
-                        gr_make_io_signature(1, 1, sizeof(gr_complex)))
+        : block("pfb_decimator_ccf", gr_make_io_signature(decim, decim, sizeof(gr_complex)),
+                gr_make_io_signature(1, 1, sizeof(gr_complex)))
     {
-        grhip_detail::check(grhip_pfb_decimator_ccf_create(&d_h, decim, taps.data(), taps.size(), channel, device));
+        grhip_detail::check(grhip_pfb_decimator_ccf_create(d_h.out(), decim, taps.data(), taps.size(), channel, device));
         set_history(grhip_pfb_decimator_ccf_history(d_h));           // .cc:108
     }
-    friend grhip_pfb_decimator_ccf_sptr grhip_make_pfb_decimator_ccf(unsigned, const std::vector<float> &, unsigned, int);
 public:
-    ~grhip_pfb_decimator_ccf_blk() { grhip_pfb_decimator_ccf_destroy(d_h); }
     void set_taps(const std::vector<float> &taps)
     {
         grhip_detail::check(grhip_pfb_decimator_ccf_set_taps(d_h, taps.data(), taps.size()));
@@ -660,37 +699,32 @@ public:
     }
     int work(int n, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_pfb_decimator_ccf_work(d_h, n, in.data(), out[0]);
-        grhip_detail::check(r);
-        return r;
+        return checked(grhip_pfb_decimator_ccf_work(d_h, n, in.data(), out[0]));
     }
 };
+typedef boost::shared_ptr<grhip_pfb_decimator_ccf_blk> grhip_pfb_decimator_ccf_sptr;
 inline grhip_pfb_decimator_ccf_sptr grhip_make_pfb_decimator_ccf(unsigned decim, const std::vector<float> &taps,
                                                                  unsigned channel = 0, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_pfb_decimator_ccf_blk(decim, taps, channel, device));
+    return grhip_detail::factory::make<grhip_pfb_decimator_ccf_blk>(decim, taps, channel, device);
 }
 
-class grhip_pfb_channelizer_ccf_blk;
-typedef boost::shared_ptr<grhip_pfb_channelizer_ccf_blk> grhip_pfb_channelizer_ccf_sptr;
-class grhip_pfb_channelizer_ccf_blk : public gr_block {
-    grhip_pfb_channelizer_ccf *d_h = nullptr;
+class grhip_pfb_channelizer_ccf_blk : public GRHIP_BLOCK_NO_MODE(gr_block, pfb_channelizer_ccf) {
+    friend struct grhip_detail::factory;
     unsigned d_numchans;
     grhip_pfb_channelizer_ccf_blk(unsigned numchans, const std::vector<float> &taps, float oversample_rate, int device)
-        : gr_block("pfb_channelizer_ccf", gr_make_io_signature(numchans, numchans, sizeof(gr_complex)),
-                   gr_make_io_signature(1, 1, numchans * sizeof(gr_complex))),
+        : block("pfb_channelizer_ccf", gr_make_io_signature(numchans, numchans, sizeof(gr_complex)),
+                gr_make_io_signature(1, 1, numchans * sizeof(gr_complex))),
           d_numchans(numchans)
     {
         // std::invalid_argument when numchans/oversample_rate is not an integer (.cc:57-60)
-        grhip_detail::check(grhip_pfb_channelizer_ccf_create(&d_h, numchans, taps.data(), taps.size(), oversample_rate,
+        grhip_detail::check(grhip_pfb_channelizer_ccf_create(d_h.out(), numchans, taps.data(), taps.size(), oversample_rate,
                                                              device));
         set_history(grhip_pfb_channelizer_ccf_history(d_h));
         set_relative_rate(1.0 / (numchans / oversample_rate));    // set_relative_rate(1.0/intp), .cc:62
         set_output_multiple(grhip_pfb_channelizer_ccf_output_multiple(d_h));     // gr_pfb_channelizer_ccf.cc:92
     }
-    friend grhip_pfb_channelizer_ccf_sptr grhip_make_pfb_channelizer_ccf(unsigned, const std::vector<float> &, float, int);
 public:
-    ~grhip_pfb_channelizer_ccf_blk() { grhip_pfb_channelizer_ccf_destroy(d_h); }
     void set_taps(const std::vector<float> &taps)
     {
         grhip_detail::check(grhip_pfb_channelizer_ccf_set_taps(d_h, taps.data(), taps.size()));
@@ -699,78 +733,61 @@ public:
     int general_work(int noutput_items, gr_vector_int &, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         int consumed = 0;
-        int r = grhip_pfb_channelizer_ccf_general_work(d_h, noutput_items, in.data(), out[0], &consumed);
-        grhip_detail::check(r);
+        int r = checked(grhip_pfb_channelizer_ccf_general_work(d_h, noutput_items, in.data(), out[0], &consumed));
         consume_each(consumed);
         return r;
     }
 };
+typedef boost::shared_ptr<grhip_pfb_channelizer_ccf_blk> grhip_pfb_channelizer_ccf_sptr;
 inline grhip_pfb_channelizer_ccf_sptr grhip_make_pfb_channelizer_ccf(unsigned numchans, const std::vector<float> &taps,
                                                                      float oversample_rate = 1, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_pfb_channelizer_ccf_blk(numchans, taps, oversample_rate, device));
+    return grhip_detail::factory::make<grhip_pfb_channelizer_ccf_blk>(numchans, taps, oversample_rate, device);
 }
 
 // ---------------------------------------------------------------------------
 // gr_pfb_arb_resampler_ccf / _fff  (a gr_block: general_work + consume_each, gr_block's default forecast)
 // ---------------------------------------------------------------------------
-template <class ITEM, class H, int (*CREATE)(H **, float, const float *, size_t, unsigned, int), void (*DESTROY)(H *),
-          int (*SET_RATE)(H *, float), int (*SET_MODE)(H *, int), int (*HISTORY)(const H *),
-          int (*WORK)(H *, int, int, const void *, void *, int *)>
-class grhip_pfb_arb_resampler_blk : public gr_block {
-    H *d_h = nullptr;
-protected:
-    grhip_pfb_arb_resampler_blk(const char *name, float rate, const std::vector<float> &taps, unsigned filter_size,
-                                int device)
-        : gr_block(name, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM)))
+template <class T, class ITEM>
+class grhip_pfb_arb_resampler_blk : public grhip_detail::block<gr_block, typename T::H, T::destroy, T::set_mode> {
+    friend struct grhip_detail::factory;
+    grhip_pfb_arb_resampler_blk(float rate, const std::vector<float> &taps, unsigned filter_size, int device)
+        : grhip_pfb_arb_resampler_blk::block(T::name, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM)))
     {
-        grhip_detail::check(CREATE(&d_h, rate, taps.data(), taps.size(), filter_size, device));
-        int h = HISTORY(d_h);
-        grhip_detail::check(h);
-        set_history((unsigned)h);                                      // tpf + 1 (.cc:118)
-        set_relative_rate(rate);                                       // set_rate (.h:169)
+        grhip_detail::check(T::create(this->d_h.out(), rate, taps.data(), taps.size(), filter_size, device));
+        this->set_history((unsigned)this->checked(T::history(this->d_h)));         // tpf + 1 (.cc:118)
+        this->set_relative_rate(rate);                                             // set_rate (.h:169)
     }
 public:
-    ~grhip_pfb_arb_resampler_blk() { DESTROY(d_h); }
     void set_rate(float rate)
     {
-        grhip_detail::check(SET_RATE(d_h, rate));
-        set_relative_rate(rate);
+        grhip_detail::check(T::set_rate(this->d_h, rate));
+        this->set_relative_rate(rate);
     }
-    void set_mode(int mode) { grhip_detail::check(SET_MODE(d_h, mode)); }
     int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
                      gr_vector_void_star &out) override
     {
-        int consumed = 0;
-        int r = WORK(d_h, noutput_items, ninput_items[0], in[0], out[0], &consumed);
-        grhip_detail::check(r);
-        consume_each(consumed);
-        return r;
+        return this->work_consumed(T::general_work, noutput_items, ninput_items, in, out);
     }
 };
 
 #define GRHIP_ARB_BLOCK(SUF, ITEM)                                                                                     \
-    class grhip_pfb_arb_resampler_##SUF##_blk;                                                                         \
-    typedef boost::shared_ptr<grhip_pfb_arb_resampler_##SUF##_blk> grhip_pfb_arb_resampler_##SUF##_sptr;               \
-    class grhip_pfb_arb_resampler_##SUF##_blk                                                                          \
-        : public grhip_pfb_arb_resampler_blk<ITEM, grhip_pfb_arb_resampler_##SUF,                                      \
-                                             grhip_pfb_arb_resampler_##SUF##_create,                                   \
-                                             grhip_pfb_arb_resampler_##SUF##_destroy,                                  \
-                                             grhip_pfb_arb_resampler_##SUF##_set_rate,                                 \
-                                             grhip_pfb_arb_resampler_##SUF##_set_mode,                                 \
-                                             grhip_pfb_arb_resampler_##SUF##_history,                                  \
-                                             grhip_pfb_arb_resampler_##SUF##_general_work> {                           \
-        grhip_pfb_arb_resampler_##SUF##_blk(float rate, const std::vector<float> &taps, unsigned filter_size,          \
-                                            int device)                                                               \
-            : grhip_pfb_arb_resampler_blk("pfb_arb_resampler_" #SUF, rate, taps, filter_size, device) {}               \
-        friend grhip_pfb_arb_resampler_##SUF##_sptr grhip_make_pfb_arb_resampler_##SUF(float,                          \
-                                                                                      const std::vector<float> &,      \
-                                                                                      unsigned, int);                  \
+    namespace grhip_detail {                                                                                           \
+    struct pfb_arb_resampler_##SUF##_fns {                                                                             \
+        typedef grhip_pfb_arb_resampler_##SUF H;                                                                       \
+        static constexpr const char *name = "pfb_arb_resampler_" #SUF;                                                 \
+        GRHIP_FN(pfb_arb_resampler_##SUF, create); GRHIP_FN(pfb_arb_resampler_##SUF, destroy);                         \
+        GRHIP_FN(pfb_arb_resampler_##SUF, set_rate); GRHIP_FN(pfb_arb_resampler_##SUF, set_mode);                      \
+        GRHIP_FN(pfb_arb_resampler_##SUF, history); GRHIP_FN(pfb_arb_resampler_##SUF, general_work);                   \
     };                                                                                                                 \
+    }                                                                                                                  \
+    typedef grhip_pfb_arb_resampler_blk<grhip_detail::pfb_arb_resampler_##SUF##_fns, ITEM>                             \
+        grhip_pfb_arb_resampler_##SUF##_blk;                                                                           \
+    typedef boost::shared_ptr<grhip_pfb_arb_resampler_##SUF##_blk> grhip_pfb_arb_resampler_##SUF##_sptr;               \
     inline grhip_pfb_arb_resampler_##SUF##_sptr grhip_make_pfb_arb_resampler_##SUF(                                   \
         float rate, const std::vector<float> &taps, unsigned filter_size = 32, int device = 0)                        \
     {                                                                                                                  \
-        return gnuradio::get_initial_sptr(new grhip_pfb_arb_resampler_##SUF##_blk(rate, taps, filter_size, device));  \
+        return grhip_detail::factory::make<grhip_pfb_arb_resampler_##SUF##_blk>(rate, taps, filter_size, device);     \
     }
 
 GRHIP_ARB_BLOCK(ccf, gr_complex)
@@ -781,51 +798,51 @@ GRHIP_ARB_BLOCK(fff, float)
 // gr_fractional_interpolator_ff / _cc  (a gr_block: general_work + consume_each, its own forecast, relative rate
 // 1 / interp_ratio; filter/gr_fractional_interpolator_ff.h:41-66).  std::out_of_range where the reference throws it.
 // ---------------------------------------------------------------------------
+template <class T, class ITEM>
+class grhip_fractional_interpolator_blk : public grhip_detail::block<gr_block, typename T::H, T::destroy, T::set_mode> {
+    friend struct grhip_detail::factory;
+    grhip_fractional_interpolator_blk(float phase_shift, float interp_ratio, int device)
+        : grhip_fractional_interpolator_blk::block(T::name, gr_make_io_signature(1, 1, sizeof(ITEM)),
+                                                   gr_make_io_signature(1, 1, sizeof(ITEM)))
+    {
+        grhip_detail::check(T::create(this->d_h.out(), phase_shift, interp_ratio, device));
+        this->set_relative_rate(1.0 / interp_ratio);                               // .cc:49
+    }
+public:
+    float mu() const { return T::mu(this->d_h); }
+    float interp_ratio() const { return T::interp_ratio(this->d_h); }
+    void set_mu(float mu) { grhip_detail::check(T::set_mu(this->d_h, mu)); }
+    void set_interp_ratio(float r) { grhip_detail::check(T::set_interp_ratio(this->d_h, r)); }
+    void forecast(int noutput_items, gr_vector_int &ninput_items_required) override
+    {
+        this->forecast_each(T::forecast, noutput_items, ninput_items_required);    // .cc:57-65
+    }
+    int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
+                     gr_vector_void_star &out) override
+    {
+        return this->work_consumed(T::general_work, noutput_items, ninput_items, in, out);
+    }
+};
+
 #define GRHIP_FRAC_BLOCK(SUF, ITEM)                                                                                    \
-    class grhip_fractional_interpolator_##SUF##_blk;                                                                   \
-    typedef boost::shared_ptr<grhip_fractional_interpolator_##SUF##_blk> grhip_fractional_interpolator_##SUF##_sptr;   \
-    class grhip_fractional_interpolator_##SUF##_blk : public gr_block {                                                \
-        grhip_fractional_interpolator_##SUF *d_h = nullptr;                                                            \
-        grhip_fractional_interpolator_##SUF##_blk(float phase_shift, float interp_ratio, int device)                   \
-            : gr_block("fractional_interpolator_" #SUF, gr_make_io_signature(1, 1, sizeof(ITEM)),                      \
-                       gr_make_io_signature(1, 1, sizeof(ITEM)))                                                       \
-        {                                                                                                              \
-            grhip_detail::check(grhip_fractional_interpolator_##SUF##_create(&d_h, phase_shift, interp_ratio, device)); \
-            set_relative_rate(1.0 / interp_ratio);                             /* .cc:49 */                            \
-        }                                                                                                              \
-        friend grhip_fractional_interpolator_##SUF##_sptr grhip_make_fractional_interpolator_##SUF(float, float, int); \
-    public:                                                                                                            \
-        ~grhip_fractional_interpolator_##SUF##_blk() { grhip_fractional_interpolator_##SUF##_destroy(d_h); }           \
-        float mu() const { return grhip_fractional_interpolator_##SUF##_mu(d_h); }                                     \
-        float interp_ratio() const { return grhip_fractional_interpolator_##SUF##_interp_ratio(d_h); }                 \
-        void set_mu(float mu) { grhip_detail::check(grhip_fractional_interpolator_##SUF##_set_mu(d_h, mu)); }          \
-        void set_interp_ratio(float r)                                                                                 \
-        {                                                                                                              \
-            grhip_detail::check(grhip_fractional_interpolator_##SUF##_set_interp_ratio(d_h, r));                       \
-        }                                                                                                              \
-        void set_mode(int mode) { grhip_detail::check(grhip_fractional_interpolator_##SUF##_set_mode(d_h, mode)); }    \
-        void forecast(int noutput_items, gr_vector_int &ninput_items_required) override                               \
-        {                                                                                                              \
-            int n = grhip_fractional_interpolator_##SUF##_forecast(d_h, noutput_items);     /* .cc:57-65 */            \
-            grhip_detail::check(n);                                                                                    \
-            for (size_t i = 0; i < ninput_items_required.size(); i++) ninput_items_required[i] = n;                    \
-        }                                                                                                              \
-        int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,                \
-                         gr_vector_void_star &out) override                                                            \
-        {                                                                                                              \
-            int consumed = 0;                                                                                          \
-            int r = grhip_fractional_interpolator_##SUF##_general_work(d_h, noutput_items, ninput_items[0], in[0],     \
-                                                                       out[0], &consumed);                             \
-            grhip_detail::check(r);                                                                                    \
-            consume_each(consumed);                                                                                    \
-            return r;                                                                                                  \
-        }                                                                                                              \
+    namespace grhip_detail {                                                                                           \
+    struct fractional_interpolator_##SUF##_fns {                                                                       \
+        typedef grhip_fractional_interpolator_##SUF H;                                                                 \
+        static constexpr const char *name = "fractional_interpolator_" #SUF;                                           \
+        GRHIP_FN(fractional_interpolator_##SUF, create); GRHIP_FN(fractional_interpolator_##SUF, destroy);             \
+        GRHIP_FN(fractional_interpolator_##SUF, set_mode); GRHIP_FN(fractional_interpolator_##SUF, mu);                \
+        GRHIP_FN(fractional_interpolator_##SUF, interp_ratio); GRHIP_FN(fractional_interpolator_##SUF, set_mu);        \
+        GRHIP_FN(fractional_interpolator_##SUF, set_interp_ratio); GRHIP_FN(fractional_interpolator_##SUF, forecast);  \
+        GRHIP_FN(fractional_interpolator_##SUF, general_work);                                                         \
     };                                                                                                                 \
+    }                                                                                                                  \
+    typedef grhip_fractional_interpolator_blk<grhip_detail::fractional_interpolator_##SUF##_fns, ITEM>                 \
+        grhip_fractional_interpolator_##SUF##_blk;                                                                     \
+    typedef boost::shared_ptr<grhip_fractional_interpolator_##SUF##_blk> grhip_fractional_interpolator_##SUF##_sptr;   \
     inline grhip_fractional_interpolator_##SUF##_sptr grhip_make_fractional_interpolator_##SUF(                       \
         float phase_shift, float interp_ratio, int device = 0)                                                        \
     {                                                                                                                  \
-        return gnuradio::get_initial_sptr(                                                                             \
-            new grhip_fractional_interpolator_##SUF##_blk(phase_shift, interp_ratio, device));                         \
+        return grhip_detail::factory::make<grhip_fractional_interpolator_##SUF##_blk>(phase_shift, interp_ratio, device); \
     }
 
 GRHIP_FRAC_BLOCK(ff, float)
@@ -837,55 +854,44 @@ GRHIP_FRAC_BLOCK(cc, gr_complex)
 // gr_rational_resampler_base_XXX  (a gr_block: gr_block's history stays 1, the reference's own forecast, relative
 // rate I/D; filter/gr_rational_resampler_base_XXX.h.t)
 // ---------------------------------------------------------------------------
-template <class ITEM, class TAP> class grhip_interp_fir_filter_blk : public gr_sync_interpolator {
-    grhip_interp_fir_filter *d_h = nullptr;
+template <class ITEM, class TAP> class grhip_interp_fir_filter_blk : public GRHIP_BLOCK(gr_sync_interpolator, interp_fir_filter) {
 public:
     grhip_interp_fir_filter_blk(const char *kind, unsigned interpolation, const std::vector<TAP> &taps, int device)
-        : gr_sync_interpolator(std::string("interp_fir_filter_") + kind, gr_make_io_signature(1, 1, sizeof(ITEM)),
-                               gr_make_io_signature(1, 1, sizeof(ITEM)), interpolation)
+        : block(std::string("interp_fir_filter_") + kind, gr_make_io_signature(1, 1, sizeof(ITEM)),
+                gr_make_io_signature(1, 1, sizeof(ITEM)), interpolation)
     {
-        grhip_detail::check(grhip_interp_fir_filter_create(&d_h, kind, interpolation,
+        grhip_detail::check(grhip_interp_fir_filter_create(d_h.out(), kind, interpolation,
                                                            reinterpret_cast<const float *>(taps.data()), taps.size(),
                                                            device));
         sync_history();
     }
-    ~grhip_interp_fir_filter_blk() { grhip_interp_fir_filter_destroy(d_h); }
     void set_taps(const std::vector<TAP> &taps)
     {
         grhip_detail::check(grhip_interp_fir_filter_set_taps(d_h, reinterpret_cast<const float *>(taps.data()),
                                                              taps.size()));
     }
-    void set_mode(int mode) { grhip_detail::check(grhip_interp_fir_filter_set_mode(d_h, mode)); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_interp_fir_filter_work(d_h, noutput_items, in[0], out[0]);
-        grhip_detail::check(r);
+        int r = checked(grhip_interp_fir_filter_work(d_h, noutput_items, in[0], out[0]));
         sync_history();                                                 // install_taps: set_history(nt)
         return r;
     }
 private:
-    void sync_history()
-    {
-        int h = grhip_interp_fir_filter_history(d_h);
-        grhip_detail::check(h);
-        set_history((unsigned)h);
-    }
+    void sync_history() { set_history((unsigned)checked(grhip_interp_fir_filter_history(d_h))); }
 };
 
-template <class ITEM, class TAP> class grhip_rational_resampler_base_blk : public gr_block {
-    grhip_rational_resampler_base *d_h = nullptr;
+template <class ITEM, class TAP> class grhip_rational_resampler_base_blk : public GRHIP_BLOCK(gr_block, rational_resampler_base) {
 public:
     grhip_rational_resampler_base_blk(const char *kind, unsigned interpolation, unsigned decimation,
                                       const std::vector<TAP> &taps, int device)
-        : gr_block(std::string("rational_resampler_base_") + kind, gr_make_io_signature(1, 1, sizeof(ITEM)),
-                   gr_make_io_signature(1, 1, sizeof(ITEM)))
+        : block(std::string("rational_resampler_base_") + kind, gr_make_io_signature(1, 1, sizeof(ITEM)),
+                gr_make_io_signature(1, 1, sizeof(ITEM)))
     {
-        grhip_detail::check(grhip_rational_resampler_base_create(&d_h, kind, interpolation, decimation,
+        grhip_detail::check(grhip_rational_resampler_base_create(d_h.out(), kind, interpolation, decimation,
                                                                  reinterpret_cast<const float *>(taps.data()),
                                                                  taps.size(), device));
         set_relative_rate(1.0 * interpolation / decimation);          // .cc.t:63
     }
-    ~grhip_rational_resampler_base_blk() { grhip_rational_resampler_base_destroy(d_h); }
     unsigned interpolation() const { return (unsigned)grhip_rational_resampler_base_interpolation(d_h); }
     unsigned decimation() const { return (unsigned)grhip_rational_resampler_base_decimation(d_h); }
     // the block's own history (nt), which hides gr_block's: the scheduler keeps seeing 1 (.h.t:51,72-73)
@@ -895,22 +901,14 @@ public:
         grhip_detail::check(grhip_rational_resampler_base_set_taps(d_h, reinterpret_cast<const float *>(taps.data()),
                                                                    taps.size()));
     }
-    void set_mode(int mode) { grhip_detail::check(grhip_rational_resampler_base_set_mode(d_h, mode)); }
     void forecast(int noutput_items, gr_vector_int &req) override
     {
-        int n = grhip_rational_resampler_base_forecast(d_h, noutput_items);
-        grhip_detail::check(n);
-        for (size_t i = 0; i < req.size(); i++) req[i] = n;
+        forecast_each(grhip_rational_resampler_base_forecast, noutput_items, req);
     }
     int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
                      gr_vector_void_star &out) override
     {
-        int consumed = 0;
-        int r = grhip_rational_resampler_base_general_work(d_h, noutput_items, ninput_items[0], in[0], out[0],
-                                                           &consumed);
-        grhip_detail::check(r);
-        consume_each(consumed);
-        return r;
+        return work_consumed(grhip_rational_resampler_base_general_work, noutput_items, ninput_items, in, out);
     }
 };
 
@@ -920,15 +918,15 @@ public:
     inline grhip_interp_fir_filter_##SUF##_sptr grhip_make_interp_fir_filter_##SUF(                                   \
         unsigned interpolation, const std::vector<TAP> &taps, int device = 0)                                         \
     {                                                                                                                  \
-        return gnuradio::get_initial_sptr(new grhip_interp_fir_filter_##SUF(#SUF, interpolation, taps, device));      \
+        return grhip_detail::factory::make<grhip_interp_fir_filter_##SUF>(#SUF, interpolation, taps, device);         \
     }                                                                                                                  \
     typedef grhip_rational_resampler_base_blk<ITEM, TAP> grhip_rational_resampler_base_##SUF;                         \
     typedef boost::shared_ptr<grhip_rational_resampler_base_##SUF> grhip_rational_resampler_base_##SUF##_sptr;        \
     inline grhip_rational_resampler_base_##SUF##_sptr grhip_make_rational_resampler_base_##SUF(                       \
         unsigned interpolation, unsigned decimation, const std::vector<TAP> &taps, int device = 0)                    \
     {                                                                                                                  \
-        return gnuradio::get_initial_sptr(                                                                             \
-            new grhip_rational_resampler_base_##SUF(#SUF, interpolation, decimation, taps, device));                   \
+        return grhip_detail::factory::make<grhip_rational_resampler_base_##SUF>(#SUF, interpolation, decimation,      \
+                                                                                taps, device);                         \
     }
 
 GRHIP_RS_BLOCKS(ccf, gr_complex, float)
@@ -942,86 +940,67 @@ GRHIP_RS_BLOCKS(ccc, gr_complex, gr_complex)
 // filter/gr_pfb_synthesis_filterbank_ccf.h).  set_taps latches; the next work() installs the taps, returns 0 and the
 // history follows (the library's convention, as grhip_interp_fir_filter_XXX).
 // ---------------------------------------------------------------------------
-class grhip_pfb_interpolator_ccf_blk;
-typedef boost::shared_ptr<grhip_pfb_interpolator_ccf_blk> grhip_pfb_interpolator_ccf_sptr;
-class grhip_pfb_interpolator_ccf_blk : public gr_sync_interpolator {
-    grhip_pfb_interpolator_ccf *d_h = nullptr;
+class grhip_pfb_interpolator_ccf_blk : public GRHIP_BLOCK(gr_sync_interpolator, pfb_interpolator_ccf) {
+    friend struct grhip_detail::factory;
     grhip_pfb_interpolator_ccf_blk(unsigned interp, const std::vector<float> &taps, int device)
-        : gr_sync_interpolator("pfb_interpolator_ccf", gr_make_io_signature(1, 1, sizeof(gr_complex)),
-                               gr_make_io_signature(1, 1, sizeof(gr_complex)), interp)
+        : block("pfb_interpolator_ccf", gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                gr_make_io_signature(1, 1, sizeof(gr_complex)), interp)
     {
-        grhip_detail::check(grhip_pfb_interpolator_ccf_create(&d_h, interp, taps.data(), taps.size(), device));
+        grhip_detail::check(grhip_pfb_interpolator_ccf_create(d_h.out(), interp, taps.data(), taps.size(), device));
         sync_history();
     }
-    friend grhip_pfb_interpolator_ccf_sptr grhip_make_pfb_interpolator_ccf(unsigned, const std::vector<float> &, int);
-    void sync_history()
-    {
-        int h = grhip_pfb_interpolator_ccf_history(d_h);
-        grhip_detail::check(h);
-        set_history((unsigned)h);                                       // set_history(d_taps_per_filter), .cc:101
-    }
+    // set_history(d_taps_per_filter), .cc:101
+    void sync_history() { set_history((unsigned)checked(grhip_pfb_interpolator_ccf_history(d_h))); }
 public:
-    ~grhip_pfb_interpolator_ccf_blk() { grhip_pfb_interpolator_ccf_destroy(d_h); }
     void set_taps(const std::vector<float> &taps)
     {
         grhip_detail::check(grhip_pfb_interpolator_ccf_set_taps(d_h, taps.data(), taps.size()));
     }
-    void set_mode(int mode) { grhip_detail::check(grhip_pfb_interpolator_ccf_set_mode(d_h, mode)); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_pfb_interpolator_ccf_work(d_h, noutput_items, in[0], out[0]);
-        grhip_detail::check(r);
+        int r = checked(grhip_pfb_interpolator_ccf_work(d_h, noutput_items, in[0], out[0]));
         sync_history();
         return r;
     }
 };
+typedef boost::shared_ptr<grhip_pfb_interpolator_ccf_blk> grhip_pfb_interpolator_ccf_sptr;
 inline grhip_pfb_interpolator_ccf_sptr grhip_make_pfb_interpolator_ccf(unsigned interp, const std::vector<float> &taps,
                                                                        int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_pfb_interpolator_ccf_blk(interp, taps, device));
+    return grhip_detail::factory::make<grhip_pfb_interpolator_ccf_blk>(interp, taps, device);
 }
 
-class grhip_pfb_synthesis_filterbank_ccf_blk;
-typedef boost::shared_ptr<grhip_pfb_synthesis_filterbank_ccf_blk> grhip_pfb_synthesis_filterbank_ccf_sptr;
-class grhip_pfb_synthesis_filterbank_ccf_blk : public gr_sync_interpolator {
-    grhip_pfb_synthesis_filterbank_ccf *d_h = nullptr;
+class grhip_pfb_synthesis_filterbank_ccf_blk : public GRHIP_BLOCK(gr_sync_interpolator, pfb_synthesis_filterbank_ccf) {
+    friend struct grhip_detail::factory;
     grhip_pfb_synthesis_filterbank_ccf_blk(unsigned numchans, const std::vector<float> &taps, int device)
-        : gr_sync_interpolator("pfb_synthesis_filterbank_ccf", gr_make_io_signature(1, numchans, sizeof(gr_complex)),
-                               gr_make_io_signature(1, 1, sizeof(gr_complex)), numchans)      // .cc:43-46
+        : block("pfb_synthesis_filterbank_ccf", gr_make_io_signature(1, numchans, sizeof(gr_complex)),
+                gr_make_io_signature(1, 1, sizeof(gr_complex)), numchans)                       // .cc:43-46
     {
-        grhip_detail::check(grhip_pfb_synthesis_filterbank_ccf_create(&d_h, numchans, taps.data(), taps.size(), device));
+        grhip_detail::check(grhip_pfb_synthesis_filterbank_ccf_create(d_h.out(), numchans, taps.data(), taps.size(), device));
         sync_history();
     }
-    friend grhip_pfb_synthesis_filterbank_ccf_sptr grhip_make_pfb_synthesis_filterbank_ccf(unsigned,
-                                                                                            const std::vector<float> &, int);
-    void sync_history()
-    {
-        int h = grhip_pfb_synthesis_filterbank_ccf_history(d_h);
-        grhip_detail::check(h);
-        set_history((unsigned)h);                                       // set_history(d_taps_per_filter + 1), .cc:103
-    }
+    // set_history(d_taps_per_filter + 1), .cc:103
+    void sync_history() { set_history((unsigned)checked(grhip_pfb_synthesis_filterbank_ccf_history(d_h))); }
 public:
-    ~grhip_pfb_synthesis_filterbank_ccf_blk() { grhip_pfb_synthesis_filterbank_ccf_destroy(d_h); }
     unsigned taps_per_filter() const { return (unsigned)grhip_pfb_synthesis_filterbank_ccf_taps_per_filter(d_h); }
     void set_taps(const std::vector<float> &taps)
     {
         grhip_detail::check(grhip_pfb_synthesis_filterbank_ccf_set_taps(d_h, taps.data(), taps.size()));
     }
-    void set_mode(int mode) { grhip_detail::check(grhip_pfb_synthesis_filterbank_ccf_set_mode(d_h, mode)); }
     // the connected inputs are the streams (numsigs = input_items.size(), .cc:129)
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_pfb_synthesis_filterbank_ccf_work(d_h, noutput_items, in.data(), (int)in.size(), out[0]);
-        grhip_detail::check(r);
+        int r = checked(grhip_pfb_synthesis_filterbank_ccf_work(d_h, noutput_items, in.data(), (int)in.size(), out[0]));
         sync_history();
         return r;
     }
 };
+typedef boost::shared_ptr<grhip_pfb_synthesis_filterbank_ccf_blk> grhip_pfb_synthesis_filterbank_ccf_sptr;
 inline grhip_pfb_synthesis_filterbank_ccf_sptr grhip_make_pfb_synthesis_filterbank_ccf(unsigned numchans,
                                                                                        const std::vector<float> &taps,
                                                                                        int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_pfb_synthesis_filterbank_ccf_blk(numchans, taps, device));
+    return grhip_detail::factory::make<grhip_pfb_synthesis_filterbank_ccf_blk>(numchans, taps, device);
 }
 
 // ---------------------------------------------------------------------------
@@ -1029,20 +1008,15 @@ inline grhip_pfb_synthesis_filterbank_ccf_sptr grhip_make_pfb_synthesis_filterba
 // gr_filter_delay_fc(taps)  (gr_sync_block, 1 or 2 float inputs -> complex, history ntaps; filter/gr_filter_delay_fc.cc:38-46)
 // gr_goertzel_fc(rate, len, freq)  (gr_sync_decimator by len, float -> complex; filter/gr_goertzel_fc.cc:38-50)
 // ---------------------------------------------------------------------------
-class grhip_hilbert_fc_blk;
-typedef boost::shared_ptr<grhip_hilbert_fc_blk> grhip_hilbert_fc_sptr;
-class grhip_hilbert_fc_blk : public gr_sync_block {
-    grhip_hilbert_fc *d_h = nullptr;
+class grhip_hilbert_fc_blk : public GRHIP_BLOCK(gr_sync_block, hilbert_fc) {
+    friend struct grhip_detail::factory;
     grhip_hilbert_fc_blk(unsigned ntaps, int device)
-        : gr_sync_block("hilbert_fc", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(gr_complex)))
+        : block("hilbert_fc", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(gr_complex)))
     {
-        grhip_detail::check(grhip_hilbert_fc_create(&d_h, ntaps, device));
+        grhip_detail::check(grhip_hilbert_fc_create(d_h.out(), ntaps, device));
         set_history((unsigned)grhip_hilbert_fc_history(d_h));           // set_history(d_ntaps), .cc:49
     }
-    friend grhip_hilbert_fc_sptr grhip_make_hilbert_fc(unsigned, int);
 public:
-    ~grhip_hilbert_fc_blk() { grhip_hilbert_fc_destroy(d_h); }
-    void set_mode(int mode) { grhip_detail::check(grhip_hilbert_fc_set_mode(d_h, mode)); }
     std::vector<float> taps() const
     {
         std::vector<float> t((size_t)grhip_hilbert_fc_ntaps(d_h));
@@ -1051,70 +1025,56 @@ public:
     }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_hilbert_fc_work(d_h, noutput_items, in[0], out[0]);
-        grhip_detail::check(r);
-        return r;
+        return checked(grhip_hilbert_fc_work(d_h, noutput_items, in[0], out[0]));
     }
 };
+typedef boost::shared_ptr<grhip_hilbert_fc_blk> grhip_hilbert_fc_sptr;
 inline grhip_hilbert_fc_sptr grhip_make_hilbert_fc(unsigned ntaps, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_hilbert_fc_blk(ntaps, device));
+    return grhip_detail::factory::make<grhip_hilbert_fc_blk>(ntaps, device);
 }
 
-class grhip_filter_delay_fc_blk;
-typedef boost::shared_ptr<grhip_filter_delay_fc_blk> grhip_filter_delay_fc_sptr;
-class grhip_filter_delay_fc_blk : public gr_sync_block {
-    grhip_filter_delay_fc *d_h = nullptr;
+class grhip_filter_delay_fc_blk : public GRHIP_BLOCK(gr_sync_block, filter_delay_fc) {
+    friend struct grhip_detail::factory;
     grhip_filter_delay_fc_blk(const std::vector<float> &taps, int device)
-        : gr_sync_block("filter_delay_fc", gr_make_io_signature(1, 2, sizeof(float)),
-                        gr_make_io_signature(1, 1, sizeof(gr_complex)))
+        : block("filter_delay_fc", gr_make_io_signature(1, 2, sizeof(float)), gr_make_io_signature(1, 1, sizeof(gr_complex)))
     {
-        grhip_detail::check(grhip_filter_delay_fc_create(&d_h, taps.data(), taps.size(), device));
+        grhip_detail::check(grhip_filter_delay_fc_create(d_h.out(), taps.data(), taps.size(), device));
         set_history((unsigned)grhip_filter_delay_fc_history(d_h));      // set_history(d_fir->ntaps()), .cc:45
     }
-    friend grhip_filter_delay_fc_sptr grhip_make_filter_delay_fc(const std::vector<float> &, int);
 public:
-    ~grhip_filter_delay_fc_blk() { grhip_filter_delay_fc_destroy(d_h); }
-    void set_mode(int mode) { grhip_detail::check(grhip_filter_delay_fc_set_mode(d_h, mode)); }
     // the connected inputs decide the form (input_items.size(), .cc:61)
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_filter_delay_fc_work(d_h, noutput_items, in[0], in.size() > 1 ? in[1] : nullptr, out[0]);
-        grhip_detail::check(r);
-        return r;
+        return checked(grhip_filter_delay_fc_work(d_h, noutput_items, in[0], in.size() > 1 ? in[1] : nullptr, out[0]));
     }
 };
+typedef boost::shared_ptr<grhip_filter_delay_fc_blk> grhip_filter_delay_fc_sptr;
 inline grhip_filter_delay_fc_sptr grhip_make_filter_delay_fc(const std::vector<float> &taps, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_filter_delay_fc_blk(taps, device));
+    return grhip_detail::factory::make<grhip_filter_delay_fc_blk>(taps, device);
 }
 
-class grhip_goertzel_fc_blk;
-typedef boost::shared_ptr<grhip_goertzel_fc_blk> grhip_goertzel_fc_sptr;
-class grhip_goertzel_fc_blk : public gr_sync_decimator {
-    grhip_goertzel_fc *d_h = nullptr;
+class grhip_goertzel_fc_blk : public GRHIP_BLOCK(gr_sync_decimator, goertzel_fc) {
+    friend struct grhip_detail::factory;
     grhip_goertzel_fc_blk(int rate, int len, float freq, int device)
-        : gr_sync_decimator("goertzel_fc", gr_make_io_signature(1, 1, sizeof(float)),
-                            gr_make_io_signature(1, 1, sizeof(gr_complex)), len < 1 ? 1 : len)
+        : block("goertzel_fc", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                len < 1 ? 1 : len)
     {
-        grhip_detail::check(grhip_goertzel_fc_create(&d_h, rate, len, freq, device));
+        grhip_detail::check(grhip_goertzel_fc_create(d_h.out(), rate, len, freq, device));
     }
-    friend grhip_goertzel_fc_sptr grhip_make_goertzel_fc(int, int, float, int);
 public:
-    ~grhip_goertzel_fc_blk() { grhip_goertzel_fc_destroy(d_h); }
     void set_freq(float freq) { grhip_detail::check(grhip_goertzel_fc_set_freq(d_h, freq)); }
     void set_rate(int rate) { grhip_detail::check(grhip_goertzel_fc_set_rate(d_h, rate)); }
-    void set_mode(int mode) { grhip_detail::check(grhip_goertzel_fc_set_mode(d_h, mode)); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_goertzel_fc_work(d_h, noutput_items, in[0], out[0]);
-        grhip_detail::check(r);
-        return r;
+        return checked(grhip_goertzel_fc_work(d_h, noutput_items, in[0], out[0]));
     }
 };
+typedef boost::shared_ptr<grhip_goertzel_fc_blk> grhip_goertzel_fc_sptr;
 inline grhip_goertzel_fc_sptr grhip_make_goertzel_fc(int rate, int len, float freq, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_goertzel_fc_blk(rate, len, freq, device));
+    return grhip_detail::factory::make<grhip_goertzel_fc_blk>(rate, len, freq, device);
 }
 
 // ---------------------------------------------------------------------------
@@ -1123,30 +1083,24 @@ inline grhip_goertzel_fc_sptr grhip_make_goertzel_fc(int rate, int len, float fr
 // gr_integrate_XX (decim)  (gr_sync_decimator by decim; gengen/gr_integrate_XX.cc.t:38-46)
 // ---------------------------------------------------------------------------
 #define GRHIP_DC_BLOCKER_BLK(SFX, ITEM)                                                                                \
-    class grhip_dc_blocker_##SFX##_blk;                                                                                \
-    typedef boost::shared_ptr<grhip_dc_blocker_##SFX##_blk> grhip_dc_blocker_##SFX##_sptr;                             \
-    class grhip_dc_blocker_##SFX##_blk : public gr_sync_block {                                                        \
-        grhip_dc_blocker_##SFX *d_h = nullptr;                                                                         \
+    class grhip_dc_blocker_##SFX##_blk : public GRHIP_BLOCK(gr_sync_block, dc_blocker_##SFX) {                         \
+        friend struct grhip_detail::factory;                                                                           \
         grhip_dc_blocker_##SFX##_blk(int D, bool long_form, int device)                                                \
-            : gr_sync_block("dc_blocker_" #SFX, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM))) \
+            : block("dc_blocker_" #SFX, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM))) \
         {                                                                                                              \
-            grhip_detail::check(grhip_dc_blocker_##SFX##_create(&d_h, D, long_form ? 1 : 0, device));                  \
+            grhip_detail::check(grhip_dc_blocker_##SFX##_create(d_h.out(), D, long_form ? 1 : 0, device));             \
         }                                                                                                              \
-        friend grhip_dc_blocker_##SFX##_sptr grhip_make_dc_blocker_##SFX(int, bool, int);                              \
     public:                                                                                                            \
-        ~grhip_dc_blocker_##SFX##_blk() { grhip_dc_blocker_##SFX##_destroy(d_h); }                                     \
         int get_group_delay() { return grhip_dc_blocker_##SFX##_group_delay(d_h); }                                    \
-        void set_mode(int mode) { grhip_detail::check(grhip_dc_blocker_##SFX##_set_mode(d_h, mode)); }                 \
         int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override                  \
         {                                                                                                              \
-            int r = grhip_dc_blocker_##SFX##_work(d_h, noutput_items, in[0], out[0]);                                  \
-            grhip_detail::check(r);                                                                                    \
-            return r;                                                                                                  \
+            return checked(grhip_dc_blocker_##SFX##_work(d_h, noutput_items, in[0], out[0]));                          \
         }                                                                                                              \
     };                                                                                                                 \
+    typedef boost::shared_ptr<grhip_dc_blocker_##SFX##_blk> grhip_dc_blocker_##SFX##_sptr;                             \
     inline grhip_dc_blocker_##SFX##_sptr grhip_make_dc_blocker_##SFX(int D = 32, bool long_form = true, int device = 0) \
     {                                                                                                                  \
-        return gnuradio::get_initial_sptr(new grhip_dc_blocker_##SFX##_blk(D, long_form, device));                     \
+        return grhip_detail::factory::make<grhip_dc_blocker_##SFX##_blk>(D, long_form, device);                        \
     }
 GRHIP_DC_BLOCKER_BLK(ff, float)
 GRHIP_DC_BLOCKER_BLK(cc, gr_complex)
@@ -1163,33 +1117,38 @@ inline int ma_set(grhip_moving_average_ss *h, int n, short s) { return grhip_mov
 inline int ma_set(grhip_moving_average_ii *h, int n, int s) { return grhip_moving_average_ii_set_length_and_scale(h, n, s); }
 }  // namespace grhip_detail
 
+// work re-reads the history after the call: a latched set_length_and_scale has taken effect by then (.cc.t:72)
+template <class H, void (*DESTROY)(H *), int (*SET_MODE)(H *, int), auto HISTORY, auto WORK, class ITEM>
+class grhip_moving_average_blk : public grhip_detail::block<gr_sync_block, H, DESTROY, SET_MODE> {
+protected:
+    grhip_moving_average_blk(const char *name, int length, ITEM scale, int max_iter, int device)
+        : grhip_moving_average_blk::block(name, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM)))
+    {
+        grhip_detail::check(grhip_detail::ma_create(this->d_h.out(), length, scale, max_iter, device));
+        this->set_history((unsigned)length);                                        // .cc.t:49
+    }
+public:
+    void set_length_and_scale(int length, ITEM scale) { grhip_detail::check(grhip_detail::ma_set(this->d_h, length, scale)); }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        int r = this->checked(WORK(this->d_h, noutput_items, in[0], out[0]));
+        this->set_history((unsigned)HISTORY(this->d_h));
+        return r;
+    }
+};
 #define GRHIP_MOVING_AVERAGE_BLK(SFX, ITEM)                                                                            \
-    class grhip_moving_average_##SFX##_blk;                                                                            \
-    typedef boost::shared_ptr<grhip_moving_average_##SFX##_blk> grhip_moving_average_##SFX##_sptr;                     \
-    class grhip_moving_average_##SFX##_blk : public gr_sync_block {                                                    \
-        grhip_moving_average_##SFX *d_h = nullptr;                                                                     \
+    class grhip_moving_average_##SFX##_blk                                                                             \
+        : public grhip_moving_average_blk<grhip_moving_average_##SFX, grhip_moving_average_##SFX##_destroy,            \
+                                          grhip_moving_average_##SFX##_set_mode, grhip_moving_average_##SFX##_history, \
+                                          grhip_moving_average_##SFX##_work, ITEM> {                                   \
+        friend struct grhip_detail::factory;                                                                           \
         grhip_moving_average_##SFX##_blk(int length, ITEM scale, int max_iter, int device)                             \
-            : gr_sync_block("moving_average_" #SFX, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM))) \
-        {                                                                                                              \
-            grhip_detail::check(grhip_detail::ma_create(&d_h, length, scale, max_iter, device));                       \
-            set_history((unsigned)length);                                          /* .cc.t:49 */                     \
-        }                                                                                                              \
-        friend grhip_moving_average_##SFX##_sptr grhip_make_moving_average_##SFX(int, ITEM, int, int);                 \
-    public:                                                                                                            \
-        ~grhip_moving_average_##SFX##_blk() { grhip_moving_average_##SFX##_destroy(d_h); }                             \
-        void set_length_and_scale(int length, ITEM scale) { grhip_detail::check(grhip_detail::ma_set(d_h, length, scale)); } \
-        void set_mode(int mode) { grhip_detail::check(grhip_moving_average_##SFX##_set_mode(d_h, mode)); }             \
-        int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override                  \
-        {                                                                                                              \
-            int r = grhip_moving_average_##SFX##_work(d_h, noutput_items, in[0], out[0]);                              \
-            grhip_detail::check(r);                                                                                    \
-            set_history((unsigned)grhip_moving_average_##SFX##_history(d_h));       /* .cc.t:72: after a latched update */ \
-            return r;                                                                                                  \
-        }                                                                                                              \
+            : grhip_moving_average_blk("moving_average_" #SFX, length, scale, max_iter, device) {}                     \
     };                                                                                                                 \
+    typedef boost::shared_ptr<grhip_moving_average_##SFX##_blk> grhip_moving_average_##SFX##_sptr;                     \
     inline grhip_moving_average_##SFX##_sptr grhip_make_moving_average_##SFX(int length, ITEM scale, int max_iter = 4096, int device = 0) \
     {                                                                                                                  \
-        return gnuradio::get_initial_sptr(new grhip_moving_average_##SFX##_blk(length, scale, max_iter, device));      \
+        return grhip_detail::factory::make<grhip_moving_average_##SFX##_blk>(length, scale, max_iter, device);         \
     }
 GRHIP_MOVING_AVERAGE_BLK(ff, float)
 GRHIP_MOVING_AVERAGE_BLK(cc, gr_complex)
@@ -1198,30 +1157,24 @@ GRHIP_MOVING_AVERAGE_BLK(ii, int)
 #undef GRHIP_MOVING_AVERAGE_BLK
 
 #define GRHIP_INTEGRATE_BLK(SFX, ITEM)                                                                                 \
-    class grhip_integrate_##SFX##_blk;                                                                                 \
-    typedef boost::shared_ptr<grhip_integrate_##SFX##_blk> grhip_integrate_##SFX##_sptr;                               \
-    class grhip_integrate_##SFX##_blk : public gr_sync_decimator {                                                     \
-        grhip_integrate_##SFX *d_h = nullptr;                                                                          \
+    class grhip_integrate_##SFX##_blk : public GRHIP_BLOCK(gr_sync_decimator, integrate_##SFX) {                       \
+        friend struct grhip_detail::factory;                                                                           \
         grhip_integrate_##SFX##_blk(int decim, int device)                                                             \
-            : gr_sync_decimator("integrate_" #SFX, gr_make_io_signature(1, 1, sizeof(ITEM)),                           \
-                                gr_make_io_signature(1, 1, sizeof(ITEM)), decim < 1 ? 1 : decim)                       \
+            : block("integrate_" #SFX, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM)), \
+                    decim < 1 ? 1 : decim)                                                                             \
         {                                                                                                              \
-            grhip_detail::check(grhip_integrate_##SFX##_create(&d_h, decim, device));                                  \
+            grhip_detail::check(grhip_integrate_##SFX##_create(d_h.out(), decim, device));                             \
         }                                                                                                              \
-        friend grhip_integrate_##SFX##_sptr grhip_make_integrate_##SFX(int, int);                                      \
     public:                                                                                                            \
-        ~grhip_integrate_##SFX##_blk() { grhip_integrate_##SFX##_destroy(d_h); }                                       \
-        void set_mode(int mode) { grhip_detail::check(grhip_integrate_##SFX##_set_mode(d_h, mode)); }                  \
         int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override                  \
         {                                                                                                              \
-            int r = grhip_integrate_##SFX##_work(d_h, noutput_items, in[0], out[0]);                                   \
-            grhip_detail::check(r);                                                                                    \
-            return r;                                                                                                  \
+            return checked(grhip_integrate_##SFX##_work(d_h, noutput_items, in[0], out[0]));                           \
         }                                                                                                              \
     };                                                                                                                 \
+    typedef boost::shared_ptr<grhip_integrate_##SFX##_blk> grhip_integrate_##SFX##_sptr;                               \
     inline grhip_integrate_##SFX##_sptr grhip_make_integrate_##SFX(int decim, int device = 0)                          \
     {                                                                                                                  \
-        return gnuradio::get_initial_sptr(new grhip_integrate_##SFX##_blk(decim, device));                             \
+        return grhip_detail::factory::make<grhip_integrate_##SFX##_blk>(decim, device);                                \
     }
 GRHIP_INTEGRATE_BLK(ff, float)
 GRHIP_INTEGRATE_BLK(cc, gr_complex)
@@ -1235,70 +1188,57 @@ GRHIP_INTEGRATE_BLK(ii, int)
 // general/gr_nlog10_ff.cc:31-64).  gr_keep_one_in_n (item_size, n): gr_block, general_work
 // (general/gr_keep_one_in_n.cc:31-105).
 // ---------------------------------------------------------------------------
-#define GRHIP_SPECTRUM_BLK(NAME, IN_T, CTOR_ARGS, CTOR_DECL, CREATE_ARGS, EXTRA)                                       \
-    class grhip_##NAME##_blk;                                                                                          \
-    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                 \
-    class grhip_##NAME##_blk : public gr_sync_block {                                                                  \
-        grhip_##NAME *d_h = nullptr;                                                                                   \
+#define GRHIP_SPECTRUM_BLK(NAME, IN_T, CTOR_DECL, CREATE_ARGS, EXTRA)                                                  \
+    class grhip_##NAME##_blk : public GRHIP_BLOCK(gr_sync_block, NAME) {                                               \
+        friend struct grhip_detail::factory;                                                                           \
         grhip_##NAME##_blk CTOR_DECL                                                                                   \
-            : gr_sync_block(#NAME, gr_make_io_signature(1, 1, sizeof(IN_T) * (vlen ? vlen : 1)),                       \
-                            gr_make_io_signature(1, 1, sizeof(float) * (vlen ? vlen : 1)))                             \
+            : block(#NAME, gr_make_io_signature(1, 1, sizeof(IN_T) * (vlen ? vlen : 1)),                               \
+                    gr_make_io_signature(1, 1, sizeof(float) * (vlen ? vlen : 1)))                                     \
         {                                                                                                              \
             grhip_detail::check(grhip_##NAME##_create CREATE_ARGS);                                                    \
         }                                                                                                              \
-        friend grhip_##NAME##_sptr gr_make_##NAME CTOR_ARGS;                                                           \
     public:                                                                                                            \
-        ~grhip_##NAME##_blk() { grhip_##NAME##_destroy(d_h); }                                                         \
-        void set_mode(int mode) { grhip_detail::check(grhip_##NAME##_set_mode(d_h, mode)); }                           \
         EXTRA                                                                                                          \
         int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override                  \
         {                                                                                                              \
-            int r = grhip_##NAME##_work(d_h, noutput_items, in[0], out[0]);                                            \
-            grhip_detail::check(r);                                                                                    \
-            return r;                                                                                                  \
+            return checked(grhip_##NAME##_work(d_h, noutput_items, in[0], out[0]));                                    \
         }                                                                                                              \
-    };
-GRHIP_SPECTRUM_BLK(complex_to_mag_squared, gr_complex, (unsigned int, int), (unsigned int vlen, int device),
-                   (&d_h, (int)vlen, device), )
+    };                                                                                                                 \
+    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;
+GRHIP_SPECTRUM_BLK(complex_to_mag_squared, gr_complex, (unsigned int vlen, int device), (d_h.out(), (int)vlen, device), )
 inline grhip_complex_to_mag_squared_sptr gr_make_complex_to_mag_squared(unsigned int vlen = 1, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_complex_to_mag_squared_blk(vlen, device));
+    return grhip_detail::factory::make<grhip_complex_to_mag_squared_blk>(vlen, device);
 }
 // gr_complex_to_mag (vlen = 1): general/gr_complex_to_xxx.cc:143-171
-GRHIP_SPECTRUM_BLK(complex_to_mag, gr_complex, (unsigned int, int), (unsigned int vlen, int device), (&d_h, (int)vlen, device), )
+GRHIP_SPECTRUM_BLK(complex_to_mag, gr_complex, (unsigned int vlen, int device), (d_h.out(), (int)vlen, device), )
 inline grhip_complex_to_mag_sptr gr_make_complex_to_mag(unsigned int vlen = 1, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_complex_to_mag_blk(vlen, device));
+    return grhip_detail::factory::make<grhip_complex_to_mag_blk>(vlen, device);
 }
-GRHIP_SPECTRUM_BLK(single_pole_iir_filter_ff, float, (double, unsigned int, int), (double alpha, unsigned int vlen, int device),
-                   (&d_h, alpha, (int)vlen, device),
+GRHIP_SPECTRUM_BLK(single_pole_iir_filter_ff, float, (double alpha, unsigned int vlen, int device), (d_h.out(), alpha, (int)vlen, device),
                    void set_taps(double alpha) { grhip_detail::check(grhip_single_pole_iir_filter_ff_set_taps(d_h, alpha)); })
 inline grhip_single_pole_iir_filter_ff_sptr gr_make_single_pole_iir_filter_ff(double alpha, unsigned int vlen = 1, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_single_pole_iir_filter_ff_blk(alpha, vlen, device));
+    return grhip_detail::factory::make<grhip_single_pole_iir_filter_ff_blk>(alpha, vlen, device);
 }
-GRHIP_SPECTRUM_BLK(nlog10_ff, float, (float, unsigned, float, int), (float n, unsigned vlen, float k, int device),
-                   (&d_h, n, (int)vlen, k, device), )
+GRHIP_SPECTRUM_BLK(nlog10_ff, float, (float n, unsigned vlen, float k, int device), (d_h.out(), n, (int)vlen, k, device), )
 inline grhip_nlog10_ff_sptr gr_make_nlog10_ff(float n, unsigned vlen = 1, float k = 0, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_nlog10_ff_blk(n, vlen, k, device));
+    return grhip_detail::factory::make<grhip_nlog10_ff_blk>(n, vlen, k, device);
 }
 #undef GRHIP_SPECTRUM_BLK
 
-class grhip_keep_one_in_n_blk;
-typedef boost::shared_ptr<grhip_keep_one_in_n_blk> grhip_keep_one_in_n_sptr;
-class grhip_keep_one_in_n_blk : public gr_block {
-    grhip_keep_one_in_n *d_h = nullptr;
+class grhip_keep_one_in_n_blk : public GRHIP_BLOCK_NO_MODE(gr_block, keep_one_in_n) {
+    friend struct grhip_detail::factory;
     int d_n = 1;
     grhip_keep_one_in_n_blk(size_t item_size, int n, int device)
-        : gr_block("keep_one_in_n", gr_make_io_signature(1, 1, (int)item_size), gr_make_io_signature(1, 1, (int)item_size))
+        : block("keep_one_in_n", gr_make_io_signature(1, 1, (int)item_size), gr_make_io_signature(1, 1, (int)item_size))
     {
-        grhip_detail::check(grhip_keep_one_in_n_create(&d_h, item_size, n, device));
+        grhip_detail::check(grhip_keep_one_in_n_create(d_h.out(), item_size, n, device));
         set_n(n);
     }
-    friend grhip_keep_one_in_n_sptr gr_make_keep_one_in_n(size_t, int, int);
 public:
-    ~grhip_keep_one_in_n_blk() { grhip_keep_one_in_n_destroy(d_h); }
     void set_n(int n)
     {
         d_n = n < 1 ? 1 : n;
@@ -1310,20 +1250,16 @@ public:
     int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
                      gr_vector_void_star &out) override
     {
-        int ni = ninput_items[0];
-        while (ni > 0 && grhip_keep_one_in_n_produced(d_h, ni) > noutput_items) {
-            const int over = grhip_keep_one_in_n_produced(d_h, ni) - noutput_items;
-            ni -= over > 1 ? (over - 1) * d_n : 1;
-        }
-        int r = ni > 0 ? grhip_keep_one_in_n_work(d_h, ni, in[0], out[0]) : 0;
-        grhip_detail::check(r);
+        const int ni = grhip_detail::cut_to_output(d_h.get(), grhip_keep_one_in_n_produced, ninput_items[0], noutput_items, d_n);
+        int r = checked(ni > 0 ? grhip_keep_one_in_n_work(d_h, ni, in[0], out[0]) : 0);
         consume_each(ni > 0 ? ni : 0);
         return r;
     }
 };
+typedef boost::shared_ptr<grhip_keep_one_in_n_blk> grhip_keep_one_in_n_sptr;
 inline grhip_keep_one_in_n_sptr gr_make_keep_one_in_n(size_t item_size, int n, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_keep_one_in_n_blk(item_size, n, device));
+    return grhip_detail::factory::make<grhip_keep_one_in_n_blk>(item_size, n, device);
 }
 
 // ---------------------------------------------------------------------------
@@ -1333,64 +1269,80 @@ inline grhip_keep_one_in_n_sptr gr_make_keep_one_in_n(size_t item_size, int n, i
 // setter and getter names; `win` is what the reference's window function returns for fft_size (doubles; empty: the
 // default, window.blackmanharris).
 // ---------------------------------------------------------------------------
+template <class T, class IN_T>
+class grhip_logpwrfft_blk : public grhip_detail::block<gr_block, typename T::H, T::destroy, T::set_mode> {
+    friend struct grhip_detail::factory;
+    int d_fft_size;
+    grhip_logpwrfft_blk(double sample_rate, int fft_size, double ref_scale, double frame_rate, double avg_alpha, bool average,
+                        const std::vector<double> &win, int device)
+        : grhip_logpwrfft_blk::block(T::name, gr_make_io_signature(1, 1, sizeof(IN_T)),
+                                     gr_make_io_signature(1, 1, sizeof(float) * (fft_size > 0 ? fft_size : 1))),
+          d_fft_size(fft_size)
+    {
+        grhip_detail::check(T::create(this->d_h.out(), sample_rate, fft_size, ref_scale, frame_rate, avg_alpha, average, win.data(),
+                                      win.size(), device));
+        update_rate();
+    }
+    void update_rate() { this->set_relative_rate(1.0 / ((double)d_fft_size * decimation())); }
+public:
+    void set_decimation(double decim)
+    {
+        grhip_detail::check(T::set_decimation(this->d_h, decim));
+        update_rate();
+    }
+    void set_vec_rate(double r)
+    {
+        grhip_detail::check(T::set_vec_rate(this->d_h, r));
+        update_rate();
+    }
+    void set_sample_rate(double r)
+    {
+        grhip_detail::check(T::set_sample_rate(this->d_h, r));
+        update_rate();
+    }
+    void set_average(bool average) { grhip_detail::check(T::set_average(this->d_h, average)); }
+    void set_avg_alpha(double a) { grhip_detail::check(T::set_avg_alpha(this->d_h, a)); }
+    double sample_rate() const { return T::sample_rate(this->d_h); }
+    int decimation() const { return T::decimation(this->d_h); }
+    double frame_rate() const { return T::frame_rate(this->d_h); }
+    bool average() const { return T::average(this->d_h) != 0; }
+    double avg_alpha() const { return T::avg_alpha(this->d_h); }
+    // one whole frame per output at least (stream_to_vector is a decimator by fft_size)
+    void forecast(int noutput_items, gr_vector_int &req) override
+    {
+        for (size_t i = 0; i < req.size(); i++) req[i] = noutput_items * d_fft_size;
+    }
+    // as many whole frames as there are, cut so that no more than noutput_items come out (gr_keep_one_in_n.cc:80)
+    int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
+                     gr_vector_void_star &out) override
+    {
+        const int n = decimation();
+        const int nf = grhip_detail::cut_to_output(this->d_h.get(), T::produced, ninput_items[0] / d_fft_size, noutput_items, n);
+        int r = this->checked(nf > 0 ? T::work(this->d_h, nf, in[0], out[0]) : 0);
+        this->consume_each(nf > 0 ? nf * d_fft_size : 0);
+        return r;
+    }
+};
 #define GRHIP_LOGPWRFFT_BLK(NAME, IN_T)                                                                                \
-    class grhip_##NAME##_blk;                                                                                          \
-    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                 \
-    class grhip_##NAME##_blk : public gr_block {                                                                       \
-        grhip_##NAME *d_h = nullptr;                                                                                   \
-        int d_fft_size;                                                                                                \
-        grhip_##NAME##_blk(double sample_rate, int fft_size, double ref_scale, double frame_rate, double avg_alpha,    \
-                           bool average, const std::vector<double> &win, int device)                                   \
-            : gr_block(#NAME, gr_make_io_signature(1, 1, sizeof(IN_T)),                                                \
-                       gr_make_io_signature(1, 1, sizeof(float) * (fft_size > 0 ? fft_size : 1))),                     \
-              d_fft_size(fft_size)                                                                                     \
-        {                                                                                                              \
-            grhip_detail::check(grhip_##NAME##_create(&d_h, sample_rate, fft_size, ref_scale, frame_rate, avg_alpha,   \
-                                                      average, win.data(), win.size(), device));                       \
-            update_rate();                                                                                             \
-        }                                                                                                              \
-        void update_rate() { set_relative_rate(1.0 / ((double)d_fft_size * decimation())); }                           \
-        friend grhip_##NAME##_sptr gr_make_##NAME(double, int, double, double, double, bool, const std::vector<double> &, int); \
-    public:                                                                                                            \
-        ~grhip_##NAME##_blk() { grhip_##NAME##_destroy(d_h); }                                                         \
-        void set_mode(int mode) { grhip_detail::check(grhip_##NAME##_set_mode(d_h, mode)); }                           \
-        void set_decimation(double decim) { grhip_detail::check(grhip_##NAME##_set_decimation(d_h, decim)); update_rate(); } \
-        void set_vec_rate(double r) { grhip_detail::check(grhip_##NAME##_set_vec_rate(d_h, r)); update_rate(); }       \
-        void set_sample_rate(double r) { grhip_detail::check(grhip_##NAME##_set_sample_rate(d_h, r)); update_rate(); } \
-        void set_average(bool average) { grhip_detail::check(grhip_##NAME##_set_average(d_h, average)); }              \
-        void set_avg_alpha(double a) { grhip_detail::check(grhip_##NAME##_set_avg_alpha(d_h, a)); }                    \
-        double sample_rate() const { return grhip_##NAME##_sample_rate(d_h); }                                         \
-        int decimation() const { return grhip_##NAME##_decimation(d_h); }                                              \
-        double frame_rate() const { return grhip_##NAME##_frame_rate(d_h); }                                           \
-        bool average() const { return grhip_##NAME##_average(d_h) != 0; }                                              \
-        double avg_alpha() const { return grhip_##NAME##_avg_alpha(d_h); }                                             \
-        /* one whole frame per output at least (stream_to_vector is a decimator by fft_size) */                        \
-        void forecast(int noutput_items, gr_vector_int &req) override                                                  \
-        {                                                                                                              \
-            for (size_t i = 0; i < req.size(); i++) req[i] = noutput_items * d_fft_size;                               \
-        }                                                                                                              \
-        /* as many whole frames as there are, cut so that no more than noutput_items come out (gr_keep_one_in_n.cc:80) */ \
-        int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,                \
-                         gr_vector_void_star &out) override                                                            \
-        {                                                                                                              \
-            const int n = decimation();                                                                                \
-            int nf = ninput_items[0] / d_fft_size;                                                                     \
-            while (nf > 0 && grhip_##NAME##_produced(d_h, nf) > noutput_items) {                                       \
-                const int over = grhip_##NAME##_produced(d_h, nf) - noutput_items;                                     \
-                nf -= over > 1 ? (over - 1) * n : 1;                                                                   \
-            }                                                                                                          \
-            int r = nf > 0 ? grhip_##NAME##_work(d_h, nf, in[0], out[0]) : 0;                                          \
-            grhip_detail::check(r);                                                                                    \
-            consume_each(nf > 0 ? nf * d_fft_size : 0);                                                                \
-            return r;                                                                                                  \
-        }                                                                                                              \
+    namespace grhip_detail {                                                                                           \
+    struct NAME##_fns {                                                                                                \
+        typedef grhip_##NAME H;                                                                                        \
+        static constexpr const char *name = #NAME;                                                                     \
+        GRHIP_FN(NAME, create); GRHIP_FN(NAME, destroy); GRHIP_FN(NAME, set_mode); GRHIP_FN(NAME, set_decimation);     \
+        GRHIP_FN(NAME, set_vec_rate); GRHIP_FN(NAME, set_sample_rate); GRHIP_FN(NAME, set_average);                    \
+        GRHIP_FN(NAME, set_avg_alpha); GRHIP_FN(NAME, sample_rate); GRHIP_FN(NAME, decimation);                        \
+        GRHIP_FN(NAME, frame_rate); GRHIP_FN(NAME, average); GRHIP_FN(NAME, avg_alpha); GRHIP_FN(NAME, produced);      \
+        GRHIP_FN(NAME, work);                                                                                          \
     };                                                                                                                 \
+    }                                                                                                                  \
+    typedef grhip_logpwrfft_blk<grhip_detail::NAME##_fns, IN_T> grhip_##NAME##_blk;                                    \
+    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                 \
     inline grhip_##NAME##_sptr gr_make_##NAME(double sample_rate, int fft_size, double ref_scale, double frame_rate,   \
                                               double avg_alpha, bool average,                                          \
                                               const std::vector<double> &win = std::vector<double>(), int device = 0)  \
     {                                                                                                                  \
-        return gnuradio::get_initial_sptr(                                                                             \
-            new grhip_##NAME##_blk(sample_rate, fft_size, ref_scale, frame_rate, avg_alpha, average, win, device));    \
+        return grhip_detail::factory::make<grhip_##NAME##_blk>(sample_rate, fft_size, ref_scale, frame_rate, avg_alpha, \
+                                                               average, win, device);                                  \
     }
 GRHIP_LOGPWRFFT_BLK(logpwrfft_c, gr_complex)
 GRHIP_LOGPWRFFT_BLK(logpwrfft_f, float)
@@ -1414,19 +1366,14 @@ inline std::vector<float> squelch_range()
 }  // namespace grhip_detail
 
 #define GRHIP_PWR_SQUELCH_BLK(NAME, ITEM)                                                                              \
-    class grhip_##NAME##_blk;                                                                                          \
-    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                 \
-    class grhip_##NAME##_blk : public gr_block {                                                                       \
-        grhip_##NAME *d_h = nullptr;                                                                                   \
+    class grhip_##NAME##_blk : public GRHIP_BLOCK(gr_block, NAME) {                                                    \
+        friend struct grhip_detail::factory;                                                                           \
         grhip_##NAME##_blk(double db, double alpha, int ramp, bool gate, int device)                                   \
-            : gr_block(#NAME, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM)))      \
+            : block(#NAME, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM)))         \
         {                                                                                                              \
-            grhip_detail::check(grhip_##NAME##_create(&d_h, db, alpha, ramp, gate, device));                           \
+            grhip_detail::check(grhip_##NAME##_create(d_h.out(), db, alpha, ramp, gate, device));                      \
         }                                                                                                              \
-        friend grhip_##NAME##_sptr gr_make_##NAME(double, double, int, bool, int);                                     \
     public:                                                                                                            \
-        ~grhip_##NAME##_blk() { grhip_##NAME##_destroy(d_h); }                                                         \
-        void set_mode(int mode) { grhip_detail::check(grhip_##NAME##_set_mode(d_h, mode)); }                           \
         double threshold() const { return grhip_##NAME##_threshold(d_h); }                                             \
         void set_threshold(double db) { grhip_detail::check(grhip_##NAME##_set_threshold(d_h, db)); }                  \
         void set_alpha(double alpha) { grhip_detail::check(grhip_##NAME##_set_alpha(d_h, alpha)); }                    \
@@ -1434,52 +1381,33 @@ inline std::vector<float> squelch_range()
         void set_ramp(int ramp) { grhip_detail::check(grhip_##NAME##_set_ramp(d_h, ramp)); }                           \
         bool gate() const { return grhip_##NAME##_gate(d_h) != 0; }                                                    \
         void set_gate(bool gate) { grhip_detail::check(grhip_##NAME##_set_gate(d_h, gate)); }                          \
-        bool unmuted() const                                                                                           \
-        {                                                                                                              \
-            int r = grhip_##NAME##_unmuted(d_h, 0);                                                                    \
-            grhip_detail::check(r);                                                                                    \
-            return r != 0;                                                                                             \
-        }                                                                                                              \
+        bool unmuted() const { return checked(grhip_##NAME##_unmuted(d_h, 0)) != 0; }                                  \
         std::vector<float> squelch_range() const { return grhip_detail::squelch_range(); }                             \
         int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,                \
                          gr_vector_void_star &out) override                                                            \
         {                                                                                                              \
-            const int n = noutput_items < ninput_items[0] ? noutput_items : ninput_items[0];                           \
-            int produced = 0;                                                                                          \
-            grhip_detail::check(grhip_##NAME##_work(d_h, n, in[0], out[0], &produced));                                \
-            consume_each(n);                                    /* use all the inputs, report the outputs copied */     \
-            return produced;                                                                                           \
+            return work_all_inputs(grhip_##NAME##_work, noutput_items, ninput_items, in, out);                         \
         }                                                                                                              \
     };                                                                                                                 \
+    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                 \
     inline grhip_##NAME##_sptr gr_make_##NAME(double db, double alpha = 0.0001, int ramp = 0, bool gate = false,       \
                                               int device = 0)                                                          \
     {                                                                                                                  \
-        return gnuradio::get_initial_sptr(new grhip_##NAME##_blk(db, alpha, ramp, gate, device));                      \
+        return grhip_detail::factory::make<grhip_##NAME##_blk>(db, alpha, ramp, gate, device);                         \
     }
 GRHIP_PWR_SQUELCH_BLK(pwr_squelch_cc, gr_complex)
 GRHIP_PWR_SQUELCH_BLK(pwr_squelch_ff, float)
 #undef GRHIP_PWR_SQUELCH_BLK
 
-class grhip_simple_squelch_cc_blk;
-typedef boost::shared_ptr<grhip_simple_squelch_cc_blk> grhip_simple_squelch_cc_sptr;
-class grhip_simple_squelch_cc_blk : public gr_sync_block {
-    grhip_simple_squelch_cc *d_h = nullptr;
+class grhip_simple_squelch_cc_blk : public GRHIP_BLOCK(gr_sync_block, simple_squelch_cc) {
+    friend struct grhip_detail::factory;
     grhip_simple_squelch_cc_blk(double threshold_db, double alpha, int device)
-        : gr_sync_block("simple_squelch_cc", gr_make_io_signature(1, 1, sizeof(gr_complex)),
-                        gr_make_io_signature(1, 1, sizeof(gr_complex)))
+        : block("simple_squelch_cc", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(gr_complex)))
     {
-        grhip_detail::check(grhip_simple_squelch_cc_create(&d_h, threshold_db, alpha, device));
+        grhip_detail::check(grhip_simple_squelch_cc_create(d_h.out(), threshold_db, alpha, device));
     }
-    friend grhip_simple_squelch_cc_sptr gr_make_simple_squelch_cc(double, double, int);
 public:
-    ~grhip_simple_squelch_cc_blk() { grhip_simple_squelch_cc_destroy(d_h); }
-    void set_mode(int mode) { grhip_detail::check(grhip_simple_squelch_cc_set_mode(d_h, mode)); }
-    bool unmuted() const
-    {
-        int r = grhip_simple_squelch_cc_unmuted(d_h, 0);
-        grhip_detail::check(r);
-        return r != 0;
-    }
+    bool unmuted() const { return checked(grhip_simple_squelch_cc_unmuted(d_h, 0)) != 0; }
     void set_alpha(double alpha) { grhip_detail::check(grhip_simple_squelch_cc_set_alpha(d_h, alpha)); }
     void set_threshold(double decibels) { grhip_detail::check(grhip_simple_squelch_cc_set_threshold(d_h, decibels)); }
     double threshold() const { return grhip_simple_squelch_cc_threshold(d_h); }
@@ -1491,9 +1419,10 @@ public:
         return noutput_items ? produced : 0;
     }
 };
+typedef boost::shared_ptr<grhip_simple_squelch_cc_blk> grhip_simple_squelch_cc_sptr;
 inline grhip_simple_squelch_cc_sptr gr_make_simple_squelch_cc(double threshold_db, double alpha = 0.0001, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_simple_squelch_cc_blk(threshold_db, alpha, device));
+    return grhip_detail::factory::make<grhip_simple_squelch_cc_blk>(threshold_db, alpha, device);
 }
 
 // ---------------------------------------------------------------------------
@@ -1501,19 +1430,14 @@ inline grhip_simple_squelch_cc_sptr gr_make_simple_squelch_cc(double threshold_d
 // general_work consumes every input and returns the items produced (general/gr_ctcss_squelch_ff.h:33-66,
 // gr_squelch_base_ff.cc:42-93).  The blocks of len samples run across general_work calls.
 // ---------------------------------------------------------------------------
-class grhip_ctcss_squelch_ff_blk;
-typedef boost::shared_ptr<grhip_ctcss_squelch_ff_blk> grhip_ctcss_squelch_ff_sptr;
-class grhip_ctcss_squelch_ff_blk : public gr_block {
-    grhip_ctcss_squelch_ff *d_h = nullptr;
+class grhip_ctcss_squelch_ff_blk : public GRHIP_BLOCK(gr_block, ctcss_squelch_ff) {
+    friend struct grhip_detail::factory;
     grhip_ctcss_squelch_ff_blk(int rate, float freq, float level, int len, int ramp, bool gate, int device)
-        : gr_block("ctcss_squelch_ff", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(float)))
+        : block("ctcss_squelch_ff", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(float)))
     {
-        grhip_detail::check(grhip_ctcss_squelch_ff_create(&d_h, rate, freq, level, len, ramp, gate, device));
+        grhip_detail::check(grhip_ctcss_squelch_ff_create(d_h.out(), rate, freq, level, len, ramp, gate, device));
     }
-    friend grhip_ctcss_squelch_ff_sptr gr_make_ctcss_squelch_ff(int, float, float, int, int, bool, int);
 public:
-    ~grhip_ctcss_squelch_ff_blk() { grhip_ctcss_squelch_ff_destroy(d_h); }
-    void set_mode(int mode) { grhip_detail::check(grhip_ctcss_squelch_ff_set_mode(d_h, mode)); }
     float level() const { return grhip_ctcss_squelch_ff_level(d_h); }
     void set_level(float level) { grhip_detail::check(grhip_ctcss_squelch_ff_set_level(d_h, level)); }
     int len() const { return grhip_ctcss_squelch_ff_len(d_h); }
@@ -1521,12 +1445,7 @@ public:
     void set_ramp(int ramp) { grhip_detail::check(grhip_ctcss_squelch_ff_set_ramp(d_h, ramp)); }
     bool gate() const { return grhip_ctcss_squelch_ff_gate(d_h) != 0; }
     void set_gate(bool gate) { grhip_detail::check(grhip_ctcss_squelch_ff_set_gate(d_h, gate)); }
-    bool unmuted() const
-    {
-        int r = grhip_ctcss_squelch_ff_unmuted(d_h, 0);
-        grhip_detail::check(r);
-        return r != 0;
-    }
+    bool unmuted() const { return checked(grhip_ctcss_squelch_ff_unmuted(d_h, 0)) != 0; }
     std::vector<float> squelch_range() const
     {
         std::vector<float> r(3);
@@ -1536,17 +1455,14 @@ public:
     int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in,
                      gr_vector_void_star &out) override
     {
-        const int n = noutput_items < ninput_items[0] ? noutput_items : ninput_items[0];
-        int produced = 0;
-        grhip_detail::check(grhip_ctcss_squelch_ff_work(d_h, n, in[0], out[0], &produced));
-        consume_each(n);                                        /* use all the inputs, report the outputs copied */
-        return produced;
+        return work_all_inputs(grhip_ctcss_squelch_ff_work, noutput_items, ninput_items, in, out);
     }
 };
+typedef boost::shared_ptr<grhip_ctcss_squelch_ff_blk> grhip_ctcss_squelch_ff_sptr;
 inline grhip_ctcss_squelch_ff_sptr gr_make_ctcss_squelch_ff(int rate, float freq, float level = 0.01, int len = 0, int ramp = 0,
                                                             bool gate = false, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_ctcss_squelch_ff_blk(rate, freq, level, len, ramp, gate, device));
+    return grhip_detail::factory::make<grhip_ctcss_squelch_ff_blk>(rate, freq, level, len, ramp, gate, device);
 }
 
 // ---------------------------------------------------------------------------
@@ -1555,71 +1471,80 @@ inline grhip_ctcss_squelch_ff_sptr gr_make_ctcss_squelch_ff(int rate, float freq
 // setters of gri_agc_cc / gri_agc2_cc that the reference's blocks inherit (general/gr_agc_cc.h:33-52,
 // gr_agc2_cc.h:34-54).  The gain carries across work calls; the setters act at once.
 // ---------------------------------------------------------------------------
-#define GRHIP_AGC_BLK_COMMON(NAME, ITEM)                                                                                 \
-    public:                                                                                                              \
-        ~grhip_##NAME##_blk() { grhip_##NAME##_destroy(d_h); }                                                           \
-        void set_mode(int mode) { grhip_detail::check(grhip_##NAME##_set_mode(d_h, mode)); }                             \
-        float reference() const { return grhip_##NAME##_reference(d_h); }                                                \
-        float max_gain() const { return grhip_##NAME##_max_gain(d_h); }                                                  \
-        float gain() const                                                                                               \
-        {                                                                                                                \
-            float g = 0.f;                                                                                               \
-            grhip_detail::check(grhip_##NAME##_gain(d_h, 0, &g));                                                        \
-            return g;                                                                                                    \
-        }                                                                                                                \
-        void set_reference(float reference) { grhip_detail::check(grhip_##NAME##_set_reference(d_h, reference)); }       \
-        void set_gain(float gain) { grhip_detail::check(grhip_##NAME##_set_gain(d_h, gain)); }                           \
-        void set_max_gain(float max_gain) { grhip_detail::check(grhip_##NAME##_set_max_gain(d_h, max_gain)); }           \
-        int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override                    \
-        {                                                                                                                \
-            grhip_detail::check(grhip_##NAME##_work(d_h, noutput_items, in[0], out[0]));                                 \
-            return noutput_items;                                                                                        \
-        }                                                                                                                \
+namespace grhip_detail {
+// what the four have in common: reference, gain and max_gain, and work.  T is the table GRHIP_AGC_FNS builds
+template <class T, class ITEM> class agc_block : public block<gr_sync_block, typename T::H, T::destroy, T::set_mode> {
+protected:
+    agc_block() : agc_block::block(T::name, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM))) {}
+public:
+    float reference() const { return T::reference(this->d_h); }
+    float max_gain() const { return T::max_gain(this->d_h); }
+    float gain() const
+    {
+        float g = 0.f;
+        check(T::gain(this->d_h, 0, &g));
+        return g;
+    }
+    void set_reference(float reference) { check(T::set_reference(this->d_h, reference)); }
+    void set_gain(float gain) { check(T::set_gain(this->d_h, gain)); }
+    void set_max_gain(float max_gain) { check(T::set_max_gain(this->d_h, max_gain)); }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        check(T::work(this->d_h, noutput_items, in[0], out[0]));
+        return noutput_items;
+    }
+};
+}  // namespace grhip_detail
+#define GRHIP_AGC_FNS(NAME)                                                                                              \
+    namespace grhip_detail {                                                                                             \
+    struct NAME##_fns {                                                                                                  \
+        typedef grhip_##NAME H;                                                                                          \
+        static constexpr const char *name = #NAME;                                                                       \
+        GRHIP_FN(NAME, destroy); GRHIP_FN(NAME, set_mode); GRHIP_FN(NAME, reference); GRHIP_FN(NAME, max_gain);          \
+        GRHIP_FN(NAME, gain); GRHIP_FN(NAME, set_reference); GRHIP_FN(NAME, set_gain); GRHIP_FN(NAME, set_max_gain);     \
+        GRHIP_FN(NAME, work);                                                                                            \
+    };                                                                                                                   \
     }
 
 #define GRHIP_AGC_BLK(NAME, ITEM)                                                                                        \
-    class grhip_##NAME##_blk;                                                                                            \
-    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                   \
-    class grhip_##NAME##_blk : public gr_sync_block {                                                                    \
-        grhip_##NAME *d_h = nullptr;                                                                                     \
+    GRHIP_AGC_FNS(NAME)                                                                                                  \
+    class grhip_##NAME##_blk : public grhip_detail::agc_block<grhip_detail::NAME##_fns, ITEM> {                          \
+        friend struct grhip_detail::factory;                                                                             \
         grhip_##NAME##_blk(float rate, float reference, float gain, float max_gain, int device)                          \
-            : gr_sync_block(#NAME, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM)))   \
         {                                                                                                                \
-            grhip_detail::check(grhip_##NAME##_create(&d_h, rate, reference, gain, max_gain, device));                   \
+            grhip_detail::check(grhip_##NAME##_create(d_h.out(), rate, reference, gain, max_gain, device));              \
         }                                                                                                                \
-        friend grhip_##NAME##_sptr gr_make_##NAME(float, float, float, float, int);                                      \
     public:                                                                                                              \
         float rate() const { return grhip_##NAME##_rate(d_h); }                                                          \
         void set_rate(float rate) { grhip_detail::check(grhip_##NAME##_set_rate(d_h, rate)); }                           \
-    GRHIP_AGC_BLK_COMMON(NAME, ITEM);                                                                                    \
+    };                                                                                                                   \
+    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                   \
     inline grhip_##NAME##_sptr gr_make_##NAME(float rate = 1e-4, float reference = 1.0, float gain = 1.0,                \
                                               float max_gain = 0.0, int device = 0)                                      \
     {                                                                                                                    \
-        return gnuradio::get_initial_sptr(new grhip_##NAME##_blk(rate, reference, gain, max_gain, device));              \
+        return grhip_detail::factory::make<grhip_##NAME##_blk>(rate, reference, gain, max_gain, device);                 \
     }
 
 #define GRHIP_AGC2_BLK(NAME, ITEM)                                                                                       \
-    class grhip_##NAME##_blk;                                                                                            \
-    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                   \
-    class grhip_##NAME##_blk : public gr_sync_block {                                                                    \
-        grhip_##NAME *d_h = nullptr;                                                                                     \
+    GRHIP_AGC_FNS(NAME)                                                                                                  \
+    class grhip_##NAME##_blk : public grhip_detail::agc_block<grhip_detail::NAME##_fns, ITEM> {                          \
+        friend struct grhip_detail::factory;                                                                             \
         grhip_##NAME##_blk(float attack_rate, float decay_rate, float reference, float gain, float max_gain, int device) \
-            : gr_sync_block(#NAME, gr_make_io_signature(1, 1, sizeof(ITEM)), gr_make_io_signature(1, 1, sizeof(ITEM)))   \
         {                                                                                                                \
-            grhip_detail::check(grhip_##NAME##_create(&d_h, attack_rate, decay_rate, reference, gain, max_gain, device)); \
+            grhip_detail::check(grhip_##NAME##_create(d_h.out(), attack_rate, decay_rate, reference, gain, max_gain, device)); \
         }                                                                                                                \
-        friend grhip_##NAME##_sptr gr_make_##NAME(float, float, float, float, float, int);                               \
     public:                                                                                                              \
         float attack_rate() const { return grhip_##NAME##_attack_rate(d_h); }                                            \
         float decay_rate() const { return grhip_##NAME##_decay_rate(d_h); }                                              \
         void set_attack_rate(float rate) { grhip_detail::check(grhip_##NAME##_set_attack_rate(d_h, rate)); }             \
         void set_decay_rate(float rate) { grhip_detail::check(grhip_##NAME##_set_decay_rate(d_h, rate)); }               \
-    GRHIP_AGC_BLK_COMMON(NAME, ITEM);                                                                                    \
+    };                                                                                                                   \
+    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                   \
     inline grhip_##NAME##_sptr gr_make_##NAME(float attack_rate = 1e-1, float decay_rate = 1e-2, float reference = 1.0,  \
                                               float gain = 1.0, float max_gain = 0.0, int device = 0)                    \
     {                                                                                                                    \
-        return gnuradio::get_initial_sptr(new grhip_##NAME##_blk(attack_rate, decay_rate, reference, gain, max_gain,     \
-                                                                 device));                                               \
+        return grhip_detail::factory::make<grhip_##NAME##_blk>(attack_rate, decay_rate, reference, gain, max_gain,       \
+                                                               device);                                                  \
     }
 
 GRHIP_AGC_BLK(agc_cc, gr_complex)
@@ -1628,7 +1553,7 @@ GRHIP_AGC2_BLK(agc2_cc, gr_complex)
 GRHIP_AGC2_BLK(agc2_ff, float)
 #undef GRHIP_AGC_BLK
 #undef GRHIP_AGC2_BLK
-#undef GRHIP_AGC_BLK_COMMON
+#undef GRHIP_AGC_FNS
 
 // ---------------------------------------------------------------------------
 // digital_costas_loop_cc (loop_bw, order; 1 input, 1..2 outputs: gr-digital/include/digital_costas_loop_cc.h:61-112) and
@@ -1638,57 +1563,80 @@ GRHIP_AGC2_BLK(agc2_ff, float)
 // setters act at once.  A value the reference refuses (std::out_of_range, std::invalid_argument) throws
 // std::invalid_argument here.
 // ---------------------------------------------------------------------------
-#define GRHIP_LOOP_BLK_COMMON(NAME)                                                                                      \
-    public:                                                                                                              \
-        ~grhip_##NAME##_blk() { grhip_##NAME##_destroy(d_h); }                                                           \
-        void set_mode(int mode) { grhip_detail::check(grhip_##NAME##_set_mode(d_h, mode)); }                             \
-        void set_loop_bandwidth(float bw) { grhip_detail::check(grhip_##NAME##_set_loop_bandwidth(d_h, bw)); }           \
-        void set_damping_factor(float df) { grhip_detail::check(grhip_##NAME##_set_damping_factor(d_h, df)); }           \
-        void set_alpha(float alpha) { grhip_detail::check(grhip_##NAME##_set_alpha(d_h, alpha)); }                       \
-        void set_beta(float beta) { grhip_detail::check(grhip_##NAME##_set_beta(d_h, beta)); }                           \
-        void set_frequency(float freq) { grhip_detail::check(grhip_##NAME##_set_frequency(d_h, freq)); }                 \
-        void set_phase(float phase) { grhip_detail::check(grhip_##NAME##_set_phase(d_h, phase)); }                       \
-        float get_loop_bandwidth() const { return grhip_##NAME##_get_loop_bandwidth(d_h); }                              \
-        float get_damping_factor() const { return grhip_##NAME##_get_damping_factor(d_h); }                              \
-        float get_alpha() const { return grhip_##NAME##_get_alpha(d_h); }                                                \
-        float get_beta() const { return grhip_##NAME##_get_beta(d_h); }                                                  \
-        float get_frequency() const                                                                                      \
-        {                                                                                                                \
-            float v = 0.f;                                                                                               \
-            grhip_detail::check(grhip_##NAME##_get_frequency(d_h, 0, &v));                                               \
-            return v;                                                                                                    \
-        }                                                                                                                \
-        float get_phase() const                                                                                          \
-        {                                                                                                                \
-            float v = 0.f;                                                                                               \
-            grhip_detail::check(grhip_##NAME##_get_phase(d_h, 0, &v));                                                   \
-            return v;                                                                                                    \
-        }
-
-#define GRHIP_PLL_BLK(NAME, OUT_ITEM)                                                                                    \
-    class grhip_##NAME##_blk;                                                                                            \
-    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                   \
-    class grhip_##NAME##_blk : public gr_sync_block {                                                                    \
-    protected:                                                                                                           \
-        grhip_##NAME *d_h = nullptr;                                                                                     \
-        grhip_##NAME##_blk(float loop_bw, float max_freq, float min_freq, int device)                                    \
-            : gr_sync_block(#NAME, gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(OUT_ITEM))) \
-        {                                                                                                                \
-            grhip_detail::check(grhip_##NAME##_create(&d_h, loop_bw, max_freq, min_freq, device));                       \
-        }                                                                                                                \
-        friend grhip_##NAME##_sptr gr_make_##NAME(float, float, float, int);                                             \
-    GRHIP_LOOP_BLK_COMMON(NAME)                                                                                          \
-        int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override                    \
-        {                                                                                                                \
-            grhip_detail::check(grhip_##NAME##_work(d_h, noutput_items, in[0], out[0]));                                 \
-            return noutput_items;                                                                                        \
-        }
-
-GRHIP_PLL_BLK(pll_freqdet_cf, float)
+namespace grhip_detail {
+// gri_control_loop's interface over the handle of a block<BASE, ...>.  T is the table GRHIP_LOOP_FNS builds
+template <class BASE, class T> class loop_block : public block<BASE, typename T::H, T::destroy, T::set_mode> {
+protected:
+    template <class... A> explicit loop_block(A &&...a) : loop_block::block(std::forward<A>(a)...) {}
+public:
+    void set_loop_bandwidth(float bw) { check(T::set_loop_bandwidth(this->d_h, bw)); }
+    void set_damping_factor(float df) { check(T::set_damping_factor(this->d_h, df)); }
+    void set_alpha(float alpha) { check(T::set_alpha(this->d_h, alpha)); }
+    void set_beta(float beta) { check(T::set_beta(this->d_h, beta)); }
+    void set_frequency(float freq) { check(T::set_frequency(this->d_h, freq)); }
+    void set_phase(float phase) { check(T::set_phase(this->d_h, phase)); }
+    float get_loop_bandwidth() const { return T::get_loop_bandwidth(this->d_h); }
+    float get_damping_factor() const { return T::get_damping_factor(this->d_h); }
+    float get_alpha() const { return T::get_alpha(this->d_h); }
+    float get_beta() const { return T::get_beta(this->d_h); }
+    float get_frequency() const
+    {
+        float v = 0.f;
+        check(T::get_frequency(this->d_h, 0, &v));
+        return v;
+    }
+    float get_phase() const
+    {
+        float v = 0.f;
+        check(T::get_phase(this->d_h, 0, &v));
+        return v;
+    }
 };
-GRHIP_PLL_BLK(pll_refout_cc, gr_complex)
+}  // namespace grhip_detail
+#define GRHIP_LOOP_FNS(NAME)                                                                                             \
+    namespace grhip_detail {                                                                                             \
+    struct NAME##_fns {                                                                                                  \
+        typedef grhip_##NAME H;                                                                                          \
+        static constexpr const char *name = #NAME;                                                                       \
+        GRHIP_FN(NAME, create); GRHIP_FN(NAME, destroy); GRHIP_FN(NAME, set_mode); GRHIP_FN(NAME, work);                 \
+        GRHIP_FN(NAME, set_loop_bandwidth); GRHIP_FN(NAME, set_damping_factor); GRHIP_FN(NAME, set_alpha);               \
+        GRHIP_FN(NAME, set_beta); GRHIP_FN(NAME, set_frequency); GRHIP_FN(NAME, set_phase);                              \
+        GRHIP_FN(NAME, get_loop_bandwidth); GRHIP_FN(NAME, get_damping_factor); GRHIP_FN(NAME, get_alpha);               \
+        GRHIP_FN(NAME, get_beta); GRHIP_FN(NAME, get_frequency); GRHIP_FN(NAME, get_phase);                              \
+    };                                                                                                                   \
+    }
+#define GRHIP_LOOP_BLOCK(GRBASE, NAME) grhip_detail::loop_block<GRBASE, grhip_detail::NAME##_fns>
+GRHIP_LOOP_FNS(pll_freqdet_cf)
+GRHIP_LOOP_FNS(pll_refout_cc)
+GRHIP_LOOP_FNS(pll_carriertracking_cc)
+GRHIP_LOOP_FNS(costas_loop_cc)
+GRHIP_LOOP_FNS(fll_band_edge_cc)
+GRHIP_LOOP_FNS(constellation_receiver_cb)
+GRHIP_LOOP_FNS(constellation_demod_cb)
+#undef GRHIP_LOOP_FNS
+
+// the three PLLs: complex in, OUT_ITEM out
+template <class T, class OUT_ITEM> class grhip_pll_blk : public grhip_detail::loop_block<gr_sync_block, T> {
+    friend struct grhip_detail::factory;
+protected:
+    grhip_pll_blk(float loop_bw, float max_freq, float min_freq, int device)
+        : grhip_pll_blk::loop_block(T::name, gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(OUT_ITEM)))
+    {
+        grhip_detail::check(T::create(this->d_h.out(), loop_bw, max_freq, min_freq, device));
+    }
+public:
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(T::work(this->d_h, noutput_items, in[0], out[0]));
+        return noutput_items;
+    }
 };
-GRHIP_PLL_BLK(pll_carriertracking_cc, gr_complex)
+typedef grhip_pll_blk<grhip_detail::pll_freqdet_cf_fns, float> grhip_pll_freqdet_cf_blk;
+typedef grhip_pll_blk<grhip_detail::pll_refout_cc_fns, gr_complex> grhip_pll_refout_cc_blk;
+class grhip_pll_carriertracking_cc_blk : public grhip_pll_blk<grhip_detail::pll_carriertracking_cc_fns, gr_complex> {
+    friend struct grhip_detail::factory;
+    using grhip_pll_blk::grhip_pll_blk;
+public:
     // general/gr_pll_carriertracking_cc.h:84-90
     bool lock_detector()
     {
@@ -1708,28 +1656,25 @@ GRHIP_PLL_BLK(pll_carriertracking_cc, gr_complex)
     }
 };
 #define GRHIP_PLL_MAKE(NAME)                                                                                             \
+    typedef boost::shared_ptr<grhip_##NAME##_blk> grhip_##NAME##_sptr;                                                   \
     inline grhip_##NAME##_sptr gr_make_##NAME(float loop_bw, float max_freq, float min_freq, int device = 0)             \
     {                                                                                                                    \
-        return gnuradio::get_initial_sptr(new grhip_##NAME##_blk(loop_bw, max_freq, min_freq, device));                  \
+        return grhip_detail::factory::make<grhip_##NAME##_blk>(loop_bw, max_freq, min_freq, device);                     \
     }
 GRHIP_PLL_MAKE(pll_freqdet_cf)
 GRHIP_PLL_MAKE(pll_refout_cc)
 GRHIP_PLL_MAKE(pll_carriertracking_cc)
 #undef GRHIP_PLL_MAKE
-#undef GRHIP_PLL_BLK
 
-class grhip_costas_loop_cc_blk;
-typedef boost::shared_ptr<grhip_costas_loop_cc_blk> grhip_costas_loop_cc_sptr;
-class grhip_costas_loop_cc_blk : public gr_sync_block {
-    grhip_costas_loop_cc *d_h = nullptr;
+class grhip_costas_loop_cc_blk : public GRHIP_LOOP_BLOCK(gr_sync_block, costas_loop_cc) {
+    friend struct grhip_detail::factory;
     grhip_costas_loop_cc_blk(float loop_bw, int order, int device)
-        : gr_sync_block("costas_loop_cc", gr_make_io_signature(1, 1, sizeof(gr_complex)),
-                        gr_make_io_signature2(1, 2, sizeof(gr_complex), sizeof(float)))     // digital_costas_loop_cc.cc:43-45
+        : loop_block("costas_loop_cc", gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                     gr_make_io_signature2(1, 2, sizeof(gr_complex), sizeof(float)))     // digital_costas_loop_cc.cc:43-45
     {
-        grhip_detail::check(grhip_costas_loop_cc_create(&d_h, loop_bw, order, device));
+        grhip_detail::check(grhip_costas_loop_cc_create(d_h.out(), loop_bw, order, device));
     }
-    friend grhip_costas_loop_cc_sptr digital_make_costas_loop_cc(float, int, int);
-GRHIP_LOOP_BLK_COMMON(costas_loop_cc)
+public:
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         // the second output is optional (digital_costas_loop_cc.cc:119)
@@ -1737,9 +1682,10 @@ GRHIP_LOOP_BLK_COMMON(costas_loop_cc)
         return noutput_items;
     }
 };
+typedef boost::shared_ptr<grhip_costas_loop_cc_blk> grhip_costas_loop_cc_sptr;
 inline grhip_costas_loop_cc_sptr digital_make_costas_loop_cc(float loop_bw, int order, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_costas_loop_cc_blk(loop_bw, order, device));
+    return grhip_detail::factory::make<grhip_costas_loop_cc_blk>(loop_bw, order, device);
 }
 // ---------------------------------------------------------------------------
 // digital_fll_band_edge_cc (samps_per_sym, rolloff, filter_size, bandwidth; 1 input, 1 or 4 outputs: the derotated
@@ -1748,20 +1694,17 @@ inline grhip_costas_loop_cc_sptr digital_make_costas_loop_cc(float loop_bw, int 
 // work the filter_size items before the new ones too, the handle keeps what it needs of the past itself and takes the
 // new items only (include/grhip.h states what is computed).  gr_firdes::root_raised_cosine comes with it.
 // ---------------------------------------------------------------------------
-class grhip_fll_band_edge_cc_blk;
-typedef boost::shared_ptr<grhip_fll_band_edge_cc_blk> grhip_fll_band_edge_cc_sptr;
-class grhip_fll_band_edge_cc_blk : public gr_sync_block {
-    grhip_fll_band_edge_cc *d_h = nullptr;
+class grhip_fll_band_edge_cc_blk : public GRHIP_LOOP_BLOCK(gr_sync_block, fll_band_edge_cc) {
+    friend struct grhip_detail::factory;
     static std::vector<int> iosig() { return {(int)sizeof(gr_complex), (int)sizeof(float), (int)sizeof(float), (int)sizeof(float)}; }
     grhip_fll_band_edge_cc_blk(float samps_per_sym, float rolloff, int filter_size, float bandwidth, int device)
-        : gr_sync_block("fll_band_edge_cc", gr_make_io_signature(1, 1, sizeof(gr_complex)),
-                        gr_make_io_signaturev(1, 4, iosig()))                                // digital_fll_band_edge_cc.cc:51-57
+        : loop_block("fll_band_edge_cc", gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                     gr_make_io_signaturev(1, 4, iosig()))                                   // digital_fll_band_edge_cc.cc:51-57
     {
-        grhip_detail::check(grhip_fll_band_edge_cc_create(&d_h, samps_per_sym, rolloff, filter_size, bandwidth, device));
+        grhip_detail::check(grhip_fll_band_edge_cc_create(d_h.out(), samps_per_sym, rolloff, filter_size, bandwidth, device));
         set_history(filter_size + 1);                                                       // :187
     }
-    friend grhip_fll_band_edge_cc_sptr digital_make_fll_band_edge_cc(float, float, int, float, int);
-GRHIP_LOOP_BLK_COMMON(fll_band_edge_cc)
+public:
     void set_samples_per_symbol(float sps) { grhip_detail::check(grhip_fll_band_edge_cc_set_samples_per_symbol(d_h, sps)); }
     void set_rolloff(float rolloff) { grhip_detail::check(grhip_fll_band_edge_cc_set_rolloff(d_h, rolloff)); }
     void set_filter_size(int filter_size)
@@ -1771,12 +1714,7 @@ GRHIP_LOOP_BLK_COMMON(fll_band_edge_cc)
     }
     float get_samples_per_symbol() const { return grhip_fll_band_edge_cc_get_samples_per_symbol(d_h); }
     float get_rolloff() const { return grhip_fll_band_edge_cc_get_rolloff(d_h); }
-    int get_filter_size() const
-    {
-        const int v = grhip_fll_band_edge_cc_get_filter_size(d_h);
-        grhip_detail::check(v);
-        return v;
-    }
+    int get_filter_size() const { return checked(grhip_fll_band_edge_cc_get_filter_size(d_h)); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         const gr_complex *fresh = (const gr_complex *)in[0] + (history() - 1);
@@ -1786,10 +1724,11 @@ GRHIP_LOOP_BLK_COMMON(fll_band_edge_cc)
         return noutput_items;
     }
 };
+typedef boost::shared_ptr<grhip_fll_band_edge_cc_blk> grhip_fll_band_edge_cc_sptr;
 inline grhip_fll_band_edge_cc_sptr digital_make_fll_band_edge_cc(float samps_per_sym, float rolloff, int filter_size, float bandwidth,
                                                                  int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_fll_band_edge_cc_blk(samps_per_sym, rolloff, filter_size, bandwidth, device));
+    return grhip_detail::factory::make<grhip_fll_band_edge_cc_blk>(samps_per_sym, rolloff, filter_size, bandwidth, device);
 }
 
 // ---------------------------------------------------------------------------
@@ -1802,17 +1741,15 @@ inline grhip_fll_band_edge_cc_sptr digital_make_fll_band_edge_cc(float samps_per
 // produced; a symbol whose last items have not arrived comes with a later call.  output_multiple() is osps (floor(sps) + 1),
 // so that a scheduler never offers less space than one new item may need.  set_taps is not offered.
 // ---------------------------------------------------------------------------
-class grhip_pfb_clock_sync_ccf_blk;
-typedef boost::shared_ptr<grhip_pfb_clock_sync_ccf_blk> grhip_pfb_clock_sync_ccf_sptr;
-class grhip_pfb_clock_sync_ccf_blk : public gr_block {
-    grhip_pfb_clock_sync_ccf *d_h = nullptr;
+class grhip_pfb_clock_sync_ccf_blk : public GRHIP_BLOCK(gr_block, pfb_clock_sync_ccf) {
+    friend struct grhip_detail::factory;
     int d_nfilters = 0, d_tpf = 0, d_isps = 0, d_osps = 0;
     static std::vector<int> iosig() { return {(int)sizeof(gr_complex), (int)sizeof(float), (int)sizeof(float), (int)sizeof(float)}; }
     grhip_pfb_clock_sync_ccf_blk(double sps, float loop_bw, const std::vector<float> &taps, unsigned int filter_size, float init_phase,
                                  float max_rate_deviation, int osps, int device)
-        : gr_block("pfb_clock_sync_ccf", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signaturev(1, 4, iosig()))  // .cc:58-60
+        : block("pfb_clock_sync_ccf", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signaturev(1, 4, iosig()))  // .cc:58-60
     {
-        grhip_detail::check(grhip_pfb_clock_sync_ccf_create(&d_h, sps, loop_bw, taps.data(), (int)taps.size(),
+        grhip_detail::check(grhip_pfb_clock_sync_ccf_create(d_h.out(), sps, loop_bw, taps.data(), (int)taps.size(),
                                                              filter_size > 0x7fffffffu ? -1 : (int)filter_size, init_phase,
                                                              max_rate_deviation, osps, device));
         grhip_detail::check(grhip_pfb_clock_sync_taps(taps.data(), (int)taps.size(), (int)filter_size, nullptr, nullptr, &d_tpf));
@@ -1824,7 +1761,6 @@ class grhip_pfb_clock_sync_ccf_blk : public gr_block {
         // sets none and leaves noutput_items - osps of its space unused instead (.cc:379)
         set_output_multiple(d_osps * (d_isps + 1));
     }
-    friend grhip_pfb_clock_sync_ccf_sptr gr_make_pfb_clock_sync_ccf(double, float, const std::vector<float> &, unsigned int, float, float, int, int);
     float stream_float(int (*get)(grhip_pfb_clock_sync_ccf *, int, float *)) const
     {
         float v = 0;
@@ -1841,8 +1777,6 @@ class grhip_pfb_clock_sync_ccf_blk : public gr_block {
         return b;
     }
 public:
-    ~grhip_pfb_clock_sync_ccf_blk() { grhip_pfb_clock_sync_ccf_destroy(d_h); }
-    void set_mode(int mode) { grhip_detail::check(grhip_pfb_clock_sync_ccf_set_mode(d_h, mode)); }
     std::vector<std::vector<float> > get_taps() const { return bank(grhip_pfb_clock_sync_ccf_get_taps); }
     std::vector<std::vector<float> > get_diff_taps() const { return bank(grhip_pfb_clock_sync_ccf_get_diff_taps); }
     std::vector<float> get_channel_taps(int channel) const { return get_taps().at(channel); }
@@ -1884,12 +1818,13 @@ public:
         return produced;
     }
 };
+typedef boost::shared_ptr<grhip_pfb_clock_sync_ccf_blk> grhip_pfb_clock_sync_ccf_sptr;
 inline grhip_pfb_clock_sync_ccf_sptr gr_make_pfb_clock_sync_ccf(double sps, float loop_bw, const std::vector<float> &taps,
                                                                 unsigned int filter_size = 32, float init_phase = 0,
                                                                 float max_rate_deviation = 1.5, int osps = 1, int device = 0)
 {
-    return gnuradio::get_initial_sptr(
-        new grhip_pfb_clock_sync_ccf_blk(sps, loop_bw, taps, filter_size, init_phase, max_rate_deviation, osps, device));
+    return grhip_detail::factory::make<grhip_pfb_clock_sync_ccf_blk>(sps, loop_bw, taps, filter_size, init_phase, max_rate_deviation,
+                                                                     osps, device);
 }
 
 // gr_firdes::root_raised_cosine(gain, sampling_freq, symbol_rate, alpha, ntaps)
@@ -1909,15 +1844,14 @@ inline std::vector<float> grhip_firdes_root_raised_cosine_taps(double gain, doub
 // (gr-digital/python/generic_mod_demod.py:296-313) as one block.  A constellation is a host object; a block copies the
 // one it is made from.  What the reference refuses with std::runtime_error throws std::invalid_argument here.
 // ---------------------------------------------------------------------------
-class grhip_constellation_obj;
-typedef boost::shared_ptr<grhip_constellation_obj> grhip_constellation_sptr;
+namespace grhip_detail {
+typedef handle<grhip_constellation, grhip_constellation_destroy> constellation_handle;
+}
 class grhip_constellation_obj {
-    grhip_constellation *d_h = nullptr;
+    grhip_detail::constellation_handle d_h;
 public:
     explicit grhip_constellation_obj(grhip_constellation *h) : d_h(h) {}
-    grhip_constellation_obj(const grhip_constellation_obj &) = delete;
-    grhip_constellation_obj &operator=(const grhip_constellation_obj &) = delete;
-    ~grhip_constellation_obj() { grhip_constellation_destroy(d_h); }
+    explicit grhip_constellation_obj(grhip_detail::constellation_handle &&h) : d_h(std::move(h)) {}
     const grhip_constellation *handle() const { return d_h; }
     std::vector<gr_complex> points() const
     {
@@ -1949,18 +1883,19 @@ public:
         return k;
     }
 };
+typedef boost::shared_ptr<grhip_constellation_obj> grhip_constellation_sptr;
 namespace grhip_detail {
-inline grhip_constellation_sptr constellation(int rc, grhip_constellation *h)
+inline grhip_constellation_sptr constellation(int rc, constellation_handle &h)
 {
     check(rc);
-    return grhip_constellation_sptr(new grhip_constellation_obj(h));
+    return grhip_constellation_sptr(new grhip_constellation_obj(std::move(h)));
 }
 }  // namespace grhip_detail
 #define GRHIP_CONSTELLATION_FIXED(KIND)                                                                                  \
     inline grhip_constellation_sptr digital_make_constellation_##KIND()                                                  \
     {                                                                                                                    \
-        grhip_constellation *h = nullptr;                                                                                \
-        const int rc = grhip_constellation_create_##KIND(&h);                                                            \
+        grhip_detail::constellation_handle h;                                                                            \
+        const int rc = grhip_constellation_create_##KIND(h.out());                                                       \
         return grhip_detail::constellation(rc, h);                                                                       \
     }
 GRHIP_CONSTELLATION_FIXED(bpsk)
@@ -1971,16 +1906,16 @@ GRHIP_CONSTELLATION_FIXED(8psk)
 inline grhip_constellation_sptr digital_make_constellation_calcdist(std::vector<gr_complex> constellation, std::vector<unsigned int> pre_diff_code,
                                                                     unsigned int rotational_symmetry, unsigned int dimensionality)
 {
-    grhip_constellation *h = nullptr;
-    const int rc = grhip_constellation_create_calcdist(&h, (const float *)constellation.data(), constellation.size(), pre_diff_code.data(),
+    grhip_detail::constellation_handle h;
+    const int rc = grhip_constellation_create_calcdist(h.out(), (const float *)constellation.data(), constellation.size(), pre_diff_code.data(),
                                                        pre_diff_code.size(), rotational_symmetry, dimensionality);
     return grhip_detail::constellation(rc, h);
 }
 inline grhip_constellation_sptr digital_make_constellation_psk(std::vector<gr_complex> constellation, std::vector<unsigned int> pre_diff_code,
                                                                unsigned int n_sectors)
 {
-    grhip_constellation *h = nullptr;
-    const int rc = grhip_constellation_create_psk(&h, (const float *)constellation.data(), constellation.size(), pre_diff_code.data(),
+    grhip_detail::constellation_handle h;
+    const int rc = grhip_constellation_create_psk(h.out(), (const float *)constellation.data(), constellation.size(), pre_diff_code.data(),
                                                   pre_diff_code.size(), n_sectors);
     return grhip_detail::constellation(rc, h);
 }
@@ -1988,29 +1923,25 @@ inline grhip_constellation_sptr digital_make_constellation_rect(std::vector<gr_c
                                                                 unsigned int rotational_symmetry, unsigned int real_sectors,
                                                                 unsigned int imag_sectors, float width_real_sectors, float width_imag_sectors)
 {
-    grhip_constellation *h = nullptr;
-    const int rc = grhip_constellation_create_rect(&h, (const float *)constellation.data(), constellation.size(), pre_diff_code.data(),
+    grhip_detail::constellation_handle h;
+    const int rc = grhip_constellation_create_rect(h.out(), (const float *)constellation.data(), constellation.size(), pre_diff_code.data(),
                                                    pre_diff_code.size(), rotational_symmetry, real_sectors, imag_sectors, width_real_sectors,
                                                    width_imag_sectors);
     return grhip_detail::constellation(rc, h);
 }
 
 // digital_constellation_decoder_cb.cc:39-78: a gr_block, `dimensionality` complex items per output byte
-class grhip_constellation_decoder_cb_blk;
-typedef boost::shared_ptr<grhip_constellation_decoder_cb_blk> grhip_constellation_decoder_cb_sptr;
-class grhip_constellation_decoder_cb_blk : public gr_block {
-    grhip_constellation_decoder_cb *d_h = nullptr;
+class grhip_constellation_decoder_cb_blk : public GRHIP_BLOCK_NO_MODE(gr_block, constellation_decoder_cb) {
+    friend struct grhip_detail::factory;
     unsigned d_dim;
     grhip_constellation_decoder_cb_blk(grhip_constellation_sptr c, int device)
-        : gr_block("constellation_decoder_cb", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(unsigned char))),
+        : block("constellation_decoder_cb", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(unsigned char))),
           d_dim(c->dimensionality())
     {
         set_relative_rate(1.0 / ((double)d_dim));
-        grhip_detail::check(grhip_constellation_decoder_cb_create(&d_h, c->handle(), device));
+        grhip_detail::check(grhip_constellation_decoder_cb_create(d_h.out(), c->handle(), device));
     }
-    friend grhip_constellation_decoder_cb_sptr digital_make_constellation_decoder_cb(grhip_constellation_sptr, int);
 public:
-    ~grhip_constellation_decoder_cb_blk() { grhip_constellation_decoder_cb_destroy(d_h); }
     void forecast(int noutput_items, gr_vector_int &req) override
     {
         for (size_t i = 0; i < req.size(); i++) req[i] = noutput_items * d_dim;
@@ -2022,76 +1953,68 @@ public:
         return noutput_items;
     }
 };
+typedef boost::shared_ptr<grhip_constellation_decoder_cb_blk> grhip_constellation_decoder_cb_sptr;
 inline grhip_constellation_decoder_cb_sptr digital_make_constellation_decoder_cb(grhip_constellation_sptr constellation, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_constellation_decoder_cb_blk(constellation, device));
+    return grhip_detail::factory::make<grhip_constellation_decoder_cb_blk>(constellation, device);
 }
 
 // gr_diff_decoder_bb.cc:36-61: a gr_sync_block with history 2.  in[0] is the byte in front of the first output's; the
 // handle keeps that byte itself (the last one of the call before, 0 at the start, which is what the scheduler's
 // history holds), so the work call hands it the items from in[1] on.
-class grhip_diff_decoder_bb_blk;
-typedef boost::shared_ptr<grhip_diff_decoder_bb_blk> grhip_diff_decoder_bb_sptr;
-class grhip_diff_decoder_bb_blk : public gr_sync_block {
-    grhip_diff_decoder_bb *d_h = nullptr;
+class grhip_diff_decoder_bb_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_block, diff_decoder_bb) {
+    friend struct grhip_detail::factory;
     grhip_diff_decoder_bb_blk(unsigned int modulus, int device)
-        : gr_sync_block("diff_decoder_bb", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(unsigned char)))
+        : block("diff_decoder_bb", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(unsigned char)))
     {
         set_history(2);
-        grhip_detail::check(grhip_diff_decoder_bb_create(&d_h, modulus, device));
+        grhip_detail::check(grhip_diff_decoder_bb_create(d_h.out(), modulus, device));
     }
-    friend grhip_diff_decoder_bb_sptr gr_make_diff_decoder_bb(unsigned int, int);
 public:
-    ~grhip_diff_decoder_bb_blk() { grhip_diff_decoder_bb_destroy(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         grhip_detail::check(grhip_diff_decoder_bb_work(d_h, noutput_items, (const unsigned char *)in[0] + 1, out[0]));
         return noutput_items;
     }
 };
+typedef boost::shared_ptr<grhip_diff_decoder_bb_blk> grhip_diff_decoder_bb_sptr;
 inline grhip_diff_decoder_bb_sptr gr_make_diff_decoder_bb(unsigned int modulus, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_diff_decoder_bb_blk(modulus, device));
+    return grhip_detail::factory::make<grhip_diff_decoder_bb_blk>(modulus, device);
 }
 
 // gr_map_bb.cc:36-60
-class grhip_map_bb_blk;
-typedef boost::shared_ptr<grhip_map_bb_blk> grhip_map_bb_sptr;
-class grhip_map_bb_blk : public gr_sync_block {
-    grhip_map_bb *d_h = nullptr;
+class grhip_map_bb_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_block, map_bb) {
+    friend struct grhip_detail::factory;
     grhip_map_bb_blk(const std::vector<int> &map, int device)
-        : gr_sync_block("map_bb", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(unsigned char)))
+        : block("map_bb", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(unsigned char)))
     {
-        grhip_detail::check(grhip_map_bb_create(&d_h, map.data(), map.size(), device));
+        grhip_detail::check(grhip_map_bb_create(d_h.out(), map.data(), map.size(), device));
     }
-    friend grhip_map_bb_sptr gr_make_map_bb(const std::vector<int> &, int);
 public:
-    ~grhip_map_bb_blk() { grhip_map_bb_destroy(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         grhip_detail::check(grhip_map_bb_work(d_h, noutput_items, in[0], out[0]));
         return noutput_items;
     }
 };
+typedef boost::shared_ptr<grhip_map_bb_blk> grhip_map_bb_sptr;
 inline grhip_map_bb_sptr gr_make_map_bb(const std::vector<int> &map, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_map_bb_blk(map, device));
+    return grhip_detail::factory::make<grhip_map_bb_blk>(map, device);
 }
 
 // digital_constellation_receiver_cb.cc:52-122: a gr_block with gri_control_loop's interface; outputs 2 .. 4 (error,
 // phase, frequency) are connected all three or not at all
-class grhip_constellation_receiver_cb_blk;
-typedef boost::shared_ptr<grhip_constellation_receiver_cb_blk> grhip_constellation_receiver_cb_sptr;
-class grhip_constellation_receiver_cb_blk : public gr_block {
-    grhip_constellation_receiver_cb *d_h = nullptr;
+class grhip_constellation_receiver_cb_blk : public GRHIP_LOOP_BLOCK(gr_block, constellation_receiver_cb) {
+    friend struct grhip_detail::factory;
     grhip_constellation_receiver_cb_blk(grhip_constellation_sptr c, float loop_bw, float fmin, float fmax, int device)
-        : gr_block("constellation_receiver_cb", gr_make_io_signature(1, 1, sizeof(gr_complex)),
-                   gr_make_io_signature2(1, 4, sizeof(char), sizeof(float)))                    // :50-56
+        : loop_block("constellation_receiver_cb", gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                     gr_make_io_signature2(1, 4, sizeof(char), sizeof(float)))                    // :50-56
     {
-        grhip_detail::check(grhip_constellation_receiver_cb_create(&d_h, c->handle(), loop_bw, fmin, fmax, device));
+        grhip_detail::check(grhip_constellation_receiver_cb_create(d_h.out(), c->handle(), loop_bw, fmin, fmax, device));
     }
-    friend grhip_constellation_receiver_cb_sptr digital_make_constellation_receiver_cb(grhip_constellation_sptr, float, float, float, int);
-GRHIP_LOOP_BLK_COMMON(constellation_receiver_cb)
+public:
     int form() const { return grhip_constellation_receiver_cb_form(d_h); }
     int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
@@ -2103,26 +2026,24 @@ GRHIP_LOOP_BLK_COMMON(constellation_receiver_cb)
         return n;
     }
 };
+typedef boost::shared_ptr<grhip_constellation_receiver_cb_blk> grhip_constellation_receiver_cb_sptr;
 inline grhip_constellation_receiver_cb_sptr digital_make_constellation_receiver_cb(grhip_constellation_sptr constellation, float loop_bw,
                                                                                    float fmin, float fmax, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_constellation_receiver_cb_blk(constellation, loop_bw, fmin, fmax, device));
+    return grhip_detail::factory::make<grhip_constellation_receiver_cb_blk>(constellation, loop_bw, fmin, fmax, device);
 }
 
 // the receiver, diff_decoder_bb(arity) if differential, map_bb(invert_code(pre_diff_code)) if gray_coded and the
 // constellation applies one, unpack_k_bits_bb(bits_per_symbol): bits_per_symbol bytes out per complex item in
-class grhip_constellation_demod_cb_blk;
-typedef boost::shared_ptr<grhip_constellation_demod_cb_blk> grhip_constellation_demod_cb_sptr;
-class grhip_constellation_demod_cb_blk : public gr_sync_interpolator {
-    grhip_constellation_demod_cb *d_h = nullptr;
+class grhip_constellation_demod_cb_blk : public GRHIP_LOOP_BLOCK(gr_sync_interpolator, constellation_demod_cb) {
+    friend struct grhip_detail::factory;
     grhip_constellation_demod_cb_blk(grhip_constellation_sptr c, float loop_bw, float fmin, float fmax, bool differential, bool gray_coded, int device)
-        : gr_sync_interpolator("constellation_demod_cb", gr_make_io_signature(1, 1, sizeof(gr_complex)),
-                               gr_make_io_signature(1, 1, sizeof(unsigned char)), std::max(1u, c->bits_per_symbol()))
+        : loop_block("constellation_demod_cb", gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                     gr_make_io_signature(1, 1, sizeof(unsigned char)), std::max(1u, c->bits_per_symbol()))
     {
-        grhip_detail::check(grhip_constellation_demod_cb_create(&d_h, c->handle(), loop_bw, fmin, fmax, differential, gray_coded, device));
+        grhip_detail::check(grhip_constellation_demod_cb_create(d_h.out(), c->handle(), loop_bw, fmin, fmax, differential, gray_coded, device));
     }
-    friend grhip_constellation_demod_cb_sptr grhip_make_constellation_demod_cb(grhip_constellation_sptr, float, float, float, bool, bool, int);
-GRHIP_LOOP_BLK_COMMON(constellation_demod_cb)
+public:
     int form() const { return grhip_constellation_demod_cb_form(d_h); }
     int engine() const { return grhip_constellation_demod_cb_engine(d_h); }
     void set_engine(int engine) { grhip_detail::check(grhip_constellation_demod_cb_set_engine(d_h, engine)); }
@@ -2132,32 +2053,28 @@ GRHIP_LOOP_BLK_COMMON(constellation_demod_cb)
         return noutput_items;
     }
 };
+typedef boost::shared_ptr<grhip_constellation_demod_cb_blk> grhip_constellation_demod_cb_sptr;
 inline grhip_constellation_demod_cb_sptr grhip_make_constellation_demod_cb(grhip_constellation_sptr constellation, float loop_bw, float fmin,
                                                                            float fmax, bool differential = true, bool gray_coded = true,
                                                                            int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_constellation_demod_cb_blk(constellation, loop_bw, fmin, fmax, differential, gray_coded, device));
+    return grhip_detail::factory::make<grhip_constellation_demod_cb_blk>(constellation, loop_bw, fmin, fmax, differential, gray_coded, device);
 }
-#undef GRHIP_LOOP_BLK_COMMON
+#undef GRHIP_LOOP_BLOCK
 
 // ---------------------------------------------------------------------------
 // gr_iir_filter_ffd (fftaps, fbtaps in double; filter/gr_iir_filter_ffd.h:62-85): a gr_sync_block, history 1, float in
 // and out.  set_taps is latched until the next work call, as the reference's is.  fm_deemph_taps and
 // gr_make_fm_deemph are blks2.fm_deemph (blks2impl/fm_emph.py:44-72), one gr_iir_filter_ffd.
 // ---------------------------------------------------------------------------
-class grhip_iir_filter_ffd_blk;
-typedef boost::shared_ptr<grhip_iir_filter_ffd_blk> grhip_iir_filter_ffd_sptr;
-class grhip_iir_filter_ffd_blk : public gr_sync_block {
-    grhip_iir_filter_ffd *d_h = nullptr;
+class grhip_iir_filter_ffd_blk : public GRHIP_BLOCK(gr_sync_block, iir_filter_ffd) {
+    friend struct grhip_detail::factory;
     grhip_iir_filter_ffd_blk(const std::vector<double> &fftaps, const std::vector<double> &fbtaps, int device)
-        : gr_sync_block("iir_filter_ffd", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(float)))
+        : block("iir_filter_ffd", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(float)))
     {
-        grhip_detail::check(grhip_iir_filter_ffd_create(&d_h, fftaps.data(), fftaps.size(), fbtaps.data(), fbtaps.size(), device));
+        grhip_detail::check(grhip_iir_filter_ffd_create(d_h.out(), fftaps.data(), fftaps.size(), fbtaps.data(), fbtaps.size(), device));
     }
-    friend grhip_iir_filter_ffd_sptr gr_make_iir_filter_ffd(const std::vector<double> &, const std::vector<double> &, int);
 public:
-    ~grhip_iir_filter_ffd_blk() { grhip_iir_filter_ffd_destroy(d_h); }
-    void set_mode(int mode) { grhip_detail::check(grhip_iir_filter_ffd_set_mode(d_h, mode)); }
     void set_taps(const std::vector<double> &fftaps, const std::vector<double> &fbtaps)
     {
         grhip_detail::check(grhip_iir_filter_ffd_set_taps(d_h, fftaps.data(), fftaps.size(), fbtaps.data(), fbtaps.size()));
@@ -2169,10 +2086,11 @@ public:
         return noutput_items;
     }
 };
+typedef boost::shared_ptr<grhip_iir_filter_ffd_blk> grhip_iir_filter_ffd_sptr;
 inline grhip_iir_filter_ffd_sptr gr_make_iir_filter_ffd(const std::vector<double> &fftaps, const std::vector<double> &fbtaps,
                                                         int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_iir_filter_ffd_blk(fftaps, fbtaps, device));
+    return grhip_detail::factory::make<grhip_iir_filter_ffd_blk>(fftaps, fbtaps, device);
 }
 
 // (btaps, ataps) of blks2.fm_deemph(fs, tau)
@@ -2206,23 +2124,17 @@ inline std::vector<float> grhip_firdes_low_pass_taps(double gain, double samplin
 // audio_decim, complex in and float out, history 1 (the handle takes new items only and keeps every inner block's
 // history itself).  gr_make_fm_demod_cf takes the audio taps as given; the presets below design them as the reference does.
 // ---------------------------------------------------------------------------
-class grhip_fm_demod_cf_blk;
-typedef boost::shared_ptr<grhip_fm_demod_cf_blk> grhip_fm_demod_cf_sptr;
-class grhip_fm_demod_cf_blk : public gr_sync_decimator {
-    grhip_fm_demod_cf *d_h = nullptr;
+class grhip_fm_demod_cf_blk : public GRHIP_BLOCK(gr_sync_decimator, fm_demod_cf) {
+    friend struct grhip_detail::factory;
     grhip_fm_demod_cf_blk(float k, const std::vector<double> &fftaps, const std::vector<double> &fbtaps, int audio_decim,
                           const std::vector<float> &audio_taps, int device)
-        : gr_sync_decimator("fm_demod_cf", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(float)),
-                            audio_decim < 1 ? 1u : (unsigned)audio_decim)
+        : block("fm_demod_cf", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(float)),
+                audio_decim < 1 ? 1u : (unsigned)audio_decim)
     {
-        grhip_detail::check(grhip_fm_demod_cf_create(&d_h, k, fftaps.data(), fftaps.size(), fbtaps.data(), fbtaps.size(), audio_decim,
+        grhip_detail::check(grhip_fm_demod_cf_create(d_h.out(), k, fftaps.data(), fftaps.size(), fbtaps.data(), fbtaps.size(), audio_decim,
                                                      audio_taps.data(), audio_taps.size(), device));
     }
-    friend grhip_fm_demod_cf_sptr grhip_make_fm_demod_cf(float, const std::vector<double> &, const std::vector<double> &, int,
-                                                         const std::vector<float> &, int);
 public:
-    ~grhip_fm_demod_cf_blk() { grhip_fm_demod_cf_destroy(d_h); }
-    void set_mode(int mode) { grhip_detail::check(grhip_fm_demod_cf_set_mode(d_h, mode)); }
     int engine() const { return grhip_fm_demod_cf_engine(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
@@ -2231,11 +2143,12 @@ public:
         return produced;
     }
 };
+typedef boost::shared_ptr<grhip_fm_demod_cf_blk> grhip_fm_demod_cf_sptr;
 // the chain on given taps: quadrature_demod_cf(k) -> iir_filter_ffd(fftaps, fbtaps) (both empty: none) -> fir_filter_fff
 inline grhip_fm_demod_cf_sptr grhip_make_fm_demod_cf(float k, const std::vector<double> &fftaps, const std::vector<double> &fbtaps,
                                                      int audio_decim, const std::vector<float> &audio_taps, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_fm_demod_cf_blk(k, fftaps, fbtaps, audio_decim, audio_taps, device));
+    return grhip_detail::factory::make<grhip_fm_demod_cf_blk>(k, fftaps, fbtaps, audio_decim, audio_taps, device);
 }
 // blks2.fm_demod_cf(channel_rate, audio_decim, deviation, ..., tau) on given audio taps; tau <= 0: no de-emphasis
 inline grhip_fm_demod_cf_sptr gr_make_fm_demod_cf(double channel_rate, int audio_decim, double deviation,
@@ -2295,22 +2208,17 @@ inline grhip_fm_demod_cf_sptr gr_make_demod_200kf3e_cf(double channel_rate, int 
 // blks2.am_demod_cf / blks2.demod_10k0a3e_cf (blks2impl/am_demod.py:42-76) as ONE block: a gr_sync_decimator by audio_decim,
 // complex in and float out, history 1 (the handle takes new items only and keeps the FIR's delay line itself).
 // ---------------------------------------------------------------------------
-class grhip_am_demod_cf_blk;
-typedef boost::shared_ptr<grhip_am_demod_cf_blk> grhip_am_demod_cf_sptr;
-class grhip_am_demod_cf_blk : public gr_sync_decimator {
-    grhip_am_demod_cf *d_h = nullptr;
+class grhip_am_demod_cf_blk : public GRHIP_BLOCK(gr_sync_decimator, am_demod_cf) {
+    friend struct grhip_detail::factory;
     std::vector<float> d_taps;
     grhip_am_demod_cf_blk(int audio_decim, const std::vector<float> &audio_taps, int device)
-        : gr_sync_decimator("am_demod_cf", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(float)),
-                            audio_decim < 1 ? 1u : (unsigned)audio_decim),
+        : block("am_demod_cf", gr_make_io_signature(1, 1, sizeof(gr_complex)), gr_make_io_signature(1, 1, sizeof(float)),
+                audio_decim < 1 ? 1u : (unsigned)audio_decim),
           d_taps(audio_taps)
     {
-        grhip_detail::check(grhip_am_demod_cf_create(&d_h, audio_decim, audio_taps.data(), audio_taps.size(), device));
+        grhip_detail::check(grhip_am_demod_cf_create(d_h.out(), audio_decim, audio_taps.data(), audio_taps.size(), device));
     }
-    friend grhip_am_demod_cf_sptr grhip_make_am_demod_cf(int, const std::vector<float> &, int);
 public:
-    ~grhip_am_demod_cf_blk() { grhip_am_demod_cf_destroy(d_h); }
-    void set_mode(int mode) { grhip_detail::check(grhip_am_demod_cf_set_mode(d_h, mode)); }
     int engine() const { return grhip_am_demod_cf_engine(d_h); }
     const std::vector<float> &audio_taps() const { return d_taps; }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
@@ -2320,10 +2228,11 @@ public:
         return produced;
     }
 };
+typedef boost::shared_ptr<grhip_am_demod_cf_blk> grhip_am_demod_cf_sptr;
 // the chain on given taps: complex_to_mag -> add_const_ff(-1) -> fir_filter_fff(audio_decim, audio_taps)
 inline grhip_am_demod_cf_sptr grhip_make_am_demod_cf(int audio_decim, const std::vector<float> &audio_taps, int device = 0)
 {
-    return gnuradio::get_initial_sptr(new grhip_am_demod_cf_blk(audio_decim, audio_taps, device));
+    return grhip_detail::factory::make<grhip_am_demod_cf_blk>(audio_decim, audio_taps, device);
 }
 // blks2.am_demod_cf(channel_rate, audio_decim, audio_pass, audio_stop)
 inline grhip_am_demod_cf_sptr gr_make_am_demod_cf(double channel_rate, int audio_decim, double audio_pass, double audio_stop,

@@ -19,32 +19,50 @@
 #pragma once
 #include "grhip_blocks.h"
 
+// one gr_fir_XXX over a fir_filter handle of decimation 1; set_taps makes a new handle
+template <class BASE, class I, class O, class TAP> class grhip_fir_kernel : public BASE {
+    grhip_detail::handle<grhip_fir_filter, grhip_fir_filter_destroy> d_h;
+    const char *d_kind;
+    int d_device;
+    void rebuild()
+    {
+        const std::vector<TAP> fwd = this->get_taps();
+        grhip_detail::check(grhip_fir_filter_create(d_h.out(), d_kind, 1, (const float *)fwd.data(), fwd.size(), d_device));
+    }
+protected:
+    grhip_fir_kernel(const char *kind, const std::vector<TAP> &taps, int device) : BASE(taps), d_kind(kind), d_device(device)
+    {
+        rebuild();
+    }
+public:
+    O filter(const I input[]) override
+    {
+        O y = O();
+        filterNdec(&y, input, 1, 1);
+        return y;
+    }
+    void filterN(O output[], const I input[], unsigned long n) override { filterNdec(output, input, n, 1); }
+    void filterNdec(O output[], const I input[], unsigned long n, unsigned decimate) override
+    {
+        if (n == 0) return;
+        if (this->ntaps() == 0) {
+            for (unsigned long i = 0; i < n; ++i) output[i] = O();
+            return;
+        }
+        grhip_detail::check(grhip_fir_filterNdec(d_h, output, input, n, decimate));
+    }
+    void set_taps(const std::vector<TAP> &taps) override
+    {
+        BASE::set_taps(taps);
+        rebuild();
+    }
+    // numeric mode of the underlying handle (GRHIP_MODE_*)
+    void set_mode(int mode) { grhip_detail::check(grhip_fir_filter_set_mode(d_h, mode)); }
+};
 #define GRHIP_FIR_IMPL(NAME, BASE, KIND, I, O, TAP)                                                              \
-    class NAME : public BASE {                                                                                   \
-        grhip_fir_filter *d_h = nullptr;                                                                         \
-        int d_device;                                                                                            \
-        void rebuild()                                                                                           \
-        {                                                                                                        \
-            if (d_h) grhip_fir_filter_destroy(d_h);                                                              \
-            d_h = nullptr;                                                                                       \
-            const std::vector<TAP> fwd = get_taps();                                                             \
-            grhip_detail::check(grhip_fir_filter_create(&d_h, KIND, 1, (const float *)fwd.data(), fwd.size(),    \
-                                                        d_device));                                              \
-        }                                                                                                        \
+    class NAME : public grhip_fir_kernel<BASE, I, O, TAP> {                                                      \
     public:                                                                                                      \
-        NAME(const std::vector<TAP> &taps, int device = 0) : BASE(taps), d_device(device) { rebuild(); }         \
-        ~NAME() { if (d_h) grhip_fir_filter_destroy(d_h); }                                                      \
-        O filter(const I input[]) override { O y = O(); filterNdec(&y, input, 1, 1); return y; }                 \
-        void filterN(O output[], const I input[], unsigned long n) override { filterNdec(output, input, n, 1); } \
-        void filterNdec(O output[], const I input[], unsigned long n, unsigned decimate) override                \
-        {                                                                                                        \
-            if (n == 0) return;                                                                                  \
-            if (ntaps() == 0) { for (unsigned long i = 0; i < n; ++i) output[i] = O(); return; }                 \
-            grhip_detail::check(grhip_fir_filterNdec(d_h, output, input, n, decimate));                          \
-        }                                                                                                        \
-        void set_taps(const std::vector<TAP> &taps) override { BASE::set_taps(taps); rebuild(); }                \
-        /* numeric mode of the underlying handle (GRHIP_MODE_*) */                                               \
-        void set_mode(int mode) { grhip_detail::check(grhip_fir_filter_set_mode(d_h, mode)); }                   \
+        NAME(const std::vector<TAP> &taps, int device = 0) : grhip_fir_kernel(KIND, taps, device) {}             \
     };
 GRHIP_FIR_IMPL(gr_fir_ccf_hip, gr_fir_ccf, "ccf", gr_complex, gr_complex, float)
 GRHIP_FIR_IMPL(gr_fir_fff_hip, gr_fir_fff, "fff", float, float, float)
@@ -52,6 +70,7 @@ GRHIP_FIR_IMPL(gr_fir_ccc_hip, gr_fir_ccc, "ccc", gr_complex, gr_complex, gr_com
 GRHIP_FIR_IMPL(gr_fir_fcc_hip, gr_fir_fcc, "fcc", float, gr_complex, gr_complex)
 GRHIP_FIR_IMPL(gr_fir_scc_hip, gr_fir_scc, "scc", short, gr_complex, gr_complex)
 GRHIP_FIR_IMPL(gr_fir_fsf_hip, gr_fir_fsf, "fsf", float, short, float)
+#undef GRHIP_FIR_IMPL
 
 // what a platform's gr_fir_sysconfig does for its implementations (filter/gr_fir_sysconfig_x86.cc:175-201, 260-300):
 // create_gr_fir_XXX picks the best one, get_gr_fir_XXX_info APPENDS to the table the base class started
@@ -91,33 +110,29 @@ struct grhip_fir_sysconfig {
 // ---------------------------------------------------------------------------
 // N-port adapters
 // ---------------------------------------------------------------------------
-class grhip_stream_to_streams_blk : public gr_sync_decimator {       // general/gr_stream_to_streams.cc:32-66
-    grhip_stream_adapter *d_h = nullptr;
+class grhip_stream_to_streams_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_decimator, stream_adapter) {   // general/gr_stream_to_streams.cc:32-66
 public:
     grhip_stream_to_streams_blk(size_t item_size, size_t nstreams, int device = 0)
-        : gr_sync_decimator("stream_to_streams", gr_make_io_signature(1, 1, item_size),
-                            gr_make_io_signature(nstreams, nstreams, item_size), nstreams)
+        : block("stream_to_streams", gr_make_io_signature(1, 1, item_size), gr_make_io_signature(nstreams, nstreams, item_size),
+                nstreams)
     {
-        grhip_detail::check(grhip_stream_adapter_create(&d_h, 1, item_size, nstreams, device));
+        grhip_detail::check(grhip_stream_adapter_create(d_h.out(), 1, item_size, nstreams, device));
     }
-    ~grhip_stream_to_streams_blk() { grhip_stream_adapter_destroy(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         grhip_detail::check(grhip_stream_adapter_work(d_h, noutput_items, const_cast<void *>(in[0]), out.data()));
         return noutput_items;
     }
 };
-class grhip_streams_to_stream_blk : public gr_sync_interpolator {    // general/gr_streams_to_stream.cc:32-69
-    grhip_stream_adapter *d_h = nullptr;
+class grhip_streams_to_stream_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_interpolator, stream_adapter) {   // general/gr_streams_to_stream.cc:32-69
     size_t d_n;
 public:
     grhip_streams_to_stream_blk(size_t item_size, size_t nstreams, int device = 0)
-        : gr_sync_interpolator("streams_to_stream", gr_make_io_signature(nstreams, nstreams, item_size),
-                               gr_make_io_signature(1, 1, item_size), nstreams), d_n(nstreams)
+        : block("streams_to_stream", gr_make_io_signature(nstreams, nstreams, item_size), gr_make_io_signature(1, 1, item_size),
+                nstreams), d_n(nstreams)
     {
-        grhip_detail::check(grhip_stream_adapter_create(&d_h, 0, item_size, nstreams, device));
+        grhip_detail::check(grhip_stream_adapter_create(d_h.out(), 0, item_size, nstreams, device));
     }
-    ~grhip_streams_to_stream_blk() { grhip_stream_adapter_destroy(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         std::vector<void *> ins(in.size());
@@ -126,54 +141,45 @@ public:
         return noutput_items;
     }
 };
-class grhip_vector_to_streams_blk : public gr_sync_block {           // general/gr_vector_to_streams.cc:31-70
-    grhip_stream_adapter *d_h = nullptr;
+class grhip_vector_to_streams_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_block, stream_adapter) {   // general/gr_vector_to_streams.cc:31-70
 public:
     grhip_vector_to_streams_blk(size_t item_size, size_t nstreams, int device = 0)
-        : gr_sync_block("vector_to_streams", gr_make_io_signature(1, 1, nstreams * item_size),
-                        gr_make_io_signature(nstreams, nstreams, item_size))
+        : block("vector_to_streams", gr_make_io_signature(1, 1, nstreams * item_size),
+                gr_make_io_signature(nstreams, nstreams, item_size))
     {
-        grhip_detail::check(grhip_stream_adapter_create(&d_h, 1, item_size, nstreams, device));
+        grhip_detail::check(grhip_stream_adapter_create(d_h.out(), 1, item_size, nstreams, device));
     }
-    ~grhip_vector_to_streams_blk() { grhip_stream_adapter_destroy(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         grhip_detail::check(grhip_stream_adapter_work(d_h, noutput_items, const_cast<void *>(in[0]), out.data()));
         return noutput_items;
     }
 };
-class grhip_stream_to_vector_blk : public gr_sync_decimator {        // general/gr_stream_to_vector.cc:31-60
-    grhip_copy_adapter *d_h = nullptr;
+class grhip_stream_to_vector_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_decimator, copy_adapter) {   // general/gr_stream_to_vector.cc:31-60
 public:
     grhip_stream_to_vector_blk(size_t item_size, size_t nitems_per_block, int device = 0)
-        : gr_sync_decimator("stream_to_vector", gr_make_io_signature(1, 1, item_size),
-                            gr_make_io_signature(1, 1, item_size * nitems_per_block), nitems_per_block)
+        : block("stream_to_vector", gr_make_io_signature(1, 1, item_size), gr_make_io_signature(1, 1, item_size * nitems_per_block),
+                nitems_per_block)
     {
-        grhip_detail::check(grhip_stream_to_vector_create(&d_h, item_size, nitems_per_block, device));
+        grhip_detail::check(grhip_stream_to_vector_create(d_h.out(), item_size, nitems_per_block, device));
     }
-    ~grhip_stream_to_vector_blk() { grhip_copy_adapter_destroy(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_copy_adapter_work(d_h, noutput_items, in[0], out[0]);
-        grhip_detail::check(r);
-        return r;
+        return checked(grhip_copy_adapter_work(d_h, noutput_items, in[0], out[0]));
     }
 };
-class grhip_head_blk : public gr_sync_block {                        // general/gr_head.cc:31-62
-    grhip_copy_adapter *d_h = nullptr;
+class grhip_head_blk : public GRHIP_BLOCK_NO_MODE(gr_sync_block, copy_adapter) {   // general/gr_head.cc:31-62
 public:
     grhip_head_blk(size_t sizeof_stream_item, unsigned long long nitems, int device = 0)
-        : gr_sync_block("head", gr_make_io_signature(1, 1, sizeof_stream_item), gr_make_io_signature(1, 1, sizeof_stream_item))
+        : block("head", gr_make_io_signature(1, 1, sizeof_stream_item), gr_make_io_signature(1, 1, sizeof_stream_item))
     {
-        grhip_detail::check(grhip_head_create(&d_h, sizeof_stream_item, nitems, device));
+        grhip_detail::check(grhip_head_create(d_h.out(), sizeof_stream_item, nitems, device));
     }
-    ~grhip_head_blk() { grhip_copy_adapter_destroy(d_h); }
     void reset() { grhip_detail::check(grhip_head_reset(d_h)); }       // gr_head.h:51
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        int r = grhip_copy_adapter_work(d_h, noutput_items, in[0], out[0]);
-        grhip_detail::check(r);
+        int r = checked(grhip_copy_adapter_work(d_h, noutput_items, in[0], out[0]));
         return r == GRHIP_WORK_DONE ? -1 : r;                           // WORK_DONE is -1 in gr_block.h:63-66
     }
 };
-template <class B, class... A> inline boost::shared_ptr<B> grhip_make_adapter(A... a) { return gnuradio::get_initial_sptr(new B(a...)); }
+template <class B, class... A> inline boost::shared_ptr<B> grhip_make_adapter(A... a) { return grhip_detail::factory::make<B>(a...); }
