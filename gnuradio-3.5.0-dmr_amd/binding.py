@@ -33,6 +33,8 @@ __all__ = [
     "constellation_calcdist", "constellation_psk", "constellation_rect", "psk_constellation", "qam_constellation",
     "gray_code", "invert_code", "constellation_decoder_cb", "diff_decoder_bb", "map_bb", "constellation_receiver_cb",
     "constellation_demod_cb",
+    "packed_to_unpacked_bb", "unpacked_to_packed_bb", "GR_MSB_FIRST", "GR_LSB_FIRST", "diff_encoder_bb", "chunks_to_symbols_bc",
+    "generic_mod", "psk_mod", "qam_mod", "bpsk_mod", "dbpsk_mod", "qpsk_mod", "dqpsk_mod",
     "iir_filter_ffd", "fm_deemph", "fm_deemph_taps", "firdes_low_pass", "fm_demod_cf", "nbfm_rx",
     "remez", "optfir_low_pass", "optfir_high_pass", "optfir_band_pass", "optfir_band_reject", "optfir_spec",
     "complex_to_mag", "am_demod_cf", "demod_10k0a3e_cf", "demod_20k0f3e_cf", "demod_200kf3e_cf",
@@ -2307,6 +2309,210 @@ class constellation_demod_cb(_control_loop):
         out = np.zeros(max(m, 1), dtype=np.uint8)
         self._call("work", int(n_in), _ptr(x), _ptr(out))
         return out[:m]
+
+
+# ----------------------------------------------------------------------------
+# the blocks in front of generic_mod's pulse shaper (gengen/gr_packed_to_unpacked_XX.i.t, gr_unpacked_to_packed_XX.i.t,
+# gr_chunks_to_symbols_XX.i.t, gengen/gr_endianness.h, general/gr_diff_encoder_bb.i,
+# gr-digital/python/generic_mod_demod.py:114-150)
+# ----------------------------------------------------------------------------
+GR_MSB_FIRST = 0
+GR_LSB_FIRST = 1
+
+
+class _pack_block(_Block):
+    """a gr_block that repacks bits: streams x ninput bytes back to back in, streams x noutput_items bytes out; the
+    bit index it keeps between calls is one value for all streams"""
+
+    def __init__(self, bits_per_chunk, endianness=GR_MSB_FIRST, device=0):
+        _Block.__init__(self)
+        self._create(int(bits_per_chunk), int(endianness), int(device))
+
+    def history(self):
+        return 1
+
+    def forecast(self, noutput_items):
+        return self._call("forecast", int(noutput_items))
+
+    def general_work(self, noutput_items, input_items, ninput_items=None):
+        """returns (out, consumed); input_items holds streams x ninput_items bytes (all of it by default)"""
+        x = np.ascontiguousarray(input_items, dtype=np.uint8).reshape(-1)
+        if ninput_items is None:
+            ninput_items = len(x) // self._streams
+        if len(x) < ninput_items * self._streams:
+            raise ValueError("general_work needs %d items, got %d" % (ninput_items * self._streams, len(x)))
+        out = np.zeros(max(int(noutput_items) * self._streams, 1), dtype=np.uint8)
+        consumed = C.c_int(0)
+        n = self._call("general_work", int(noutput_items), int(ninput_items), _ptr(x), _ptr(out), C.byref(consumed))
+        return out[:n * self._streams].copy(), consumed.value
+
+    def general_work_device(self, noutput_items, ninput_items, d_in, d_out, stream=None):
+        """returns (produced, consumed), known at once; the outputs are in d_out once `stream` has run"""
+        consumed = C.c_int(0)
+        n = self._call("general_work_device", int(noutput_items), int(ninput_items), _devptr(d_in), _devptr(d_out),
+                       C.byref(consumed), _stream(stream))
+        return n, consumed.value
+
+
+class packed_to_unpacked_bb(_pack_block):
+    """gr.packed_to_unpacked_bb(bits_per_chunk, endianness): chunk i is the bits_per_chunk bits from bit
+    d_index + i * bits_per_chunk of the bytes, the first one its most significant (also for GR_LSB_FIRST, which takes
+    a byte's bits from the bottom)"""
+    _name = "packed_to_unpacked_bb"
+
+
+class unpacked_to_packed_bb(_pack_block):
+    """gr.unpacked_to_packed_bb(bits_per_chunk, endianness): the inverse; the low bits_per_chunk bits of the input
+    bytes, laid end to end, in bytes"""
+    _name = "unpacked_to_packed_bb"
+
+
+class diff_encoder_bb(_byte_block):
+    """gr.diff_encoder_bb(modulus): out[i] = (in[i] + out[i-1]) % modulus stored as a byte; the last output is kept
+    per stream (0 at the start)"""
+    _name = "diff_encoder_bb"
+
+    def __init__(self, modulus, device=0):
+        _Block.__init__(self)
+        self._create(int(modulus), int(device))
+
+
+class chunks_to_symbols_bc(_Block):
+    """gr.chunks_to_symbols_bc(symbol_table, D=1): n bytes in, n * D complex items out per stream,
+    symbol_table[in * D : in * D + D]; an index outside the table gives zeros"""
+    _name = "chunks_to_symbols_bc"
+
+    def __init__(self, symbol_table, D=1, device=0):
+        _Block.__init__(self)
+        t, pt, n = _points(symbol_table)            # t owns the memory until the call returns
+        self._create(pt, n, int(D), int(device))
+
+    def history(self):
+        return 1
+
+    def D(self):
+        return self._call("D")
+
+    def work(self, input_items, n=None):
+        x = np.ascontiguousarray(input_items, dtype=np.uint8).reshape(-1)
+        if n is None:
+            n = len(x) // self._streams
+        if len(x) < n * self._streams:
+            raise ValueError("work needs %d items, got %d" % (n * self._streams, len(x)))
+        m = n * self._streams * self.D()
+        out = np.zeros(max(m, 1), dtype=np.complex64)
+        self._call("work", int(n), _ptr(x), _ptr(out))
+        return out[:m]
+
+
+class generic_mod(_Block):
+    """digital.generic_mod (generic_mod_demod.py:76-157) as one block: packed_to_unpacked_bb(bits_per_symbol, MSB_FIRST)
+    -> map_bb(pre_diff_code) if gray_coded -> diff_encoder_bb(2^bits_per_symbol) if differential ->
+    chunks_to_symbols_bc(points) -> pfb_arb_resampler_ccf(samples_per_symbol, root raised cosine, 32).  work(bytes)
+    takes NEW bytes only, streams x n_bytes back to back, and returns the samples they complete, streams x produced;
+    the output depends on the concatenated input alone.  engine() 1 (the default) is the fused kernel, 0 runs the
+    blocks in a row; MODE_GENERIC is the reference bit for bit in both."""
+    _name = "generic_mod"
+
+    def __init__(self, constellation, samples_per_symbol=2, differential=True, excess_bw=0.35, gray_coded=True, device=0):
+        _Block.__init__(self)
+        self._create(constellation.base()._h, float(samples_per_symbol), int(bool(differential)), float(excess_bw),
+                     int(bool(gray_coded)), int(device))
+
+    def engine(self):
+        return self._call("engine")
+
+    def set_engine(self, engine):
+        self._call("set_engine", int(engine))
+
+    def bits_per_symbol(self):
+        return self._call("bits_per_symbol")
+
+    def samples_per_symbol(self):
+        return self._fn("samples_per_symbol")(self._h)          # the float itself, not a status
+
+    def ntaps(self):
+        return self._call("ntaps")
+
+    def taps(self):
+        t = np.zeros(self.ntaps(), np.float32)
+        self._call("taps", _ptr(t), len(t))
+        return t
+
+    def max_produced(self, n_bytes):
+        """the items per stream that the next work call of n_bytes produces"""
+        return self._call("max_produced", int(n_bytes))
+
+    def work(self, input_items, n_bytes=None):
+        x = np.ascontiguousarray(input_items, dtype=np.uint8).reshape(-1)
+        if n_bytes is None:
+            n_bytes = len(x) // self._streams
+        if len(x) < n_bytes * self._streams:
+            raise ValueError("work needs %d items, got %d" % (n_bytes * self._streams, len(x)))
+        cap = self.max_produced(n_bytes)
+        out = np.zeros(max(cap * self._streams, 1), dtype=np.complex64)
+        produced = C.c_longlong(0)
+        self._call("work", int(n_bytes), _ptr(x), _ptr(out), cap, C.byref(produced))
+        return out[:produced.value * self._streams]
+
+    def work_device(self, n_bytes, d_in, d_out, out_stride_items, out_capacity, stream=None):
+        """device buffers, queued on `stream`; returns the items produced per stream, known at once"""
+        produced = C.c_longlong(0)
+        self._call("work_device", int(n_bytes), _devptr(d_in), _devptr(d_out), int(out_stride_items), int(out_capacity),
+                   C.byref(produced), _stream(stream))
+        return produced.value
+
+
+class psk_mod(generic_mod):
+    """digital.psk_mod (psk.py:76-93)"""
+
+    def __init__(self, constellation_points=4, mod_code="gray", **kw):
+        generic_mod.__init__(self, psk_constellation(constellation_points, mod_code), **kw)
+
+
+class qam_mod(generic_mod):
+    """digital.qam_mod (qam.py:176-196): the Gray coding is in the constellation; differential is forwarded"""
+
+    def __init__(self, constellation_points=16, differential=True, mod_code="none", **kw):
+        generic_mod.__init__(self, qam_constellation(constellation_points, differential, mod_code), differential=differential, **kw)
+
+
+class bpsk_mod(generic_mod):
+    """digital.bpsk_mod (bpsk.py:52-71)"""
+
+    def __init__(self, constellation_points=2, differential=False, **kw):
+        if constellation_points != 2:
+            raise ValueError("Number of constellation points must be 2 for BPSK.")
+        generic_mod.__init__(self, constellation_bpsk(), differential=differential, **kw)
+
+
+class dbpsk_mod(generic_mod):
+    """digital.dbpsk_mod (bpsk.py:114-135): differential is forced"""
+
+    def __init__(self, constellation_points=2, differential=True, **kw):
+        if constellation_points != 2:
+            raise ValueError("Number of constellation points must be 2 for DBPSK.")
+        generic_mod.__init__(self, constellation_bpsk(), differential=True, **kw)
+
+
+class qpsk_mod(generic_mod):
+    """digital.qpsk_mod (qpsk.py:51-75)"""
+
+    def __init__(self, constellation_points=4, gray_coded=True, **kw):
+        if constellation_points != 4:
+            raise ValueError("QPSK can only have 4 constellation points.")
+        if not gray_coded:
+            raise ValueError("This QPSK mod/demod works only for gray-coded constellations.")
+        generic_mod.__init__(self, constellation_qpsk(), gray_coded=gray_coded, **kw)
+
+
+class dqpsk_mod(generic_mod):
+    """digital.dqpsk_mod (qpsk.py:118-141): differential is forced"""
+
+    def __init__(self, constellation_points=4, gray_coded=True, differential=True, **kw):
+        if constellation_points != 4:
+            raise ValueError("Number of constellation points must be 4 for DQPSK.")
+        generic_mod.__init__(self, constellation_dqpsk(), gray_coded=gray_coded, differential=True, **kw)
 
 
 # ----------------------------------------------------------------------------

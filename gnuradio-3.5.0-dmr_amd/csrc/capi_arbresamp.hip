@@ -37,14 +37,8 @@ struct grhip_pfb_arb_resampler_base : SchedBlock<grhip_pfb_arb_resampler_base> {
     // sized to it, not to the cap, so short spans leave room for more workgroups per CU
     int tile_for(const ArbPlan &p, int *span) const
     {
-        const long long cap = span_cap(), R = rp.R;
-        if (p.closed) {
-            // pos_k - pos_0 <= k*(D+1) and pos_0 % R < R: count_k - count_0 <= (R-1 + k*(D+1)) / R
-            const long long t = 1 + (cap - (long long)tpf) * R / ((long long)p.D + 1);
-            const int tile = (int)std::min<long long>(ARB_MAX_TILE, std::max<long long>(1, t));
-            *span = (int)((R - 1 + (long long)(tile - 1) * ((long long)p.D + 1)) / R + tpf);
-            return tile;
-        }
+        const long long cap = span_cap();
+        if (p.closed) return arb_closed_tile(rp.R, p.D, tpf, cap, ARB_MAX_TILE, span);
         return walked_tile(p.steps.size(), ARB_MAX_TILE, tpf, cap, [&](size_t k) { return p.steps[k].count; }, span);
     }
 
@@ -84,19 +78,7 @@ struct grhip_pfb_arb_resampler_base : SchedBlock<grhip_pfb_arb_resampler_base> {
         int rc = init_device(device);
         if (rc) return rc;
         mode = default_mode();
-        // create_diff_taps (.cc:130-138), then create_taps (.cc:93-124) for both banks: filter i gets
-        // proto[i + t*R], zero padded to R*tpf, reversed by gr_fir_XXX::set_taps
-        std::vector<float> proto((size_t)R * tpf, 0.f), diff((size_t)R * tpf, 0.f);
-        for (size_t i = 0; i < ntaps; ++i) proto[i] = taps[i];
-        for (size_t i = 0; i + 1 < ntaps; ++i) diff[i] = taps[i + 1] - taps[i];
-        diff[ntaps - 1] = diff[ntaps - 2];
-        std::vector<float> pairs(2 * (size_t)R * S, 0.f);
-        for (unsigned i = 0; i < R; ++i)
-            for (unsigned k = 0; k < tpf; ++k) {
-                const size_t src = i + (size_t)(tpf - 1 - k) * R;
-                pairs[2 * ((size_t)i * S + k)] = proto[src];
-                pairs[2 * ((size_t)i * S + k) + 1] = diff[src];
-            }
+        const std::vector<float> pairs = arb_tap_pairs(taps, ntaps, R, tpf, S);        // sched_plan.h
         if ((rc = d_taps.reserve(pairs.size() * 4))) return rc;
         GRHIP_HIP(hipMemcpy(d_taps.p, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice));
         return GRHIP_OK;

@@ -16,10 +16,6 @@
 
 using namespace grhip;
 
-struct grhip_constellation {
-    Constellation c;
-};
-
 namespace {
 
 // a constellation's tables on the device: points | angles | sector values

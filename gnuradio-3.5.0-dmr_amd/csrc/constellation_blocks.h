@@ -7,6 +7,11 @@
 #include "constellation.h"
 #include "grhip_internal.h"
 
+// the constellation handle of the C ABI (csrc/capi_constellation.hip makes them; the blocks copy what they are given)
+struct grhip_constellation {
+    grhip::Constellation c;
+};
+
 namespace grhip {
 
 // how the receiver's walk forms decision and error

@@ -208,6 +208,35 @@ inline ArbPlan arb_plan(const ArbState &s, const ArbRate &r, long long max_input
     return p;
 }
 
+// Closed-form schedule: the largest tile (at most max_tile outputs) whose input span fits `cap` LDS items, and the span
+// that tile needs at most.  pos_k - pos_0 <= k*(D+1) and pos_0 % R < R: count_k - count_0 <= (R-1 + k*(D+1)) / R.
+inline int arb_closed_tile(unsigned R, unsigned D, unsigned tpf, long long cap, int max_tile, int *span)
+{
+    const long long t = 1 + (cap - (long long)tpf) * R / ((long long)D + 1);
+    const int tile = (int)std::min<long long>(max_tile, std::max<long long>(1, t));
+    *span = (int)(((long long)R - 1 + (long long)(tile - 1) * ((long long)D + 1)) / R + tpf);
+    return tile;
+}
+
+// create_diff_taps (.cc:130-138), then create_taps (.cc:93-124) for both banks, as the kernel reads them: R rows of S
+// (h, dh) pairs, S >= tpf, filter i's taps proto[i + t*R] zero padded to R*tpf and reversed as gr_fir_XXX::set_taps
+// stores them.  ntaps >= 2.
+inline std::vector<float> arb_tap_pairs(const float *taps, size_t ntaps, unsigned R, unsigned tpf, unsigned S)
+{
+    std::vector<float> proto((size_t)R * tpf, 0.f), diff((size_t)R * tpf, 0.f);
+    for (size_t i = 0; i < ntaps; ++i) proto[i] = taps[i];
+    for (size_t i = 0; i + 1 < ntaps; ++i) diff[i] = taps[i + 1] - taps[i];
+    diff[ntaps - 1] = diff[ntaps - 2];
+    std::vector<float> pairs(2 * (size_t)R * S, 0.f);
+    for (unsigned i = 0; i < R; ++i)
+        for (unsigned k = 0; k < tpf; ++k) {
+            const size_t src = i + (size_t)(tpf - 1 - k) * R;
+            pairs[2 * ((size_t)i * S + k)] = proto[src];
+            pairs[2 * ((size_t)i * S + k) + 1] = diff[src];
+        }
+    return pairs;
+}
+
 // the state the next call starts from and what this one consumed (.cc:204-207)
 inline ArbState arb_carry(const ArbState &end, long long ninput, int *consumed)
 {

@@ -7,6 +7,7 @@
 //   gr_sync_decimator   gnuradio-core/src/lib/runtime/gr_sync_decimator.cc:38-68
 //   gr_sync_interpolator gnuradio-core/src/lib/runtime/gr_sync_interpolator.cc:30-75
 //   gr_io_signature     gnuradio-core/src/lib/runtime/gr_io_signature.h
+//   gr_endianness_t     gnuradio-core/src/lib/gengen/gr_endianness.h:25
 //   gr_message / gr_msg_queue  gnuradio-core/src/lib/runtime/gr_message.h:36-81, gr_msg_queue.h:36-86
 //   gr_fir_{ccf,fff,ccc,fcc,scc,fsf}, gr_fir_XXX_info   gnuradio-core/src/lib/filter/gr_fir_XXX.h.t:48-122,
 //                                           filter/generate_gr_fir_util.py:25-32 (the kernel-level seam)
@@ -25,6 +26,7 @@
 #include <gr_fir_scc.h>
 #include <gr_fir_util.h>
 #include <gr_block.h>
+#include <gr_endianness.h>
 #include <gr_io_signature.h>
 #include <gr_message.h>
 #include <gr_msg_queue.h>
@@ -46,6 +48,7 @@ typedef std::complex<float> gr_complex;
 typedef std::vector<int> gr_vector_int;
 typedef std::vector<const void *> gr_vector_const_void_star;
 typedef std::vector<void *> gr_vector_void_star;
+typedef enum { GR_MSB_FIRST, GR_LSB_FIRST } gr_endianness_t;       // gengen/gr_endianness.h:25
 
 namespace boost {
 // the reference hands blocks around as boost::shared_ptr

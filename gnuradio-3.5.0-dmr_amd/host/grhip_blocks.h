@@ -42,6 +42,11 @@
 //                                            <- the factories of the same names (gr-digital/include/digital_constellation*.h,
 //                                               general/gr_diff_decoder_bb.h, gr_map_bb.h); grhip_make_constellation_demod_cb
 //                                               is generic_demod's tail behind timing recovery (generic_mod_demod.py:296-313)
+//   grhip_make_packed_to_unpacked_bb / _unpacked_to_packed_bb, grhip_make_diff_encoder_bb, grhip_make_chunks_to_symbols_bc
+//                                            <- gr_make_packed_to_unpacked_bb, gr_make_unpacked_to_packed_bb, gr_make_diff_encoder_bb,
+//                                               gr_make_chunks_to_symbols_bc (gengen/gr_*_XX.h.t, general/gr_diff_encoder_bb.h), the
+//                                               same arguments; grhip_make_generic_mod is digital.generic_mod
+//                                               (generic_mod_demod.py:76-157) as one block
 //   gr_make_agc_cc / _ff, gr_make_agc2_cc / _ff
 //                                            <- the factories of the same names (general/gr_agc_cc.h, gr_agc_ff.h,
 //                                               gr_agc2_cc.h, gr_agc2_ff.h)
@@ -2061,6 +2066,160 @@ inline grhip_constellation_demod_cb_sptr grhip_make_constellation_demod_cb(grhip
     return grhip_detail::factory::make<grhip_constellation_demod_cb_blk>(constellation, loop_bw, fmin, fmax, differential, gray_coded, device);
 }
 #undef GRHIP_LOOP_BLOCK
+
+// ---------------------------------------------------------------------------
+// The modulator: gr_packed_to_unpacked_bb / gr_unpacked_to_packed_bb (bits_per_chunk, endianness;
+// gengen/gr_packed_to_unpacked_XX.h.t, gr_unpacked_to_packed_XX.h.t: gr_blocks with their own forecast),
+// gr_diff_encoder_bb (modulus; general/gr_diff_encoder_bb.h: a gr_sync_block), gr_chunks_to_symbols_bc (symbol_table,
+// D = 1; gengen/gr_chunks_to_symbols_XX.h.t: a gr_sync_interpolator by D) and generic_mod
+// (gr-digital/python/generic_mod_demod.py:76-157) as one gr_block.  One stream each.
+// ---------------------------------------------------------------------------
+template <class T>
+class grhip_repack_bb_blk : public grhip_detail::block<gr_block, typename T::H, T::destroy, T::set_mode> {
+    friend struct grhip_detail::factory;
+    grhip_repack_bb_blk(unsigned int bits_per_chunk, gr_endianness_t endianness, int device)
+        : grhip_repack_bb_blk::block(T::name, gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(unsigned char)))
+    {
+        grhip_detail::check(T::create(this->d_h.out(), bits_per_chunk, (int)endianness, device));      // refuses 0 and above 8
+        this->set_relative_rate(T::unpacks ? 8.0 / bits_per_chunk : bits_per_chunk / 8.0);              // .cc.t:55 / :53
+    }
+public:
+    void forecast(int noutput_items, gr_vector_int &ninput_items_required) override
+    {
+        this->forecast_each(T::forecast, noutput_items, ninput_items_required);                         // .cc.t:62 / :59
+    }
+    int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        return this->work_consumed(T::general_work, noutput_items, ninput_items, in, out);
+    }
+};
+namespace grhip_detail {
+struct packed_to_unpacked_bb_fns {
+    typedef grhip_packed_to_unpacked_bb H;
+    static constexpr const char *name = "packed_to_unpacked_bb";
+    static constexpr bool unpacks = true;
+    GRHIP_FN(packed_to_unpacked_bb, create); GRHIP_FN(packed_to_unpacked_bb, destroy); GRHIP_FN(packed_to_unpacked_bb, set_mode);
+    GRHIP_FN(packed_to_unpacked_bb, forecast); GRHIP_FN(packed_to_unpacked_bb, general_work);
+};
+struct unpacked_to_packed_bb_fns {
+    typedef grhip_unpacked_to_packed_bb H;
+    static constexpr const char *name = "unpacked_to_packed_bb";
+    static constexpr bool unpacks = false;
+    GRHIP_FN(unpacked_to_packed_bb, create); GRHIP_FN(unpacked_to_packed_bb, destroy); GRHIP_FN(unpacked_to_packed_bb, set_mode);
+    GRHIP_FN(unpacked_to_packed_bb, forecast); GRHIP_FN(unpacked_to_packed_bb, general_work);
+};
+}  // namespace grhip_detail
+typedef grhip_repack_bb_blk<grhip_detail::packed_to_unpacked_bb_fns> grhip_packed_to_unpacked_bb_blk;
+typedef grhip_repack_bb_blk<grhip_detail::unpacked_to_packed_bb_fns> grhip_unpacked_to_packed_bb_blk;
+typedef boost::shared_ptr<grhip_packed_to_unpacked_bb_blk> grhip_packed_to_unpacked_bb_sptr;
+typedef boost::shared_ptr<grhip_unpacked_to_packed_bb_blk> grhip_unpacked_to_packed_bb_sptr;
+inline grhip_packed_to_unpacked_bb_sptr grhip_make_packed_to_unpacked_bb(unsigned int bits_per_chunk, gr_endianness_t endianness, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_packed_to_unpacked_bb_blk>(bits_per_chunk, endianness, device);
+}
+inline grhip_unpacked_to_packed_bb_sptr grhip_make_unpacked_to_packed_bb(unsigned int bits_per_chunk, gr_endianness_t endianness, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_unpacked_to_packed_bb_blk>(bits_per_chunk, endianness, device);
+}
+
+class grhip_diff_encoder_bb_blk : public GRHIP_BLOCK(gr_sync_block, diff_encoder_bb) {
+    friend struct grhip_detail::factory;
+    grhip_diff_encoder_bb_blk(unsigned int modulus, int device)
+        : block("diff_encoder_bb", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(unsigned char)))
+    {
+        grhip_detail::check(grhip_diff_encoder_bb_create(d_h.out(), modulus, device));
+    }
+public:
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(grhip_diff_encoder_bb_work(d_h, noutput_items, in[0], out[0]));
+        return noutput_items;
+    }
+};
+typedef boost::shared_ptr<grhip_diff_encoder_bb_blk> grhip_diff_encoder_bb_sptr;
+inline grhip_diff_encoder_bb_sptr grhip_make_diff_encoder_bb(unsigned int modulus, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_diff_encoder_bb_blk>(modulus, device);
+}
+
+class grhip_chunks_to_symbols_bc_blk : public GRHIP_BLOCK(gr_sync_interpolator, chunks_to_symbols_bc) {
+    friend struct grhip_detail::factory;
+    std::vector<gr_complex> d_symbol_table;
+    grhip_chunks_to_symbols_bc_blk(const std::vector<gr_complex> &symbol_table, const int D, int device)
+        : block("chunks_to_symbols_bc", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(gr_complex)),
+                (unsigned)(D < 1 ? 1 : D)),
+          d_symbol_table(symbol_table)
+    {
+        grhip_detail::check(grhip_chunks_to_symbols_bc_create(d_h.out(), (const float *)symbol_table.data(), symbol_table.size(), D, device));
+    }
+public:
+    int D() const { return (int)interpolation(); }
+    std::vector<gr_complex> symbol_table() const { return d_symbol_table; }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(grhip_chunks_to_symbols_bc_work(d_h, noutput_items / (int)interpolation(), in[0], out[0]));
+        return noutput_items;
+    }
+};
+typedef boost::shared_ptr<grhip_chunks_to_symbols_bc_blk> grhip_chunks_to_symbols_bc_sptr;
+inline grhip_chunks_to_symbols_bc_sptr grhip_make_chunks_to_symbols_bc(const std::vector<gr_complex> &symbol_table, const int D = 1, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_chunks_to_symbols_bc_blk>(symbol_table, D, device);
+}
+
+// generic_mod: bytes in, complex samples out.  The handle takes new bytes only and keeps what the chain's blocks would
+// keep, so a call consumes whole bytes: as many as still fit noutput_items, which the handle tells in advance
+// (max_produced).  The output multiple is what one byte can bring at most, so that a call always has room for a byte;
+// forecast asks for the bytes that are sure to fit, at least one.
+class grhip_generic_mod_blk : public GRHIP_BLOCK(gr_block, generic_mod) {
+    friend struct grhip_detail::factory;
+    int d_k = 1;
+    double d_sps = 2;
+    grhip_generic_mod_blk(grhip_constellation_sptr c, double samples_per_symbol, bool differential, double excess_bw, bool gray_coded, int device)
+        : block("generic_mod", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(gr_complex)))
+    {
+        grhip_detail::check(grhip_generic_mod_create(d_h.out(), c->handle(), samples_per_symbol, differential, excess_bw, gray_coded, device));
+        d_k = bits_per_symbol();
+        d_sps = samples_per_symbol;
+        set_relative_rate(8.0 / d_k * d_sps);
+        set_output_multiple((int)most(1));
+    }
+    // no call of n bytes brings more: the symbols that n bytes and k - 1 carried bits complete, each at most
+    // ceil(samples_per_symbol) samples
+    long long most(long long n_bytes) const { return ((8 * n_bytes + d_k - 1) / d_k) * (long long)std::ceil(d_sps); }
+public:
+    int bits_per_symbol() const { return grhip_generic_mod_bits_per_symbol(d_h); }
+    double samples_per_symbol() const { return grhip_generic_mod_samples_per_symbol(d_h); }
+    int engine() const { return grhip_generic_mod_engine(d_h); }
+    void set_engine(int engine) { grhip_detail::check(grhip_generic_mod_set_engine(d_h, engine)); }
+    std::vector<float> taps() const
+    {
+        std::vector<float> t((size_t)grhip_generic_mod_ntaps(d_h));
+        grhip_generic_mod_taps(d_h, t.data(), t.size());
+        return t;
+    }
+    void forecast(int noutput_items, gr_vector_int &req) override
+    {
+        long long n = (long long)(noutput_items / (std::ceil(d_sps) * 8.0 / d_k));
+        while (n > 1 && most(n) > noutput_items) --n;
+        for (size_t i = 0; i < req.size(); i++) req[i] = n < 1 ? 1 : (int)n;
+    }
+    int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        long long n = std::min<long long>(ninput_items[0], (long long)(noutput_items / relative_rate()) + 1);
+        while (n > 0 && grhip_generic_mod_max_produced(d_h, (int)n) > noutput_items) --n;       // the most bytes whose samples fit
+        long long produced = 0;
+        if (n > 0) grhip_detail::check(grhip_generic_mod_work(d_h, (int)n, in[0], out[0], noutput_items, &produced));
+        consume_each((int)n);
+        return (int)produced;
+    }
+};
+typedef boost::shared_ptr<grhip_generic_mod_blk> grhip_generic_mod_sptr;
+inline grhip_generic_mod_sptr grhip_make_generic_mod(grhip_constellation_sptr constellation, double samples_per_symbol = 2, bool differential = false,
+                                                     double excess_bw = 0.35, bool gray_coded = true, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_generic_mod_blk>(constellation, samples_per_symbol, differential, excess_bw, gray_coded, device);
+}
 
 // ---------------------------------------------------------------------------
 // gr_iir_filter_ffd (fftaps, fbtaps in double; filter/gr_iir_filter_ffd.h:62-85): a gr_sync_block, history 1, float in

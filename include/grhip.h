@@ -2335,6 +2335,140 @@ GRHIP_API int grhip_constellation_demod_cb_work(grhip_constellation_demod_cb *h,
 GRHIP_API int grhip_constellation_demod_cb_work_device(grhip_constellation_demod_cb *h, int n_in, const void *d_in, void *d_bits, void *stream);
 
 /* ======================================================================
+ * The blocks in front of the pulse shaper of generic_mod (gr-digital/python/generic_mod_demod.py:114-150):
+ * gr_packed_to_unpacked_bb, gr_unpacked_to_packed_bb, gr_diff_encoder_bb, gr_chunks_to_symbols_bc
+ *   replace gr_make_packed_to_unpacked_bb (bits_per_chunk, endianness), gr_make_unpacked_to_packed_bb (same),
+ *       gr_make_diff_encoder_bb (modulus), gr_make_chunks_to_symbols_bc (symbol_table, D)
+ *   gengen/gr_packed_to_unpacked_XX.cc.t:58-137, gengen/gr_unpacked_to_packed_XX.cc.t:56-129,
+ *   general/gr_diff_encoder_bb.cc:44-62, gengen/gr_chunks_to_symbols_XX.cc.t:51-74
+ * Handles take S streams back to back as diff_decoder_bb and map_bb do (S = 1 after create); set_mode is
+ * accepted and every mode gives the same bytes (the arithmetic is integer, the symbols are copied); an
+ * output that overlaps its input is refused; n == 0 (noutput_items == 0) is a successful no-op; the device
+ * entries do not synchronise.
+ *
+ * packed_to_unpacked_bb: output chunk i is the bits_per_chunk bits from bit address d_index + i * k of
+ * the input bytes, the first bit the chunk's most significant.  GRHIP_MSB_FIRST counts a byte's bits from
+ * the top, GRHIP_LSB_FIRST from the bottom; the reference shifts left for both (x = (x << 1) | bit,
+ * .cc.t:109 and :119), so an LSB_FIRST chunk is the byte's bits in reverse order.  A gr_block:
+ * forecast(n) = ceil((d_index + n * k) / 8) (.cc.t:62); general_work reads in [S][ninput_items], writes
+ * out [S][noutput_items], returns noutput_items and sets *consumed = d_index >> 3, keeping d_index & 7:
+ * one value for all streams, as in the reference, 0 after create and set_streams.  The counts do not
+ * depend on the data, so the device entry has them on return.  Refused: bits_per_chunk outside 1 .. 8
+ * and an endianness that is neither (the reference asserts); ninput_items below forecast (the reference
+ * only asserts, .cc.t:129); a call whose last bit address passes 2^32, where the reference's unsigned
+ * index wraps (noutput_items * k < 2^32 - 8).
+ * unpacked_to_packed_bb: the inverse.  Output byte i is the 8 bits from bit address d_index + i * 8 of
+ * the chunks' bits_per_chunk low bits laid end to end, most significant first (get_bit_be1, .cc.t:66-73);
+ * MSB_FIRST shifts them in from the right, LSB_FIRST builds the byte from the top down (:112), so the
+ * first bit ends as bit 0.  forecast(n) = ceil((d_index + 8 n) / k) (.cc.t:59), *consumed =
+ * d_index / k, d_index % k is kept (it counts bits within an input chunk).  Refusals as above, the
+ * address limit being noutput_items * 8 < 2^32 - 8.
+ * diff_encoder_bb: out[i] = (in[i] + last_out) % modulus in unsigned, stored as a byte, last_out = the
+ * byte (.cc:55-58); last_out is kept per stream, 0 after create and set_streams.  Moduli up to 256 are a
+ * prefix sum modulo the modulus whether or not the inputs lie below it, moduli above 510 (where
+ * in + last_out <= 510 is never reduced and the byte store alone wraps) one modulo 256: both run as a
+ * scan -- per-tile sums, a carry pass seeded with last_out, the tile again from its carry -- and give
+ * the serial loop's bytes.  For 257 .. 510 the byte store between two steps breaks associativity, and
+ * those moduli walk serially, one lane per stream.  Modulus 0 is refused (the reference divides by it).
+ * chunks_to_symbols_bc: n input bytes per stream give n * D complex items, table[in * D .. in * D + D)
+ * (.cc.t:65-69).  Deviation: an index whose D entries do not lie inside the table gives zeros; the
+ * reference asserts (:66) or, built without assertions, reads outside its vector.  Refused: an empty
+ * table, more than 65536 entries, D < 1, n * D above INT_MAX (the reference's noutput_items).
+ * ====================================================================== */
+#define GRHIP_MSB_FIRST 0 /* GR_MSB_FIRST, gengen/gr_endianness.h:25 */
+#define GRHIP_LSB_FIRST 1 /* GR_LSB_FIRST */
+typedef struct grhip_packed_to_unpacked_bb grhip_packed_to_unpacked_bb;
+GRHIP_API int grhip_packed_to_unpacked_bb_create(grhip_packed_to_unpacked_bb **h, unsigned bits_per_chunk, int endianness, int device);
+GRHIP_API void grhip_packed_to_unpacked_bb_destroy(grhip_packed_to_unpacked_bb *h);
+GRHIP_API int grhip_packed_to_unpacked_bb_set_mode(grhip_packed_to_unpacked_bb *h, int mode);
+GRHIP_API int grhip_packed_to_unpacked_bb_set_streams(grhip_packed_to_unpacked_bb *h, int nstreams);
+GRHIP_API int grhip_packed_to_unpacked_bb_forecast(grhip_packed_to_unpacked_bb *h, int noutput_items);
+GRHIP_API int grhip_packed_to_unpacked_bb_general_work(grhip_packed_to_unpacked_bb *h, int noutput_items, int ninput_items,
+                                                       const void *in, void *out, int *consumed);
+GRHIP_API int grhip_packed_to_unpacked_bb_general_work_device(grhip_packed_to_unpacked_bb *h, int noutput_items, int ninput_items,
+                                                              const void *d_in, void *d_out, int *consumed, void *stream);
+typedef struct grhip_unpacked_to_packed_bb grhip_unpacked_to_packed_bb;
+GRHIP_API int grhip_unpacked_to_packed_bb_create(grhip_unpacked_to_packed_bb **h, unsigned bits_per_chunk, int endianness, int device);
+GRHIP_API void grhip_unpacked_to_packed_bb_destroy(grhip_unpacked_to_packed_bb *h);
+GRHIP_API int grhip_unpacked_to_packed_bb_set_mode(grhip_unpacked_to_packed_bb *h, int mode);
+GRHIP_API int grhip_unpacked_to_packed_bb_set_streams(grhip_unpacked_to_packed_bb *h, int nstreams);
+GRHIP_API int grhip_unpacked_to_packed_bb_forecast(grhip_unpacked_to_packed_bb *h, int noutput_items);
+GRHIP_API int grhip_unpacked_to_packed_bb_general_work(grhip_unpacked_to_packed_bb *h, int noutput_items, int ninput_items,
+                                                       const void *in, void *out, int *consumed);
+GRHIP_API int grhip_unpacked_to_packed_bb_general_work_device(grhip_unpacked_to_packed_bb *h, int noutput_items, int ninput_items,
+                                                              const void *d_in, void *d_out, int *consumed, void *stream);
+typedef struct grhip_diff_encoder_bb grhip_diff_encoder_bb;
+GRHIP_API int grhip_diff_encoder_bb_create(grhip_diff_encoder_bb **h, unsigned modulus, int device);
+GRHIP_API void grhip_diff_encoder_bb_destroy(grhip_diff_encoder_bb *h);
+GRHIP_API int grhip_diff_encoder_bb_set_mode(grhip_diff_encoder_bb *h, int mode);
+GRHIP_API int grhip_diff_encoder_bb_set_streams(grhip_diff_encoder_bb *h, int nstreams);
+GRHIP_API int grhip_diff_encoder_bb_work(grhip_diff_encoder_bb *h, int n, const void *in, void *out);
+GRHIP_API int grhip_diff_encoder_bb_work_device(grhip_diff_encoder_bb *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_chunks_to_symbols_bc grhip_chunks_to_symbols_bc;
+GRHIP_API int grhip_chunks_to_symbols_bc_create(grhip_chunks_to_symbols_bc **h, const float *symbol_table_re_im, size_t nsymbols, int D,
+                                                int device);
+GRHIP_API void grhip_chunks_to_symbols_bc_destroy(grhip_chunks_to_symbols_bc *h);
+GRHIP_API int grhip_chunks_to_symbols_bc_set_mode(grhip_chunks_to_symbols_bc *h, int mode);
+GRHIP_API int grhip_chunks_to_symbols_bc_set_streams(grhip_chunks_to_symbols_bc *h, int nstreams);
+GRHIP_API int grhip_chunks_to_symbols_bc_D(grhip_chunks_to_symbols_bc *h);
+GRHIP_API int grhip_chunks_to_symbols_bc_work(grhip_chunks_to_symbols_bc *h, int n, const void *in, void *out);
+GRHIP_API int grhip_chunks_to_symbols_bc_work_device(grhip_chunks_to_symbols_bc *h, int n, const void *d_in, void *d_out, void *stream);
+
+/* generic_mod: the digital modulator as one handle
+ *   replaces digital.generic_mod (constellation, samples_per_symbol, differential, excess_bw, gray_coded)
+ *   gr-digital/python/generic_mod_demod.py:76-157
+ * packed_to_unpacked_bb(bits_per_symbol, MSB_FIRST) -> map_bb(pre_diff_code) if gray_coded ->
+ * diff_encoder_bb(2^bits_per_symbol) if differential -> chunks_to_symbols_bc(points) ->
+ * pfb_arb_resampler_ccf(samples_per_symbol, root_raised_cosine(32, 32, 1.0, excess_bw,
+ * 32 * 11 * int(samples_per_symbol)), 32)   (:114-150).  firdes makes the tap count odd: ntaps() is one more,
+ * and a filter has 11 * int(samples_per_symbol) + 1 taps.  samples_per_symbol and excess_bw are doubles, as the
+ * Python floats of the reference are: the taps are designed from the double excess_bw, the resampler's rate is
+ * samples_per_symbol narrowed to float (gr_make_pfb_arb_resampler_ccf takes a float).
+ * The modulator does not ask apply_pre_diff_code() (:123-124): an empty code is the identity, and
+ * constellation_qpsk's code IS applied here although constellation_demod_cb / generic_demod skip it.  The
+ * asymmetry is the reference's.
+ * Refused: samples_per_symbol below 2 (the reference raises, :114-115) or not finite; int(samples_per_symbol)
+ * above 11, the handle's limit (with 32 arms the resampler's tap banks leave LDS at 12); a constellation of
+ * dimensionality above 1, of fewer than 2 points or of more than 8 bits per symbol; an excess_bw that leaves no
+ * finite taps.
+ * The handle takes NEW BYTES ONLY, S streams back to back ([S][n_bytes]).  Between calls it keeps, per stream, the
+ * unread bits of the last byte, the encoder's last_out and the last taps-per-filter symbols, and for all
+ * streams the bit index and the resampler's (j, acc).  So the output depends on the concatenated input alone,
+ * never on where the calls cut it: a chunk that straddles two calls (3 or 6 bits per symbol) comes with the
+ * call that completes it, and output m comes with the call that brings symbol count_m (the rule of
+ * pfb_arb_resampler_ccf_run_captures_device, "count_k < n_samples"; the scheduler's history zeros in front of
+ * the stream are complex zeros, not point 0).  The reference's first general_work that returns 0 (d_updated)
+ * is a scheduler artefact without effect on the stream and is not reproduced.
+ * *produced, the items per stream, is known on return (the schedule does not depend on the data) and is the
+ * same for every stream; max_produced(n_bytes) is that number for the NEXT call of n_bytes, from the handle's
+ * current state.  An out_capacity (items per stream) below it is refused before anything is written or
+ * carried.  work: out is [S][*produced] back to back.  work_device: stream s at d_out + s * out_stride_items;
+ * it does not synchronise.  n_bytes == 0 is a successful no-op.  The output may not overlap the input.
+ * engine 0 runs the library's own five blocks in a row inside the handle and is the yardstick.  engine 1 (the
+ * default) is one fused kernel behind a carry pre-pass (csrc/modulator_fused.hip): k/8 bytes in and
+ * 8 * samples_per_symbol bytes out per symbol.  Both keep the same state, so the engine may change between
+ * calls.  GRHIP_MODE_GENERIC: gr_fir_ccf_generic's order and the unfused o0 + o1 * acc, engine 1 equal to
+ * engine 0 and to the reference bit for bit.  Every other mode: the blended tap h + acc * dh and FMAs, as
+ * pfb_arb_resampler_ccf. */
+typedef struct grhip_generic_mod grhip_generic_mod;
+GRHIP_API int grhip_generic_mod_create(grhip_generic_mod **h, const grhip_constellation *constellation, double samples_per_symbol,
+                                       int differential, double excess_bw, int gray_coded, int device);
+GRHIP_API void grhip_generic_mod_destroy(grhip_generic_mod *h);
+GRHIP_API int grhip_generic_mod_set_mode(grhip_generic_mod *h, int mode);
+GRHIP_API int grhip_generic_mod_set_streams(grhip_generic_mod *h, int nstreams);
+GRHIP_API int grhip_generic_mod_set_engine(grhip_generic_mod *h, int engine);
+GRHIP_API int grhip_generic_mod_engine(grhip_generic_mod *h);
+GRHIP_API int grhip_generic_mod_bits_per_symbol(grhip_generic_mod *h);
+GRHIP_API double grhip_generic_mod_samples_per_symbol(grhip_generic_mod *h);
+GRHIP_API int grhip_generic_mod_ntaps(grhip_generic_mod *h);
+GRHIP_API int grhip_generic_mod_taps(grhip_generic_mod *h, float *taps, size_t capacity);
+GRHIP_API long long grhip_generic_mod_max_produced(grhip_generic_mod *h, int n_bytes);
+GRHIP_API int grhip_generic_mod_work(grhip_generic_mod *h, int n_bytes, const void *in, void *out, long long out_capacity,
+                                     long long *produced);
+GRHIP_API int grhip_generic_mod_work_device(grhip_generic_mod *h, int n_bytes, const void *d_in, void *d_out, long long out_stride_items,
+                                            long long out_capacity, long long *produced, void *stream);
+
+/* ======================================================================
  * gr_iir_filter_ffd
  *   replaces gr_make_iir_filter_ffd(const std::vector<double> &fftaps,
  *       const std::vector<double> &fbtaps)
