@@ -1139,6 +1139,10 @@ GRHIP_API int grhip_hilbert_fc_work_device(grhip_hilbert_fc *h, int noutput_item
  * antisymmetric (is_sparse() == 1; checked on the given floats, no tolerance) and there is one
  * input, a kernel that multiplies t[h+i] by (x[c-i] - x[c+i]) over odd i only; otherwise, and
  * with two inputs, a kernel that uses every tap.  Above 2048 taps FAST runs the GENERIC kernel.
+ * Stated deviation of that first kernel: the zero taps are never multiplied.  A sample that is
+ * not finite therefore reaches the imaginary part of the outputs it lies an odd distance <= h
+ * from the centre of, and no other; the reference (and GENERIC) also form 0 * inf = NaN at the
+ * even distances.  The real part carries the sample itself in every mode.
  * ====================================================================== */
 typedef struct grhip_filter_delay_fc grhip_filter_delay_fc;
 GRHIP_API int grhip_filter_delay_fc_create(grhip_filter_delay_fc **h, const float *taps, size_t ntaps, int device);

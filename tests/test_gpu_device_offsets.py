@@ -6,6 +6,8 @@ the mode is documented bit exact.  Each case: run, synchronise, compare, check t
 input guards with another poison and require a bit-identical result from a fresh handle.
 
 Sizes per row: three of the kernel's tiles plus an odd remainder, and one call shorter than a vector chunk."""
+import contextlib
+
 import numpy as np
 import pytest
 
@@ -61,21 +63,67 @@ def offset_pairs(in_size, out_size):
     return pairs
 
 
-def _rc(rng, n):
-    return (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n)).astype(np.complex64)
+# every float or complex input the builders generate is multiplied by AMPLITUDE (tests/test_gpu_float_range.py sets
+# powers of two); at 1 nothing is touched, so the cases of this file are byte for byte what they were without it.
+# Taps and parameters are never scaled.
+AMPLITUDE = 1.0
+_POISON = []                    # one value: it replaces the middle sample of the next input _amp() sees
 
 
-def _rf(rng, n):
-    return rng.uniform(-1, 1, n).astype(np.float32)
+@contextlib.contextmanager
+def amplitude(a, poison=None):
+    """builders called inside see their input times `a`; with `poison`, the middle sample of the first input they
+    generate is that value (an inf or a NaN)"""
+    global AMPLITUDE
+    before, AMPLITUDE = AMPLITUDE, a
+    _POISON[:] = [] if poison is None else [poison]
+    try:
+        yield
+    finally:
+        AMPLITUDE = before
+        del _POISON[:]
+
+
+def _amp(x):
+    if AMPLITUDE != 1:
+        x = x * np.float32(AMPLITUDE)
+    if _POISON:
+        x = x.copy()
+        x[tuple(s // 2 for s in x.shape)] = _POISON.pop()
+    return x
+
+
+def _rc(rng, n, scaled=True):
+    x = (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n)).astype(np.complex64)
+    return _amp(x) if scaled else x
+
+
+def _rf(rng, n, scaled=True):
+    x = rng.uniform(-1, 1, n).astype(np.float32)
+    return _amp(x) if scaled else x
+
+
+class Deferred(object):
+    """a reference that the library itself computes on the device: formed when it is first compared, so that the
+    builder touches no device"""
+
+    def __init__(self, fn):
+        self.fn, self.value = fn, None
+
+    def __array__(self, dtype=None, copy=None):
+        if self.value is None:
+            self.value = self.fn()
+        return self.value
 
 
 class Spec(object):
     """one call, independent of offsets and strides: how to make the handle, the host inputs, the outputs' shapes, the
     call itself, the reference and the comparison"""
 
-    def __init__(self, make, ins, outs, call, ref, check, ret=None, post=None, ref_post=None):
+    def __init__(self, make, ins, outs, call, ref, check, ret=None, post=None, ref_post=None, cpu_ref=None):
         self.make, self.ins, self.outs, self.call, self.ref, self.check = make, ins, outs, call, ref, check
         self.ret, self.post, self.ref_post = ret, post, ref_post
+        self.cpu_ref = cpu_ref          # where `ref` is Deferred: the CPU form of it, for tests that have no device
 
 
 class Out(object):
@@ -144,10 +192,10 @@ def build_fir(gpu, po, wl, variant, n):
     rng = np.random.default_rng(ntaps * 10 + decim)
     nin = n * decim + ntaps - 1
     if kind == "fff":
-        x, taps = _rf(rng, nin), _rf(rng, ntaps)
+        x, taps = _rf(rng, nin), _rf(rng, ntaps, scaled=False)
     else:
         x = _rc(rng, nin)
-        taps = _rf(rng, ntaps) if kind == "ccf" else _rc(rng, ntaps)
+        taps = _rf(rng, ntaps, scaled=False) if kind == "ccf" else _rc(rng, ntaps, scaled=False)
     bound = np.abs(taps).sum() * (np.sqrt(2) if kind == "ccc" else 1.0)
     ref = getattr(po, "fir_" + kind)(taps, x, n, decim)
 
@@ -155,6 +203,8 @@ def build_fir(gpu, po, wl, variant, n):
         blk = getattr(gpu, "fir_filter_" + kind)(decim, taps)
         blk.set_mode(getattr(gpu, "MODE_" + mode))
         return blk
+    if AMPLITUDE != 1:                                                  # the absolute term follows the input
+        bound = bound * AMPLITUDE
     return _simple(gpu, make, x, n, ref.dtype, ref, exact if mode == "GENERIC" else fir_fast(bound))
 
 
@@ -187,7 +237,7 @@ def build_xlating_demod(gpu, po, wl, variant, n):
     ntaps, decim = int(ntaps[1:]), int(decim[1:])
     c = wl.CFG2
     gain = 3.0
-    x = wl.fsk4_capture(n * decim, stream_id=17)
+    x = _amp(wl.fsk4_capture(n * decim, stream_id=17))
     proto = wl.lowpass_taps(ntaps, 100e3, 10e6).astype(np.complex64)
     ref = po.chain_xlating_demod(decim, proto, c["center_freq"], c["fs"], gain, x)
     xin = wl.with_history(x, ntaps - 1)
@@ -216,7 +266,7 @@ def build_quad_demod(gpu, po, wl, variant, n):
 
 def build_pager_slicer(gpu, po, wl, variant, n):
     rng = np.random.default_rng(n)
-    x = (rng.integers(0, 4, n) * 2.0 - 3.0 + 0.7 + 0.3 * rng.standard_normal(n)).astype(np.float32)
+    x = _amp((rng.integers(0, 4, n) * 2.0 - 3.0 + 0.7 + 0.3 * rng.standard_normal(n)).astype(np.float32))
     ref = po.PagerSlicer(0.002).work(x)
     return _simple(gpu, lambda: gpu.pager_slicer_fb(0.002), x, n, np.uint8, ref, exact)
 
@@ -288,7 +338,7 @@ def build_fft_vcc(gpu, po, wl, variant, n):
 def build_fft_filter_ccc(gpu, po, wl, variant, n):
     ntaps, decim = (int(v[1:]) for v in variant.split("-"))
     rng = np.random.default_rng(ntaps + decim)
-    taps = _rc(rng, ntaps)
+    taps = _rc(rng, ntaps, scaled=False)
     ref_blk = po.FftFilterCcc(decim, taps)
     ns = ref_blk.nsamples
     nout = n * ns
@@ -309,16 +359,16 @@ def build_fft_filter_ccc(gpu, po, wl, variant, n):
 def build_pfb_channelizer(gpu, po, wl, variant, n):
     M, osr = {"M8": (8, 1.0), "M5": (5, 1.0), "M8os2": (8, 2.0)}[variant]
     rng = np.random.default_rng(M * 10 + int(osr))
-    taps = _rf(rng, 5 * M - M // 2)
+    taps = _rf(rng, 5 * M - M // 2, scaled=False)
     o = po.PfbChannelizer(M, taps, osr)
     tpf = o.taps_per_filter
     nout = max(n - n % o.output_multiple, o.output_multiple)
     nin = int(round(nout / osr))
     per = tpf + nin + 4
     ins = np.zeros((M, per), np.complex64)
-    ins[:, tpf:] = _rc(rng, M * (nin + 4)).reshape(M, nin + 4)
+    ins[:, tpf:] = _amp(_rc(rng, M * (nin + 4), scaled=False).reshape(M, nin + 4))
     ref, _used = o.general_work(nout, [ins[j] for j in range(M)])
-    scale = np.abs(ref).max()
+    scale = np.abs(ref[np.isfinite(ref)]).max()
 
     def check(got, ref):                                                # tests/test_gpu_fft_pfb.py:209
         err = np.abs(got.reshape(nout, M) - ref).max()
@@ -336,7 +386,7 @@ def build_pfb_hier(gpu, po, wl, variant, n):
     """the one-call hierarchical entry: one interleaved stream in, M streams out"""
     M, osr = {"M8": (8, 1.0), "M5": (5, 1.0), "M8os2": (8, 2.0)}[variant]
     rng = np.random.default_rng(M * 10 + int(osr) + 1)
-    taps = _rf(rng, 5 * M - M // 2)
+    taps = _rf(rng, 5 * M - M // 2, scaled=False)
     o = po.PfbChannelizer(M, taps, osr)
     tpf = o.taps_per_filter
     nout = max(n - n % o.output_multiple, o.output_multiple)
@@ -380,13 +430,13 @@ def first(p, check):
 
 def _sig(rng, n, cplx):
     x = rng.standard_normal(n).astype(np.float32)
-    return (x + 1j * rng.standard_normal(n)).astype(np.complex64) if cplx else x
+    return _amp((x + 1j * rng.standard_normal(n)).astype(np.complex64) if cplx else x)
 
 
 def build_fft_vfc(gpu, po, wl, variant, n):
     N = int(variant[1:])
     rng = np.random.default_rng(N + n)
-    x = rng.standard_normal(N * n).astype(np.float32)
+    x = _amp(rng.standard_normal(N * n).astype(np.float32))
     w = np.hamming(N).astype(np.float32)
     ref = fft_real_ref.fft_vfc(x, N, w).astype(np.complex64).reshape(-1)
     tol = 1e-6 * max(np.log2(N), 1) * np.abs(ref).max()                  # tests/test_gpu_fft_real.py:261
@@ -406,7 +456,7 @@ def build_fft_filter_fff(gpu, po, wl, variant, n):
     ref_blk = fft_real_ref.FftFilterFff(decim, taps)
     ns = ref_blk.nsamples
     nout = n * ns
-    x = rng.standard_normal(nout * decim).astype(np.float32)
+    x = _amp(rng.standard_normal(nout * decim).astype(np.float32))
     ref = np.asarray(ref_blk.filter(nout, x), np.float32)
     tol = 2e-6 * np.log2(2 * ns) * np.abs(ref).max()                     # tests/test_gpu_fft_real.py:33
 
@@ -601,7 +651,7 @@ def _rs_input(kind, n, seed):
     if kind == "ii":
         return rng.integers(-2 ** 31, 2 ** 31, n).astype(np.int32)
     x = rng.uniform(-1, 1, n) + 1.0
-    return (x + 1j * (rng.uniform(-1, 1, n) - 0.5)).astype(np.complex64) if kind == "cc" else x.astype(np.float32)
+    return _amp((x + 1j * (rng.uniform(-1, 1, n) - 0.5)).astype(np.complex64) if kind == "cc" else x.astype(np.float32))
 
 
 def build_runsum(gpu, po, wl, variant, n):
@@ -646,11 +696,11 @@ def build_spectrum(gpu, po, wl, variant, n):
     S = spectrum_ref
     rng = np.random.default_rng(n)
     if variant == "complex_to_mag_squared":
-        z = (rng.normal(size=n) * 10 ** rng.uniform(-3, 3, n) + 1j * rng.normal(size=n)).astype(np.complex64)
+        z = _amp((rng.normal(size=n) * 10 ** rng.uniform(-3, 3, n) + 1j * rng.normal(size=n)).astype(np.complex64))
         return _simple(gpu, lambda: gpu.complex_to_mag_squared(1), z, n, np.float32, S.mag_squared(z), exact)
     if variant.startswith("single_pole_iir_filter_ff"):
         mode = variant.rsplit("-", 1)[1]
-        x = (rng.normal(size=n) + 2.0).astype(np.float32)
+        x = _amp((rng.normal(size=n) + 2.0).astype(np.float32))
 
         def make():
             blk = gpu.single_pole_iir_filter_ff(0.125, 1)
@@ -661,7 +711,9 @@ def build_spectrum(gpu, po, wl, variant, n):
                            exact)
         want, _ = S.iir_f64(x.reshape(n, 1), 0.125)                     # tests/test_gpu_spectrum.py:97
         return _simple(gpu, make, x, n, np.float32, want.reshape(-1), peak(1e-5))
-    x = np.logspace(-30, 30, n).astype(np.float32)
+    # 60 decades at amplitude 1; 50 where a scale of up to 2^40 comes on top, so that every input stays a normal float
+    decades = 30 if AMPLITUDE == 1 else 25
+    x = _amp(np.logspace(-decades, decades, n).astype(np.float32))
     want = S.nlog10_f64(x, 10, 0)                                      # n and k of tests/golden/ref_qa_spectrum.json
 
     def ulps(got, ref):                                                 # tests/test_gpu_spectrum.py:102, :116
@@ -708,7 +760,9 @@ def build_logpwrfft(gpu, po, wl, variant, n):
              ).astype(np.complex64)
     else:
         x = (0.5 * np.cos(2 * np.pi * 0.1234 * t) + 0.05 * rng.normal(size=t.size)).astype(np.float32)
-    ref = np.asarray(LogpwrChain(gpu, kind, N, 1, 1, alpha, True, None, 2.0, mode).work(n, x), np.float32)
+    x = _amp(x)
+    ref = Deferred(lambda: np.asarray(LogpwrChain(gpu, kind, N, 1, 1, alpha, True, None, 2.0, mode).work(n, x),
+                                      np.float32))
     wd = logpwrfft_ref.blackmanharris(N)
     k = np.float32(logpwrfft_ref.k_of(N, wd, 2.0))
     ref_db, p_ref, _ = spectrum_ref.chain_f64(x.reshape(n, N), np.asarray(wd, np.float64).astype(np.float32), alpha, k)
@@ -716,7 +770,10 @@ def build_logpwrfft(gpu, po, wl, variant, n):
     def check(got, ref):
         exact(got, ref)
         out = got.reshape(n, N).astype(np.float64)
-        e_lin = np.abs(10.0 ** ((out - float(k)) / 10.0) - p_ref).max() / p_ref.max()
+        # what the logarithm sees: gr_nlog10_ff takes max(p, 1e-18), so a spectrum below -180 dB reads -180 dB (no
+        # power of this file's amplitude-1 signal is that small)
+        p_lin = np.maximum(p_ref, 1e-18)
+        e_lin = np.abs(10.0 ** ((out - float(k)) / 10.0) - p_lin).max() / p_lin.max()
         near = p_ref >= p_ref.max() * 1e-4
         e_db = np.abs(out - ref_db)[near].max()
         assert e_lin <= 2.5e-6 * max(np.log2(N), 1) and e_db <= 0.02, (e_lin, e_db)
@@ -729,7 +786,8 @@ def build_logpwrfft(gpu, po, wl, variant, n):
 
     def call(blk, ins, outs, strides):
         return blk.work_device(n, ins[0].ptr(), outs[0].ptr())
-    return Spec(make, [dict(arr=x)], [Out(n * N, np.float32)], call, [ref], check, ret=n)
+    return Spec(make, [dict(arr=x)], [Out(n * N, np.float32)], call, [ref], check, ret=n,
+                cpu_ref=[ref_db.astype(np.float32).reshape(-1)])
 
 
 def _sq_bursts(n):
@@ -745,7 +803,7 @@ def build_squelch(gpu, po, wl, variant, n):
     xs = []
     for seed in (1, 2):
         x = squelch_ref.signal(seed, n=n, bursts=_sq_bursts(n))
-        x = x if cc else x.real.astype(np.float32)
+        x = _amp(x if cc else x.real.astype(np.float32))
         if n > 100:                                                     # the no-exceptions condition of that file
             assert squelch_ref.closest_approach(x, alpha, db) > 1e-9
         xs.append(x)
@@ -788,7 +846,7 @@ def build_ctcss(gpu, po, wl, variant, n):
         x = ctcss_ref.signal(seed, rate, L, True)
         margin, deviation = ctcss_ref.condition(rate, L, freq, level, x)
         assert margin >= 10 * deviation
-        xs.append(np.ascontiguousarray(x[:n], np.float32))
+        xs.append(_amp(np.ascontiguousarray(x[:n], np.float32)))
     refs = [ctcss_ref.CtcssSquelch(rate, freq, level, L, 64, True).work(x) for x in xs]
     return _two_streams(gpu, lambda: gpu.ctcss_squelch_ff(rate, freq, level, L, 64, True), variant, xs, refs, n)
 
@@ -796,7 +854,7 @@ def build_ctcss(gpu, po, wl, variant, n):
 def build_agc2(gpu, po, wl, variant, n):
     """every mode of agc2_cc is the reference's recurrence bit for bit (tests/test_gpu_agc.py)"""
     params = agc_ref.sets("agc2_cc")[0]
-    xs = [np.ascontiguousarray(agc_ref.signal(seed, "agc2_cc")[1400:1400 + n]) for seed in (1, 2)]
+    xs = [_amp(np.ascontiguousarray(agc_ref.signal(seed, "agc2_cc")[1400:1400 + n])) for seed in (1, 2)]
     refs = [agc_ref.serial("agc2_cc", x, params).out for x in xs]
     return _two_streams(gpu, lambda: gpu.agc2_cc(*params), variant, xs, refs, n, with_counts=False)
 
@@ -805,7 +863,7 @@ def build_mm_ff(gpu, po, wl, variant, n):
     omega, gm = 4.3, 0.3
     go = 0.25 * gm * gm
     rng = np.random.default_rng(n)
-    x = _fsk_soft(rng, max(n // 4, 8), sps=4)[:n]
+    x = _amp(_fsk_soft(rng, max(n // 4, 8), sps=4)[:n])
     n = len(x)
     ref, st = po.chain_mm(omega, go, 0.5, gm, 0.005, x)
     p = len(ref)
@@ -823,7 +881,7 @@ def build_run_captures(gpu, po, wl, variant, n):
     c = wl.CFG2
     gain = c["demod_gain"]
     proto = wl.cfg2_proto_taps() if ntaps == 256 else wl.lowpass_taps(ntaps, 100e3, 10e6).astype(np.complex64)
-    xs = np.stack([wl.fsk4_capture(n, stream_id=70 + s) for s in range(2)])
+    xs = np.stack([_amp(wl.fsk4_capture(n, stream_id=70 + s)) for s in range(2)])
     nout = n // decim
     refs = np.stack([po.chain_xlating_demod(decim, proto, c["center_freq"], c["fs"], gain, x[:nout * decim])
                      for x in xs])
@@ -861,7 +919,7 @@ def build_dmr_chain(gpu, po, wl, variant, n):
     tail, mode = variant.split("-")
     c, c4 = wl.CFG2, wl.CFG4
     code, thr = wl.access_code_string(), c4["threshold"]
-    xs = np.stack([wl.fsk4_capture(n, stream_id=40 + s) for s in range(2)])
+    xs = np.stack([_amp(wl.fsk4_capture(n, stream_id=40 + s)) for s in range(2)])
     four, alpha, generic = tail == "four_level", 0.002, mode == "GENERIC"
     per = 2 if four else 1                                              # items per symbol (tests/test_gpu_chain.py:578)
     n_dem = n // c["decim"]
