@@ -13,7 +13,9 @@ high_pass / band_pass / band_reject (as optfir_*), gr.complex_to_mag, blks2.am_d
 blks2.demod_20k0f3e_cf, blks2.demod_200kf3e_cf, gr.interp_fir_filter_XXX,
 gr.rational_resampler_base_XXX, blks2.rational_resampler_XXX, gr.pfb_interpolator_ccf,
 gr.pfb_synthesis_filterbank_ccf, gr.packed_to_unpacked_bb, gr.unpacked_to_packed_bb, gr.diff_encoder_bb,
-gr.chunks_to_symbols_bc, digital.generic_mod, psk_mod, qam_mod, bpsk_mod, dbpsk_mod, qpsk_mod, dqpsk_mod) with the same
+gr.chunks_to_symbols_bc, digital.generic_mod, psk_mod, qam_mod, bpsk_mod, dbpsk_mod, qpsk_mod, dqpsk_mod,
+gr.scrambler_bb, gr.descrambler_bb, gr.additive_scrambler_bb, digital.crc32 / update_crc32 (on a crc32 handle),
+packet_utils.make_packet / unmake_packet in batches as packet_maker / packet_check) with the same
 constructor arguments; `work()` takes/returns numpy arrays with the
 gr_sync_block contract (history items in front of the input).
 

@@ -35,6 +35,8 @@ __all__ = [
     "constellation_demod_cb",
     "packed_to_unpacked_bb", "unpacked_to_packed_bb", "GR_MSB_FIRST", "GR_LSB_FIRST", "diff_encoder_bb", "chunks_to_symbols_bc",
     "generic_mod", "psk_mod", "qam_mod", "bpsk_mod", "dbpsk_mod", "qpsk_mod", "dqpsk_mod",
+    "scrambler_bb", "descrambler_bb", "additive_scrambler_bb", "crc32", "packet_maker", "packet_check", "random_mask_vec8",
+    "default_access_code", "PACKET_JOB", "PACKET_REC",
     "iir_filter_ffd", "fm_deemph", "fm_deemph_taps", "firdes_low_pass", "fm_demod_cf", "nbfm_rx",
     "remez", "optfir_low_pass", "optfir_high_pass", "optfir_band_pass", "optfir_band_reject", "optfir_spec",
     "complex_to_mag", "am_demod_cf", "demod_10k0a3e_cf", "demod_20k0f3e_cf", "demod_200kf3e_cf",
@@ -694,6 +696,16 @@ class framer_sink_1_batch(_Block):
     def run_device(self, d_in, stream_stride_items, d_nitems, n_items_max, stream=None, nitems_stride=1):
         self._call("run_device", _devptr(d_in), int(stream_stride_items), _devptr(d_nitems), int(nitems_stride),
                    int(n_items_max), _stream(stream))
+
+    def device_view(self):
+        """where the last run_device left its messages on the device, as packet_check.work_device takes them:
+        dict(d_recs, rec_stride, d_counts, count_stride_words, d_pool, pool_stride).  Addresses and strides are fixed at
+        create; their contents are the last run's until the next one"""
+        recs, counts, pool = C.c_void_p(0), C.c_void_p(0), C.c_void_p(0)
+        rs, ps, cs = C.c_longlong(0), C.c_longlong(0), C.c_int(0)
+        self._call("device_view", C.byref(recs), C.byref(rs), C.byref(counts), C.byref(cs), C.byref(pool), C.byref(ps))
+        return dict(d_recs=recs.value, rec_stride=rs.value, d_counts=counts.value, count_stride_words=cs.value,
+                    d_pool=pool.value, pool_stride=ps.value)
 
     def messages(self, stream=None):
         self._call("fetch", _stream(stream))
@@ -2513,6 +2525,149 @@ class dqpsk_mod(generic_mod):
         if constellation_points != 4:
             raise ValueError("Number of constellation points must be 4 for DQPSK.")
         generic_mod.__init__(self, constellation_dqpsk(), gray_coded=gray_coded, differential=True, **kw)
+
+
+# ----------------------------------------------------------------------------
+# the scramblers (general/gr_scrambler_bb.i, gr_descrambler_bb.i, gr_additive_scrambler_bb.i) and the packet layer
+# (gr-digital/python/packet_utils.py, crc.py, gr-digital/swig/digital_crc32.i)
+# ----------------------------------------------------------------------------
+class scrambler_bb(_byte_block):
+    """gr.scrambler_bb(mask, seed, len): out = the register's bit 0; parity(reg & mask) ^ (in & 1) enters at bit len.
+    The register is kept per stream across calls.  MODE_GENERIC walks serially, every other mode is a scan; the bytes
+    are the same."""
+    _name = "scrambler_bb"
+
+    def __init__(self, mask, seed, len, device=0):
+        _Block.__init__(self)
+        self._create(C.c_int(int(mask) & 0xffffffff).value, C.c_int(int(seed) & 0xffffffff).value, int(len), int(device))
+
+
+class descrambler_bb(scrambler_bb):
+    """gr.descrambler_bb(mask, seed, len): out = parity(reg & mask) ^ (in & 1); in & 1 enters at bit len"""
+    _name = "descrambler_bb"
+
+
+class additive_scrambler_bb(_byte_block):
+    """gr.additive_scrambler_bb(mask, seed, len, count=0): out = in ^ the register's bit 0 (the whole byte is XORed
+    with the bit); the register is the seed again after every `count` items if count > 0"""
+    _name = "additive_scrambler_bb"
+
+    def __init__(self, mask, seed, len, count=0, device=0):
+        _Block.__init__(self)
+        self._create(C.c_int(int(mask) & 0xffffffff).value, C.c_int(int(seed) & 0xffffffff).value, int(len), int(count),
+                     int(device))
+
+
+def random_mask_vec8():
+    """packet_utils.random_mask_vec8: the 4096 whitening bytes, generated by the library"""
+    t = np.zeros(4096, np.uint8)
+    _check(lib().grhip_whitening_table(_ptr(t), 4096))
+    return t
+
+
+default_access_code = "".join("{:08b}".format(b) for b in (0xAC, 0xDD, 0xA4, 0xE2, 0xF2, 0x8C, 0x20, 0xFC))   # packet_utils.py:72-73
+
+
+class crc32(_Block):
+    """digital.crc32 / digital.update_crc32 on the device: polynomial 0x04C11DB7, MSB first, start and final XOR
+    0xFFFFFFFF.  crc32(bytes) and update_crc32(crc, bytes) stage a host buffer; the _device forms take an address
+    or a tensor and a length."""
+    _name = "crc32"
+
+    def __init__(self, device=0):
+        _Block.__init__(self)
+        self._create(int(device))
+
+    def set_segment_bytes(self, nbytes):
+        """tuning: bytes one workgroup takes in a row (0 = chosen per call); results do not depend on it"""
+        self._call("set_segment_bytes", int(nbytes))
+
+    @staticmethod
+    def _bytes(s):
+        return np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray)) else np.ascontiguousarray(s, dtype=np.uint8).reshape(-1)
+
+    def crc32(self, s):
+        x, out = self._bytes(s), C.c_uint(0)
+        self._call("compute", _ptr(x) if len(x) else C.c_void_p(0), len(x), C.byref(out))
+        return out.value
+
+    def update_crc32(self, crc, s):
+        x, out = self._bytes(s), C.c_uint(0)
+        self._call("update", int(crc) & 0xffffffff, _ptr(x) if len(x) else C.c_void_p(0), len(x), C.byref(out))
+        return out.value
+
+    def crc32_device(self, d_buf, n, stream=None):
+        out = C.c_uint(0)
+        self._call("compute_device", _devptr(d_buf), int(n), C.byref(out), _stream(stream))
+        return out.value
+
+    def update_crc32_device(self, crc, d_buf, n, stream=None):
+        out = C.c_uint(0)
+        self._call("update_device", int(crc) & 0xffffffff, _devptr(d_buf), int(n), C.byref(out), _stream(stream))
+        return out.value
+
+
+PACKET_JOB = np.dtype([("whitener_offset", np.uint32), ("length", np.uint32), ("in_offset", np.uint32), ("out_offset", np.uint32)])
+PACKET_REC = np.dtype([("whitener_offset", np.uint32), ("length", np.uint32), ("offset", np.uint32), ("reserved", np.uint32)])
+
+
+class packet_maker(_Block):
+    """packet_utils.make_packet for many payloads in one call: preamble, access code, doubled header, payload + CRC-32
+    (whitened from whitener_offset), 0x55 and the padding of pad_for_usrp.  make_packets(payloads, whitener_offsets)
+    returns the packets as bytes; plan() and work_device() are the same on device buffers."""
+    _name = "packet_maker"
+
+    def __init__(self, samples_per_symbol, bits_per_symbol, access_code=default_access_code, pad_for_usrp=True, whitening=True,
+                 device=0):
+        _Block.__init__(self)
+        if not isinstance(access_code, str):
+            raise ValueError("access_code must be a string containing only 0's and 1's (%r)" % (access_code,))
+        self._create(C.c_char_p(access_code.encode()), float(samples_per_symbol), int(bits_per_symbol), int(bool(pad_for_usrp)),
+                     int(bool(whitening)), int(device))
+
+    def packet_bytes(self, payload_len):
+        return self._call("packet_bytes", int(payload_len))
+
+    def plan(self, lengths, whitener_offsets=None):
+        """(jobs as a PACKET_JOB array, payload bytes in all, packet bytes in all)"""
+        ln = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+        wo = None if whitener_offsets is None else np.ascontiguousarray(whitener_offsets, dtype=np.int32).reshape(-1)
+        if wo is not None and len(wo) != len(ln):
+            raise ValueError("one whitener offset per payload")
+        jobs = np.zeros(max(len(ln), 1), PACKET_JOB)
+        tin, tout = C.c_longlong(0), C.c_longlong(0)
+        self._call("plan", len(ln), _ptr(ln), C.c_void_p(0) if wo is None else _ptr(wo), _ptr(jobs), C.byref(tin), C.byref(tout))
+        return jobs[:len(ln)], tin.value, tout.value
+
+    def work_device(self, n, d_jobs, d_payloads, d_out, stream=None):
+        return self._call("work_device", int(n), _devptr(d_jobs), _devptr(d_payloads), _devptr(d_out), _stream(stream))
+
+    def make_packets(self, payloads, whitener_offsets=None):
+        """payloads: a list of bytes; returns the list of packets"""
+        jobs, tin, tout = self.plan([len(p) for p in payloads], whitener_offsets)
+        ln = np.ascontiguousarray(jobs["length"], dtype=np.int32)
+        wo = np.ascontiguousarray(jobs["whitener_offset"], dtype=np.int32)
+        x = np.frombuffer(b"".join(bytes(p) for p in payloads) + b"\0", np.uint8)
+        out = np.zeros(max(tout, 1), np.uint8)
+        total = C.c_longlong(0)
+        self._call("work", len(ln), _ptr(ln), _ptr(wo), _ptr(x), _ptr(out), int(tout), C.byref(total))
+        ends = list(jobs["out_offset"][1:]) + [total.value]
+        return [out[int(a):int(b)].tobytes() for a, b in zip(jobs["out_offset"], ends)]
+
+
+class packet_check(_Block):
+    """packet_utils.unmake_packet for messages on the device: dewhiten, compare the CRC-32, one ok byte per message"""
+    _name = "packet_check"
+
+    def __init__(self, device=0):
+        _Block.__init__(self)
+        self._create(int(device))
+
+    def work_device(self, n_streams, max_msgs, d_recs, rec_stride, d_counts, count_stride_words, d_pool, pool_stride, dewhitening,
+                    d_payload_out, d_ok, stream=None):
+        return self._call("work_device", int(n_streams), int(max_msgs), _devptr(d_recs), int(rec_stride), _devptr(d_counts),
+                          int(count_stride_words), _devptr(d_pool), int(pool_stride), int(bool(dewhitening)), _devptr(d_payload_out),
+                          _devptr(d_ok), _stream(stream))
 
 
 # ----------------------------------------------------------------------------

@@ -799,6 +799,24 @@ int grhip_framer_sink_1_batch_run_device(grhip_framer_sink_1_batch *h, const uns
     return GRHIP_OK;
 }
 
+// where the last run_device left its messages, for a consumer on the device (grhip_packet_check_work_device): read-only,
+// valid until the next run
+int grhip_framer_sink_1_batch_device_view(grhip_framer_sink_1_batch *h, const grhip_packet_rec **d_recs, long long *rec_stride,
+                                          const unsigned **d_counts, int *count_stride_words, const unsigned char **d_pool,
+                                          long long *pool_stride)
+{
+    if (!h) return fail(GRHIP_EINVAL, "null handle");
+    if (!d_recs || !rec_stride || !d_counts || !count_stride_words || !d_pool || !pool_stride) return fail(GRHIP_EINVAL, "null argument");
+    static_assert(sizeof(FramerMsg) == sizeof(grhip_packet_rec) && sizeof(FramerState) % sizeof(unsigned) == 0, "the view's layout");
+    *d_recs = h->d_msgs.as<grhip_packet_rec>();
+    *rec_stride = h->rec_stride;
+    *d_counts = &h->d_state.as<FramerState>()->msg_count;
+    *count_stride_words = (int)(sizeof(FramerState) / sizeof(unsigned));
+    *d_pool = h->d_pool.as<unsigned char>();
+    *pool_stride = h->pool_stride;
+    return GRHIP_OK;
+}
+
 int grhip_framer_sink_1_batch_fetch(grhip_framer_sink_1_batch *h, void *stream)
 {
     if (!h) return fail(GRHIP_EINVAL, "null handle");

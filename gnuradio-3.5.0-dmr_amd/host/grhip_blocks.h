@@ -47,6 +47,9 @@
 //                                               gr_make_chunks_to_symbols_bc (gengen/gr_*_XX.h.t, general/gr_diff_encoder_bb.h), the
 //                                               same arguments; grhip_make_generic_mod is digital.generic_mod
 //                                               (generic_mod_demod.py:76-157) as one block
+//   gr_make_scrambler_bb, gr_make_descrambler_bb, gr_make_additive_scrambler_bb
+//                                            <- the factories of the same names (general/gr_scrambler_bb.h,
+//                                               gr_descrambler_bb.h, gr_additive_scrambler_bb.h)
 //   gr_make_agc_cc / _ff, gr_make_agc2_cc / _ff
 //                                            <- the factories of the same names (general/gr_agc_cc.h, gr_agc_ff.h,
 //                                               gr_agc2_cc.h, gr_agc2_ff.h)
@@ -2219,6 +2222,58 @@ inline grhip_generic_mod_sptr grhip_make_generic_mod(grhip_constellation_sptr co
                                                      double excess_bw = 0.35, bool gray_coded = true, int device = 0)
 {
     return grhip_detail::factory::make<grhip_generic_mod_blk>(constellation, samples_per_symbol, differential, excess_bw, gray_coded, device);
+}
+
+// ---------------------------------------------------------------------------
+// gr_scrambler_bb, gr_descrambler_bb (mask, seed, len) and gr_additive_scrambler_bb (mask, seed, len, count = 0):
+// general/gr_scrambler_bb.h:31-32, gr_descrambler_bb.h:31-32, gr_additive_scrambler_bb.h:31-32.  gr_sync_blocks of
+// bytes, history 1; the register (and d_bits) live in the handle, so work() may be cut anywhere.  One stream each.
+// ---------------------------------------------------------------------------
+template <class T>
+class grhip_lfsr_bb_blk : public grhip_detail::block<gr_sync_block, typename T::H, T::destroy, T::set_mode> {
+    friend struct grhip_detail::factory;
+    // (mask, seed, len[, count], device), as T::create takes them
+    template <class... A> explicit grhip_lfsr_bb_blk(A... args)
+        : grhip_lfsr_bb_blk::block(T::name, gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(unsigned char)))
+    {
+        grhip_detail::check(T::create(this->d_h.out(), args...));                  // len above 31 throws, gri_lfsr.h:109-110
+    }
+public:
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(T::work(this->d_h, noutput_items, in[0], out[0]));
+        return noutput_items;
+    }
+};
+namespace grhip_detail {
+#define GRHIP_LFSR_FNS(NAME)                                                                                           \
+    struct NAME##_fns {                                                                                               \
+        typedef grhip_##NAME H;                                                                                       \
+        static constexpr const char *name = #NAME;                                                                    \
+        GRHIP_FN(NAME, create); GRHIP_FN(NAME, destroy); GRHIP_FN(NAME, set_mode); GRHIP_FN(NAME, work);              \
+    };
+GRHIP_LFSR_FNS(scrambler_bb)
+GRHIP_LFSR_FNS(descrambler_bb)
+GRHIP_LFSR_FNS(additive_scrambler_bb)
+#undef GRHIP_LFSR_FNS
+}  // namespace grhip_detail
+typedef grhip_lfsr_bb_blk<grhip_detail::scrambler_bb_fns> grhip_scrambler_bb_blk;
+typedef grhip_lfsr_bb_blk<grhip_detail::descrambler_bb_fns> grhip_descrambler_bb_blk;
+typedef grhip_lfsr_bb_blk<grhip_detail::additive_scrambler_bb_fns> grhip_additive_scrambler_bb_blk;
+typedef boost::shared_ptr<grhip_scrambler_bb_blk> grhip_scrambler_bb_sptr;
+typedef boost::shared_ptr<grhip_descrambler_bb_blk> grhip_descrambler_bb_sptr;
+typedef boost::shared_ptr<grhip_additive_scrambler_bb_blk> grhip_additive_scrambler_bb_sptr;
+inline grhip_scrambler_bb_sptr gr_make_scrambler_bb(int mask, int seed, int len, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_scrambler_bb_blk>(mask, seed, len, device);
+}
+inline grhip_descrambler_bb_sptr gr_make_descrambler_bb(int mask, int seed, int len, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_descrambler_bb_blk>(mask, seed, len, device);
+}
+inline grhip_additive_scrambler_bb_sptr gr_make_additive_scrambler_bb(int mask, int seed, int len, int count = 0, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_additive_scrambler_bb_blk>(mask, seed, len, count, device);
 }
 
 // ---------------------------------------------------------------------------

@@ -2473,6 +2473,139 @@ GRHIP_API int grhip_generic_mod_work_device(grhip_generic_mod *h, int n_bytes, c
                                             long long out_capacity, long long *produced, void *stream);
 
 /* ======================================================================
+ * The packet layer: CRC-32, make_packet / unmake_packet in batches, the whitening table
+ *   replace digital_crc32 / digital_update_crc32          gr-digital/lib/digital_crc32.cc:45-134
+ *           packet_utils.make_packet, unmake_packet        gr-digital/python/packet_utils.py:89-194
+ *           crc.gen_and_append_crc32, crc.check_crc32      gr-digital/python/crc.py:26-38
+ *           packet_utils.random_mask_tuple                 gr-digital/python/packet_utils.py:198-454
+ * as gr-digital/python/pkt.py:78-100 (transmit) and :143-167 (receive) use them.  The Reed-Solomon code of
+ * digital_crc32.cc:142-883 is not built.
+ *
+ * CRC-32: polynomial 0x04C11DB7, most significant bit first, no reflection; compute is
+ * update(0xFFFFFFFF, buf, len) ^ 0xFFFFFFFF (.cc:133), update the bare loop of .cc:115-120.  len is 0 ..
+ * 2^31 - 1; a buffer may start at any byte.  The device entries queue on `stream`, wait for it and store the
+ * CRC in the host word *crc; the host-buffer entries stage the bytes to the device (there is no CPU path).
+ * Every lane takes bytes of its own from a raw CRC of 0 and multiplies the result by x^(8 * bytes behind it)
+ * modulo the generator; the start value enters as crc * x^(8 len).  set_segment_bytes is a tuning and test
+ * knob: the bytes one workgroup takes in a row, rounded up to 16 KiB passes (0: chosen per call); results do
+ * not depend on it.
+ *
+ * grhip_whitening_table writes the 4096 bytes of random_mask_tuple.  They are generated, not stored: bytes
+ * 0 .. 4093 are next_bit() of gri_lfsr(0x3, 0x3FFF, 14), eight to a byte, least significant bit first, and the
+ * last two are 255, 63.
+ *
+ * packet_maker: make_packet for n payloads in one call.  create takes the access code as '0' / '1'
+ * characters, 1 .. 64 of them (more is refused, a deviation: correlate_access_code_bb takes 64; anything else
+ * in the string is refused as :121-122 raises), samples_per_symbol (int() of it is used, :146),
+ * bits_per_symbol, pad_for_usrp and whitening.  packet_bytes(payload_len) is the length of one packet;
+ * plan fills n 16-byte job records, payloads and packets back to back, and the two totals (either may be
+ * NULL; whitener_offsets NULL: 0 each); work_device, one wavefront per packet, writes the preamble A4 F2, the
+ * packed access code (leading zeros up to a whole byte), the header '!HH' of
+ * ((o & 0xf) << 12) | (L & 0x0fff) twice, the payload and its CRC-32 big-endian XORed with the mask from
+ * offset o, one 0x55, and with pad_for_usrp _npadding_bytes more (:151-172, Python 2's integer
+ * arithmetic).  As in the reference L = len + 4 <= 4096, L = 4096 puts 0 into the header, and the mask is read
+ * from the full o.  Refused: o < 0 (:124 only means to), L + o > 4096 (numpy raises), a byte modulus of 0.
+ * work_device takes the records from device memory, as plan wrote them or with out_offset moved; a record
+ * whose length or whitener_offset breaks these limits is skipped on the device: nothing is written for it.
+ * work is the same for host buffers; out_capacity below the total is refused before anything runs.
+ *
+ * packet_check: unmake_packet for messages that lie on the device.  Message m of stream s is
+ * d_recs[s * rec_stride + m] (grhip_packet_rec, the layout framer_sink_1_batch keeps), its bytes at
+ * d_pool + s * pool_stride + offset; stream s has d_counts[s * count_stride_words] messages (d_counts NULL:
+ * max_msgs each).  One wavefront per message dewhitens (if dewhitening) into d_payload_out at the same
+ * stride and offset -- d_payload_out may be d_pool -- and compares the CRC of all but the last 4 bytes with
+ * those 4, big-endian: d_ok[s * max_msgs + m] is 1 or 0; the payload is the first length - 4 bytes.  0 too
+ * for length < 4 (crc.py:31-32, (False, '')), for length + whitener_offset > 4096 (deviation: the
+ * reference's watcher thread dies on numpy's exception) and for m at or above the stream's count; nothing is
+ * written for those.  No synchronisation.
+ *
+ * grhip_framer_sink_1_batch_device_view: where the batch framer keeps its records, counts and pool on the
+ * device, in the terms of packet_check's arguments.  Addresses and strides are fixed at create; what they hold
+ * is the last run_device's, once its stream has come that far, until the next run.  Read-only.  The
+ * single-stream framer has no such view: its buffers move when they grow.
+ * ====================================================================== */
+typedef struct grhip_packet_job { unsigned whitener_offset, length, in_offset, out_offset; } grhip_packet_job;
+typedef struct grhip_packet_rec { unsigned whitener_offset, length, offset, reserved; } grhip_packet_rec;
+GRHIP_API int grhip_whitening_table(unsigned char *table, size_t capacity);
+typedef struct grhip_crc32 grhip_crc32;
+GRHIP_API int grhip_crc32_create(grhip_crc32 **h, int device);
+GRHIP_API void grhip_crc32_destroy(grhip_crc32 *h);
+GRHIP_API int grhip_crc32_set_segment_bytes(grhip_crc32 *h, long long bytes);
+GRHIP_API int grhip_crc32_compute_device(grhip_crc32 *h, const void *d_buf, long long len, unsigned *crc, void *stream);
+GRHIP_API int grhip_crc32_update_device(grhip_crc32 *h, unsigned crc_in, const void *d_buf, long long len, unsigned *crc, void *stream);
+GRHIP_API int grhip_crc32_compute(grhip_crc32 *h, const void *buf, long long len, unsigned *crc);
+GRHIP_API int grhip_crc32_update(grhip_crc32 *h, unsigned crc_in, const void *buf, long long len, unsigned *crc);
+typedef struct grhip_packet_maker grhip_packet_maker;
+GRHIP_API int grhip_packet_maker_create(grhip_packet_maker **h, const char *access_code, double samples_per_symbol, int bits_per_symbol,
+                                        int pad_for_usrp, int whitening, int device);
+GRHIP_API void grhip_packet_maker_destroy(grhip_packet_maker *h);
+GRHIP_API long long grhip_packet_maker_packet_bytes(grhip_packet_maker *h, int payload_len);
+GRHIP_API int grhip_packet_maker_plan(grhip_packet_maker *h, int n, const int *lengths, const int *whitener_offsets,
+                                      grhip_packet_job *jobs_out, long long *total_in, long long *total_out);
+GRHIP_API int grhip_packet_maker_work_device(grhip_packet_maker *h, int n, const grhip_packet_job *d_jobs, const void *d_payloads,
+                                             void *d_out, void *stream);
+GRHIP_API int grhip_packet_maker_work(grhip_packet_maker *h, int n, const int *lengths, const int *whitener_offsets, const void *payloads,
+                                      void *out, long long out_capacity, long long *total);
+typedef struct grhip_packet_check grhip_packet_check;
+GRHIP_API int grhip_packet_check_create(grhip_packet_check **h, int device);
+GRHIP_API void grhip_packet_check_destroy(grhip_packet_check *h);
+GRHIP_API int grhip_packet_check_work_device(grhip_packet_check *h, int n_streams, int max_msgs, const grhip_packet_rec *d_recs,
+                                             long long rec_stride, const unsigned *d_counts, int count_stride_words, const void *d_pool,
+                                             long long pool_stride, int dewhitening, void *d_payload_out, unsigned char *d_ok,
+                                             void *stream);
+GRHIP_API int grhip_framer_sink_1_batch_device_view(grhip_framer_sink_1_batch *h, const grhip_packet_rec **d_recs, long long *rec_stride,
+                                                    const unsigned **d_counts, int *count_stride_words, const unsigned char **d_pool,
+                                                    long long *pool_stride);
+
+/* ======================================================================
+ * gr_scrambler_bb, gr_descrambler_bb, gr_additive_scrambler_bb
+ *   replace gr_make_scrambler_bb (mask, seed, len), gr_make_descrambler_bb (mask, seed, len),
+ *       gr_make_additive_scrambler_bb (mask, seed, len, count = 0)
+ *   general/gr_scrambler_bb.cc:44-57, general/gr_descrambler_bb.cc:44-57,
+ *   general/gr_additive_scrambler_bb.cc:46-65, general/gri_lfsr.h:103-147
+ * Bytes in, bytes out, S streams back to back ([S][n], S = 1 after create; `out` may not overlap `in`; n == 0
+ * is a successful no-op; work_device does not synchronise).  Per stream the handle keeps gri_lfsr's 32-bit
+ * register on the device, additive_scrambler_bb d_bits as well, across calls: the output depends on the
+ * concatenated input alone.  set_streams restarts every stream from the seed.
+ *   scrambler_bb    out = register bit 0; the register shifts right and takes parity(reg & mask) ^ (in & 1)
+ *                   at bit len (gri_lfsr.h:120-125);
+ *   descrambler_bb  out = parity(reg & mask) ^ (in & 1); the register takes in & 1 at bit len (:127-132);
+ *   additive        out = in ^ register bit 0 -- the whole input byte is XORed with the 0/1 bit, .cc:55 --
+ *                   and after every `count` items (count > 0) the register is the seed again (.cc:56-61).
+ * len above 31 is refused (gri_lfsr.h:109-110 throws); mask and seed are taken as 32-bit patterns.
+ * GRHIP_MODE_GENERIC is one lane per stream running the reference's statements.  Every other mode is the
+ * parallel form and gives the same bytes: the step is linear over GF(2) once the register has no bit above
+ * len, where the reference's OR of the new bit is an XOR.  The descrambler's register is the len + 1 input
+ * bits before an item; the additive register does not depend on the data and is jumped to a lane's first item
+ * with the powers M^(2^j) of the one-step matrix; the scrambler's step reg' = M reg ^ in e_len is affine and
+ * is scanned (chunks from a zero register, a scan over a tile's chunks, a carry pass along a stream's tiles,
+ * the tiles again from their true registers).  Bits of the seed above len shift out within 31 steps; until
+ * then the reference's statement runs: the scrambler walks the first 32 items of a stream's life serially,
+ * the additive jump steps serially while such bits remain, the descrambler's register needs no such care.
+ * ====================================================================== */
+typedef struct grhip_scrambler_bb grhip_scrambler_bb;
+GRHIP_API int grhip_scrambler_bb_create(grhip_scrambler_bb **h, int mask, int seed, int len, int device);
+GRHIP_API void grhip_scrambler_bb_destroy(grhip_scrambler_bb *h);
+GRHIP_API int grhip_scrambler_bb_set_mode(grhip_scrambler_bb *h, int mode);
+GRHIP_API int grhip_scrambler_bb_set_streams(grhip_scrambler_bb *h, int nstreams);
+GRHIP_API int grhip_scrambler_bb_work(grhip_scrambler_bb *h, int n, const void *in, void *out);
+GRHIP_API int grhip_scrambler_bb_work_device(grhip_scrambler_bb *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_descrambler_bb grhip_descrambler_bb;
+GRHIP_API int grhip_descrambler_bb_create(grhip_descrambler_bb **h, int mask, int seed, int len, int device);
+GRHIP_API void grhip_descrambler_bb_destroy(grhip_descrambler_bb *h);
+GRHIP_API int grhip_descrambler_bb_set_mode(grhip_descrambler_bb *h, int mode);
+GRHIP_API int grhip_descrambler_bb_set_streams(grhip_descrambler_bb *h, int nstreams);
+GRHIP_API int grhip_descrambler_bb_work(grhip_descrambler_bb *h, int n, const void *in, void *out);
+GRHIP_API int grhip_descrambler_bb_work_device(grhip_descrambler_bb *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_additive_scrambler_bb grhip_additive_scrambler_bb;
+GRHIP_API int grhip_additive_scrambler_bb_create(grhip_additive_scrambler_bb **h, int mask, int seed, int len, int count, int device);
+GRHIP_API void grhip_additive_scrambler_bb_destroy(grhip_additive_scrambler_bb *h);
+GRHIP_API int grhip_additive_scrambler_bb_set_mode(grhip_additive_scrambler_bb *h, int mode);
+GRHIP_API int grhip_additive_scrambler_bb_set_streams(grhip_additive_scrambler_bb *h, int nstreams);
+GRHIP_API int grhip_additive_scrambler_bb_work(grhip_additive_scrambler_bb *h, int n, const void *in, void *out);
+GRHIP_API int grhip_additive_scrambler_bb_work_device(grhip_additive_scrambler_bb *h, int n, const void *d_in, void *d_out, void *stream);
+
+/* ======================================================================
  * gr_iir_filter_ffd
  *   replaces gr_make_iir_filter_ffd(const std::vector<double> &fftaps,
  *       const std::vector<double> &fbtaps)
