@@ -15,7 +15,9 @@ gr.rational_resampler_base_XXX, blks2.rational_resampler_XXX, gr.pfb_interpolato
 gr.pfb_synthesis_filterbank_ccf, gr.packed_to_unpacked_bb, gr.unpacked_to_packed_bb, gr.diff_encoder_bb,
 gr.chunks_to_symbols_bc, digital.generic_mod, psk_mod, qam_mod, bpsk_mod, dbpsk_mod, qpsk_mod, dqpsk_mod,
 gr.scrambler_bb, gr.descrambler_bb, gr.additive_scrambler_bb, digital.crc32 / update_crc32 (on a crc32 handle),
-packet_utils.make_packet / unmake_packet in batches as packet_maker / packet_check) with the same
+packet_utils.make_packet / unmake_packet in batches as packet_maker / packet_check, gr.frequency_modulator_fc,
+gr.bytes_to_syms, gr.char_to_float, gr.chunks_to_symbols_bf, gr.cpm.phase_response (as cpm_phase_response),
+gr.firdes.gaussian (as firdes_gaussian), digital.cpmmod_bc, digital.gmskmod_bc, digital.gmsk_mod) with the same
 constructor arguments; `work()` takes/returns numpy arrays with the
 gr_sync_block contract (history items in front of the input).
 

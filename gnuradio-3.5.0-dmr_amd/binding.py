@@ -37,6 +37,8 @@ __all__ = [
     "generic_mod", "psk_mod", "qam_mod", "bpsk_mod", "dbpsk_mod", "qpsk_mod", "dqpsk_mod",
     "scrambler_bb", "descrambler_bb", "additive_scrambler_bb", "crc32", "packet_maker", "packet_check", "random_mask_vec8",
     "default_access_code", "PACKET_JOB", "PACKET_REC",
+    "frequency_modulator_fc", "bytes_to_syms", "char_to_float", "chunks_to_symbols_bf", "cpm_phase_response", "firdes_gaussian",
+    "gmsk_mod_taps", "frequency_modulator_fc_tile", "cpmmod_bc", "gmskmod_bc", "gmsk_mod", "CPM_LRC", "CPM_LSRC", "CPM_LREC", "CPM_TFM", "CPM_GAUSSIAN",
     "iir_filter_ffd", "fm_deemph", "fm_deemph_taps", "firdes_low_pass", "fm_demod_cf", "nbfm_rx",
     "remez", "optfir_low_pass", "optfir_high_pass", "optfir_band_pass", "optfir_band_reject", "optfir_spec",
     "complex_to_mag", "am_demod_cf", "demod_10k0a3e_cf", "demod_20k0f3e_cf", "demod_200kf3e_cf",
@@ -2556,6 +2558,219 @@ class additive_scrambler_bb(_byte_block):
         _Block.__init__(self)
         self._create(C.c_int(int(mask) & 0xffffffff).value, C.c_int(int(seed) & 0xffffffff).value, int(len), int(count),
                      int(device))
+
+
+# ----------------------------------------------------------------------------
+# the continuous-phase transmitter (general/gr_frequency_modulator_fc.i, gr_bytes_to_syms.i, gr_char_to_float.i,
+# gengen/gr_chunks_to_symbols_bf.i, general/gr_cpm.i, gr-digital/swig/digital_cpmmod_bc.i, digital_gmskmod_bc.i,
+# gr-digital/python/gmsk.py)
+# ----------------------------------------------------------------------------
+CPM_LRC, CPM_LSRC, CPM_LREC, CPM_TFM, CPM_GAUSSIAN = range(5)       # gr.cpm.LRC ... gr.cpm.GAUSSIAN
+
+
+def _designed(fn, *args):
+    """the taps of a designer entry: ask for the count, then for the floats"""
+    n = _check(fn(*(args + (C.c_void_p(0), 0))))
+    t = np.zeros(n, np.float32)
+    _check(fn(*(args + (_ptr(t), n))))
+    return t
+
+
+def cpm_phase_response(type, samples_per_sym, L, beta=0.3):
+    """gr.cpm.phase_response(type, samples_per_sym, L, beta=0.3): host arithmetic, no device"""
+    return _designed(lib().grhip_cpm_phase_response, int(type), int(samples_per_sym), int(L), float(beta))
+
+
+def firdes_gaussian(gain, spb, bt, ntaps):
+    """gr.firdes.gaussian(gain, spb, bt, ntaps): host arithmetic, no device"""
+    return _designed(lib().grhip_firdes_gaussian, float(gain), float(spb), float(bt), int(ntaps))
+
+
+def gmsk_mod_taps(samples_per_symbol, bt):
+    """the taps of gmsk_mod's interpolator (gmsk.py:99-107): gaussian(1, sps, bt, 4 sps) convolved with sps ones"""
+    return _designed(lib().grhip_gmsk_mod_taps, int(samples_per_symbol), float(bt))
+
+
+class frequency_modulator_fc(_Block):
+    """gr.frequency_modulator_fc(sensitivity): phase += sensitivity * in in double, out = (cos, sin) of (float)phase;
+    after the last item of a work call |phase| > 16 pi is brought back by whole turns, so the output depends on where
+    the calls are cut, as the reference's does.  MODE_GENERIC walks serially and keeps the reference's phase bit for
+    bit; every other mode is a scan within 1e-5 + 2^-50 sum|sensitivity * in| of the double evaluation."""
+    _name = "frequency_modulator_fc"
+
+    def __init__(self, sensitivity, device=0):
+        _Block.__init__(self)
+        self._create(float(sensitivity), int(device))
+
+    def history(self):
+        return 1
+
+    def set_sensitivity(self, sens):
+        self._call("set_sensitivity", float(sens))
+
+    def sensitivity(self):
+        return self._fn("sensitivity")(self._h)                     # the float itself, not a status
+
+    def phase(self, stream=0):
+        p = C.c_double(0.0)
+        self._call("phase", int(stream), C.byref(p))
+        return p.value
+
+    def set_phase(self, phase):
+        self._call("set_phase", float(phase))
+
+    def work(self, input_items, n=None):
+        x = np.ascontiguousarray(input_items, dtype=np.float32).reshape(-1)
+        if n is None:
+            n = len(x) // self._streams
+        if len(x) < n * self._streams:
+            raise ValueError("work needs %d items, got %d" % (n * self._streams, len(x)))
+        out = np.zeros(max(n * self._streams, 1), dtype=np.complex64)
+        self._call("work", int(n), _ptr(x), _ptr(out))
+        return out[:n * self._streams]
+
+
+class _byte_to_float(_Block):
+    """streams x n bytes back to back in, _per floats out for each"""
+    _per = 1
+
+    def __init__(self, device=0):
+        _Block.__init__(self)
+        self._create(int(device))
+
+    def history(self):
+        return 1
+
+    def per_byte(self):
+        return self._per
+
+    def work(self, input_items, n=None):
+        x = np.ascontiguousarray(input_items).view(np.uint8).reshape(-1)
+        if n is None:
+            n = len(x) // self._streams
+        if len(x) < n * self._streams:
+            raise ValueError("work needs %d items, got %d" % (n * self._streams, len(x)))
+        m = n * self._streams * self.per_byte()
+        out = np.zeros(max(m, 1), dtype=np.float32)
+        self._call("work", int(n), _ptr(x), _ptr(out))
+        return out[:m]
+
+
+class bytes_to_syms(_byte_to_float):
+    """gr.bytes_to_syms(): eight floats -1 / +1 per byte, bit 7 first"""
+    _name = "bytes_to_syms"
+    _per = 8
+
+    def interpolation(self):
+        return 8
+
+
+class char_to_float(_byte_to_float):
+    """gr.char_to_float(): (float)(signed char)"""
+    _name = "char_to_float"
+
+
+class chunks_to_symbols_bf(_byte_to_float):
+    """gr.chunks_to_symbols_bf(symbol_table, D=1): n bytes in, n * D floats out per stream,
+    symbol_table[in * D : in * D + D]; an index outside the table gives zeros"""
+    _name = "chunks_to_symbols_bf"
+
+    def __init__(self, symbol_table, D=1, device=0):
+        _Block.__init__(self)
+        t = np.ascontiguousarray(symbol_table, dtype=np.float32).reshape(-1)    # owns the memory until the call returns
+        self._create(_ptr(t) if len(t) else C.c_void_p(0), len(t), int(D), int(device))
+
+    def D(self):
+        return self._call("D")
+
+    per_byte = D
+
+
+class _cpm_hier(_Block):
+    """one handle for char_to_float / bytes_to_syms -> interp_fir_filter_fff -> frequency_modulator_fc on NEW items
+    only: streams x n items back to back in, streams x n * items_out() complex items out.  A work call is a work call
+    of every inner block (the modulator's wrap falls at its end).  engine() 1 is the fused kernel (the default outside
+    MODE_GENERIC where the taps fit), 0 the blocks in a row."""
+    _per_item = 1           # symbols per input item
+
+    def engine(self):
+        return self._call("engine")
+
+    def set_engine(self, engine):
+        self._call("set_engine", int(engine))
+
+    def samples_per_symbol(self):
+        return self._call("samples_per_symbol")
+
+    def items_out(self):
+        return self._per_item * self.samples_per_symbol()
+
+    def taps(self):
+        return _designed(self._fn("filter_taps"), self._h)
+
+    def phase(self, stream=0):
+        p = C.c_double(0.0)
+        self._call("phase", int(stream), C.byref(p))
+        return p.value
+
+    def work(self, input_items, n=None, want_freq=False):
+        x = np.ascontiguousarray(input_items).view(np.uint8).reshape(-1)
+        if n is None:
+            n = len(x) // self._streams
+        if len(x) < n * self._streams:
+            raise ValueError("work needs %d items, got %d" % (n * self._streams, len(x)))
+        m = n * self._streams * self.items_out()
+        out = np.zeros(max(m, 1), dtype=np.complex64)
+        freq = np.zeros(max(m, 1), dtype=np.float32) if want_freq else None
+        self._call("work", int(n), _ptr(x), _ptr(out), _ptr(freq) if want_freq else C.c_void_p(0))
+        return (out[:m], freq[:m]) if want_freq else out[:m]
+
+    def work_device(self, n, d_in, d_out, d_freq=None, stream=None):
+        """device buffers, queued on `stream`; d_freq (optional) takes the frequency samples"""
+        return self._call("work_device", int(n), _devptr(d_in), _devptr(d_out), _devptr(d_freq), _stream(stream))
+
+
+class cpmmod_bc(_cpm_hier):
+    """digital.cpmmod_bc(type, h, samples_per_sym, L, beta=0.3): signed-char symbols in"""
+    _name = "cpmmod_bc"
+
+    def __init__(self, type, h, samples_per_sym, L, beta=0.3, device=0):
+        _Block.__init__(self)
+        self._create(int(type), float(h), int(samples_per_sym), int(L), float(beta), int(device))
+
+    @staticmethod
+    def tile():
+        return lib().grhip_cpmmod_bc_tile()
+
+
+class gmskmod_bc(_cpm_hier):
+    """digital.gmskmod_bc(samples_per_sym=2, bt=0.3, L=4): cpmmod_bc(GAUSSIAN, 0.5, samples_per_sym, L, bt)"""
+    _name = "gmskmod_bc"
+
+    def __init__(self, samples_per_sym=2, bt=0.3, L=4, device=0):
+        _Block.__init__(self)
+        self._create(int(samples_per_sym), float(bt), int(L), int(device))
+
+
+class gmsk_mod(_cpm_hier):
+    """digital.gmsk_mod(samples_per_symbol=2, bt=0.35) of gmsk.py: bytes in, eight symbols each"""
+    _name = "gmsk_mod"
+    _per_item = 8
+
+    def __init__(self, samples_per_symbol=2, bt=0.35, device=0):
+        _Block.__init__(self)
+        if int(samples_per_symbol) != samples_per_symbol:           # gmsk.py:84 truncates; a fraction is refused here
+            raise ValueError("samples_per_symbol must be an integer >= 2, is %r" % (samples_per_symbol,))
+        self._create(int(samples_per_symbol), float(bt), int(device))
+
+    @staticmethod
+    def bits_per_symbol():
+        return 1
+
+
+def frequency_modulator_fc_tile():
+    """items per workgroup of frequency_modulator_fc's scan: calls at or below it are one launch"""
+    return lib().grhip_frequency_modulator_fc_tile()
 
 
 def random_mask_vec8():

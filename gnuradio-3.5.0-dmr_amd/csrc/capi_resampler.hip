@@ -90,21 +90,10 @@ struct grhip_rs_core : ModeBlock {
 
     const char *name() const { return pad_end ? "pfb_interpolator" : interp ? "interp_fir_filter" : "rational_resampler_base"; }
 
-    // install_taps (.cc.t:102-120): filter f gets padded[f + k*I], reversed as gr_fir_XXX::set_taps stores them; bank
-    // row f = WP zeros, the reversed taps, WP zeros (resampler.hip); row I zeros
+    // install_taps (.cc.t:102-120): the bank of resampler.h's rs_bank
     int install(const std::vector<float> &padded)
     {
-        const int w = tw();
-        const size_t n = padded.size() / w;
-        nt = (int)(n / I);
-        WP = (int)(((unsigned long long)(rs_group((int)std::min<unsigned long long>(P, 64), false) - 1) * D + I - 1) / I);
-        const size_t RS = (size_t)nt + 2 * (size_t)WP;
-        std::vector<float> bank((I + 1) * RS * w, 0.f);
-        for (unsigned long long f = 0; f < I; ++f)
-            for (int k = 0; k < nt; ++k) {
-                const size_t src = f + (size_t)(nt - 1 - k) * I;
-                for (int c = 0; c < w; ++c) bank[(f * RS + WP + k) * w + c] = padded[src * w + c];
-            }
+        const std::vector<float> bank = rs_bank(padded, tw(), I, D, P, &nt, &WP);
         int rc = d_bank.reserve(bank.size() * sizeof(float));
         if (rc) return rc;
         GRHIP_HIP(hipMemcpy(d_bank.p, bank.data(), bank.size() * sizeof(float), hipMemcpyHostToDevice));

@@ -3,6 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <vector>
+
 namespace grhip {
 
 enum RsKind { RS_CCF = 0, RS_FFF = 1, RS_CCC = 2 };
@@ -49,5 +52,24 @@ int rs_config(RsKind kind, bool generic, unsigned long long I, unsigned long lon
 int rs_prepare_device(RsKind kind);
 
 int rs_launch(RsKind kind, bool generic, const RsLaunch &a, hipStream_t st);
+
+// install_taps (gr_rational_resampler_base_XXX.cc.t:102-120) as RsLaunch::bank: `padded` holds a multiple of I taps of
+// w floats each; filter f gets padded[f + k*I], reversed as gr_fir_XXX::set_taps stores them.  Row f = WP zeros, the
+// reversed taps, WP zeros; row I zeros.  Leaves the taps per filter and the pad in *nt and *WP.
+inline std::vector<float> rs_bank(const std::vector<float> &padded, int w, unsigned long long I, unsigned long long D,
+                                  unsigned long long P, int *nt, int *WP)
+{
+    const size_t n = padded.size() / w;
+    *nt = (int)(n / I);
+    *WP = (int)(((unsigned long long)(rs_group((int)std::min<unsigned long long>(P, 64), false) - 1) * D + I - 1) / I);
+    const size_t RS = (size_t)*nt + 2 * (size_t)*WP;
+    std::vector<float> bank((I + 1) * RS * w, 0.f);
+    for (unsigned long long f = 0; f < I; ++f)
+        for (int k = 0; k < *nt; ++k) {
+            const size_t src = f + (size_t)(*nt - 1 - k) * I;
+            for (int c = 0; c < w; ++c) bank[(f * RS + *WP + k) * w + c] = padded[src * w + c];
+        }
+    return bank;
+}
 
 }  // namespace grhip

@@ -50,6 +50,13 @@
 //   gr_make_scrambler_bb, gr_make_descrambler_bb, gr_make_additive_scrambler_bb
 //                                            <- the factories of the same names (general/gr_scrambler_bb.h,
 //                                               gr_descrambler_bb.h, gr_additive_scrambler_bb.h)
+//   gr_make_frequency_modulator_fc, gr_make_bytes_to_syms, gr_make_char_to_float, grhip_make_chunks_to_symbols_bf
+//                                            <- the factories of the same names (general/gr_frequency_modulator_fc.h,
+//                                               gr_bytes_to_syms.h, gr_char_to_float.h, gengen/gr_chunks_to_symbols_XX.h.t)
+//   digital_make_cpmmod_bc, digital_make_gmskmod_bc, grhip_make_gmsk_mod
+//                                            <- digital_make_cpmmod_bc, digital_make_gmskmod_bc (gr-digital/lib) and
+//                                               digital.gmsk_mod (gr-digital/python/gmsk.py:55-120), one block each;
+//                                               grhip_cpm_phase_response_taps is gr_cpm::phase_response
 //   gr_make_agc_cc / _ff, gr_make_agc2_cc / _ff
 //                                            <- the factories of the same names (general/gr_agc_cc.h, gr_agc_ff.h,
 //                                               gr_agc2_cc.h, gr_agc2_ff.h)
@@ -2274,6 +2281,170 @@ inline grhip_descrambler_bb_sptr gr_make_descrambler_bb(int mask, int seed, int 
 inline grhip_additive_scrambler_bb_sptr gr_make_additive_scrambler_bb(int mask, int seed, int len, int count = 0, int device = 0)
 {
     return grhip_detail::factory::make<grhip_additive_scrambler_bb_blk>(mask, seed, len, count, device);
+}
+
+// ---------------------------------------------------------------------------
+// The continuous-phase transmitter.  gr_frequency_modulator_fc (general/gr_frequency_modulator_fc.h:32-56): a
+// gr_sync_block, float in, complex out; the phase lives in the handle and is wrapped at the end of every work call, as
+// the reference's, so the output depends on where the scheduler cuts.  gr_bytes_to_syms (general/gr_bytes_to_syms.h),
+// gr_char_to_float (general/gr_char_to_float.h) and gr_chunks_to_symbols_bf keep nothing.  One stream each.
+// ---------------------------------------------------------------------------
+class grhip_frequency_modulator_fc_blk : public GRHIP_BLOCK(gr_sync_block, frequency_modulator_fc) {
+    friend struct grhip_detail::factory;
+    grhip_frequency_modulator_fc_blk(double sensitivity, int device)
+        : block("frequency_modulator_fc", gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(gr_complex)))
+    {
+        grhip_detail::check(grhip_frequency_modulator_fc_create(d_h.out(), sensitivity, device));
+    }
+public:
+    void set_sensitivity(float sens) { grhip_detail::check(grhip_frequency_modulator_fc_set_sensitivity(d_h, sens)); }
+    float sensitivity() const { return grhip_frequency_modulator_fc_sensitivity(d_h); }
+    double phase() const
+    {
+        double p = 0.0;
+        grhip_detail::check(grhip_frequency_modulator_fc_phase(d_h, 0, &p));
+        return p;
+    }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(grhip_frequency_modulator_fc_work(d_h, noutput_items, in[0], out[0]));
+        return noutput_items;
+    }
+};
+typedef boost::shared_ptr<grhip_frequency_modulator_fc_blk> grhip_frequency_modulator_fc_sptr;
+inline grhip_frequency_modulator_fc_sptr gr_make_frequency_modulator_fc(double sensitivity, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_frequency_modulator_fc_blk>(sensitivity, device);
+}
+
+class grhip_bytes_to_syms_blk : public GRHIP_BLOCK(gr_sync_interpolator, bytes_to_syms) {
+    friend struct grhip_detail::factory;
+    explicit grhip_bytes_to_syms_blk(int device)
+        : block("bytes_to_syms", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(float)), 8)
+    {
+        grhip_detail::check(grhip_bytes_to_syms_create(d_h.out(), device));
+    }
+public:
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(grhip_bytes_to_syms_work(d_h, noutput_items / 8, in[0], out[0]));
+        return noutput_items;
+    }
+};
+typedef boost::shared_ptr<grhip_bytes_to_syms_blk> grhip_bytes_to_syms_sptr;
+inline grhip_bytes_to_syms_sptr gr_make_bytes_to_syms(int device = 0) { return grhip_detail::factory::make<grhip_bytes_to_syms_blk>(device); }
+
+class grhip_char_to_float_blk : public GRHIP_BLOCK(gr_sync_block, char_to_float) {
+    friend struct grhip_detail::factory;
+    explicit grhip_char_to_float_blk(int device)
+        : block("gr_char_to_float", gr_make_io_signature(1, 1, sizeof(char)), gr_make_io_signature(1, 1, sizeof(float)))
+    {
+        grhip_detail::check(grhip_char_to_float_create(d_h.out(), device));
+    }
+public:
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(grhip_char_to_float_work(d_h, noutput_items, in[0], out[0]));
+        return noutput_items;
+    }
+};
+typedef boost::shared_ptr<grhip_char_to_float_blk> grhip_char_to_float_sptr;
+inline grhip_char_to_float_sptr gr_make_char_to_float(int device = 0) { return grhip_detail::factory::make<grhip_char_to_float_blk>(device); }
+
+class grhip_chunks_to_symbols_bf_blk : public GRHIP_BLOCK(gr_sync_interpolator, chunks_to_symbols_bf) {
+    friend struct grhip_detail::factory;
+    std::vector<float> d_symbol_table;
+    grhip_chunks_to_symbols_bf_blk(const std::vector<float> &symbol_table, const int D, int device)
+        : block("chunks_to_symbols_bf", gr_make_io_signature(1, 1, sizeof(unsigned char)), gr_make_io_signature(1, 1, sizeof(float)),
+                (unsigned)(D < 1 ? 1 : D)),
+          d_symbol_table(symbol_table)
+    {
+        grhip_detail::check(grhip_chunks_to_symbols_bf_create(d_h.out(), symbol_table.data(), symbol_table.size(), D, device));
+    }
+public:
+    int D() const { return (int)interpolation(); }
+    std::vector<float> symbol_table() const { return d_symbol_table; }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(grhip_chunks_to_symbols_bf_work(d_h, noutput_items / (int)interpolation(), in[0], out[0]));
+        return noutput_items;
+    }
+};
+typedef boost::shared_ptr<grhip_chunks_to_symbols_bf_blk> grhip_chunks_to_symbols_bf_sptr;
+inline grhip_chunks_to_symbols_bf_sptr grhip_make_chunks_to_symbols_bf(const std::vector<float> &symbol_table, const int D = 1, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_chunks_to_symbols_bf_blk>(symbol_table, D, device);
+}
+
+// gr_cpm::phase_response (general/gr_cpm.h:40-74): host arithmetic, no device
+inline std::vector<float> grhip_cpm_phase_response_taps(int type, unsigned samples_per_sym, unsigned L, double beta = 0.3)
+{
+    const int n = grhip_cpm_phase_response(type, samples_per_sym, L, beta, nullptr, 0);
+    grhip_detail::check(n);
+    std::vector<float> t((size_t)n);
+    grhip_detail::check(grhip_cpm_phase_response(type, samples_per_sym, L, beta, t.data(), t.size()));
+    return t;
+}
+
+// digital_cpmmod_bc, digital_gmskmod_bc (gr-digital/lib/digital_cpmmod_bc.h:33-95, digital_gmskmod_bc.h:32-60) and gmsk_mod
+// (gr-digital/python/gmsk.py:55-120), each one gr_sync_interpolator on new items only: symbols (gmsk_mod: bytes) in,
+// samples_per_sym (8 * samples_per_symbol) complex items out for each.  A work call of the block is a work call of the
+// inner modulator: its phase wrap falls where the scheduler cuts.  One stream each.
+template <class T>
+class grhip_cpm_hier_blk : public grhip_detail::block<gr_sync_interpolator, typename T::H, T::destroy, T::set_mode> {
+    friend struct grhip_detail::factory;
+    // per: output items per input item; then the arguments of T::create
+    template <class... A> explicit grhip_cpm_hier_blk(unsigned per, A... args)
+        : grhip_cpm_hier_blk::block(T::name, gr_make_io_signature(1, 1, sizeof(char)), gr_make_io_signature(1, 1, sizeof(gr_complex)), per)
+    {
+        grhip_detail::check(T::create(this->d_h.out(), args...));
+    }
+public:
+    int engine() const { return T::engine(this->d_h); }
+    void set_engine(int engine) { grhip_detail::check(T::set_engine(this->d_h, engine)); }
+    int samples_per_symbol() const { return T::samples_per_symbol(this->d_h); }
+    std::vector<float> get_taps() const                                        // digital_cpmmod_bc.h:92
+    {
+        std::vector<float> t((size_t)T::filter_taps(this->d_h, nullptr, 0));
+        T::filter_taps(this->d_h, t.data(), t.size());
+        return t;
+    }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(T::work(this->d_h, noutput_items / (int)this->interpolation(), in[0], out[0], nullptr));
+        return noutput_items;
+    }
+};
+namespace grhip_detail {
+#define GRHIP_CPM_FNS(NAME)                                                                                            \
+    struct NAME##_fns {                                                                                               \
+        typedef grhip_##NAME H;                                                                                       \
+        static constexpr const char *name = #NAME;                                                                    \
+        GRHIP_FN(NAME, create); GRHIP_FN(NAME, destroy); GRHIP_FN(NAME, set_mode); GRHIP_FN(NAME, work);              \
+        GRHIP_FN(NAME, engine); GRHIP_FN(NAME, set_engine); GRHIP_FN(NAME, samples_per_symbol); GRHIP_FN(NAME, filter_taps); \
+    };
+GRHIP_CPM_FNS(cpmmod_bc)
+GRHIP_CPM_FNS(gmskmod_bc)
+GRHIP_CPM_FNS(gmsk_mod)
+#undef GRHIP_CPM_FNS
+}  // namespace grhip_detail
+typedef grhip_cpm_hier_blk<grhip_detail::cpmmod_bc_fns> grhip_cpmmod_bc_blk;
+typedef grhip_cpm_hier_blk<grhip_detail::gmskmod_bc_fns> grhip_gmskmod_bc_blk;
+typedef grhip_cpm_hier_blk<grhip_detail::gmsk_mod_fns> grhip_gmsk_mod_blk;
+typedef boost::shared_ptr<grhip_cpmmod_bc_blk> grhip_cpmmod_bc_sptr;
+typedef boost::shared_ptr<grhip_gmskmod_bc_blk> grhip_gmskmod_bc_sptr;
+typedef boost::shared_ptr<grhip_gmsk_mod_blk> grhip_gmsk_mod_sptr;
+inline grhip_cpmmod_bc_sptr digital_make_cpmmod_bc(int type, float h, unsigned samples_per_sym, unsigned L, double beta = 0.3, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_cpmmod_bc_blk>(samples_per_sym, type, h, samples_per_sym, L, beta, device);
+}
+inline grhip_gmskmod_bc_sptr digital_make_gmskmod_bc(unsigned samples_per_sym = 2, double bt = 0.3, unsigned L = 4, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_gmskmod_bc_blk>(samples_per_sym, samples_per_sym, bt, L, device);
+}
+inline grhip_gmsk_mod_sptr grhip_make_gmsk_mod(int samples_per_symbol = 2, double bt = 0.35, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_gmsk_mod_blk>(8u * (unsigned)(samples_per_symbol < 1 ? 1 : samples_per_symbol), samples_per_symbol, bt, device);
 }
 
 // ---------------------------------------------------------------------------

@@ -2606,6 +2606,177 @@ GRHIP_API int grhip_additive_scrambler_bb_work(grhip_additive_scrambler_bb *h, i
 GRHIP_API int grhip_additive_scrambler_bb_work_device(grhip_additive_scrambler_bb *h, int n, const void *d_in, void *d_out, void *stream);
 
 /* ======================================================================
+ * gr_frequency_modulator_fc
+ *   replaces gr_make_frequency_modulator_fc (double sensitivity)
+ *   general/gr_frequency_modulator_fc.cc:49-72 (work), .h:42-52 (d_sensitivity, d_phase, set_sensitivity)
+ * Float in, complex out, S streams back to back ([S][n], S = 1 after create; `out` may not overlap `in`; n == 0
+ * is a successful no-op; work_device does not synchronise).  Per item phase += sensitivity * in[i] in double
+ * and out[i] = (cos, sin) of (float)phase (.cc:58-61).  After the LAST item of a work call only, |phase| > 16 pi
+ * becomes phase - trunc(phase / 2 pi) * 2 pi (.cc:66-69).  The float cast sees the unwrapped phase inside a
+ * call, so THE OUTPUT DEPENDS ON WHERE THE CALLS ARE CUT, exactly as the reference's does on its scheduler's
+ * calls: a stream run as one call, and the same stream cut in two, differ by float roundings of the phase
+ * wherever it has passed 16 pi.  The phase is one double per stream on the device; set_streams zeroes it.
+ * set_sensitivity takes a float and widens it, as .h:51 does, and holds from the next work call; sensitivity()
+ * returns the float of .h:52.  phase() / set_phase() read one stream's d_phase and set every stream's.
+ *   GRHIP_MODE_GENERIC  one wavefront per stream walks the recurrence in the reference's order, every double
+ *       operation rounded once; out = ((float)cos((double)p), (float)sin((double)p)) of p = (float)phase.  The
+ *       phase state equals the reference's bit for bit, across cuts; the outputs are within one float ulp per
+ *       component of glibc's sincosf, which is not the rounded double sine (as for pll_refout_cc).
+ *   every other mode  a scan in three launches: sums of sensitivity * x in double per tile of
+ *       grhip_frequency_modulator_fc_tile() items, the tiles' start phases from the call's entry phase, then a
+ *       workgroup scan per tile; phi - 2 pi rint(phi / 2 pi) in double before the float cast and a float
+ *       polynomial sine / cosine.  Calls of at most one tile are one launch.  Every output lies within
+ *       1e-5 + 2^-50 * Phi of exp(j phi) evaluated in double, Phi = sum |sensitivity * x| over the call plus
+ *       |entry phase| -- inside long calls that is closer than the reference, whose float cast loses
+ *       2^-24 |phase|.  The wrap rule is applied to the call's total, so the state follows GENERIC within
+ *       n * 2^-53 * Phi.
+ * From a stream's first non-finite product on, every output of that stream is NaN in both modes and its state
+ * is non-finite; other streams are untouched.
+ * ====================================================================== */
+typedef struct grhip_frequency_modulator_fc grhip_frequency_modulator_fc;
+GRHIP_API int grhip_frequency_modulator_fc_create(grhip_frequency_modulator_fc **h, double sensitivity, int device);
+GRHIP_API void grhip_frequency_modulator_fc_destroy(grhip_frequency_modulator_fc *h);
+GRHIP_API int grhip_frequency_modulator_fc_set_mode(grhip_frequency_modulator_fc *h, int mode);
+GRHIP_API int grhip_frequency_modulator_fc_set_streams(grhip_frequency_modulator_fc *h, int nstreams);
+GRHIP_API int grhip_frequency_modulator_fc_work(grhip_frequency_modulator_fc *h, int n, const void *in, void *out);
+GRHIP_API int grhip_frequency_modulator_fc_work_device(grhip_frequency_modulator_fc *h, int n, const void *d_in, void *d_out, void *stream);
+GRHIP_API int grhip_frequency_modulator_fc_set_sensitivity(grhip_frequency_modulator_fc *h, float sensitivity);
+GRHIP_API float grhip_frequency_modulator_fc_sensitivity(grhip_frequency_modulator_fc *h);
+GRHIP_API int grhip_frequency_modulator_fc_phase(grhip_frequency_modulator_fc *h, int stream, double *phase);
+GRHIP_API int grhip_frequency_modulator_fc_set_phase(grhip_frequency_modulator_fc *h, double phase);
+GRHIP_API int grhip_frequency_modulator_fc_tile(void);
+
+/* ======================================================================
+ * gr_bytes_to_syms, gr_char_to_float, gr_chunks_to_symbols_bf
+ *   replace gr_make_bytes_to_syms (), gr_make_char_to_float (),
+ *       gr_make_chunks_to_symbols_bf (const std::vector<float> &symbol_table, const int D = 1)
+ *   general/gr_bytes_to_syms.cc:45-71, general/gr_char_to_float.cc:42-53 with general/gri_char_to_float.cc:26-40,
+ *   gengen/gr_chunks_to_symbols_XX.cc.t:51-74
+ * Bytes in, floats out, S streams back to back, one lane per output item, the reference's values bit for bit
+ * in every mode; nothing is kept between calls.
+ *   bytes_to_syms         n bytes in, 8 n floats out: bit 7 first, 0 -> -1, 1 -> +1
+ *   char_to_float         out = (float)(signed char)in
+ *   chunks_to_symbols_bf  n bytes in, n * D floats out, symbol_table[in * D + d]; an index whose D entries do
+ *                         not lie inside the table gives zeros (the reference asserts), as chunks_to_symbols_bc;
+ *                         at most 65536 entries, D >= 1
+ * ====================================================================== */
+typedef struct grhip_bytes_to_syms grhip_bytes_to_syms;
+GRHIP_API int grhip_bytes_to_syms_create(grhip_bytes_to_syms **h, int device);
+GRHIP_API void grhip_bytes_to_syms_destroy(grhip_bytes_to_syms *h);
+GRHIP_API int grhip_bytes_to_syms_set_mode(grhip_bytes_to_syms *h, int mode);
+GRHIP_API int grhip_bytes_to_syms_set_streams(grhip_bytes_to_syms *h, int nstreams);
+GRHIP_API int grhip_bytes_to_syms_work(grhip_bytes_to_syms *h, int n, const void *in, void *out);
+GRHIP_API int grhip_bytes_to_syms_work_device(grhip_bytes_to_syms *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_char_to_float grhip_char_to_float;
+GRHIP_API int grhip_char_to_float_create(grhip_char_to_float **h, int device);
+GRHIP_API void grhip_char_to_float_destroy(grhip_char_to_float *h);
+GRHIP_API int grhip_char_to_float_set_mode(grhip_char_to_float *h, int mode);
+GRHIP_API int grhip_char_to_float_set_streams(grhip_char_to_float *h, int nstreams);
+GRHIP_API int grhip_char_to_float_work(grhip_char_to_float *h, int n, const void *in, void *out);
+GRHIP_API int grhip_char_to_float_work_device(grhip_char_to_float *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_chunks_to_symbols_bf grhip_chunks_to_symbols_bf;
+GRHIP_API int grhip_chunks_to_symbols_bf_create(grhip_chunks_to_symbols_bf **h, const float *symbol_table, size_t nsymbols, int D, int device);
+GRHIP_API void grhip_chunks_to_symbols_bf_destroy(grhip_chunks_to_symbols_bf *h);
+GRHIP_API int grhip_chunks_to_symbols_bf_set_mode(grhip_chunks_to_symbols_bf *h, int mode);
+GRHIP_API int grhip_chunks_to_symbols_bf_set_streams(grhip_chunks_to_symbols_bf *h, int nstreams);
+GRHIP_API int grhip_chunks_to_symbols_bf_work(grhip_chunks_to_symbols_bf *h, int n, const void *in, void *out);
+GRHIP_API int grhip_chunks_to_symbols_bf_work_device(grhip_chunks_to_symbols_bf *h, int n, const void *d_in, void *d_out, void *stream);
+GRHIP_API int grhip_chunks_to_symbols_bf_D(grhip_chunks_to_symbols_bf *h);
+
+/* ======================================================================
+ * gr_cpm::phase_response, gr_firdes::gaussian, the taps of gmsk_mod: host arithmetic, no device
+ *   replace gr_cpm::phase_response (type, samples_per_sym, L, beta = 0.3)   general/gr_cpm.cc:43-218
+ *       gr_firdes::gaussian (gain, spb, bt, ntaps)                          general/gr_firdes.cc:571-594
+ *       numpy.convolve(gaussian(1, sps, bt, 4 sps), (1,) * sps)             gr-digital/python/gmsk.py:99-107
+ * Each returns the tap count and, when `taps` is not null, writes that many floats (`capacity` is the room at
+ * `taps`; too little is GRHIP_EINVAL).  The statements and types are the reference's; boost::math::erf is
+ * std::erf.  type: GRHIP_CPM_LRC .. GRHIP_CPM_GAUSSIAN; any other value gives LREC with L = 1, as
+ * gr_cpm.cc:214 does.
+ * Refused with GRHIP_EINVAL: samples_per_sym * L == 0; more than 4096 taps (samples_per_sym * L, ntaps,
+ * 5 * samples_per_symbol - 1); ntaps < 1; samples_per_symbol < 2 for the gmsk taps (gmsk.py:87-88 raises); a
+ * non-finite beta, gain, spb or bt.
+ * ====================================================================== */
+#define GRHIP_CPM_LRC 0
+#define GRHIP_CPM_LSRC 1
+#define GRHIP_CPM_LREC 2
+#define GRHIP_CPM_TFM 3
+#define GRHIP_CPM_GAUSSIAN 4
+GRHIP_API int grhip_cpm_phase_response(int type, unsigned samples_per_sym, unsigned L, double beta, float *taps, size_t capacity);
+GRHIP_API int grhip_firdes_gaussian(double gain, double spb, double bt, int ntaps, float *taps, size_t capacity);
+GRHIP_API int grhip_gmsk_mod_taps(int samples_per_symbol, double bt, float *taps, size_t capacity);
+
+/* ======================================================================
+ * digital_cpmmod_bc, digital_gmskmod_bc, gmsk_mod
+ *   replace digital_make_cpmmod_bc (type, h, samples_per_sym, L, beta = 0.3)     gr-digital/lib/digital_cpmmod_bc.cc:30-72
+ *       digital_make_gmskmod_bc (samples_per_sym = 2, bt = 0.3, L = 4)           gr-digital/lib/digital_gmskmod_bc.cc:31-45
+ *       gmsk_mod (samples_per_symbol = 2, bt = 0.35)                             gr-digital/python/gmsk.py:55-120
+ * One handle each for the hier block, on NEW items only, S streams back to back:
+ *   cpmmod_bc   char_to_float -> interp_fir_filter_fff(samples_per_sym, phase_response(type, ...)) ->
+ *               frequency_modulator_fc(pi * h): n signed-char symbols in, n * samples_per_sym items out
+ *   gmskmod_bc  cpmmod_bc(GAUSSIAN, 0.5, samples_per_sym, L, bt)
+ *   gmsk_mod    bytes_to_syms -> interp_fir_filter_fff(sps, gmsk_mod_taps(sps, bt)) ->
+ *               frequency_modulator_fc((pi / 2) / sps): n bytes in, 8 * n * sps items out
+ * Per stream the interpolator's last nt - 1 symbols (nt taps per filter; zeros at the start, as the scheduler's
+ * history) and the modulator's phase stay on the device; set_streams restarts every stream.  A work call of the
+ * handle is a work call of every inner block, so the modulator's end-of-call wrap (above) falls where the
+ * handle's calls end and THE OUTPUT DEPENDS ON THE CUTS as the inner modulator's does.  freq_out / d_freq_out
+ * is optional (null: not wanted): the interpolator's output, [S][outputs] floats, the second output of
+ * digital_cpmmod_bc's signature.
+ * The phase integrates the frequency samples, so both engines form them in gr_fir_fff_generic's order in every
+ * mode: they are the reference's floats bit for bit.
+ *   engine 0  the library's blocks in a row; the only engine in GRHIP_MODE_GENERIC, where the handle equals the
+ *             composition of char_to_float / bytes_to_syms, interp_fir_filter_fff and frequency_modulator_fc bit
+ *             for bit, whatever the cuts.
+ *   engine 1  the default in every other mode when the taps fit: at most 16 taps per filter and at most 1024
+ *             taps after padding to a multiple of samples_per_sym (cpmmod_bc: L <= 16, samples_per_sym * L <=
+ *             1024; gmsk_mod: sps <= 204).  One fused kernel behind a carry pre-pass: per tile of
+ *             grhip_cpmmod_bc_tile() outputs the symbols go to LDS, each output's frequency sample is nt products
+ *             against taps in LDS, and the tile is scanned in double as frequency_modulator_fc does; 1 / sps + 8
+ *             bytes move per output.  Within frequency_modulator_fc's bound of the double evaluation.
+ *   set_engine(1) where the taps do not fit is GRHIP_EINVAL; engine() reports the engine the next call runs.
+ * Refused: a type outside GRHIP_CPM_LRC .. GRHIP_CPM_GAUSSIAN (digital_cpmmod_bc.cc:64-65 throws); what the
+ * designers refuse; gmsk_mod's samples_per_symbol < 2; outputs per stream that do not fit an int.
+ * Not built: cpm_mod of gr-digital/python/cpm.py (on pfb_arb_resampler_fff), cpfsk_bc, vco_f, gmsk_demod.
+ * ====================================================================== */
+typedef struct grhip_cpmmod_bc grhip_cpmmod_bc;
+GRHIP_API int grhip_cpmmod_bc_create(grhip_cpmmod_bc **h, int type, float h_index, unsigned samples_per_sym, unsigned L, double beta, int device);
+GRHIP_API void grhip_cpmmod_bc_destroy(grhip_cpmmod_bc *h);
+GRHIP_API int grhip_cpmmod_bc_set_mode(grhip_cpmmod_bc *h, int mode);
+GRHIP_API int grhip_cpmmod_bc_set_streams(grhip_cpmmod_bc *h, int nstreams);
+GRHIP_API int grhip_cpmmod_bc_set_engine(grhip_cpmmod_bc *h, int engine);
+GRHIP_API int grhip_cpmmod_bc_engine(grhip_cpmmod_bc *h);
+GRHIP_API int grhip_cpmmod_bc_samples_per_symbol(grhip_cpmmod_bc *h);
+GRHIP_API int grhip_cpmmod_bc_filter_taps(grhip_cpmmod_bc *h, float *taps, size_t capacity);
+GRHIP_API int grhip_cpmmod_bc_phase(grhip_cpmmod_bc *h, int stream, double *phase);
+GRHIP_API int grhip_cpmmod_bc_work(grhip_cpmmod_bc *h, int n, const void *in, void *out, void *freq_out);
+GRHIP_API int grhip_cpmmod_bc_work_device(grhip_cpmmod_bc *h, int n, const void *d_in, void *d_out, void *d_freq_out, void *stream);
+GRHIP_API int grhip_cpmmod_bc_tile(void);
+typedef struct grhip_gmskmod_bc grhip_gmskmod_bc;
+GRHIP_API int grhip_gmskmod_bc_create(grhip_gmskmod_bc **h, unsigned samples_per_sym, double bt, unsigned L, int device);
+GRHIP_API void grhip_gmskmod_bc_destroy(grhip_gmskmod_bc *h);
+GRHIP_API int grhip_gmskmod_bc_set_mode(grhip_gmskmod_bc *h, int mode);
+GRHIP_API int grhip_gmskmod_bc_set_streams(grhip_gmskmod_bc *h, int nstreams);
+GRHIP_API int grhip_gmskmod_bc_set_engine(grhip_gmskmod_bc *h, int engine);
+GRHIP_API int grhip_gmskmod_bc_engine(grhip_gmskmod_bc *h);
+GRHIP_API int grhip_gmskmod_bc_samples_per_symbol(grhip_gmskmod_bc *h);
+GRHIP_API int grhip_gmskmod_bc_filter_taps(grhip_gmskmod_bc *h, float *taps, size_t capacity);
+GRHIP_API int grhip_gmskmod_bc_phase(grhip_gmskmod_bc *h, int stream, double *phase);
+GRHIP_API int grhip_gmskmod_bc_work(grhip_gmskmod_bc *h, int n, const void *in, void *out, void *freq_out);
+GRHIP_API int grhip_gmskmod_bc_work_device(grhip_gmskmod_bc *h, int n, const void *d_in, void *d_out, void *d_freq_out, void *stream);
+typedef struct grhip_gmsk_mod grhip_gmsk_mod;
+GRHIP_API int grhip_gmsk_mod_create(grhip_gmsk_mod **h, int samples_per_symbol, double bt, int device);
+GRHIP_API void grhip_gmsk_mod_destroy(grhip_gmsk_mod *h);
+GRHIP_API int grhip_gmsk_mod_set_mode(grhip_gmsk_mod *h, int mode);
+GRHIP_API int grhip_gmsk_mod_set_streams(grhip_gmsk_mod *h, int nstreams);
+GRHIP_API int grhip_gmsk_mod_set_engine(grhip_gmsk_mod *h, int engine);
+GRHIP_API int grhip_gmsk_mod_engine(grhip_gmsk_mod *h);
+GRHIP_API int grhip_gmsk_mod_samples_per_symbol(grhip_gmsk_mod *h);
+GRHIP_API int grhip_gmsk_mod_filter_taps(grhip_gmsk_mod *h, float *taps, size_t capacity);
+GRHIP_API int grhip_gmsk_mod_phase(grhip_gmsk_mod *h, int stream, double *phase);
+GRHIP_API int grhip_gmsk_mod_work(grhip_gmsk_mod *h, int n, const void *in, void *out, void *freq_out);
+GRHIP_API int grhip_gmsk_mod_work_device(grhip_gmsk_mod *h, int n, const void *d_in, void *d_out, void *d_freq_out, void *stream);
+
+/* ======================================================================
  * gr_iir_filter_ffd
  *   replaces gr_make_iir_filter_ffd(const std::vector<double> &fftaps,
  *       const std::vector<double> &fbtaps)
