@@ -17,7 +17,8 @@ gr.chunks_to_symbols_bc, digital.generic_mod, psk_mod, qam_mod, bpsk_mod, dbpsk_
 gr.scrambler_bb, gr.descrambler_bb, gr.additive_scrambler_bb, digital.crc32 / update_crc32 (on a crc32 handle),
 packet_utils.make_packet / unmake_packet in batches as packet_maker / packet_check, gr.frequency_modulator_fc,
 gr.bytes_to_syms, gr.char_to_float, gr.chunks_to_symbols_bf, gr.cpm.phase_response (as cpm_phase_response),
-gr.firdes.gaussian (as firdes_gaussian), digital.cpmmod_bc, digital.gmskmod_bc, digital.gmsk_mod) with the same
+gr.firdes.gaussian (as firdes_gaussian), digital.cpmmod_bc, digital.gmskmod_bc, digital.gmsk_mod, trellis.fsm,
+trellis.encoder_XX / metrics_X / constellation_metrics_cf / viterbi_X / viterbi_combined_XX (as trellis_*)) with the same
 constructor arguments; `work()` takes/returns numpy arrays with the
 gr_sync_block contract (history items in front of the input).
 

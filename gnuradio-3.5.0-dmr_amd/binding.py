@@ -39,6 +39,13 @@ __all__ = [
     "default_access_code", "PACKET_JOB", "PACKET_REC",
     "frequency_modulator_fc", "bytes_to_syms", "char_to_float", "chunks_to_symbols_bf", "cpm_phase_response", "firdes_gaussian",
     "gmsk_mod_taps", "frequency_modulator_fc_tile", "cpmmod_bc", "gmskmod_bc", "gmsk_mod", "CPM_LRC", "CPM_LSRC", "CPM_LREC", "CPM_TFM", "CPM_GAUSSIAN",
+    "fsm", "trellis_encoder_bb", "trellis_encoder_bs", "trellis_encoder_bi", "trellis_encoder_ss", "trellis_encoder_si",
+    "trellis_encoder_ii", "trellis_metrics_s", "trellis_metrics_i", "trellis_metrics_f", "trellis_metrics_c",
+    "trellis_constellation_metrics_cf", "trellis_viterbi_b", "trellis_viterbi_s", "trellis_viterbi_i",
+    "trellis_viterbi_combined_sb", "trellis_viterbi_combined_ss", "trellis_viterbi_combined_si", "trellis_viterbi_combined_ib",
+    "trellis_viterbi_combined_is", "trellis_viterbi_combined_ii", "trellis_viterbi_combined_fb", "trellis_viterbi_combined_fs",
+    "trellis_viterbi_combined_fi", "trellis_viterbi_combined_cb", "trellis_viterbi_combined_cs", "trellis_viterbi_combined_ci",
+    "TRELLIS_EUCLIDEAN", "TRELLIS_HARD_SYMBOL", "TRELLIS_HARD_BIT",
     "iir_filter_ffd", "fm_deemph", "fm_deemph_taps", "firdes_low_pass", "fm_demod_cf", "nbfm_rx",
     "remez", "optfir_low_pass", "optfir_high_pass", "optfir_band_pass", "optfir_band_reject", "optfir_spec",
     "complex_to_mag", "am_demod_cf", "demod_10k0a3e_cf", "demod_20k0f3e_cf", "demod_200kf3e_cf",
@@ -2771,6 +2778,388 @@ class gmsk_mod(_cpm_hier):
 def frequency_modulator_fc_tile():
     """items per workgroup of frequency_modulator_fc's scan: calls at or below it are one launch"""
     return lib().grhip_frequency_modulator_fc_tile()
+
+
+# ----------------------------------------------------------------------------
+# gr-trellis (gr-trellis/src/lib/fsm.i, trellis.i): fsm, trellis_encoder_XX, trellis_metrics_X,
+# trellis_constellation_metrics_cf, trellis_viterbi_X
+# ----------------------------------------------------------------------------
+TRELLIS_EUCLIDEAN, TRELLIS_HARD_SYMBOL, TRELLIS_HARD_BIT = 200, 201, 202       # digital_metric_type.h:26-28
+
+
+def _ints(v):
+    return np.ascontiguousarray(v, dtype=np.int32).reshape(-1)
+
+
+class fsm(object):
+    """trellis.fsm: a host object, no device needed.  The reference's constructors by their arguments:
+    fsm(I, S, O, NS, OS); fsm(name) with the path of an .fsm file (fsm(text=...) takes the file's text);
+    fsm(k, n, G) the binary convolutional code; fsm(mod_size, ch_length) ISI; fsm(P, M, L) CPM;
+    fsm(FSM1, FSM2) the joint trellis; fsm(FSM, n) radix-n; fsm(FSM) a copy."""
+
+    def __init__(self, *args, **kw):
+        self._h = C.c_void_p(0)
+        L = lib()
+        h = C.byref(self._h)
+        if kw:
+            if args or list(kw) != ["text"]:
+                raise TypeError("fsm(text=...) takes nothing else")
+            _check(L.grhip_fsm_create_text(h, str(kw["text"]).encode()))
+        elif len(args) == 5:
+            ns, os_ = _ints(args[3]), _ints(args[4])
+            _check(L.grhip_fsm_create(h, int(args[0]), int(args[1]), int(args[2]), _ptr(ns), len(ns), _ptr(os_), len(os_)))
+        elif len(args) == 1 and isinstance(args[0], fsm):
+            f = args[0]
+            ns, os_ = f.NS(), f.OS()
+            _check(L.grhip_fsm_create(h, f.I(), f.S(), f.O(), _ptr(ns), len(ns), _ptr(os_), len(os_)))
+        elif len(args) == 1:
+            _check(L.grhip_fsm_create_file(h, os.fsencode(args[0])))
+        elif len(args) == 2 and isinstance(args[0], fsm) and isinstance(args[1], fsm):
+            _check(L.grhip_fsm_create_joint(h, args[0]._h, args[1]._h))
+        elif len(args) == 2 and isinstance(args[0], fsm):
+            _check(L.grhip_fsm_create_radix(h, args[0]._h, int(args[1])))
+        elif len(args) == 2:
+            _check(L.grhip_fsm_create_isi(h, int(args[0]), int(args[1])))
+        elif len(args) == 3 and np.ndim(args[2]) > 0:
+            g = _ints(args[2])
+            _check(L.grhip_fsm_create_generator(h, int(args[0]), int(args[1]), _ptr(g), len(g)))
+        elif len(args) == 3:
+            _check(L.grhip_fsm_create_cpm(h, int(args[0]), int(args[1]), int(args[2])))
+        else:
+            raise TypeError("fsm: no constructor takes %d arguments" % len(args))
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().grhip_fsm_destroy(self._h)
+                self._h = C.c_void_p(0)
+        except Exception:
+            pass
+
+    def _int(self, name):
+        return _check(getattr(lib(), "grhip_fsm_" + name)(self._h))
+
+    def _table(self, name, *state):
+        fn = getattr(lib(), "grhip_fsm_" + name)
+        n = _check(fn(self._h, *(state + (C.c_void_p(0), 0))))
+        a = np.zeros(max(n, 1), np.int32)
+        _check(fn(self._h, *(state + (_ptr(a), n))))
+        return a[:n]
+
+    def I(self):
+        return self._int("I")
+
+    def S(self):
+        return self._int("S")
+
+    def O(self):
+        return self._int("O")
+
+    def connected(self):
+        """False where the reference prints "FSM appears to be disconnected" """
+        return bool(self._int("connected"))
+
+    def NS(self):
+        return self._table("NS")
+
+    def OS(self):
+        return self._table("OS")
+
+    def PS(self):
+        return [self._table("PS", j) for j in range(self.S())]
+
+    def PI(self):
+        return [self._table("PI", j) for j in range(self.S())]
+
+    def TMl(self):
+        return self._table("TMl")
+
+    def TMi(self):
+        return self._table("TMi")
+
+
+class _trellis_block(_Block):
+    """streams x n * _per_in items of _in back to back in, n * _per_out items of _out for each out"""
+    _in = np.uint8
+    _out = np.uint8
+    _per_in = 1
+    _per_out = 1
+
+    def history(self):
+        return 1
+
+    def work(self, input_items, n=None):
+        x = np.ascontiguousarray(input_items, dtype=self._in).reshape(-1)
+        if n is None:
+            n = len(x) // (self._streams * self._per_in)
+        if len(x) < n * self._streams * self._per_in:
+            raise ValueError("work needs %d items, got %d" % (n * self._streams * self._per_in, len(x)))
+        m = n * self._streams * self._per_out
+        out = np.zeros(max(m, 1), dtype=self._out)
+        self._call("work", int(n), _ptr(x), _ptr(out))
+        return out[:m]
+
+
+class trellis_encoder_bb(_trellis_block):
+    """trellis.encoder_bb(FSM, ST): out[i] = OS[ST * I + in[i]], ST = NS[ST * I + in[i]]; one state per stream, kept
+    across calls.  An input outside [0, I) is refused and leaves the states alone."""
+    _name = "trellis_encoder_bb"
+
+    def __init__(self, FSM, ST, device=0):
+        _Block.__init__(self)
+        self._create(FSM._h, int(ST), int(device))
+
+    def ST(self, stream=0):
+        st = C.c_int(0)
+        self._call("ST", int(stream), C.byref(st))
+        return st.value
+
+    def set_ST(self, ST):
+        self._call("set_ST", int(ST))
+
+
+class trellis_encoder_bs(trellis_encoder_bb):
+    _name = "trellis_encoder_bs"
+    _out = np.int16
+
+
+class trellis_encoder_bi(trellis_encoder_bb):
+    _name = "trellis_encoder_bi"
+    _out = np.int32
+
+
+class trellis_encoder_ss(trellis_encoder_bb):
+    _name = "trellis_encoder_ss"
+    _in = np.int16
+    _out = np.int16
+
+
+class trellis_encoder_si(trellis_encoder_bb):
+    _name = "trellis_encoder_si"
+    _in = np.int16
+    _out = np.int32
+
+
+class trellis_encoder_ii(trellis_encoder_bb):
+    _name = "trellis_encoder_ii"
+    _in = np.int32
+    _out = np.int32
+
+
+class trellis_metrics_f(_trellis_block):
+    """trellis.metrics_f(O, D, TABLE, TYPE): n steps of D items in, O floats per step out, the reference bit for bit.
+    TYPE is TRELLIS_EUCLIDEAN or TRELLIS_HARD_SYMBOL; anything else is refused here, where the reference throws in work."""
+    _name = "trellis_metrics_f"
+    _in = np.float32
+    _out = np.float32
+
+    def __init__(self, O, D, TABLE, TYPE, device=0):
+        _Block.__init__(self)
+        t = np.ascontiguousarray(TABLE, dtype=self._in).reshape(-1)
+        self._create(int(O), int(D), _ptr(t), len(t), int(TYPE), int(device))
+        self._per_in, self._per_out = int(D), int(O)
+
+    def set_TABLE(self, TABLE):
+        t = np.ascontiguousarray(TABLE, dtype=self._in).reshape(-1)
+        self._call("set_TABLE", _ptr(t), len(t))
+
+    def O(self):
+        return self._call("O")
+
+    def D(self):
+        return self._call("D")
+
+    def TYPE(self):
+        return self._call("TYPE")
+
+
+class trellis_metrics_s(trellis_metrics_f):
+    _name = "trellis_metrics_s"
+    _in = np.int16
+
+
+class trellis_metrics_i(trellis_metrics_f):
+    _name = "trellis_metrics_i"
+    _in = np.int32
+
+
+class trellis_metrics_c(trellis_metrics_f):
+    _name = "trellis_metrics_c"
+    _in = np.complex64
+
+
+class trellis_constellation_metrics_cf(_trellis_block):
+    """trellis.constellation_metrics_cf(constellation, TYPE): the constellation's calc_metric, dimensionality() complex
+    items per step in, arity() floats out"""
+    _name = "trellis_constellation_metrics_cf"
+    _in = np.complex64
+    _out = np.float32
+
+    def __init__(self, constellation, TYPE, device=0):
+        _Block.__init__(self)
+        self._create(constellation.base()._h, int(TYPE), int(device))
+        self._per_in, self._per_out = self.D(), self.O()
+
+    def O(self):
+        return self._call("O")
+
+    def D(self):
+        return self._call("D")
+
+    def TYPE(self):
+        return self._call("TYPE")
+
+
+class trellis_viterbi_b(_trellis_block):
+    """trellis.viterbi_b(FSM, K, S0, SK): n * O floats in, n symbols out per stream, n a multiple of K; every block of
+    K steps is viterbi_algorithm's output byte for byte in every mode"""
+    _name = "trellis_viterbi_b"
+    _in = np.float32
+
+    def __init__(self, FSM, K, S0, SK, device=0):
+        _Block.__init__(self)
+        self._create(FSM._h, int(K), int(S0), int(SK), int(device))
+        self._per_in = FSM.O()
+
+    def K(self):
+        return self._call("K")
+
+    def _state(self, name):
+        v = C.c_int(0)
+        self._call(name, C.byref(v))
+        return v.value
+
+    def S0(self):
+        return self._state("S0")
+
+    def SK(self):
+        return self._state("SK")
+
+    def trace_window(self):
+        """the steps whose trace fits in LDS; a larger K goes through the workspace"""
+        return self._call("trace_window")
+
+    def resident_blocks(self):
+        """the blocks decoded at once; a call with more has its persistent wavefronts take further ones"""
+        return self._call("resident_blocks")
+
+    def blocks_per_wavefront(self):
+        return self._call("blocks_per_wavefront")
+
+    def workspace_bytes(self):
+        v = C.c_ulonglong(0)
+        self._call("workspace_bytes", C.byref(v))
+        return v.value
+
+    def dead_ends(self):
+        """steps at which the traceback stood in a state without predecessors, over the handle's life"""
+        v = C.c_longlong(0)
+        self._call("dead_ends", C.byref(v))
+        return v.value
+
+
+class trellis_viterbi_s(trellis_viterbi_b):
+    _name = "trellis_viterbi_s"
+    _out = np.int16
+
+
+class trellis_viterbi_i(trellis_viterbi_b):
+    _name = "trellis_viterbi_i"
+    _out = np.int32
+
+
+class _trellis_viterbi_combined(trellis_viterbi_b):
+    """trellis.viterbi_combined_XX(FSM, K, S0, SK, D, TABLE, TYPE): the metrics of trellis_metrics_X computed per step
+    inside the decoder; n * D items in, n symbols out per stream.  engine() 1 (the default) forms the metrics in the
+    decoder's LDS window, 0 runs the metrics kernel and then the decoder; MODE_GENERIC runs engine 0.  The symbols are
+    the reference's in both."""
+
+    def __init__(self, FSM, K, S0, SK, D, TABLE, TYPE, device=0):
+        _Block.__init__(self)
+        t = np.ascontiguousarray(TABLE, dtype=self._in).reshape(-1)
+        self._create(FSM._h, int(K), int(S0), int(SK), int(D), _ptr(t), len(t), int(TYPE), int(device))
+        self._per_in = int(D)
+
+    def set_TABLE(self, TABLE):
+        t = np.ascontiguousarray(TABLE, dtype=self._in).reshape(-1)
+        self._call("set_TABLE", _ptr(t), len(t))
+
+    def set_engine(self, engine):
+        self._call("set_engine", int(engine))
+
+    def engine(self):
+        return self._call("engine")
+
+    def D(self):
+        return self._call("D")
+
+    def TYPE(self):
+        return self._call("TYPE")
+
+
+class trellis_viterbi_combined_sb(_trellis_viterbi_combined):
+    _name = "trellis_viterbi_combined_sb"
+    _in = np.int16
+
+
+class trellis_viterbi_combined_ss(_trellis_viterbi_combined):
+    _name = "trellis_viterbi_combined_ss"
+    _in = np.int16
+    _out = np.int16
+
+
+class trellis_viterbi_combined_si(_trellis_viterbi_combined):
+    _name = "trellis_viterbi_combined_si"
+    _in = np.int16
+    _out = np.int32
+
+
+class trellis_viterbi_combined_ib(_trellis_viterbi_combined):
+    _name = "trellis_viterbi_combined_ib"
+    _in = np.int32
+
+
+class trellis_viterbi_combined_is(_trellis_viterbi_combined):
+    _name = "trellis_viterbi_combined_is"
+    _in = np.int32
+    _out = np.int16
+
+
+class trellis_viterbi_combined_ii(_trellis_viterbi_combined):
+    _name = "trellis_viterbi_combined_ii"
+    _in = np.int32
+    _out = np.int32
+
+
+class trellis_viterbi_combined_fb(_trellis_viterbi_combined):
+    _name = "trellis_viterbi_combined_fb"
+
+
+class trellis_viterbi_combined_fs(_trellis_viterbi_combined):
+    _name = "trellis_viterbi_combined_fs"
+    _out = np.int16
+
+
+class trellis_viterbi_combined_fi(_trellis_viterbi_combined):
+    _name = "trellis_viterbi_combined_fi"
+    _out = np.int32
+
+
+class trellis_viterbi_combined_cb(_trellis_viterbi_combined):
+    _name = "trellis_viterbi_combined_cb"
+    _in = np.complex64
+
+
+class trellis_viterbi_combined_cs(_trellis_viterbi_combined):
+    _name = "trellis_viterbi_combined_cs"
+    _in = np.complex64
+    _out = np.int16
+
+
+class trellis_viterbi_combined_ci(_trellis_viterbi_combined):
+    _name = "trellis_viterbi_combined_ci"
+    _in = np.complex64
+    _out = np.int32
 
 
 def random_mask_vec8():

@@ -57,6 +57,12 @@
 //                                            <- digital_make_cpmmod_bc, digital_make_gmskmod_bc (gr-digital/lib) and
 //                                               digital.gmsk_mod (gr-digital/python/gmsk.py:55-120), one block each;
 //                                               grhip_cpm_phase_response_taps is gr_cpm::phase_response
+//   fsm, trellis_make_encoder_XX, trellis_make_metrics_X, trellis_make_constellation_metrics_cf, trellis_make_viterbi_X,
+//   trellis_make_viterbi_combined_XX
+//                                            <- the class and the factories of the same names (gr-trellis/src/lib/fsm.h,
+//                                               trellis_encoder_XX.h.t, trellis_metrics_X.h.t,
+//                                               trellis_constellation_metrics_cf.h, trellis_viterbi_X.h.t,
+//                                               trellis_viterbi_combined_XX.h.t)
 //   gr_make_agc_cc / _ff, gr_make_agc2_cc / _ff
 //                                            <- the factories of the same names (general/gr_agc_cc.h, gr_agc_ff.h,
 //                                               gr_agc2_cc.h, gr_agc2_ff.h)
@@ -2282,6 +2288,365 @@ inline grhip_additive_scrambler_bb_sptr gr_make_additive_scrambler_bb(int mask, 
 {
     return grhip_detail::factory::make<grhip_additive_scrambler_bb_blk>(mask, seed, len, count, device);
 }
+
+// ---------------------------------------------------------------------------
+// gr-trellis.  fsm (gr-trellis/src/lib/fsm.h:39-74) is a host object with the reference's constructors and accessors;
+// a block copies the one it is made from.  trellis_encoder_XX (FSM, ST) is a gr_sync_block; trellis_metrics_X
+// (O, D, TABLE, TYPE) and trellis_constellation_metrics_cf (constellation, TYPE) are gr_blocks with
+// set_relative_rate(O / D), set_output_multiple(O) and D * noutput_items / O inputs (trellis_metrics_X.cc.t:53-70);
+// trellis_viterbi_X (FSM, K, S0, SK) is a gr_block with set_relative_rate(1 / O), set_output_multiple(K) and
+// O * noutput_items inputs (trellis_viterbi_X.cc.t:60-72).  One stream each.  What the reference indexes out of range
+// for (an input symbol >= I, sizes that do not fit) throws std::invalid_argument here.
+// ---------------------------------------------------------------------------
+class fsm {
+    grhip_detail::handle<grhip_fsm, grhip_fsm_destroy> d_h;
+    static size_t count(int rc)
+    {
+        grhip_detail::check(rc);
+        return (size_t)rc;
+    }
+    std::vector<int> table(int (*get)(const grhip_fsm *, int *, int)) const
+    {
+        if (!d_h) return std::vector<int>();
+        std::vector<int> v(count(get(d_h, nullptr, 0)));
+        grhip_detail::check(get(d_h, v.data(), (int)v.size()));
+        return v;
+    }
+    std::vector<std::vector<int> > lists(int (*get)(const grhip_fsm *, int, int *, int)) const
+    {
+        std::vector<std::vector<int> > ll((size_t)S());
+        for (int j = 0; j < S(); j++) {
+            ll[j].resize(count(get(d_h, j, nullptr, 0)));
+            grhip_detail::check(get(d_h, j, ll[j].data(), (int)ll[j].size()));
+        }
+        return ll;
+    }
+public:
+    fsm() {}                                        // fsm.cc:34-45: I = S = O = 0 and empty tables; no block takes it
+    fsm(const fsm &FSM)
+    {
+        if (FSM.d_h) *this = fsm(FSM.I(), FSM.S(), FSM.O(), FSM.NS(), FSM.OS());
+    }
+    fsm(fsm &&) = default;
+    fsm &operator=(fsm &&) = default;
+    fsm &operator=(const fsm &FSM)
+    {
+        fsm copy(FSM);
+        d_h = std::move(copy.d_h);
+        return *this;
+    }
+    fsm(int I, int S, int O, const std::vector<int> &NS, const std::vector<int> &OS)
+    {
+        grhip_detail::check(grhip_fsm_create(d_h.out(), I, S, O, NS.data(), (int)NS.size(), OS.data(), (int)OS.size()));
+    }
+    explicit fsm(const char *name) { grhip_detail::check(grhip_fsm_create_file(d_h.out(), name)); }
+    fsm(int k, int n, const std::vector<int> &G) { grhip_detail::check(grhip_fsm_create_generator(d_h.out(), k, n, G.data(), (int)G.size())); }
+    fsm(int mod_size, int ch_length) { grhip_detail::check(grhip_fsm_create_isi(d_h.out(), mod_size, ch_length)); }
+    fsm(int P, int M, int L) { grhip_detail::check(grhip_fsm_create_cpm(d_h.out(), P, M, L)); }
+    fsm(const fsm &FSM1, const fsm &FSM2) { grhip_detail::check(grhip_fsm_create_joint(d_h.out(), FSM1.d_h, FSM2.d_h)); }
+    fsm(const fsm &FSM, int n) { grhip_detail::check(grhip_fsm_create_radix(d_h.out(), FSM.d_h, n)); }
+    const grhip_fsm *handle() const { return d_h; }
+    int I() const { return d_h ? grhip_fsm_I(d_h) : 0; }
+    int S() const { return d_h ? grhip_fsm_S(d_h) : 0; }
+    int O() const { return d_h ? grhip_fsm_O(d_h) : 0; }
+    bool connected() const { return d_h && grhip_fsm_connected(d_h) != 0; }        // false where the reference prints its message
+    std::vector<int> NS() const { return table(grhip_fsm_NS); }
+    std::vector<int> OS() const { return table(grhip_fsm_OS); }
+    std::vector<int> TMl() const { return table(grhip_fsm_TMl); }
+    std::vector<int> TMi() const { return table(grhip_fsm_TMi); }
+    std::vector<std::vector<int> > PS() const { return lists(grhip_fsm_PS); }
+    std::vector<std::vector<int> > PI() const { return lists(grhip_fsm_PI); }
+};
+
+typedef enum { TRELLIS_EUCLIDEAN = GRHIP_TRELLIS_EUCLIDEAN, TRELLIS_HARD_SYMBOL, TRELLIS_HARD_BIT } trellis_metric_type_t;
+
+// T names the C entries and the item types of one signature
+template <class T>
+class grhip_trellis_encoder_blk : public grhip_detail::block<gr_sync_block, typename T::H, T::destroy, T::set_mode> {
+    friend struct grhip_detail::factory;
+    fsm d_FSM;
+    grhip_trellis_encoder_blk(const fsm &FSM, int ST, int device)
+        : grhip_trellis_encoder_blk::block(T::name, gr_make_io_signature(1, 1, sizeof(typename T::in_t)), gr_make_io_signature(1, 1, sizeof(typename T::out_t))),
+          d_FSM(FSM)
+    {
+        grhip_detail::check(T::create(this->d_h.out(), d_FSM.handle(), ST, device));
+    }
+public:
+    fsm FSM() const { return d_FSM; }
+    int ST() const
+    {
+        int st = 0;
+        grhip_detail::check(T::ST(this->d_h, 0, &st));
+        return st;
+    }
+    void set_ST(int ST) { grhip_detail::check(T::set_ST(this->d_h, ST)); }
+    int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(T::work(this->d_h, noutput_items, in[0], out[0]));
+        return noutput_items;
+    }
+};
+
+// the block of trellis_metrics_X and of trellis_constellation_metrics_cf: what differs is how the handle is made
+template <class T>
+class grhip_trellis_metrics_blk : public grhip_detail::block<gr_block, typename T::H, T::destroy, T::set_mode> {
+    friend struct grhip_detail::factory;
+    int d_O, d_D;
+    template <class... A> explicit grhip_trellis_metrics_blk(A... args)
+        : grhip_trellis_metrics_blk::block(T::name, gr_make_io_signature(1, 1, sizeof(typename T::in_t)), gr_make_io_signature(1, 1, sizeof(float)))
+    {
+        grhip_detail::check(T::make(this->d_h.out(), args...));
+        d_O = T::O(this->d_h);
+        d_D = T::D(this->d_h);
+        this->set_relative_rate(1.0 * d_O / ((double)d_D));
+        this->set_output_multiple(d_O);
+    }
+public:
+    int O() const { return d_O; }
+    int D() const { return d_D; }
+    trellis_metric_type_t TYPE() const { return (trellis_metric_type_t)T::TYPE(this->d_h); }
+    template <class V> void set_TABLE(const std::vector<V> &table)
+    {
+        static_assert(sizeof(V) == sizeof(typename T::in_t), "TABLE holds the block's input items");
+        grhip_detail::check(T::set_TABLE(this->d_h, table.data(), (int)table.size()));
+    }
+    void forecast(int noutput_items, gr_vector_int &req) override
+    {
+        for (size_t i = 0; i < req.size(); i++) req[i] = d_D * noutput_items / d_O;
+    }
+    int general_work(int noutput_items, gr_vector_int &, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(T::work(this->d_h, noutput_items / d_O, in[0], out[0]));
+        this->consume_each(d_D * noutput_items / d_O);
+        return noutput_items;
+    }
+};
+
+template <class T>
+class grhip_trellis_viterbi_blk : public grhip_detail::block<gr_block, typename T::H, T::destroy, T::set_mode> {
+    friend struct grhip_detail::factory;
+    fsm d_FSM;
+    int d_K, d_S0, d_SK;
+    grhip_trellis_viterbi_blk(const fsm &FSM, int K, int S0, int SK, int device)
+        : grhip_trellis_viterbi_blk::block(T::name, gr_make_io_signature(1, 1, sizeof(float)), gr_make_io_signature(1, 1, sizeof(typename T::out_t))),
+          d_FSM(FSM), d_K(K), d_S0(S0), d_SK(SK)
+    {
+        grhip_detail::check(T::create(this->d_h.out(), d_FSM.handle(), K, S0, SK, device));
+        this->set_relative_rate(1.0 / ((double)d_FSM.O()));
+        this->set_output_multiple(d_K);
+    }
+public:
+    fsm FSM() const { return d_FSM; }
+    int K() const { return d_K; }
+    int S0() const { return d_S0; }
+    int SK() const { return d_SK; }
+    long long dead_ends() const
+    {
+        long long n = 0;
+        grhip_detail::check(T::dead_ends(this->d_h, &n));
+        return n;
+    }
+    void forecast(int noutput_items, gr_vector_int &req) override
+    {
+        for (size_t i = 0; i < req.size(); i++) req[i] = d_FSM.O() * noutput_items;
+    }
+    int general_work(int noutput_items, gr_vector_int &, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(T::work(this->d_h, noutput_items, in[0], out[0]));
+        this->consume_each(d_FSM.O() * noutput_items);
+        return noutput_items;
+    }
+};
+
+// trellis_viterbi_combined_XX (FSM, K, S0, SK, D, TABLE, TYPE): trellis_viterbi_combined_XX.cc.t:62-75, a gr_block with
+// set_relative_rate(1 / D), set_output_multiple(K) and D * noutput_items inputs
+template <class T>
+class grhip_trellis_viterbi_combined_blk : public grhip_detail::block<gr_block, typename T::H, T::destroy, T::set_mode> {
+    friend struct grhip_detail::factory;
+    fsm d_FSM;
+    int d_K, d_S0, d_SK, d_D;
+    std::vector<typename T::in_t> d_TABLE;
+    trellis_metric_type_t d_TYPE;
+    grhip_trellis_viterbi_combined_blk(const fsm &FSM, int K, int S0, int SK, int D, const std::vector<typename T::in_t> &TABLE,
+                                       trellis_metric_type_t TYPE, int device)
+        : grhip_trellis_viterbi_combined_blk::block(T::name, gr_make_io_signature(1, 1, sizeof(typename T::in_t)),
+                                                    gr_make_io_signature(1, 1, sizeof(typename T::out_t))),
+          d_FSM(FSM), d_K(K), d_S0(S0), d_SK(SK), d_D(D), d_TABLE(TABLE), d_TYPE(TYPE)
+    {
+        grhip_detail::check(T::create(this->d_h.out(), d_FSM.handle(), K, S0, SK, D, d_TABLE.data(), (int)d_TABLE.size(), (int)TYPE, device));
+        this->set_relative_rate(1.0 / ((double)d_D));
+        this->set_output_multiple(d_K);
+    }
+public:
+    fsm FSM() const { return d_FSM; }
+    int K() const { return d_K; }
+    int S0() const { return d_S0; }
+    int SK() const { return d_SK; }
+    int D() const { return d_D; }
+    std::vector<typename T::in_t> TABLE() const { return d_TABLE; }
+    trellis_metric_type_t TYPE() const { return d_TYPE; }
+    void set_TABLE(const std::vector<typename T::in_t> &table)
+    {
+        grhip_detail::check(T::set_TABLE(this->d_h, table.data(), (int)table.size()));
+        d_TABLE = table;
+    }
+    int engine() const { return this->checked(T::engine(this->d_h)); }
+    void set_engine(int e) { grhip_detail::check(T::set_engine(this->d_h, e)); }
+    void forecast(int noutput_items, gr_vector_int &req) override
+    {
+        for (size_t i = 0; i < req.size(); i++) req[i] = d_D * noutput_items;
+    }
+    int general_work(int noutput_items, gr_vector_int &, gr_vector_const_void_star &in, gr_vector_void_star &out) override
+    {
+        grhip_detail::check(T::work(this->d_h, noutput_items, in[0], out[0]));
+        this->consume_each(d_D * noutput_items);
+        return noutput_items;
+    }
+};
+
+namespace grhip_detail {
+#define GRHIP_TRELLIS_COMMON(NAME)                                                                                     \
+    typedef grhip_##NAME H;                                                                                           \
+    static constexpr const char *name = #NAME;                                                                        \
+    GRHIP_FN(NAME, create); GRHIP_FN(NAME, destroy); GRHIP_FN(NAME, set_mode); GRHIP_FN(NAME, work);
+#define GRHIP_TRELLIS_ENCODER_FNS(NAME, IN, OUT)                                                                       \
+    struct NAME##_fns {                                                                                               \
+        GRHIP_TRELLIS_COMMON(NAME)                                                                                    \
+        typedef IN in_t;                                                                                              \
+        typedef OUT out_t;                                                                                            \
+        GRHIP_FN(NAME, ST); GRHIP_FN(NAME, set_ST);                                                                   \
+    };
+GRHIP_TRELLIS_ENCODER_FNS(trellis_encoder_bb, unsigned char, unsigned char)
+GRHIP_TRELLIS_ENCODER_FNS(trellis_encoder_bs, unsigned char, short)
+GRHIP_TRELLIS_ENCODER_FNS(trellis_encoder_bi, unsigned char, int)
+GRHIP_TRELLIS_ENCODER_FNS(trellis_encoder_ss, short, short)
+GRHIP_TRELLIS_ENCODER_FNS(trellis_encoder_si, short, int)
+GRHIP_TRELLIS_ENCODER_FNS(trellis_encoder_ii, int, int)
+#undef GRHIP_TRELLIS_ENCODER_FNS
+#define GRHIP_TRELLIS_METRICS_FNS(NAME, IN)                                                                            \
+    struct NAME##_fns {                                                                                               \
+        GRHIP_TRELLIS_COMMON(NAME)                                                                                    \
+        typedef IN in_t;                                                                                              \
+        GRHIP_FN(NAME, O); GRHIP_FN(NAME, D); GRHIP_FN(NAME, TYPE); GRHIP_FN(NAME, set_TABLE);                        \
+        static int make(H **h, int O, int D, const std::vector<IN> &TABLE, trellis_metric_type_t TYPE, int device)    \
+        {                                                                                                             \
+            return create(h, O, D, TABLE.data(), (int)TABLE.size(), (int)TYPE, device);                               \
+        }                                                                                                             \
+    };
+GRHIP_TRELLIS_METRICS_FNS(trellis_metrics_s, short)
+GRHIP_TRELLIS_METRICS_FNS(trellis_metrics_i, int)
+GRHIP_TRELLIS_METRICS_FNS(trellis_metrics_f, float)
+GRHIP_TRELLIS_METRICS_FNS(trellis_metrics_c, gr_complex)
+#undef GRHIP_TRELLIS_METRICS_FNS
+struct trellis_constellation_metrics_cf_fns {
+    GRHIP_TRELLIS_COMMON(trellis_constellation_metrics_cf)
+    typedef gr_complex in_t;
+    GRHIP_FN(trellis_constellation_metrics_cf, O); GRHIP_FN(trellis_constellation_metrics_cf, D); GRHIP_FN(trellis_constellation_metrics_cf, TYPE);
+    static int make(H **h, grhip_constellation_sptr constellation, trellis_metric_type_t TYPE, int device)
+    {
+        return create(h, constellation->handle(), (int)TYPE, device);
+    }
+};
+#define GRHIP_TRELLIS_VITERBI_FNS(NAME, OUT)                                                                           \
+    struct NAME##_fns {                                                                                               \
+        GRHIP_TRELLIS_COMMON(NAME)                                                                                    \
+        typedef OUT out_t;                                                                                            \
+        GRHIP_FN(NAME, dead_ends);                                                                                    \
+    };
+GRHIP_TRELLIS_VITERBI_FNS(trellis_viterbi_b, unsigned char)
+GRHIP_TRELLIS_VITERBI_FNS(trellis_viterbi_s, short)
+GRHIP_TRELLIS_VITERBI_FNS(trellis_viterbi_i, int)
+#undef GRHIP_TRELLIS_VITERBI_FNS
+#define GRHIP_TRELLIS_COMBINED_FNS(NAME, IN, OUT)                                                                      \
+    struct NAME##_fns {                                                                                               \
+        GRHIP_TRELLIS_COMMON(NAME)                                                                                    \
+        typedef IN in_t;                                                                                              \
+        typedef OUT out_t;                                                                                            \
+        GRHIP_FN(NAME, set_TABLE); GRHIP_FN(NAME, set_engine); GRHIP_FN(NAME, engine);                                \
+    };
+GRHIP_TRELLIS_COMBINED_FNS(trellis_viterbi_combined_sb, short, unsigned char)
+GRHIP_TRELLIS_COMBINED_FNS(trellis_viterbi_combined_ss, short, short)
+GRHIP_TRELLIS_COMBINED_FNS(trellis_viterbi_combined_si, short, int)
+GRHIP_TRELLIS_COMBINED_FNS(trellis_viterbi_combined_ib, int, unsigned char)
+GRHIP_TRELLIS_COMBINED_FNS(trellis_viterbi_combined_is, int, short)
+GRHIP_TRELLIS_COMBINED_FNS(trellis_viterbi_combined_ii, int, int)
+GRHIP_TRELLIS_COMBINED_FNS(trellis_viterbi_combined_fb, float, unsigned char)
+GRHIP_TRELLIS_COMBINED_FNS(trellis_viterbi_combined_fs, float, short)
+GRHIP_TRELLIS_COMBINED_FNS(trellis_viterbi_combined_fi, float, int)
+GRHIP_TRELLIS_COMBINED_FNS(trellis_viterbi_combined_cb, gr_complex, unsigned char)
+GRHIP_TRELLIS_COMBINED_FNS(trellis_viterbi_combined_cs, gr_complex, short)
+GRHIP_TRELLIS_COMBINED_FNS(trellis_viterbi_combined_ci, gr_complex, int)
+#undef GRHIP_TRELLIS_COMBINED_FNS
+#undef GRHIP_TRELLIS_COMMON
+}  // namespace grhip_detail
+
+// the reference's factory names and signatures, one block type and one sptr each
+#define GRHIP_TRELLIS_ENCODER(SUF)                                                                                     \
+    typedef grhip_trellis_encoder_blk<grhip_detail::trellis_encoder_##SUF##_fns> grhip_trellis_encoder_##SUF##_blk;   \
+    typedef boost::shared_ptr<grhip_trellis_encoder_##SUF##_blk> grhip_trellis_encoder_##SUF##_sptr;                  \
+    inline grhip_trellis_encoder_##SUF##_sptr trellis_make_encoder_##SUF(const fsm &FSM, int ST, int device = 0)      \
+    {                                                                                                                 \
+        return grhip_detail::factory::make<grhip_trellis_encoder_##SUF##_blk>(FSM, ST, device);                       \
+    }
+GRHIP_TRELLIS_ENCODER(bb)
+GRHIP_TRELLIS_ENCODER(bs)
+GRHIP_TRELLIS_ENCODER(bi)
+GRHIP_TRELLIS_ENCODER(ss)
+GRHIP_TRELLIS_ENCODER(si)
+GRHIP_TRELLIS_ENCODER(ii)
+#undef GRHIP_TRELLIS_ENCODER
+#define GRHIP_TRELLIS_METRICS(SUF, IN)                                                                                 \
+    typedef grhip_trellis_metrics_blk<grhip_detail::trellis_metrics_##SUF##_fns> grhip_trellis_metrics_##SUF##_blk;   \
+    typedef boost::shared_ptr<grhip_trellis_metrics_##SUF##_blk> grhip_trellis_metrics_##SUF##_sptr;                  \
+    inline grhip_trellis_metrics_##SUF##_sptr trellis_make_metrics_##SUF(int O, int D, const std::vector<IN> &TABLE,  \
+                                                                         trellis_metric_type_t TYPE, int device = 0)  \
+    {                                                                                                                 \
+        return grhip_detail::factory::make<grhip_trellis_metrics_##SUF##_blk>(O, D, TABLE, TYPE, device);             \
+    }
+GRHIP_TRELLIS_METRICS(s, short)
+GRHIP_TRELLIS_METRICS(i, int)
+GRHIP_TRELLIS_METRICS(f, float)
+GRHIP_TRELLIS_METRICS(c, gr_complex)
+#undef GRHIP_TRELLIS_METRICS
+typedef grhip_trellis_metrics_blk<grhip_detail::trellis_constellation_metrics_cf_fns> grhip_trellis_constellation_metrics_cf_blk;
+typedef boost::shared_ptr<grhip_trellis_constellation_metrics_cf_blk> grhip_trellis_constellation_metrics_cf_sptr;
+inline grhip_trellis_constellation_metrics_cf_sptr trellis_make_constellation_metrics_cf(grhip_constellation_sptr constellation,
+                                                                                         trellis_metric_type_t TYPE, int device = 0)
+{
+    return grhip_detail::factory::make<grhip_trellis_constellation_metrics_cf_blk>(constellation, TYPE, device);
+}
+#define GRHIP_TRELLIS_VITERBI(SUF)                                                                                     \
+    typedef grhip_trellis_viterbi_blk<grhip_detail::trellis_viterbi_##SUF##_fns> grhip_trellis_viterbi_##SUF##_blk;   \
+    typedef boost::shared_ptr<grhip_trellis_viterbi_##SUF##_blk> grhip_trellis_viterbi_##SUF##_sptr;                  \
+    inline grhip_trellis_viterbi_##SUF##_sptr trellis_make_viterbi_##SUF(const fsm &FSM, int K, int S0, int SK, int device = 0) \
+    {                                                                                                                 \
+        return grhip_detail::factory::make<grhip_trellis_viterbi_##SUF##_blk>(FSM, K, S0, SK, device);                \
+    }
+GRHIP_TRELLIS_VITERBI(b)
+GRHIP_TRELLIS_VITERBI(s)
+GRHIP_TRELLIS_VITERBI(i)
+#undef GRHIP_TRELLIS_VITERBI
+#define GRHIP_TRELLIS_COMBINED(SUF, IN)                                                                                \
+    typedef grhip_trellis_viterbi_combined_blk<grhip_detail::trellis_viterbi_combined_##SUF##_fns> grhip_trellis_viterbi_combined_##SUF##_blk; \
+    typedef boost::shared_ptr<grhip_trellis_viterbi_combined_##SUF##_blk> grhip_trellis_viterbi_combined_##SUF##_sptr; \
+    inline grhip_trellis_viterbi_combined_##SUF##_sptr trellis_make_viterbi_combined_##SUF(                           \
+        const fsm &FSM, int K, int S0, int SK, int D, const std::vector<IN> &TABLE, trellis_metric_type_t TYPE, int device = 0) \
+    {                                                                                                                 \
+        return grhip_detail::factory::make<grhip_trellis_viterbi_combined_##SUF##_blk>(FSM, K, S0, SK, D, TABLE, TYPE, device); \
+    }
+GRHIP_TRELLIS_COMBINED(sb, short)
+GRHIP_TRELLIS_COMBINED(ss, short)
+GRHIP_TRELLIS_COMBINED(si, short)
+GRHIP_TRELLIS_COMBINED(ib, int)
+GRHIP_TRELLIS_COMBINED(is, int)
+GRHIP_TRELLIS_COMBINED(ii, int)
+GRHIP_TRELLIS_COMBINED(fb, float)
+GRHIP_TRELLIS_COMBINED(fs, float)
+GRHIP_TRELLIS_COMBINED(fi, float)
+GRHIP_TRELLIS_COMBINED(cb, gr_complex)
+GRHIP_TRELLIS_COMBINED(cs, gr_complex)
+GRHIP_TRELLIS_COMBINED(ci, gr_complex)
+#undef GRHIP_TRELLIS_COMBINED
 
 // ---------------------------------------------------------------------------
 // The continuous-phase transmitter.  gr_frequency_modulator_fc (general/gr_frequency_modulator_fc.h:32-56): a

@@ -3025,6 +3025,551 @@ GRHIP_API int grhip_dmr_chain_run_device(grhip_dmr_chain *h, const void *d_in, s
  * *stride receives the per-stream stride in items */
 GRHIP_API int grhip_dmr_chain_intermediate(grhip_dmr_chain *h, int which, void **d_ptr, size_t *stride);
 
+/* ======================================================================
+ * fsm -- gr-trellis' finite-state machine
+ *   replaces fsm (gr-trellis/src/lib/fsm.cc:34-452, base.cc:29-81)
+ * Host arithmetic, no device.  The constructors, in the reference's order:
+ *   create            fsm(I, S, O, NS, OS), :60-70
+ *   create_text/_file fsm(const char *name), :82-117: "I S O", S * I next states, S * I outputs; the rest is comment
+ *   create_generator  fsm(k, n, G), the (n, k) binary convolutional code, :125-224
+ *   create_isi        fsm(mod_size, ch_length), :234-253
+ *   create_cpm        fsm(P, M, L), :267-292
+ *   create_joint      fsm(FSM1, FSM2), :307-329
+ *   create_radix      fsm(FSM, n), :338-364
+ * The tables: NS, OS (I * S ints, [state][input]); PS(state), PI(state), the (state, input) pairs that lead to
+ * `state` in ascending (state, input) order (generate_PS_PI, :377-395 -- the decoder's tie-breaking depends on that
+ * order); TMl, TMi (S * S ints, generate_TM / find_es, :401-452).  A table getter copies into `out` (cap ints) and
+ * returns the count; with out == NULL it only returns the count.
+ * Deviations:
+ *   - the reference validates nothing and indexes out of range; here I, S, O < 1, table lengths other than I * S,
+ *     an NS entry outside [0, S) and an OS entry outside [0, O) are GRHIP_EINVAL;
+ *   - a text that ends early (or holds something that is no number) is GRHIP_EINVAL; the reference leaves the
+ *     entries unset;
+ *   - a disconnected FSM is accepted, as in the reference, which prints a message (:420-424) and goes on;
+ *     grhip_fsm_connected() returns 0 for it instead of printing;
+ *   - sizes are capped where an int product of the reference would overflow or a table would not be practical:
+ *     S <= 2048, I <= 2^21, O <= 2^24, I * S <= 2^22; k <= 21, n <= 24 and a generator matrix without an all-zero
+ *     row (the reference shifts by -1 there), ch_length, L and the radix at most 64.
+ * Not built: write_trellis_svg, write_fsm_txt.
+ * ====================================================================== */
+typedef struct grhip_fsm grhip_fsm;
+GRHIP_API int grhip_fsm_create(grhip_fsm **h, int I, int S, int O, const int *NS, int n_NS, const int *OS, int n_OS);
+GRHIP_API int grhip_fsm_create_text(grhip_fsm **h, const char *text);
+GRHIP_API int grhip_fsm_create_file(grhip_fsm **h, const char *path);
+GRHIP_API int grhip_fsm_create_generator(grhip_fsm **h, int k, int n, const int *G, int n_G);
+GRHIP_API int grhip_fsm_create_isi(grhip_fsm **h, int mod_size, int ch_length);
+GRHIP_API int grhip_fsm_create_cpm(grhip_fsm **h, int P, int M, int L);
+GRHIP_API int grhip_fsm_create_joint(grhip_fsm **h, const grhip_fsm *fsm1, const grhip_fsm *fsm2);
+GRHIP_API int grhip_fsm_create_radix(grhip_fsm **h, const grhip_fsm *fsm, int n);
+GRHIP_API void grhip_fsm_destroy(grhip_fsm *h);
+GRHIP_API int grhip_fsm_I(const grhip_fsm *h);
+GRHIP_API int grhip_fsm_S(const grhip_fsm *h);
+GRHIP_API int grhip_fsm_O(const grhip_fsm *h);
+GRHIP_API int grhip_fsm_connected(const grhip_fsm *h);
+GRHIP_API int grhip_fsm_NS(const grhip_fsm *h, int *out, int cap);
+GRHIP_API int grhip_fsm_OS(const grhip_fsm *h, int *out, int cap);
+GRHIP_API int grhip_fsm_PS(const grhip_fsm *h, int state, int *out, int cap);
+GRHIP_API int grhip_fsm_PI(const grhip_fsm *h, int state, int *out, int cap);
+GRHIP_API int grhip_fsm_TMl(const grhip_fsm *h, int *out, int cap);
+GRHIP_API int grhip_fsm_TMi(const grhip_fsm *h, int *out, int cap);
+
+/* ======================================================================
+ * trellis_encoder_bb / bs / bi / ss / si / ii
+ *   replace trellis_make_encoder_XX (FSM, ST)
+ *   gr-trellis/src/lib/trellis_encoder_XX.cc.t:50-75: out[i] = OS[ST * I + in[i]], ST = NS[ST * I + in[i]]
+ * S streams back to back ([S][n], S = 1 after create; `out` may not overlap `in`; n == 0 is a successful no-op).
+ * The handle copies the FSM and keeps one state per stream on the device across calls; ST(stream) reads it,
+ * set_ST sets every stream's, set_streams restarts every stream from the constructor's (or the last set) ST.
+ * Deviations:
+ *   - with several streams the reference starts every stream of a call from the same d_ST and keeps the last
+ *     stream's end state; here every stream carries its own.  For one stream the two agree, across any cuts;
+ *   - an input symbol >= I or < 0 makes the reference read outside its tables; here the call fails with
+ *     GRHIP_EINVAL, the outputs of that call are unspecified and every state is as before the call.  The check is
+ *     a flag word written by the kernels and read after the call, so work_device waits for its stream;
+ *   - ST outside [0, S) is GRHIP_EINVAL.
+ * GRHIP_MODE_GENERIC: one wavefront per stream moves windows of 1024 items through LDS, coalesced, and one lane walks
+ * each window.  Every other mode, for S <= 64 and calls above 256
+ * items: the items are cut into chunks of 256; one wavefront per chunk runs the chunk from every start state at
+ * once (lane s starts in state s) and leaves an S-byte end-state map; the maps are chained along the stream; every
+ * chunk is walked again from its true start state, one lane per chunk.  The outputs are the same bytes.
+ * ====================================================================== */
+typedef struct grhip_trellis_encoder_bb grhip_trellis_encoder_bb;
+GRHIP_API int grhip_trellis_encoder_bb_create(grhip_trellis_encoder_bb **h, const grhip_fsm *fsm, int ST, int device);
+GRHIP_API void grhip_trellis_encoder_bb_destroy(grhip_trellis_encoder_bb *h);
+GRHIP_API int grhip_trellis_encoder_bb_set_mode(grhip_trellis_encoder_bb *h, int mode);
+GRHIP_API int grhip_trellis_encoder_bb_set_streams(grhip_trellis_encoder_bb *h, int nstreams);
+GRHIP_API int grhip_trellis_encoder_bb_ST(grhip_trellis_encoder_bb *h, int stream, int *ST);
+GRHIP_API int grhip_trellis_encoder_bb_set_ST(grhip_trellis_encoder_bb *h, int ST);
+GRHIP_API int grhip_trellis_encoder_bb_work(grhip_trellis_encoder_bb *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_encoder_bb_work_device(grhip_trellis_encoder_bb *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_encoder_bs grhip_trellis_encoder_bs;
+GRHIP_API int grhip_trellis_encoder_bs_create(grhip_trellis_encoder_bs **h, const grhip_fsm *fsm, int ST, int device);
+GRHIP_API void grhip_trellis_encoder_bs_destroy(grhip_trellis_encoder_bs *h);
+GRHIP_API int grhip_trellis_encoder_bs_set_mode(grhip_trellis_encoder_bs *h, int mode);
+GRHIP_API int grhip_trellis_encoder_bs_set_streams(grhip_trellis_encoder_bs *h, int nstreams);
+GRHIP_API int grhip_trellis_encoder_bs_ST(grhip_trellis_encoder_bs *h, int stream, int *ST);
+GRHIP_API int grhip_trellis_encoder_bs_set_ST(grhip_trellis_encoder_bs *h, int ST);
+GRHIP_API int grhip_trellis_encoder_bs_work(grhip_trellis_encoder_bs *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_encoder_bs_work_device(grhip_trellis_encoder_bs *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_encoder_bi grhip_trellis_encoder_bi;
+GRHIP_API int grhip_trellis_encoder_bi_create(grhip_trellis_encoder_bi **h, const grhip_fsm *fsm, int ST, int device);
+GRHIP_API void grhip_trellis_encoder_bi_destroy(grhip_trellis_encoder_bi *h);
+GRHIP_API int grhip_trellis_encoder_bi_set_mode(grhip_trellis_encoder_bi *h, int mode);
+GRHIP_API int grhip_trellis_encoder_bi_set_streams(grhip_trellis_encoder_bi *h, int nstreams);
+GRHIP_API int grhip_trellis_encoder_bi_ST(grhip_trellis_encoder_bi *h, int stream, int *ST);
+GRHIP_API int grhip_trellis_encoder_bi_set_ST(grhip_trellis_encoder_bi *h, int ST);
+GRHIP_API int grhip_trellis_encoder_bi_work(grhip_trellis_encoder_bi *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_encoder_bi_work_device(grhip_trellis_encoder_bi *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_encoder_ss grhip_trellis_encoder_ss;
+GRHIP_API int grhip_trellis_encoder_ss_create(grhip_trellis_encoder_ss **h, const grhip_fsm *fsm, int ST, int device);
+GRHIP_API void grhip_trellis_encoder_ss_destroy(grhip_trellis_encoder_ss *h);
+GRHIP_API int grhip_trellis_encoder_ss_set_mode(grhip_trellis_encoder_ss *h, int mode);
+GRHIP_API int grhip_trellis_encoder_ss_set_streams(grhip_trellis_encoder_ss *h, int nstreams);
+GRHIP_API int grhip_trellis_encoder_ss_ST(grhip_trellis_encoder_ss *h, int stream, int *ST);
+GRHIP_API int grhip_trellis_encoder_ss_set_ST(grhip_trellis_encoder_ss *h, int ST);
+GRHIP_API int grhip_trellis_encoder_ss_work(grhip_trellis_encoder_ss *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_encoder_ss_work_device(grhip_trellis_encoder_ss *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_encoder_si grhip_trellis_encoder_si;
+GRHIP_API int grhip_trellis_encoder_si_create(grhip_trellis_encoder_si **h, const grhip_fsm *fsm, int ST, int device);
+GRHIP_API void grhip_trellis_encoder_si_destroy(grhip_trellis_encoder_si *h);
+GRHIP_API int grhip_trellis_encoder_si_set_mode(grhip_trellis_encoder_si *h, int mode);
+GRHIP_API int grhip_trellis_encoder_si_set_streams(grhip_trellis_encoder_si *h, int nstreams);
+GRHIP_API int grhip_trellis_encoder_si_ST(grhip_trellis_encoder_si *h, int stream, int *ST);
+GRHIP_API int grhip_trellis_encoder_si_set_ST(grhip_trellis_encoder_si *h, int ST);
+GRHIP_API int grhip_trellis_encoder_si_work(grhip_trellis_encoder_si *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_encoder_si_work_device(grhip_trellis_encoder_si *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_encoder_ii grhip_trellis_encoder_ii;
+GRHIP_API int grhip_trellis_encoder_ii_create(grhip_trellis_encoder_ii **h, const grhip_fsm *fsm, int ST, int device);
+GRHIP_API void grhip_trellis_encoder_ii_destroy(grhip_trellis_encoder_ii *h);
+GRHIP_API int grhip_trellis_encoder_ii_set_mode(grhip_trellis_encoder_ii *h, int mode);
+GRHIP_API int grhip_trellis_encoder_ii_set_streams(grhip_trellis_encoder_ii *h, int nstreams);
+GRHIP_API int grhip_trellis_encoder_ii_ST(grhip_trellis_encoder_ii *h, int stream, int *ST);
+GRHIP_API int grhip_trellis_encoder_ii_set_ST(grhip_trellis_encoder_ii *h, int ST);
+GRHIP_API int grhip_trellis_encoder_ii_work(grhip_trellis_encoder_ii *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_encoder_ii_work_device(grhip_trellis_encoder_ii *h, int n, const void *d_in, void *d_out, void *stream);
+
+/* ======================================================================
+ * trellis_metrics_s / i / f / c, trellis_constellation_metrics_cf
+ *   replace trellis_make_metrics_X (O, D, TABLE, TYPE), trellis_make_constellation_metrics_cf (constellation, TYPE)
+ *   gr-trellis/src/lib/trellis_metrics_X.cc.t, calc_metric.cc:29-72 (s, i, f) and :212-250 (c),
+ *   trellis_constellation_metrics_cf.cc, gr-digital/lib/digital_constellation.cc:86-94, :160-201
+ * `n` counts trellis steps per stream: a step takes D items (short, int, float, complex) and gives O floats;
+ * S streams back to back ([S][n * D] in, [S][n * O] out).  TABLE holds O * D items, [o][d]; set_TABLE replaces it
+ * (its length must stay O * D).  The constellation form takes O = arity, D = dimensionality and the points of a
+ * grhip_constellation, and get_distance's sum is the complex form's.
+ * TYPE: GRHIP_TRELLIS_EUCLIDEAN  metric[o] = sum over d of s * s, s = in[d] - TABLE[o * D + d];
+ *       GRHIP_TRELLIS_HARD_SYMBOL  0 for the first minimum of those sums in o order, from FLT_MAX, 1 elsewhere.
+ * GRHIP_TRELLIS_HARD_BIT and every other value are refused at creation (GRHIP_EINVAL): the reference throws in work.
+ * The arithmetic is the reference's, statement for statement and bit for bit in every mode: s is formed in the item's
+ * type and metric[o] += s * s in float.  For short the difference is truncated to short and the product is an int;
+ * for int difference and product wrap in two's complement (the reference's signed overflow beyond |s| > 46340 is
+ * undefined); for complex the term is re * re + im * im, then the add.
+ * ====================================================================== */
+#define GRHIP_TRELLIS_EUCLIDEAN 200     /* gr-digital/include/digital_metric_type.h:26-28 */
+#define GRHIP_TRELLIS_HARD_SYMBOL 201
+#define GRHIP_TRELLIS_HARD_BIT 202
+typedef struct grhip_trellis_metrics_s grhip_trellis_metrics_s;
+GRHIP_API int grhip_trellis_metrics_s_create(grhip_trellis_metrics_s **h, int O, int D, const void *TABLE, int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_metrics_s_destroy(grhip_trellis_metrics_s *h);
+GRHIP_API int grhip_trellis_metrics_s_set_mode(grhip_trellis_metrics_s *h, int mode);
+GRHIP_API int grhip_trellis_metrics_s_set_streams(grhip_trellis_metrics_s *h, int nstreams);
+GRHIP_API int grhip_trellis_metrics_s_set_TABLE(grhip_trellis_metrics_s *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_metrics_s_O(grhip_trellis_metrics_s *h);
+GRHIP_API int grhip_trellis_metrics_s_D(grhip_trellis_metrics_s *h);
+GRHIP_API int grhip_trellis_metrics_s_TYPE(grhip_trellis_metrics_s *h);
+GRHIP_API int grhip_trellis_metrics_s_work(grhip_trellis_metrics_s *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_metrics_s_work_device(grhip_trellis_metrics_s *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_metrics_i grhip_trellis_metrics_i;
+GRHIP_API int grhip_trellis_metrics_i_create(grhip_trellis_metrics_i **h, int O, int D, const void *TABLE, int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_metrics_i_destroy(grhip_trellis_metrics_i *h);
+GRHIP_API int grhip_trellis_metrics_i_set_mode(grhip_trellis_metrics_i *h, int mode);
+GRHIP_API int grhip_trellis_metrics_i_set_streams(grhip_trellis_metrics_i *h, int nstreams);
+GRHIP_API int grhip_trellis_metrics_i_set_TABLE(grhip_trellis_metrics_i *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_metrics_i_O(grhip_trellis_metrics_i *h);
+GRHIP_API int grhip_trellis_metrics_i_D(grhip_trellis_metrics_i *h);
+GRHIP_API int grhip_trellis_metrics_i_TYPE(grhip_trellis_metrics_i *h);
+GRHIP_API int grhip_trellis_metrics_i_work(grhip_trellis_metrics_i *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_metrics_i_work_device(grhip_trellis_metrics_i *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_metrics_f grhip_trellis_metrics_f;
+GRHIP_API int grhip_trellis_metrics_f_create(grhip_trellis_metrics_f **h, int O, int D, const void *TABLE, int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_metrics_f_destroy(grhip_trellis_metrics_f *h);
+GRHIP_API int grhip_trellis_metrics_f_set_mode(grhip_trellis_metrics_f *h, int mode);
+GRHIP_API int grhip_trellis_metrics_f_set_streams(grhip_trellis_metrics_f *h, int nstreams);
+GRHIP_API int grhip_trellis_metrics_f_set_TABLE(grhip_trellis_metrics_f *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_metrics_f_O(grhip_trellis_metrics_f *h);
+GRHIP_API int grhip_trellis_metrics_f_D(grhip_trellis_metrics_f *h);
+GRHIP_API int grhip_trellis_metrics_f_TYPE(grhip_trellis_metrics_f *h);
+GRHIP_API int grhip_trellis_metrics_f_work(grhip_trellis_metrics_f *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_metrics_f_work_device(grhip_trellis_metrics_f *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_metrics_c grhip_trellis_metrics_c;
+GRHIP_API int grhip_trellis_metrics_c_create(grhip_trellis_metrics_c **h, int O, int D, const void *TABLE, int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_metrics_c_destroy(grhip_trellis_metrics_c *h);
+GRHIP_API int grhip_trellis_metrics_c_set_mode(grhip_trellis_metrics_c *h, int mode);
+GRHIP_API int grhip_trellis_metrics_c_set_streams(grhip_trellis_metrics_c *h, int nstreams);
+GRHIP_API int grhip_trellis_metrics_c_set_TABLE(grhip_trellis_metrics_c *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_metrics_c_O(grhip_trellis_metrics_c *h);
+GRHIP_API int grhip_trellis_metrics_c_D(grhip_trellis_metrics_c *h);
+GRHIP_API int grhip_trellis_metrics_c_TYPE(grhip_trellis_metrics_c *h);
+GRHIP_API int grhip_trellis_metrics_c_work(grhip_trellis_metrics_c *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_metrics_c_work_device(grhip_trellis_metrics_c *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_constellation_metrics_cf grhip_trellis_constellation_metrics_cf;
+GRHIP_API int grhip_trellis_constellation_metrics_cf_create(grhip_trellis_constellation_metrics_cf **h, const grhip_constellation *constellation,
+                                                            int TYPE, int device);
+GRHIP_API void grhip_trellis_constellation_metrics_cf_destroy(grhip_trellis_constellation_metrics_cf *h);
+GRHIP_API int grhip_trellis_constellation_metrics_cf_set_mode(grhip_trellis_constellation_metrics_cf *h, int mode);
+GRHIP_API int grhip_trellis_constellation_metrics_cf_set_streams(grhip_trellis_constellation_metrics_cf *h, int nstreams);
+GRHIP_API int grhip_trellis_constellation_metrics_cf_O(grhip_trellis_constellation_metrics_cf *h);
+GRHIP_API int grhip_trellis_constellation_metrics_cf_D(grhip_trellis_constellation_metrics_cf *h);
+GRHIP_API int grhip_trellis_constellation_metrics_cf_TYPE(grhip_trellis_constellation_metrics_cf *h);
+GRHIP_API int grhip_trellis_constellation_metrics_cf_work(grhip_trellis_constellation_metrics_cf *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_constellation_metrics_cf_work_device(grhip_trellis_constellation_metrics_cf *h, int n, const void *d_in,
+                                                                 void *d_out, void *stream);
+
+/* ======================================================================
+ * trellis_viterbi_b / s / i
+ *   replace trellis_make_viterbi_X (FSM, K, S0, SK)
+ *   gr-trellis/src/lib/trellis_viterbi_X.cc.t:163-183, core_algorithms.cc:45-109 (viterbi_algorithm)
+ * `n` counts output items per stream: [S][n * O] floats in, [S][n] bytes, shorts or ints out.  Every K steps are a
+ * block that starts in S0 (negative: any state) and ends in SK (negative: the best state) and is decoded on its own.
+ * The handle keeps nothing between calls, so n must be a multiple of K (set_output_multiple(K) in the reference):
+ * any other n is GRHIP_EINVAL.  Refused at creation: K < 1, S0 >= S, SK >= S, S > 1024, and sizes whose byte counts do
+ * not fit an int (in a call as well).
+ * For every block the outputs equal viterbi_algorithm's in every mode: the predecessors of a state are tried in
+ * PS[j] order under a strict <, so the first wins a tie; minm starts from INF = 1.0e9f and minmi from 0, so minmi = 0
+ * where nothing is below INF; the step's norm is subtracted in float; for SK < 0 the first minimum below INF in state
+ * order ends the path, state 0 where there is none.  NaN and infinite metrics go through the same statements: a NaN
+ * never wins a comparison and never becomes the norm.
+ * One deviation: where the traceback stands in a state without a predecessor the reference indexes an empty vector;
+ * the handle writes input symbol 0 for that step, stays in that state and counts the event in dead_ends(), which
+ * adds up over the handle's life in 64 bits and waits for the handle's stream.
+ * The lanes of a wavefront are the states.  For S <= 64 a wavefront decodes blocks_per_wavefront() = 64 / S blocks
+ * side by side; for larger S one workgroup of S lanes decodes one block.  Workgroups are persistent and loop over
+ * the call's blocks; resident_blocks() is how many blocks the grid holds at once: 8 workgroups per CU for S <= 64; for the
+ * large form what 7 waves per SIMD and two workgroups' LDS allow, one workgroup per CU from 449 states on.  Decisions are bit-packed,
+ * ceil(log2 Pmax) bits per state and step (Pmax: the longest predecessor list).  trace_window() is the number of
+ * steps whose trace fits in LDS (INT_MAX where a decision takes no bit); a larger K flushes the trace to a workspace
+ * owned by the handle, sized by the resident blocks, not by the call, and reported by workspace_bytes().  The
+ * workspace is capped at 1 GiB: fewer blocks are then resident, and a K whose single block needs more is GRHIP_EINVAL.
+ * GRHIP_MODE_GENERIC reads metrics and predecessor table from device memory; every other mode stages the metrics in
+ * an LDS window and keeps short predecessor lists in registers.  The bytes are the same.
+ * Not built: splitting one block across wavefronts (a (min,+) matrix scan would not be bit-exact), sliding-window
+ * decoding, trellis_siso_f / siso_combined_f, the sccc / pccc encoders and decoders,
+ * trellis_permutation and the interleaver.
+ * ====================================================================== */
+typedef struct grhip_trellis_viterbi_b grhip_trellis_viterbi_b;
+GRHIP_API int grhip_trellis_viterbi_b_create(grhip_trellis_viterbi_b **h, const grhip_fsm *fsm, int K, int S0, int SK, int device);
+GRHIP_API void grhip_trellis_viterbi_b_destroy(grhip_trellis_viterbi_b *h);
+GRHIP_API int grhip_trellis_viterbi_b_set_mode(grhip_trellis_viterbi_b *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_b_set_streams(grhip_trellis_viterbi_b *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_b_K(grhip_trellis_viterbi_b *h);
+GRHIP_API int grhip_trellis_viterbi_b_S0(grhip_trellis_viterbi_b *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_b_SK(grhip_trellis_viterbi_b *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_b_trace_window(grhip_trellis_viterbi_b *h);
+GRHIP_API int grhip_trellis_viterbi_b_resident_blocks(grhip_trellis_viterbi_b *h);
+GRHIP_API int grhip_trellis_viterbi_b_blocks_per_wavefront(grhip_trellis_viterbi_b *h);
+GRHIP_API int grhip_trellis_viterbi_b_workspace_bytes(grhip_trellis_viterbi_b *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_b_dead_ends(grhip_trellis_viterbi_b *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_b_work(grhip_trellis_viterbi_b *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_b_work_device(grhip_trellis_viterbi_b *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_s grhip_trellis_viterbi_s;
+GRHIP_API int grhip_trellis_viterbi_s_create(grhip_trellis_viterbi_s **h, const grhip_fsm *fsm, int K, int S0, int SK, int device);
+GRHIP_API void grhip_trellis_viterbi_s_destroy(grhip_trellis_viterbi_s *h);
+GRHIP_API int grhip_trellis_viterbi_s_set_mode(grhip_trellis_viterbi_s *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_s_set_streams(grhip_trellis_viterbi_s *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_s_K(grhip_trellis_viterbi_s *h);
+GRHIP_API int grhip_trellis_viterbi_s_S0(grhip_trellis_viterbi_s *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_s_SK(grhip_trellis_viterbi_s *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_s_trace_window(grhip_trellis_viterbi_s *h);
+GRHIP_API int grhip_trellis_viterbi_s_resident_blocks(grhip_trellis_viterbi_s *h);
+GRHIP_API int grhip_trellis_viterbi_s_blocks_per_wavefront(grhip_trellis_viterbi_s *h);
+GRHIP_API int grhip_trellis_viterbi_s_workspace_bytes(grhip_trellis_viterbi_s *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_s_dead_ends(grhip_trellis_viterbi_s *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_s_work(grhip_trellis_viterbi_s *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_s_work_device(grhip_trellis_viterbi_s *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_i grhip_trellis_viterbi_i;
+GRHIP_API int grhip_trellis_viterbi_i_create(grhip_trellis_viterbi_i **h, const grhip_fsm *fsm, int K, int S0, int SK, int device);
+GRHIP_API void grhip_trellis_viterbi_i_destroy(grhip_trellis_viterbi_i *h);
+GRHIP_API int grhip_trellis_viterbi_i_set_mode(grhip_trellis_viterbi_i *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_i_set_streams(grhip_trellis_viterbi_i *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_i_K(grhip_trellis_viterbi_i *h);
+GRHIP_API int grhip_trellis_viterbi_i_S0(grhip_trellis_viterbi_i *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_i_SK(grhip_trellis_viterbi_i *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_i_trace_window(grhip_trellis_viterbi_i *h);
+GRHIP_API int grhip_trellis_viterbi_i_resident_blocks(grhip_trellis_viterbi_i *h);
+GRHIP_API int grhip_trellis_viterbi_i_blocks_per_wavefront(grhip_trellis_viterbi_i *h);
+GRHIP_API int grhip_trellis_viterbi_i_workspace_bytes(grhip_trellis_viterbi_i *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_i_dead_ends(grhip_trellis_viterbi_i *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_i_work(grhip_trellis_viterbi_i *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_i_work_device(grhip_trellis_viterbi_i *h, int n, const void *d_in, void *d_out, void *stream);
+
+/* ======================================================================
+ * trellis_viterbi_combined_{s,i,f,c}{b,s,i}
+ *   replace trellis_make_viterbi_combined_XX (FSM, K, S0, SK, D, TABLE, TYPE)
+ *   gr-trellis/src/lib/trellis_viterbi_combined_XX.cc.t, core_algorithms.cc:147-217 (viterbi_algorithm_combined)
+ * The metrics of trellis_metrics_X computed per step inside the decoder of trellis_viterbi_X: [S][n * D] items (short,
+ * int, float, complex) in, [S][n] bytes, shorts or ints out, n a multiple of K.  TABLE holds O * D items; set_TABLE
+ * replaces it (same length).  Everything the two sections above state holds here: the metric arithmetic, the metric
+ * types (GRHIP_TRELLIS_HARD_BIT and unknown types are GRHIP_EINVAL at creation), the decoder's contract, its one
+ * deviation and its refusals; D outside 1 .. 65536 is GRHIP_EINVAL as well.  The outputs are the reference's in every
+ * mode and engine.
+ * Engine 0 runs the library's metrics kernel into a scratch buffer owned by the handle and then the decoder.  Engine 1,
+ * the default, forms the step's O metrics inside the decoder's LDS window from the D raw inputs, so that a step moves
+ * D * sizeof(item) bytes instead of 4 * O.  GRHIP_MODE_GENERIC, and an O too large for the metric window, run engine 0
+ * whatever was set; engine() returns the engine the next call takes.
+ * ====================================================================== */
+typedef struct grhip_trellis_viterbi_combined_sb grhip_trellis_viterbi_combined_sb;
+GRHIP_API int grhip_trellis_viterbi_combined_sb_create(grhip_trellis_viterbi_combined_sb **h, const grhip_fsm *fsm, int K, int S0, int SK, int D, const void *TABLE,
+    int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_viterbi_combined_sb_destroy(grhip_trellis_viterbi_combined_sb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_set_mode(grhip_trellis_viterbi_combined_sb *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_set_streams(grhip_trellis_viterbi_combined_sb *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_set_TABLE(grhip_trellis_viterbi_combined_sb *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_set_engine(grhip_trellis_viterbi_combined_sb *h, int engine);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_engine(grhip_trellis_viterbi_combined_sb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_D(grhip_trellis_viterbi_combined_sb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_TYPE(grhip_trellis_viterbi_combined_sb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_K(grhip_trellis_viterbi_combined_sb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_S0(grhip_trellis_viterbi_combined_sb *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_SK(grhip_trellis_viterbi_combined_sb *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_resident_blocks(grhip_trellis_viterbi_combined_sb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_blocks_per_wavefront(grhip_trellis_viterbi_combined_sb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_workspace_bytes(grhip_trellis_viterbi_combined_sb *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_trace_window(grhip_trellis_viterbi_combined_sb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_dead_ends(grhip_trellis_viterbi_combined_sb *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_work(grhip_trellis_viterbi_combined_sb *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_combined_sb_work_device(grhip_trellis_viterbi_combined_sb *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_combined_ss grhip_trellis_viterbi_combined_ss;
+GRHIP_API int grhip_trellis_viterbi_combined_ss_create(grhip_trellis_viterbi_combined_ss **h, const grhip_fsm *fsm, int K, int S0, int SK, int D, const void *TABLE,
+    int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_viterbi_combined_ss_destroy(grhip_trellis_viterbi_combined_ss *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_set_mode(grhip_trellis_viterbi_combined_ss *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_set_streams(grhip_trellis_viterbi_combined_ss *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_set_TABLE(grhip_trellis_viterbi_combined_ss *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_set_engine(grhip_trellis_viterbi_combined_ss *h, int engine);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_engine(grhip_trellis_viterbi_combined_ss *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_D(grhip_trellis_viterbi_combined_ss *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_TYPE(grhip_trellis_viterbi_combined_ss *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_K(grhip_trellis_viterbi_combined_ss *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_S0(grhip_trellis_viterbi_combined_ss *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_SK(grhip_trellis_viterbi_combined_ss *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_resident_blocks(grhip_trellis_viterbi_combined_ss *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_blocks_per_wavefront(grhip_trellis_viterbi_combined_ss *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_workspace_bytes(grhip_trellis_viterbi_combined_ss *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_trace_window(grhip_trellis_viterbi_combined_ss *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_dead_ends(grhip_trellis_viterbi_combined_ss *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_work(grhip_trellis_viterbi_combined_ss *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_combined_ss_work_device(grhip_trellis_viterbi_combined_ss *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_combined_si grhip_trellis_viterbi_combined_si;
+GRHIP_API int grhip_trellis_viterbi_combined_si_create(grhip_trellis_viterbi_combined_si **h, const grhip_fsm *fsm, int K, int S0, int SK, int D, const void *TABLE,
+    int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_viterbi_combined_si_destroy(grhip_trellis_viterbi_combined_si *h);
+GRHIP_API int grhip_trellis_viterbi_combined_si_set_mode(grhip_trellis_viterbi_combined_si *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_combined_si_set_streams(grhip_trellis_viterbi_combined_si *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_combined_si_set_TABLE(grhip_trellis_viterbi_combined_si *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_viterbi_combined_si_set_engine(grhip_trellis_viterbi_combined_si *h, int engine);
+GRHIP_API int grhip_trellis_viterbi_combined_si_engine(grhip_trellis_viterbi_combined_si *h);
+GRHIP_API int grhip_trellis_viterbi_combined_si_D(grhip_trellis_viterbi_combined_si *h);
+GRHIP_API int grhip_trellis_viterbi_combined_si_TYPE(grhip_trellis_viterbi_combined_si *h);
+GRHIP_API int grhip_trellis_viterbi_combined_si_K(grhip_trellis_viterbi_combined_si *h);
+GRHIP_API int grhip_trellis_viterbi_combined_si_S0(grhip_trellis_viterbi_combined_si *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_combined_si_SK(grhip_trellis_viterbi_combined_si *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_combined_si_resident_blocks(grhip_trellis_viterbi_combined_si *h);
+GRHIP_API int grhip_trellis_viterbi_combined_si_blocks_per_wavefront(grhip_trellis_viterbi_combined_si *h);
+GRHIP_API int grhip_trellis_viterbi_combined_si_workspace_bytes(grhip_trellis_viterbi_combined_si *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_combined_si_trace_window(grhip_trellis_viterbi_combined_si *h);
+GRHIP_API int grhip_trellis_viterbi_combined_si_dead_ends(grhip_trellis_viterbi_combined_si *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_combined_si_work(grhip_trellis_viterbi_combined_si *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_combined_si_work_device(grhip_trellis_viterbi_combined_si *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_combined_ib grhip_trellis_viterbi_combined_ib;
+GRHIP_API int grhip_trellis_viterbi_combined_ib_create(grhip_trellis_viterbi_combined_ib **h, const grhip_fsm *fsm, int K, int S0, int SK, int D, const void *TABLE,
+    int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_viterbi_combined_ib_destroy(grhip_trellis_viterbi_combined_ib *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_set_mode(grhip_trellis_viterbi_combined_ib *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_set_streams(grhip_trellis_viterbi_combined_ib *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_set_TABLE(grhip_trellis_viterbi_combined_ib *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_set_engine(grhip_trellis_viterbi_combined_ib *h, int engine);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_engine(grhip_trellis_viterbi_combined_ib *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_D(grhip_trellis_viterbi_combined_ib *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_TYPE(grhip_trellis_viterbi_combined_ib *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_K(grhip_trellis_viterbi_combined_ib *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_S0(grhip_trellis_viterbi_combined_ib *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_SK(grhip_trellis_viterbi_combined_ib *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_resident_blocks(grhip_trellis_viterbi_combined_ib *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_blocks_per_wavefront(grhip_trellis_viterbi_combined_ib *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_workspace_bytes(grhip_trellis_viterbi_combined_ib *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_trace_window(grhip_trellis_viterbi_combined_ib *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_dead_ends(grhip_trellis_viterbi_combined_ib *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_work(grhip_trellis_viterbi_combined_ib *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_combined_ib_work_device(grhip_trellis_viterbi_combined_ib *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_combined_is grhip_trellis_viterbi_combined_is;
+GRHIP_API int grhip_trellis_viterbi_combined_is_create(grhip_trellis_viterbi_combined_is **h, const grhip_fsm *fsm, int K, int S0, int SK, int D, const void *TABLE,
+    int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_viterbi_combined_is_destroy(grhip_trellis_viterbi_combined_is *h);
+GRHIP_API int grhip_trellis_viterbi_combined_is_set_mode(grhip_trellis_viterbi_combined_is *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_combined_is_set_streams(grhip_trellis_viterbi_combined_is *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_combined_is_set_TABLE(grhip_trellis_viterbi_combined_is *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_viterbi_combined_is_set_engine(grhip_trellis_viterbi_combined_is *h, int engine);
+GRHIP_API int grhip_trellis_viterbi_combined_is_engine(grhip_trellis_viterbi_combined_is *h);
+GRHIP_API int grhip_trellis_viterbi_combined_is_D(grhip_trellis_viterbi_combined_is *h);
+GRHIP_API int grhip_trellis_viterbi_combined_is_TYPE(grhip_trellis_viterbi_combined_is *h);
+GRHIP_API int grhip_trellis_viterbi_combined_is_K(grhip_trellis_viterbi_combined_is *h);
+GRHIP_API int grhip_trellis_viterbi_combined_is_S0(grhip_trellis_viterbi_combined_is *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_combined_is_SK(grhip_trellis_viterbi_combined_is *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_combined_is_resident_blocks(grhip_trellis_viterbi_combined_is *h);
+GRHIP_API int grhip_trellis_viterbi_combined_is_blocks_per_wavefront(grhip_trellis_viterbi_combined_is *h);
+GRHIP_API int grhip_trellis_viterbi_combined_is_workspace_bytes(grhip_trellis_viterbi_combined_is *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_combined_is_trace_window(grhip_trellis_viterbi_combined_is *h);
+GRHIP_API int grhip_trellis_viterbi_combined_is_dead_ends(grhip_trellis_viterbi_combined_is *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_combined_is_work(grhip_trellis_viterbi_combined_is *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_combined_is_work_device(grhip_trellis_viterbi_combined_is *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_combined_ii grhip_trellis_viterbi_combined_ii;
+GRHIP_API int grhip_trellis_viterbi_combined_ii_create(grhip_trellis_viterbi_combined_ii **h, const grhip_fsm *fsm, int K, int S0, int SK, int D, const void *TABLE,
+    int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_viterbi_combined_ii_destroy(grhip_trellis_viterbi_combined_ii *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_set_mode(grhip_trellis_viterbi_combined_ii *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_set_streams(grhip_trellis_viterbi_combined_ii *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_set_TABLE(grhip_trellis_viterbi_combined_ii *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_set_engine(grhip_trellis_viterbi_combined_ii *h, int engine);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_engine(grhip_trellis_viterbi_combined_ii *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_D(grhip_trellis_viterbi_combined_ii *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_TYPE(grhip_trellis_viterbi_combined_ii *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_K(grhip_trellis_viterbi_combined_ii *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_S0(grhip_trellis_viterbi_combined_ii *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_SK(grhip_trellis_viterbi_combined_ii *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_resident_blocks(grhip_trellis_viterbi_combined_ii *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_blocks_per_wavefront(grhip_trellis_viterbi_combined_ii *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_workspace_bytes(grhip_trellis_viterbi_combined_ii *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_trace_window(grhip_trellis_viterbi_combined_ii *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_dead_ends(grhip_trellis_viterbi_combined_ii *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_work(grhip_trellis_viterbi_combined_ii *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_combined_ii_work_device(grhip_trellis_viterbi_combined_ii *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_combined_fb grhip_trellis_viterbi_combined_fb;
+GRHIP_API int grhip_trellis_viterbi_combined_fb_create(grhip_trellis_viterbi_combined_fb **h, const grhip_fsm *fsm, int K, int S0, int SK, int D, const void *TABLE,
+    int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_viterbi_combined_fb_destroy(grhip_trellis_viterbi_combined_fb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_set_mode(grhip_trellis_viterbi_combined_fb *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_set_streams(grhip_trellis_viterbi_combined_fb *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_set_TABLE(grhip_trellis_viterbi_combined_fb *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_set_engine(grhip_trellis_viterbi_combined_fb *h, int engine);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_engine(grhip_trellis_viterbi_combined_fb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_D(grhip_trellis_viterbi_combined_fb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_TYPE(grhip_trellis_viterbi_combined_fb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_K(grhip_trellis_viterbi_combined_fb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_S0(grhip_trellis_viterbi_combined_fb *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_SK(grhip_trellis_viterbi_combined_fb *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_resident_blocks(grhip_trellis_viterbi_combined_fb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_blocks_per_wavefront(grhip_trellis_viterbi_combined_fb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_workspace_bytes(grhip_trellis_viterbi_combined_fb *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_trace_window(grhip_trellis_viterbi_combined_fb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_dead_ends(grhip_trellis_viterbi_combined_fb *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_work(grhip_trellis_viterbi_combined_fb *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_combined_fb_work_device(grhip_trellis_viterbi_combined_fb *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_combined_fs grhip_trellis_viterbi_combined_fs;
+GRHIP_API int grhip_trellis_viterbi_combined_fs_create(grhip_trellis_viterbi_combined_fs **h, const grhip_fsm *fsm, int K, int S0, int SK, int D, const void *TABLE,
+    int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_viterbi_combined_fs_destroy(grhip_trellis_viterbi_combined_fs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_set_mode(grhip_trellis_viterbi_combined_fs *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_set_streams(grhip_trellis_viterbi_combined_fs *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_set_TABLE(grhip_trellis_viterbi_combined_fs *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_set_engine(grhip_trellis_viterbi_combined_fs *h, int engine);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_engine(grhip_trellis_viterbi_combined_fs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_D(grhip_trellis_viterbi_combined_fs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_TYPE(grhip_trellis_viterbi_combined_fs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_K(grhip_trellis_viterbi_combined_fs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_S0(grhip_trellis_viterbi_combined_fs *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_SK(grhip_trellis_viterbi_combined_fs *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_resident_blocks(grhip_trellis_viterbi_combined_fs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_blocks_per_wavefront(grhip_trellis_viterbi_combined_fs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_workspace_bytes(grhip_trellis_viterbi_combined_fs *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_trace_window(grhip_trellis_viterbi_combined_fs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_dead_ends(grhip_trellis_viterbi_combined_fs *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_work(grhip_trellis_viterbi_combined_fs *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_combined_fs_work_device(grhip_trellis_viterbi_combined_fs *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_combined_fi grhip_trellis_viterbi_combined_fi;
+GRHIP_API int grhip_trellis_viterbi_combined_fi_create(grhip_trellis_viterbi_combined_fi **h, const grhip_fsm *fsm, int K, int S0, int SK, int D, const void *TABLE,
+    int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_viterbi_combined_fi_destroy(grhip_trellis_viterbi_combined_fi *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_set_mode(grhip_trellis_viterbi_combined_fi *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_set_streams(grhip_trellis_viterbi_combined_fi *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_set_TABLE(grhip_trellis_viterbi_combined_fi *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_set_engine(grhip_trellis_viterbi_combined_fi *h, int engine);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_engine(grhip_trellis_viterbi_combined_fi *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_D(grhip_trellis_viterbi_combined_fi *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_TYPE(grhip_trellis_viterbi_combined_fi *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_K(grhip_trellis_viterbi_combined_fi *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_S0(grhip_trellis_viterbi_combined_fi *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_SK(grhip_trellis_viterbi_combined_fi *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_resident_blocks(grhip_trellis_viterbi_combined_fi *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_blocks_per_wavefront(grhip_trellis_viterbi_combined_fi *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_workspace_bytes(grhip_trellis_viterbi_combined_fi *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_trace_window(grhip_trellis_viterbi_combined_fi *h);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_dead_ends(grhip_trellis_viterbi_combined_fi *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_work(grhip_trellis_viterbi_combined_fi *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_combined_fi_work_device(grhip_trellis_viterbi_combined_fi *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_combined_cb grhip_trellis_viterbi_combined_cb;
+GRHIP_API int grhip_trellis_viterbi_combined_cb_create(grhip_trellis_viterbi_combined_cb **h, const grhip_fsm *fsm, int K, int S0, int SK, int D, const void *TABLE,
+    int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_viterbi_combined_cb_destroy(grhip_trellis_viterbi_combined_cb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_set_mode(grhip_trellis_viterbi_combined_cb *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_set_streams(grhip_trellis_viterbi_combined_cb *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_set_TABLE(grhip_trellis_viterbi_combined_cb *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_set_engine(grhip_trellis_viterbi_combined_cb *h, int engine);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_engine(grhip_trellis_viterbi_combined_cb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_D(grhip_trellis_viterbi_combined_cb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_TYPE(grhip_trellis_viterbi_combined_cb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_K(grhip_trellis_viterbi_combined_cb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_S0(grhip_trellis_viterbi_combined_cb *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_SK(grhip_trellis_viterbi_combined_cb *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_resident_blocks(grhip_trellis_viterbi_combined_cb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_blocks_per_wavefront(grhip_trellis_viterbi_combined_cb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_workspace_bytes(grhip_trellis_viterbi_combined_cb *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_trace_window(grhip_trellis_viterbi_combined_cb *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_dead_ends(grhip_trellis_viterbi_combined_cb *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_work(grhip_trellis_viterbi_combined_cb *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_combined_cb_work_device(grhip_trellis_viterbi_combined_cb *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_combined_cs grhip_trellis_viterbi_combined_cs;
+GRHIP_API int grhip_trellis_viterbi_combined_cs_create(grhip_trellis_viterbi_combined_cs **h, const grhip_fsm *fsm, int K, int S0, int SK, int D, const void *TABLE,
+    int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_viterbi_combined_cs_destroy(grhip_trellis_viterbi_combined_cs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_set_mode(grhip_trellis_viterbi_combined_cs *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_set_streams(grhip_trellis_viterbi_combined_cs *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_set_TABLE(grhip_trellis_viterbi_combined_cs *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_set_engine(grhip_trellis_viterbi_combined_cs *h, int engine);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_engine(grhip_trellis_viterbi_combined_cs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_D(grhip_trellis_viterbi_combined_cs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_TYPE(grhip_trellis_viterbi_combined_cs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_K(grhip_trellis_viterbi_combined_cs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_S0(grhip_trellis_viterbi_combined_cs *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_SK(grhip_trellis_viterbi_combined_cs *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_resident_blocks(grhip_trellis_viterbi_combined_cs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_blocks_per_wavefront(grhip_trellis_viterbi_combined_cs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_workspace_bytes(grhip_trellis_viterbi_combined_cs *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_trace_window(grhip_trellis_viterbi_combined_cs *h);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_dead_ends(grhip_trellis_viterbi_combined_cs *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_work(grhip_trellis_viterbi_combined_cs *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_combined_cs_work_device(grhip_trellis_viterbi_combined_cs *h, int n, const void *d_in, void *d_out, void *stream);
+typedef struct grhip_trellis_viterbi_combined_ci grhip_trellis_viterbi_combined_ci;
+GRHIP_API int grhip_trellis_viterbi_combined_ci_create(grhip_trellis_viterbi_combined_ci **h, const grhip_fsm *fsm, int K, int S0, int SK, int D, const void *TABLE,
+    int n_TABLE, int TYPE, int device);
+GRHIP_API void grhip_trellis_viterbi_combined_ci_destroy(grhip_trellis_viterbi_combined_ci *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_set_mode(grhip_trellis_viterbi_combined_ci *h, int mode);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_set_streams(grhip_trellis_viterbi_combined_ci *h, int nstreams);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_set_TABLE(grhip_trellis_viterbi_combined_ci *h, const void *TABLE, int n_TABLE);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_set_engine(grhip_trellis_viterbi_combined_ci *h, int engine);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_engine(grhip_trellis_viterbi_combined_ci *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_D(grhip_trellis_viterbi_combined_ci *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_TYPE(grhip_trellis_viterbi_combined_ci *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_K(grhip_trellis_viterbi_combined_ci *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_S0(grhip_trellis_viterbi_combined_ci *h, int *S0);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_SK(grhip_trellis_viterbi_combined_ci *h, int *SK);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_resident_blocks(grhip_trellis_viterbi_combined_ci *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_blocks_per_wavefront(grhip_trellis_viterbi_combined_ci *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_workspace_bytes(grhip_trellis_viterbi_combined_ci *h, unsigned long long *bytes);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_trace_window(grhip_trellis_viterbi_combined_ci *h);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_dead_ends(grhip_trellis_viterbi_combined_ci *h, long long *count);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_work(grhip_trellis_viterbi_combined_ci *h, int n, const void *in, void *out);
+GRHIP_API int grhip_trellis_viterbi_combined_ci_work_device(grhip_trellis_viterbi_combined_ci *h, int n, const void *d_in, void *d_out, void *stream);
+
 /* ---- small device-memory helpers for hosts without a HIP binding -------- */
 GRHIP_API int grhip_malloc(void **d_ptr, size_t bytes, int device);
 GRHIP_API int grhip_free(void *d_ptr);
