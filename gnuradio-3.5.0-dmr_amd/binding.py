@@ -203,8 +203,17 @@ def _stream(s):
 
 
 class _Block(object):
-    """one C handle.  Its entries are grhip_<_name>_<entry>; what most blocks share is spelled once here."""
+    """one C handle.  Its entries are grhip_<_name>_<entry>; what most blocks share is spelled once here.
+
+    A block whose host work takes streams x n steps back to back (StreamBlock::host_work in csrc/stream_block.h) says
+    so in five attributes, any of which may be set per instance or be a property, and gets its checks and buffers from
+    _work_in and _work_out, or the whole call from _stream_work."""
     _name = None
+    _in = None              # dtype of the input items, cast to it ...
+    _view = False           # ... or True: the input's own bytes, whatever its dtype
+    _out = None             # dtype of the (first) output
+    _per_in = 1             # items in per step and stream
+    _per_out = 1            # items out per step and stream
 
     def __init__(self):
         self._h = C.c_void_p(0)
@@ -239,6 +248,49 @@ class _Block(object):
     def work_device(self, n, d_in, d_out, stream=None):
         """work on device buffers (addresses or tensors), queued on `stream`"""
         return self._call("work_device", int(n), _devptr(d_in), _devptr(d_out), _stream(stream))
+
+    def _stream_value(self, name, ctype, stream):
+        """one value of one stream, which the entry `name` hands back through an out-parameter"""
+        v = ctype(0)
+        self._call(name, int(stream), C.byref(v))
+        return v.value
+
+    def _work_in(self, input_items, n=None):
+        """(x, n): the input flat and contiguous, and the steps it is good for (all it holds where n is None)"""
+        if self._view:
+            x = np.ascontiguousarray(input_items).view(np.uint8).reshape(-1)
+        else:
+            x = np.ascontiguousarray(input_items, dtype=self._in).reshape(-1)
+        n = len(x) // (self._streams * self._per_in) if n is None else int(n)
+        if len(x) < n * self._streams * self._per_in:
+            raise ValueError("work needs %d items, got %d" % (n * self._streams * self._per_in, len(x)))
+        return x, n
+
+    def _work_out(self, n, optional=(), wanted=False):
+        """(pointers, arrays) of the outputs of n steps: the _out array and, where wanted, one array per dtype in
+        `optional` (null pointers otherwise).  Every pointer is valid for n == 0 too; the arrays are cut to the items."""
+        m = n * self._streams * self._per_out
+        bufs = [np.zeros(max(m, 1), dtype=d) for d in [self._out] + (list(optional) if wanted else [])]
+        nulls = [C.c_void_p(0)] * (0 if wanted else len(optional))
+        return [_ptr(b) for b in bufs] + nulls, [b[:m] for b in bufs]
+
+    def _stream_work(self, input_items, n, optional=(), wanted=False):
+        """the work entry between the two: the _out array, or the tuple of it and the optional outputs where wanted"""
+        x, n = self._work_in(input_items, n)
+        ptrs, outs = self._work_out(n, optional, wanted)
+        self._call("work", n, _ptr(x), *ptrs)
+        return tuple(outs) if wanted else outs[0]
+
+
+class _stream_block(_Block):
+    """the blocks whose work is nothing but that contract and which keep no history.  A family that names the count
+    otherwise, or takes it first, keeps a work of its own that hands over to _stream_work."""
+
+    def history(self):
+        return 1
+
+    def work(self, input_items, n=None):
+        return self._stream_work(input_items, n)
 
 
 # ----------------------------------------------------------------------------
@@ -1261,10 +1313,11 @@ class _runsum(_Block):
         return out, r
 
 
-class _dc_blocker(_runsum):
+class _dc_blocker(_stream_block):
     """gr.dc_blocker_XX(D=32, long_form=True): the input delayed by get_group_delay() minus 2 or 4 cascaded D-point
     moving averages of it.  The state lives in the block and carries across work calls; set_streams restarts the
     filter."""
+    _in = _out = _runsum._dtype
 
     def __init__(self, D=32, long_form=True, device=0):
         _Block.__init__(self)
@@ -1273,18 +1326,11 @@ class _dc_blocker(_runsum):
     def get_group_delay(self):
         return self._call("group_delay")
 
-    def history(self):
-        return 1
-
     def decimation(self):
         return 1
 
     def work(self, noutput_items, input_items):
-        x = np.ascontiguousarray(input_items, dtype=self._dtype).reshape(-1)
-        if len(x) < noutput_items * self._streams:
-            raise ValueError("work needs %d input items, got %d" % (noutput_items * self._streams, len(x)))
-        out, r = self._work(noutput_items, x, noutput_items * self._streams)
-        return out[:r * self._streams]
+        return self._stream_work(input_items, noutput_items)
 
 
 class dc_blocker_ff(_dc_blocker):
@@ -1390,25 +1436,16 @@ class integrate_ii(_integrate):
 # gr.complex_to_mag_squared, gr.single_pole_iir_filter_ff, gr.nlog10_ff, gr.keep_one_in_n (general/gr_complex_to_xxx.i,
 # filter/gr_single_pole_iir_filter_ff.i, general/gr_nlog10_ff.i, general/gr_keep_one_in_n.i)
 # ----------------------------------------------------------------------------
-class _spectrum(_Block):
-    _in = np.float32
+class _spectrum(_stream_block):
+    _in = _out = np.float32
 
     def __init__(self, vlen):
         _Block.__init__(self)
-        self._vlen = int(vlen)
-
-    def history(self):
-        return 1
+        self._per_in = self._per_out = int(vlen)
 
     def work(self, noutput_items, input_items):
         """items are vectors of vlen; input_items holds streams x noutput_items of them"""
-        x = np.ascontiguousarray(input_items, dtype=self._in).reshape(-1)
-        need = noutput_items * self._streams * self._vlen
-        if len(x) < need:
-            raise ValueError("work needs %d input elements, got %d" % (need, len(x)))
-        out = np.zeros(need, dtype=np.float32)
-        r = self._call("work", int(noutput_items), _ptr(x), _ptr(out))
-        return out[:r * self._streams * self._vlen]
+        return self._stream_work(input_items, noutput_items)
 
 
 class complex_to_mag_squared(_spectrum):
@@ -1462,15 +1499,15 @@ class _squelch_streams(_Block):
     """what every squelch block shares: work(x) takes streams x n_in items back to back and returns every stream's
     produced items (one array for one stream, a list otherwise); the detector and the ramp machine carry across calls.
     set_streams restarts every stream from the reference's initial state."""
-    _dtype = np.complex64
+    _in = np.complex64
 
     def unmuted(self, stream=0):
         return bool(self._call("unmuted", int(stream)))
 
     def work_into(self, n_in, input_items, out):
         """the raw call: `out` (streams x n_in items, C-contiguous) is written up to every stream's count; returns the counts"""
-        x = np.ascontiguousarray(input_items, dtype=self._dtype).reshape(-1)
-        if len(x) < n_in * self._streams or out.size < n_in * self._streams or out.dtype != self._dtype:
+        x = np.ascontiguousarray(input_items, dtype=self._in).reshape(-1)
+        if len(x) < n_in * self._streams or out.size < n_in * self._streams or out.dtype != self._in:
             raise ValueError("work needs %d items in and room for as many out" % (n_in * self._streams))
         produced = np.zeros(self._streams, dtype=np.int32)
         self._call("work", int(n_in), _ptr(x), _ptr(out), _ptr(produced))
@@ -1479,10 +1516,8 @@ class _squelch_streams(_Block):
         return produced
 
     def work(self, input_items, n_in=None):
-        x = np.ascontiguousarray(input_items, dtype=self._dtype).reshape(-1)
-        if n_in is None:
-            n_in = len(x) // self._streams
-        out = np.zeros(max(n_in * self._streams, 1), dtype=self._dtype)
+        x, n_in = self._work_in(input_items, n_in)
+        out = np.zeros(max(n_in * self._streams, 1), dtype=self._in)
         p = self.work_into(n_in, x, out)
         res = [out[s * n_in:s * n_in + int(p[s])] for s in range(self._streams)]
         return res[0] if self._streams == 1 else res
@@ -1551,7 +1586,7 @@ class pwr_squelch_cc(_pwr_squelch):
 class pwr_squelch_ff(_pwr_squelch):
     """gr.pwr_squelch_ff(db, alpha=0.0001, ramp=0, gate=False)"""
     _name = "pwr_squelch_ff"
-    _dtype = np.float32
+    _in = np.float32
 
 
 class simple_squelch_cc(_squelch):
@@ -1568,7 +1603,7 @@ class ctcss_squelch_ff(_squelch_streams, _ramp_gate):
     unless the tone at freq stands above level and above its two guard tones, decided once per len samples (len 0:
     rate / 10).  work() as the power squelch blocks; blocks of len samples run across calls."""
     _name = "ctcss_squelch_ff"
-    _dtype = np.float32
+    _in = np.float32
 
     def __init__(self, rate, freq, level=0.01, len=0, ramp=0, gate=False, device=0):
         _Block.__init__(self)
@@ -1608,15 +1643,12 @@ class ctcss_squelch_ff(_squelch_streams, _ramp_gate):
         return out[:got]
 
 
-class _agc(_Block):
+class _agc(_stream_block):
     """what the four gain loops share: work(x) takes streams x n_in items back to back and returns as many; every
     stream's gain carries across calls.  The setters act at once (they hold from the next work call), as the
     reference's do; set_gain sets every stream's gain, and set_streams sets it to the constructor's.  work_device
     does not synchronise.  The float getters return the value itself, not a status."""
-    _dtype = np.complex64
-
-    def history(self):
-        return 1
+    _in = _out = np.complex64
 
     def reference(self):
         return self._fn("reference")(self._h)
@@ -1631,22 +1663,13 @@ class _agc(_Block):
         self._call("set_max_gain", float(max_gain))
 
     def gain(self, stream=0):
-        v = C.c_float(0)
-        self._call("gain", int(stream), C.byref(v))
-        return np.float32(v.value)
+        return np.float32(self._stream_value("gain", C.c_float, stream))
 
     def set_gain(self, gain):
         self._call("set_gain", float(gain))
 
     def work(self, input_items, n_in=None):
-        x = np.ascontiguousarray(input_items, dtype=self._dtype).reshape(-1)
-        if n_in is None:
-            n_in = len(x) // self._streams
-        if len(x) < n_in * self._streams:
-            raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
-        out = np.zeros(max(n_in * self._streams, 1), dtype=self._dtype)
-        self._call("work", int(n_in), _ptr(x), _ptr(out))
-        return out[:n_in * self._streams]
+        return self._stream_work(input_items, n_in)
 
     @staticmethod
     def chunk():
@@ -1694,7 +1717,7 @@ class agc_cc(_agc1):
 class agc_ff(_agc1):
     """gr.agc_ff(rate=1e-4, reference=1.0, gain=1.0, max_gain=0.0) (general/gr_agc_ff.i): agc_cc on floats"""
     _name = "agc_ff"
-    _dtype = np.float32
+    _in = _out = np.float32
 
 
 class agc2_cc(_agc2):
@@ -1708,22 +1731,19 @@ class agc2_ff(_agc2):
     """gr.agc2_ff(attack_rate=1e-1, decay_rate=1e-2, reference=1.0, gain=1.0, max_gain=0.0) (general/gr_agc2_ff.i):
     agc2_cc on floats, with the rate test on the magnitude of |out| - reference as the reference has it"""
     _name = "agc2_ff"
-    _dtype = np.float32
+    _in = _out = np.float32
 
 
 # ----------------------------------------------------------------------------
 # digital.costas_loop_cc, gr.pll_freqdet_cf, gr.pll_refout_cc, gr.pll_carriertracking_cc  (gr-digital/swig/
 # digital_costas_loop_cc.i, general/gr_pll_*.i, general/gri_control_loop.i)
 # ----------------------------------------------------------------------------
-class _control_loop(_Block):
+class _control_loop(_stream_block):
     """what the four carrier loops share: gri_control_loop's setters and getters under their own names, and
     work(x), which takes streams x n_in complex items back to back.  Phase and frequency are per stream and carry
     across calls; a setter acts at once on every stream.  A value the reference refuses with std::out_of_range
     raises GrhipError (code -1).  work_device does not synchronise."""
-    _out = np.complex64
-
-    def history(self):
-        return 1
+    _in = _out = np.complex64
 
     def set_loop_bandwidth(self, bw):
         self._call("set_loop_bandwidth", float(bw))
@@ -1755,30 +1775,14 @@ class _control_loop(_Block):
     def get_beta(self):
         return self._fn("get_beta")(self._h)
 
-    def _stream_float(self, name, stream):
-        v = C.c_float(0)
-        self._call(name, int(stream), C.byref(v))
-        return np.float32(v.value)
-
     def get_frequency(self, stream=0):
-        return self._stream_float("get_frequency", stream)
+        return np.float32(self._stream_value("get_frequency", C.c_float, stream))
 
     def get_phase(self, stream=0):
-        return self._stream_float("get_phase", stream)
-
-    def _items(self, input_items, n_in):
-        x = np.ascontiguousarray(input_items, dtype=np.complex64).reshape(-1)
-        if n_in is None:
-            n_in = len(x) // self._streams
-        if len(x) < n_in * self._streams:
-            raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
-        return x, n_in
+        return np.float32(self._stream_value("get_phase", C.c_float, stream))
 
     def work(self, input_items, n_in=None):
-        x, n_in = self._items(input_items, n_in)
-        out = np.zeros(max(n_in * self._streams, 1), dtype=self._out)
-        self._call("work", int(n_in), _ptr(x), _ptr(out))
-        return out[:n_in * self._streams]
+        return self._stream_work(input_items, n_in)
 
 
 class _pll(_control_loop):
@@ -1806,12 +1810,10 @@ class pll_carriertracking_cc(_pll):
     _name = "pll_carriertracking_cc"
 
     def lock_detector(self, stream=0):
-        v = C.c_int(0)
-        self._call("lock_detector", int(stream), C.byref(v))
-        return bool(v.value)
+        return bool(self._stream_value("lock_detector", C.c_int, stream))
 
     def locksig(self, stream=0):
-        return self._stream_float("locksig", stream)
+        return np.float32(self._stream_value("locksig", C.c_float, stream))
 
     def squelch_enable(self, enable):
         self._call("squelch_enable", int(bool(enable)))
@@ -1834,11 +1836,7 @@ class costas_loop_cc(_control_loop):
         self._create(float(loop_bw), int(order), int(device))
 
     def work(self, input_items, n_in=None, freq=False):
-        x, n_in = self._items(input_items, n_in)
-        out = np.zeros(max(n_in * self._streams, 1), dtype=np.complex64)
-        f = np.zeros(max(n_in * self._streams, 1), dtype=np.float32) if freq else None
-        self._call("work", int(n_in), _ptr(x), _ptr(out), _ptr(f) if freq else C.c_void_p(0))
-        return (out[:n_in * self._streams], f[:n_in * self._streams]) if freq else out[:n_in * self._streams]
+        return self._stream_work(input_items, n_in, [np.float32], freq)
 
     def work_device(self, n, d_in, d_out, d_freq_out=None, stream=None):
         return self._call("work_device", int(n), _devptr(d_in), _devptr(d_out), _devptr(d_freq_out), _stream(stream))
@@ -1880,14 +1878,7 @@ class fll_band_edge_cc(_control_loop):
         return self._call("get_filter_size")
 
     def work(self, input_items, n_in=None, aux=False):
-        x, n_in = self._items(input_items, n_in)
-        m = max(n_in * self._streams, 1)
-        out = np.zeros(m, dtype=np.complex64)
-        f = [np.zeros(m, dtype=np.float32) for _ in range(3)] if aux else []
-        null = C.c_void_p(0)
-        self._call("work", int(n_in), _ptr(x), _ptr(out), *([_ptr(a) for a in f] if aux else [null, null, null]))
-        m = n_in * self._streams
-        return (out[:m], f[0][:m], f[1][:m], f[2][:m]) if aux else out[:m]
+        return self._stream_work(input_items, n_in, [np.float32] * 3, aux)
 
     def work_device(self, n, d_in, d_out, d_frq=None, d_phs=None, d_err=None, stream=None):
         return self._call("work_device", int(n), _devptr(d_in), _devptr(d_out), _devptr(d_frq), _devptr(d_phs), _devptr(d_err),
@@ -1924,6 +1915,7 @@ class pfb_clock_sync_ccf(_Block):
     (include/grhip.h).  MODE_GENERIC is bit for bit the restatement in tests/pfb_clock_sync_ref.py and through it the
     reference; every other mode runs the same scalar loop with fused products and tree-order sums."""
     _name = "pfb_clock_sync_ccf"
+    _in = np.complex64
 
     def __init__(self, sps, loop_bw, taps, filter_size=32, init_phase=0.0, max_rate_deviation=1.5, osps=1, device=0):
         _Block.__init__(self)
@@ -1961,26 +1953,21 @@ class pfb_clock_sync_ccf(_Block):
     def get_max_rate_deviation(self):
         return self._fn("get_max_rate_deviation")(self._h)
 
-    def _stream_value(self, name, stream, ctype, dtype):
-        v = ctype(0)
-        self._call(name, int(stream), C.byref(v))
-        return dtype(v.value)
-
     def get_clock_rate(self, stream=0):
-        return self._stream_value("get_clock_rate", stream, C.c_float, np.float32)
+        return np.float32(self._stream_value("get_clock_rate", C.c_float, stream))
 
     def k(self, stream=0):
-        return self._stream_value("k", stream, C.c_float, np.float32)
+        return np.float32(self._stream_value("k", C.c_float, stream))
 
     def error(self, stream=0):
-        return self._stream_value("error", stream, C.c_float, np.float32)
+        return np.float32(self._stream_value("error", C.c_float, stream))
 
     def slips(self, stream=0):
-        return self._stream_value("slips", stream, C.c_int, int)
+        return self._stream_value("slips", C.c_int, stream)
 
     def position(self, stream=0):
         """the index into xz (tpf + floor(sps) - 1 zeros, then the stream) at which the next symbol starts"""
-        return self._stream_value("position", stream, C.c_longlong, int)
+        return self._stream_value("position", C.c_longlong, stream)
 
     def _bank(self, name):
         nf, tpf = C.c_int(0), C.c_int(0)
@@ -2001,11 +1988,7 @@ class pfb_clock_sync_ccf(_Block):
         return self._call("max_produced", int(n_in))
 
     def work(self, input_items, n_in=None, aux=False):
-        x = np.ascontiguousarray(input_items, dtype=np.complex64).reshape(-1)
-        if n_in is None:
-            n_in = len(x) // self._streams
-        if len(x) < n_in * self._streams:
-            raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
+        x, n_in = self._work_in(input_items, n_in)
         cap = self.max_produced(n_in)
         S = self._streams
         out = np.zeros((S, cap), dtype=np.complex64)
@@ -2216,23 +2199,9 @@ def qam_constellation(constellation_points=16, differential=True, mod_code="none
     return constellation_rect(points, [], 4, side, side, width, width)
 
 
-class _byte_block(_Block):
-    """streams x n items back to back in, as many bytes out"""
-    _in = np.uint8
-    _per_out = 1            # input items per output item
-
-    def history(self):
-        return 1
-
-    def work(self, input_items, n=None):
-        x = np.ascontiguousarray(input_items, dtype=self._in).reshape(-1)
-        if n is None:
-            n = len(x) // (self._streams * self._per_out)
-        if len(x) < n * self._streams * self._per_out:
-            raise ValueError("work needs %d items, got %d" % (n * self._streams * self._per_out, len(x)))
-        out = np.zeros(max(n * self._streams, 1), dtype=np.uint8)
-        self._call("work", int(n), _ptr(x), _ptr(out))
-        return out[:n * self._streams]
+class _byte_block(_stream_block):
+    """bytes in and bytes out, unless the block says otherwise"""
+    _in = _out = np.uint8
 
 
 class constellation_decoder_cb(_byte_block):
@@ -2243,7 +2212,7 @@ class constellation_decoder_cb(_byte_block):
 
     def __init__(self, constellation, device=0):
         _Block.__init__(self)
-        self._per_out = constellation.dimensionality()
+        self._per_in = constellation.dimensionality()
         self._create(constellation._h, int(device))
 
 
@@ -2276,6 +2245,7 @@ class constellation_receiver_cb(_control_loop):
     each sample's update.  form() says how decision and error are formed: 0 the reference's statements (MODE_GENERIC),
     1 cartesian (rect, calcdist), 2 on the sample's angle (bpsk, qpsk, dqpsk, 8psk, psk)."""
     _name = "constellation_receiver_cb"
+    _out = np.uint8
     FORM_GENERIC, FORM_CARTESIAN, FORM_ANGLE = 0, 1, 2
 
     def __init__(self, constellation, loop_bw, fmin, fmax, device=0):
@@ -2286,13 +2256,7 @@ class constellation_receiver_cb(_control_loop):
         return self._call("form")
 
     def work(self, input_items, n_in=None, floats=False):
-        x, n_in = self._items(input_items, n_in)
-        m = max(n_in * self._streams, 1)
-        sym = np.zeros(m, dtype=np.uint8)
-        f = [np.zeros(m, dtype=np.float32) for _ in range(3)] if floats else []
-        self._call("work", int(n_in), _ptr(x), _ptr(sym), *([_ptr(a) for a in f] if floats else [C.c_void_p(0)] * 3))
-        m = n_in * self._streams
-        return (sym[:m], f[0][:m], f[1][:m], f[2][:m]) if floats else sym[:m]
+        return self._stream_work(input_items, n_in, [np.float32] * 3, floats)
 
     def work_device(self, n, d_in, d_symbols, d_error=None, d_phase=None, d_freq=None, stream=None):
         return self._call("work_device", int(n), _devptr(d_in), _devptr(d_symbols), _devptr(d_error), _devptr(d_phase),
@@ -2306,6 +2270,7 @@ class constellation_demod_cb(_control_loop):
     bytes out per stream.  engine() 1 (the default) stores the bits from the receiver's walk, 0 runs the blocks in a
     row; the bytes are the same."""
     _name = "constellation_demod_cb"
+    _out = np.uint8
 
     def __init__(self, constellation, loop_bw, fmin, fmax, differential=True, gray_coded=True, device=0):
         _Block.__init__(self)
@@ -2324,12 +2289,7 @@ class constellation_demod_cb(_control_loop):
     def bits_per_symbol(self):
         return self._call("bits_per_symbol")
 
-    def work(self, input_items, n_in=None):
-        x, n_in = self._items(input_items, n_in)
-        m = n_in * self._streams * self.bits_per_symbol()
-        out = np.zeros(max(m, 1), dtype=np.uint8)
-        self._call("work", int(n_in), _ptr(x), _ptr(out))
-        return out[:m]
+    _per_out = property(bits_per_symbol)
 
 
 # ----------------------------------------------------------------------------
@@ -2344,6 +2304,7 @@ GR_LSB_FIRST = 1
 class _pack_block(_Block):
     """a gr_block that repacks bits: streams x ninput bytes back to back in, streams x noutput_items bytes out; the
     bit index it keeps between calls is one value for all streams"""
+    _in = _out = np.uint8
 
     def __init__(self, bits_per_chunk, endianness=GR_MSB_FIRST, device=0):
         _Block.__init__(self)
@@ -2357,14 +2318,10 @@ class _pack_block(_Block):
 
     def general_work(self, noutput_items, input_items, ninput_items=None):
         """returns (out, consumed); input_items holds streams x ninput_items bytes (all of it by default)"""
-        x = np.ascontiguousarray(input_items, dtype=np.uint8).reshape(-1)
-        if ninput_items is None:
-            ninput_items = len(x) // self._streams
-        if len(x) < ninput_items * self._streams:
-            raise ValueError("general_work needs %d items, got %d" % (ninput_items * self._streams, len(x)))
-        out = np.zeros(max(int(noutput_items) * self._streams, 1), dtype=np.uint8)
+        x, ninput_items = self._work_in(input_items, ninput_items)
+        (p_out,), (out,) = self._work_out(int(noutput_items))
         consumed = C.c_int(0)
-        n = self._call("general_work", int(noutput_items), int(ninput_items), _ptr(x), _ptr(out), C.byref(consumed))
+        n = self._call("general_work", int(noutput_items), ninput_items, _ptr(x), p_out, C.byref(consumed))
         return out[:n * self._streams].copy(), consumed.value
 
     def general_work_device(self, noutput_items, ninput_items, d_in, d_out, stream=None):
@@ -2398,32 +2355,21 @@ class diff_encoder_bb(_byte_block):
         self._create(int(modulus), int(device))
 
 
-class chunks_to_symbols_bc(_Block):
+class chunks_to_symbols_bc(_byte_block):
     """gr.chunks_to_symbols_bc(symbol_table, D=1): n bytes in, n * D complex items out per stream,
     symbol_table[in * D : in * D + D]; an index outside the table gives zeros"""
     _name = "chunks_to_symbols_bc"
+    _out = np.complex64
 
     def __init__(self, symbol_table, D=1, device=0):
         _Block.__init__(self)
         t, pt, n = _points(symbol_table)            # t owns the memory until the call returns
         self._create(pt, n, int(D), int(device))
 
-    def history(self):
-        return 1
-
     def D(self):
         return self._call("D")
 
-    def work(self, input_items, n=None):
-        x = np.ascontiguousarray(input_items, dtype=np.uint8).reshape(-1)
-        if n is None:
-            n = len(x) // self._streams
-        if len(x) < n * self._streams:
-            raise ValueError("work needs %d items, got %d" % (n * self._streams, len(x)))
-        m = n * self._streams * self.D()
-        out = np.zeros(max(m, 1), dtype=np.complex64)
-        self._call("work", int(n), _ptr(x), _ptr(out))
-        return out[:m]
+    _per_out = property(D)
 
 
 class generic_mod(_Block):
@@ -2434,6 +2380,7 @@ class generic_mod(_Block):
     the output depends on the concatenated input alone.  engine() 1 (the default) is the fused kernel, 0 runs the
     blocks in a row; MODE_GENERIC is the reference bit for bit in both."""
     _name = "generic_mod"
+    _in, _out = np.uint8, np.complex64
 
     def __init__(self, constellation, samples_per_symbol=2, differential=True, excess_bw=0.35, gray_coded=True, device=0):
         _Block.__init__(self)
@@ -2465,15 +2412,11 @@ class generic_mod(_Block):
         return self._call("max_produced", int(n_bytes))
 
     def work(self, input_items, n_bytes=None):
-        x = np.ascontiguousarray(input_items, dtype=np.uint8).reshape(-1)
-        if n_bytes is None:
-            n_bytes = len(x) // self._streams
-        if len(x) < n_bytes * self._streams:
-            raise ValueError("work needs %d items, got %d" % (n_bytes * self._streams, len(x)))
+        x, n_bytes = self._work_in(input_items, n_bytes)
         cap = self.max_produced(n_bytes)
-        out = np.zeros(max(cap * self._streams, 1), dtype=np.complex64)
+        (p_out,), (out,) = self._work_out(cap)
         produced = C.c_longlong(0)
-        self._call("work", int(n_bytes), _ptr(x), _ptr(out), cap, C.byref(produced))
+        self._call("work", n_bytes, _ptr(x), p_out, cap, C.byref(produced))
         return out[:produced.value * self._streams]
 
     def work_device(self, n_bytes, d_in, d_out, out_stride_items, out_capacity, stream=None):
@@ -2598,19 +2541,17 @@ def gmsk_mod_taps(samples_per_symbol, bt):
     return _designed(lib().grhip_gmsk_mod_taps, int(samples_per_symbol), float(bt))
 
 
-class frequency_modulator_fc(_Block):
+class frequency_modulator_fc(_stream_block):
     """gr.frequency_modulator_fc(sensitivity): phase += sensitivity * in in double, out = (cos, sin) of (float)phase;
     after the last item of a work call |phase| > 16 pi is brought back by whole turns, so the output depends on where
     the calls are cut, as the reference's does.  MODE_GENERIC walks serially and keeps the reference's phase bit for
     bit; every other mode is a scan within 1e-5 + 2^-50 sum|sensitivity * in| of the double evaluation."""
     _name = "frequency_modulator_fc"
+    _in, _out = np.float32, np.complex64
 
     def __init__(self, sensitivity, device=0):
         _Block.__init__(self)
         self._create(float(sensitivity), int(device))
-
-    def history(self):
-        return 1
 
     def set_sensitivity(self, sens):
         self._call("set_sensitivity", float(sens))
@@ -2619,54 +2560,28 @@ class frequency_modulator_fc(_Block):
         return self._fn("sensitivity")(self._h)                     # the float itself, not a status
 
     def phase(self, stream=0):
-        p = C.c_double(0.0)
-        self._call("phase", int(stream), C.byref(p))
-        return p.value
+        return self._stream_value("phase", C.c_double, stream)
 
     def set_phase(self, phase):
         self._call("set_phase", float(phase))
 
-    def work(self, input_items, n=None):
-        x = np.ascontiguousarray(input_items, dtype=np.float32).reshape(-1)
-        if n is None:
-            n = len(x) // self._streams
-        if len(x) < n * self._streams:
-            raise ValueError("work needs %d items, got %d" % (n * self._streams, len(x)))
-        out = np.zeros(max(n * self._streams, 1), dtype=np.complex64)
-        self._call("work", int(n), _ptr(x), _ptr(out))
-        return out[:n * self._streams]
 
-
-class _byte_to_float(_Block):
-    """streams x n bytes back to back in, _per floats out for each"""
-    _per = 1
+class _byte_to_float(_stream_block):
+    """streams x n bytes back to back in, per_byte() floats out for each"""
+    _view, _out = True, np.float32
 
     def __init__(self, device=0):
         _Block.__init__(self)
         self._create(int(device))
 
-    def history(self):
-        return 1
-
     def per_byte(self):
-        return self._per
-
-    def work(self, input_items, n=None):
-        x = np.ascontiguousarray(input_items).view(np.uint8).reshape(-1)
-        if n is None:
-            n = len(x) // self._streams
-        if len(x) < n * self._streams:
-            raise ValueError("work needs %d items, got %d" % (n * self._streams, len(x)))
-        m = n * self._streams * self.per_byte()
-        out = np.zeros(max(m, 1), dtype=np.float32)
-        self._call("work", int(n), _ptr(x), _ptr(out))
-        return out[:m]
+        return self._per_out
 
 
 class bytes_to_syms(_byte_to_float):
     """gr.bytes_to_syms(): eight floats -1 / +1 per byte, bit 7 first"""
     _name = "bytes_to_syms"
-    _per = 8
+    _per_out = 8
 
     def interpolation(self):
         return 8
@@ -2690,7 +2605,7 @@ class chunks_to_symbols_bf(_byte_to_float):
     def D(self):
         return self._call("D")
 
-    per_byte = D
+    per_byte, _per_out = D, property(D)
 
 
 class _cpm_hier(_Block):
@@ -2698,6 +2613,7 @@ class _cpm_hier(_Block):
     only: streams x n items back to back in, streams x n * items_out() complex items out.  A work call is a work call
     of every inner block (the modulator's wrap falls at its end).  engine() 1 is the fused kernel (the default outside
     MODE_GENERIC where the taps fit), 0 the blocks in a row."""
+    _view, _out = True, np.complex64
     _per_item = 1           # symbols per input item
 
     def engine(self):
@@ -2712,25 +2628,16 @@ class _cpm_hier(_Block):
     def items_out(self):
         return self._per_item * self.samples_per_symbol()
 
+    _per_out = property(items_out)
+
     def taps(self):
         return _designed(self._fn("filter_taps"), self._h)
 
     def phase(self, stream=0):
-        p = C.c_double(0.0)
-        self._call("phase", int(stream), C.byref(p))
-        return p.value
+        return self._stream_value("phase", C.c_double, stream)
 
     def work(self, input_items, n=None, want_freq=False):
-        x = np.ascontiguousarray(input_items).view(np.uint8).reshape(-1)
-        if n is None:
-            n = len(x) // self._streams
-        if len(x) < n * self._streams:
-            raise ValueError("work needs %d items, got %d" % (n * self._streams, len(x)))
-        m = n * self._streams * self.items_out()
-        out = np.zeros(max(m, 1), dtype=np.complex64)
-        freq = np.zeros(max(m, 1), dtype=np.float32) if want_freq else None
-        self._call("work", int(n), _ptr(x), _ptr(out), _ptr(freq) if want_freq else C.c_void_p(0))
-        return (out[:m], freq[:m]) if want_freq else out[:m]
+        return self._stream_work(input_items, n, [np.float32], want_freq)
 
     def work_device(self, n, d_in, d_out, d_freq=None, stream=None):
         """device buffers, queued on `stream`; d_freq (optional) takes the frequency samples"""
@@ -2878,29 +2785,7 @@ class fsm(object):
         return self._table("TMi")
 
 
-class _trellis_block(_Block):
-    """streams x n * _per_in items of _in back to back in, n * _per_out items of _out for each out"""
-    _in = np.uint8
-    _out = np.uint8
-    _per_in = 1
-    _per_out = 1
-
-    def history(self):
-        return 1
-
-    def work(self, input_items, n=None):
-        x = np.ascontiguousarray(input_items, dtype=self._in).reshape(-1)
-        if n is None:
-            n = len(x) // (self._streams * self._per_in)
-        if len(x) < n * self._streams * self._per_in:
-            raise ValueError("work needs %d items, got %d" % (n * self._streams * self._per_in, len(x)))
-        m = n * self._streams * self._per_out
-        out = np.zeros(max(m, 1), dtype=self._out)
-        self._call("work", int(n), _ptr(x), _ptr(out))
-        return out[:m]
-
-
-class trellis_encoder_bb(_trellis_block):
+class trellis_encoder_bb(_byte_block):
     """trellis.encoder_bb(FSM, ST): out[i] = OS[ST * I + in[i]], ST = NS[ST * I + in[i]]; one state per stream, kept
     across calls.  An input outside [0, I) is refused and leaves the states alone."""
     _name = "trellis_encoder_bb"
@@ -2910,9 +2795,7 @@ class trellis_encoder_bb(_trellis_block):
         self._create(FSM._h, int(ST), int(device))
 
     def ST(self, stream=0):
-        st = C.c_int(0)
-        self._call("ST", int(stream), C.byref(st))
-        return st.value
+        return self._stream_value("ST", C.c_int, stream)
 
     def set_ST(self, ST):
         self._call("set_ST", int(ST))
@@ -2946,7 +2829,7 @@ class trellis_encoder_ii(trellis_encoder_bb):
     _out = np.int32
 
 
-class trellis_metrics_f(_trellis_block):
+class trellis_metrics_f(_stream_block):
     """trellis.metrics_f(O, D, TABLE, TYPE): n steps of D items in, O floats per step out, the reference bit for bit.
     TYPE is TRELLIS_EUCLIDEAN or TRELLIS_HARD_SYMBOL; anything else is refused here, where the reference throws in work."""
     _name = "trellis_metrics_f"
@@ -2988,7 +2871,7 @@ class trellis_metrics_c(trellis_metrics_f):
     _in = np.complex64
 
 
-class trellis_constellation_metrics_cf(_trellis_block):
+class trellis_constellation_metrics_cf(_stream_block):
     """trellis.constellation_metrics_cf(constellation, TYPE): the constellation's calc_metric, dimensionality() complex
     items per step in, arity() floats out"""
     _name = "trellis_constellation_metrics_cf"
@@ -3010,7 +2893,7 @@ class trellis_constellation_metrics_cf(_trellis_block):
         return self._call("TYPE")
 
 
-class trellis_viterbi_b(_trellis_block):
+class trellis_viterbi_b(_byte_block):
     """trellis.viterbi_b(FSM, K, S0, SK): n * O floats in, n symbols out per stream, n a multiple of K; every block of
     K steps is viterbi_algorithm's output byte for byte in every mode"""
     _name = "trellis_viterbi_b"
@@ -3283,22 +3166,20 @@ def _taps_d(taps):
     return t, (_ptr(t) if len(t) else C.c_void_p(0)), len(t)
 
 
-class iir_filter_ffd(_Block):
+class iir_filter_ffd(_stream_block):
     """gr.iir_filter_ffd(fftaps, fbtaps): y[t] = sum ff[i] x[t-i] + sum_{i>=1} fb[i] y[t-i] in double (the feedback is
     added, fbtaps[0] is never read), float in and out.  work(x) takes streams x n_in items back to back and returns
     as many; the delay lines carry across calls.  MODE_GENERIC is the reference's recurrence bit for bit; every other
     mode runs calls of more than chunk() items in chunks where the taps allow it (chunked()).  set_taps is latched:
     it holds, with zeroed delay lines, from the next work call.  work_device does not synchronise."""
     _name = "iir_filter_ffd"
+    _in = _out = np.float32
 
     def __init__(self, fftaps, fbtaps, device=0):
         _Block.__init__(self)
         f, pf, n = _taps_d(fftaps)          # f and b own the memory until the call returns
         b, pb, m = _taps_d(fbtaps)
         self._create(pf, n, pb, m, int(device))
-
-    def history(self):
-        return 1
 
     def set_taps(self, fftaps, fbtaps):
         f, pf, n = _taps_d(fftaps)
@@ -3310,14 +3191,7 @@ class iir_filter_ffd(_Block):
         return bool(self._call("chunked"))
 
     def work(self, input_items, n_in=None):
-        x = np.ascontiguousarray(input_items, dtype=np.float32).reshape(-1)
-        if n_in is None:
-            n_in = len(x) // self._streams
-        if len(x) < n_in * self._streams:
-            raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
-        out = np.zeros(max(n_in * self._streams, 1), dtype=np.float32)
-        self._call("work", int(n_in), _ptr(x), _ptr(out))
-        return out[:n_in * self._streams]
+        return self._stream_work(input_items, n_in)
 
     @staticmethod
     def chunk():
@@ -3354,7 +3228,31 @@ def firdes_low_pass(gain, sampling_freq, cutoff_freq, transition_width, window=0
     return out[:n.value]
 
 
-class fm_demod_cf(_Block):
+class _demod_cf(_Block):
+    """what the fused FM and AM receivers share: streams x n_in NEW complex items in, streams x produced floats out"""
+    _in, _out = np.complex64, np.float32
+
+    def produced(self, n_in):
+        """outputs per stream of the next work call of n_in items"""
+        return self._call("produced", int(n_in))
+
+    def engine(self):
+        """1: the fused kernel runs the next call; 0: the three blocks in a row"""
+        return self._call("engine")
+
+    def work(self, input_items, n_in=None):
+        x, n_in = self._work_in(input_items, n_in)
+        got = C.c_int(0)
+        (p_out,), (out,) = self._work_out(self.produced(n_in))
+        self._call("work", n_in, _ptr(x) if len(x) else C.c_void_p(0), p_out, C.byref(got))
+        return out[:got.value * self._streams]
+
+    def work_device(self, n_in, d_in, d_out, d_produced=None, stream=None):
+        """work on device buffers, queued on `stream`; d_produced: a device int that receives the count, or None"""
+        return self._call("work_device", int(n_in), _devptr(d_in), _devptr(d_out), _devptr(d_produced), _stream(stream))
+
+
+class fm_demod_cf(_demod_cf):
     """blks2.fm_demod_cf (blks2impl/fm_demod.py:51-72) as one handle: quadrature_demod_cf(channel_rate / (2 pi deviation))
     -> fm_deemph(channel_rate, tau) (tau=None: none) -> fir_filter_fff(audio_decim, audio_taps).  The reference designs
     its audio taps with optfir.low_pass; this constructor takes them as given, and design(...) designs them as the
@@ -3386,33 +3284,10 @@ class fm_demod_cf(_Block):
         fm_demod_cf.__init__(blk, channel_rate, audio_decim, deviation, taps, tau, device)
         return blk
 
-    def produced(self, n_in):
-        """outputs per stream of the next work call of n_in items"""
-        return self._call("produced", int(n_in))
-
-    def engine(self):
-        """1: the fused kernel runs the next call; 0: the three blocks in a row"""
-        return self._call("engine")
-
     @staticmethod
     def tile():
         """input samples per workgroup of the fused kernel"""
         return lib().grhip_fm_demod_cf_tile()
-
-    def work(self, input_items, n_in=None):
-        x = np.ascontiguousarray(input_items, dtype=np.complex64).reshape(-1)
-        if n_in is None:
-            n_in = len(x) // self._streams
-        if len(x) < n_in * self._streams:
-            raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
-        got = C.c_int(0)
-        out = np.zeros(max(self.produced(n_in) * self._streams, 1), dtype=np.float32)
-        self._call("work", int(n_in), _ptr(x) if len(x) else C.c_void_p(0), _ptr(out), C.byref(got))
-        return out[:got.value * self._streams]
-
-    def work_device(self, n_in, d_in, d_out, d_produced=None, stream=None):
-        """work on device buffers, queued on `stream`; d_produced: a device int that receives the count, or None"""
-        return self._call("work_device", int(n_in), _devptr(d_in), _devptr(d_out), _devptr(d_produced), _stream(stream))
 
 
 class nbfm_rx(fm_demod_cf):
@@ -3515,7 +3390,7 @@ def optfir_spec(kind, gain, Fs, freqs, passband_ripple_db, stopband_atten_db, ne
 # ----------------------------------------------------------------------------
 # blks2.am_demod_cf / demod_10k0a3e_cf (blks2impl/am_demod.py)
 # ----------------------------------------------------------------------------
-class am_demod_cf(_Block):
+class am_demod_cf(_demod_cf):
     """blks2.am_demod_cf(channel_rate, audio_decim, audio_pass, audio_stop) (blks2impl/am_demod.py:42-58) as one handle:
     complex_to_mag -> add_const_ff(-1) -> fir_filter_fff(audio_decim, audio_taps), the taps those of
     optfir_low_pass(0.5, channel_rate, audio_pass, audio_stop, 0.1, 60) narrowed to float.  work(x) takes streams x n_in
@@ -3543,14 +3418,6 @@ class am_demod_cf(_Block):
         self._create(int(audio_decim), _ptr(t) if len(t) else C.c_void_p(0), len(t), int(device))
         self.audio_taps, self.audio_decim = t, int(audio_decim)
 
-    def produced(self, n_in):
-        """outputs per stream of the next work call of n_in items"""
-        return self._call("produced", int(n_in))
-
-    def engine(self):
-        """1: the fused kernel runs the next call; 0: the three blocks in a row"""
-        return self._call("engine")
-
     @staticmethod
     def tile():
         """input samples per workgroup of the fused kernel"""
@@ -3565,21 +3432,6 @@ class am_demod_cf(_Block):
     def max_taps():
         """the longest filter the fused kernel takes"""
         return lib().grhip_am_demod_cf_max_taps()
-
-    def work(self, input_items, n_in=None):
-        x = np.ascontiguousarray(input_items, dtype=np.complex64).reshape(-1)
-        if n_in is None:
-            n_in = len(x) // self._streams
-        if len(x) < n_in * self._streams:
-            raise ValueError("work needs %d items, got %d" % (n_in * self._streams, len(x)))
-        got = C.c_int(0)
-        out = np.zeros(max(self.produced(n_in) * self._streams, 1), dtype=np.float32)
-        self._call("work", int(n_in), _ptr(x) if len(x) else C.c_void_p(0), _ptr(out), C.byref(got))
-        return out[:got.value * self._streams]
-
-    def work_device(self, n_in, d_in, d_out, d_produced=None, stream=None):
-        """work on device buffers, queued on `stream`; d_produced: a device int that receives the count, or None"""
-        return self._call("work_device", int(n_in), _devptr(d_in), _devptr(d_out), _devptr(d_produced), _stream(stream))
 
 
 class demod_10k0a3e_cf(am_demod_cf):
